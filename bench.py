@@ -35,13 +35,17 @@ the pair and float64 decides it the HIP way) and `near_ties`, the rows that are 
 probabilities.  The leg has a time budget enforced inside each platform's loop (`--gt-seconds`; a platform cut short says `truncated`).
 `--scaling strong --shard-of R/W` (one GPU): exactly the block rank R of a W-rank job over `--candidates` would run; per_rank[0] reads as that
 rank's entry of the W-rank line (configs[3] and configs[4] on a one-GPU box).
+`--dump-outputs DIR`: right after the timed region, the four arrays rank 0's last timed step computed are written as DIR/<head>.npy
+(float32, at most 64 MB: a fixed, seeded sample of rows beyond that).  Weights and inputs are seeded, so two builds run with the
+same arguments can be compared output for output.
 
 Prints ONE JSON line on rank 0 with the contract fields plus
   roofline     -- the dominant kernel = the one with the most chip time (stand-alone duration x share of the 256 CUs its grid
                   occupies) in THIS run's own per-kernel table: SURVEY.md 8(d) algorithmic FLOP per launch / its mean
                   HIP-event duration IN the multi-stream configuration of the timed loop / the 2.5 PFLOP/s dense f16 MFMA
                   peak (ONE number: `frac` == `kernels[dominant].frac`; `frac_rocprof` / `kernel_ms_rocprof` are the same from the committed
-                  rocprofv3 trace of this configuration -- no marker packets in the queues -- when it was taken on these kernel sources).
+                  rocprofv3 trace of this configuration -- no marker packets in the queues -- when it was taken on these kernel sources
+                  with as many hardware queues as this run has).
                   `executed_frac` counts the three fp16 MFMAs the 2-way split issues per product; `alone_*` is the
                   same kernel with nothing else on the chip; `kernels` carries the same fractions for every kernel of the
                   pass; `traffic` comes from profiles/pmc_traffic.json and is null unless that table was measured on exactly
@@ -116,15 +120,22 @@ def load_pmc(batch, fused):
     return table, "%s (kernel sources %s)" % (entry.get("source"), here)
 
 
+TRACE_HW_QUEUES = 4    # the committed traces ran with the HIP runtime's default number of hardware queues per process
+
+
 def load_rocprof_ms(batch):
     """{kernel: mean ms in the timed leg} from the committed `rocprofv3 --kernel-trace --stats` summary of this configuration, when
-    profiles/pmc_traffic.json carries one stamped with the digest of the kernel sources this run executes; else None."""
+    profiles/pmc_traffic.json carries one stamped with the digest of the kernel sources this run executes and this run has the hardware
+    queues that trace had; else None.  With fewer queues than lanes, lanes share a queue and overlap less: every in-flight duration
+    differs from the trace's (2 queues: the dominant kernel 0.09-0.10 ms in flight against 0.13 ms traced with 4)."""
     from clair_amd import build
     try:
         entry = json.load(open(PMC_TABLE)).get("entries", {}).get(str(batch))
     except (OSError, ValueError):
         return None
     if not entry or entry.get("csrc_digest") != build.csrc_digest():
+        return None
+    if int(os.environ.get("GPU_MAX_HW_QUEUES") or TRACE_HW_QUEUES) != TRACE_HW_QUEUES:
         return None
     return entry.get("kernel_ms_rocprof")
 
@@ -165,7 +176,26 @@ def parse_args(argv=None):
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="skip the oracle spot check and the 1 024-candidate decode (timing-only builds whose results are garbage: tools/gpu/nozx_variants.sh)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what rank 0's last timed step computed -- the four arrays "
+                    "Clair.predict returns for that batch -- as DIR/<head>.npy (float32), for comparing two builds output for output")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000      # --dump-outputs: all four files together, .npy headers included
+
+
+def dump_outputs(path, packed):
+    """Write [n, 90] packed output rows as the four head arrays (gt21, genotype, len1, len2: what Clair.predict returns) to
+    path/<head>.npy.  Beyond DUMP_MAX_BYTES a fixed, seeded sample of rows is kept, in order: the same rows on every run."""
+    keep = (DUMP_MAX_BYTES - 4096) // packed[:1].nbytes
+    if packed.shape[0] > keep:
+        packed = packed[np.sort(np.random.default_rng(20250928).choice(packed.shape[0], keep, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    for name, a in zip(weights.HEAD_NAMES, _capi.split_outputs(packed)):
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def spawn_and_relay(args):
@@ -476,6 +506,8 @@ def run_ranked(args, group, json_fd):
     eng.timing_enable(False)
     mine_s = timed("value", lambda: run(steps, ragged_last=True), eng.sync)
     phases.append(["timed (value), %d lanes in flight" % streams, steps])
+    if args.dump_outputs and rank == 0 and steps:      # before any later leg writes `od` again
+        dump_outputs(args.dump_outputs, eng.dataset_download(od, ((steps - 1) % nuniq) * batch, last_n))
     elapsed = group.max_float(mine_s)          # the slowest rank defines the job time
     per_rank_s = group.gather_floats(mine_s)
     per_rank_steps = [int(round(v)) for v in group.gather_floats(steps)]
@@ -626,7 +658,7 @@ def run_ranked(args, group, json_fd):
                           "table (`kernels`); frac = SURVEY.md 8(d) algorithmic FLOP of that kernel per launch (%d per candidate x batch) / its mean "
                           "HIP-event duration with %d batches in flight (the timed loop repeated with HIP events on every kernel: the same number as "
                           "kernels[dominant].in_flight_ms and .frac) / dense f16 MFMA peak; the rocprofv3 mean of the same kernel in the same loop is "
-                          "`kernel_ms_rocprof` when profiles/pmc_traffic.json was stamped on these kernel sources" % (kflop[dom], streams),
+                          "`kernel_ms_rocprof` when profiles/pmc_traffic.json was stamped on these kernel sources and this run has the trace's %d hardware queues" % (kflop[dom], streams, TRACE_HW_QUEUES),
             "kernel_ms": round(dom_ms_mean, 5), "launches": times[dom][1], "algorithmic_flop_per_launch": flop,
             "kernel_ms_with_events_on_it_only": round(dom_ms_only, 5),
             "kernel_ms_rocprof": rocprof_ms.get(dom) if rocprof_ms else None,

@@ -590,6 +590,32 @@ def test_bench_strong_scaling_counts_one_ranks_share_of_the_whole_genome_set():
     assert abs(d["value"] - 625000 / (d["ms_per_step"] * 611e-3)) < 0.01 * d["value"] and d["value"] > 1e6
 
 
+def test_bench_dump_outputs_is_the_last_timed_step_and_the_same_on_every_run(tmp_path):
+    """`bench.py --dump-outputs DIR`: the four arrays of the last of --steps timed steps (inputs: batch (steps - 1) % unique batches of the
+    seeded synthetic set), bit-identical over two runs with the same arguments and within PROB_TOL of the oracle on those inputs."""
+    import os
+    import subprocess
+    import sys
+    from clair_amd import weights
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, BENCH_WARM_STEPS="16")
+    steps, warmup, batch = 5, 2, 1024
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, "bench.py", "--steps", str(steps), "--warmup", str(warmup), "--no-cpu-baseline", "--gt-candidates", "0",
+                            "--sustained-seconds", "0", "--full-candidates", "0", "--boundary-slots", "0", "--dump-outputs", str(tmp_path / d)],
+                           cwd=root, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+    heads = weights.HEAD_NAMES
+    got = [np.load(tmp_path / "a" / (k + ".npy")) for k in heads]
+    assert all(np.array_equal(g, np.load(tmp_path / "b" / (k + ".npy"))) for g, k in zip(got, heads))
+    nuniq = min(8, steps + warmup)
+    x, _ = synth.synthetic_input(nuniq * batch, "ont", seed=20250928)
+    last = (steps - 1) % nuniq
+    want = _oracle(weights.synthetic_weights(seed=20250928, head_gain=4.0), x[last * batch:(last + 1) * batch])
+    assert all(g.dtype == np.float32 and g.shape == t.shape for g, t in zip(got, want))
+    assert max(float(np.abs(g - t).max()) for g, t in zip(got, want)) < PROB_TOL
+
+
 def test_whole_genome_share_of_one_gpu_config3(synth_weights):
     """BASELINE.json configs[3]: ~5 M ONT candidates over 8 GPUs = 625 k per GPU.  One rank's share through the resident path
     (clair_run_resident, batch 1024, three batches in flight), checked by properties at full size -- every row a distribution,
