@@ -27,6 +27,7 @@ SYMBOLS = (
     "clair_frontend_find_candidates", "clair_frontend_set_candidates", "clair_frontend_get_candidates", "clair_frontend_build_windows",
     "clair_frontend_build_windows_ex", "clair_frontend_window_info", "clair_frontend_window_counts", "clair_frontend_counts_device", "clair_frontend_budget_inputs",
     "clair_frontend_stats", "clair_frontend_text_options", "clair_frontend_add_text", "clair_frontend_text_stats", "clair_frontend_slab_reads",
+    "clair_frontend_bam_options", "clair_frontend_add_bam",
 )
 KERNEL_NAMES = ("proj1", "lstm1", "proj2", "lstm2", "l3", "l4", "tail", "decode")
 
@@ -132,6 +133,9 @@ def load(path=None):
         lib.clair_frontend_add_text.argtypes = [c_vp, c_vp, c_i64]
         lib.clair_frontend_text_stats.argtypes = [c_vp, c_vp]
         lib.clair_frontend_slab_reads.argtypes = [c_vp, c_i64, c_vp, c_i64, ctypes.POINTER(c_i64)]
+        if hasattr(lib, "clair_frontend_add_bam") or not older_ok:
+            lib.clair_frontend_bam_options.argtypes = [c_vp, c_int, c_int, c_int, c_int, c_i64, c_i64, c_i64, c_i64]
+            lib.clair_frontend_add_bam.argtypes = [c_vp, c_vp, c_i64, c_vp, c_i64]
     for name in SYMBOLS:
         if older_ok and not hasattr(lib, name):
             continue
@@ -361,6 +365,14 @@ class MalformedText(EngineError):
     pass
 
 
+class MalformedRecord(EngineError):
+    """clair_frontend_add_bam: a BAM record whose sizes do not fit its block_size; .index = its index in the chunk."""
+
+    def __init__(self, msg, index):
+        EngineError.__init__(self, msg)
+        self.index = index
+
+
 class DeviceWindows(object):
     """n pileup windows [33][8][4] int16 in device memory (clair_frontend_counts_device): what Engine.submit_calls takes in place of a
     host array.  Keeps its Frontend alive; host() copies the counts back (the decode needs them only when a BAM is consulted)."""
@@ -445,6 +457,9 @@ class Frontend(object):
         if rc == 2:
             raise MalformedText(self._lib.clair_frontend_last_error(self._h).decode())
         self._check(rc, "clair_frontend_add_text")
+        self._keep_slab_reads(before)
+
+    def _keep_slab_reads(self, before):
         if self.stats()["slabs"] > before:
             from clair_amd._hostapi import READ_DTYPE
             n = ctypes.c_int64(0)
@@ -452,6 +467,29 @@ class Frontend(object):
             reads = np.empty(n.value, dtype=READ_DTYPE)
             self._check(self._lib.clair_frontend_slab_reads(self._h, before, _ptr(reads), n.value, ctypes.byref(n)), "clair_frontend_slab_reads")
             self.slab_reads.append(reads)
+
+    def bam_options(self, tid, dcov=250, evc_min_mq=0, pile_min_mq=0, pile_region=None, region=None):
+        """The binary twin of text_options: records of reference id `tid`; region = (lo, hi) of `samtools view <bam> ctg:lo-hi` (None: the
+        whole contig), pile_region as text_options'.  From here on add_bam() feeds the front end."""
+        a, b = (-1, -1) if pile_region is None else (int(pile_region[0]), int(pile_region[1]))
+        lo, hi = (-1, -1) if region is None else (int(region[0]), int(region[1]))
+        self._check(self._lib.clair_frontend_bam_options(self._h, int(tid), int(dcov), int(evc_min_mq), int(pile_min_mq), a, b, lo, hi),
+                    "clair_frontend_bam_options")
+
+    def add_bam(self, records, length, offsets, n_records):
+        """Whole BAM records (clair_amd._hostapi.BamReader.readinto): records = address (int) or a uint8 array, offsets an int64 array of
+        their starts.  Raises MalformedRecord (with .index) when a record's sizes do not fit its block_size."""
+        address = int(records) if isinstance(records, int) else records.ctypes.data
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        before = self.stats()["slabs"]
+        rc = self._lib.clair_frontend_add_bam(self._h, address, int(length), _ptr(offsets), int(n_records))
+        if rc == 2:
+            import re
+            msg = self._lib.clair_frontend_last_error(self._h).decode()
+            m = re.search(r"record (\d+)", msg)
+            raise MalformedRecord(msg, int(m.group(1)) if m else 0)
+        self._check(rc, "clair_frontend_add_bam")
+        self._keep_slab_reads(before)
 
     def text_stats(self):
         v = (ctypes.c_int64 * 4)()

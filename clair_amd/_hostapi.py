@@ -15,7 +15,9 @@ SYMBOLS = ("clair_host_abi_version", "clair_host_last_error", "clair_host_thread
            "clair_host_evc_create", "clair_host_evc_destroy", "clair_host_evc_feed", "clair_host_evc_finish",
            "clair_host_evc_pending", "clair_host_evc_reads", "clair_host_evc_take", "clair_host_evc_take_text",
            "clair_host_sampack_create", "clair_host_sampack_destroy", "clair_host_sampack_feed", "clair_host_sampack_stats",
-           "clair_host_sampack_slab", "clair_host_sampack_reset", "clair_host_tuple_budget_binds")
+           "clair_host_sampack_slab", "clair_host_sampack_reset", "clair_host_tuple_budget_binds",
+           "clair_host_bam_open", "clair_host_bam_close", "clair_host_bam_info", "clair_host_bam_ref", "clair_host_bam_tid", "clair_host_bam_query",
+           "clair_host_bam_next", "clair_host_bam_voffset", "clair_host_bam_render", "clair_host_faidx")
 N_VALUES = 1056
 _lib = None
 
@@ -74,6 +76,17 @@ def load():
         lib.clair_host_sampack_stats.argtypes = [vp, vp]
         lib.clair_host_sampack_slab.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]
         lib.clair_host_sampack_reset.argtypes = [vp]
+        lib.clair_host_bam_open.argtypes = [ctypes.c_char_p, i32, ctypes.POINTER(vp)]
+        lib.clair_host_bam_close.argtypes = [vp]
+        lib.clair_host_bam_close.restype = None
+        lib.clair_host_bam_info.argtypes = [vp, vp]
+        lib.clair_host_bam_ref.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(i64)]
+        lib.clair_host_bam_tid.argtypes = [vp, ctypes.c_char_p]
+        lib.clair_host_bam_query.argtypes = [vp, ctypes.c_char_p, i32, i64, i64]
+        lib.clair_host_bam_next.argtypes = [vp, vp, i64, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)]
+        lib.clair_host_bam_voffset.argtypes = [vp, i64, ctypes.POINTER(ctypes.c_uint64)]
+        lib.clair_host_bam_render.argtypes = [vp, vp, vp, i64, i32, i64, i64, ctypes.POINTER(vp), ctypes.POINTER(i64)]
+        lib.clair_host_faidx.argtypes = [ctypes.c_char_p, ctypes.c_char_p, i64, i64, vp, i64, ctypes.POINTER(i64)]
         lib.clair_host_tuple_budget_binds.argtypes = [vp, vp, i64, vp, vp, i64, vp, ctypes.POINTER(i32)]
         if lib.clair_host_abi_version() != 6:
             raise RuntimeError("libclair_host.so has ABI version %d, expected 6: run `python -m clair_amd.build`"
@@ -558,3 +571,159 @@ def tuple_budget_binds(reads, tuples, centres, window_tuples, state):
                                             len(centres), state.ctypes.data, ctypes.byref(binds)) != 0:
         raise ValueError(load().clair_host_last_error().decode())
     return bool(binds.value)
+
+
+class BamError(ValueError):
+    """The BAM, its index or the request cannot be read natively (callVarBam turns it into a message and a non-zero exit)."""
+
+
+def bam_index_for(bam_fn):
+    """-> (kind, path) of the index samtools would open for bam_fn: ("bai", <bam>.bai or <stem>.bai), ("csi", <bam>.csi), or (None, None)."""
+    stem = bam_fn[:-4] if bam_fn.endswith(".bam") else None
+    for path in [bam_fn + ".bai"] + ([stem + ".bai"] if stem else []):
+        if os.path.isfile(path):
+            return "bai", path
+    if os.path.isfile(bam_fn + ".csi") or (stem and os.path.isfile(stem + ".csi")):
+        return "csi", bam_fn + ".csi"
+    return None, None
+
+
+class BamReader(object):
+    """clair_host_bam_*: the records of one contig / region of a BAM, read without samtools (callVarBam --bam_reader native).
+
+        r = BamReader(path, threads=4)
+        r.query("chr1", 1000, 2000)                      # 1-based inclusive; None, None = the whole contig
+        n_bytes, n_records = r.readinto(buf, offsets)    # whole records, offsets[k] = where record k starts; 0, 0 at the end
+        text = r.render(buf, offsets, n_records)         # what `samtools view -F 2316 <bam> <region>` prints for them (11 columns)
+
+    The records readinto() hands out are all those the index yields for the region; the view filter is the consumer's (the device's
+    clair_frontend_add_bam or render())."""
+
+    def __init__(self, path, threads=4):
+        self._lib = load()
+        if not 1 <= int(threads) <= 16:
+            raise BamError("--bam_threads %d: 1 .. 16" % threads)
+        h = ctypes.c_void_p()
+        if self._lib.clair_host_bam_open(path.encode(), int(threads), ctypes.byref(h)) != 0:
+            raise BamError(self._lib.clair_host_last_error().decode())
+        self._h, self.path = h, path
+        self.tid, self.region, self.used_index = -1, (-1, -1), False
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.clair_host_bam_close(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def info(self):
+        v = (ctypes.c_int64 * 4)()
+        self._lib.clair_host_bam_info(self._h, v)
+        return dict(zip(("n_ref", "eof_block", "records", "used_index"), [int(x) for x in v]))
+
+    def references(self):
+        out = []
+        for tid in range(self.info()["n_ref"]):
+            name, length = ctypes.c_char_p(), ctypes.c_int64(0)
+            self._lib.clair_host_bam_ref(self._h, tid, ctypes.byref(name), ctypes.byref(length))
+            out.append((name.value.decode(), int(length.value)))
+        return out
+
+    def query(self, ctg_name, beg1=None, end1=None, use_index=True):
+        """Select ctg_name:beg1-end1 (or the whole contig).  With use_index, the .bai next to the BAM when there is one (a .csi alone is a
+        BamError: samtools reads those); without one the records are scanned from the first.  -> True when an index is used."""
+        tid = self._lib.clair_host_bam_tid(self._h, ctg_name.encode())
+        if tid < 0:
+            raise BamError("contig %s is not in the header of %s" % (ctg_name, self.path))
+        index = None
+        if use_index:
+            kind, index = bam_index_for(self.path)
+            if kind == "csi":
+                raise BamError("%s has only a .csi index, which the native reader does not read: use --bam_reader samtools" % self.path)
+        self.tid = tid
+        self.region = (-1, -1) if beg1 is None or end1 is None else (int(beg1), int(end1))
+        if self._lib.clair_host_bam_query(self._h, None if index is None else index.encode(), tid, self.region[0], self.region[1]) != 0:
+            raise BamError(self._lib.clair_host_last_error().decode())
+        self.used_index = index is not None
+        return self.used_index
+
+    def readinto(self, buf, offsets, cap=None):
+        """Whole records into buf (a writable uint8 array: NumPy, or a page-locked buffer), their starts into offsets (int64 array) ->
+        (bytes, records); (0, 0) when the query is exhausted."""
+        cap = len(buf) if cap is None else int(cap)
+        n_bytes, n_rec = ctypes.c_int64(0), ctypes.c_int64(0)
+        if self._lib.clair_host_bam_next(self._h, buf.ctypes.data, cap, offsets.ctypes.data, len(offsets), ctypes.byref(n_bytes), ctypes.byref(n_rec)) != 0:
+            raise BamError(self._lib.clair_host_last_error().decode())
+        return int(n_bytes.value), int(n_rec.value)
+
+    def voffset(self, k):
+        """BGZF virtual offset of record k of the last chunk readinto() handed out."""
+        v = ctypes.c_uint64(0)
+        if self._lib.clair_host_bam_voffset(self._h, int(k), ctypes.byref(v)) != 0:
+            raise BamError(self._lib.clair_host_last_error().decode())
+        return int(v.value)
+
+    def render(self, buf, offsets, n_records):
+        """The lines `samtools view -F 2316` prints for those of the n_records records that are on the queried contig and overlap the region."""
+        text, n = ctypes.c_void_p(), ctypes.c_int64(0)
+        if self._lib.clair_host_bam_render(self._h, buf.ctypes.data, offsets.ctypes.data, int(n_records), self.tid, self.region[0], self.region[1],
+                                           ctypes.byref(text), ctypes.byref(n)) != 0:
+            raise BamError(self._lib.clair_host_last_error().decode())
+        return ctypes.string_at(text.value, n.value) if n.value else b""
+
+
+BAM_CHUNK = 64 << 20       # bytes of whole records per BamReader.readinto (the page-locked buffer the device front end reads them from)
+
+
+def bam_offsets_for(cap):
+    """An offsets array for a chunk of cap bytes: a record is at least 36 bytes."""
+    return np.empty(max(1, cap // 36 + 1), dtype=np.int64)
+
+
+class BamText(object):
+    """The text `samtools view -F 2316 <bam> <region>` prints, rendered from a BamReader query: read() / readinto() / abort() / finish() like the
+    pipe it replaces (callVarBam's host stages and the device front end's host packer)."""
+
+    def __init__(self, reader, chunk=8 << 20):
+        self.reader, self.buf, self.offsets = reader, np.empty(chunk, dtype=np.uint8), bam_offsets_for(chunk)
+        self.text, self.at, self.eof = b"", 0, False
+
+    def _more(self):
+        while not self.eof and self.at >= len(self.text):
+            n_bytes, n_rec = self.reader.readinto(self.buf, self.offsets)
+            if n_rec == 0:
+                self.eof = True
+                break
+            self.text, self.at = self.reader.render(self.buf, self.offsets, n_rec), 0
+
+    def read(self, n):
+        self._more()
+        out = self.text[self.at:self.at + n]
+        self.at += len(out)
+        return out
+
+    def readinto(self, mv):
+        piece = self.read(len(mv))
+        mv[:len(piece)] = piece
+        return len(piece)
+
+    def abort(self):
+        self.reader.close()
+
+    def finish(self):
+        self.reader.close()
+        return 0
+
+
+def faidx(ref_fn, ctg_name, beg1=None, end1=None):
+    """`samtools faidx ref_fn ctg:beg1-end1` (clamped; None = whole contig) without samtools: the bases as str, case kept, or None when the contig
+    is not in the .fai (samtools fails there too)."""
+    lib = load()
+    a, b = (-1, -1) if beg1 is None or end1 is None else (int(beg1), int(end1))
+    n = ctypes.c_int64(0)
+    if lib.clair_host_faidx(ref_fn.encode(), ctg_name.encode(), a, b, None, 0, ctypes.byref(n)) != 0:
+        return None
+    out = ctypes.create_string_buffer(max(1, n.value))
+    if lib.clair_host_faidx(ref_fn.encode(), ctg_name.encode(), a, b, out, n.value, ctypes.byref(n)) != 0:
+        return None
+    return out.raw[:n.value].decode("latin-1")

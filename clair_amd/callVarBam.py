@@ -23,6 +23,11 @@ are read twice (`samtools view` once per stage): the pileup needs the candidates
 Same candidates, same windows, same VCF (tests/test_frontend_gpu.py, tests/test_e2e_gpu.py); where the input leaves the regime
 that formulation reproduces exactly (CLAIR_FE_* in include/clair_reads.h, a tuple budget that binds) the run falls back to the
 host stages above and says so.
+
+--bam_reader native reads the BAM without samtools (include/clair_host.h: clair_host_bam_*; docs/bam_reader.md): BGZF inflated on
+--bam_threads host threads, the region's records found with the .bai, and with the device front end the binary records go to the GPU
+as they are (clair_frontend_add_bam), which decodes them and applies the view's filter itself.  The host stages, and the device front
+end's fall-back, read the text `samtools view` would have printed, rendered from the records; the reference slice comes from the .fai.
 """
 import logging
 import os
@@ -49,6 +54,68 @@ def view_command(args, region):
                                                   ct.SAMTOOLS_VIEW_FILTER_FLAG, args.bam_fn, region))
 
 
+def split_region(region):
+    """samtools' region syntax -> (ctg, start, end) 1-based inclusive, or (ctg, None, None) for a whole contig."""
+    import re
+    m = re.fullmatch(r"(.+):(\d+)-(\d+)", region)
+    return (m.group(1), int(m.group(2)), int(m.group(3))) if m else (region, None, None)
+
+
+def native_reader(args, region):
+    """--bam_reader native: a clair_amd._hostapi.BamReader positioned on `region` (samtools' syntax).  What it cannot read ends the run."""
+    from . import _hostapi
+    ctg, lo, hi = split_region(region)
+    try:
+        reader = _hostapi.BamReader(args.bam_fn, threads=getattr(args, "bam_threads", 4))
+        if not reader.info()["eof_block"]:
+            logging.warning("[W::bgzf] %s: no BGZF EOF marker; the file may be truncated" % args.bam_fn)
+        if not reader.query(ctg, lo, hi):
+            logging.info("%s has no .bai index: reading it from the first record" % args.bam_fn)
+    except _hostapi.BamError as exc:
+        sys.exit("[ERROR] %s" % exc)
+    return reader
+
+
+class _NativeText(object):
+    """What `samtools view -F 2316 <bam> <region>` prints, rendered from the BAM's records without samtools: read() / readinto() / abort() /
+    finish() like _OnePipe."""
+
+    def __init__(self, args, region):
+        from . import _hostapi
+        self.text = _hostapi.BamText(native_reader(args, region))
+
+    def read(self, n):
+        from . import _hostapi
+        try:
+            return self.text.read(n)
+        except _hostapi.BamError as exc:
+            sys.exit("[ERROR] %s" % exc)
+
+    def readinto(self, mv):
+        from . import _hostapi
+        try:
+            return self.text.readinto(mv)
+        except _hostapi.BamError as exc:
+            sys.exit("[ERROR] %s" % exc)
+
+    def abort(self):
+        self.text.abort()
+
+    def finish(self):
+        return self.text.finish()
+
+
+def alignment_text(args, region):
+    """The alignments of `region` as `samtools view -F 2316` text: from samtools (the default) or rendered natively (--bam_reader native)."""
+    if getattr(args, "bam_reader", "samtools") == "native":
+        return _NativeText(args, region)
+    return _OnePipe(args, region)
+
+
+def native_input(args):
+    return getattr(args, "bam_reader", "samtools") == "native"
+
+
 def candidate_positions(args, quiet=False):
     """Stage 1.  -> int64 positions (1-based, ascending for sorted alignments)."""
     from . import _hostapi
@@ -58,7 +125,7 @@ def candidate_positions(args, quiet=False):
         sys.exit("Fasta index %s.fai doesn't exist." % args.ref_fn)
     have_range = args.ctgStart is not None and args.ctgEnd is not None
     region, ref_start = evc.reference_region(args.ctgName, args.ctgStart if have_range else None, args.ctgEnd if have_range else None)
-    seq = evc.load_reference(args.samtools, args.ref_fn, region)
+    seq = evc.load_reference(args.samtools, args.ref_fn, region, native=native_input(args))
     if not seq:
         sys.exit("[ERROR] Failed to load reference seqeunce from file (%s)." % args.ref_fn)
     tree = evc.bed_regions_from(args.bed_fn)
@@ -68,11 +135,10 @@ def candidate_positions(args, quiet=False):
                                       ctg_start=args.ctgStart if have_range else None, ctg_end=args.ctgEnd if have_range else None,
                                       bed=None if tree is None else tree[args.ctgName],
                                       min_coverage=int(args.minCoverage), threshold=args.threshold, min_mq=0)   # callVarBam.py:75: int() before it reaches the extractor
-    view = ct.subprocess_popen(view_command(args, region),
-                               text=False)
+    view = alignment_text(args, region)
     chunks, tail = [], None
     while True:
-        chunk = view.stdout.read(1 << 22)
+        chunk = view.read(1 << 22)
         if not chunk:
             break
         tail = finder.feed(chunk if tail is None else tail + chunk)
@@ -82,9 +148,7 @@ def candidate_positions(args, quiet=False):
         finder.feed(tail, final=True)
     finder.finish()
     chunks.append(finder.take_positions())
-    view.stdout.close()
-    view.wait()
-    if view.returncode != 0:
+    if view.finish() != 0:
         sys.exit("[ERROR] `samtools view` failed on %s" % args.bam_fn)
     if finder.reads == 0 and not quiet:
         print("No read has been process, either the genome region you specified has no read cover, or please check the correctness of your BAM input (%s)."
@@ -128,7 +192,7 @@ def tensor_batches(args, positions, batch_size, read_flank=(0, 0), progress=True
     yields for the text records of the same windows.  read_flank = (left, right) widens the region the ALIGNMENTS are taken from
     (not the candidates): a sub-range of a larger run needs the reads that touch only the flanks of its outermost windows."""
     from . import _hostapi
-    seq, ref_start = ct.reference_sequence_from(args.samtools, args.ref_fn, args.ctgName, args.ctgStart, args.ctgEnd)
+    seq, ref_start = ct.reference_sequence_from(args.samtools, args.ref_fn, args.ctgName, args.ctgStart, args.ctgEnd, native=native_input(args))
     if not seq:
         sys.exit("Failed to load reference seqeunce. Please check if the provided reference fasta %s and the ctgName %s are correct."
                  % (args.ref_fn, args.ctgName))
@@ -138,8 +202,7 @@ def tensor_batches(args, positions, batch_size, read_flank=(0, 0), progress=True
     builder = _hostapi.PileupBuilder(args.ctgName, seq, 0 if ref_start is None else ref_start - 1, positions,
                                      consider_left_edge=not args.stop_consider_left_edge, dcov=args.dcov, set_order=ct.set_order_of(getattr(args, "pypy", None)))
     region = "%s:%d-%d" % (args.ctgName, max(1, args.ctgStart - read_flank[0]), args.ctgEnd + read_flank[1]) if have_range else args.ctgName
-    view = ct.subprocess_popen(view_command(args, region),
-                               text=False)
+    view = alignment_text(args, region)
     from .tensor_binary import MAX_CTG, InfoTable, _IUPAC_TABLE
     total = 0
     ctg_bytes = args.ctgName.encode()
@@ -187,7 +250,7 @@ def tensor_batches(args, positions, batch_size, read_flank=(0, 0), progress=True
 
     tail = None
     while True:
-        chunk = view.stdout.read(1 << 22)
+        chunk = view.read(1 << 22)
         if not chunk:
             break
         tail = builder.feed(chunk if tail is None else tail + chunk)
@@ -198,9 +261,7 @@ def tensor_batches(args, positions, batch_size, read_flank=(0, 0), progress=True
     builder.finish()
     for batch in drain(True):
         yield batch
-    view.stdout.close()
-    view.wait()
-    if view.returncode != 0:
+    if view.finish() != 0:
         sys.exit("[ERROR] `samtools view` failed on %s" % args.bam_fn)
 
 
@@ -343,6 +404,54 @@ class _OnePipe(object):
         return self.proc.returncode
 
 
+class _NativeBam(object):
+    """--bam_reader native with the device front end: whole BAM records of `region` read into the page-locked buffer and decoded on the
+    GPU (clair_frontend_add_bam), which applies the view's filter itself."""
+
+    def __init__(self, args, region):
+        self.args = args
+        self.reader = native_reader(args, region)
+        self.region = split_region(region)[1:]
+
+    def feed(self, f, pack_kw, pinned):
+        """pinned: nbytes -> page-locked uint8 array (DeviceFrontEnd's).  -> seconds spent in the device calls"""
+        from time import time
+        from . import _capi, _hostapi
+        f.bam_options(self.reader.tid, region=None if self.region[0] is None else self.region, **pack_kw)
+        buf = pinned(BAM_CHUNK + 16)
+        offsets = _hostapi.bam_offsets_for(BAM_CHUNK)
+        t_dev = 0.0
+        while True:
+            try:
+                n_bytes, n_rec = self.reader.readinto(buf, offsets, cap=BAM_CHUNK)
+            except _hostapi.BamError as exc:
+                sys.exit("[ERROR] %s" % exc)
+            if not n_rec:
+                return t_dev
+            t0 = time()
+            try:
+                f.add_bam(buf.ctypes.data, n_bytes, offsets, n_rec)
+            except _capi.MalformedRecord as exc:
+                why = str(exc)
+                try:
+                    self.reader.render(buf, offsets[exc.index:exc.index + 1], 1)
+                except _hostapi.BamError as host:
+                    why = str(host)
+                sys.exit("[ERROR] %s: the record at BGZF virtual offset %d (compressed offset %d) is malformed: %s"
+                         % (self.args.bam_fn, self.reader.voffset(exc.index), self.reader.voffset(exc.index) >> 16, why))
+            t_dev += time() - t0
+
+    def abort(self):
+        self.reader.close()
+
+    def finish(self):
+        self.reader.close()
+        return 0
+
+
+BAM_CHUNK = 64 << 20       # bytes of whole BAM records handed to the device at a time (--bam_reader native; the page-locked buffer they are read into)
+
+
 class DeviceFrontEnd(object):
     """Both pileup stages on the GPU for one contig / region.  run() -> number of windows, or None when the run has to take the host
     path (reason logged); batches() then yields what tensor_batches yields, with the counts as clair_amd._capi.DeviceWindows."""
@@ -395,7 +504,7 @@ class DeviceFrontEnd(object):
         elif not os.path.isfile("%s.fai" % args.ref_fn):
             sys.exit("Fasta index %s.fai doesn't exist." % args.ref_fn)
         # one reference slice serves both stages: they load the same region (ExtractVariantCandidates.py:228-236, CreateTensor.py:113-156)
-        seq, ref_start = ct.reference_sequence_from(args.samtools, args.ref_fn, args.ctgName, args.ctgStart, args.ctgEnd)
+        seq, ref_start = ct.reference_sequence_from(args.samtools, args.ref_fn, args.ctgName, args.ctgStart, args.ctgEnd, native=native_input(args))
         if not seq:
             sys.exit("Failed to load reference seqeunce. Please check if the provided reference fasta %s and the ctgName %s are correct."
                      % (args.ref_fn, args.ctgName))
@@ -419,14 +528,21 @@ class DeviceFrontEnd(object):
         pack_kw = dict(dcov=args.dcov, evc_min_mq=0, pile_min_mq=0, pile_region=(args.ctgStart, args.ctgEnd) if have_range else None)
         readers = max(1, int(getattr(args, "view_readers", 1) or 1))
         span = (max(1, args.ctgStart - 2), args.ctgEnd + 2) if have_range else (1, contig_length(args.ref_fn, args.ctgName) or 0)
-        if readers > 1 and span[1] - span[0] + 1 >= 2 * readers:
+        on_device = self.pinned is not None and os.environ.get("CLAIR_AMD_FE_PACK", "device") != "host"
+        if native_input(args):
+            # no samtools: the records themselves go to the GPU (or, for the host packer, the text they render to)
+            view = _NativeBam(args, region) if on_device else _NativeText(args, region)
+        elif readers > 1 and span[1] - span[0] + 1 >= 2 * readers:
             view = AlignmentStream(args, args.ctgName, span[0], span[1], readers)
         else:
             view = _OnePipe(args, region)
         from time import time
         t_start, t_pack, t_dev = time(), 0.0, 0.0
         try:
-            if self.pinned is not None and os.environ.get("CLAIR_AMD_FE_PACK", "device") != "host":
+            if on_device and isinstance(view, _NativeBam):
+                t_dev = view.feed(f, pack_kw, self.pinned)
+                pst = f.text_stats()
+            elif on_device:
                 # the text goes to the GPU as it comes out of the pipe (read into a page-locked buffer, whole lines at a time) and is
                 # parsed there: the host touches no byte of it but the last megabyte of each chunk, looking for the line end
                 f.text_options(args.ctgName, **pack_kw)
@@ -511,8 +627,10 @@ class DeviceFrontEnd(object):
             return self._fallback("; ".join(why for bit, why in FE_REASONS if bits & bit))
         t_dev += time() - t0
         logging.info("%d candidate sites" % n_cand)
-        logging.info("device front end: %d alignments, %d windows in %.2f s (%s, device %.2f s, the rest waiting for `samtools view`)"
-                     % (f.stats()["reads"], n, time() - t_start, "packing the text on the host %.2f s" % t_pack if t_pack else "text parsed on the device", t_dev))
+        logging.info("device front end: %d alignments, %d windows in %.2f s (%s, device %.2f s, the rest waiting for %s)"
+                     % (f.stats()["reads"], n, time() - t_start, "packing the text on the host %.2f s" % t_pack if t_pack else
+                        ("BAM records decoded on the device" if isinstance(view, _NativeBam) else "text parsed on the device"), t_dev,
+                        "the BAM reader" if native_input(args) else "`samtools view`"))
         self.n_windows = n
         return n
 
@@ -656,6 +774,13 @@ def normalise(args):
         args.ctgStart = args.ctgEnd = None          # callVarBam.py:97-101
     if (args.ctgStart is None) != (args.ctgEnd is None):
         args.ctgStart = args.ctgEnd = None
+    if getattr(args, "bam_reader", "samtools") == "native":
+        for name, given in (("--samtools_view_args", args.samtools_view_args is not None), ("--samtools_threads", (args.samtools_threads or 0) > 0),
+                            ("--view_readers", (args.view_readers or 1) > 1)):
+            if given:
+                sys.exit("[ERROR] %s configures `samtools view`, which --bam_reader native does not run: drop one of the two" % name)
+        if not 1 <= args.bam_threads <= 16:
+            sys.exit("[ERROR] --bam_threads %d: 1 .. 16" % args.bam_threads)
     return args
 
 
@@ -784,6 +909,11 @@ def build_parser():
              "tables) can be several times the size of the rest.  Write a value that is itself one option with `=`: --samtools_view_args=-x")
     add('--samtools_threads', type=int, default=0,
         help="extra decompression threads for `samtools view` (its -@): with the front end on the device the BAM decoder is what the run waits for")
+    add('--bam_reader', type=str, default="samtools", choices=("samtools", "native"),
+        help="how the alignments and the reference slice are read: `samtools view` / `samtools faidx` (default), or natively without samtools "
+             "(BGZF BAM with a .bai or none; the records are decoded on the GPU with the device front end).  CRAM, .csi indexes and extra view "
+             "options need samtools")
+    add('--bam_threads', type=int, default=4, help="with --bam_reader native: threads that inflate BGZF blocks (1 .. 16), default: %(default)s")
     add('--device', type=int, default=0, help="HIP device ordinal, default: %(default)s")
     add('--arith', type=str, default="legacy", choices=("legacy", "numpy2"),
         help="QUAL/AF arithmetic: float64 as under the reference's NumPy 1.x (legacy) or float32 (numpy2)")

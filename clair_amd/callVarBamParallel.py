@@ -68,6 +68,7 @@ def commands(args):
         _opt("front_end", args.front_end), _opt("batch_size", args.batch_size), _opt("samtools_threads", args.samtools_threads), _opt("view_readers", args.view_readers),
         # as ONE token: a value that is a single option ("-x", "--no-PG") would otherwise be read as the next flag
         None if args.samtools_view_args is None else '--samtools_view_args="%s"' % args.samtools_view_args,
+        _opt("bam_reader", args.bam_reader), _opt("bam_threads", args.bam_threads),
     ] if x is not None)
     out, k = [], 0
     commands.chunks = []           # (device, output file) per command, for --run
@@ -245,6 +246,8 @@ def build_parser():
     add('--samtools_threads', type=int, default=None, help="passed on (callVarBam: -@ of `samtools view`)")
     add('--view_readers', type=int, default=None, help="passed on (callVarBam: `samtools view` processes per region)")
     add('--samtools_view_args', type=str, default=None, help="passed on (callVarBam: extra options for `samtools view`)")
+    add('--bam_reader', type=str, default=None, choices=("samtools", "native"), help="passed on (callVarBam: read the BAM with samtools or natively)")
+    add('--bam_threads', type=int, default=None, help="passed on (callVarBam: BGZF inflate threads of --bam_reader native)")
     return parser
 
 

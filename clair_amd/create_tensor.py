@@ -248,14 +248,19 @@ def subprocess_popen(args, stdin=None, stdout=subprocess.PIPE, text=True):
     return subprocess.Popen(args, stdin=stdin, stdout=stdout, stderr=sys.stderr, bufsize=8388608, universal_newlines=text)
 
 
-def reference_sequence_from(samtools, ref_fn, ctg_name, ctg_start, ctg_end):
-    """`samtools faidx` for the region widened by 1 Mbp (CreateTensor.py:113-156) -> (sequence upper-cased, 1-based start or None)."""
+def reference_sequence_from(samtools, ref_fn, ctg_name, ctg_start, ctg_end, native=False):
+    """`samtools faidx` for the region widened by 1 Mbp (CreateTensor.py:113-156) -> (sequence upper-cased, 1-based start or None).
+    native: the same slice read through the .fai without samtools (clair_host_faidx; callVarBam --bam_reader native)."""
     start = end = None
     if ctg_start is not None and ctg_end is not None:
         start, end = max(1, ctg_start - EXPAND_REFERENCE_REGION), ctg_end + EXPAND_REFERENCE_REGION
         region = "%s:%d-%d" % (ctg_name, start, end)
     else:
         region = ctg_name
+    if native:
+        from . import _hostapi
+        seq = _hostapi.faidx(ref_fn, ctg_name, start, end)
+        return (None if seq is None else seq.upper()), start
     try:
         p = subprocess_popen(shlex.split("%s faidx %s %s" % (samtools, ref_fn, region)))
     except OSError:

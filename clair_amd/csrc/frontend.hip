@@ -950,18 +950,15 @@ __device__ inline int64_t token_end(const uint8_t *t, int64_t q, int64_t end) {
     return q;
 }
 
-// walks a CIGAR; EMIT writes the kept operations
-template <bool EMIT>
-__device__ inline void walk_cigar(const uint8_t *cg, uint32_t cl, uint32_t read, clair_op_t *ops, uint32_t *op_elem, uint32_t elem0,
-                                  int64_t *o_rp, int64_t *o_qp, int64_t *o_soft, int64_t *o_total, int64_t *o_rlen, uint32_t *o_ops, uint64_t *o_elems, bool *o_zero,
-                                  bool *o_lead = nullptr) {
-    int64_t adv = 0, rp = 0, qp = 0, soft = 0, total = 0, rlen = 0;
+// one CIGAR operation of `adv` bases, `ch` its letter: the rules of the walk shared by the text and the binary CIGAR; EMIT writes the kept operations
+struct CigarWalk {
+    int64_t rp = 0, qp = 0, soft = 0, total = 0, rlen = 0;
     uint32_t n_ops = 0;
     uint64_t elems = 0;
     bool zero = false, lead = false;
-    for (uint32_t i = 0; i < cl; ++i) {
-        const uint8_t ch = cg[i];
-        if (ch >= '0' && ch <= '9') { adv = adv * 10 + (ch - '0'); if (adv > ((int64_t)1 << 40)) adv = (int64_t)1 << 40; continue; }
+
+    template <bool EMIT>
+    __device__ inline void op(int64_t adv, uint8_t ch, uint32_t read, clair_op_t *ops, uint32_t *op_elem, uint32_t elem0) {
         int code = -1;
         switch (ch) {
         case 'S': soft += adv; qp += adv; break;
@@ -988,9 +985,23 @@ __device__ inline void walk_cigar(const uint8_t *cg, uint32_t cl, uint32_t read,
             if (code != CLAIR_OP_D) qp += adv;
         }
         total += adv;
+    }
+};
+
+// walks a CIGAR; EMIT writes the kept operations
+template <bool EMIT>
+__device__ inline void walk_cigar(const uint8_t *cg, uint32_t cl, uint32_t read, clair_op_t *ops, uint32_t *op_elem, uint32_t elem0,
+                                  int64_t *o_rp, int64_t *o_qp, int64_t *o_soft, int64_t *o_total, int64_t *o_rlen, uint32_t *o_ops, uint64_t *o_elems, bool *o_zero,
+                                  bool *o_lead = nullptr) {
+    int64_t adv = 0;
+    CigarWalk w;
+    for (uint32_t i = 0; i < cl; ++i) {
+        const uint8_t ch = cg[i];
+        if (ch >= '0' && ch <= '9') { adv = adv * 10 + (ch - '0'); if (adv > ((int64_t)1 << 40)) adv = (int64_t)1 << 40; continue; }
+        w.op<EMIT>(adv, ch, read, ops, op_elem, elem0);
         adv = 0;
     }
-    if (!EMIT) { *o_rp = rp; *o_qp = qp; *o_soft = soft; *o_total = total; *o_rlen = rlen; *o_ops = n_ops; *o_elems = elems; *o_zero = zero; if (o_lead) *o_lead = lead; }
+    if (!EMIT) { *o_rp = w.rp; *o_qp = w.qp; *o_soft = w.soft; *o_total = w.total; *o_rlen = w.rlen; *o_ops = w.n_ops; *o_elems = w.elems; *o_zero = w.zero; if (o_lead) *o_lead = w.lead; }
 }
 
 __device__ inline bool text_int(const uint8_t *s, uint32_t len, int64_t *out) {     // [+-]digits, at most 18 of them (host_sampack.cpp)
@@ -1203,6 +1214,197 @@ __global__ __launch_bounds__(256) void fe_text_seq_kernel(const uint8_t *text, c
     }
 }
 
+// ---- BAM records decoded on the device (clair_frontend_bam_options / _add_bam): the binary twin of the text path above ------------------
+// The host inflates BGZF and walks the records' block_size fields (hostsrc/host_bam.cpp); the chunk comes here as it was inflated, with the
+// start of every record.  fe_bam_records_kernel decodes a record into the TextLine the text path fills for the line `samtools view` would
+// print for it, and applies the view's own filter first (-F 2316, the contig, the region); the records the view drops are compacted out
+// before anything counts lines, so that --dcov, the kept lines, the counters and the slab are the text path's kernels on the same lines.
+// Records start at any byte: fields are read as two aligned dwords and v_alignbyte (the buffer is allocated 16 bytes longer).
+struct BamOptions {
+    int tid;
+    int64_t region_lo, region_hi;        // 1-based inclusive, what `samtools view <bam> ctg:lo-hi` selects; -1 -1: the whole contig
+};
+enum { TL_BAM_NOSEQ = 256 };             // SEQ '*' (l_seq 0): the slab holds the one byte '*' the text path stores
+constexpr uint16_t BAM_VIEW_FILTER = 2316;
+
+__device__ inline uint32_t bam_u32(const uint8_t *base, uint64_t off) {
+    const uint32_t *w = (const uint32_t *)(base + (off & ~(uint64_t)3));
+    return __builtin_amdgcn_alignbyte(w[1], w[0], (uint32_t)(off & 3));
+}
+
+__device__ inline uint8_t bam_cigar_letter(uint32_t op) {
+    switch (op) {
+    case 0: return 'M'; case 1: return 'I'; case 2: return 'D'; case 3: return 'N'; case 4: return 'S';
+    case 5: return 'H'; case 6: return 'P'; case 7: return '='; case 8: return 'X'; case 9: return 'B';
+    default: return '?';
+    }
+}
+
+// the binary CIGAR at `off` (n operations) through the text walker's rules
+template <bool EMIT>
+__device__ inline CigarWalk walk_cigar_bam(const uint8_t *rec, uint64_t off, uint32_t n, uint32_t read, clair_op_t *ops, uint32_t *op_elem, uint32_t elem0) {
+    CigarWalk w;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t c = bam_u32(rec, off + 4ull * i);
+        w.op<EMIT>((int64_t)(c >> 4), bam_cigar_letter(c & 15), read, ops, op_elem, elem0);
+    }
+    return w;
+}
+
+// A record whose stored CIGAR is the <l_seq>S<ref_len>N placeholder (more than 65 535 operations) keeps the real one in CG:B:I: htslib's
+// bam_tag2cigar substitutes it when it reads the record, so `samtools view` prints it.  -> true and its offset / length when it applies.
+__device__ inline bool bam_real_cigar(const uint8_t *rec, uint64_t aux, uint64_t end, uint32_t n_cigar, uint64_t *cg_off, uint32_t *cg_n) {
+    while (aux + 3 <= end) {
+        const uint8_t t0 = rec[aux], t1 = rec[aux + 1], type = rec[aux + 2];
+        const bool cg = t0 == 'C' && t1 == 'G';
+        const uint64_t v = aux + 3;
+        uint64_t size = 0;
+        switch (type) {
+        case 'A': case 'c': case 'C': size = 1; break;
+        case 's': case 'S': size = 2; break;
+        case 'i': case 'I': case 'f': size = 4; break;
+        case 'Z': case 'H': { uint64_t z = v; while (z < end && rec[z]) ++z; if (z >= end) return false; size = z - v + 1; break; }
+        case 'B': {
+            if (v + 5 > end) return false;
+            const uint8_t sub = rec[v];
+            const uint32_t count = bam_u32(rec, v + 1);
+            const uint64_t each = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : (sub == 'i' || sub == 'I' || sub == 'f') ? 4 : 0;
+            if (!each || (uint64_t)count * each > end - v - 5) return false;
+            if (cg) {
+                if (!(sub == 'I' || sub == 'i') || count < n_cigar || count >= (1u << 29)) return false;
+                *cg_off = v + 5;
+                *cg_n = count;
+                return true;
+            }
+            size = 5 + (uint64_t)count * each;
+            break;
+        }
+        default: return false;
+        }
+        if (cg) return false;
+        aux = v + size;
+    }
+    return false;
+}
+
+// one thread per record: all[k] = the line the text path would have parsed, pass[k] = 1 when `samtools view -F 2316 <bam> <region>` prints it
+__global__ __launch_bounds__(256) void fe_bam_records_kernel(const uint8_t *rec, int64_t len, const int64_t *offsets, int64_t n, TextOptions opt, BamOptions bo,
+                                                             TextLine *all, uint8_t *pass, TextState *state) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    TextLine out{};
+    pass[k] = 0;
+    const int64_t at = offsets[k];
+    bool bad = at < 0 || at + 36 > len;
+    uint32_t block_size = 0, l_read_name = 0, mq = 0, n_cigar = 0, flag = 0;
+    int32_t ref_id = 0, pos0 = 0, l_seq = 0;
+    if (!bad) {
+        block_size = bam_u32(rec, at);
+        bad = block_size < 32 || at + 4 + (int64_t)block_size > len;
+    }
+    if (!bad) {
+        ref_id = (int32_t)bam_u32(rec, at + 4);
+        pos0 = (int32_t)bam_u32(rec, at + 8);
+        const uint32_t w3 = bam_u32(rec, at + 12), w4 = bam_u32(rec, at + 16);
+        l_read_name = w3 & 0xff;
+        mq = (w3 >> 8) & 0xff;
+        n_cigar = w4 & 0xffff;
+        flag = w4 >> 16;
+        l_seq = (int32_t)bam_u32(rec, at + 20);
+        bad = l_seq < 0 || l_read_name == 0
+              || 32ull + l_read_name + 4ull * n_cigar + ((uint64_t)l_seq + 1) / 2 + (uint64_t)l_seq > (uint64_t)block_size;
+    }
+    if (bad) {                                                                // the host renderer on the same records names the field
+        atomicMin(&state->malformed, (uint32_t)(k + 1));
+        all[k] = out;
+        return;
+    }
+    const uint64_t name_off = (uint64_t)at + 36, cigar_stored = name_off + l_read_name, seq_off = cigar_stored + 4ull * n_cigar;
+    const uint64_t rec_end = (uint64_t)at + 4 + block_size;
+    uint64_t cigar_off = cigar_stored;
+    uint32_t n_ops_cigar = n_cigar;
+    if (n_cigar > 0 && ref_id >= 0 && pos0 >= 0) {
+        const uint32_t c0 = bam_u32(rec, cigar_stored);
+        if ((c0 & 15) == 4 && (c0 >> 4) == (uint32_t)l_seq)                  // rare: look for CG
+            bam_real_cigar(rec, seq_off + ((uint64_t)l_seq + 1) / 2 + (uint64_t)l_seq, rec_end, n_cigar, &cigar_off, &n_ops_cigar);
+    }
+    const CigarWalk w = walk_cigar_bam<false>(rec, cigar_off, n_ops_cigar, 0, nullptr, nullptr, 0);
+    const int64_t pos1 = (int64_t)pos0 + 1;
+    bool view = (flag & BAM_VIEW_FILTER) == 0 && ref_id == bo.tid;
+    if (view && bo.region_lo >= 0 && bo.region_hi >= 0) {
+        const int64_t end1 = pos1 + (w.rlen > 0 ? w.rlen : 1) - 1;          // bam_endpos
+        view = pos1 <= bo.region_hi && end1 >= bo.region_lo;
+    }
+    if (!view) { all[k] = out; return; }
+    const uint32_t seq_len = l_seq > 0 ? (uint32_t)l_seq : 1u;               // SEQ '*' is one byte of text
+    const bool evc_ok = (int64_t)mq >= opt.evc_min_mq && n_ops_cigar > 0 && !(1.0 - (double)w.soft / (double)(w.total + 1) < 0.55);
+    bool in_region = true;
+    if (opt.pile_start >= 0 && opt.pile_end >= 0) {
+        const int64_t end1 = pos1 + (w.rlen > 0 ? w.rlen : 1) - 1;
+        in_region = pos1 <= opt.pile_end && end1 >= opt.pile_start;
+    }
+    const bool candidate = in_region && (int64_t)mq >= opt.pile_min_mq;
+    out.pos0 = pos0;
+    out.cigar_off = (uint32_t)cigar_off; out.cigar_len = n_ops_cigar;
+    out.seq_off = (uint32_t)seq_off; out.seq_len = seq_len;
+    out.n_ops = w.n_ops;
+    out.n_elem = w.elems > 0xfffffff0ull ? 0xfffffff0u : (uint32_t)w.elems;
+    out.flags = ((flag & 16) ? CLAIR_READ_REVERSE : 0) | (evc_ok ? CLAIR_READ_EVC : 0) | (candidate ? TL_CANDIDATE : 0) | (w.zero ? TL_ZERO_INDEL : 0)
+                | (w.lead ? TL_LEAD_INDEL : 0) | (l_seq == 0 ? TL_BAM_NOSEQ : 0)
+                | ((w.rp > (int64_t)seq_len + 100000 - 64 || w.rp > 0x7fffff00 || w.qp > 0x7fffff00) ? TL_LONG_SPAN : 0);
+    all[k] = out;
+    pass[k] = 1;
+}
+
+// the records the view prints, in order: from here on they are the text path's lines
+__global__ __launch_bounds__(256) void fe_bam_gather_kernel(const TextLine *all, const int64_t *shown, int64_t n_lines, TextLine *lines, uint8_t *is_candidate) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= n_lines) return;
+    const TextLine ln = all[shown[j]];
+    lines[j] = ln;
+    is_candidate[j] = (ln.flags & TL_CANDIDATE) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void fe_bam_emit_kernel(const uint8_t *rec, const TextLine *lines, const int64_t *kept, int64_t n_kept, const uint32_t *op0,
+                                                          const uint32_t *elem0, const uint32_t *seq0, clair_read_t *reads, clair_op_t *ops, uint32_t *op_elem,
+                                                          uint64_t total_ops, uint64_t total_elems) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) op_elem[total_ops] = (uint32_t)total_elems;
+    if (i >= n_kept) return;
+    const TextLine ln = lines[kept[i]];
+    (void)walk_cigar_bam<true>(rec, ln.cigar_off, ln.cigar_len, (uint32_t)i, ops + op0[i], op_elem + op0[i], elem0[i]);
+    clair_read_t r;
+    r.pos0 = ln.pos0;
+    r.seq0 = seq0[i];
+    r.seq_len = ln.seq_len;
+    r.op0 = op0[i];
+    r.n_ops = ln.n_ops;
+    r.flags = ln.flags & (CLAIR_READ_REVERSE | CLAIR_READ_EVC | CLAIR_READ_PILE | CLAIR_READ_FLUSH);
+    r.reserved = 0;
+    reads[i] = r;
+}
+
+// "=ACMGRSVTWYHKDBN" eight letters to a word: a 4-bit code to its letter without a table in memory
+constexpr uint64_t pack8(const char *s) { uint64_t v = 0; for (int i = 7; i >= 0; --i) v = v << 8 | (uint8_t)s[i]; return v; }
+constexpr uint64_t NT16_LO = pack8("=ACMGRSV"), NT16_HI = pack8("TWYHKDBN");
+__device__ inline uint32_t nt16_letter(uint32_t c) { return (uint32_t)(((c & 8) ? NT16_HI : NT16_LO) >> ((c & 7) * 8)) & 0xff; }
+
+// The 4-bit SEQ of every kept record into the slab's packed buffer as the letters `samtools view` prints: a wave per alignment, per lane and
+// step two packed bytes in (bases 4k .. 4k+3), one dword out.  An odd l_seq leaves its padding nibble in the alignment's pad bytes.
+__global__ __launch_bounds__(256) void fe_bam_seq_kernel(const uint8_t *rec, const TextLine *lines, const int64_t *kept, int64_t n_kept, const uint32_t *seq0, uint8_t *seq) {
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= n_kept) return;
+    const int lane = threadIdx.x & 63;
+    const TextLine ln = lines[kept[i]];
+    uint32_t *dst = (uint32_t *)(seq + seq0[i]);
+    if (ln.flags & TL_BAM_NOSEQ) { if (lane == 0) dst[0] = '*'; return; }
+    const uint32_t n_dw = (ln.seq_len + 3u) >> 2;
+    for (uint32_t k = (uint32_t)lane; k < n_dw; k += 64) {
+        const uint32_t two = bam_u32(rec, (uint64_t)ln.seq_off + 2ull * k);
+        dst[k] = nt16_letter((two >> 4) & 15) | nt16_letter(two & 15) << 8 | nt16_letter((two >> 12) & 15) << 16 | nt16_letter((two >> 8) & 15) << 24;
+    }
+}
+
 int fe_fail(clair_frontend *f, const char *fmt, ...);
 
 }  // namespace
@@ -1240,6 +1442,8 @@ struct clair_frontend {
     uint8_t *d_ctg = nullptr;
     TextState text_state{};
     TextState *d_text_state = nullptr;
+    bool bam_mode = false;               // clair_frontend_bam_options was called last: records come through _add_bam
+    BamOptions bam_opt{};
     uint32_t *d_span = nullptr;          // the longest reference reach of the slab being tallied (fe_slab_span_kernel)
     unsigned long long *d_d2 = nullptr, *d_fold = nullptr;   // --stop_consider_left_edge, pass 2 per operation: tuples per window as second differences over positions
     bool pass2_per_base = false;         // CLAIR_AMD_FE_PASS2=base when the handle was created: --stop_consider_left_edge's pass 2 by fe_windows_per_base_kernel
@@ -1417,6 +1621,86 @@ static int launch_tally(clair_frontend *f, const Slab &d, int64_t p_first, int64
     return 0;
 }
 
+// freed on every way out
+struct DeviceTemp {
+    std::vector<void *> p;
+    ~DeviceTemp() { for (void *x : p) (void)hipFree(x); }
+    hipError_t get(void **out, size_t bytes) { hipError_t e = hipMalloc(out, std::max<size_t>(bytes, 16)); if (e == hipSuccess) p.push_back(*out); return e; }
+};
+
+// The lines of one chunk, parsed from text (clair_frontend_add_text) or decoded from BAM records and compacted to those the view prints
+// (clair_frontend_add_bam), in lines[0 .. n_lines) with is_cand set -> --dcov, the kept lines, their offsets and the counters, the slab
+// (operations and bases from `src`: the text, or the records when `bam`), its tally.  Returns 2 with *malformed = 1 + the index of the
+// first malformed line / record.
+static int pack_lines(clair_frontend *f, DeviceTemp &tmp, const uint8_t *src, bool bam, TextLine *lines, uint8_t *is_cand, int64_t n_lines, uint32_t *d_count,
+               const TextState &carry, uint32_t *malformed) {
+    int64_t *cand = nullptr, *kept = nullptr;
+    uint8_t *keep = nullptr;
+    uint32_t *line_sum = nullptr;
+    FE_TRY(f, tmp.get((void **)&keep, (size_t)n_lines + 1));
+    FE_TRY(f, tmp.get((void **)&line_sum, ((size_t)blocks_for(n_lines + 1, SCAN_BLOCK) + 2) * sizeof(uint32_t)));
+    int64_t n_cand = 0, n_kept = 0;
+    if (scan_count(f, is_cand, n_lines, line_sum, d_count + 1, &n_cand)) return 1;
+    FE_TRY(f, tmp.get((void **)&cand, (size_t)n_cand * sizeof(int64_t)));
+    if (scan_write(f, is_cand, n_lines, line_sum, d_count + 1, nullptr, cand, 0)) return 1;
+    if (n_cand) hipLaunchKernelGGL(fe_text_dcov_kernel, dim3(blocks_for(n_cand, 256)), dim3(256), 0, f->stream, lines, (const int64_t *)cand, n_cand, f->text_opt.dcov, carry);
+    hipLaunchKernelGGL(fe_text_keep_kernel, dim3(blocks_for(n_lines, 256)), dim3(256), 0, f->stream, (const TextLine *)lines, n_lines, keep);
+    FE_TRY(f, hipGetLastError());
+    if (scan_count(f, keep, n_lines, line_sum, d_count + 2, &n_kept)) return 1;
+    FE_TRY(f, tmp.get((void **)&kept, (size_t)n_kept * sizeof(int64_t)));
+    if (scan_write(f, keep, n_lines, line_sum, d_count + 2, nullptr, kept, 0)) return 1;
+    uint32_t *op0 = nullptr, *elem0 = nullptr, *seq0 = nullptr;
+    uint64_t *d_totals = nullptr;
+    FE_TRY(f, tmp.get((void **)&op0, (size_t)n_kept * sizeof(uint32_t)));
+    FE_TRY(f, tmp.get((void **)&elem0, (size_t)n_kept * sizeof(uint32_t)));
+    FE_TRY(f, tmp.get((void **)&seq0, (size_t)n_kept * sizeof(uint32_t)));
+    FE_TRY(f, tmp.get((void **)&d_totals, 5 * sizeof(uint64_t)));
+    hipLaunchKernelGGL(fe_text_offsets_kernel, dim3(1), dim3(256), 0, f->stream, (const TextLine *)lines, n_lines, (const int64_t *)kept, n_kept, (const int64_t *)cand, n_cand,
+                       op0, elem0, seq0, d_totals, carry, f->d_text_state);
+    FE_TRY(f, hipGetLastError());
+    uint64_t totals[5] = {0, 0, 0, 0, 0};
+    TextState after{};
+    FE_TRY(f, hipMemcpyAsync(totals, d_totals, sizeof totals, hipMemcpyDeviceToHost, f->stream));
+    FE_TRY(f, hipMemcpyAsync(&after, f->d_text_state, sizeof after, hipMemcpyDeviceToHost, f->stream));
+    FE_TRY(f, hipStreamSynchronize(f->stream));
+    if (after.malformed != 0xffffffffu) {
+        *malformed = after.malformed;
+        return 2;
+    }
+    if (totals[0] > 0xfffffff0ull || totals[1] > 0xfffffff0ull || totals[4] > 0xfffffff0ull) return fe_fail(f, "chunk too dense for 32-bit offsets: feed smaller chunks");
+    after.malformed = 0;
+    f->text_state = after;
+    if (n_kept == 0 || totals[0] == 0) return 0;
+    Slab s;
+    s.n_reads = n_kept; s.n_ops = (int64_t)totals[0]; s.n_elem = (int64_t)totals[1]; s.seq_bytes = (int64_t)totals[4];
+    FE_TRY(f, hipMalloc((void **)&s.reads, (size_t)n_kept * sizeof(clair_read_t)));
+    f->slabs.push_back(s);
+    Slab &d = f->slabs.back();
+    FE_TRY(f, hipMalloc((void **)&d.ops, (size_t)d.n_ops * sizeof(clair_op_t)));
+    FE_TRY(f, hipMalloc((void **)&d.op_elem, ((size_t)d.n_ops + 1) * sizeof(uint32_t)));
+    FE_TRY(f, hipMalloc((void **)&d.tuples, (size_t)n_kept * sizeof(uint64_t)));
+    FE_TRY(f, hipMalloc((void **)&d.seq, (size_t)std::max<uint64_t>(totals[4], 16)));      // the bases only: the text itself is released when this call returns
+    FE_TRY(f, hipMemsetAsync(d.tuples, 0, (size_t)n_kept * sizeof(uint64_t), f->stream));
+    if (bam) {
+        hipLaunchKernelGGL(fe_bam_emit_kernel, dim3(blocks_for(n_kept, 256)), dim3(256), 0, f->stream, src, (const TextLine *)lines, (const int64_t *)kept, n_kept,
+                           (const uint32_t *)op0, (const uint32_t *)elem0, (const uint32_t *)seq0, d.reads, d.ops, d.op_elem, totals[0], totals[1]);
+        hipLaunchKernelGGL(fe_bam_seq_kernel, dim3(blocks_for(n_kept, 4)), dim3(256), 0, f->stream, src, (const TextLine *)lines, (const int64_t *)kept, n_kept,
+                           (const uint32_t *)seq0, d.seq);
+    } else {
+        hipLaunchKernelGGL(fe_text_emit_kernel, dim3(blocks_for(n_kept, 256)), dim3(256), 0, f->stream, src, (const TextLine *)lines, (const int64_t *)kept, n_kept,
+                           (const uint32_t *)op0, (const uint32_t *)elem0, (const uint32_t *)seq0, d.reads, d.ops, d.op_elem, totals[0], totals[1]);
+        hipLaunchKernelGGL(fe_text_seq_kernel, dim3(blocks_for(n_kept, 4)), dim3(256), 0, f->stream, src, (const TextLine *)lines, (const int64_t *)kept, n_kept,
+                           (const uint32_t *)seq0, d.seq);
+    }
+    // the tiled tally bisects over the slab's start positions: once the packer has seen a start go backwards (this slab or an earlier
+    // one: the word is cumulative, and a start below the previous slab's last is exactly such a case) the per-base kernel is used, as
+    // clair_frontend_add_reads does -- an unsorted slab is flagged AND tallied correctly on both entry points (ADVICE r05)
+    if (launch_tally(f, d, (int64_t)totals[3], after.last_pos + (int64_t)totals[2], !(after.anomalies & CLAIR_FE_UNSORTED))) return 1;
+    FE_TRY(f, hipGetLastError());
+    FE_TRY(f, hipStreamSynchronize(f->stream));
+    return 0;
+}
+
 int clair_frontend_add_reads(clair_frontend_t *f, const clair_read_t *reads, int64_t n_reads, const clair_op_t *ops, int64_t n_ops,
                              const uint32_t *op_elem, const uint8_t *seq, int64_t seq_bytes) {
     if (!f) return fe_fail(nullptr, "front end is NULL");
@@ -1485,17 +1769,14 @@ int clair_frontend_text_options(clair_frontend_t *f, const char *ctg_name, int d
 int clair_frontend_add_text(clair_frontend_t *f, const char *sam, int64_t len) {
     if (!f) return fe_fail(nullptr, "front end is NULL");
     if (!f->text_ready) return fe_fail(f, "call clair_frontend_text_options first");
+    if (f->bam_mode) return fe_fail(f, "clair_frontend_bam_options was called: records come through clair_frontend_add_bam");
     if (len < 0 || (len > 0 && !sam)) return fe_fail(f, "bad text");
     if (len == 0) return 0;
     if (len > 0x7ffffff0ll) return fe_fail(f, "text chunk of %lld bytes: at most 2 GB at a time", (long long)len);
     if (sam[len - 1] != '\n') return fe_fail(f, "the text must end at a line end");
     if (f->n_candidates >= 0) return fe_fail(f, "reads cannot be added after the candidates were fixed");
     FE_TRY(f, hipSetDevice(f->device));
-    struct Temp {           // freed on every way out
-        std::vector<void *> p;
-        ~Temp() { for (void *x : p) (void)hipFree(x); }
-        hipError_t get(void **out, size_t bytes) { hipError_t e = hipMalloc(out, std::max<size_t>(bytes, 16)); if (e == hipSuccess) p.push_back(*out); return e; }
-    } tmp;
+    DeviceTemp tmp;
     uint8_t *d_text = nullptr;
     uint32_t *block_sum = nullptr, *d_count = nullptr;
     FE_TRY(f, tmp.get((void **)&d_text, (size_t)len + 16));            // fe_text_seq_kernel reads whole dwords
@@ -1504,76 +1785,93 @@ int clair_frontend_add_text(clair_frontend_t *f, const char *sam, int64_t len) {
     FE_TRY(f, hipMemcpyAsync(d_text, sam, (size_t)len, hipMemcpyHostToDevice, f->stream));
     int64_t n_lines = 0;
     if (scan_count(f, d_text, len, block_sum, d_count, &n_lines, true)) return 1;
-    int64_t *newline = nullptr, *cand = nullptr, *kept = nullptr;
+    int64_t *newline = nullptr;
     TextLine *lines = nullptr;
-    uint8_t *is_cand = nullptr, *keep = nullptr;
-    uint32_t *line_sum = nullptr;
+    uint8_t *is_cand = nullptr;
     FE_TRY(f, tmp.get((void **)&newline, (size_t)n_lines * sizeof(int64_t)));
     if (scan_write(f, d_text, len, block_sum, d_count, nullptr, newline, 0, true)) return 1;
     FE_TRY(f, tmp.get((void **)&lines, (size_t)n_lines * sizeof(TextLine)));
     FE_TRY(f, tmp.get((void **)&is_cand, (size_t)n_lines + 1));
-    FE_TRY(f, tmp.get((void **)&keep, (size_t)n_lines + 1));
-    FE_TRY(f, tmp.get((void **)&line_sum, ((size_t)blocks_for(n_lines + 1, SCAN_BLOCK) + 2) * sizeof(uint32_t)));
     TextState carry = f->text_state;
     carry.malformed = 0xffffffffu;
     FE_TRY(f, hipMemcpyAsync(f->d_text_state, &carry, sizeof carry, hipMemcpyHostToDevice, f->stream));
     hipLaunchKernelGGL(fe_text_lines_kernel, dim3(blocks_for(n_lines, 256)), dim3(256), 0, f->stream, (const uint8_t *)d_text, (const int64_t *)newline, n_lines,
                        f->text_opt, lines, is_cand, f->d_text_state);
     FE_TRY(f, hipGetLastError());
-    int64_t n_cand = 0, n_kept = 0;
-    if (scan_count(f, is_cand, n_lines, line_sum, d_count + 1, &n_cand)) return 1;
-    FE_TRY(f, tmp.get((void **)&cand, (size_t)n_cand * sizeof(int64_t)));
-    if (scan_write(f, is_cand, n_lines, line_sum, d_count + 1, nullptr, cand, 0)) return 1;
-    if (n_cand) hipLaunchKernelGGL(fe_text_dcov_kernel, dim3(blocks_for(n_cand, 256)), dim3(256), 0, f->stream, lines, (const int64_t *)cand, n_cand, f->text_opt.dcov, carry);
-    hipLaunchKernelGGL(fe_text_keep_kernel, dim3(blocks_for(n_lines, 256)), dim3(256), 0, f->stream, (const TextLine *)lines, n_lines, keep);
-    FE_TRY(f, hipGetLastError());
-    if (scan_count(f, keep, n_lines, line_sum, d_count + 2, &n_kept)) return 1;
-    FE_TRY(f, tmp.get((void **)&kept, (size_t)n_kept * sizeof(int64_t)));
-    if (scan_write(f, keep, n_lines, line_sum, d_count + 2, nullptr, kept, 0)) return 1;
-    uint32_t *op0 = nullptr, *elem0 = nullptr, *seq0 = nullptr;
-    uint64_t *d_totals = nullptr;
-    FE_TRY(f, tmp.get((void **)&op0, (size_t)n_kept * sizeof(uint32_t)));
-    FE_TRY(f, tmp.get((void **)&elem0, (size_t)n_kept * sizeof(uint32_t)));
-    FE_TRY(f, tmp.get((void **)&seq0, (size_t)n_kept * sizeof(uint32_t)));
-    FE_TRY(f, tmp.get((void **)&d_totals, 5 * sizeof(uint64_t)));
-    hipLaunchKernelGGL(fe_text_offsets_kernel, dim3(1), dim3(256), 0, f->stream, (const TextLine *)lines, n_lines, (const int64_t *)kept, n_kept, (const int64_t *)cand, n_cand,
-                       op0, elem0, seq0, d_totals, carry, f->d_text_state);
-    FE_TRY(f, hipGetLastError());
-    uint64_t totals[5] = {0, 0, 0, 0, 0};
-    TextState after{};
-    FE_TRY(f, hipMemcpyAsync(totals, d_totals, sizeof totals, hipMemcpyDeviceToHost, f->stream));
-    FE_TRY(f, hipMemcpyAsync(&after, f->d_text_state, sizeof after, hipMemcpyDeviceToHost, f->stream));
-    FE_TRY(f, hipStreamSynchronize(f->stream));
-    if (after.malformed != 0xffffffffu) {
+    uint32_t malformed = 0;
+    const int rc = pack_lines(f, tmp, d_text, false, lines, is_cand, n_lines, d_count, carry, &malformed);
+    if (rc == 2)
         fe_fail(f, "line %u of this chunk (%lld lines before it) is not an alignment line the scripts accept: clair_host_sampack_feed on the same text names "
-                   "the column", after.malformed - 1, (long long)f->text_state.lines);
-        return 2;
-    }
-    if (totals[0] > 0xfffffff0ull || totals[1] > 0xfffffff0ull || totals[4] > 0xfffffff0ull) return fe_fail(f, "text chunk too dense for 32-bit offsets: feed smaller chunks");
-    after.malformed = 0;
-    f->text_state = after;
-    if (n_kept == 0 || totals[0] == 0) return 0;
-    Slab s;
-    s.n_reads = n_kept; s.n_ops = (int64_t)totals[0]; s.n_elem = (int64_t)totals[1]; s.seq_bytes = (int64_t)totals[4];
-    FE_TRY(f, hipMalloc((void **)&s.reads, (size_t)n_kept * sizeof(clair_read_t)));
-    f->slabs.push_back(s);
-    Slab &d = f->slabs.back();
-    FE_TRY(f, hipMalloc((void **)&d.ops, (size_t)d.n_ops * sizeof(clair_op_t)));
-    FE_TRY(f, hipMalloc((void **)&d.op_elem, ((size_t)d.n_ops + 1) * sizeof(uint32_t)));
-    FE_TRY(f, hipMalloc((void **)&d.tuples, (size_t)n_kept * sizeof(uint64_t)));
-    FE_TRY(f, hipMalloc((void **)&d.seq, (size_t)std::max<uint64_t>(totals[4], 16)));      // the bases only: the text itself is released when this call returns
-    FE_TRY(f, hipMemsetAsync(d.tuples, 0, (size_t)n_kept * sizeof(uint64_t), f->stream));
-    hipLaunchKernelGGL(fe_text_emit_kernel, dim3(blocks_for(n_kept, 256)), dim3(256), 0, f->stream, (const uint8_t *)d_text, (const TextLine *)lines, (const int64_t *)kept, n_kept,
-                       (const uint32_t *)op0, (const uint32_t *)elem0, (const uint32_t *)seq0, d.reads, d.ops, d.op_elem, totals[0], totals[1]);
-    hipLaunchKernelGGL(fe_text_seq_kernel, dim3(blocks_for(n_kept, 4)), dim3(256), 0, f->stream, (const uint8_t *)d_text, (const TextLine *)lines, (const int64_t *)kept, n_kept,
-                       (const uint32_t *)seq0, d.seq);
-    // the tiled tally bisects over the slab's start positions: once the packer has seen a start go backwards (this slab or an earlier
-    // one: the word is cumulative, and a start below the previous slab's last is exactly such a case) the per-base kernel is used, as
-    // clair_frontend_add_reads does -- an unsorted slab is flagged AND tallied correctly on both entry points (ADVICE r05)
-    if (launch_tally(f, d, (int64_t)totals[3], after.last_pos + (int64_t)totals[2], !(after.anomalies & CLAIR_FE_UNSORTED))) return 1;
-    FE_TRY(f, hipGetLastError());
-    FE_TRY(f, hipStreamSynchronize(f->stream));
+                   "the column", malformed - 1, (long long)f->text_state.lines);
+    return rc;
+}
+
+int clair_frontend_bam_options(clair_frontend_t *f, int tid, int dcov, int evc_min_mq, int pile_min_mq, int64_t pile_start, int64_t pile_end,
+                               int64_t region_lo, int64_t region_hi) {
+    if (!f) return fe_fail(nullptr, "front end is NULL");
+    if (tid < 0) return fe_fail(f, "reference id %d", tid);
+    if (!f->slabs.empty() && f->text_ready) return fe_fail(f, "BAM options cannot change once records were added");
+    FE_TRY(f, hipSetDevice(f->device));
+    if (!f->d_text_state) FE_TRY(f, hipMalloc((void **)&f->d_text_state, sizeof(TextState)));
+    const bool have_pile = pile_start >= 0 && pile_end >= 0, have_region = region_lo >= 0 && region_hi >= 0;
+    f->text_opt = TextOptions{nullptr, 0, dcov, evc_min_mq, pile_min_mq, have_pile ? pile_start : -1, have_pile ? pile_end : -1};
+    f->bam_opt = BamOptions{tid, have_region ? region_lo : -1, have_region ? region_hi : -1};
+    f->text_state = TextState{};
+    f->text_ready = true;
+    f->bam_mode = true;
     return 0;
+}
+
+// returns 2 (not 1) when a record is malformed: the error names its index in this chunk (clair_host_bam_render on the same records says what)
+int clair_frontend_add_bam(clair_frontend_t *f, const uint8_t *records, int64_t len, const int64_t *offsets, int64_t n_records) {
+    if (!f) return fe_fail(nullptr, "front end is NULL");
+    if (!f->text_ready || !f->bam_mode) return fe_fail(f, "call clair_frontend_bam_options first");
+    if (len < 0 || n_records < 0 || (n_records > 0 && (!records || !offsets))) return fe_fail(f, "bad record chunk");
+    if (n_records == 0) return 0;
+    if (len > 0x7ffffff0ll) return fe_fail(f, "record chunk of %lld bytes: at most 2 GB at a time", (long long)len);
+    if (n_records > 0xfffffff0ll) return fe_fail(f, "%lld records in one chunk", (long long)n_records);
+    if (f->n_candidates >= 0) return fe_fail(f, "reads cannot be added after the candidates were fixed");
+    FE_TRY(f, hipSetDevice(f->device));
+    DeviceTemp tmp;
+    uint8_t *d_rec = nullptr, *pass = nullptr, *is_cand = nullptr;
+    int64_t *d_off = nullptr, *shown = nullptr;
+    uint32_t *rec_sum = nullptr, *d_count = nullptr;
+    TextLine *all = nullptr, *lines = nullptr;
+    FE_TRY(f, tmp.get((void **)&d_rec, (size_t)len + 16));               // fields and bases are read as whole dwords
+    FE_TRY(f, tmp.get((void **)&d_off, (size_t)n_records * sizeof(int64_t)));
+    FE_TRY(f, tmp.get((void **)&all, (size_t)n_records * sizeof(TextLine)));
+    FE_TRY(f, tmp.get((void **)&pass, (size_t)n_records + 1));
+    FE_TRY(f, tmp.get((void **)&rec_sum, ((size_t)blocks_for(n_records + 1, SCAN_BLOCK) + 2) * sizeof(uint32_t)));
+    FE_TRY(f, tmp.get((void **)&d_count, 4 * sizeof(uint32_t)));
+    FE_TRY(f, hipMemcpyAsync(d_rec, records, (size_t)len, hipMemcpyHostToDevice, f->stream));
+    FE_TRY(f, hipMemcpyAsync(d_off, offsets, (size_t)n_records * sizeof(int64_t), hipMemcpyHostToDevice, f->stream));
+    TextState carry = f->text_state;
+    carry.malformed = 0xffffffffu;
+    FE_TRY(f, hipMemcpyAsync(f->d_text_state, &carry, sizeof carry, hipMemcpyHostToDevice, f->stream));
+    hipLaunchKernelGGL(fe_bam_records_kernel, dim3(blocks_for(n_records, 256)), dim3(256), 0, f->stream, (const uint8_t *)d_rec, len, (const int64_t *)d_off,
+                       n_records, f->text_opt, f->bam_opt, all, pass, f->d_text_state);
+    FE_TRY(f, hipGetLastError());
+    int64_t n_lines = 0;                                                  // the records the view prints
+    if (scan_count(f, pass, n_records, rec_sum, d_count + 3, &n_lines)) return 1;
+    uint32_t malformed = 0;
+    int rc = 0;
+    if (n_lines == 0) {                                                   // nothing for the text path's kernels: the state is the carry's
+        TextState after{};
+        FE_TRY(f, hipMemcpyAsync(&after, f->d_text_state, sizeof after, hipMemcpyDeviceToHost, f->stream));
+        FE_TRY(f, hipStreamSynchronize(f->stream));
+        if (after.malformed != 0xffffffffu) { malformed = after.malformed; rc = 2; }
+    } else {
+        FE_TRY(f, tmp.get((void **)&shown, (size_t)n_lines * sizeof(int64_t)));
+        if (scan_write(f, pass, n_records, rec_sum, d_count + 3, nullptr, shown, 0)) return 1;
+        FE_TRY(f, tmp.get((void **)&lines, (size_t)n_lines * sizeof(TextLine)));
+        FE_TRY(f, tmp.get((void **)&is_cand, (size_t)n_lines + 1));
+        hipLaunchKernelGGL(fe_bam_gather_kernel, dim3(blocks_for(n_lines, 256)), dim3(256), 0, f->stream, (const TextLine *)all, (const int64_t *)shown, n_lines,
+                           lines, is_cand);
+        FE_TRY(f, hipGetLastError());
+        rc = pack_lines(f, tmp, d_rec, true, lines, is_cand, n_lines, d_count, carry, &malformed);
+    }
+    if (rc == 2) fe_fail(f, "record %u of this chunk is not a well-formed BAM record", malformed - 1);
+    return rc;
 }
 
 int clair_frontend_text_stats(clair_frontend_t *f, int64_t *stats) {

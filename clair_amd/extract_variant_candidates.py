@@ -191,7 +191,14 @@ def reference_region(ctg_name, ctg_start, ctg_end):
     return ("%s" % ctg_name if ctg_name is not None else ""), None
 
 
-def load_reference(samtools, ref_fn, region):
+def load_reference(samtools, ref_fn, region, native=False):
+    """`samtools faidx ref_fn region` upper-cased, or None; native: through the .fai without samtools (clair_host_faidx)."""
+    if native:
+        import re
+        from . import _hostapi
+        m = re.fullmatch(r"(.+):(\d+)-(\d+)", region)
+        seq = _hostapi.faidx(ref_fn, m.group(1), int(m.group(2)), int(m.group(3))) if m else _hostapi.faidx(ref_fn, region)
+        return None if seq is None else seq.upper()
     try:
         p = subprocess_popen(shlex.split("%s faidx %s %s" % (samtools, ref_fn, region)))
     except OSError:

@@ -292,6 +292,16 @@ int clair_frontend_text_options(clair_frontend_t *f, const char *ctg_name, int d
 int clair_frontend_add_text(clair_frontend_t *f, const char *sam, int64_t len);
 int clair_frontend_text_stats(clair_frontend_t *f, int64_t *stats);
 int clair_frontend_slab_reads(clair_frontend_t *f, int64_t slab, struct clair_read *reads, int64_t capacity, int64_t *n_reads);
+/* The binary twins of _text_options / _add_text (callVarBam --bam_reader native): BAM records as the host inflated them (include/clair_host.h:
+ * clair_host_bam_next), offsets[k] = where record k starts in records[0 .. len).  The device decodes each record and applies what
+ * `samtools view -F 2316 <bam> <region>` applies -- FLAG & 2316 == 0, reference id == tid, overlap (bam_endpos) with region_lo .. region_hi
+ * (1-based inclusive; -1 -1 = the whole contig) -- then handles the lines that view prints exactly as _add_text handles the same lines of
+ * text (the placeholder CIGAR of a record with more than 65 535 operations replaced by its CG tag, SEQ '*' for l_seq 0): same
+ * _text_stats, same slabs.  The other arguments as _text_options.  _add_bam returns 2 when a record's sizes do not fit its block_size
+ * (the message names the record's index in the chunk). */
+int clair_frontend_bam_options(clair_frontend_t *f, int tid, int dcov, int evc_min_mq, int pile_min_mq, int64_t pile_start, int64_t pile_end,
+                               int64_t region_lo, int64_t region_hi);
+int clair_frontend_add_bam(clair_frontend_t *f, const uint8_t *records, int64_t len, const int64_t *offsets, int64_t n_records);
 /* The candidate filter over the tallies: arguments as clair_host_evc_create (include/clair_host.h). */
 int clair_frontend_find_candidates(clair_frontend_t *f, double min_coverage, double threshold, int64_t ctg_start, int64_t ctg_end,
                                    const int64_t *bed_start, const int64_t *bed_end, int64_t n_bed, int64_t *n_candidates);

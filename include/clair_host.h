@@ -180,6 +180,36 @@ int clair_host_sampack_reset(clair_sampack_t *p);
 int clair_host_tuple_budget_binds(const struct clair_read *reads, const uint64_t *tuples, int64_t n_reads, const int64_t *centres,
                                   const uint64_t *window_tuples, int64_t n_centres, int64_t *state, int *binds);
 
+/* -- BAM input without samtools (callVarBam --bam_reader native; hostsrc/host_bam.cpp, zlib).  What `samtools view -F 2316 <bam>
+ *    <region>` does before it formats text: BGZF blocks inflated on `threads` threads (1 .. 16) with each block's CRC32 and ISIZE
+ *    checked (errors name the block's compressed offset), the header's reference names and lengths, the region's chunks from a .bai
+ *    (htslib's hts_itr_query) or a scan from the first record, and the walk over whole records that ends at the first record of the
+ *    contig starting past the region (hts_itr_next).  A file that is not BGZF (SAM text, CRAM, plain gzip) is an error that says to
+ *    use samtools.
+ *    info[0..3] = references in the header, 1 if the BGZF EOF block is present, records handed out by this query, 1 if it used an index.
+ *    query: beg1 / end1 1-based inclusive, -1 -1 = the whole contig; index_path NULL = scan.
+ *    next: whole records (block_size field included) into buf[0..cap), at most max_records; offsets[k] = where record k starts;
+ *    *n_records = 0 at the end.  The records are all those the index (or the scan) yields -- the view filter is the consumer's:
+ *    clair_frontend_add_bam on the device, clair_host_bam_render here.
+ *    voffset: BGZF virtual offset of record k of the last chunk next handed out (for messages).
+ *    render: of n records, those `samtools view -F 2316` keeps for contig tid and the region, as the 11 mandatory SAM columns it prints
+ *    (QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL; '*' for no CIGAR, no SEQ, QUAL 0xff; the CG:B:I CIGAR for the
+ *    kSmN placeholder); *text is the handle's and valid until the next render.
+ *    faidx: the bases of ctg:beg1-end1 (clamped; -1 -1 = whole contig) as `samtools faidx` prints them, case kept, line ends
+ *    dropped; out NULL = *len only. */
+typedef struct clair_bam clair_bam_t;
+int clair_host_bam_open(const char *path, int threads, clair_bam_t **out);
+void clair_host_bam_close(clair_bam_t *b);
+int clair_host_bam_info(const clair_bam_t *b, int64_t *info);
+int clair_host_bam_ref(const clair_bam_t *b, int tid, const char **name, int64_t *length);
+int clair_host_bam_tid(const clair_bam_t *b, const char *name);
+int clair_host_bam_query(clair_bam_t *b, const char *index_path, int tid, int64_t beg1, int64_t end1);
+int clair_host_bam_next(clair_bam_t *b, uint8_t *buf, int64_t cap, int64_t *offsets, int64_t max_records, int64_t *len, int64_t *n_records);
+int clair_host_bam_voffset(const clair_bam_t *b, int64_t k, uint64_t *voffset);
+int clair_host_bam_render(clair_bam_t *b, const uint8_t *records, const int64_t *offsets, int64_t n, int tid, int64_t beg1, int64_t end1,
+                          const char **text, int64_t *len);
+int clair_host_faidx(const char *fasta, const char *ctg, int64_t beg1, int64_t end1, char *out, int64_t cap, int64_t *len);
+
 #ifdef __cplusplus
 }
 #endif
