@@ -14,7 +14,10 @@ RCCL / xGMI through the C ABI's communicator (include/clair_amd.h: clair_comm_*)
 runs --steps batches.  `--scaling strong --candidates M`: a fixed set of M candidates (default 5 000 000, the
 whole-genome configs[3]) is dealt in contiguous blocks of whole batches; --steps is then derived.
 
-After the contract's timed region (`value`: inputs resident in HBM) the same K steps are timed twice more, each exactly like `value`
+A plain run sets up, warms up, times the K steps (`value`: inputs resident in HBM), writes `--dump-outputs` if asked and prints the line:
+the contract fields, `config`, `per_rank` and `launch_phases`.  Everything below runs only under `--full`, after the timed steps.
+
+After the contract's timed region the same K steps are timed twice more, each exactly like `value`
 (W warm-up steps, barrier + device sync on both sides, max over ranks):
   value_boundary        -- through the reference's own boundary, Clair.predict(batchX) on HOST arrays (clair/model.py:946-966, driven by
                            clair/call_var.py:1331-1352): pageable float32 NumPy batches in, four fresh NumPy arrays per batch out
@@ -39,7 +42,7 @@ rank's entry of the W-rank line (configs[3] and configs[4] on a one-GPU box).
 (float32, at most 64 MB: a fixed, seeded sample of rows beyond that).  Weights and inputs are seeded, so two builds run with the
 same arguments can be compared output for output.
 
-Prints ONE JSON line on rank 0 with the contract fields plus
+Prints ONE JSON line on rank 0 with the contract fields plus, under `--full`,
   roofline     -- the dominant kernel = the one with the most chip time (stand-alone duration x share of the 256 CUs its grid
                   occupies) in THIS run's own per-kernel table: SURVEY.md 8(d) algorithmic FLOP per launch / its mean
                   HIP-event duration IN the multi-stream configuration of the timed loop / the 2.5 PFLOP/s dense f16 MFMA
@@ -167,6 +170,9 @@ def parse_args(argv=None):
     ap.add_argument("--shard-of", default=None, metavar="R/W", help="--scaling strong on ONE GPU: run exactly the block rank R of a W-rank job would be dealt "
                     "(clair_amd/shard.py: shard_batches(--candidates, --batch, R, W), its ragged last batch included); per_rank[0] then reads as that "
                     "rank's entry of the W-rank line would.  How configs[3] (5 M ONT candidates / 8 GPUs) and configs[4] (>= 1 M Illumina candidates, batch 8192 / 8 GPUs) are run on a one-GPU box")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run every other leg and check: the whole-set, sustained and "
+                    "host-boundary legs, the per-kernel tables and roofline, the GPU state samples, the oracle parity and GT concordance, the CPU baseline "
+                    "(--full-candidates ... --cpu-seconds shape those legs; a plain run ignores them)")
     ap.add_argument("--full-candidates", type=int, default=200704, help="size of the untimed-by-contract leg over the whole candidate set of the config (0: skip)")
     ap.add_argument("--boundary-slots", type=int, default=6, help="batches in flight at the host-array boundary (0: skip the boundary legs)")
     ap.add_argument("--sustained-seconds", type=float, default=2.5, help="length of the value_sustained leg (0: skip)")
@@ -411,108 +417,11 @@ def boundary_legs(args, group, eng_resident, device, w, x, xd, od, batch, nuniq,
     return out
 
 
-def main():
-    args = parse_args()
-    if "WORLD_SIZE" not in os.environ and args.gpus > 1:
-        return spawn_and_relay(args)
-    # stdout carries exactly one JSON line: native libraries that print there (RCCL's start-up banner does) go to stderr
-    sys.stdout.flush()
-    json_fd = os.dup(1)
-    os.dup2(2, 1)
-    # RCCL through the C ABI when WORLD_SIZE > 1.  BENCH_SHARE_DEVICE=1 (a TEST of the multi-rank flow on a box with one GPU, never a
-    # measurement): every rank runs on device 0 and the ranks talk over the socket transport -- no rank holds an RCCL communicator, so the
-    # line says n_gpus 0 and the exit code is non-zero, as for any run without RCCL.
-    share = os.environ.get("BENCH_SHARE_DEVICE") == "1"
-    # BENCH_SHARE_TRANSPORT=rccl (with a stand-in librccl, CLAIR_AMD_RCCL_LIBRARY: real RCCL refuses two ranks on one GPU): the RCCL
-    # bring-up itself under test -- tests/test_comm_gpu.py hangs it and expects the line all the same
-    group = shard.NodeGroup(transport=os.environ.get("BENCH_SHARE_TRANSPORT", "tcp"), device=0) if share else shard.NodeGroup()
-    try:
-        rc = run_ranked(args, group, json_fd)
-    except BaseException:
-        group.close(barrier=False)     # unwinding: the peers may be gone, do not wait for them
-        raise
-    group.close()
-    if group.rccl_abandoned:           # a helper thread is still inside a hung RCCL bring-up: the line is out, do not wait for librccl's tear-down
-        group.exit_process(rc)
-    return rc
-
-
-def run_ranked(args, group, json_fd):
-    t_start = time.perf_counter()
-    rank, world, local_rank = group.rank, group.world, group.device          # the HIP device of this rank (= LOCAL_RANK unless BENCH_SHARE_DEVICE)
-    if world != args.gpus and rank == 0:
-        sys.stderr.write("bench.py: --gpus %d but the launcher started %d rank(s); reporting n_gpus=%d\n" % (args.gpus, world, world))
-
+def full_legs(args, group, eng, w, x, infos, xd, od, nuniq, steps, elapsed, per_rank_candidates, run, timed, phases, sampler):
+    """`--full`: every leg and check that follows the contract's timed region, in the order they have always run; `sampler` is closed once
+    the last GPU leg is done.  -> the fields they add to rank 0's line ({} on the other ranks)."""
+    rank, world, local_rank = group.rank, group.world, group.device
     batch, streams = args.batch, max(1, args.streams)
-    w = weights.synthetic_weights(seed=20250928, head_gain=4.0) if rank == 0 else None
-    if world > 1:
-        w = group.broadcast_weights(w, root=0)          # 9.5 MB over RCCL, once
-    eng = _capi.Engine(device=local_rank, max_batch=batch, n_slots=streams)
-    eng.load_weights(w)
-
-    steps = args.steps
-    mine_candidates = args.steps * batch
-    stands_for = None
-    if args.scaling == "strong":
-        as_rank, as_world = rank, world
-        if args.shard_of:
-            if world != 1:
-                raise SystemExit("--shard-of runs one rank's block on one GPU: use it with --gpus 1")
-            try:
-                as_rank, as_world = (int(v) for v in args.shard_of.split("/"))
-            except ValueError:
-                raise SystemExit("--shard-of takes R/W (two integers), not %r" % args.shard_of)
-            if not 0 <= as_rank < as_world:
-                raise SystemExit("--shard-of R/W needs 0 <= R < W")
-            stands_for = {"rank": as_rank, "world": as_world, "of_candidates": args.candidates}
-        first_candidate, mine_candidates = shard.shard_batches(args.candidates, batch, as_rank, as_world)
-        if stands_for:
-            stands_for["first_candidate"] = first_candidate
-        steps = (mine_candidates + batch - 1) // batch
-    steps_max = int(round(group.max_float(steps)))
-    nuniq = max(1, min(args.unique_batches, steps_max + args.warmup))
-    x, infos = synth.synthetic_input(nuniq * batch, args.platform, seed=20250928 + rank)
-    xd, od = eng.dataset_alloc(nuniq * batch)
-    eng.dataset_upload(xd, 0, x)
-    last_n = mine_candidates - (steps - 1) * batch if steps else 0       # strong scaling: the set's ragged last batch is run ragged
-
-    def run(k, ragged_last=False):
-        for i in range(k):
-            eng.run_resident(i % streams, xd, od, (i % nuniq) * batch, last_n if ragged_last and i == k - 1 else batch)
-
-    # device warm-up outside the contract's W warm-up steps: first-touch of the workspaces, clock ramp, code upload
-    device_warm = max(0, WARM_STEPS - args.warmup)
-    run(device_warm)
-    eng.sync()
-    run(args.warmup)
-    eng.sync()
-    phases = [["device warm-up + --warmup", device_warm + args.warmup]]    # forward passes launched, in order (tools/rocpd_summary.py --phases-from)
-    sampler = GpuStateSampler(local_rank)       # every rank samples ITS GPU (an 8-rank line carries eight clocks and powers)
-    legs = {}                                   # name -> (CLOCK_MONOTONIC ns at both ends) for gpu_state
-
-    def timed(name, body, finish):
-        """The contract's bracket: barrier + device sync, the body, device sync + barrier; -> this rank's seconds."""
-        group.barrier()
-        eng.sync()
-        m0, t_0 = time.monotonic_ns(), time.perf_counter()
-        body()
-        finish()
-        secs = time.perf_counter() - t_0
-        legs[name] = (m0, time.monotonic_ns())
-        group.barrier()
-        return secs
-
-    # Timed region: the plain hot path, no instrumentation.
-    eng.timing_enable(False)
-    mine_s = timed("value", lambda: run(steps, ragged_last=True), eng.sync)
-    phases.append(["timed (value), %d lanes in flight" % streams, steps])
-    if args.dump_outputs and rank == 0 and steps:      # before any later leg writes `od` again
-        dump_outputs(args.dump_outputs, eng.dataset_download(od, ((steps - 1) % nuniq) * batch, last_n))
-    elapsed = group.max_float(mine_s)          # the slowest rank defines the job time
-    per_rank_s = group.gather_floats(mine_s)
-    per_rank_steps = [int(round(v)) for v in group.gather_floats(steps)]
-    per_rank_candidates = [int(round(v)) for v in group.gather_floats(mine_candidates)]
-    rccl_ranks = int(round(sum(group.gather_floats(1.0 if group.transport == "rccl" else 0.0))))
 
     # The whole candidate set of the config, untimed by the contract: what the rate is when the run is not a handful of steps.
     full = None
@@ -599,101 +508,250 @@ def run_ranked(args, group, json_fd):
         flips = sum(key(a) != key(b) for a, b in zip(rows_g, rows_w)) if len(rows_g) == len(rows_w) else None
         concord = {"candidates": ns, "vcf_rows": len(rows_w), "gt_identical": bool(same), "gt_flips": flips}
 
-    # every rank's GPU state per leg and CPU placement, to rank 0 (bookkeeping over the bootstrap sockets; JSON text, the wire format has no floats)
     sampler.close()
-    my_state = {name: sampler.during(*span) for name, span in legs.items()}
-    my_state["source"], my_state["period_ms"] = sampler.source, sampler.period_ms
-    rank_notes = [json.loads(t_) for t_ in group.gather_objects(json.dumps({"gpu_state": my_state, "affinity": getattr(group, "affinity", None)}))]
 
     gt200k = None
     if rank == 0 and world == 1 and args.gt_candidates > 0:
         gt200k = gt_concordance_at_scale(local_rank, w, args.gt_candidates, args.gt_seconds)
         phases.append(["GT concordance at scale (a handle of its own: one slot, batch 4096)", None])
 
+    if rank != 0:
+        return {}
+    value = sum(per_rank_candidates) / elapsed
+    kflop = dict(KERNEL_FLOP)
+    if fused:
+        kflop["lstm2"] = KERNEL_FLOP["proj2"] + KERNEL_FLOP["lstm2"]
+    design = dict(DESIGN_BYTES)
+    if fused:
+        design["lstm2"] = 33 * 256 * 4 + 33 * 1024 * 4 + 33 * 256 * 4
+    pmc, pmc_note = load_pmc(batch, fused)
+    rocprof_ms = load_rocprof_ms(batch)
+    kern = {k: {"ms_mean": (round(ms / cnt, 5) if cnt else None), "launches": cnt} for k, (ms, cnt) in times.items()}
+    kern_iso = {k: round(alone_ms[k], 5) if k in alone_ms else None for k in times_iso}
+
+    def frac(flop, ms):
+        return flop / (ms * 1e-3) / 1e12 / PEAK_F16_MFMA_TFLOPS if ms else None
+
+    per_kernel = {}
+    for k in active:
+        in_ms = times[k][0] / times[k][1] if times[k][1] else None
+        fl = kflop[k] * batch
+        per_kernel[k] = {"algorithmic_flop_per_launch": fl, "in_flight_ms": round(in_ms, 5) if in_ms else None, "alone_ms": round(alone_ms[k], 5),
+                         "frac": round(frac(fl, in_ms), 4) if in_ms else None, "alone_frac": round(frac(fl, alone_ms[k]), 4),
+                         "rocprof_ms": rocprof_ms.get(k) if rocprof_ms else None,
+                         "frac_rocprof": round(frac(fl, rocprof_ms[k]), 4) if rocprof_ms and rocprof_ms.get(k) else None,
+                         "workgroups": wgs[k], "cu_share": round(cu_share[k], 4),
+                         "chip_time_share_alone": round(chip_time[k] / max(sum(chip_time.values()), 1e-12), 3),
+                         "traffic": round(pmc[k]) if pmc and k in pmc else None, "design_bytes_per_launch": design[k] * batch}
+    dom = dominant
+    # ONE duration for the dominant kernel: its mean over the timed loop repeated with HIP events on every kernel (table `kernels`,
+    # the same number as kernels[dom].in_flight_ms).  The loop with events around this kernel only is kept as `kernel_ms_with_events_on_it_only`.
+    dom_ms_mean = times[dom][0] / max(times[dom][1], 1)
+    dom_ms_only = dom_ms / max(dom_cnt, 1)
+    flop = kflop[dom] * batch
+    tf = flop / (dom_ms_mean * 1e-3) / 1e12
+    tf_alone = flop / (alone_ms[dom] * 1e-3) / 1e12
+    traffic = pmc.get(dom) if pmc else None
+    names = {"lstm1": "lstm32_kernel<true>", "proj2": "gemm_split_kernel", "lstm2": "lstm2_fused_kernel (proj2 + lstm2 in one launch)" if fused else "lstm32_kernel<false> / lstm32_pair_kernel",
+             "l4": "l3l4_kernel", "tail": "tail_kernel"}
+    roof = {
+        "bound": "mfma", "kernel": "%s (%s)" % (dom, names.get(dom, dom)), "achieved": round(tf, 2), "peak": PEAK_F16_MFMA_TFLOPS, "unit": "TFLOP/s",
+        "frac": round(tf / PEAK_F16_MFMA_TFLOPS, 4), "traffic": round(traffic) if traffic else None,
+        "traffic_source": pmc_note,
+        "definition": "dominant kernel = most chip time (stand-alone HIP-event duration x share of the 256 CUs its grid occupies) in this run's own "
+                      "table (`kernels`); frac = SURVEY.md 8(d) algorithmic FLOP of that kernel per launch (%d per candidate x batch) / its mean "
+                      "HIP-event duration with %d batches in flight (the timed loop repeated with HIP events on every kernel: the same number as "
+                      "kernels[dominant].in_flight_ms and .frac) / dense f16 MFMA peak; the rocprofv3 mean of the same kernel in the same loop is "
+                      "`kernel_ms_rocprof` when profiles/pmc_traffic.json was stamped on these kernel sources and this run has the trace's %d hardware queues" % (kflop[dom], streams, TRACE_HW_QUEUES),
+        "kernel_ms": round(dom_ms_mean, 5), "launches": times[dom][1], "algorithmic_flop_per_launch": flop,
+        "kernel_ms_with_events_on_it_only": round(dom_ms_only, 5),
+        "kernel_ms_rocprof": rocprof_ms.get(dom) if rocprof_ms else None,
+        # the same fraction from the un-instrumented duration: the kernel's rocprofv3 mean in the timed region of the committed trace of this
+        # configuration (HIP events cost marker packets in the queues: 0.143-0.166 ms with events against 0.133 ms traced, batch 1024)
+        "frac_rocprof": round(flop / (rocprof_ms[dom] * 1e-3) / 1e12 / PEAK_F16_MFMA_TFLOPS, 4) if rocprof_ms and rocprof_ms.get(dom) else None,
+        "executed_frac": round(tf * SPLIT_TERMS / PEAK_F16_MFMA_TFLOPS, 4),
+        "executed_note": "matmuls run as a 2-way fp16 split: 3 v_mfma_f32_32x32x16_f16 per algorithmic fp32 product block",
+        "alone_kernel_ms": round(alone_ms[dom], 5), "alone_frac": round(tf_alone / PEAK_F16_MFMA_TFLOPS, 4),
+        "workgroups": wgs[dom], "cu_share": round(cu_share[dom], 4),
+        "frac_of_cus_held": round(tf / PEAK_F16_MFMA_TFLOPS / max(cu_share[dom], 1e-9), 4),
+        "in_flight_note": "`frac` divides by the peak of the WHOLE chip and by a duration measured while %d forward passes share it: a launch that holds "
+                          "%d of the 256 CUs and waits for them behind the other lanes' kernels reads low by construction (3 lanes: shorter launches, lower "
+                          "throughput; profiles/r04_lanes_sweep.txt).  `frac_of_cus_held` = frac / cu_share; `alone_frac` = the same launch with the chip to "
+                          "itself; `roofline_path` = the whole pass against the same peak, which is the figure that moves with `value`" % (streams, min(wgs[dom], 256)),
+        "hbm_gbs_measured_traffic": round(traffic / (dom_ms_mean * 1e-3) / 1e9, 1) if traffic else None,
+        "hbm_frac_measured_traffic": round(traffic / (dom_ms_mean * 1e-3) / 1e9 / PEAK_HBM_GBS, 4) if traffic else None,
+        "design_bytes_per_launch": design[dom] * batch,
+        "kernels": per_kernel,
+        "value_with_events_on_this_kernel": round(steps * batch / elapsed_dom, 1),
+    }
+    path_tf = value / world * FLOP_PER_CANDIDATE / 1e12
+    out = {
+        "value_boundary": round(boundary["float32"]["value"], 1) if boundary else None,
+        "value_boundary_int16": round(boundary["int16"]["value"], 1) if boundary else None,
+        "value_full_config": round(full["value"], 1) if full else None,
+        "value_sustained": round(sustained["value"], 1) if sustained else None,
+        "value_boundary_full_config": round(boundary["float32_full"]["value"], 1) if boundary and "float32_full" in boundary else None,
+        "boundary": boundary,
+        "full_config": full,
+        "sustained": sustained,
+        "roofline": roof,
+        "roofline_path": {"achieved": round(path_tf, 2), "unit": "TFLOP/s per GPU (algorithmic, 40 386 432 FLOP / candidate)",
+                          "frac_of_f16_mfma": round(path_tf / PEAK_F16_MFMA_TFLOPS, 4),
+                          "executed_frac_of_f16_mfma": round(path_tf * SPLIT_TERMS / PEAK_F16_MFMA_TFLOPS, 4),
+                          "frac_of_fp32_mfma": round(path_tf / PEAK_FP32_MFMA_TFLOPS, 4),
+                          "algorithmic_hbm_gbs": round(value / world * BYTES_PER_CANDIDATE / 1e9, 2),
+                          "algorithmic_hbm_frac": round(value / world * BYTES_PER_CANDIDATE / 1e9 / PEAK_HBM_GBS, 6),
+                          "measured_traffic_bytes_per_candidate": round(sum(pmc[k] for k in active if k in pmc) / batch) if pmc else None,
+                          # the closest roof of the whole line: every intermediate crosses the L2 <-> fabric boundary (PMC FETCH_SIZE + WRITE_SIZE per
+                          # candidate x the sustained rate) against what a streaming copy achieves (profiles/r06_fabric_sensitivity.txt: what it costs)
+                          "fabric_tb_s": round(sum(pmc[k] for k in active if k in pmc) / batch * (sustained["value"] if sustained else value) / world / 1e12, 3) if pmc else None,
+                          "fabric_frac_of_achievable": round(sum(pmc[k] for k in active if k in pmc) / batch * (sustained["value"] if sustained else value) / world / 1e12
+                                                             / ACHIEVABLE_FABRIC_TBS, 4) if pmc else None,
+                          "fabric_achievable_tb_s": ACHIEVABLE_FABRIC_TBS,
+                          # the board is at its power cap whatever runs: what the formulation's MFMAs alone would allow
+                          "energy_bound": {"mfma_per_candidate": MFMA_PER_CANDIDATE, "nj_per_mfma": NJ_PER_MFMA, "cap_w": BOARD_CAP_W, "idle_w": BOARD_IDLE_W,
+                                           "candidates_per_s_per_gpu": round((BOARD_CAP_W - BOARD_IDLE_W) / (MFMA_PER_CANDIDATE * NJ_PER_MFMA * 1e-9), 1),
+                                           "frac": round(value / world / ((BOARD_CAP_W - BOARD_IDLE_W) / (MFMA_PER_CANDIDATE * NJ_PER_MFMA * 1e-9)), 4),
+                                           "source": "constants measured once, not in this run: profiles/r04_lstm_energy_variants.txt (nJ per v_mfma_f32_32x32x16_f16), "
+                                                     "profiles/r04_energy_by_kernel_final.txt (socket power at the cap and idle)"}},
+        "kernels_in_flight_ms": kern,
+        "kernels_alone_ms": kern_iso,
+        "parity_max_abs_err": parity,
+        "gt_concordance": concord,
+        "gt_concordance_200k": gt200k,
+    }
+    if world == 1 and not args.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(w, x, args.cpu_seconds)
+    return out
+
+
+def main():
+    args = parse_args()
+    if "WORLD_SIZE" not in os.environ and args.gpus > 1:
+        return spawn_and_relay(args)
+    # stdout carries exactly one JSON line: native libraries that print there (RCCL's start-up banner does) go to stderr
+    sys.stdout.flush()
+    json_fd = os.dup(1)
+    os.dup2(2, 1)
+    # RCCL through the C ABI when WORLD_SIZE > 1.  BENCH_SHARE_DEVICE=1 (a TEST of the multi-rank flow on a box with one GPU, never a
+    # measurement): every rank runs on device 0 and the ranks talk over the socket transport -- no rank holds an RCCL communicator, so the
+    # line says n_gpus 0 and the exit code is non-zero, as for any run without RCCL.
+    share = os.environ.get("BENCH_SHARE_DEVICE") == "1"
+    # BENCH_SHARE_TRANSPORT=rccl (with a stand-in librccl, CLAIR_AMD_RCCL_LIBRARY: real RCCL refuses two ranks on one GPU): the RCCL
+    # bring-up itself under test -- tests/test_comm_gpu.py hangs it and expects the line all the same
+    group = shard.NodeGroup(transport=os.environ.get("BENCH_SHARE_TRANSPORT", "tcp"), device=0) if share else shard.NodeGroup()
+    try:
+        rc = run_ranked(args, group, json_fd)
+    except BaseException:
+        group.close(barrier=False)     # unwinding: the peers may be gone, do not wait for them
+        raise
+    group.close()
+    if group.rccl_abandoned:           # a helper thread is still inside a hung RCCL bring-up: the line is out, do not wait for librccl's tear-down
+        group.exit_process(rc)
+    return rc
+
+
+def run_ranked(args, group, json_fd):
+    t_start = time.perf_counter()
+    rank, world, local_rank = group.rank, group.world, group.device          # the HIP device of this rank (= LOCAL_RANK unless BENCH_SHARE_DEVICE)
+    if world != args.gpus and rank == 0:
+        sys.stderr.write("bench.py: --gpus %d but the launcher started %d rank(s); reporting n_gpus=%d\n" % (args.gpus, world, world))
+
+    batch, streams = args.batch, max(1, args.streams)
+    w = weights.synthetic_weights(seed=20250928, head_gain=4.0) if rank == 0 else None
+    if world > 1:
+        w = group.broadcast_weights(w, root=0)          # 9.5 MB over RCCL, once
+    eng = _capi.Engine(device=local_rank, max_batch=batch, n_slots=streams)
+    eng.load_weights(w)
+
+    steps = args.steps
+    mine_candidates = args.steps * batch
+    stands_for = None
+    if args.scaling == "strong":
+        as_rank, as_world = rank, world
+        if args.shard_of:
+            if world != 1:
+                raise SystemExit("--shard-of runs one rank's block on one GPU: use it with --gpus 1")
+            try:
+                as_rank, as_world = (int(v) for v in args.shard_of.split("/"))
+            except ValueError:
+                raise SystemExit("--shard-of takes R/W (two integers), not %r" % args.shard_of)
+            if not 0 <= as_rank < as_world:
+                raise SystemExit("--shard-of R/W needs 0 <= R < W")
+            stands_for = {"rank": as_rank, "world": as_world, "of_candidates": args.candidates}
+        first_candidate, mine_candidates = shard.shard_batches(args.candidates, batch, as_rank, as_world)
+        if stands_for:
+            stands_for["first_candidate"] = first_candidate
+        steps = (mine_candidates + batch - 1) // batch
+    steps_max = int(round(group.max_float(steps)))
+    nuniq = max(1, min(args.unique_batches, steps_max + args.warmup))
+    x, infos = synth.synthetic_input(nuniq * batch, args.platform, seed=20250928 + rank)
+    xd, od = eng.dataset_alloc(nuniq * batch)
+    eng.dataset_upload(xd, 0, x)
+    last_n = mine_candidates - (steps - 1) * batch if steps else 0       # strong scaling: the set's ragged last batch is run ragged
+
+    def run(k, ragged_last=False):
+        for i in range(k):
+            eng.run_resident(i % streams, xd, od, (i % nuniq) * batch, last_n if ragged_last and i == k - 1 else batch)
+
+    # device warm-up outside the contract's W warm-up steps: first-touch of the workspaces, clock ramp, code upload
+    device_warm = max(0, WARM_STEPS - args.warmup)
+    run(device_warm)
+    eng.sync()
+    run(args.warmup)
+    eng.sync()
+    phases = [["device warm-up + --warmup", device_warm + args.warmup]]    # forward passes launched, in order (tools/rocpd_summary.py --phases-from)
+    # every rank samples ITS GPU (an 8-rank line carries eight clocks and powers); only --full reports the samples.  Started in every run all
+    # the same: the timed steps have always followed its start, and a short burst's rate depends on what precedes it (20 steps without it:
+    # ~5 % slower), so the contract's timed region keeps its conditions
+    sampler = GpuStateSampler(local_rank)
+    legs = {}                                   # name -> (CLOCK_MONOTONIC ns at both ends) for gpu_state
+
+    def timed(name, body, finish):
+        """The contract's bracket: barrier + device sync, the body, device sync + barrier; -> this rank's seconds."""
+        group.barrier()
+        eng.sync()
+        m0, t_0 = time.monotonic_ns(), time.perf_counter()
+        body()
+        finish()
+        secs = time.perf_counter() - t_0
+        legs[name] = (m0, time.monotonic_ns())
+        group.barrier()
+        return secs
+
+    # Timed region: the plain hot path, no instrumentation.
+    eng.timing_enable(False)
+    mine_s = timed("value", lambda: run(steps, ragged_last=True), eng.sync)
+    phases.append(["timed (value), %d lanes in flight" % streams, steps])
+    if args.dump_outputs and rank == 0 and steps:      # before any later leg writes `od` again
+        dump_outputs(args.dump_outputs, eng.dataset_download(od, ((steps - 1) % nuniq) * batch, last_n))
+    elapsed = group.max_float(mine_s)          # the slowest rank defines the job time
+    per_rank_s = group.gather_floats(mine_s)
+    per_rank_steps = [int(round(v)) for v in group.gather_floats(steps)]
+    per_rank_candidates = [int(round(v)) for v in group.gather_floats(mine_candidates)]
+    rccl_ranks = int(round(sum(group.gather_floats(1.0 if group.transport == "rccl" else 0.0))))
+    extra = full_legs(args, group, eng, w, x, infos, xd, od, nuniq, steps, elapsed, per_rank_candidates, run, timed, phases, sampler) if args.full else None
+    # every rank's GPU state per leg and CPU placement, to rank 0 (bookkeeping over the bootstrap sockets; JSON text, the wire format has no floats)
+    my_state = None
+    if args.full:                              # full_legs closed the sampler after its last GPU leg
+        my_state = {name: sampler.during(*span) for name, span in legs.items()}
+        my_state["source"], my_state["period_ms"] = sampler.source, sampler.period_ms
+    else:
+        sampler.close()
+    rank_notes = [json.loads(t_) for t_ in group.gather_objects(json.dumps({"gpu_state": my_state, "affinity": getattr(group, "affinity", None)}))]
+
     rc = 0
     if rank == 0:
         total = sum(per_rank_candidates)          # real candidates: a shard's ragged last batch counts what it holds
         value = total / elapsed
-        kflop = dict(KERNEL_FLOP)
-        if fused:
-            kflop["lstm2"] = KERNEL_FLOP["proj2"] + KERNEL_FLOP["lstm2"]
-        design = dict(DESIGN_BYTES)
-        if fused:
-            design["lstm2"] = 33 * 256 * 4 + 33 * 1024 * 4 + 33 * 256 * 4
-        pmc, pmc_note = load_pmc(batch, fused)
-        rocprof_ms = load_rocprof_ms(batch)
-        kern = {k: {"ms_mean": (round(ms / cnt, 5) if cnt else None), "launches": cnt} for k, (ms, cnt) in times.items()}
-        kern_iso = {k: round(alone_ms[k], 5) if k in alone_ms else None for k in times_iso}
-
-        def frac(flop, ms):
-            return flop / (ms * 1e-3) / 1e12 / PEAK_F16_MFMA_TFLOPS if ms else None
-
-        per_kernel = {}
-        for k in active:
-            in_ms = times[k][0] / times[k][1] if times[k][1] else None
-            fl = kflop[k] * batch
-            per_kernel[k] = {"algorithmic_flop_per_launch": fl, "in_flight_ms": round(in_ms, 5) if in_ms else None, "alone_ms": round(alone_ms[k], 5),
-                             "frac": round(frac(fl, in_ms), 4) if in_ms else None, "alone_frac": round(frac(fl, alone_ms[k]), 4),
-                             "rocprof_ms": rocprof_ms.get(k) if rocprof_ms else None,
-                             "frac_rocprof": round(frac(fl, rocprof_ms[k]), 4) if rocprof_ms and rocprof_ms.get(k) else None,
-                             "workgroups": wgs[k], "cu_share": round(cu_share[k], 4),
-                             "chip_time_share_alone": round(chip_time[k] / max(sum(chip_time.values()), 1e-12), 3),
-                             "traffic": round(pmc[k]) if pmc and k in pmc else None, "design_bytes_per_launch": design[k] * batch}
-        dom = dominant
-        # ONE duration for the dominant kernel: its mean over the timed loop repeated with HIP events on every kernel (table `kernels`,
-        # the same number as kernels[dom].in_flight_ms).  The loop with events around this kernel only is kept as `kernel_ms_with_events_on_it_only`.
-        dom_ms_mean = times[dom][0] / max(times[dom][1], 1)
-        dom_ms_only = dom_ms / max(dom_cnt, 1)
-        flop = kflop[dom] * batch
-        tf = flop / (dom_ms_mean * 1e-3) / 1e12
-        tf_alone = flop / (alone_ms[dom] * 1e-3) / 1e12
-        traffic = pmc.get(dom) if pmc else None
-        names = {"lstm1": "lstm32_kernel<true>", "proj2": "gemm_split_kernel", "lstm2": "lstm2_fused_kernel (proj2 + lstm2 in one launch)" if fused else "lstm32_kernel<false> / lstm32_pair_kernel",
-                 "l4": "l3l4_kernel", "tail": "tail_kernel"}
-        roof = {
-            "bound": "mfma", "kernel": "%s (%s)" % (dom, names.get(dom, dom)), "achieved": round(tf, 2), "peak": PEAK_F16_MFMA_TFLOPS, "unit": "TFLOP/s",
-            "frac": round(tf / PEAK_F16_MFMA_TFLOPS, 4), "traffic": round(traffic) if traffic else None,
-            "traffic_source": pmc_note,
-            "definition": "dominant kernel = most chip time (stand-alone HIP-event duration x share of the 256 CUs its grid occupies) in this run's own "
-                          "table (`kernels`); frac = SURVEY.md 8(d) algorithmic FLOP of that kernel per launch (%d per candidate x batch) / its mean "
-                          "HIP-event duration with %d batches in flight (the timed loop repeated with HIP events on every kernel: the same number as "
-                          "kernels[dominant].in_flight_ms and .frac) / dense f16 MFMA peak; the rocprofv3 mean of the same kernel in the same loop is "
-                          "`kernel_ms_rocprof` when profiles/pmc_traffic.json was stamped on these kernel sources and this run has the trace's %d hardware queues" % (kflop[dom], streams, TRACE_HW_QUEUES),
-            "kernel_ms": round(dom_ms_mean, 5), "launches": times[dom][1], "algorithmic_flop_per_launch": flop,
-            "kernel_ms_with_events_on_it_only": round(dom_ms_only, 5),
-            "kernel_ms_rocprof": rocprof_ms.get(dom) if rocprof_ms else None,
-            # the same fraction from the un-instrumented duration: the kernel's rocprofv3 mean in the timed region of the committed trace of this
-            # configuration (HIP events cost marker packets in the queues: 0.143-0.166 ms with events against 0.133 ms traced, batch 1024)
-            "frac_rocprof": round(flop / (rocprof_ms[dom] * 1e-3) / 1e12 / PEAK_F16_MFMA_TFLOPS, 4) if rocprof_ms and rocprof_ms.get(dom) else None,
-            "executed_frac": round(tf * SPLIT_TERMS / PEAK_F16_MFMA_TFLOPS, 4),
-            "executed_note": "matmuls run as a 2-way fp16 split: 3 v_mfma_f32_32x32x16_f16 per algorithmic fp32 product block",
-            "alone_kernel_ms": round(alone_ms[dom], 5), "alone_frac": round(tf_alone / PEAK_F16_MFMA_TFLOPS, 4),
-            "workgroups": wgs[dom], "cu_share": round(cu_share[dom], 4),
-            "frac_of_cus_held": round(tf / PEAK_F16_MFMA_TFLOPS / max(cu_share[dom], 1e-9), 4),
-            "in_flight_note": "`frac` divides by the peak of the WHOLE chip and by a duration measured while %d forward passes share it: a launch that holds "
-                              "%d of the 256 CUs and waits for them behind the other lanes' kernels reads low by construction (3 lanes: shorter launches, lower "
-                              "throughput; profiles/r04_lanes_sweep.txt).  `frac_of_cus_held` = frac / cu_share; `alone_frac` = the same launch with the chip to "
-                              "itself; `roofline_path` = the whole pass against the same peak, which is the figure that moves with `value`" % (streams, min(wgs[dom], 256)),
-            "hbm_gbs_measured_traffic": round(traffic / (dom_ms_mean * 1e-3) / 1e9, 1) if traffic else None,
-            "hbm_frac_measured_traffic": round(traffic / (dom_ms_mean * 1e-3) / 1e9 / PEAK_HBM_GBS, 4) if traffic else None,
-            "design_bytes_per_launch": design[dom] * batch,
-            "kernels": per_kernel,
-            "value_with_events_on_this_kernel": round(steps * batch / elapsed_dom, 1),
-        }
-        path_tf = value / world * FLOP_PER_CANDIDATE / 1e12
         n_gpus = rccl_ranks if world > 1 else 1
         if world > 1 and rccl_ranks != world:
             sys.stderr.write("bench.py: %d of %d ranks hold an RCCL communicator; reporting n_gpus=%d\n" % (rccl_ranks, world, rccl_ranks))
             rc = 1
-        gpu_state = rank_notes[0]["gpu_state"]
+        full, sustained = (extra or {}).get("full_config"), (extra or {}).get("sustained")
         out = {
             "metric": "candidate sites/sec (whole node)",
             "value": round(value, 1),
-            "value_boundary": round(boundary["float32"]["value"], 1) if boundary else None,
-            "value_boundary_int16": round(boundary["int16"]["value"], 1) if boundary else None,
-            "value_full_config": round(full["value"], 1) if full else None,
-            "value_sustained": round(sustained["value"], 1) if sustained else None,
-            "value_boundary_full_config": round(boundary["float32_full"]["value"], 1) if boundary and "float32_full" in boundary else None,
             "unit": "candidates/s",
             "n_gpus": n_gpus,
             "steps": steps_max,
@@ -720,42 +778,15 @@ def run_ranked(args, group, json_fd):
                        "transport": group.transport, "ranks_with_rccl_communicator": rccl_ranks if world > 1 else None,
                        "rccl_failure": getattr(group, "rccl_failure", None)},
             "per_rank": [{"rank": r if not stands_for else stands_for["rank"], "steps": s_, "candidates": c_, "seconds": round(t_, 6), "candidates_per_s": round(c_ / t_, 1) if t_ > 0 else None,
-                          "affinity": rank_notes[r]["affinity"], "gpu_state": rank_notes[r]["gpu_state"] if world > 1 else "see gpu_state"}
+                          "affinity": rank_notes[r]["affinity"],
+                          "gpu_state": None if extra is None else rank_notes[r]["gpu_state"] if world > 1 else "see gpu_state"}
                          for r, (s_, c_, t_) in enumerate(zip(per_rank_steps, per_rank_candidates, per_rank_s))],
-            "boundary": boundary,
-            "full_config": full,
-            "sustained": sustained,
-            "gpu_state": gpu_state,
             "launch_phases": phases,
-            "roofline": roof,
-            "roofline_path": {"achieved": round(path_tf, 2), "unit": "TFLOP/s per GPU (algorithmic, 40 386 432 FLOP / candidate)",
-                              "frac_of_f16_mfma": round(path_tf / PEAK_F16_MFMA_TFLOPS, 4),
-                              "executed_frac_of_f16_mfma": round(path_tf * SPLIT_TERMS / PEAK_F16_MFMA_TFLOPS, 4),
-                              "frac_of_fp32_mfma": round(path_tf / PEAK_FP32_MFMA_TFLOPS, 4),
-                              "algorithmic_hbm_gbs": round(value / world * BYTES_PER_CANDIDATE / 1e9, 2),
-                              "algorithmic_hbm_frac": round(value / world * BYTES_PER_CANDIDATE / 1e9 / PEAK_HBM_GBS, 6),
-                              "measured_traffic_bytes_per_candidate": round(sum(pmc[k] for k in active if k in pmc) / batch) if pmc else None,
-                              # the closest roof of the whole line: every intermediate crosses the L2 <-> fabric boundary (PMC FETCH_SIZE + WRITE_SIZE per
-                              # candidate x the sustained rate) against what a streaming copy achieves (profiles/r06_fabric_sensitivity.txt: what it costs)
-                              "fabric_tb_s": round(sum(pmc[k] for k in active if k in pmc) / batch * (sustained["value"] if sustained else value) / world / 1e12, 3) if pmc else None,
-                              "fabric_frac_of_achievable": round(sum(pmc[k] for k in active if k in pmc) / batch * (sustained["value"] if sustained else value) / world / 1e12
-                                                                 / ACHIEVABLE_FABRIC_TBS, 4) if pmc else None,
-                              "fabric_achievable_tb_s": ACHIEVABLE_FABRIC_TBS,
-                              # the board is at its power cap whatever runs: what the formulation's MFMAs alone would allow
-                              "energy_bound": {"mfma_per_candidate": MFMA_PER_CANDIDATE, "nj_per_mfma": NJ_PER_MFMA, "cap_w": BOARD_CAP_W, "idle_w": BOARD_IDLE_W,
-                                               "candidates_per_s_per_gpu": round((BOARD_CAP_W - BOARD_IDLE_W) / (MFMA_PER_CANDIDATE * NJ_PER_MFMA * 1e-9), 1),
-                                               "frac": round(value / world / ((BOARD_CAP_W - BOARD_IDLE_W) / (MFMA_PER_CANDIDATE * NJ_PER_MFMA * 1e-9)), 4),
-                                               "source": "constants measured once, not in this run: profiles/r04_lstm_energy_variants.txt (nJ per v_mfma_f32_32x32x16_f16), "
-                                                         "profiles/r04_energy_by_kernel_final.txt (socket power at the cap and idle)"}},
-            "kernels_in_flight_ms": kern,
-            "kernels_alone_ms": kern_iso,
-            "parity_max_abs_err": parity,
-            "gt_concordance": concord,
-            "gt_concordance_200k": gt200k,
         }
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(w, x, args.cpu_seconds)
-        out["bench_wall_s"] = round(time.perf_counter() - t_start, 1)       # of which gt_concordance_200k.seconds and ~17 s of cpu_baseline are host work on the oracle / port
+        if extra is not None:                    # --full
+            out["gpu_state"] = rank_notes[0]["gpu_state"]
+            out.update(extra)
+        out["bench_wall_s"] = round(time.perf_counter() - t_start, 1)       # under --full, gt_concordance_200k.seconds and ~17 s of cpu_baseline of it are host work on the oracle / port
         os.write(json_fd, (json.dumps(out) + "\n").encode())
 
     eng.dataset_free(xd, od)

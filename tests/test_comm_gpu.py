@@ -51,7 +51,7 @@ def test_bench_under_torch_distributed_run_one_rank_and_own_spawner(tmp_path):
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
-    tail = ["bench.py", "--gpus", "1", "--steps", "12", "--warmup", "2", "--no-cpu-baseline", "--gt-candidates", "0", "--sustained-seconds", "0.2"]
+    tail = ["bench.py", "--gpus", "1", "--steps", "12", "--warmup", "2", "--full", "--no-cpu-baseline", "--gt-candidates", "0", "--sustained-seconds", "0.2"]
     for cmd in ([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                  "--master-port", str(port)] + tail, [sys.executable] + tail):
         r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
@@ -74,7 +74,7 @@ def test_bench_two_ranks_share_the_one_gpu_over_the_socket_transport():
     from clair_amd import shard
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, BENCH_WARM_STEPS="16", BENCH_SHARE_DEVICE="1", CLAIR_AMD_BIND="1")
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "40", "--warmup", "4", "--no-cpu-baseline", "--gt-candidates", "0",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "40", "--warmup", "4", "--full", "--no-cpu-baseline", "--gt-candidates", "0",
            "--sustained-seconds", "0.3", "--full-candidates", "8192"]
     procs = shard.spawn_ranks(cmd, 2, env=env, stderr_pipe=True)
     out, errs, rcs = _collect(procs, 600)
@@ -171,7 +171,7 @@ def test_bench_prints_its_two_rank_line_although_the_rccl_bring_up_hangs(tmp_pat
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, BENCH_WARM_STEPS="16", BENCH_SHARE_DEVICE="1", BENCH_SHARE_TRANSPORT="rccl", CLAIR_AMD_RCCL_LIBRARY=_fake_rccl(tmp_path),
                CLAIR_FAKE_RCCL_HANG="all", CLAIR_AMD_RCCL_INIT_TIMEOUT="3")
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "4", "--no-cpu-baseline", "--gt-candidates", "0",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "4", "--full", "--no-cpu-baseline", "--gt-candidates", "0",
            "--sustained-seconds", "0.2", "--full-candidates", "4096", "--boundary-slots", "0"]
     t0 = time.time()
     procs = shard.spawn_ranks(cmd, 2, env=env, stderr_pipe=True)

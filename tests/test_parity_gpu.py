@@ -479,7 +479,7 @@ def test_submit_counts_equals_submit_on_the_float_tensor(engine):
 
 
 def test_bench_prints_one_json_line_with_the_contract_fields():
-    """`python bench.py --steps K --warmup W`: exactly one JSON line on stdout carrying the driver's contract fields plus
+    """`python bench.py --steps K --warmup W --full`: exactly one JSON line on stdout carrying the driver's contract fields plus
     `roofline` and `cpu_baseline` (short run: few steps, 2 s of CPU baseline)."""
     import json
     import os
@@ -487,7 +487,7 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, BENCH_WARM_STEPS="16")
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "24", "--warmup", "4", "--cpu-seconds", "2", "--gt-candidates", "6000", "--sustained-seconds", "0.3"], cwd=root, env=env,
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "24", "--warmup", "4", "--full", "--cpu-seconds", "2", "--gt-candidates", "6000", "--sustained-seconds", "0.3"], cwd=root, env=env,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -570,6 +570,29 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
         near = plat["near_ties"]
         assert sorted(near) == ["eps_0", "eps_1e-05", "eps_3e-06"] and near["eps_0"] <= near["eps_3e-06"] <= near["eps_1e-05"] < 600
     assert d["per_rank"][0]["affinity"] is None             # one rank: placed by the launcher, as before
+
+
+def test_bench_plain_run_prints_the_contract_line_and_runs_no_other_leg():
+    """`python bench.py --gpus 1 --steps K --warmup W` without --full: set up, warm up, time the K steps, print the line -- the contract
+    fields, config, per_rank and launch_phases; none of the legs, tables or checks --full adds."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, BENCH_WARM_STEPS="16")
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "24", "--warmup", "4"], cwd=root, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 24 and d["warmup"] == 4 and d["n_gpus"] == 1 and d["higher_is_better"] is True and d["unit"] == "candidates/s"
+    assert d["value"] > 1e6 and abs(d["value"] - 24 * d["config"]["batch"] / (d["ms_per_step"] * 24e-3)) < 0.01 * d["value"]
+    assert d["dtype"].startswith("f32") and d["metric"] == "candidate sites/sec (whole node)" and d["config"]["device_warm_steps"] == 12
+    for key in ("boundary", "full_config", "sustained", "gpu_state", "roofline", "roofline_path", "kernels_in_flight_ms", "kernels_alone_ms",
+                "parity_max_abs_err", "gt_concordance", "gt_concordance_200k", "cpu_baseline", "value_boundary", "value_sustained"):
+        assert key not in d, key
+    assert [n for _, n in d["launch_phases"]] == [12 + 4, 24] and d["per_rank"][0]["gpu_state"] is None
 
 
 def test_bench_strong_scaling_counts_one_ranks_share_of_the_whole_genome_set():
@@ -837,7 +860,7 @@ def test_bench_runs_one_ranks_block_of_the_eight_gpu_illumina_config():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, BENCH_WARM_STEPS="16")
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--scaling", "strong", "--candidates", "1000000", "--shard-of", "7/8", "--platform", "illumina", "--batch", "8192",
-                        "--warmup", "2", "--no-cpu-baseline", "--gt-candidates", "0"], cwd=root, env=env, capture_output=True, text=True, timeout=900)
+                        "--warmup", "2", "--full", "--no-cpu-baseline", "--gt-candidates", "0"], cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.strip()][0])
     first, mine = shard.shard_batches(1000000, 8192, 7, 8)

@@ -471,7 +471,7 @@ BENCH_WORKER = textwrap.dedent("""
         def kernel_workgroups(self, n): return dict(proj1=0, lstm1=64, proj2=128, lstm2=64, l3=0, l4=512, tail=64, decode=256)
         def dataset_download(self, od, first, n): return np.concatenate(c_oracle.forward(self.w, self.x[first:first + n]), axis=1)
         def dataset_free(self, xd, od): pass
-        def close(self): pass
+        def close(self): sys.stderr.write("stand-in engine: %%d resident runs\\n" %% self.runs)
 
     _capi.Engine = FakeEngine
     sys.argv = ["bench.py"] + %(args)r
@@ -479,10 +479,10 @@ BENCH_WORKER = textwrap.dedent("""
 """)
 
 
-@pytest.mark.parametrize("args,total", [(["--gpus", "2", "--steps", "6", "--warmup", "2", "--batch", "64", "--no-cpu-baseline", "--full-candidates", "640", "--sustained-seconds", "0.05"], 2 * 6 * 64),
-                                        (["--gpus", "2", "--scaling", "strong", "--candidates", "1000", "--batch", "64", "--warmup", "1", "--no-cpu-baseline"], 1000),
-                                        (["--gpus", "8", "--steps", "3", "--warmup", "1", "--batch", "32", "--no-cpu-baseline", "--full-candidates", "96", "--sustained-seconds", "0.02"], 8 * 3 * 32),
-                                        (["--gpus", "8", "--scaling", "strong", "--candidates", "1000", "--batch", "64", "--warmup", "1", "--no-cpu-baseline"], 1000)],
+@pytest.mark.parametrize("args,total", [(["--gpus", "2", "--steps", "6", "--warmup", "2", "--batch", "64", "--full", "--no-cpu-baseline", "--full-candidates", "640", "--sustained-seconds", "0.05"], 2 * 6 * 64),
+                                        (["--gpus", "2", "--scaling", "strong", "--candidates", "1000", "--batch", "64", "--warmup", "1", "--full", "--no-cpu-baseline"], 1000),
+                                        (["--gpus", "8", "--steps", "3", "--warmup", "1", "--batch", "32", "--full", "--no-cpu-baseline", "--full-candidates", "96", "--sustained-seconds", "0.02"], 8 * 3 * 32),
+                                        (["--gpus", "8", "--scaling", "strong", "--candidates", "1000", "--batch", "64", "--warmup", "1", "--full", "--no-cpu-baseline"], 1000)],
                          ids=["weak-2", "strong-2", "weak-8", "strong-8"])
 def test_bench_two_rank_flow_with_a_stand_in_engine(tmp_path, args, total):
     """bench.py's multi-rank bookkeeping on two CPU ranks (the engine replaced by the oracle, the sockets as transport): one JSON line from
@@ -526,6 +526,34 @@ def test_bench_two_rank_flow_with_a_stand_in_engine(tmp_path, args, total):
         assert set(d["config"]["rates"]) == {"value", "value_full_config", "value_sustained"} and all(d["config"]["rates"].values())
         assert "value_full_config" in d["gpu_state"] and "value_boundary_float32_full" in d["gpu_state"]
     assert set(d["gpu_state"]["value"]) == {"sclk_mhz", "power_w", "samples"} and "value_boundary" in d["gpu_state"]
+
+
+@pytest.mark.parametrize("args,runs", [(["--gpus", "2", "--steps", "6", "--warmup", "2", "--batch", "64"], 2 + 6),
+                                       (["--gpus", "2", "--scaling", "strong", "--candidates", "1000", "--batch", "64", "--warmup", "1"], 1 + 8)],
+                         ids=["weak-2", "strong-2"])
+def test_bench_plain_run_times_its_steps_and_nothing_else(tmp_path, args, runs):
+    """Without --full a run sets up, warms up, times its steps and prints the line: the contract fields, config, per_rank and
+    launch_phases, none of the later legs' fields -- and no rank launches a forward pass beyond --warmup + the timed steps."""
+    import json
+    script = tmp_path / "worker.py"
+    script.write_text(BENCH_WORKER % {"root": ROOT, "args": args})
+    env = dict(os.environ, BENCH_WARM_STEPS="0", OMP_NUM_THREADS="2")
+    procs = shard.spawn_ranks([sys.executable, str(script)], 2, env=env, stderr_pipe=True)
+    out = procs[0].stdout.read().decode()
+    errs = [p.stderr.read().decode() for p in procs]
+    rcs = [p.wait(timeout=600) for p in procs]
+    assert rcs == [1, 0], errs
+    lines = [ln for ln in out.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "scaling", "config", "per_rank"} <= set(d)
+    for key in ("boundary", "full_config", "sustained", "gpu_state", "roofline", "roofline_path", "kernels_in_flight_ms", "parity_max_abs_err",
+                "gt_concordance", "gt_concordance_200k", "cpu_baseline", "value_boundary", "value_sustained", "value_full_config"):
+        assert key not in d, key
+    assert d["value"] > 0 and d["config"]["candidates_total"] == sum(r["candidates"] for r in d["per_rank"]) and d["n_gpus"] == 0
+    assert all(r["gpu_state"] is None and r["affinity"]["pci"] is None for r in d["per_rank"])
+    assert [n for _, n in d["launch_phases"]] == [int(args[args.index("--warmup") + 1]), d["steps"]]
+    assert all("stand-in engine: %d resident runs" % runs in e for e in errs), errs
 
 
 def _fake_sysfs(root, devices, nodes):

@@ -16,7 +16,7 @@ while [ $i -le $ROUNDS ]; do
     lib=${rest%%,*}; envs=""
     case $rest in *,*) envs=$(echo "${rest#*,}" | tr ',' ' ');; esac
     [ "$lib" = "-" ] && libenv="" || libenv="CLAIR_AMD_LIB=$PWD/$lib"
-    out=$(env $libenv $envs timeout 300 python bench.py $ARGS --no-cpu-baseline --gt-candidates 0 --full-candidates 0 $BOUNDARY 2>/dev/null | python -c "
+    out=$(env $libenv $envs timeout 300 python bench.py --full $ARGS --no-cpu-baseline --gt-candidates 0 --full-candidates 0 $BOUNDARY 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 g=d['gpu_state'].get('value_sustained') or d['gpu_state'].get('value') or {}

@@ -11,7 +11,7 @@ B=${1:-1024}
 O=gpurun_out/r04_energy_by_kernel.txt
 mkdir -p gpurun_out
 run() {   # name mask steps
-  CLAIR_AMD_LIB=$PWD/exp/libclair_ablate.so CLAIR_ABLATE=$2 timeout 200 python bench.py --batch $B --steps $3 --warmup 8 --no-cpu-baseline --boundary-slots 0 --full-candidates 0 > /tmp/e_$1.json 2>/tmp/e_$1.err
+  CLAIR_AMD_LIB=$PWD/exp/libclair_ablate.so CLAIR_ABLATE=$2 timeout 200 python bench.py --full --batch $B --steps $3 --warmup 8 --no-cpu-baseline --boundary-slots 0 --full-candidates 0 > /tmp/e_$1.json 2>/tmp/e_$1.err
   python - "$1" "$2" <<'PY'
 import json, sys
 name, mask = sys.argv[1], int(sys.argv[2])

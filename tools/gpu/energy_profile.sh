@@ -7,7 +7,7 @@ B=${1:-1024}
 echo "idle:"; rocm-smi --showpower --showclocks 2>/dev/null | grep -E "Power|sclk"
 for cfg in "all 0 40000" "lstm1 108 160000" "proj2 106 160000" "lstm2 102 155000" "l3l4 78 250000" "tail 46 600000" "rec 100 90000" "lstm1+proj2 104 65000" "dense 14 200000"; do
   set -- $cfg
-  (CLAIR_AMD_LIB=$PWD/exp/libclair_ablate.so CLAIR_ABLATE=$2 timeout 200 python bench.py --batch $B --steps $3 --warmup 8 --no-cpu-baseline > /tmp/e_$1.json 2>/dev/null) &
+  (CLAIR_AMD_LIB=$PWD/exp/libclair_ablate.so CLAIR_ABLATE=$2 timeout 200 python bench.py --full --batch $B --steps $3 --warmup 8 --no-cpu-baseline > /tmp/e_$1.json 2>/dev/null) &
   BP=$!
   sleep ${WAIT:-6}
   P=""; S=""

@@ -9,7 +9,7 @@
 cd "$(dirname "$0")/../.."
 OUT=${1:-gpurun_out/r06_fabric_sensitivity.txt}
 [ -x tools/ubench/hbm_hog ] || /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 tools/ubench/hbm_hog.hip -o tools/ubench/hbm_hog
-BENCH="python bench.py --steps 200 --warmup 8 --sustained-seconds 3 --no-cpu-baseline --gt-candidates 0 --full-candidates 0 --boundary-slots 0"
+BENCH="python bench.py --full --steps 200 --warmup 8 --sustained-seconds 3 --no-cpu-baseline --gt-candidates 0 --full-candidates 0 --boundary-slots 0"
 line() {
   python -c "
 import json,sys

@@ -38,7 +38,7 @@ fi
 O=gpurun_out/r04_lstm_energy_variants.txt
 mkdir -p gpurun_out
 run() {   # variant kernel-name mask
-  CLAIR_AMD_LIB=$PWD/exp/libclair_e_$1.so CLAIR_ABLATE=$3 timeout 200 python bench.py --steps 160000 --warmup 8 --no-cpu-baseline --boundary-slots 0 --full-candidates 0 > /tmp/ev.json 2>/tmp/ev.err
+  CLAIR_AMD_LIB=$PWD/exp/libclair_e_$1.so CLAIR_ABLATE=$3 timeout 200 python bench.py --full --steps 160000 --warmup 8 --no-cpu-baseline --boundary-slots 0 --full-candidates 0 > /tmp/ev.json 2>/tmp/ev.err
   python - "$1" "$2" <<'PY'
 import json, sys
 try:

@@ -14,7 +14,7 @@ if [ "$1" = build ]; then
 fi
 for i in 1 2 3; do
   for lib in clair_amd/libclair_amd.so exp/libclair_release.so; do
-    v=$(CLAIR_AMD_LIB=$PWD/$lib timeout 200 python bench.py --streams 1 --steps 600 --warmup 8 --no-cpu-baseline --boundary-slots 0 --full-candidates 0 2>/dev/null | python -c "
+    v=$(CLAIR_AMD_LIB=$PWD/$lib timeout 200 python bench.py --full --streams 1 --steps 600 --warmup 8 --no-cpu-baseline --boundary-slots 0 --full-candidates 0 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], {k: round(v['ms_mean'], 4) for k, v in d['kernels_in_flight_ms'].items() if (v['ms_mean'] or 0) > 0.001})")
     echo "one slot, fused layer 2, $lib: $v"

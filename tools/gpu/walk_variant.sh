@@ -19,7 +19,7 @@ if [ "$1" = build ]; then
   exit $?
 fi
 one() {   # label, lib, lanes
-  v=$(CLAIR_AMD_LIB=$PWD/$2 CLAIR_AMD_LANES=$3 timeout 200 python bench.py --streams $3 --steps 2000 --warmup 8 --no-cpu-baseline --boundary-slots 0 --full-candidates 0 2>/dev/null | python -c "
+  v=$(CLAIR_AMD_LIB=$PWD/$2 CLAIR_AMD_LANES=$3 timeout 200 python bench.py --full --streams $3 --steps 2000 --warmup 8 --no-cpu-baseline --boundary-slots 0 --full-candidates 0 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], {k: round(v['ms_mean'], 4) for k, v in d['kernels_in_flight_ms'].items() if (v['ms_mean'] or 0) > 0.001}, 'alone', {k: v for k, v in d['kernels_alone_ms'].items() if v})")
   echo "$1: $v"
