@@ -9,8 +9,10 @@ SUBMODULES = {
     "callVarBamParallel": "clair_amd.callVarBamParallel",
     "CreateTensor": "clair_amd.create_tensor",
     "ExtractVariantCandidates": "clair_amd.extract_variant_candidates",
+    "GetTruth": "clair_amd.get_truth",
+    "evaluate": "clair_amd.evaluate",
 }
-NOT_COVERED = ("evaluate", "plot_tensor", "train", "train_clr", "GetTruth", "PairWithNonVariants", "Tensor2Bin", "CombineBins",
+NOT_COVERED = ("plot_tensor", "train", "train_clr", "PairWithNonVariants", "Tensor2Bin", "CombineBins",
                "Bin2To3", "ensemble", "overlap_variant")
 
 
@@ -21,7 +23,7 @@ def main():
         sys.exit(0)
     name = sys.argv[1]
     if name in NOT_COVERED:
-        sys.exit("[ERROR] Submodule %s is outside this build (variant calling only: %s)." % (name, ", ".join(SUBMODULES)))
+        sys.exit("[ERROR] Submodule %s is outside this build (variant calling and evaluation only: %s)." % (name, ", ".join(SUBMODULES)))
     if name not in SUBMODULES:
         sys.exit("[ERROR] Submodule %s not found." % name)
     sys.argv = sys.argv[1:]          # the submodule parses its own options, as under the reference's dispatcher

@@ -28,7 +28,9 @@ SYMBOLS = (
     "clair_frontend_build_windows_ex", "clair_frontend_window_info", "clair_frontend_window_counts", "clair_frontend_counts_device", "clair_frontend_budget_inputs",
     "clair_frontend_stats", "clair_frontend_text_options", "clair_frontend_add_text", "clair_frontend_text_stats", "clair_frontend_slab_reads",
     "clair_frontend_bam_options", "clair_frontend_add_bam",
+    "clair_eval_reset", "clair_submit_eval", "clair_eval", "clair_eval_read",
 )
+EVAL_COUNTS = 3 + 21 * 21 + 3 * 3 + 33 * 33 + 33 * 33      # CLAIR_EVAL_COUNTS: all, top1, top2, gt21, genotype, len1, len2
 KERNEL_NAMES = ("proj1", "lstm1", "proj2", "lstm2", "l3", "l4", "tail", "decode")
 
 _lib = None
@@ -79,6 +81,11 @@ def load(path=None):
         lib.clair_decode.argtypes = [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp]
         lib.clair_pinned_alloc.argtypes = [c_vp, c_i64, ctypes.POINTER(c_vp)]
         lib.clair_pinned_free.argtypes = [c_vp, c_vp]
+    if not older_ok or hasattr(lib, "clair_eval_reset"):
+        lib.clair_eval_reset.argtypes = [c_vp]
+        lib.clair_submit_eval.argtypes = [c_vp, c_int, c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]
+        lib.clair_eval.argtypes = [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int]
+        lib.clair_eval_read.argtypes = [c_vp, c_vp]
     lib.clair_wait.argtypes = [c_vp, c_int]
     lib.clair_slot_input.argtypes = [c_vp, c_int, ctypes.POINTER(c_vp)]
     lib.clair_submit_counts.argtypes = [c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]
@@ -281,6 +288,57 @@ class Engine(object):
         calls = np.zeros(n, dtype=CALL_DTYPE)
         self._check(self._lib.clair_decode(self._h, int(slot), _ptr(x), *[_ptr(a) for a in ys], n, _ptr(c), _ptr(calls)), "clair_decode")
         return calls
+
+    # -- scoring against truth labels (include/clair_amd.h: clair_eval_*) --------------------------
+    @staticmethod
+    def _prep_labels(labels, n):
+        lab = np.ascontiguousarray(labels, dtype=np.uint8)
+        if lab.shape != (n, 4):
+            raise ValueError("labels must be uint8 [%d,4] (gt21, genotype, len1, len2 true indices), got %r" % (n, lab.shape))
+        return lab
+
+    def eval_reset(self):
+        """clair_eval_reset: zero the handle's confusion counters."""
+        self._check(self._lib.clair_eval_reset(self._h), "clair_eval_reset")
+
+    def submit_eval(self, slot, batch, labels, counts=False, with_probabilities=False):
+        """clair_submit_eval: forward pass + scoring against `labels` (uint8 [n,4]) on the device.  batch as submit_calls takes it
+        ([n,33,8,4] float32, raw int16 counts with counts=True, or (device address, n) of int16 counts).  wait(slot) returns None, or
+        [gt21, genotype, len1, len2] with with_probabilities=True; the counters come from eval_read()."""
+        if isinstance(batch, tuple):                # (device address of dense int16 counts, n): nothing is copied
+            address, n = int(batch[0]), int(batch[1])
+            x, ptr, is_counts, stride = None, ctypes.c_void_p(address), 1, 0
+        else:
+            dtype = np.int16 if counts else np.float32
+            x = np.asarray(batch)
+            if x.ndim != 4 or x.shape[1:] != (33, 8, 4):
+                raise ValueError("batch must have shape [n,33,8,4], got %r" % (x.shape,))
+            n = x.shape[0]
+            inner_dense = x.dtype == dtype and n > 0 and x[0].flags.c_contiguous and x.strides[0] >= x[0].nbytes
+            if not inner_dense:
+                x = np.ascontiguousarray(x, dtype=dtype)
+            stride = 0 if x.flags.c_contiguous else int(x.strides[0])
+            ptr, is_counts = _ptr(x), int(bool(counts))
+        lab = self._prep_labels(labels, n)
+        outs = self._alloc_out(n) if with_probabilities else None
+        ptrs = [_ptr(o) for o in outs] if outs else [None] * 4
+        self._check(self._lib.clair_submit_eval(self._h, int(slot), ptr, is_counts, stride, n, _ptr(lab), *ptrs), "clair_submit_eval")
+        self._pending[slot] = ((x, lab), outs)
+
+    def eval_probabilities(self, Y, labels, slot=0):
+        """clair_eval: the device scoring alone on given probabilities Y = [gt21, genotype, len1, len2]."""
+        ys = [np.ascontiguousarray(a, dtype=np.float32) for a in Y]
+        n = ys[0].shape[0]
+        if [a.shape for a in ys] != [(n, 21), (n, 3), (n, 33), (n, 33)]:
+            raise ValueError("eval_probabilities: shapes do not match %d candidates" % n)
+        lab = self._prep_labels(labels, n)
+        self._check(self._lib.clair_eval(self._h, int(slot), *[_ptr(a) for a in ys], _ptr(lab), n), "clair_eval")
+
+    def eval_read(self):
+        """clair_eval_read: the counter block, int64 [EVAL_COUNTS] (clair_amd.evaluate.split_counts names its parts)."""
+        out = np.zeros(EVAL_COUNTS, dtype=np.int64)
+        self._check(self._lib.clair_eval_read(self._h, _ptr(out)), "clair_eval_read")
+        return out
 
     def slot_input(self, slot):
         """The slot's page-locked input buffer as a NumPy array [max_batch,33,8,4] float32: fill rows [0,n) and submit

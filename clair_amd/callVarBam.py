@@ -162,28 +162,12 @@ def positions_from_vcf(vcf_fn, ctg_name, ctg_start, ctg_end):
     the range, one row per run of equal positions (:127-133); a '*' alternate adds the base before the record -- first when
     '*' is one of the first two alternates, after it otherwise (:30-48), so the stream need not be sorted (the pileup handles that
     as the reference does)."""
-    have_range = ctg_start is not None and ctg_end is not None
-    p = ct.subprocess_popen(shlex.split("gzip -fdc %s" % vcf_fn))
+    from .get_truth import expanded_records
     out = []
-    for row in p.stdout:
-        col = row.strip().split()
-        if not col or col[0][0] == "#" or col[0] != ctg_name:
-            continue
-        pos = int(col[1])
-        if have_range and not ctg_start <= pos <= ctg_end:
-            continue
-        alts = col[4].split(",") if "*" in col[4] else [col[4]]
-        if "*" in col[4]:
-            if len(alts) < 2:
-                sys.exit("[ERROR] %s: a lone '*' alternate at %s:%d (the reference's GetTruth cannot read it either)" % (vcf_fn, ctg_name, pos))
-            if alts[1] == "*":
-                alts = ["*", col[4][0]]
-        for alt in alts:
-            site = pos - 1 if alt == "*" else pos
-            if not out or out[-1] != site:
-                out.append(site)
-    p.stdout.close()
-    p.wait()
+    for info in expanded_records(vcf_fn, ctg_name, ctg_start, ctg_end, get_base=None, with_genotype=False):
+        site = int(info.position)
+        if not out or out[-1] != site:
+            out.append(site)
     return np.array(out, dtype=np.int64)
 
 

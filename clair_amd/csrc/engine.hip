@@ -24,6 +24,7 @@
 #include "common.hip.h"
 #include "dense.hip.h"
 #include "decode.hip.h"
+#include "evaluate.hip.h"
 #include "gemm_split.hip.h"
 #include "lstm32.hip.h"
 #include "lstm32_pair.hip.h"
@@ -84,6 +85,8 @@ struct Slot {
     unsigned char *d_centre = nullptr, *h_centre = nullptr;   // [max_pad][2], pinned twin
     clair_call_t *d_calls = nullptr, *h_calls = nullptr;      // [max_pad], pinned twin
     clair_call_t *o_calls = nullptr;                          // caller's array of the pending submit (NULL: no decode requested)
+    // device scoring (clair_submit_eval, clair_eval): the candidates' true indices
+    unsigned char *d_labels = nullptr, *h_labels = nullptr;   // [max_pad][4], pinned twin
     // pending host outputs of a submit
     float *o_gt21 = nullptr, *o_gt = nullptr, *o_l1 = nullptr, *o_l2 = nullptr;
     int pending_n = 0;
@@ -135,6 +138,7 @@ struct clair_engine {
     struct Request {
         const void *input; bool counts; int64_t stride; int n;
         const uint8_t *centre; clair_call_t *calls; float *gt21, *gt, *l1, *l2;
+        const uint8_t *labels = nullptr;   // clair_submit_eval: [n][4] true indices, scored behind the forward pass
     };
     int staging_threads = 2;            // CLAIR_AMD_STAGING_THREADS (0: everything on the submitting thread): a 4.3 MB batch takes one core ~100 us
                                         // to copy, 75 % of the 135 us the GPU needs for it
@@ -152,6 +156,7 @@ struct clair_engine {
     unsigned short *w5s = nullptr, *whs = nullptr;   // fp16 split A fragments of the L5 branches and the heads (dense.hip.h: tail_kernel)
     float *b5 = nullptr, *bh = nullptr;
     int w5_shift[4] = {0, 0, 0, 0}, wh_shift[4] = {0, 0, 0, 0};   // per-branch power-of-two image shifts of those tensors
+    unsigned long long *eval_counts = nullptr;   // [CLAIR_EVAL_COUNTS] confusion counters of evaluate.hip.h, allocated by the first clair_eval_* call
     double ms_sum[CLAIR_K_COUNT] = {0};
     int64_t launches[CLAIR_K_COUNT] = {0};
 };
@@ -269,6 +274,8 @@ void free_slot(Slot &s) {
     if (s.h_centre) (void)hipHostFree(s.h_centre);
     if (s.d_calls) (void)hipFree(s.d_calls);
     if (s.h_calls) (void)hipHostFree(s.h_calls);
+    if (s.d_labels) (void)hipFree(s.d_labels);
+    if (s.h_labels) (void)hipHostFree(s.h_labels);
 }
 
 hipEvent_t get_event(Lane &s) {
@@ -420,6 +427,44 @@ int enqueue_decode(clair_engine *e, Lane &l, Slot &s, int n) {
     DecodeArgs a{s.d_x, s.d_out, s.d_centre, s.d_calls, n};
     hipLaunchKernelGGL(decode_kernel, dim3((n + 3) / 4), dim3(256), 0, l.stream, a);
     HIP_TRY(e, hipGetLastError());
+    return 0;
+}
+
+// The scoring of the slot's batch on the device (evaluate.hip.h): probabilities in d_out + true indices -> the handle's counter block.
+// It has no id in enum clair_kernel_id (callers size arrays by CLAIR_K_COUNT), so clair_kernel_times does not see it.
+static_assert(EVAL_COUNTS == CLAIR_EVAL_COUNTS, "evaluate.hip.h and include/clair_amd.h disagree on the counter block");
+int enqueue_eval(clair_engine *e, Lane &l, Slot &s, int n) {
+    EvalArgs a{s.d_out, s.d_labels, e->eval_counts, n};
+    hipLaunchKernelGGL(eval_kernel, dim3((n + EVAL_CAND - 1) / EVAL_CAND), dim3(256), 0, l.stream, a);
+    HIP_TRY(e, hipGetLastError());
+    return 0;
+}
+
+int ensure_slot_labels(clair_engine *e, Slot &s) {
+    if (!s.d_labels) {
+        HIP_TRY(e, hipMalloc((void **)&s.d_labels, (size_t)e->max_pad * 4));
+        HIP_TRY(e, hipHostMalloc((void **)&s.h_labels, (size_t)e->max_batch * 4, hipHostMallocDefault));
+    }
+    return 0;
+}
+
+// the counter block exists (zeroed) from the first call that needs it
+int ensure_eval_counts(clair_engine *e) {
+    if (!e->eval_counts) {
+        HIP_TRY(e, hipMalloc((void **)&e->eval_counts, (size_t)CLAIR_EVAL_COUNTS * sizeof(unsigned long long)));
+        HIP_TRY(e, hipMemset(e->eval_counts, 0, (size_t)CLAIR_EVAL_COUNTS * sizeof(unsigned long long)));
+        HIP_TRY(e, hipStreamSynchronize(nullptr));   // a memset of device memory may return before it ran; the lanes' streams do not wait for the null stream
+    }
+    return 0;
+}
+
+// true indices in range?  (evaluate.hip.h indexes its histogram with them)
+int check_labels(clair_engine *e, const uint8_t *labels, int n) {
+    for (int i = 0; i < n; ++i) {
+        const uint8_t *l = labels + (size_t)i * 4;
+        if (l[0] >= CLAIR_GT21 || l[1] >= CLAIR_GENOTYPE || l[2] >= CLAIR_INDEL_LEN || l[3] >= CLAIR_INDEL_LEN)
+            return fail(e, "label of candidate %d out of range: gt21 %d (< 21), genotype %d (< 3), lengths %d %d (< 33)", i, l[0], l[1], l[2], l[3]);
+    }
     return 0;
 }
 
@@ -585,6 +630,11 @@ int enqueue_request(clair_engine *e, int slot_index, const clair_engine::Request
         memcpy(s.h_centre, q.centre, (size_t)n * 2);
         HIP_TRY(e, hipMemcpyAsync(s.d_centre, s.h_centre, (size_t)n * 2, hipMemcpyHostToDevice, s.cin));
     }
+    if (q.labels) {
+        if (ensure_slot_labels(e, s)) return 1;
+        memcpy(s.h_labels, q.labels, (size_t)n * 4);
+        HIP_TRY(e, hipMemcpyAsync(s.d_labels, s.h_labels, (size_t)n * 4, hipMemcpyHostToDevice, s.cin));
+    }
     // int16 counts -> the float32 tensor.  On the LANE, in front of LSTM1 (default): a kernel of 1 056 small workgroups on the incoming stream has to
     // find CUs of its own among lanes whose recurrent workgroups hold whole CUs (one wave per SIMD, every register), and now and then it waits for
     // them long enough to leave a lane without input -- 5.3-5.5 instead of 7.2-7.6 M candidates/s in one run out of four (profiles/r04_convert_stream.txt);
@@ -606,6 +656,7 @@ int enqueue_request(clair_engine *e, int slot_index, const clair_engine::Request
         if (convert_on_lane) launch_convert(l.stream);
         if (enqueue_forward(e, l, s.d_x, s.d_out, n, slot_index)) return 1;
         if (q.calls && enqueue_decode(e, l, s, n)) return 1;
+        if (q.labels && enqueue_eval(e, l, s, n)) return 1;
         if (same_out) return enqueue_results(e, l, s, n, q.calls != nullptr, want_probs);      // in line with the kernels, under the lane's lock
         HIP_TRY(e, hipEventRecord(s.ev_done, l.stream));
     }
@@ -817,6 +868,7 @@ void clair_engine_destroy(clair_engine_t *e) {
     float *w[] = {e->bx1, e->bx2, e->b4, e->b5, e->bh};
     for (float *p : w) (void)hipFree(p);
     (void)hipFree(e->w5s); (void)hipFree(e->whs);
+    (void)hipFree(e->eval_counts);
     (void)hipFree(e->wx2s); (void)hipFree(e->wh1s); (void)hipFree(e->wh2s); (void)hipFree(e->wx1s); (void)hipFree(e->w4s); (void)hipFree(e->w3s);
     delete e;
 }
@@ -1089,6 +1141,74 @@ int clair_decode(clair_engine_t *e, int slot, const float *x, const float *gt21,
     HIP_TRY(e, hipMemcpyAsync(s.h_calls, s.d_calls, (size_t)n * sizeof(clair_call_t), hipMemcpyDeviceToHost, l.stream));
     HIP_TRY(e, hipStreamSynchronize(l.stream));
     memcpy(calls, s.h_calls, (size_t)n * sizeof(clair_call_t));
+    return 0;
+}
+
+// -- scoring against truth labels on the device (evaluate.hip.h; clair/evaluate.py:87-129) --------------------------------------
+int clair_eval_reset(clair_engine_t *e) {
+    if (!e) return fail(nullptr, "engine is NULL");
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (quiesce(e)) return 1;
+    if (ensure_eval_counts(e)) return 1;
+    HIP_TRY(e, hipMemset(e->eval_counts, 0, (size_t)CLAIR_EVAL_COUNTS * sizeof(unsigned long long)));
+    HIP_TRY(e, hipStreamSynchronize(nullptr));
+    return 0;
+}
+
+int clair_submit_eval(clair_engine_t *e, int slot, const void *input, int input_is_counts, int64_t input_stride_bytes, int n, const uint8_t *labels,
+                      float *gt21, float *genotype, float *l1, float *l2) {
+    if (check_slot(e, slot)) return 1;
+    if (n < 1 || n > e->max_batch) return fail(e, "n=%d out of range [1,%d]", n, e->max_batch);
+    const bool want_probs = gt21 || genotype || l1 || l2;
+    if (!input || !labels) return fail(e, "NULL input or label pointer");
+    if (want_probs && !(gt21 && genotype && l1 && l2)) return fail(e, "the four probability arrays come together or not at all");
+    if (input_stride_bytes != 0 && input_stride_bytes < (int64_t)(CLAIR_INPUT_FLOATS * (input_is_counts ? sizeof(short) : sizeof(float))))
+        return fail(e, "input stride of %lld bytes is shorter than one candidate", (long long)input_stride_bytes);
+    // a fused layer-2 launch (opt-in) may be re-run after the fact (recover_fused), which would count its batch twice
+    if (fused_possible(e)) return fail(e, "clair_submit_eval runs on the two-launch layer-2 path only: unset CLAIR_AMD_LSTM2_FUSED");
+    if (check_labels(e, labels, n)) return 1;
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (ensure_eval_counts(e)) return 1;
+    clair_engine::Request q{input, input_is_counts != 0, input_stride_bytes, n, nullptr, nullptr, gt21, genotype, l1, l2};
+    q.labels = labels;
+    return submit_request(e, slot, q);
+}
+
+// The scoring alone, on probabilities the caller holds: synchronous, needs no weights (the twin of clair_decode).
+int clair_eval(clair_engine_t *e, int slot, const float *gt21, const float *genotype, const float *l1, const float *l2, const uint8_t *labels, int n) {
+    if (!e) return fail(nullptr, "engine is NULL");
+    if (slot < 0 || slot >= (int)e->slots.size()) return fail(e, "slot %d out of range [0,%d)", slot, (int)e->slots.size());
+    if (n < 1 || n > e->max_batch) return fail(e, "n=%d out of range [1,%d]", n, e->max_batch);
+    if (!gt21 || !genotype || !l1 || !l2 || !labels) return fail(e, "NULL input pointer");
+    if (check_labels(e, labels, n)) return 1;
+    HIP_TRY(e, hipSetDevice(e->device));
+    Slot &s = e->slots[slot];
+    if (s.pending_n) return fail(e, "slot %d still has a pending submit; call clair_wait first", slot);
+    if (ensure_eval_counts(e) || ensure_slot_labels(e, s)) return 1;
+    for (int i = 0; i < n; ++i) {   // the packed [n][90] rows the kernels exchange
+        float *row = s.h_out + (size_t)i * OUT_FLOATS;
+        memcpy(row, gt21 + (size_t)i * 21, 21 * sizeof(float));
+        memcpy(row + 21, genotype + (size_t)i * 3, 3 * sizeof(float));
+        memcpy(row + 24, l1 + (size_t)i * 33, 33 * sizeof(float));
+        memcpy(row + 57, l2 + (size_t)i * 33, 33 * sizeof(float));
+    }
+    memcpy(s.h_labels, labels, (size_t)n * 4);
+    Lane &l = *e->lanes[s.lane];
+    std::lock_guard<std::mutex> g(l.order);
+    HIP_TRY(e, hipMemcpyAsync(s.d_out, s.h_out, (size_t)n * OUT_FLOATS * sizeof(float), hipMemcpyHostToDevice, l.stream));
+    HIP_TRY(e, hipMemcpyAsync(s.d_labels, s.h_labels, (size_t)n * 4, hipMemcpyHostToDevice, l.stream));
+    if (enqueue_eval(e, l, s, n)) return 1;
+    HIP_TRY(e, hipStreamSynchronize(l.stream));
+    return 0;
+}
+
+int clair_eval_read(clair_engine_t *e, int64_t *counts) {
+    if (!e) return fail(nullptr, "engine is NULL");
+    if (!counts) return fail(e, "counts is NULL");
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (quiesce(e)) return 1;
+    if (ensure_eval_counts(e)) return 1;
+    HIP_TRY(e, hipMemcpy(counts, e->eval_counts, (size_t)CLAIR_EVAL_COUNTS * sizeof(int64_t), hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -1,13 +1,14 @@
 """Output-task layout of the four heads and the label algebra the VCF decode needs.
 
-Counterpart of /root/reference/clair/task/{main,gt21,genotype,variant_length}.py, inference
-side only (label encoders for training are out of scope):
+Counterpart of /root/reference/clair/task/{main,gt21,genotype,variant_length}.py: the inference side, and the label
+encoders `evaluate` scores a checkpoint against (training itself is out of scope):
 
   head sizes 21 / 3 / 33 / 33 and their slices in a packed 90-vector   task/main.py:10-29
   the 21 genotype labels and their indices                              task/gt21.py:3-50
   genotype classes 0/0, 1/1, 0/1, 1/2                                   task/genotype.py:3-10
   indel length range -16..+16, index offset 16                          task/variant_length.py:6-12
   gt21 label of a (REF, ALT, genotype) triple                           task/gt21.py:60-110
+  true labels of a truth row / of a reference site                      task/main.py:36-81
 """
 
 GT21_LABELS = ("AA", "AC", "AG", "AT", "CC", "CG", "CT", "GG", "GT", "TT",
@@ -76,3 +77,29 @@ def genotype_class_of(g1, g2):
     if g1 == g2:
         return HOMO_VARIANT
     return HETERO_VARIANT
+
+
+def labels_from_reference(base):
+    """task/main.py:36-48 -- true indices (gt21, genotype, len1, len2) of a site without a truth variant: homozygous `base`."""
+    return GT21_INDEX[base + base], HOMO_REFERENCE, LENGTH_OFFSET, LENGTH_OFFSET
+
+
+def labels_from_vcf_columns(columns):
+    """task/main.py:51-81 -- true indices (gt21, genotype, len1, len2) of one row `ctg pos ref alt g1 g2` of a truth-variant file
+    (clair_amd.get_truth).  A single ALT is paired with REF when a genotype digit is 0, else with itself; 1/2 folds into the
+    heterozygous class (task/genotype.py:20-33); the two allele lengths are clamped to -16..+16 and put in ascending order."""
+    ref, alt = columns[2], columns[3]
+    g1, g2 = int(columns[4]), int(columns[5])
+    alts = alt.split(",")
+    if len(alts) == 1:
+        alts = [ref if (g1 == 0 or g2 == 0) else alts[0]] + alts
+    lengths = sorted(max(min(len(a) - len(ref), LENGTH_MAX), -LENGTH_MAX) for a in alts)
+    return gt21_index_of_call(ref, alt, g1, g2), genotype_class_of(g1, g2), lengths[0] + LENGTH_OFFSET, lengths[1] + LENGTH_OFFSET
+
+
+def one_hot_labels(indices):
+    """The reference's 90-element label vector (task/main.py:48, :81) from the four true indices."""
+    vec = [0] * SLICES["len2"][1]
+    for (start, _), index in zip((SLICES[k] for k in ("gt21", "genotype", "len1", "len2")), indices):
+        vec[start + index] = 1
+    return vec

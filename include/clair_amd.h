@@ -173,6 +173,40 @@ int clair_pinned_free(clair_engine_t *e, void *ptr);
 int clair_decode(clair_engine_t *e, int slot, const float *x, const float *gt21, const float *genotype, const float *indel_len1,
                  const float *indel_len2, int n, const uint8_t *centre, clair_call_t *calls);
 
+/* -- scoring against truth labels on the device: clair.py evaluate (clair/evaluate.py:38-163) ------------------------------------
+ * The reference's second consumer of Clair.predict runs the model over a labelled tensor set and accumulates four confusion
+ * matrices and the top-1 / top-2 counters of the gt21 head (evaluate.py:87-129).  Here that accumulation is one more kernel behind
+ * the forward pass (clair_amd/csrc/evaluate.hip.h), on the slot's own lane like the decode, into a counter block the handle owns in
+ * device memory: in evaluation mode only the block ever crosses the host link.  Added without an ABI bump, as the native BAM
+ * reader's entry points were; no kernel id (enum clair_kernel_id is what callers size arrays by).
+ * Counter block: CLAIR_EVAL_COUNTS int64 = all, top1, top2 (evaluate.py:96-102), then row-major [true][predicted]: gt21 21x21
+ * (:92-94), genotype 3x3 (:105-109), indel length 1 33x33 and indel length 2 33x33 (:118-129: the pair of true indices and the pair of
+ * predicted arg-maxes are each put in ascending order first).
+ * Labels: [n][4] bytes per candidate, the TRUE indices gt21 0..20, genotype 0..2, len1 0..32, len2 0..32 (np.argmax of the four
+ * slices of the reference's 90-element label vector, clair/task/main.py:36-81).  A label out of range is an error of the call that
+ * takes it, raised on the host before anything is enqueued: the counters stay as they were.
+ * Ties: arg-max is the lowest index among equals (np.argmax).  Top-1 / top-2 order: descending probability, then DESCENDING index
+ * (a reversed stable sort; the reference's argsort()[::-1], :97, leaves the order among exactly equal values to NumPy's sort).
+ * NaN probabilities are out of scope.  The counts are integers added with atomics: they do not depend on launch order or on the
+ * number of slots and lanes in flight. */
+#define CLAIR_EVAL_COUNTS (3 + 21 * 21 + 3 * 3 + 33 * 33 + 33 * 33) /* 2631 */
+/* Allocate the block on first use and zero it (waits for the handle's streams): confusion matrices of evaluate.py:59-64. */
+int clair_eval_reset(clair_engine_t *e);
+/* m.predict + the scoring of one batch (evaluate.py:81-129), pipelined: input, input_is_counts and input_stride_bytes as for
+ * clair_submit_ex (float32 tensor or raw int16 counts, host or device address, strided); forward pass, then the scoring of its
+ * probabilities against `labels` ([n][4]; must stay valid until clair_wait, like `input`).
+ * gt21 / genotype / indel_len1 / indel_len2: all NULL (the probabilities stay on the device: the normal evaluation mode) or all
+ * given (tests).  Pair with clair_wait(slot).  Not available on a handle that opted into the fused layer-2 launch
+ * (CLAIR_AMD_LSTM2_FUSED=1): a pass re-run after a misplaced launch would be counted twice. */
+int clair_submit_eval(clair_engine_t *e, int slot, const void *input, int input_is_counts, int64_t input_stride_bytes, int n,
+                      const uint8_t *labels, float *gt21, float *genotype, float *indel_len1, float *indel_len2);
+/* The scoring alone (evaluate.py:87-129), on probabilities the caller holds: synchronous, needs no weights -- the twin of
+ * clair_decode, and how crafted rows (exact ties) reach the kernel. */
+int clair_eval(clair_engine_t *e, int slot, const float *gt21, const float *genotype, const float *indel_len1, const float *indel_len2,
+               const uint8_t *labels, int n);
+/* Wait for all slots' device work, then copy the block to counts[CLAIR_EVAL_COUNTS] (what evaluate.py:136-163 prints from). */
+int clair_eval_read(clair_engine_t *e, int64_t *counts);
+
 /* -- device-resident candidate sets (benchmark / multi-GPU shard driver) ------------------------
  * The candidate set lives in HBM: x_dev [N,33,8,4]; outputs out_dev [N,90] rows laid out
  * gt21(21) | genotype(3) | len1(33) | len2(33).  clair_run_resident enqueues the forward pass
