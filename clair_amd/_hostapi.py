@@ -316,7 +316,41 @@ def pyset_order(ops):
     return keys[:n.value].tolist()
 
 
-class PileupBuilder(object):
+class _LineSink(object):
+    """A native consumer of `samtools view` text.  A subclass sets _lib, _h (its handle) and _feed (its clair_host_*_feed)."""
+
+    def feed(self, sam, final=False):
+        """Consume complete lines of `sam` (bytes or str); returns the unconsumed tail (same type)."""
+        data = sam.encode("latin-1") if isinstance(sam, str) else sam
+        used = ctypes.c_int64(0)
+        base = ctypes.cast(ctypes.c_char_p(data), ctypes.c_void_p).value
+        if self._feed(self._h, base, len(data), 1 if final else 0, ctypes.byref(used)) != 0:
+            from .create_tensor import PileupError
+            raise PileupError(self._lib.clair_host_last_error().decode())
+        return sam[used.value:]
+
+    def finish(self):
+        """Nothing is held back between lines unless the subclass says so."""
+
+
+def feed_stream(sink, read, chunk_bytes):
+    """Feed a SAM stream to a _LineSink, read(chunk_bytes) at a time (bytes or str; empty at the end), whole lines only: what a chunk ends with
+    goes in front of the next.  Yields after every feed for the caller to take what has become ready: False after a chunk, True once, after
+    the last line (with or without its line end) and finish()."""
+    tail = None
+    while True:
+        chunk = read(chunk_bytes)
+        if not chunk:
+            break
+        tail = sink.feed(chunk if tail is None else tail + chunk)
+        yield False
+    if tail:
+        sink.feed(tail, final=True)
+    sink.finish()
+    yield True
+
+
+class PileupBuilder(_LineSink):
     """clair_host_pileup_*: the native twin of clair_amd.create_tensor.PileupBuilderPy (same constructor, same records)."""
 
     def __init__(self, ctg_name, reference_sequence, reference_start_0_based, candidates, consider_left_edge=True,
@@ -333,7 +367,7 @@ class PileupBuilder(object):
                                                 int(available_slots), int(bool(force_general_path)), ctypes.byref(h))
         if rc != 0:
             raise ValueError("pileup: " + self._lib.clair_host_last_error().decode())
-        self._h = h
+        self._h, self._feed = h, self._lib.clair_host_pileup_feed
         self._text = None
         if set_order == "cpython" and self._lib.clair_host_pileup_set_order(self._h, 1) != 0:
             raise ValueError("pileup: " + self._lib.clair_host_last_error().decode())
@@ -345,17 +379,6 @@ class PileupBuilder(object):
 
     __del__ = close
 
-    def feed(self, sam, final=False):
-        """Consume complete lines of `sam` (bytes or str); returns the unconsumed tail (same type)."""
-        data = sam.encode("latin-1") if isinstance(sam, str) else sam
-        used = ctypes.c_int64(0)
-        base = ctypes.cast(ctypes.c_char_p(data), ctypes.c_void_p).value
-        rc = self._lib.clair_host_pileup_feed(self._h, base, len(data), 1 if final else 0, ctypes.byref(used))
-        if rc != 0:
-            from .create_tensor import PileupError
-            raise PileupError(self._lib.clair_host_last_error().decode())
-        return sam[used.value:]
-
     def finish(self):
         self._lib.clair_host_pileup_finish(self._h)
 
@@ -364,15 +387,9 @@ class PileupBuilder(object):
 
     def take_arrays(self, max_rows=None):
         """-> (centres int64 [n], refseq list of str, counts int32 [n,33,8,4])"""
-        n = self.pending() if max_rows is None else min(self.pending(), int(max_rows))
-        centres = np.empty(n, dtype=np.int64)
-        seqs = np.zeros((n, 34), dtype=np.uint8)
-        counts = np.empty((n, 33, 8, 4), dtype=np.int32)
-        taken = ctypes.c_int64(0)
-        if n:
-            self._lib.clair_host_pileup_take(self._h, n, centres.ctypes.data, seqs.ctypes.data, counts.ctypes.data, ctypes.byref(taken))
+        centres, seqs, counts = self.take_columns(max_rows)
         raw = seqs.tobytes()
-        return centres, [raw[i * 34:i * 34 + 34].split(b"\0", 1)[0].decode("latin-1") for i in range(n)], counts
+        return centres, [raw[i * 34:i * 34 + 34].split(b"\0", 1)[0].decode("latin-1") for i in range(len(centres))], counts
 
     def take_columns(self, max_rows=None):
         """take_arrays without a Python string per window: -> (centres int64 [n], refseq bytes uint8 [n,34] NUL-terminated,
@@ -405,22 +422,12 @@ class PileupBuilder(object):
 
     def text_from_sam(self, handle, chunk_bytes=1 << 22):
         """Feed a SAM stream (binary or text file object); yield the finished records as text chunks (str)."""
-        tail = None
-        while True:
-            chunk = handle.read(chunk_bytes)
-            if not chunk:
-                break
-            tail = self.feed(chunk if tail is None else tail + chunk)
+        for _ in feed_stream(self, handle.read, chunk_bytes):
             while self.pending():
                 yield self.take_text().decode("latin-1")
-        if tail:
-            self.feed(tail, final=True)
-        self.finish()
-        while self.pending():
-            yield self.take_text().decode("latin-1")
 
 
-class CandidateFinder(object):
+class CandidateFinder(_LineSink):
     """clair_host_evc_*: the native twin of clair_amd.extract_variant_candidates.CandidateFinderPy."""
 
     def __init__(self, ctg_name, reference_sequence, reference_start_0_based, ctg_start=None, ctg_end=None, bed=None,
@@ -442,7 +449,7 @@ class CandidateFinder(object):
                                              int(min_mq), ctypes.byref(h))
         if rc != 0:
             raise ValueError("candidates: " + self._lib.clair_host_last_error().decode())
-        self._h = h
+        self._h, self._feed = h, self._lib.clair_host_evc_feed
         self._text = None
 
     def close(self):
@@ -455,16 +462,6 @@ class CandidateFinder(object):
     @property
     def reads(self):
         return int(self._lib.clair_host_evc_reads(self._h))
-
-    def feed(self, sam, final=False):
-        data = sam.encode("latin-1") if isinstance(sam, str) else sam
-        used = ctypes.c_int64(0)
-        base = ctypes.cast(ctypes.c_char_p(data), ctypes.c_void_p).value
-        rc = self._lib.clair_host_evc_feed(self._h, base, len(data), 1 if final else 0, ctypes.byref(used))
-        if rc != 0:
-            from .create_tensor import PileupError
-            raise PileupError(self._lib.clair_host_last_error().decode())
-        return sam[used.value:]
 
     def finish(self):
         self._lib.clair_host_evc_finish(self._h)
@@ -488,19 +485,9 @@ class CandidateFinder(object):
         return self._text.raw[:n.value]
 
     def text_from_sam(self, handle, chunk_bytes=1 << 22):
-        tail = None
-        while True:
-            chunk = handle.read(chunk_bytes)
-            if not chunk:
-                break
-            tail = self.feed(chunk if tail is None else tail + chunk)
+        for _ in feed_stream(self, handle.read, chunk_bytes):
             while self.pending():
                 yield self.take_text().decode("latin-1")
-        if tail:
-            self.feed(tail, final=True)
-        self.finish()
-        while self.pending():
-            yield self.take_text().decode("latin-1")
 
 
 READ_DTYPE = np.dtype([("pos0", "<i8"), ("seq0", "<u4"), ("seq_len", "<u4"), ("op0", "<u4"), ("n_ops", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
@@ -508,7 +495,7 @@ OP_DTYPE = np.dtype([("read", "<u4"), ("code_len", "<u4"), ("ref_off", "<i4"), (
 READ_REVERSE, READ_EVC, READ_PILE, READ_FLUSH = 1, 2, 4, 8
 
 
-class SamPacker(object):
+class SamPacker(_LineSink):
     """clair_host_sampack_*: `samtools view` text -> slabs of packed alignments (include/clair_reads.h) for the device front end."""
 
     def __init__(self, ctg_name, dcov=250, evc_min_mq=0, pile_min_mq=0, pile_region=None):
@@ -517,7 +504,7 @@ class SamPacker(object):
         a, b = (-1, -1) if pile_region is None else (int(pile_region[0]), int(pile_region[1]))
         if self._lib.clair_host_sampack_create(ctg_name.encode(), int(dcov), int(evc_min_mq), int(pile_min_mq), a, b, ctypes.byref(h)) != 0:
             raise ValueError("sampack: " + self._lib.clair_host_last_error().decode())
-        self._h = h
+        self._h, self._feed = h, self._lib.clair_host_sampack_feed
 
     def close(self):
         if getattr(self, "_h", None):
@@ -525,15 +512,6 @@ class SamPacker(object):
             self._h = None
 
     __del__ = close
-
-    def feed(self, sam, final=False):
-        """Consume complete lines of `sam` (bytes); returns the unconsumed tail."""
-        used = ctypes.c_int64(0)
-        base = ctypes.cast(ctypes.c_char_p(sam), ctypes.c_void_p).value
-        if self._lib.clair_host_sampack_feed(self._h, base, len(sam), 1 if final else 0, ctypes.byref(used)) != 0:
-            from .create_tensor import PileupError
-            raise PileupError(self._lib.clair_host_last_error().decode())
-        return sam[used.value:]
 
     def stats(self):
         v = (ctypes.c_int64 * 8)()

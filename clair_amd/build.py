@@ -44,6 +44,7 @@ def build_host(force=False):
     """Host-side helpers (include/clair_host.h): plain C++, no HIP."""
     # every header a host source includes: clair_call.h is the 32-byte record host_decode.cpp shares bit for bit with the device decode
     hdrs = [os.path.join(HERE, "..", "include", h) for h in ("clair_host.h", "clair_reads.h", "clair_call.h", "clair_amd.h")]
+    hdrs.append(os.path.join(HERE, "hostsrc", "sam_line.h"))
     if (force or not os.path.isfile(HOST_OUT)
             or max([os.path.getmtime(f) for f in HOST_SRCS + hdrs]) > os.path.getmtime(HOST_OUT)):
         # -ffp-contract=off: the decode restates float32 product chains bit for bit (no fused multiply-add)

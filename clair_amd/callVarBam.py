@@ -107,7 +107,7 @@ class _NativeText(object):
 
 def alignment_text(args, region):
     """The alignments of `region` as `samtools view -F 2316` text: from samtools (the default) or rendered natively (--bam_reader native)."""
-    if getattr(args, "bam_reader", "samtools") == "native":
+    if native_input(args):
         return _NativeText(args, region)
     return _OnePipe(args, region)
 
@@ -116,44 +116,53 @@ def native_input(args):
     return getattr(args, "bam_reader", "samtools") == "native"
 
 
+def reference_and_bed(args, search, not_loaded):
+    """What both front ends start with: the reference slice of the region (widened by 1 Mbp: the two stages load the same one,
+    ExtractVariantCandidates.py:228-236, CreateTensor.py:113-156) and, where candidates are searched for, the .fai looked for before it and the
+    bed intervals of the contig after it.  not_loaded: the exit message for a slice that cannot be had (the stages word it differently).
+    -> (sequence, its 0-based start, bed intervals or None)"""
+    if search and not os.path.isfile("%s.fai" % args.ref_fn):
+        sys.exit("Fasta index %s.fai doesn't exist." % args.ref_fn)
+    seq, ref_start = ct.reference_sequence_from(args.samtools, args.ref_fn, args.ctgName, args.ctgStart, args.ctgEnd, native=native_input(args))
+    if not seq:
+        sys.exit(not_loaded)
+    tree = evc.bed_regions_from(args.bed_fn) if search else None
+    if tree is not None and args.ctgName not in tree:
+        sys.exit("[ERROR] ctg_name(%s) not exists in bed file(%s)." % (args.ctgName, args.bed_fn))
+    return seq, 0 if ref_start is None else ref_start - 1, None if tree is None else tree[args.ctgName]
+
+
+def window_infos(ctg_name, centres, seqs):
+    """[[ctg, pos, refseq], ...] of a batch of windows (centres int64 [n], seqs uint8 [n,34] NUL-terminated): in column form, without a Python
+    string per window (tensor_binary.InfoTable), or the list itself for a contig name too long for that."""
+    from .tensor_binary import MAX_CTG, InfoTable
+    ctg, n = ctg_name.encode(), len(centres)
+    if len(ctg) <= MAX_CTG:
+        return InfoTable(np.full(n, ctg, dtype="S%d" % MAX_CTG), np.full(n, len(ctg), dtype=np.uint8), centres,
+                         np.ascontiguousarray(seqs[:, :33]).view("S33").ravel(), (seqs[:, :33] != 0).sum(axis=1).astype(np.uint8))
+    raw = seqs.tobytes()
+    return [[ctg_name, str(c), raw[i * 34:i * 34 + 34].split(b"\0", 1)[0].decode("latin-1")] for i, c in enumerate(centres.tolist())]
+
+
 def candidate_positions(args, quiet=False):
     """Stage 1.  -> int64 positions (1-based, ascending for sorted alignments)."""
     from . import _hostapi
     if args.vcf_fn is not None:
         return positions_from_vcf(args.vcf_fn, args.ctgName, args.ctgStart, args.ctgEnd)
-    if not os.path.isfile("%s.fai" % args.ref_fn):
-        sys.exit("Fasta index %s.fai doesn't exist." % args.ref_fn)
+    seq, ref0, bed = reference_and_bed(args, True, "[ERROR] Failed to load reference seqeunce from file (%s)." % args.ref_fn)
     have_range = args.ctgStart is not None and args.ctgEnd is not None
-    region, ref_start = evc.reference_region(args.ctgName, args.ctgStart if have_range else None, args.ctgEnd if have_range else None)
-    seq = evc.load_reference(args.samtools, args.ref_fn, region, native=native_input(args))
-    if not seq:
-        sys.exit("[ERROR] Failed to load reference seqeunce from file (%s)." % args.ref_fn)
-    tree = evc.bed_regions_from(args.bed_fn)
-    if tree is not None and args.ctgName not in tree:
-        sys.exit("[ERROR] ctg_name(%s) not exists in bed file(%s)." % (args.ctgName, args.bed_fn))
-    finder = _hostapi.CandidateFinder(args.ctgName, seq, 0 if ref_start is None else ref_start - 1,
-                                      ctg_start=args.ctgStart if have_range else None, ctg_end=args.ctgEnd if have_range else None,
-                                      bed=None if tree is None else tree[args.ctgName],
+    finder = _hostapi.CandidateFinder(args.ctgName, seq, ref0, ctg_start=args.ctgStart if have_range else None,
+                                      ctg_end=args.ctgEnd if have_range else None, bed=bed,
                                       min_coverage=int(args.minCoverage), threshold=args.threshold, min_mq=0)   # callVarBam.py:75: int() before it reaches the extractor
-    view = alignment_text(args, region)
-    chunks, tail = [], None
-    while True:
-        chunk = view.read(1 << 22)
-        if not chunk:
-            break
-        tail = finder.feed(chunk if tail is None else tail + chunk)
-        if finder.pending():
-            chunks.append(finder.take_positions())
-    if tail:
-        finder.feed(tail, final=True)
-    finder.finish()
-    chunks.append(finder.take_positions())
+    # the search reads the alignments of the region its reference slice covers (ExtractVariantCandidates.py:228-240)
+    view = alignment_text(args, evc.reference_region(args.ctgName, args.ctgStart if have_range else None, args.ctgEnd if have_range else None)[0])
+    chunks = [finder.take_positions() for _ in _hostapi.feed_stream(finder, view.read, 1 << 22)]
     if view.finish() != 0:
         sys.exit("[ERROR] `samtools view` failed on %s" % args.bam_fn)
     if finder.reads == 0 and not quiet:
         print("No read has been process, either the genome region you specified has no read cover, or please check the correctness of your BAM input (%s)."
               % args.bam_fn, file=sys.stderr)
-    return np.concatenate(chunks) if chunks else np.zeros(0, np.int64)
+    return np.concatenate(chunks)
 
 
 def positions_from_vcf(vcf_fn, ctg_name, ctg_start, ctg_end):
@@ -187,26 +196,17 @@ def tensor_batches(args, positions, batch_size, read_flank=(0, 0), progress=True
                                      consider_left_edge=not args.stop_consider_left_edge, dcov=args.dcov, set_order=ct.set_order_of(getattr(args, "pypy", None)))
     region = "%s:%d-%d" % (args.ctgName, max(1, args.ctgStart - read_flank[0]), args.ctgEnd + read_flank[1]) if have_range else args.ctgName
     view = alignment_text(args, region)
-    from .tensor_binary import MAX_CTG, InfoTable, _IUPAC_TABLE
+    from .tensor_binary import _IUPAC_TABLE
     total = 0
-    ctg_bytes = args.ctgName.encode()
-    use_table = len(ctg_bytes) <= MAX_CTG           # the column form of [[ctg, pos, refseq], ...] (no Python string per window)
     held = [[], [], []]                             # centres, refseq bytes [n,34], counts of windows not yet handed out
     held_n = 0
 
     def emit(centres, seqs, counts):
         nonlocal total
-        n = len(centres)
-        total += n
+        total += len(centres)
         if progress:
             print("Processed %d tensors" % total, file=sys.stderr)
-        if use_table:
-            seq_col = np.ascontiguousarray(seqs[:, :33]).view("S33").ravel()
-            infos = InfoTable(np.full(n, ctg_bytes, dtype="S%d" % MAX_CTG), np.full(n, len(ctg_bytes), dtype=np.uint8), centres, seq_col,
-                              (seqs[:, :33] != 0).sum(axis=1).astype(np.uint8))
-        else:
-            raw = seqs.tobytes()
-            infos = [[args.ctgName, str(c), raw[i * 34:i * 34 + 34].split(b"\0", 1)[0].decode("latin-1")] for i, c in enumerate(centres.tolist())]
+        infos = window_infos(args.ctgName, centres, seqs)
         x = _hostapi.counts_to_input(counts)              # the decode reads depth and allele support from the tensor
         # the GPU takes the raw counts (half the bytes on the host link) when they fit int16
         small = counts.astype(np.int16) if int(counts.max()) <= 32767 and int(counts.min()) >= -32768 else None
@@ -232,19 +232,9 @@ def tensor_batches(args, positions, batch_size, read_flank=(0, 0), progress=True
             held, held_n = [[], [], []], 0
             yield emit(*cols)
 
-    tail = None
-    while True:
-        chunk = view.read(1 << 22)
-        if not chunk:
-            break
-        tail = builder.feed(chunk if tail is None else tail + chunk)
-        for batch in drain(False):
+    for last in _hostapi.feed_stream(builder, view.read, 1 << 22):
+        for batch in drain(last):
             yield batch
-    if tail:
-        builder.feed(tail, final=True)
-    builder.finish()
-    for batch in drain(True):
-        yield batch
     if view.finish() != 0:
         sys.exit("[ERROR] `samtools view` failed on %s" % args.bam_fn)
 
@@ -485,20 +475,8 @@ class DeviceFrontEnd(object):
                 given = given[(given >= args.ctgStart) & (given <= args.ctgEnd)]
             if len(given) > 1 and not (np.diff(given) > 0).all():
                 return self._fallback(FE_REASONS[8][1])
-        elif not os.path.isfile("%s.fai" % args.ref_fn):
-            sys.exit("Fasta index %s.fai doesn't exist." % args.ref_fn)
-        # one reference slice serves both stages: they load the same region (ExtractVariantCandidates.py:228-236, CreateTensor.py:113-156)
-        seq, ref_start = ct.reference_sequence_from(args.samtools, args.ref_fn, args.ctgName, args.ctgStart, args.ctgEnd, native=native_input(args))
-        if not seq:
-            sys.exit("Failed to load reference seqeunce. Please check if the provided reference fasta %s and the ctgName %s are correct."
-                     % (args.ref_fn, args.ctgName))
-        ref0 = 0 if ref_start is None else ref_start - 1
-        bed = None
-        if given is None:
-            tree = evc.bed_regions_from(args.bed_fn)
-            if tree is not None and args.ctgName not in tree:
-                sys.exit("[ERROR] ctg_name(%s) not exists in bed file(%s)." % (args.ctgName, args.bed_fn))
-            bed = None if tree is None else tree[args.ctgName]
+        seq, ref0, bed = reference_and_bed(args, given is None, "Failed to load reference seqeunce. Please check if the provided reference fasta %s "
+                                           "and the ctgName %s are correct." % (args.ref_fn, args.ctgName))
         if have_range:
             lo, hi = args.ctgStart - 1 - TABLE_MARGIN, args.ctgEnd + TABLE_MARGIN
             # the candidate search reads the widened region, the pileup the plain one (callVarBam.py:124-199); an alignment can only
@@ -568,25 +546,21 @@ class DeviceFrontEnd(object):
                 pst = f.text_stats()
             else:
                 packer = _hostapi.SamPacker(args.ctgName, **pack_kw)
-                tail = None
-                while True:
-                    chunk = view.read(1 << 23)
-                    if not chunk:
-                        break
+
+                def read(n):                                   # packing time is the feed loop's less what it waits for here
+                    nonlocal t_pack
                     t0 = time()
-                    tail = packer.feed(chunk if tail is None else tail + chunk)
+                    chunk = view.read(n)
+                    t_pack -= time() - t0
+                    return chunk
+                t0 = time()
+                for last in _hostapi.feed_stream(packer, read, 1 << 23):
                     t_pack += time() - t0
-                    if packer.stats()["seq_bytes"] >= SLAB_BYTES:
+                    if last or packer.stats()["seq_bytes"] >= SLAB_BYTES:
                         t0 = time()
                         f.add_slab(packer)
                         t_dev += time() - t0
-                t0 = time()
-                if tail:
-                    packer.feed(tail, final=True)
-                t_pack += time() - t0
-                t0 = time()
-                f.add_slab(packer)
-                t_dev += time() - t0
+                    t0 = time()
                 pst = packer.stats()
         except BaseException:
             view.abort()
@@ -622,9 +596,7 @@ class DeviceFrontEnd(object):
         """(X float32 or None, infos, counts) per batch.  lean: nobody on the host reads the tensor (decode on the device, no BAM open):
         the counts stay in HBM (DeviceWindows) and X is None; otherwise both come back to the host, as from tensor_batches."""
         from . import _capi, _hostapi
-        from .tensor_binary import MAX_CTG, InfoTable
-        f, ctg = self.frontend, self.args.ctgName.encode()
-        use_table = len(ctg) <= MAX_CTG
+        f = self.frontend
         total = 0
         for first in range(0, self.n_windows, batch_size):
             n = min(batch_size, self.n_windows - first)
@@ -632,12 +604,7 @@ class DeviceFrontEnd(object):
             total += n
             if progress:
                 print("Processed %d tensors" % total, file=sys.stderr)
-            if use_table:
-                infos = InfoTable(np.full(n, ctg, dtype="S%d" % MAX_CTG), np.full(n, len(ctg), dtype=np.uint8), centres,
-                                  np.ascontiguousarray(seqs[:, :33]).view("S33").ravel(), (seqs[:, :33] != 0).sum(axis=1).astype(np.uint8))
-            else:
-                raw = seqs.tobytes()
-                infos = [[self.args.ctgName, str(c), raw[i * 34:i * 34 + 34].split(b"\0", 1)[0].decode("latin-1")] for i, c in enumerate(centres.tolist())]
+            infos = window_infos(self.args.ctgName, centres, seqs)
             if lean:
                 yield None, infos, _capi.DeviceWindows(f, first, n)
             else:
@@ -758,7 +725,7 @@ def normalise(args):
         args.ctgStart = args.ctgEnd = None          # callVarBam.py:97-101
     if (args.ctgStart is None) != (args.ctgEnd is None):
         args.ctgStart = args.ctgEnd = None
-    if getattr(args, "bam_reader", "samtools") == "native":
+    if native_input(args):
         for name, given in (("--samtools_view_args", args.samtools_view_args is not None), ("--samtools_threads", (args.samtools_threads or 0) > 0),
                             ("--view_readers", (args.view_readers or 1) > 1)):
             if given:

@@ -314,20 +314,14 @@ def records_from_sam(builder, sam_handle, chunk_bytes=1 << 22):
             if builder.out:
                 for rec in builder.take():
                     yield rec
+        builder.finish()
+        for rec in builder.take():
+            yield rec
     else:
-        tail = None
-        while True:
-            chunk = sam_handle.read(chunk_bytes)
-            if not chunk:
-                break
-            tail = builder.feed(chunk if tail is None else tail + chunk)
+        from . import _hostapi
+        for _ in _hostapi.feed_stream(builder, sam_handle.read, chunk_bytes):
             for rec in builder.take():
                 yield rec
-        if tail:
-            builder.feed(tail, final=True)
-    builder.finish()
-    for rec in builder.take():
-        yield rec
 
 
 def output_aln_tensor(args, native=True):

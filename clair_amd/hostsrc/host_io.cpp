@@ -1,5 +1,6 @@
 // Host-side helpers of the Clair hot path (include/clair_host.h): native ingest.  Plain C++17, no HIP.
 #include "../../include/clair_host.h"
+#include "sam_line.h"
 
 #include <cerrno>
 #include <cstdarg>
@@ -28,9 +29,6 @@ int fail(const char *fmt, ...) {
     g_error = buf;
     return 1;
 }
-
-// str.split() whitespace: space, \t, \n, \r, \v, \f (and the ASCII separators 0x1c-0x1f, which text records never hold)
-inline bool is_space(unsigned char c) { return c == ' ' || (c >= 9 && c <= 13) || (c >= 0x1c && c <= 0x1f); }
 
 // centre-base filter: keys of IUPAC_base_to_num_dict (shared/utils.py:24-27)
 inline bool is_iupac(unsigned char c) {

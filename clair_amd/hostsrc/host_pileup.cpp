@@ -14,6 +14,7 @@
 //     within [position-16, position+17], tracked with two cursors per read.  Unsorted lists take a hash-map path that
 //     mirrors the dict.
 #include "../../include/clair_host.h"
+#include "sam_line.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -25,16 +26,12 @@
 #include <unordered_map>
 #include <vector>
 
-int clair_host_fail(const char *fmt, ...);   // host_io.cpp
-
 namespace {
 
 constexpr int FLANK = 16;                 // shared/param.py:9
 constexpr int N_POS = 2 * FLANK + 1;      // 33
 constexpr int N_VAL = N_POS * 8 * 4;      // 1056
 constexpr int64_t LOOKAHEAD = 100000;     // CreateTensor.py:275
-
-inline bool is_space(unsigned char c) { return c == ' ' || (c >= 9 && c <= 13) || (c >= 0x1c && c <= 0x1f); }
 
 // IUPAC_base_to_num_dict (shared/utils.py:24-27); -1: not a key
 struct BaseTable {
@@ -393,38 +390,13 @@ struct clair_pileup {
 
     int add_line(const char *p, const char *end, int64_t line_no) {
         // str.split(): columns 1, 3, 4, 5, 9 of a whitespace-separated line (CreateTensor.py:252-263)
-        const char *col[10];
-        size_t len[10];
-        int n = 0;
-        while (p < end && n < 10) {
-            while (p < end && is_space((unsigned char)*p)) ++p;
-            if (p >= end) break;
-            const char *q = p;
-            while (q < end && !is_space((unsigned char)*q)) ++q;
-            col[n] = p;
-            len[n] = (size_t)(q - p);
-            ++n;
-            p = q;
-        }
-        if (n == 0) return clair_host_fail("alignment line %lld is empty", (long long)line_no);
-        if (col[0][0] == '@') return 0;
-        if (n < 10) return clair_host_fail("alignment line %lld has %d columns (11 expected)", (long long)line_no, n);
-        int64_t v[3];
-        const int which[3] = {1, 3, 4};
-        for (int i = 0; i < 3; ++i) {
-            const char *s = col[which[i]], *e = s + len[which[i]];
-            bool neg = false;
-            if (s < e && (*s == '-' || *s == '+')) { neg = *s == '-'; ++s; }
-            if (s == e || e - s > 18) return clair_host_fail("alignment line %lld: column %d is not an integer", (long long)line_no, which[i] + 1);
-            int64_t x = 0;
-            for (; s < e; ++s) {
-                if (*s < '0' || *s > '9') return clair_host_fail("alignment line %lld: column %d is not an integer", (long long)line_no, which[i] + 1);
-                x = x * 10 + (*s - '0');
-            }
-            v[i] = neg ? -x : x;
-        }
-        scratch_seq.assign(col[9], len[9]);
-        return add_read((int)v[0], v[1], v[2], col[5], len[5], scratch_seq.data(), scratch_seq.size());
+        SamLine line;
+        const SamSplit split = split_sam_line(p, end, line_no, &line);
+        if (split != SAM_OK) return split == SAM_ERROR;
+        int64_t flag, pos1, mapq;
+        if (!sam_int(line, 1, line_no, &flag) || !sam_int(line, 3, line_no, &pos1) || !sam_int(line, 4, line_no, &mapq)) return 1;
+        scratch_seq.assign(line.col[9], line.len[9]);
+        return add_read((int)flag, pos1, mapq, line.col[5], line.len[5], scratch_seq.data(), scratch_seq.size());
     }
     std::string scratch_seq;
     int64_t lines_seen = 0;
@@ -479,20 +451,7 @@ int clair_host_pyset_order(const int64_t *ops, int64_t n_ops, int64_t *keys, int
     return 0;
 }
 
-int clair_host_pileup_feed(clair_pileup_t *p, const char *sam, int64_t len, int final, int64_t *bytes_consumed) {
-    if (!p || (!sam && len > 0) || !bytes_consumed) return clair_host_fail("bad argument");
-    int64_t at = 0;
-    while (at < len) {
-        const char *nl = (const char *)memchr(sam + at, '\n', (size_t)(len - at));
-        if (!nl && !final) break;
-        const char *end = nl ? nl : sam + len;
-        if (p->add_line(sam + at, end, p->lines_seen)) { *bytes_consumed = at; return 1; }
-        ++p->lines_seen;
-        at = (nl ? nl + 1 : end) - sam;
-    }
-    *bytes_consumed = at;
-    return 0;
-}
+int clair_host_pileup_feed(clair_pileup_t *p, const char *sam, int64_t len, int final, int64_t *bytes_consumed) { return feed_lines(p, sam, len, final, bytes_consumed); }
 
 int clair_host_pileup_finish(clair_pileup_t *p) {
     if (!p) return clair_host_fail("bad argument");
@@ -667,41 +626,16 @@ struct clair_evc {
     }
 
     int add_line(const char *p, const char *end, int64_t line_no) {
-        const char *col[10];
-        size_t len[10];
-        int n = 0;
-        while (p < end && n < 10) {
-            while (p < end && is_space((unsigned char)*p)) ++p;
-            if (p >= end) break;
-            const char *q = p;
-            while (q < end && !is_space((unsigned char)*q)) ++q;
-            col[n] = p;
-            len[n] = (size_t)(q - p);
-            ++n;
-            p = q;
-        }
-        if (n == 0) return clair_host_fail("alignment line %lld is empty", (long long)line_no);
-        if (col[0][0] == '@') return 0;
-        if (n < 10) return clair_host_fail("alignment line %lld has %d columns (11 expected)", (long long)line_no, n);
-        if (len[2] != ctg.size() || memcmp(col[2], ctg.data(), ctg.size()) != 0) return 0;   // RNAME != ctgName (:279-281)
-        int64_t v[2];
-        const int which[2] = {3, 4};
-        for (int i = 0; i < 2; ++i) {
-            const char *s = col[which[i]], *e = s + len[which[i]];
-            bool neg = false;
-            if (s < e && (*s == '-' || *s == '+')) { neg = *s == '-'; ++s; }
-            if (s == e || e - s > 18) return clair_host_fail("alignment line %lld: column %d is not an integer", (long long)line_no, which[i] + 1);
-            int64_t x = 0;
-            for (; s < e; ++s) {
-                if (*s < '0' || *s > '9') return clair_host_fail("alignment line %lld: column %d is not an integer", (long long)line_no, which[i] + 1);
-                x = x * 10 + (*s - '0');
-            }
-            v[i] = neg ? -x : x;
-        }
-        const int64_t pos = v[0] - 1;
-        if (v[1] < min_mq) return 0;
-        const char *cigar = col[5];
-        const size_t cl = len[5];
+        SamLine line;
+        const SamSplit split = split_sam_line(p, end, line_no, &line);
+        if (split != SAM_OK) return split == SAM_ERROR;
+        if (line.len[2] != ctg.size() || memcmp(line.col[2], ctg.data(), ctg.size()) != 0) return 0;   // RNAME != ctgName (:279-281)
+        int64_t pos1, mapq;
+        if (!sam_int(line, 3, line_no, &pos1) || !sam_int(line, 4, line_no, &mapq)) return 1;
+        const int64_t pos = pos1 - 1;
+        if (mapq < min_mq) return 0;
+        const char *cigar = line.col[5];
+        const size_t cl = line.len[5];
         if (cl == 1 && cigar[0] == '*') return 0;
         {   // a read less than 55 % aligned is skipped (:143-157)
             int64_t soft = 0, total = 0, adv = 0;
@@ -712,14 +646,14 @@ struct clair_evc {
                 total += adv;
                 adv = 0;
             }
-            if (1.0 - (double)soft / (double)(total + 1) < 0.55) return 0;
+            if (mostly_clipped(soft, total)) return 0;
         }
         ++reads;
         // positions before POS - 1 cannot change any more: write them now rather than zero-filling across a coverage gap
         // (POS - 1 itself can still receive this read's leading insertion / deletion, :307-313)
         if (!window.empty() && pos - 1 > base + (int64_t)window.size()) flush(pos - 1, false);
-        const char *seq = col[9];
-        const int64_t sl = (int64_t)len[9];
+        const char *seq = line.col[9];
+        const int64_t sl = (int64_t)line.len[9];
         int64_t rp = pos, qp = 0, adv = 0;
         for (size_t i = 0; i < cl; ++i) {
             const char ch = cigar[i];
@@ -728,11 +662,11 @@ struct clair_evc {
                 qp += adv;
             } else if (ch == 'M' || ch == '=' || ch == 'X') {
                 for (int64_t k = 0; k < adv; ++k) {
-                    if (qp >= sl) return clair_host_fail("read at %lld: CIGAR walks past the end of SEQ (%lld bases)", (long long)v[0], (long long)sl);
+                    if (qp >= sl) return clair_host_fail("read at %lld: CIGAR walks past the end of SEQ (%lld bases)", (long long)pos1, (long long)sl);
                     unsigned char b = (unsigned char)seq[qp];
                     if (b >= 'a' && b <= 'z') b = (unsigned char)(b - 32);
                     const int bi = ACGT.idx[b];
-                    if (bi < 0) return clair_host_fail("read at %lld: SEQ holds '%c', not an IUPAC base code", (long long)v[0], (char)b);
+                    if (bi < 0) return clair_host_fail("read at %lld: SEQ holds '%c', not an IUPAC base code", (long long)pos1, (char)b);
                     at(rp).n[bi] += 1;
                     ++rp;
                     ++qp;
@@ -788,20 +722,7 @@ int clair_host_evc_create(const char *ctg_name, const char *ref_seq, int64_t ref
 
 void clair_host_evc_destroy(clair_evc_t *e) { delete e; }
 
-int clair_host_evc_feed(clair_evc_t *e, const char *sam, int64_t len, int final, int64_t *bytes_consumed) {
-    if (!e || (!sam && len > 0) || !bytes_consumed) return clair_host_fail("bad argument");
-    int64_t at = 0;
-    while (at < len) {
-        const char *nl = (const char *)memchr(sam + at, '\n', (size_t)(len - at));
-        if (!nl && !final) break;
-        const char *end = nl ? nl : sam + len;
-        if (e->add_line(sam + at, end, e->lines_seen)) { *bytes_consumed = at; return 1; }
-        ++e->lines_seen;
-        at = (nl ? nl + 1 : end) - sam;
-    }
-    *bytes_consumed = at;
-    return 0;
-}
+int clair_host_evc_feed(clair_evc_t *e, const char *sam, int64_t len, int final, int64_t *bytes_consumed) { return feed_lines(e, sam, len, final, bytes_consumed); }
 
 int clair_host_evc_finish(clair_evc_t *e) {
     if (!e) return clair_host_fail("bad argument");

@@ -8,6 +8,7 @@
 // oracle/frontend_np.py: pack_sam is the Python twin this file is tested against (tests/test_frontend.py).
 #include "../../include/clair_host.h"
 #include "../../include/clair_reads.h"
+#include "sam_line.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -15,13 +16,9 @@
 #include <string>
 #include <vector>
 
-int clair_host_fail(const char *fmt, ...);   // host_io.cpp
-
 namespace {
 
 constexpr int64_t LOOKAHEAD = 100000;        // CreateTensor.py:275
-
-inline bool is_space(unsigned char c) { return c == ' ' || (c >= 9 && c <= 13) || (c >= 0x1c && c <= 0x1f); }
 
 }  // namespace
 
@@ -54,41 +51,15 @@ struct clair_sampack {
     }
 
     int add_line(const char *p, const char *end, int64_t line_no) {
-        // str.split(): columns 1..5 and 9 of a whitespace-separated line
-        const char *col[10];
-        size_t len[10];
-        int n = 0;
-        while (p < end && n < 10) {
-            while (p < end && is_space((unsigned char)*p)) ++p;
-            if (p >= end) break;
-            const char *q = p;
-            while (q < end && !is_space((unsigned char)*q)) ++q;
-            col[n] = p;
-            len[n] = (size_t)(q - p);
-            ++n;
-            p = q;
-        }
-        if (n == 0) return clair_host_fail("alignment line %lld is empty", (long long)line_no);
-        if (col[0][0] == '@') return 0;
-        if (n < 10) return clair_host_fail("alignment line %lld has %d columns (11 expected)", (long long)line_no, n);
-        int64_t v[3];
-        const int which[3] = {1, 3, 4};
-        for (int i = 0; i < 3; ++i) {
-            const char *s = col[which[i]], *e = s + len[which[i]];
-            bool neg = false;
-            if (s < e && (*s == '-' || *s == '+')) { neg = *s == '-'; ++s; }
-            if (s == e || e - s > 18) return clair_host_fail("alignment line %lld: column %d is not an integer", (long long)line_no, which[i] + 1);
-            int64_t x = 0;
-            for (; s < e; ++s) {
-                if (*s < '0' || *s > '9') return clair_host_fail("alignment line %lld: column %d is not an integer", (long long)line_no, which[i] + 1);
-                x = x * 10 + (*s - '0');
-            }
-            v[i] = neg ? -x : x;
-        }
-        const int64_t flag = v[0], pos1 = v[1], mq = v[2], pos = pos1 - 1;
-        const char *cigar = col[5];
-        const size_t cl = len[5], sl = len[9];
-        const bool same_ctg = len[2] == ctg.size() && memcmp(col[2], ctg.data(), ctg.size()) == 0;
+        SamLine line;
+        const SamSplit split = split_sam_line(p, end, line_no, &line);
+        if (split != SAM_OK) return split == SAM_ERROR;
+        int64_t flag, pos1, mq;
+        if (!sam_int(line, 1, line_no, &flag) || !sam_int(line, 3, line_no, &pos1) || !sam_int(line, 4, line_no, &mq)) return 1;
+        const int64_t pos = pos1 - 1;
+        const char *cigar = line.col[5];
+        const size_t cl = line.len[5], sl = line.len[9];
+        const bool same_ctg = line.len[2] == ctg.size() && memcmp(line.col[2], ctg.data(), ctg.size()) == 0;
 
         // the CIGAR, once: the operations, the aligned fraction of the candidate search (EVC :143-157), samtools' reference length
         const size_t op_first = ops.size();
@@ -125,7 +96,7 @@ struct clair_sampack {
             total += adv;
             adv = 0;
         }
-        const bool evc_ok = same_ctg && mq >= evc_min_mq && !(cl == 1 && cigar[0] == '*') && !(1.0 - (double)soft / (double)(total + 1) < 0.55);
+        const bool evc_ok = same_ctg && mq >= evc_min_mq && !(cl == 1 && cigar[0] == '*') && !mostly_clipped(soft, total);
         bool in_region = true;
         if (have_region) {
             const int64_t end1 = pos1 + (rlen > 0 ? rlen : 1) - 1;    // bam_endpos
@@ -172,7 +143,7 @@ struct clair_sampack {
         reads.push_back(r);
         const size_t at = seq.size();
         seq.resize(at + sl);
-        const unsigned char *s = (const unsigned char *)col[9];
+        const unsigned char *s = (const unsigned char *)line.col[9];
         uint8_t *d = seq.data() + at;
         for (size_t i = 0; i < sl; ++i) {
             const unsigned char c = s[i];
@@ -205,20 +176,7 @@ int clair_host_sampack_create(const char *ctg_name, int dcov, int evc_min_mq, in
 
 void clair_host_sampack_destroy(clair_sampack_t *p) { delete p; }
 
-int clair_host_sampack_feed(clair_sampack_t *p, const char *sam, int64_t len, int final, int64_t *bytes_consumed) {
-    if (!p || (!sam && len > 0) || !bytes_consumed) return clair_host_fail("bad argument");
-    int64_t at = 0;
-    while (at < len) {
-        const char *nl = (const char *)memchr(sam + at, '\n', (size_t)(len - at));
-        if (!nl && !final) break;
-        const char *end = nl ? nl : sam + len;
-        if (p->add_line(sam + at, end, p->lines_seen)) { *bytes_consumed = at; return 1; }
-        ++p->lines_seen;
-        at = (nl ? nl + 1 : end) - sam;
-    }
-    *bytes_consumed = at;
-    return 0;
-}
+int clair_host_sampack_feed(clair_sampack_t *p, const char *sam, int64_t len, int final, int64_t *bytes_consumed) { return feed_lines(p, sam, len, final, bytes_consumed); }
 
 int clair_host_sampack_stats(const clair_sampack_t *p, int64_t *stats) {
     if (!p || !stats) return clair_host_fail("bad argument");

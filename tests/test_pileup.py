@@ -228,6 +228,57 @@ def test_malformed_alignments_are_reported():
     assert b.feed(b"@HD\tVN:1.6\nr1\t0\tc\t1\t60\t10M\t*\t0\t0\tACGTACGTAC\tIIIIIIIIII\npartial") == b"partial"
 
 
+def _sam_line(flag="0", rname="c", pos="1", mapq="60"):
+    return ("r1\t%s\t%s\t%s\t%s\t10M\t*\t0\t0\tACGTACGTAC\tIIIIIIIIII\n" % (flag, rname, pos, mapq)).encode()
+
+
+LINE_SINKS = {
+    "pileup": lambda: _hostapi.PileupBuilder("c", "ACGT" * 50, 0, [20, 198]),
+    "finder": lambda: _hostapi.CandidateFinder("c", "ACGT" * 50, 0),
+    "packer": lambda: _hostapi.SamPacker("c"),
+}
+# what each sink has taken in so far: alignments the pileup builder walked, the candidate finder accepted, the packer packed
+LINE_SINK_READS = {"pileup": lambda s: s.stats()["reads"], "finder": lambda s: s.reads, "packer": lambda s: s.stats()["reads"]}
+# (text fed, outcome per sink): a str is the exact message of the PileupError, an int the alignments taken in; one outcome = all three sinks
+LINE_CASES = {
+    "six_columns": (_sam_line() + b"r2\t0\tc\t1\t60\t10M\n", "alignment line 1 has 6 columns (11 expected)"),
+    "empty_line": (_sam_line() + b"\n", "alignment line 1 is empty"),
+    "pos_not_a_number": (_sam_line(pos="x"), "alignment line 0: column 4 is not an integer"),
+    "flag_not_a_number": (_sam_line(flag="zz"), {"pileup": "alignment line 0: column 2 is not an integer", "finder": 1,      # FLAG is never read there
+                                                 "packer": "alignment line 0: column 2 is not an integer"}),
+    "other_contig_and_bad_pos": (_sam_line(rname="d", pos="x"), {"pileup": "alignment line 0: column 4 is not an integer",
+                                                                 "finder": 0,                   # RNAME is compared before any integer is parsed
+                                                                 "packer": "alignment line 0: column 4 is not an integer"}),
+    "mapq_of_19_digits": (_sam_line(mapq="1" * 19), "alignment line 0: column 5 is not an integer"),
+    "plus_signs": (_sam_line(flag="+0", pos="+1", mapq="+60"), 1),
+    "header_line_and_partial_last_line": (b"@HD\tVN:1.6\n" + _sam_line() + b"partial", 1),
+}
+
+
+@pytest.mark.parametrize("sink", sorted(LINE_SINKS))
+@pytest.mark.parametrize("case", sorted(LINE_CASES))
+def test_alignment_lines_are_read_alike_by_every_sink(case, sink):
+    """The line reader the three consumers of `samtools view` text share: the same messages for the same lines, and each stage's own order
+    of looking at the columns (the candidate finder never reads FLAG and compares RNAME before it parses a number)."""
+    sam, want = LINE_CASES[case]
+    want = want[sink] if isinstance(want, dict) else want
+    s = LINE_SINKS[sink]()
+    if isinstance(want, str):
+        with pytest.raises(ct.PileupError) as err:
+            s.feed(sam)
+        assert str(err.value) == want
+        # the failing line was not counted: a bad line fed next carries the same number
+        with pytest.raises(ct.PileupError) as err:
+            s.feed(b"r3\t0\tc\n")
+        assert str(err.value) == "alignment line %s has 3 columns (11 expected)" % want.split()[2].rstrip(":")
+    else:
+        assert s.feed(sam) == (b"partial" if sam.endswith(b"partial") else b"")
+        assert LINE_SINK_READS[sink](s) == want
+        with pytest.raises(ct.PileupError) as err:           # every complete line was counted, the @ line included
+            s.feed(b"r3\t0\tc\n")
+        assert str(err.value) == "alignment line %d has 3 columns (11 expected)" % sam.count(b"\n")
+
+
 def test_cli_without_arguments_prints_help_and_exits_1():
     r = subprocess.run([sys.executable, "-m", "clair_amd.create_tensor"], capture_output=True, text=True, cwd=ROOT)
     assert r.returncode == 1 and "--can_fn" in r.stdout
