@@ -22,6 +22,8 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <deque>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -68,12 +70,29 @@ constexpr int PQ_BITS = 21;
 constexpr unsigned long long PQ_MASK = (1ull << PQ_BITS) - 1;
 __device__ inline uint32_t pq_field(unsigned long long w, int field) { return (uint32_t)((w >> (field * PQ_BITS)) & PQ_MASK); }
 
+// a device allocation that is freed with its owner: what the handle and its slabs hold (kernels take the plain views below)
+struct DeviceBuffer {
+    void *p = nullptr;
+    size_t bytes = 0;
+    DeviceBuffer() = default;
+    DeviceBuffer(const DeviceBuffer &) = delete;
+    DeviceBuffer &operator=(const DeviceBuffer &) = delete;
+    ~DeviceBuffer() { reset(); }
+    void reset() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+    hipError_t ensure(size_t n) {      // exactly n bytes (at least one): kept when it has them, freed and allocated anew when the size changes
+        n = std::max<size_t>(n, 1);
+        if (p && bytes == n) return hipSuccess;
+        reset();
+        const hipError_t e = hipMalloc(&p, n);
+        if (e == hipSuccess) bytes = n; else p = nullptr;
+        return e;
+    }
+    template <typename T> T *as() const { return (T *)p; }
+};
+
 struct Slab {
-    clair_read_t *reads = nullptr;
-    clair_op_t *ops = nullptr;
-    uint32_t *op_elem = nullptr;
-    uint8_t *seq = nullptr;
-    uint64_t *tuples = nullptr;      // per read, pass 2
+    DeviceBuffer reads, ops, op_elem, seq;   // clair_read_t, clair_op_t, uint32_t [n_ops + 1], uint8_t
+    DeviceBuffer tuples;                     // uint64_t per read, pass 2
     int64_t n_reads = 0, n_ops = 0, n_elem = 0, seq_bytes = 0;
 };
 
@@ -394,65 +413,102 @@ __global__ __launch_bounds__(256) void fe_given_flags_kernel(const int64_t *posi
     if (t >= 0 && t < n) flags[t] = 1;
 }
 
-// ---- flags -> exclusive prefix (uint32, n + 1 entries) and the list of flagged indices; 4096 flags per workgroup ---------------
+// ---- the block scan: sums of 4096 items per workgroup, one workgroup over the block sums, then every workgroup writes ---------------
+// Instantiated for flags -> exclusive prefix (uint32, n + 1 entries) and the list of flagged indices (candidates, kept windows, kept lines;
+// line feeds of the text), and for 64-bit inclusive running sums (the candidate prefix; the second differences of pass 2, in place).
 constexpr int SCAN_ITEMS = 16, SCAN_BLOCK = 256 * SCAN_ITEMS;
 
-__device__ inline uint32_t block_exclusive_scan(uint32_t v, uint32_t *total) {   // 256 threads
-    __shared__ uint32_t wave_sum[4];
+template <typename T> __device__ inline T block_exclusive_scan(T v, T *total) {   // 256 threads
+    __shared__ T wave_sum[4];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t x = v;
+    T x = v;
     for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d, 64);
+        const T y = __shfl_up(x, d, 64);
         if (lane >= d) x += y;
     }
     if (lane == 63) wave_sum[w] = x;
     __syncthreads();
-    uint32_t before = 0, all = 0;
+    T before = 0, all = 0;
     for (int i = 0; i < 4; ++i) { if (i < w) before += wave_sum[i]; all += wave_sum[i]; }
     __syncthreads();
     *total = all;
     return before + x - v;
 }
 
-// NEWLINES: the "flags" are text and a line feed is a set flag
-template <bool NEWLINES> __device__ inline uint8_t flag_of(const uint8_t *flags, int64_t i) { return NEWLINES ? (uint8_t)(flags[i] == '\n') : flags[i]; }
+// how an item is loaded: an In widened to the Sum the scan runs in (signed sums in two's complement) ...
+template <typename In, typename Sum> struct ScanValues {
+    using in_t = In;
+    using sum_t = Sum;
+    static __device__ inline Sum value(In item) { return (Sum)item; }
+};
+using ScanU32 = ScanValues<uint32_t, unsigned long long>;
+using ScanU64 = ScanValues<unsigned long long, unsigned long long>;
+using ScanInt = ScanValues<int, long long>;
+// ... or a byte that counts one when it is set (NEWLINES: the bytes are text and a line feed is a set flag)
+template <bool NEWLINES> struct ScanBytes {
+    using in_t = uint8_t;
+    using sum_t = uint32_t;
+    static __device__ inline uint32_t value(uint8_t item) { return NEWLINES ? item == '\n' : item != 0; }
+};
+using ScanFlags = ScanBytes<false>;
+using ScanNewlines = ScanBytes<true>;
 
-template <bool NEWLINES>
-__global__ __launch_bounds__(256) void fe_block_count_kernel(const uint8_t *flags, int64_t n, uint32_t *block_sum) {
+// what is written for item i, `before` the sum of the items before it.  Flags: the exclusive prefix (optional; entry n = the total) and the list of set indices
+struct WriteCompact {
+    static constexpr int PAST_END = 1;      // the thread that owns index n writes the total
+    uint32_t *prefix;
+    int64_t *list, list_base;
+    __device__ inline uint32_t seed() const { return 0; }
+    __device__ inline void write(int64_t i, int64_t n, uint32_t before, uint32_t item) const {
+        if (prefix) prefix[i] = before;
+        if (i < n && item) list[before] = list_base + i;
+    }
+};
+// the inclusive running sum, seeded with 0 (fold == NULL), fold[0], or (second) lo fold[0] - fold[1]: see fe_windows_per_op_noleft_kernel
+struct WriteRunning {
+    static constexpr int PAST_END = 0;
+    unsigned long long *out;
+    const unsigned long long *fold;
+    int second;
+    int64_t lo;
+    __device__ inline unsigned long long seed() const { return !fold ? 0 : second ? (unsigned long long)lo * fold[0] - fold[1] : fold[0]; }
+    __device__ inline void write(int64_t i, int64_t, unsigned long long before, unsigned long long item) const { out[i] = before + item; }
+};
+
+template <typename L>
+__global__ __launch_bounds__(256) void fe_scan_sums_kernel(const typename L::in_t *v, int64_t n, typename L::sum_t *block_sum) {
     const int64_t at = (int64_t)blockIdx.x * SCAN_BLOCK + (int64_t)threadIdx.x * SCAN_ITEMS;
-    uint32_t c = 0;
-    for (int i = 0; i < SCAN_ITEMS; ++i) if (at + i < n) c += flag_of<NEWLINES>(flags, at + i);
-    uint32_t total;
+    typename L::sum_t c = 0, total;
+    for (int i = 0; i < SCAN_ITEMS; ++i) if (at + i < n) c += L::value(v[at + i]);
     (void)block_exclusive_scan(c, &total);
     if (threadIdx.x == 0) block_sum[blockIdx.x] = total;
 }
 
-__global__ __launch_bounds__(256) void fe_scan_block_sums_kernel(uint32_t *block_sum, int64_t n_blocks, uint32_t *grand_total) {
-    uint32_t carry = 0;                      // one workgroup walks the block sums 256 at a time
-    for (int64_t at = 0; at < n_blocks; at += 256) {
+// one workgroup walks n items 256 at a time: out[i] = the sum of the items before i (INCLUSIVE: and of item i); in place where out is v
+template <typename L, bool INCLUSIVE>
+__global__ __launch_bounds__(256) void fe_scan_serial_kernel(const typename L::in_t *v, int64_t n, typename L::sum_t *out, typename L::sum_t *grand_total) {
+    typename L::sum_t carry = 0, total;
+    for (int64_t at = 0; at < n; at += 256) {
         const int64_t i = at + threadIdx.x;
-        const uint32_t v = i < n_blocks ? block_sum[i] : 0;
-        uint32_t total;
-        const uint32_t ex = block_exclusive_scan(v, &total);
-        if (i < n_blocks) block_sum[i] = carry + ex;
+        const typename L::sum_t x = i < n ? L::value(v[i]) : 0;
+        const typename L::sum_t ex = block_exclusive_scan(x, &total);
+        if (i < n) out[i] = carry + ex + (INCLUSIVE ? x : 0);
         carry += total;
     }
-    if (threadIdx.x == 0) *grand_total = carry;
+    if (grand_total && threadIdx.x == 0) *grand_total = carry;
 }
 
-template <bool NEWLINES>
-__global__ __launch_bounds__(256) void fe_scan_write_kernel(const uint8_t *flags, int64_t n, const uint32_t *block_sum, uint32_t *prefix,
-                                                            int64_t *list, int64_t list_base) {
+template <typename L, typename W>
+__global__ __launch_bounds__(256) void fe_scan_write_kernel(const typename L::in_t *v, int64_t n, const typename L::sum_t *block_sum, W w) {
     const int64_t at = (int64_t)blockIdx.x * SCAN_BLOCK + (int64_t)threadIdx.x * SCAN_ITEMS;
-    uint8_t f[SCAN_ITEMS];
-    uint32_t c = 0;
-    for (int i = 0; i < SCAN_ITEMS; ++i) { f[i] = at + i < n ? flag_of<NEWLINES>(flags, at + i) : 0; c += f[i]; }
-    uint32_t total;
-    uint32_t run = block_sum[blockIdx.x] + block_exclusive_scan(c, &total);
+    typename L::in_t f[SCAN_ITEMS];
+    typename L::sum_t c = 0, total;
+    for (int i = 0; i < SCAN_ITEMS; ++i) { f[i] = at + i < n ? v[at + i] : 0; c += L::value(f[i]); }
+    typename L::sum_t run = w.seed() + block_sum[blockIdx.x] + block_exclusive_scan(c, &total);
     for (int i = 0; i < SCAN_ITEMS; ++i) {
-        if (at + i > n) break;
-        if (prefix) prefix[at + i] = run;     // entry n = the total
-        if (at + i < n && f[i]) { list[run] = list_base + at + i; ++run; }
+        if (at + i >= n + W::PAST_END) break;
+        w.write(at + i, n, run, L::value(f[i]));
+        run += L::value(f[i]);
     }
 }
 
@@ -474,6 +530,30 @@ constexpr int LATE_ROW = 12;
 
 __device__ inline uint32_t before_at(const Region &g, const Candidates &c, int64_t t) {
     return c.before[t < 0 ? 0 : (t > g.n ? g.n : t)];
+}
+
+// generate_tensor :51-53: the k-th base (row: its base row + 4 on the reverse strand) of an insertion at rp into the windows i0 .. i1 - 1 that
+// hold it: column min(idx + k, 32), channel 1
+__device__ inline void scatter_inserted_base(const Candidates &c, uint32_t i0, uint32_t i1, int64_t rp, int64_t k, int row) {
+    for (uint32_t i = i0; i < i1; ++i) {
+        const int64_t col = rp - c.centre[i] + 17 + k;
+        atomicAdd(&c.ins[((size_t)i * N_POS + (col < N_POS - 1 ? col : N_POS - 1)) * N_ROW + row], 1u);
+    }
+}
+
+// nc tuples of `read` from every lane (whole waves only): one atomic per run of equal reads in the wave (64 consecutive bases or operations are
+// nearly always one alignment's): 64 lanes adding to one address serialise at the memory side, which made this pass four times the first one
+__device__ inline void add_read_tuples(const SlabView &s, uint32_t read, unsigned long long nc) {
+    unsigned long long todo = __ballot(nc != 0);
+    while (todo) {
+        const int leader = __ffsll((long long)todo) - 1;
+        const uint32_t r = __shfl(read, leader, 64);
+        const bool mine = nc != 0 && read == r;
+        unsigned long long v = mine ? nc : 0;
+        for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+        if ((int)(threadIdx.x & 63) == leader) atomicAdd((unsigned long long *)&s.tuples[r], v);
+        todo &= ~__ballot(mine);
+    }
 }
 
 __global__ __launch_bounds__(256) void fe_windows_per_base_kernel(Region g, SlabView s, Candidates c) {
@@ -519,27 +599,12 @@ __global__ __launch_bounds__(256) void fe_windows_per_base_kernel(Region g, Slab
                 if (row != 255) {
                     int64_t first = el.rp - 15;
                     if (!left_edge && first < el.r.pos0 + 17) first = el.r.pos0 + 17;
-                    const uint32_t i0 = before_at(g, c, first - 1 - g.lo), i1 = before_at(g, c, el.rp + 16 - g.lo);
-                    for (uint32_t i = i0; i < i1; ++i) {       // generate_tensor :51-53: column min(idx + k, 32), channel 1
-                        const int64_t col = el.rp - c.centre[i] + 17 + (int64_t)el.k;
-                        atomicAdd(&c.ins[((size_t)i * N_POS + (col < N_POS - 1 ? col : N_POS - 1)) * N_ROW + row + so], 1u);
-                    }
+                    scatter_inserted_base(c, before_at(g, c, first - 1 - g.lo), before_at(g, c, el.rp + 16 - g.lo), el.rp, (int64_t)el.k, row + so);
                 }
             }
         }
     }
-    // one atomic per run of equal reads in the wave (64 consecutive bases are nearly always one alignment's): 64 lanes adding to one
-    // address serialise at the memory side, which made this pass four times the first one
-    unsigned long long todo = __ballot(nc != 0);
-    while (todo) {
-        const int leader = __ffsll((long long)todo) - 1;
-        const uint32_t r = __shfl(read, leader, 64);
-        const bool mine = nc != 0 && read == r;
-        unsigned long long v = mine ? nc : 0;
-        for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-        if ((int)(threadIdx.x & 63) == leader) atomicAdd((unsigned long long *)&s.tuples[r], v);
-        todo &= ~__ballot(mine);
-    }
+    add_read_tuples(s, read, nc);
 }
 
 // ---- pass 2 with left-edge windows, per OPERATION: the windows open over a run of positions is a difference of sums of the prefix ----
@@ -579,28 +644,15 @@ __global__ __launch_bounds__(256) void fe_windows_per_op_kernel(Region g, SlabVi
                 nc += (unsigned long long)len * (before_at(g, c, a + 16 - g.lo) - before_at(g, c, a - 18 - g.lo));
                 const int so = (r.flags & CLAIR_READ_REVERSE) ? 4 : 0;
                 const uint32_t i0 = before_at(g, c, a - 15 - 1 - g.lo), i1 = before_at(g, c, a + 16 - g.lo);
-                for (int64_t k = 0; k < len && i1 > i0; ++k) {         // generate_tensor :51-53: column min(idx + k, 32), channel 1
+                for (int64_t k = 0; k < len && i1 > i0; ++k) {
                     if (op.q_off + k >= r.seq_len) break;
                     const uint8_t row = BASES.pile[s.seq[r.seq0 + op.q_off + k]];
-                    if (row == 255) continue;
-                    for (uint32_t i = i0; i < i1; ++i) {
-                        const int64_t col = a - c.centre[i] + 17 + k;
-                        atomicAdd(&c.ins[((size_t)i * N_POS + (col < N_POS - 1 ? col : N_POS - 1)) * N_ROW + row + so], 1u);
-                    }
+                    if (row != 255) scatter_inserted_base(c, i0, i1, a, k, row + so);
                 }
             }
         }
     }
-    unsigned long long todo = __ballot(nc != 0);                       // one atomic per run of equal reads in the wave
-    while (todo) {
-        const int leader = __ffsll((long long)todo) - 1;
-        const uint32_t r = __shfl(read, leader, 64);
-        const bool mine = nc != 0 && read == r;
-        unsigned long long v = mine ? nc : 0;
-        for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-        if ((int)(threadIdx.x & 63) == leader) atomicAdd((unsigned long long *)&s.tuples[r], v);
-        todo &= ~__ballot(mine);
-    }
+    add_read_tuples(s, read, nc);
 }
 
 // ---- pass 2 WITHOUT left-edge windows, per operation (round 4; per base: fe_windows_per_base_kernel above, kept as the checker) ----
@@ -610,7 +662,7 @@ __global__ __launch_bounds__(256) void fe_windows_per_op_kernel(Region g, SlabVi
 //     multiple of one prefix value;
 //   * the tuples PER WINDOW are a trapezoid over u (a ramp of min(length, window width) centres up, a plateau, the same ramp down), cut off
 //     below POS + 17: six second-difference entries over the centre VALUE instead of two range additions per base over the candidate index;
-//     two running sums over the positions and a gather at the centres give the totals (fe_tuple_scan_*, fe_window_totals_at_kernel).
+//     two running sums over the positions and a gather at the centres give the totals (the block scan with WriteRunning, fe_window_totals_at_kernel).
 __device__ inline void d2_add(const Region &g, const Candidates &c, int64_t u, long long v) {
     const int64_t i = u - g.lo;
     if (i < 0) { atomicAdd(&c.fold[0], (unsigned long long)v); atomicAdd(&c.fold[1], (unsigned long long)(v * u)); }
@@ -672,28 +724,15 @@ __global__ __launch_bounds__(256) void fe_windows_per_op_noleft_kernel(Region g,
                 const int so = (r.flags & CLAIR_READ_REVERSE) ? 4 : 0;
                 const int64_t first = a - 15 > c0 ? a - 15 : c0;
                 const uint32_t i0 = before_at(g, c, first - 1 - g.lo), i1 = before_at(g, c, a + 16 - g.lo);
-                for (int64_t k = 0; k < len && i1 > i0; ++k) {         // generate_tensor :51-53: column min(idx + k, 32), channel 1
+                for (int64_t k = 0; k < len && i1 > i0; ++k) {
                     if (op.q_off + k >= r.seq_len) break;
                     const uint8_t row = BASES.pile[s.seq[r.seq0 + op.q_off + k]];
-                    if (row == 255) continue;
-                    for (uint32_t i = i0; i < i1; ++i) {
-                        const int64_t col = a - c.centre[i] + 17 + k;
-                        atomicAdd(&c.ins[((size_t)i * N_POS + (col < N_POS - 1 ? col : N_POS - 1)) * N_ROW + row + so], 1u);
-                    }
+                    if (row != 255) scatter_inserted_base(c, i0, i1, a, k, row + so);
                 }
             }
         }
     }
-    unsigned long long todo = __ballot(nc != 0);                       // one atomic per run of equal reads in the wave
-    while (todo) {
-        const int leader = __ffsll((long long)todo) - 1;
-        const uint32_t r = __shfl(read, leader, 64);
-        const bool mine = nc != 0 && read == r;
-        unsigned long long v = mine ? nc : 0;
-        for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-        if ((int)(threadIdx.x & 63) == leader) atomicAdd((unsigned long long *)&s.tuples[r], v);
-        todo &= ~__ballot(mine);
-    }
+    add_read_tuples(s, read, nc);
 }
 
 // what the first 32 walked positions of an alignment put into the tables belongs to none of the windows it starts inside (centres rp - 15 ..
@@ -729,28 +768,9 @@ __global__ __launch_bounds__(256) void fe_late_starters_kernel(Region g, SlabVie
     }
 }
 
-__device__ inline unsigned long long block_exclusive_scan64(unsigned long long v, unsigned long long *total);   // below, with the candidate prefix's running sum
-
-// running sums of a 64-bit array in place, twice in a row: d2 -> first differences (seeded with fold[0]) -> tuples per centre value (seeded with
-// the tuples of u = lo - 1: lo fold[0] - fold[1]).  Two's complement throughout: signed sums come out right modulo 2^64.
-__global__ __launch_bounds__(256) void fe_tuple_scan_sums_kernel(const unsigned long long *v, int64_t n, unsigned long long *block_sum) {
-    const int64_t at = (int64_t)blockIdx.x * SCAN_BLOCK + (int64_t)threadIdx.x * SCAN_ITEMS;
-    unsigned long long x = 0;
-    for (int i = 0; i < SCAN_ITEMS; ++i) if (at + i < n) x += v[at + i];
-    unsigned long long total;
-    (void)block_exclusive_scan64(x, &total);
-    if (threadIdx.x == 0) block_sum[blockIdx.x] = total;
-}
-__global__ __launch_bounds__(256) void fe_tuple_scan_write_kernel(unsigned long long *v, int64_t n, const unsigned long long *block_sum, const unsigned long long *fold,
-                                                                  int second, int64_t lo) {
-    const int64_t at = (int64_t)blockIdx.x * SCAN_BLOCK + (int64_t)threadIdx.x * SCAN_ITEMS;
-    unsigned long long f[SCAN_ITEMS], x = 0;
-    for (int i = 0; i < SCAN_ITEMS; ++i) { f[i] = at + i < n ? v[at + i] : 0; x += f[i]; }
-    unsigned long long total;
-    const unsigned long long seed = second ? (unsigned long long)lo * fold[0] - fold[1] : fold[0];
-    unsigned long long run = seed + block_sum[blockIdx.x] + block_exclusive_scan64(x, &total);
-    for (int i = 0; i < SCAN_ITEMS && at + i < n; ++i) { run += f[i]; v[at + i] = run; }
-}
+// the tuples per window from the second differences: two running sums in place (WriteRunning: d2 -> first differences, seeded with fold[0] ->
+// tuples per centre value, seeded with the tuples of u = lo - 1: lo fold[0] - fold[1]; two's complement throughout: signed sums come out
+// right modulo 2^64), then a gather at the centres
 __global__ __launch_bounds__(256) void fe_window_totals_at_kernel(const unsigned long long *tuples_at, const int64_t *centre, int64_t n_candidates, int64_t lo, int64_t n,
                                                                   uint64_t *window_tuples) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -759,75 +779,12 @@ __global__ __launch_bounds__(256) void fe_window_totals_at_kernel(const unsigned
     window_tuples[i] = at >= 0 && at <= n + 1 ? tuples_at[at] : 0;
 }
 
-// before[0..n] -> before_sum (inclusive running sum, 64 bit): block sums, one workgroup over them, write
-__device__ inline unsigned long long block_exclusive_scan64(unsigned long long v, unsigned long long *total) {   // 256 threads
-    __shared__ unsigned long long wave_sum64[4];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    unsigned long long x = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) wave_sum64[w] = x;
-    __syncthreads();
-    unsigned long long before = 0, all = 0;
-    for (int i = 0; i < 4; ++i) { if (i < w) before += wave_sum64[i]; all += wave_sum64[i]; }
-    __syncthreads();
-    *total = all;
-    return before + x - v;
-}
-
-__global__ __launch_bounds__(256) void fe_prefix_block_sums_kernel(const uint32_t *before, int64_t n, unsigned long long *block_sum) {
-    const int64_t at = (int64_t)blockIdx.x * SCAN_BLOCK + (int64_t)threadIdx.x * SCAN_ITEMS;
-    unsigned long long v = 0;
-    for (int i = 0; i < SCAN_ITEMS; ++i) if (at + i < n) v += before[at + i];
-    unsigned long long total;
-    (void)block_exclusive_scan64(v, &total);
-    if (threadIdx.x == 0) block_sum[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(256) void fe_prefix_scan_sums_kernel(unsigned long long *block_sum, int64_t n_blocks) {
-    unsigned long long carry = 0;
-    for (int64_t at = 0; at < n_blocks; at += 256) {
-        const int64_t i = at + threadIdx.x;
-        unsigned long long total;
-        const unsigned long long ex = block_exclusive_scan64(i < n_blocks ? block_sum[i] : 0, &total);
-        if (i < n_blocks) block_sum[i] = carry + ex;
-        carry += total;
-    }
-}
-
-__global__ __launch_bounds__(256) void fe_prefix_write_kernel(const uint32_t *before, int64_t n, const unsigned long long *block_sum, unsigned long long *before_sum) {
-    const int64_t at = (int64_t)blockIdx.x * SCAN_BLOCK + (int64_t)threadIdx.x * SCAN_ITEMS;
-    uint32_t f[SCAN_ITEMS];
-    unsigned long long v = 0;
-    for (int i = 0; i < SCAN_ITEMS; ++i) { f[i] = at + i < n ? before[at + i] : 0; v += f[i]; }
-    unsigned long long total;
-    unsigned long long run = block_sum[blockIdx.x] + block_exclusive_scan64(v, &total);
-    for (int i = 0; i < SCAN_ITEMS && at + i < n; ++i) { run += f[i]; before_sum[at + i] = run; }
-}
-
 // ---- per candidate: was its window ever opened, how many tuples did it hold, does it survive -----------------------------------
 struct WindowRule {
     int min_coverage;
     int drop_non_iupac_centre;   // clair/utils.py:90-91
-    const uint32_t *late;        // --stop_consider_left_edge: see Candidates; window_tuples then comes in filled (fe_window_totals_kernel)
+    const uint32_t *late;        // --stop_consider_left_edge: see Candidates; window_tuples then comes in filled (fe_window_totals_at_kernel, or the running sum of tuple_diff)
 };
-
-// --stop_consider_left_edge: tuples per window = running sum of the range additions of pass 2
-__global__ __launch_bounds__(256) void fe_window_totals_kernel(const int *diff, int64_t n_candidates, uint64_t *window_tuples) {
-    long long carry = 0;
-    for (int64_t at = 0; at < n_candidates; at += 256) {
-        const int64_t i = at + threadIdx.x;
-        const int v = i < n_candidates ? diff[i] : 0;
-        // signed values: scan the positive and the negative parts apart (the exclusive scan is unsigned)
-        uint32_t tp, tn;
-        const uint32_t ep = block_exclusive_scan(v > 0 ? (uint32_t)v : 0u, &tp);
-        const uint32_t en = block_exclusive_scan(v < 0 ? (uint32_t)(-v) : 0u, &tn);
-        if (i < n_candidates) window_tuples[i] = (uint64_t)(carry + (long long)ep - (long long)en + v);
-        carry += (long long)tp - (long long)tn;
-    }
-}
 
 __global__ __launch_bounds__(256) void fe_window_flags_kernel(Region g, const int64_t *centre, int64_t n_candidates, WindowRule rule,
                                                               uint8_t *keep, uint64_t *window_tuples) {
@@ -990,9 +947,7 @@ struct CigarWalk {
 
 // walks a CIGAR; EMIT writes the kept operations
 template <bool EMIT>
-__device__ inline void walk_cigar(const uint8_t *cg, uint32_t cl, uint32_t read, clair_op_t *ops, uint32_t *op_elem, uint32_t elem0,
-                                  int64_t *o_rp, int64_t *o_qp, int64_t *o_soft, int64_t *o_total, int64_t *o_rlen, uint32_t *o_ops, uint64_t *o_elems, bool *o_zero,
-                                  bool *o_lead = nullptr) {
+__device__ inline CigarWalk walk_cigar(const uint8_t *cg, uint32_t cl, uint32_t read, clair_op_t *ops, uint32_t *op_elem, uint32_t elem0) {
     int64_t adv = 0;
     CigarWalk w;
     for (uint32_t i = 0; i < cl; ++i) {
@@ -1001,7 +956,7 @@ __device__ inline void walk_cigar(const uint8_t *cg, uint32_t cl, uint32_t read,
         w.op<EMIT>(adv, ch, read, ops, op_elem, elem0);
         adv = 0;
     }
-    if (!EMIT) { *o_rp = w.rp; *o_qp = w.qp; *o_soft = w.soft; *o_total = w.total; *o_rlen = w.rlen; *o_ops = w.n_ops; *o_elems = w.elems; *o_zero = w.zero; if (o_lead) *o_lead = w.lead; }
+    return w;
 }
 
 __device__ inline bool text_int(const uint8_t *s, uint32_t len, int64_t *out) {     // [+-]digits, at most 18 of them (host_sampack.cpp)
@@ -1049,25 +1004,22 @@ __global__ __launch_bounds__(256) void fe_text_lines_kernel(const uint8_t *text,
     }
     bool same_ctg = (int)len[2] == opt.ctg_len;
     for (int i = 0; same_ctg && i < opt.ctg_len; ++i) same_ctg = text[col[2] + i] == opt.ctg[i];
-    int64_t rp, qp, soft, total, rlen;
-    uint32_t n_ops;
-    uint64_t elems;
-    bool zero, lead;
-    walk_cigar<false>(text + col[5], len[5], 0, nullptr, nullptr, 0, &rp, &qp, &soft, &total, &rlen, &n_ops, &elems, &zero, &lead);
-    const bool evc_ok = same_ctg && mq >= opt.evc_min_mq && !(len[5] == 1 && text[col[5]] == '*') && !(1.0 - (double)soft / (double)(total + 1) < 0.55);
+    const CigarWalk w = walk_cigar<false>(text + col[5], len[5], 0, nullptr, nullptr, 0);
+    const bool evc_ok = same_ctg && mq >= opt.evc_min_mq && !(len[5] == 1 && text[col[5]] == '*') && !(1.0 - (double)w.soft / (double)(w.total + 1) < 0.55);
     bool in_region = true;
     if (opt.pile_start >= 0 && opt.pile_end >= 0) {
-        const int64_t end1 = pos1 + (rlen > 0 ? rlen : 1) - 1;                // bam_endpos
+        const int64_t end1 = pos1 + (w.rlen > 0 ? w.rlen : 1) - 1;            // bam_endpos
         in_region = same_ctg && pos1 <= opt.pile_end && end1 >= opt.pile_start;
     }
     const bool candidate = in_region && mq >= opt.pile_min_mq;
     out.pos0 = pos1 - 1;
     out.cigar_off = col[5]; out.cigar_len = len[5];
     out.seq_off = col[9]; out.seq_len = len[9];
-    out.n_ops = n_ops;
-    out.n_elem = elems > 0xfffffff0ull ? 0xfffffff0u : (uint32_t)elems;
-    out.flags = ((flag & 16) ? CLAIR_READ_REVERSE : 0) | (evc_ok ? CLAIR_READ_EVC : 0) | (candidate ? TL_CANDIDATE : 0) | (zero ? TL_ZERO_INDEL : 0) | (lead ? TL_LEAD_INDEL : 0)
-                | ((rp > (int64_t)len[9] + 100000 - 64 || rp > 0x7fffff00 || qp > 0x7fffff00) ? TL_LONG_SPAN : 0);
+    out.n_ops = w.n_ops;
+    out.n_elem = w.elems > 0xfffffff0ull ? 0xfffffff0u : (uint32_t)w.elems;
+    out.flags = ((flag & 16) ? CLAIR_READ_REVERSE : 0) | (evc_ok ? CLAIR_READ_EVC : 0) | (candidate ? TL_CANDIDATE : 0) | (w.zero ? TL_ZERO_INDEL : 0)
+                | (w.lead ? TL_LEAD_INDEL : 0)
+                | ((w.rp > (int64_t)len[9] + 100000 - 64 || w.rp > 0x7fffff00 || w.qp > 0x7fffff00) ? TL_LONG_SPAN : 0);
     lines[k] = out;
     is_candidate[k] = candidate ? 1 : 0;
 }
@@ -1175,26 +1127,6 @@ __global__ __launch_bounds__(256) void fe_text_offsets_kernel(const TextLine *li
         }
         *state = st;
     }
-}
-
-__global__ __launch_bounds__(256) void fe_text_emit_kernel(const uint8_t *text, const TextLine *lines, const int64_t *kept, int64_t n_kept, const uint32_t *op0,
-                                                           const uint32_t *elem0, const uint32_t *seq0, clair_read_t *reads, clair_op_t *ops, uint32_t *op_elem,
-                                                           uint64_t total_ops, uint64_t total_elems) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i == 0) op_elem[total_ops] = (uint32_t)total_elems;
-    if (i >= n_kept) return;
-    const TextLine ln = lines[kept[i]];
-    walk_cigar<true>(text + ln.cigar_off, ln.cigar_len, (uint32_t)i, ops + op0[i], op_elem + op0[i], elem0[i], nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                     nullptr);
-    clair_read_t r;
-    r.pos0 = ln.pos0;
-    r.seq0 = seq0[i];
-    r.seq_len = ln.seq_len;
-    r.op0 = op0[i];
-    r.n_ops = ln.n_ops;
-    r.flags = ln.flags & (CLAIR_READ_REVERSE | CLAIR_READ_EVC | CLAIR_READ_PILE | CLAIR_READ_FLUSH);
-    r.reserved = 0;
-    reads[i] = r;
 }
 
 // The SEQ column of every kept line into the slab's packed buffer: a wave per alignment, a dword per lane and step.  The source starts at any
@@ -1365,14 +1297,17 @@ __global__ __launch_bounds__(256) void fe_bam_gather_kernel(const TextLine *all,
     is_candidate[j] = (ln.flags & TL_CANDIDATE) ? 1 : 0;
 }
 
-__global__ __launch_bounds__(256) void fe_bam_emit_kernel(const uint8_t *rec, const TextLine *lines, const int64_t *kept, int64_t n_kept, const uint32_t *op0,
-                                                          const uint32_t *elem0, const uint32_t *seq0, clair_read_t *reads, clair_op_t *ops, uint32_t *op_elem,
-                                                          uint64_t total_ops, uint64_t total_elems) {
+// the kept lines' alignments and their operations into the slab, from the text (`src` the text) or from the records (BAM: `src` the records)
+template <bool BAM>
+__global__ __launch_bounds__(256) void fe_emit_kernel(const uint8_t *src, const TextLine *lines, const int64_t *kept, int64_t n_kept, const uint32_t *op0,
+                                                      const uint32_t *elem0, const uint32_t *seq0, clair_read_t *reads, clair_op_t *ops, uint32_t *op_elem,
+                                                      uint64_t total_ops, uint64_t total_elems) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i == 0) op_elem[total_ops] = (uint32_t)total_elems;
     if (i >= n_kept) return;
     const TextLine ln = lines[kept[i]];
-    (void)walk_cigar_bam<true>(rec, ln.cigar_off, ln.cigar_len, (uint32_t)i, ops + op0[i], op_elem + op0[i], elem0[i]);
+    if (BAM) (void)walk_cigar_bam<true>(src, ln.cigar_off, ln.cigar_len, (uint32_t)i, ops + op0[i], op_elem + op0[i], elem0[i]);
+    else (void)walk_cigar<true>(src + ln.cigar_off, ln.cigar_len, (uint32_t)i, ops + op0[i], op_elem + op0[i], elem0[i]);
     clair_read_t r;
     r.pos0 = ln.pos0;
     r.seq0 = seq0[i];
@@ -1409,49 +1344,53 @@ int fe_fail(clair_frontend *f, const char *fmt, ...);
 
 }  // namespace
 
+// what depends on the candidate list: replaced as a whole when the candidates are fixed again
+struct CandidateBuffers {
+    DeviceBuffer centre;                         // int64_t
+    // windows
+    DeviceBuffer ins;                            // uint32_t
+    DeviceBuffer before_sum, prefix_block_sum;   // unsigned long long: running sum of `before` (pass 2 per operation)
+    DeviceBuffer late;                           // uint32_t, --stop_consider_left_edge only
+    DeviceBuffer tuple_diff;                     // int
+    DeviceBuffer keep;                           // uint8_t
+    DeviceBuffer window_tuples;                  // uint64_t
+    DeviceBuffer kept;                           // int64_t
+    DeviceBuffer block_sum;                      // uint32_t
+    DeviceBuffer counts, out_centre, out_refseq; // short4, int64_t, uint8_t: sized by the kept windows of the last build
+};
+
 struct clair_frontend {
     int device = 0;
     hipStream_t stream = nullptr;
     Region g{};
-    uint8_t *d_ref = nullptr;
-    std::vector<Slab> slabs;
+    DeviceBuffer ref, pq, misc, anomalies;       // what `g` points into
+    std::deque<Slab> slabs;                      // (a deque: a slab never moves)
     // candidates
-    uint8_t *d_flags = nullptr;          // per position
-    uint32_t *d_before = nullptr;        // n + 1
-    uint32_t *d_block_sum = nullptr;
-    uint32_t *d_total = nullptr;         // [2]: candidates, kept windows
-    int64_t *d_centre = nullptr;
-    int64_t n_candidates = -1, cap_candidates = 0;
-    int64_t *d_bed = nullptr;
-    // windows
-    uint32_t *d_ins = nullptr;
-    unsigned long long *d_before_sum = nullptr, *d_prefix_block_sum = nullptr;   // running sum of d_before (pass 2 per operation)
-    uint32_t *d_late = nullptr;          // --stop_consider_left_edge only
-    int *d_tuple_diff = nullptr;
-    uint8_t *d_keep = nullptr;
-    uint64_t *d_window_tuples = nullptr;
-    int64_t *d_kept = nullptr;
-    uint32_t *d_cand_block_sum = nullptr;
-    short4 *d_counts = nullptr;
-    int64_t *d_out_centre = nullptr;
-    uint8_t *d_out_refseq = nullptr;
+    DeviceBuffer flags;                  // uint8_t per position
+    DeviceBuffer before;                 // uint32_t, n + 1
+    DeviceBuffer block_sum;              // uint32_t
+    DeviceBuffer total;                  // uint32_t [2]: candidates, kept windows
+    int64_t n_candidates = -1;
+    DeviceBuffer bed;                    // int64_t
+    std::unique_ptr<CandidateBuffers> cand{new CandidateBuffers};
     int64_t n_windows = -1;
     // text parsed on the device (clair_frontend_text_options / _add_text)
     bool text_ready = false;
     TextOptions text_opt{};
-    uint8_t *d_ctg = nullptr;
+    DeviceBuffer ctg;
     TextState text_state{};
-    TextState *d_text_state = nullptr;
+    DeviceBuffer d_text_state;           // TextState
     bool bam_mode = false;               // clair_frontend_bam_options was called last: records come through _add_bam
     BamOptions bam_opt{};
-    uint32_t *d_span = nullptr;          // the longest reference reach of the slab being tallied (fe_slab_span_kernel)
-    unsigned long long *d_d2 = nullptr, *d_fold = nullptr;   // --stop_consider_left_edge, pass 2 per operation: tuples per window as second differences over positions
+    DeviceBuffer span;                   // uint32_t: the longest reference reach of the slab being tallied (fe_slab_span_kernel)
+    DeviceBuffer d2, fold;               // unsigned long long; --stop_consider_left_edge, pass 2 per operation: tuples per window as second differences over positions
     bool pass2_per_base = false;         // CLAIR_AMD_FE_PASS2=base when the handle was created: --stop_consider_left_edge's pass 2 by fe_windows_per_base_kernel
     bool tally_per_base = false;         // CLAIR_AMD_FE_TALLY=atomic when the handle was created: pass 1 by fe_tally_kernel (one device atomic per base)
     std::string error;
 
     SlabView view(const Slab &s) const {
-        return SlabView{s.reads, s.ops, s.op_elem, s.seq, s.tuples, (uint32_t)s.n_ops, (uint32_t)s.n_elem};
+        return SlabView{s.reads.as<clair_read_t>(), s.ops.as<clair_op_t>(), s.op_elem.as<uint32_t>(), s.seq.as<uint8_t>(), s.tuples.as<uint64_t>(),
+                        (uint32_t)s.n_ops, (uint32_t)s.n_elem};
     }
 };
 
@@ -1479,9 +1418,9 @@ inline unsigned blocks_for(int64_t n, int64_t per_block) { return (unsigned)((n 
 // flags[n] -> how many are set (block sums left scanned in block_sum for scan_write)
 int scan_count(clair_frontend *f, const uint8_t *flags, int64_t n, uint32_t *block_sum, uint32_t *d_count, int64_t *count, bool newlines = false) {
     const unsigned nb = blocks_for(n, SCAN_BLOCK);
-    if (n > 0 && newlines) hipLaunchKernelGGL(fe_block_count_kernel<true>, dim3(nb), dim3(256), 0, f->stream, flags, n, block_sum);
-    else if (n > 0) hipLaunchKernelGGL(fe_block_count_kernel<false>, dim3(nb), dim3(256), 0, f->stream, flags, n, block_sum);
-    hipLaunchKernelGGL(fe_scan_block_sums_kernel, dim3(1), dim3(256), 0, f->stream, block_sum, (int64_t)nb, d_count);
+    if (n > 0 && newlines) hipLaunchKernelGGL(fe_scan_sums_kernel<ScanNewlines>, dim3(nb), dim3(256), 0, f->stream, flags, n, block_sum);
+    else if (n > 0) hipLaunchKernelGGL(fe_scan_sums_kernel<ScanFlags>, dim3(nb), dim3(256), 0, f->stream, flags, n, block_sum);
+    hipLaunchKernelGGL((fe_scan_serial_kernel<ScanValues<uint32_t, uint32_t>, false>), dim3(1), dim3(256), 0, f->stream, (const uint32_t *)block_sum, (int64_t)nb, block_sum, d_count);
     FE_TRY(f, hipGetLastError());
     uint32_t total = 0;
     FE_TRY(f, hipMemcpyAsync(&total, d_count, sizeof total, hipMemcpyDeviceToHost, f->stream));
@@ -1496,26 +1435,25 @@ int scan_write(clair_frontend *f, const uint8_t *flags, int64_t n, uint32_t *blo
     // entry n of the prefix is written by the thread that owns index n: cover it with one more (empty) item
     const unsigned nb = blocks_for(n, SCAN_BLOCK), nbw = blocks_for(n + 1, SCAN_BLOCK);
     if (nbw > nb) FE_TRY(f, hipMemcpyAsync(block_sum + nb, d_count, sizeof(uint32_t), hipMemcpyDeviceToDevice, f->stream));
-    if (newlines) hipLaunchKernelGGL(fe_scan_write_kernel<true>, dim3(nbw), dim3(256), 0, f->stream, flags, n, (const uint32_t *)block_sum, prefix, list, list_base);
-    else hipLaunchKernelGGL(fe_scan_write_kernel<false>, dim3(nbw), dim3(256), 0, f->stream, flags, n, (const uint32_t *)block_sum, prefix, list, list_base);
+    const WriteCompact w{prefix, list, list_base};
+    if (newlines) hipLaunchKernelGGL((fe_scan_write_kernel<ScanNewlines, WriteCompact>), dim3(nbw), dim3(256), 0, f->stream, flags, n, (const uint32_t *)block_sum, w);
+    else hipLaunchKernelGGL((fe_scan_write_kernel<ScanFlags, WriteCompact>), dim3(nbw), dim3(256), 0, f->stream, flags, n, (const uint32_t *)block_sum, w);
     FE_TRY(f, hipGetLastError());
     return 0;
 }
 
+// v[n] -> its seeded inclusive running sum in 64 bits (w.out may be v); block_sum: one entry per SCAN_BLOCK items
+template <typename L>
+void running_sum(clair_frontend *f, const typename L::in_t *v, int64_t n, unsigned long long *block_sum, const WriteRunning &w) {
+    const unsigned nb = blocks_for(n, SCAN_BLOCK);
+    hipLaunchKernelGGL(fe_scan_sums_kernel<L>, dim3(nb), dim3(256), 0, f->stream, v, n, block_sum);
+    hipLaunchKernelGGL((fe_scan_serial_kernel<ScanU64, false>), dim3(1), dim3(256), 0, f->stream, (const unsigned long long *)block_sum, (int64_t)nb, block_sum,
+                       (unsigned long long *)nullptr);
+    hipLaunchKernelGGL((fe_scan_write_kernel<L, WriteRunning>), dim3(nb), dim3(256), 0, f->stream, v, n, (const unsigned long long *)block_sum, w);
+}
+
 void free_candidates(clair_frontend *f) {
-    (void)hipFree(f->d_centre); f->d_centre = nullptr;
-    (void)hipFree(f->d_ins); f->d_ins = nullptr;
-    (void)hipFree(f->d_before_sum); f->d_before_sum = nullptr;
-    (void)hipFree(f->d_prefix_block_sum); f->d_prefix_block_sum = nullptr;
-    (void)hipFree(f->d_late); f->d_late = nullptr;
-    (void)hipFree(f->d_tuple_diff); f->d_tuple_diff = nullptr;
-    (void)hipFree(f->d_keep); f->d_keep = nullptr;
-    (void)hipFree(f->d_window_tuples); f->d_window_tuples = nullptr;
-    (void)hipFree(f->d_kept); f->d_kept = nullptr;
-    (void)hipFree(f->d_cand_block_sum); f->d_cand_block_sum = nullptr;
-    (void)hipFree(f->d_counts); f->d_counts = nullptr;
-    (void)hipFree(f->d_out_centre); f->d_out_centre = nullptr;
-    (void)hipFree(f->d_out_refseq); f->d_out_refseq = nullptr;
+    f->cand.reset(new CandidateBuffers);
     f->n_candidates = -1;
     f->n_windows = -1;
 }
@@ -1524,12 +1462,54 @@ void free_candidates(clair_frontend *f) {
 int finish_candidates(clair_frontend *f, int64_t *n_candidates) {
     free_candidates(f);
     int64_t n = 0;
-    if (scan_count(f, f->d_flags, f->g.n, f->d_block_sum, f->d_total, &n)) return 1;
-    FE_TRY(f, hipMalloc((void **)&f->d_centre, (size_t)std::max<int64_t>(n, 1) * sizeof(int64_t)));
-    if (scan_write(f, f->d_flags, f->g.n, f->d_block_sum, f->d_total, f->d_before, f->d_centre, f->g.lo + 1)) return 1;
+    if (scan_count(f, f->flags.as<uint8_t>(), f->g.n, f->block_sum.as<uint32_t>(), f->total.as<uint32_t>(), &n)) return 1;
+    FE_TRY(f, f->cand->centre.ensure((size_t)n * sizeof(int64_t)));
+    if (scan_write(f, f->flags.as<uint8_t>(), f->g.n, f->block_sum.as<uint32_t>(), f->total.as<uint32_t>(), f->before.as<uint32_t>(), f->cand->centre.as<int64_t>(), f->g.lo + 1))
+        return 1;
     f->n_candidates = n;
     *n_candidates = n;
     return 0;
+}
+
+// a slab of these sizes, owned by the handle from here on, its tuples zeroed (on the stream)
+int new_slab(clair_frontend *f, int64_t n_reads, int64_t n_ops, int64_t n_elem, int64_t seq_bytes, Slab **out) {
+    f->slabs.emplace_back();
+    Slab &d = f->slabs.back();
+    d.n_reads = n_reads; d.n_ops = n_ops; d.n_elem = n_elem; d.seq_bytes = seq_bytes;
+    FE_TRY(f, d.reads.ensure((size_t)n_reads * sizeof(clair_read_t)));
+    FE_TRY(f, d.ops.ensure((size_t)n_ops * sizeof(clair_op_t)));
+    FE_TRY(f, d.op_elem.ensure(((size_t)n_ops + 1) * sizeof(uint32_t)));
+    FE_TRY(f, d.seq.ensure((size_t)std::max<int64_t>(seq_bytes, 16)));
+    FE_TRY(f, d.tuples.ensure((size_t)n_reads * sizeof(uint64_t)));
+    FE_TRY(f, hipMemsetAsync(d.tuples.p, 0, (size_t)n_reads * sizeof(uint64_t), f->stream));
+    *out = &d;
+    return 0;
+}
+
+// the part of clair_frontend_create that can fail on the device (the caller destroys the handle then)
+int frontend_init(clair_frontend *f, const char *ref_seq, int64_t ref_len) {
+    auto failed = [](const char *what, hipError_t err) { return err != hipSuccess && fe_fail(nullptr, "%s failed: %s", what, hipGetErrorString(err)); };
+    if (failed("hipSetDevice", hipSetDevice(f->device))) return 1;
+    if (failed("hipStreamCreate", hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking))) return 1;
+    Region &g = f->g;
+    if (failed("hipMalloc(reference)", f->ref.ensure((size_t)ref_len))) return 1;
+    if (failed("hipMemcpy(reference)", hipMemcpy(f->ref.p, ref_seq, (size_t)ref_len, hipMemcpyHostToDevice))) return 1;
+    const size_t table = (size_t)g.n * 32;
+    if (failed("hipMalloc(read-base counters)", f->pq.ensure(table))) return 1;
+    if (failed("hipMalloc(counts)", f->misc.ensure(table))) return 1;
+    if (failed("hipMalloc", f->anomalies.ensure(sizeof(uint32_t)))) return 1;
+    if (failed("hipMalloc(flags)", f->flags.ensure((size_t)g.n + 1))) return 1;
+    if (failed("hipMalloc(prefix)", f->before.ensure(((size_t)g.n + 1) * sizeof(uint32_t)))) return 1;
+    if (failed("hipMalloc", f->block_sum.ensure(((size_t)blocks_for(g.n + 1, SCAN_BLOCK) + 1) * sizeof(uint32_t)))) return 1;
+    if (failed("hipMalloc", f->total.ensure(2 * sizeof(uint32_t)))) return 1;
+    g.ref = f->ref.as<uint8_t>();
+    g.pq = f->pq.as<unsigned long long>();
+    g.misc = f->misc.as<uint32_t>();
+    g.anomalies = f->anomalies.as<uint32_t>();
+    (void)hipMemsetAsync(g.pq, 0, table, f->stream);
+    (void)hipMemsetAsync(g.misc, 0, table, f->stream);
+    (void)hipMemsetAsync(g.anomalies, 0, sizeof(uint32_t), f->stream);
+    return failed("hipMemset", hipStreamSynchronize(f->stream)) ? 1 : 0;
 }
 
 }  // namespace
@@ -1553,34 +1533,14 @@ int clair_frontend_create(int device, const char *ref_seq, int64_t ref_len, int6
     { const char *t = getenv("CLAIR_AMD_FE_TALLY"); f->tally_per_base = t && !strcmp(t, "atomic"); }
     { const char *t = getenv("CLAIR_AMD_FE_PASS2"); f->pass2_per_base = t && !strcmp(t, "base"); }
     f->device = device;
-    auto bail = [&](const char *what, hipError_t err) {
-        fe_fail(nullptr, "%s failed: %s", what, hipGetErrorString(err));
+    f->g.lo = span_lo;
+    f->g.n = span_hi - span_lo;
+    f->g.ref0 = reference_start_0_based;
+    f->g.ref_len = ref_len;
+    if (frontend_init(f, ref_seq, ref_len)) {
         clair_frontend_destroy(f);
         return 1;
-    };
-    hipError_t err;
-    if ((err = hipSetDevice(device)) != hipSuccess) return bail("hipSetDevice", err);
-    if ((err = hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", err);
-    Region &g = f->g;
-    g.lo = span_lo;
-    g.n = span_hi - span_lo;
-    g.ref0 = reference_start_0_based;
-    g.ref_len = ref_len;
-    if ((err = hipMalloc((void **)&f->d_ref, (size_t)std::max<int64_t>(ref_len, 1))) != hipSuccess) return bail("hipMalloc(reference)", err);
-    if ((err = hipMemcpy(f->d_ref, ref_seq, (size_t)ref_len, hipMemcpyHostToDevice)) != hipSuccess) return bail("hipMemcpy(reference)", err);
-    g.ref = f->d_ref;
-    const size_t table = (size_t)g.n * 32;
-    if ((err = hipMalloc((void **)&g.pq, table)) != hipSuccess) return bail("hipMalloc(read-base counters)", err);
-    if ((err = hipMalloc((void **)&g.misc, table)) != hipSuccess) return bail("hipMalloc(counts)", err);
-    if ((err = hipMalloc((void **)&g.anomalies, sizeof(uint32_t))) != hipSuccess) return bail("hipMalloc", err);
-    if ((err = hipMalloc((void **)&f->d_flags, (size_t)g.n + 1)) != hipSuccess) return bail("hipMalloc(flags)", err);
-    if ((err = hipMalloc((void **)&f->d_before, ((size_t)g.n + 1) * sizeof(uint32_t))) != hipSuccess) return bail("hipMalloc(prefix)", err);
-    if ((err = hipMalloc((void **)&f->d_block_sum, ((size_t)blocks_for(g.n + 1, SCAN_BLOCK) + 1) * sizeof(uint32_t))) != hipSuccess) return bail("hipMalloc", err);
-    if ((err = hipMalloc((void **)&f->d_total, 2 * sizeof(uint32_t))) != hipSuccess) return bail("hipMalloc", err);
-    (void)hipMemsetAsync(g.pq, 0, table, f->stream);
-    (void)hipMemsetAsync(g.misc, 0, table, f->stream);
-    (void)hipMemsetAsync(g.anomalies, 0, sizeof(uint32_t), f->stream);
-    if ((err = hipStreamSynchronize(f->stream)) != hipSuccess) return bail("hipMemset", err);
+    }
     *out = f;
     return 0;
 }
@@ -1588,16 +1548,10 @@ int clair_frontend_create(int device, const char *ref_seq, int64_t ref_len, int6
 void clair_frontend_destroy(clair_frontend_t *f) {
     if (!f) return;
     (void)hipSetDevice(f->device);
-    if (f->stream) (void)hipStreamSynchronize(f->stream);
-    for (Slab &s : f->slabs) {
-        (void)hipFree(s.reads); (void)hipFree(s.ops); (void)hipFree(s.op_elem); (void)hipFree(s.seq); (void)hipFree(s.tuples);
-    }
-    free_candidates(f);
-    (void)hipFree(f->d_ref); (void)hipFree(f->g.pq); (void)hipFree(f->g.misc); (void)hipFree(f->g.anomalies);
-    (void)hipFree(f->d_flags); (void)hipFree(f->d_before); (void)hipFree(f->d_block_sum); (void)hipFree(f->d_total); (void)hipFree(f->d_bed);
-    (void)hipFree(f->d_ctg); (void)hipFree(f->d_text_state); (void)hipFree(f->d_span); (void)hipFree(f->d_d2); (void)hipFree(f->d_fold);
-    if (f->stream) (void)hipStreamDestroy(f->stream);
-    delete f;
+    const hipStream_t stream = f->stream;
+    if (stream) (void)hipStreamSynchronize(stream);
+    delete f;                                   // every buffer goes with its owner, after the work on the stream is done ...
+    if (stream) (void)hipStreamDestroy(stream); // ... and before the stream is
 }
 
 __global__ void fe_flag_kernel(Region g, uint32_t bits) { atomicOr(g.anomalies, bits); }
@@ -1611,13 +1565,13 @@ static int launch_tally(clair_frontend *f, const Slab &d, int64_t p_first, int64
         hipLaunchKernelGGL(fe_tally_kernel, dim3(blocks_for(d.n_elem, 256)), dim3(256), 0, f->stream, f->g, f->view(d));
         return 0;
     }
-    if (!f->d_span) FE_TRY(f, hipMalloc((void **)&f->d_span, sizeof(uint32_t)));
-    FE_TRY(f, hipMemsetAsync(f->d_span, 0, sizeof(uint32_t), f->stream));
-    hipLaunchKernelGGL(fe_slab_span_kernel, dim3(blocks_for(d.n_reads, 256)), dim3(256), 0, f->stream, f->view(d), (uint32_t)d.n_reads, f->d_span);
+    FE_TRY(f, f->span.ensure(sizeof(uint32_t)));
+    FE_TRY(f, hipMemsetAsync(f->span.p, 0, sizeof(uint32_t), f->stream));
+    hipLaunchKernelGGL(fe_slab_span_kernel, dim3(blocks_for(d.n_reads, 256)), dim3(256), 0, f->stream, f->view(d), (uint32_t)d.n_reads, f->span.as<uint32_t>());
     const int64_t n_tiles = (f->g.n + TT_POS - 1) / TT_POS;
     const int64_t tile0 = std::min(std::max<int64_t>((p_first - f->g.lo) / TT_POS - (p_first < f->g.lo ? 1 : 0), 0), n_tiles - 1);
     const int64_t tile1 = std::min(std::max<int64_t>((p_reach - f->g.lo) / TT_POS, tile0), n_tiles - 1);
-    hipLaunchKernelGGL(fe_tally_tile_kernel, dim3((unsigned)(tile1 - tile0 + 1)), dim3(TT_THREADS), 0, f->stream, f->g, f->view(d), (uint32_t)d.n_reads, (const uint32_t *)f->d_span, tile0);
+    hipLaunchKernelGGL(fe_tally_tile_kernel, dim3((unsigned)(tile1 - tile0 + 1)), dim3(TT_THREADS), 0, f->stream, f->g, f->view(d), (uint32_t)d.n_reads, f->span.as<const uint32_t>(), tile0);
     return 0;
 }
 
@@ -1656,12 +1610,12 @@ static int pack_lines(clair_frontend *f, DeviceTemp &tmp, const uint8_t *src, bo
     FE_TRY(f, tmp.get((void **)&seq0, (size_t)n_kept * sizeof(uint32_t)));
     FE_TRY(f, tmp.get((void **)&d_totals, 5 * sizeof(uint64_t)));
     hipLaunchKernelGGL(fe_text_offsets_kernel, dim3(1), dim3(256), 0, f->stream, (const TextLine *)lines, n_lines, (const int64_t *)kept, n_kept, (const int64_t *)cand, n_cand,
-                       op0, elem0, seq0, d_totals, carry, f->d_text_state);
+                       op0, elem0, seq0, d_totals, carry, f->d_text_state.as<TextState>());
     FE_TRY(f, hipGetLastError());
     uint64_t totals[5] = {0, 0, 0, 0, 0};
     TextState after{};
     FE_TRY(f, hipMemcpyAsync(totals, d_totals, sizeof totals, hipMemcpyDeviceToHost, f->stream));
-    FE_TRY(f, hipMemcpyAsync(&after, f->d_text_state, sizeof after, hipMemcpyDeviceToHost, f->stream));
+    FE_TRY(f, hipMemcpyAsync(&after, f->d_text_state.p, sizeof after, hipMemcpyDeviceToHost, f->stream));
     FE_TRY(f, hipStreamSynchronize(f->stream));
     if (after.malformed != 0xffffffffu) {
         *malformed = after.malformed;
@@ -1671,27 +1625,15 @@ static int pack_lines(clair_frontend *f, DeviceTemp &tmp, const uint8_t *src, bo
     after.malformed = 0;
     f->text_state = after;
     if (n_kept == 0 || totals[0] == 0) return 0;
-    Slab s;
-    s.n_reads = n_kept; s.n_ops = (int64_t)totals[0]; s.n_elem = (int64_t)totals[1]; s.seq_bytes = (int64_t)totals[4];
-    FE_TRY(f, hipMalloc((void **)&s.reads, (size_t)n_kept * sizeof(clair_read_t)));
-    f->slabs.push_back(s);
-    Slab &d = f->slabs.back();
-    FE_TRY(f, hipMalloc((void **)&d.ops, (size_t)d.n_ops * sizeof(clair_op_t)));
-    FE_TRY(f, hipMalloc((void **)&d.op_elem, ((size_t)d.n_ops + 1) * sizeof(uint32_t)));
-    FE_TRY(f, hipMalloc((void **)&d.tuples, (size_t)n_kept * sizeof(uint64_t)));
-    FE_TRY(f, hipMalloc((void **)&d.seq, (size_t)std::max<uint64_t>(totals[4], 16)));      // the bases only: the text itself is released when this call returns
-    FE_TRY(f, hipMemsetAsync(d.tuples, 0, (size_t)n_kept * sizeof(uint64_t), f->stream));
-    if (bam) {
-        hipLaunchKernelGGL(fe_bam_emit_kernel, dim3(blocks_for(n_kept, 256)), dim3(256), 0, f->stream, src, (const TextLine *)lines, (const int64_t *)kept, n_kept,
-                           (const uint32_t *)op0, (const uint32_t *)elem0, (const uint32_t *)seq0, d.reads, d.ops, d.op_elem, totals[0], totals[1]);
-        hipLaunchKernelGGL(fe_bam_seq_kernel, dim3(blocks_for(n_kept, 4)), dim3(256), 0, f->stream, src, (const TextLine *)lines, (const int64_t *)kept, n_kept,
-                           (const uint32_t *)seq0, d.seq);
-    } else {
-        hipLaunchKernelGGL(fe_text_emit_kernel, dim3(blocks_for(n_kept, 256)), dim3(256), 0, f->stream, src, (const TextLine *)lines, (const int64_t *)kept, n_kept,
-                           (const uint32_t *)op0, (const uint32_t *)elem0, (const uint32_t *)seq0, d.reads, d.ops, d.op_elem, totals[0], totals[1]);
-        hipLaunchKernelGGL(fe_text_seq_kernel, dim3(blocks_for(n_kept, 4)), dim3(256), 0, f->stream, src, (const TextLine *)lines, (const int64_t *)kept, n_kept,
-                           (const uint32_t *)seq0, d.seq);
-    }
+    Slab *slab = nullptr;
+    if (new_slab(f, n_kept, (int64_t)totals[0], (int64_t)totals[1], (int64_t)totals[4], &slab)) return 1;    // the bases only: the text itself is released when this call returns
+    const Slab &d = *slab;
+    const auto emit = bam ? fe_emit_kernel<true> : fe_emit_kernel<false>;       // same arguments; `src` is the records or the text
+    const auto seq = bam ? fe_bam_seq_kernel : fe_text_seq_kernel;
+    hipLaunchKernelGGL(emit, dim3(blocks_for(n_kept, 256)), dim3(256), 0, f->stream, src, (const TextLine *)lines, (const int64_t *)kept, n_kept, (const uint32_t *)op0,
+                       (const uint32_t *)elem0, (const uint32_t *)seq0, d.reads.as<clair_read_t>(), d.ops.as<clair_op_t>(), d.op_elem.as<uint32_t>(), totals[0], totals[1]);
+    hipLaunchKernelGGL(seq, dim3(blocks_for(n_kept, 4)), dim3(256), 0, f->stream, src, (const TextLine *)lines, (const int64_t *)kept, n_kept, (const uint32_t *)seq0,
+                       d.seq.as<uint8_t>());
     // the tiled tally bisects over the slab's start positions: once the packer has seen a start go backwards (this slab or an earlier
     // one: the word is cumulative, and a start below the previous slab's last is exactly such a case) the per-base kernel is used, as
     // clair_frontend_add_reads does -- an unsorted slab is flagged AND tallied correctly on both entry points
@@ -1710,20 +1652,13 @@ int clair_frontend_add_reads(clair_frontend_t *f, const clair_read_t *reads, int
     if (n_ops > 0xfffffff0ll || seq_bytes > 0xfffffff0ll) return fe_fail(f, "slab too large for 32-bit offsets");
     if (f->n_candidates >= 0) return fe_fail(f, "reads cannot be added after the candidates were fixed");
     FE_TRY(f, hipSetDevice(f->device));
-    Slab s;
-    s.n_reads = n_reads; s.n_ops = n_ops; s.n_elem = op_elem[n_ops]; s.seq_bytes = seq_bytes;
-    FE_TRY(f, hipMalloc((void **)&s.reads, (size_t)n_reads * sizeof(clair_read_t)));
-    f->slabs.push_back(s);                    // owned from here on: destroy frees whatever was allocated
-    Slab &d = f->slabs.back();
-    FE_TRY(f, hipMalloc((void **)&d.ops, (size_t)n_ops * sizeof(clair_op_t)));
-    FE_TRY(f, hipMalloc((void **)&d.op_elem, ((size_t)n_ops + 1) * sizeof(uint32_t)));
-    FE_TRY(f, hipMalloc((void **)&d.seq, (size_t)std::max<int64_t>(seq_bytes, 1)));
-    FE_TRY(f, hipMalloc((void **)&d.tuples, (size_t)n_reads * sizeof(uint64_t)));
-    FE_TRY(f, hipMemcpyAsync(d.reads, reads, (size_t)n_reads * sizeof(clair_read_t), hipMemcpyHostToDevice, f->stream));
-    FE_TRY(f, hipMemcpyAsync(d.ops, ops, (size_t)n_ops * sizeof(clair_op_t), hipMemcpyHostToDevice, f->stream));
-    FE_TRY(f, hipMemcpyAsync(d.op_elem, op_elem, ((size_t)n_ops + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, f->stream));
-    if (seq_bytes) FE_TRY(f, hipMemcpyAsync(d.seq, seq, (size_t)seq_bytes, hipMemcpyHostToDevice, f->stream));
-    FE_TRY(f, hipMemsetAsync(d.tuples, 0, (size_t)n_reads * sizeof(uint64_t), f->stream));
+    Slab *slab = nullptr;
+    if (new_slab(f, n_reads, n_ops, op_elem[n_ops], seq_bytes, &slab)) return 1;
+    const Slab &d = *slab;
+    FE_TRY(f, hipMemcpyAsync(d.reads.p, reads, (size_t)n_reads * sizeof(clair_read_t), hipMemcpyHostToDevice, f->stream));
+    FE_TRY(f, hipMemcpyAsync(d.ops.p, ops, (size_t)n_ops * sizeof(clair_op_t), hipMemcpyHostToDevice, f->stream));
+    FE_TRY(f, hipMemcpyAsync(d.op_elem.p, op_elem, ((size_t)n_ops + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, f->stream));
+    if (seq_bytes) FE_TRY(f, hipMemcpyAsync(d.seq.p, seq, (size_t)seq_bytes, hipMemcpyHostToDevice, f->stream));
     {   // where the slab lies, for the grid of the tiled tally: first and last start, the longest reach (host arrays: one look at every alignment's last operation)
         int64_t p_first = reads[0].pos0, p_last = reads[0].pos0, reach = 0;
         bool sorted = true;
@@ -1754,12 +1689,11 @@ int clair_frontend_text_options(clair_frontend_t *f, const char *ctg_name, int d
     if (!f->slabs.empty() && f->text_ready) return fe_fail(f, "text options cannot change once text was added");
     FE_TRY(f, hipSetDevice(f->device));
     const size_t n = strlen(ctg_name);
-    (void)hipFree(f->d_ctg); f->d_ctg = nullptr;
-    FE_TRY(f, hipMalloc((void **)&f->d_ctg, std::max<size_t>(n, 1)));
-    if (n) FE_TRY(f, hipMemcpy(f->d_ctg, ctg_name, n, hipMemcpyHostToDevice));
-    if (!f->d_text_state) FE_TRY(f, hipMalloc((void **)&f->d_text_state, sizeof(TextState)));
+    FE_TRY(f, f->ctg.ensure(n));
+    if (n) FE_TRY(f, hipMemcpy(f->ctg.p, ctg_name, n, hipMemcpyHostToDevice));
+    FE_TRY(f, f->d_text_state.ensure(sizeof(TextState)));
     const bool have_region = pile_start >= 0 && pile_end >= 0;
-    f->text_opt = TextOptions{f->d_ctg, (int)n, dcov, evc_min_mq, pile_min_mq, have_region ? pile_start : -1, have_region ? pile_end : -1};
+    f->text_opt = TextOptions{f->ctg.as<uint8_t>(), (int)n, dcov, evc_min_mq, pile_min_mq, have_region ? pile_start : -1, have_region ? pile_end : -1};
     f->text_state = TextState{};
     f->text_ready = true;
     return 0;
@@ -1794,9 +1728,9 @@ int clair_frontend_add_text(clair_frontend_t *f, const char *sam, int64_t len) {
     FE_TRY(f, tmp.get((void **)&is_cand, (size_t)n_lines + 1));
     TextState carry = f->text_state;
     carry.malformed = 0xffffffffu;
-    FE_TRY(f, hipMemcpyAsync(f->d_text_state, &carry, sizeof carry, hipMemcpyHostToDevice, f->stream));
+    FE_TRY(f, hipMemcpyAsync(f->d_text_state.p, &carry, sizeof carry, hipMemcpyHostToDevice, f->stream));
     hipLaunchKernelGGL(fe_text_lines_kernel, dim3(blocks_for(n_lines, 256)), dim3(256), 0, f->stream, (const uint8_t *)d_text, (const int64_t *)newline, n_lines,
-                       f->text_opt, lines, is_cand, f->d_text_state);
+                       f->text_opt, lines, is_cand, f->d_text_state.as<TextState>());
     FE_TRY(f, hipGetLastError());
     uint32_t malformed = 0;
     const int rc = pack_lines(f, tmp, d_text, false, lines, is_cand, n_lines, d_count, carry, &malformed);
@@ -1812,7 +1746,7 @@ int clair_frontend_bam_options(clair_frontend_t *f, int tid, int dcov, int evc_m
     if (tid < 0) return fe_fail(f, "reference id %d", tid);
     if (!f->slabs.empty() && f->text_ready) return fe_fail(f, "BAM options cannot change once records were added");
     FE_TRY(f, hipSetDevice(f->device));
-    if (!f->d_text_state) FE_TRY(f, hipMalloc((void **)&f->d_text_state, sizeof(TextState)));
+    FE_TRY(f, f->d_text_state.ensure(sizeof(TextState)));
     const bool have_pile = pile_start >= 0 && pile_end >= 0, have_region = region_lo >= 0 && region_hi >= 0;
     f->text_opt = TextOptions{nullptr, 0, dcov, evc_min_mq, pile_min_mq, have_pile ? pile_start : -1, have_pile ? pile_end : -1};
     f->bam_opt = BamOptions{tid, have_region ? region_lo : -1, have_region ? region_hi : -1};
@@ -1847,9 +1781,9 @@ int clair_frontend_add_bam(clair_frontend_t *f, const uint8_t *records, int64_t 
     FE_TRY(f, hipMemcpyAsync(d_off, offsets, (size_t)n_records * sizeof(int64_t), hipMemcpyHostToDevice, f->stream));
     TextState carry = f->text_state;
     carry.malformed = 0xffffffffu;
-    FE_TRY(f, hipMemcpyAsync(f->d_text_state, &carry, sizeof carry, hipMemcpyHostToDevice, f->stream));
+    FE_TRY(f, hipMemcpyAsync(f->d_text_state.p, &carry, sizeof carry, hipMemcpyHostToDevice, f->stream));
     hipLaunchKernelGGL(fe_bam_records_kernel, dim3(blocks_for(n_records, 256)), dim3(256), 0, f->stream, (const uint8_t *)d_rec, len, (const int64_t *)d_off,
-                       n_records, f->text_opt, f->bam_opt, all, pass, f->d_text_state);
+                       n_records, f->text_opt, f->bam_opt, all, pass, f->d_text_state.as<TextState>());
     FE_TRY(f, hipGetLastError());
     int64_t n_lines = 0;                                                  // the records the view prints
     if (scan_count(f, pass, n_records, rec_sum, d_count + 3, &n_lines)) return 1;
@@ -1857,7 +1791,7 @@ int clair_frontend_add_bam(clair_frontend_t *f, const uint8_t *records, int64_t 
     int rc = 0;
     if (n_lines == 0) {                                                   // nothing for the text path's kernels: the state is the carry's
         TextState after{};
-        FE_TRY(f, hipMemcpyAsync(&after, f->d_text_state, sizeof after, hipMemcpyDeviceToHost, f->stream));
+        FE_TRY(f, hipMemcpyAsync(&after, f->d_text_state.p, sizeof after, hipMemcpyDeviceToHost, f->stream));
         FE_TRY(f, hipStreamSynchronize(f->stream));
         if (after.malformed != 0xffffffffu) { malformed = after.malformed; rc = 2; }
     } else {
@@ -1893,7 +1827,7 @@ int clair_frontend_slab_reads(clair_frontend_t *f, int64_t slab, struct clair_re
     if (!reads) return 0;
     if (capacity < s.n_reads) return fe_fail(f, "room for %lld alignments, the slab holds %lld", (long long)capacity, (long long)s.n_reads);
     FE_TRY(f, hipSetDevice(f->device));
-    FE_TRY(f, hipMemcpy(reads, s.reads, (size_t)s.n_reads * sizeof(clair_read_t), hipMemcpyDeviceToHost));
+    FE_TRY(f, hipMemcpy(reads, s.reads.p, (size_t)s.n_reads * sizeof(clair_read_t), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -1914,18 +1848,18 @@ int clair_frontend_find_candidates(clair_frontend_t *f, double min_coverage, dou
             if (!st.empty() && x.first <= en.back()) en.back() = std::max(en.back(), x.second);
             else { st.push_back(x.first); en.push_back(x.second); }
         }
-        (void)hipFree(f->d_bed); f->d_bed = nullptr;
         const size_t m = st.size();
-        FE_TRY(f, hipMalloc((void **)&f->d_bed, std::max<size_t>(2 * m, 1) * sizeof(int64_t)));
+        FE_TRY(f, f->bed.ensure(2 * m * sizeof(int64_t)));
+        int64_t *d_bed = f->bed.as<int64_t>();
         if (m) {
-            FE_TRY(f, hipMemcpy(f->d_bed, st.data(), m * sizeof(int64_t), hipMemcpyHostToDevice));
-            FE_TRY(f, hipMemcpy(f->d_bed + m, en.data(), m * sizeof(int64_t), hipMemcpyHostToDevice));
+            FE_TRY(f, hipMemcpy(d_bed, st.data(), m * sizeof(int64_t), hipMemcpyHostToDevice));
+            FE_TRY(f, hipMemcpy(d_bed + m, en.data(), m * sizeof(int64_t), hipMemcpyHostToDevice));
         }
-        rule.bed_start = f->d_bed;
-        rule.bed_end = f->d_bed + m;
+        rule.bed_start = d_bed;
+        rule.bed_end = d_bed + m;
         rule.n_bed = (int64_t)m;
     }
-    hipLaunchKernelGGL(fe_candidate_flags_kernel, dim3(blocks_for(f->g.n, 256)), dim3(256), 0, f->stream, f->g, rule, f->d_flags);
+    hipLaunchKernelGGL(fe_candidate_flags_kernel, dim3(blocks_for(f->g.n, 256)), dim3(256), 0, f->stream, f->g, rule, f->flags.as<uint8_t>());
     FE_TRY(f, hipGetLastError());
     return finish_candidates(f, n_candidates);
 }
@@ -1942,16 +1876,16 @@ int clair_frontend_set_candidates(clair_frontend_t *f, const int64_t *positions,
             FE_TRY(f, hipMemcpy(f->g.anomalies, &cur, sizeof cur, hipMemcpyHostToDevice));
             break;
         }
-    FE_TRY(f, hipMemsetAsync(f->d_flags, 0, (size_t)f->g.n + 1, f->stream));
+    FE_TRY(f, hipMemsetAsync(f->flags.p, 0, (size_t)f->g.n + 1, f->stream));
     if (n_positions) {
-        int64_t *d_pos = nullptr;
-        FE_TRY(f, hipMalloc((void **)&d_pos, (size_t)n_positions * sizeof(int64_t)));
-        hipError_t err = hipMemcpyAsync(d_pos, positions, (size_t)n_positions * sizeof(int64_t), hipMemcpyHostToDevice, f->stream);
+        DeviceBuffer d_pos;
+        FE_TRY(f, d_pos.ensure((size_t)n_positions * sizeof(int64_t)));
+        hipError_t err = hipMemcpyAsync(d_pos.p, positions, (size_t)n_positions * sizeof(int64_t), hipMemcpyHostToDevice, f->stream);
         if (err == hipSuccess) {
-            hipLaunchKernelGGL(fe_given_flags_kernel, dim3(blocks_for(n_positions, 256)), dim3(256), 0, f->stream, (const int64_t *)d_pos, n_positions, f->g.lo, f->g.n, f->d_flags);
+            hipLaunchKernelGGL(fe_given_flags_kernel, dim3(blocks_for(n_positions, 256)), dim3(256), 0, f->stream, d_pos.as<const int64_t>(), n_positions, f->g.lo, f->g.n,
+                               f->flags.as<uint8_t>());
             err = hipStreamSynchronize(f->stream);
         }
-        (void)hipFree(d_pos);
         FE_TRY(f, err);
     }
     return finish_candidates(f, n_candidates);
@@ -1962,7 +1896,7 @@ int clair_frontend_get_candidates(clair_frontend_t *f, int64_t *positions) {
     if (f->n_candidates < 0) return fe_fail(f, "no candidates yet: call clair_frontend_find_candidates / _set_candidates first");
     if (f->n_candidates && !positions) return fe_fail(f, "positions is NULL");
     FE_TRY(f, hipSetDevice(f->device));
-    if (f->n_candidates) FE_TRY(f, hipMemcpy(positions, f->d_centre, (size_t)f->n_candidates * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (f->n_candidates) FE_TRY(f, hipMemcpy(positions, f->cand->centre.p, (size_t)f->n_candidates * sizeof(int64_t), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -1976,47 +1910,41 @@ int clair_frontend_build_windows_ex(clair_frontend_t *f, int min_coverage, int d
     if (f->n_candidates < 0) return fe_fail(f, "no candidates yet: call clair_frontend_find_candidates / _set_candidates first");
     FE_TRY(f, hipSetDevice(f->device));
     const int64_t nc = f->n_candidates, room = std::max<int64_t>(nc, 1);
-    if (!f->d_ins) {
-        FE_TRY(f, hipMalloc((void **)&f->d_ins, (size_t)room * N_QUAD * sizeof(uint32_t)));
-        FE_TRY(f, hipMalloc((void **)&f->d_keep, (size_t)room + 1));
-        FE_TRY(f, hipMalloc((void **)&f->d_window_tuples, (size_t)room * sizeof(uint64_t)));
-        FE_TRY(f, hipMalloc((void **)&f->d_kept, (size_t)room * sizeof(int64_t)));
-        FE_TRY(f, hipMalloc((void **)&f->d_cand_block_sum, ((size_t)blocks_for(room + 1, SCAN_BLOCK) + 1) * sizeof(uint32_t)));
-    }
-    FE_TRY(f, hipMemsetAsync(f->d_ins, 0, (size_t)room * N_QUAD * sizeof(uint32_t), f->stream));
+    CandidateBuffers &cb = *f->cand;
+    FE_TRY(f, cb.ins.ensure((size_t)room * N_QUAD * sizeof(uint32_t)));
+    FE_TRY(f, cb.keep.ensure((size_t)room + 1));
+    FE_TRY(f, cb.window_tuples.ensure((size_t)room * sizeof(uint64_t)));
+    FE_TRY(f, cb.kept.ensure((size_t)room * sizeof(int64_t)));
+    FE_TRY(f, cb.block_sum.ensure(((size_t)blocks_for(room + 1, SCAN_BLOCK) + 1) * sizeof(uint32_t)));
+    FE_TRY(f, hipMemsetAsync(cb.ins.p, 0, cb.ins.bytes, f->stream));
     if (!consider_left_edge) {
-        if (!f->d_late) {
-            FE_TRY(f, hipMalloc((void **)&f->d_late, (size_t)room * N_POS * LATE_ROW * sizeof(uint32_t)));
-            FE_TRY(f, hipMalloc((void **)&f->d_tuple_diff, ((size_t)room + 1) * sizeof(int)));
-        }
-        FE_TRY(f, hipMemsetAsync(f->d_late, 0, (size_t)room * N_POS * LATE_ROW * sizeof(uint32_t), f->stream));
-        FE_TRY(f, hipMemsetAsync(f->d_tuple_diff, 0, ((size_t)room + 1) * sizeof(int), f->stream));
+        FE_TRY(f, cb.late.ensure((size_t)room * N_POS * LATE_ROW * sizeof(uint32_t)));
+        FE_TRY(f, cb.tuple_diff.ensure(((size_t)room + 1) * sizeof(int)));
+        FE_TRY(f, hipMemsetAsync(cb.late.p, 0, cb.late.bytes, f->stream));
+        FE_TRY(f, hipMemsetAsync(cb.tuple_diff.p, 0, cb.tuple_diff.bytes, f->stream));
     }
-    uint32_t *late = consider_left_edge ? nullptr : f->d_late;
+    uint32_t *late = consider_left_edge ? nullptr : cb.late.as<uint32_t>();
+    const int64_t *centre = cb.centre.as<int64_t>();
+    uint64_t *window_tuples = cb.window_tuples.as<uint64_t>();
     const bool per_op = consider_left_edge || !f->pass2_per_base;
     const int64_t m2 = f->g.n + 2;
     if (per_op && nc) {      // the running sum of the candidate prefix: what lets pass 2 go operation by operation
         const int64_t m = f->g.n + 1;
-        const unsigned nb = blocks_for(m2, SCAN_BLOCK);
-        if (!f->d_before_sum) {
-            FE_TRY(f, hipMalloc((void **)&f->d_before_sum, (size_t)m * sizeof(unsigned long long)));
-            FE_TRY(f, hipMalloc((void **)&f->d_prefix_block_sum, ((size_t)nb + 1) * sizeof(unsigned long long)));
-        }
-        hipLaunchKernelGGL(fe_prefix_block_sums_kernel, dim3(blocks_for(m, SCAN_BLOCK)), dim3(256), 0, f->stream, (const uint32_t *)f->d_before, m, f->d_prefix_block_sum);
-        hipLaunchKernelGGL(fe_prefix_scan_sums_kernel, dim3(1), dim3(256), 0, f->stream, f->d_prefix_block_sum, (int64_t)blocks_for(m, SCAN_BLOCK));
-        hipLaunchKernelGGL(fe_prefix_write_kernel, dim3(blocks_for(m, SCAN_BLOCK)), dim3(256), 0, f->stream, (const uint32_t *)f->d_before, m, (const unsigned long long *)f->d_prefix_block_sum, f->d_before_sum);
+        FE_TRY(f, cb.before_sum.ensure((size_t)m * sizeof(unsigned long long)));
+        FE_TRY(f, cb.prefix_block_sum.ensure(((size_t)blocks_for(m2, SCAN_BLOCK) + 1) * sizeof(unsigned long long)));
+        running_sum<ScanU32>(f, f->before.as<uint32_t>(), m, cb.prefix_block_sum.as<unsigned long long>(), WriteRunning{cb.before_sum.as<unsigned long long>(), nullptr, 0, 0});
         if (!consider_left_edge) {
-            if (!f->d_d2) {
-                FE_TRY(f, hipMalloc((void **)&f->d_d2, (size_t)m2 * sizeof(unsigned long long)));
-                FE_TRY(f, hipMalloc((void **)&f->d_fold, 2 * sizeof(unsigned long long)));
-            }
-            FE_TRY(f, hipMemsetAsync(f->d_d2, 0, (size_t)m2 * sizeof(unsigned long long), f->stream));
-            FE_TRY(f, hipMemsetAsync(f->d_fold, 0, 2 * sizeof(unsigned long long), f->stream));
+            FE_TRY(f, f->d2.ensure((size_t)m2 * sizeof(unsigned long long)));
+            FE_TRY(f, f->fold.ensure(2 * sizeof(unsigned long long)));
+            FE_TRY(f, hipMemsetAsync(f->d2.p, 0, f->d2.bytes, f->stream));
+            FE_TRY(f, hipMemsetAsync(f->fold.p, 0, f->fold.bytes, f->stream));
         }
     }
-    Candidates c{f->d_centre, f->d_before, f->d_ins, f->d_before_sum, late, consider_left_edge ? nullptr : f->d_tuple_diff, f->d_d2, f->d_fold};
+    unsigned long long *d2 = f->d2.as<unsigned long long>();
+    Candidates c{centre, f->before.as<uint32_t>(), cb.ins.as<uint32_t>(), cb.before_sum.as<unsigned long long>(), late,
+                 consider_left_edge ? nullptr : cb.tuple_diff.as<int>(), d2, f->fold.as<unsigned long long>()};
     for (Slab &s : f->slabs) {
-        FE_TRY(f, hipMemsetAsync(s.tuples, 0, (size_t)s.n_reads * sizeof(uint64_t), f->stream));
+        FE_TRY(f, hipMemsetAsync(s.tuples.p, 0, (size_t)s.n_reads * sizeof(uint64_t), f->stream));
         if (!s.n_elem || !nc) continue;
         if (consider_left_edge) hipLaunchKernelGGL(fe_windows_per_op_kernel, dim3(blocks_for(s.n_ops, 256)), dim3(256), 0, f->stream, f->g, f->view(s), c);
         else if (per_op) {
@@ -2025,33 +1953,26 @@ int clair_frontend_build_windows_ex(clair_frontend_t *f, int min_coverage, int d
         } else hipLaunchKernelGGL(fe_windows_per_base_kernel, dim3(blocks_for(s.n_elem, 256)), dim3(256), 0, f->stream, f->g, f->view(s), c);
     }
     if (nc && late && per_op) {          // second differences -> first differences -> tuples per centre value -> per window
-        const unsigned nb = blocks_for(m2, SCAN_BLOCK);
-        for (int second = 0; second < 2; ++second) {
-            hipLaunchKernelGGL(fe_tuple_scan_sums_kernel, dim3(nb), dim3(256), 0, f->stream, (const unsigned long long *)f->d_d2, m2, f->d_prefix_block_sum);
-            hipLaunchKernelGGL(fe_prefix_scan_sums_kernel, dim3(1), dim3(256), 0, f->stream, f->d_prefix_block_sum, (int64_t)nb);
-            hipLaunchKernelGGL(fe_tuple_scan_write_kernel, dim3(nb), dim3(256), 0, f->stream, f->d_d2, m2, (const unsigned long long *)f->d_prefix_block_sum,
-                               (const unsigned long long *)f->d_fold, second, f->g.lo);
-        }
-        hipLaunchKernelGGL(fe_window_totals_at_kernel, dim3(blocks_for(nc, 256)), dim3(256), 0, f->stream, (const unsigned long long *)f->d_d2, (const int64_t *)f->d_centre, nc,
-                           f->g.lo, f->g.n, f->d_window_tuples);
+        for (int second = 0; second < 2; ++second)
+            running_sum<ScanU64>(f, d2, m2, cb.prefix_block_sum.as<unsigned long long>(), WriteRunning{d2, f->fold.as<unsigned long long>(), second, f->g.lo});
+        hipLaunchKernelGGL(fe_window_totals_at_kernel, dim3(blocks_for(nc, 256)), dim3(256), 0, f->stream, (const unsigned long long *)d2, centre, nc, f->g.lo, f->g.n, window_tuples);
     }
     WindowRule rule{min_coverage, drop_non_iupac_centre, late};
-    if (nc && late && !per_op) hipLaunchKernelGGL(fe_window_totals_kernel, dim3(1), dim3(256), 0, f->stream, (const int *)f->d_tuple_diff, nc, f->d_window_tuples);
-    if (nc) hipLaunchKernelGGL(fe_window_flags_kernel, dim3(blocks_for(nc, 256)), dim3(256), 0, f->stream, f->g, (const int64_t *)f->d_centre, nc, rule, f->d_keep, f->d_window_tuples);
+    if (nc && late && !per_op)           // per-base pass 2: tuples per window = the (signed) running sum of its range additions, by one workgroup
+        hipLaunchKernelGGL((fe_scan_serial_kernel<ScanInt, true>), dim3(1), dim3(256), 0, f->stream, cb.tuple_diff.as<const int>(), nc, (long long *)window_tuples, (long long *)nullptr);
+    if (nc) hipLaunchKernelGGL(fe_window_flags_kernel, dim3(blocks_for(nc, 256)), dim3(256), 0, f->stream, f->g, centre, nc, rule, cb.keep.as<uint8_t>(), window_tuples);
     FE_TRY(f, hipGetLastError());
     int64_t kept = 0;
-    if (scan_count(f, f->d_keep, nc, f->d_cand_block_sum, f->d_total + 1, &kept)) return 1;
-    if (scan_write(f, f->d_keep, nc, f->d_cand_block_sum, f->d_total + 1, nullptr, f->d_kept, 0)) return 1;
-    (void)hipFree(f->d_counts); f->d_counts = nullptr;
-    (void)hipFree(f->d_out_centre); f->d_out_centre = nullptr;
-    (void)hipFree(f->d_out_refseq); f->d_out_refseq = nullptr;
+    uint32_t *d_kept_total = f->total.as<uint32_t>() + 1;
+    if (scan_count(f, cb.keep.as<uint8_t>(), nc, cb.block_sum.as<uint32_t>(), d_kept_total, &kept)) return 1;
+    if (scan_write(f, cb.keep.as<uint8_t>(), nc, cb.block_sum.as<uint32_t>(), d_kept_total, nullptr, cb.kept.as<int64_t>(), 0)) return 1;
     // + one engine batch of slack is the caller's business: clair_submit_ex reads exactly n windows
-    FE_TRY(f, hipMalloc((void **)&f->d_counts, (size_t)std::max<int64_t>(kept, 1) * WINDOW_VALUES * sizeof(int16_t)));
-    FE_TRY(f, hipMalloc((void **)&f->d_out_centre, (size_t)std::max<int64_t>(kept, 1) * sizeof(int64_t)));
-    FE_TRY(f, hipMalloc((void **)&f->d_out_refseq, (size_t)std::max<int64_t>(kept, 1) * 34));
+    FE_TRY(f, cb.counts.ensure((size_t)kept * WINDOW_VALUES * sizeof(int16_t)));
+    FE_TRY(f, cb.out_centre.ensure((size_t)kept * sizeof(int64_t)));
+    FE_TRY(f, cb.out_refseq.ensure((size_t)kept * 34));
     if (kept)
-        hipLaunchKernelGGL(fe_assemble_kernel, dim3(blocks_for(kept * N_QUAD, 256)), dim3(256), 0, f->stream, f->g, (const int64_t *)f->d_centre,
-                           (const int64_t *)f->d_kept, kept, (const uint32_t *)f->d_ins, (const uint32_t *)late, f->d_counts, f->d_out_centre, f->d_out_refseq);
+        hipLaunchKernelGGL(fe_assemble_kernel, dim3(blocks_for(kept * N_QUAD, 256)), dim3(256), 0, f->stream, f->g, centre, cb.kept.as<const int64_t>(), kept,
+                           cb.ins.as<const uint32_t>(), (const uint32_t *)late, cb.counts.as<short4>(), cb.out_centre.as<int64_t>(), cb.out_refseq.as<uint8_t>());
     FE_TRY(f, hipGetLastError());
     FE_TRY(f, hipStreamSynchronize(f->stream));
     f->n_windows = kept;
@@ -2066,8 +1987,8 @@ int clair_frontend_window_info(clair_frontend_t *f, int64_t first, int64_t n, in
     if (n == 0) return 0;
     if (!centres || !refseq) return fe_fail(f, "NULL output pointer");
     FE_TRY(f, hipSetDevice(f->device));
-    FE_TRY(f, hipMemcpy(centres, f->d_out_centre + first, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
-    FE_TRY(f, hipMemcpy(refseq, f->d_out_refseq + first * 34, (size_t)n * 34, hipMemcpyDeviceToHost));
+    FE_TRY(f, hipMemcpy(centres, f->cand->out_centre.as<int64_t>() + first, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
+    FE_TRY(f, hipMemcpy(refseq, f->cand->out_refseq.as<uint8_t>() + first * 34, (size_t)n * 34, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -2078,13 +1999,13 @@ int clair_frontend_window_counts(clair_frontend_t *f, int64_t first, int64_t n, 
     if (n == 0) return 0;
     if (!counts) return fe_fail(f, "NULL output pointer");
     FE_TRY(f, hipSetDevice(f->device));
-    FE_TRY(f, hipMemcpy(counts, (const int16_t *)f->d_counts + first * WINDOW_VALUES, (size_t)n * WINDOW_VALUES * sizeof(int16_t), hipMemcpyDeviceToHost));
+    FE_TRY(f, hipMemcpy(counts, f->cand->counts.as<const int16_t>() + first * WINDOW_VALUES, (size_t)n * WINDOW_VALUES * sizeof(int16_t), hipMemcpyDeviceToHost));
     return 0;
 }
 
 const int16_t *clair_frontend_counts_device(clair_frontend_t *f, int64_t first) {
     if (!f || f->n_windows < 0 || first < 0 || first > f->n_windows) return nullptr;
-    return (const int16_t *)f->d_counts + first * WINDOW_VALUES;
+    return f->cand->counts.as<const int16_t>() + first * WINDOW_VALUES;
 }
 
 int clair_frontend_budget_inputs(clair_frontend_t *f, int64_t slab, uint64_t *read_tuples, int64_t *centres, uint64_t *window_tuples) {
@@ -2094,10 +2015,10 @@ int clair_frontend_budget_inputs(clair_frontend_t *f, int64_t slab, uint64_t *re
     if (read_tuples) {
         if (slab < 0 || slab >= (int64_t)f->slabs.size()) return fe_fail(f, "slab %lld out of range [0, %lld)", (long long)slab, (long long)f->slabs.size());
         const Slab &s = f->slabs[(size_t)slab];
-        FE_TRY(f, hipMemcpy(read_tuples, s.tuples, (size_t)s.n_reads * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        FE_TRY(f, hipMemcpy(read_tuples, s.tuples.p, (size_t)s.n_reads * sizeof(uint64_t), hipMemcpyDeviceToHost));
     }
-    if (centres && f->n_candidates) FE_TRY(f, hipMemcpy(centres, f->d_centre, (size_t)f->n_candidates * sizeof(int64_t), hipMemcpyDeviceToHost));
-    if (window_tuples && f->n_candidates) FE_TRY(f, hipMemcpy(window_tuples, f->d_window_tuples, (size_t)f->n_candidates * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (centres && f->n_candidates) FE_TRY(f, hipMemcpy(centres, f->cand->centre.p, (size_t)f->n_candidates * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (window_tuples && f->n_candidates) FE_TRY(f, hipMemcpy(window_tuples, f->cand->window_tuples.p, (size_t)f->n_candidates * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -36,16 +36,19 @@ def main():
         "fe_tally_tile_kernel": elements * (1 + 16 / 8.0) + positions * 64 * 2,               # SEQ byte + its share of an operation; the tile's 64 B of counters read and written once
         "fe_windows_per_base_kernel": elements * (1 + 16 / 8.0 + 4) + elements * 2 * 4,      # + two prefix look-ups
         "fe_candidate_flags_kernel": positions * (32 + 1),
-        "fe_block_count_kernel": positions * 1,
-        "fe_scan_write_kernel": positions * (1 + 4),
+        # the block scan is one kernel family: the model is for its flag instantiations (candidate flags -> prefix and candidate list)
+        "fe_scan_sums_kernel<ScanBytes<false>>": positions * 1,
+        "fe_scan_write_kernel<ScanBytes<false>,WriteCompact>": positions * (1 + 4),
         "fe_window_flags_kernel": windows * 35 * 32,
         "fe_assemble_kernel": windows * (2112 + 33 * (32 + 8) + 1056),
         "fe_text_lines_kernel": elements * 2.03,             # every byte of the text once (SEQ + QUAL + the rest ~ 2 bytes per aligned base)
-        "fe_text_emit_kernel": elements * (16 + 4) / 8.0,     # the operations written
+        "fe_emit_kernel<false>": elements * (16 + 4) / 8.0,   # the operations written (<false>: from text, <true>: from BAM records)
+        "fe_emit_kernel<true>": elements * (16 + 4) / 8.0,
     }
-    print("%-34s %8s %10s %10s %12s %12s %12s %14s %10s" % ("kernel", "launches", "mean_us", "grid", "fetch_MB(x2)", "write_MB", "GB/s moved", "algorithmic_MB", "GB/s alg."))
+    print("%-52s %8s %10s %10s %12s %12s %12s %14s %10s" % ("kernel", "launches", "mean_us", "grid", "fetch_MB(x2)", "write_MB", "GB/s moved", "algorithmic_MB", "GB/s alg."))
     for name in sorted(dur, key=lambda k: -sum(d for d, _ in dur[k])):
-        short = re.search(r"fe_\w+", name).group(0)
+        m = re.search(r"(fe_\w+)(<[^(]*>)?", name.replace("(anonymous namespace)::", ""))
+        short = (m.group(1) + (m.group(2) or "")).replace(" ", "")      # with its template arguments: the instantiations are different kernels
         d = [x for x, _ in dur[name]]
         big = max(d)
         sel = [x for x in d if x > 0.25 * big]              # the bench's full-size launches (drop the tiny warm-up front end)
@@ -55,7 +58,7 @@ def main():
         fmb = max(fm) if fm else 0.0
         wmb = max(wm) if wm else 0.0
         alg = algorithmic.get(short, 0) / 1e6
-        print("%-34s %8d %10.1f %10d %12.1f %12.1f %12.0f %14.1f %10.0f"
+        print("%-52s %8d %10.1f %10d %12.1f %12.1f %12.0f %14.1f %10.0f"
               % (short, len(sel), mean, max(g for _, g in dur[name]), fmb, wmb, (fmb + wmb) / mean * 1e3 if mean else 0, alg, alg / mean * 1e3 if mean else 0))
     if elements:
         for key, label in (("fe_tally", "pass 1"), ("fe_windows_per_", "pass 2")):   # pass 2: per operation, or per base with --stop_consider_left_edge
