@@ -29,6 +29,7 @@ SYMBOLS = (
     "clair_frontend_stats", "clair_frontend_text_options", "clair_frontend_add_text", "clair_frontend_text_stats", "clair_frontend_slab_reads",
     "clair_frontend_bam_options", "clair_frontend_add_bam",
     "clair_eval_reset", "clair_submit_eval", "clair_eval", "clair_eval_read",
+    "clair_inflate_create", "clair_inflate_destroy", "clair_inflate_last_error", "clair_inflate_blocks", "clair_inflate_blocks_cb",
 )
 EVAL_COUNTS = 3 + 21 * 21 + 3 * 3 + 33 * 33 + 33 * 33      # CLAIR_EVAL_COUNTS: all, top1, top2, gt21, genotype, len1, len2
 KERNEL_NAMES = ("proj1", "lstm1", "proj2", "lstm2", "l3", "l4", "tail", "decode")
@@ -143,12 +144,21 @@ def load(path=None):
         if hasattr(lib, "clair_frontend_add_bam") or not older_ok:
             lib.clair_frontend_bam_options.argtypes = [c_vp, c_int, c_int, c_int, c_int, c_i64, c_i64, c_i64, c_i64]
             lib.clair_frontend_add_bam.argtypes = [c_vp, c_vp, c_i64, c_vp, c_i64]
+    if not older_ok or hasattr(lib, "clair_inflate_create"):
+        lib.clair_inflate_create.argtypes = [c_int, c_int, ctypes.POINTER(c_vp)]
+        lib.clair_inflate_destroy.argtypes = [c_vp]
+        lib.clair_inflate_destroy.restype = None
+        lib.clair_inflate_last_error.argtypes = [c_vp]
+        lib.clair_inflate_last_error.restype = ctypes.c_char_p
+        lib.clair_inflate_blocks.argtypes = [c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
+        lib.clair_inflate_blocks_cb.argtypes = lib.clair_inflate_blocks.argtypes
     for name in SYMBOLS:
         if older_ok and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
         if name not in ("clair_last_error", "clair_engine_destroy", "clair_comm_last_error", "clair_comm_destroy",
-                        "clair_frontend_last_error", "clair_frontend_destroy", "clair_frontend_counts_device"):
+                        "clair_frontend_last_error", "clair_frontend_destroy", "clair_frontend_counts_device",
+                        "clair_inflate_last_error", "clair_inflate_destroy"):
             fn.restype = c_int
     if path is None:
         _lib = lib
@@ -635,3 +645,53 @@ class Frontend(object):
         window_tuples = np.empty(n_cand, dtype=np.uint64)
         self._check(self._lib.clair_frontend_budget_inputs(self._h, 0, None, _ptr(centres), _ptr(window_tuples)), "clair_frontend_budget_inputs")
         return centres, window_tuples
+
+
+class Inflater(object):
+    """clair_inflate_*: BGZF blocks inflated on the device, a wave per block (csrc/inflate.hip).
+
+        inf = Inflater(device=0, max_blocks=2048)
+        out, status = inf.blocks(cdata, in_at, csize, out_at, out_len)       # whole BGZF blocks inside cdata -> bytes, status per block
+
+    status: 0 ok, 1 corrupt deflate data, 2 inflated size differs from ISIZE, 3 CRC32 mismatch.  `handle` and `callback` are what
+    clair_host_bam_set_inflater takes (_hostapi.BamReader(inflate="device"))."""
+    STATUS = ("ok", "corrupt deflate data", "inflated size differs from ISIZE", "CRC32 mismatch")
+
+    def __init__(self, device=0, max_blocks=2048):
+        self._lib = load()
+        self._h = ctypes.c_void_p()
+        if self._lib.clair_inflate_create(int(device), int(max_blocks), ctypes.byref(self._h)) != 0:
+            msg = self._lib.clair_inflate_last_error(None).decode()
+            self._h = None
+            raise EngineError("clair_inflate_create failed: %s" % msg)
+        self.max_blocks = int(max_blocks)
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def callback(self):
+        return ctypes.cast(self._lib.clair_inflate_blocks_cb, ctypes.c_void_p)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.clair_inflate_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def blocks(self, cdata, in_at, csize, out_at, out_len, out=None, cbytes=None):
+        """-> (out, status): out is a uint8 array (given, or zeros up to the last output range)."""
+        cdata = np.frombuffer(cdata, dtype=np.uint8) if not isinstance(cdata, np.ndarray) else cdata
+        in_at, out_at = np.ascontiguousarray(in_at, dtype=np.int64), np.ascontiguousarray(out_at, dtype=np.int64)
+        csize, out_len = np.ascontiguousarray(csize, dtype=np.int32), np.ascontiguousarray(out_len, dtype=np.int32)
+        n = len(in_at)
+        if out is None:
+            out = np.zeros(int((out_at + out_len).max()) if n else 0, dtype=np.uint8)
+        status = np.full(n, -1, dtype=np.int32)
+        rc = self._lib.clair_inflate_blocks(self._h, _ptr(cdata), len(cdata) if cbytes is None else int(cbytes), n, _ptr(in_at), _ptr(csize), _ptr(out_at),
+                                            _ptr(out_len), _ptr(out), _ptr(status))
+        if rc != 0:
+            raise EngineError("clair_inflate_blocks failed: %s" % self._lib.clair_inflate_last_error(self._h).decode())
+        return out, status

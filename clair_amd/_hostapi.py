@@ -17,7 +17,8 @@ SYMBOLS = ("clair_host_abi_version", "clair_host_last_error", "clair_host_thread
            "clair_host_sampack_create", "clair_host_sampack_destroy", "clair_host_sampack_feed", "clair_host_sampack_stats",
            "clair_host_sampack_slab", "clair_host_sampack_reset", "clair_host_tuple_budget_binds",
            "clair_host_bam_open", "clair_host_bam_close", "clair_host_bam_info", "clair_host_bam_ref", "clair_host_bam_tid", "clair_host_bam_query",
-           "clair_host_bam_next", "clair_host_bam_voffset", "clair_host_bam_render", "clair_host_faidx")
+           "clair_host_bam_next", "clair_host_bam_voffset", "clair_host_bam_render", "clair_host_faidx",
+           "clair_host_bam_set_inflater", "clair_host_inflate_block", "clair_host_inflate_bgzf")
 N_VALUES = 1056
 _lib = None
 
@@ -87,6 +88,9 @@ def load():
         lib.clair_host_bam_voffset.argtypes = [vp, i64, ctypes.POINTER(ctypes.c_uint64)]
         lib.clair_host_bam_render.argtypes = [vp, vp, vp, i64, i32, i64, i64, ctypes.POINTER(vp), ctypes.POINTER(i64)]
         lib.clair_host_faidx.argtypes = [ctypes.c_char_p, ctypes.c_char_p, i64, i64, vp, i64, ctypes.POINTER(i64)]
+        lib.clair_host_bam_set_inflater.argtypes = [vp, vp, vp, i32]
+        lib.clair_host_inflate_block.argtypes = [vp, i64, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(i32)]
+        lib.clair_host_inflate_bgzf.argtypes = [vp, i64, vp, ctypes.POINTER(i64), ctypes.POINTER(i32)]
         lib.clair_host_tuple_budget_binds.argtypes = [vp, vp, i64, vp, vp, i64, vp, ctypes.POINTER(i32)]
         if lib.clair_host_abi_version() != 6:
             raise RuntimeError("libclair_host.so has ABI version %d, expected 6: run `python -m clair_amd.build`"
@@ -551,6 +555,34 @@ def tuple_budget_binds(reads, tuples, centres, window_tuples, state):
     return bool(binds.value)
 
 
+INFLATE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p)    # clair_host_inflate_fn
+INFLATE_BATCH = 2048       # BGZF blocks per device batch (BamReader(inflate="device")): 128 MiB of staging each way
+INFLATE_STATUS = ("ok", "corrupt deflate data", "inflated size differs from ISIZE", "CRC32 mismatch")
+
+
+def inflate_block(data, cap):
+    """clair_host_inflate_block: one raw deflate stream through the host twin of the device decoder -> (status, bytes, crc32)."""
+    lib = load()
+    src = np.frombuffer(bytes(data), dtype=np.uint8) if len(data) else np.zeros(1, dtype=np.uint8)
+    out = np.zeros(max(1, int(cap)), dtype=np.uint8)
+    n, crc, status = ctypes.c_int64(0), ctypes.c_uint32(0), ctypes.c_int(0)
+    if lib.clair_host_inflate_block(src.ctypes.data, len(data), out.ctypes.data, int(cap), ctypes.byref(n), ctypes.byref(crc), ctypes.byref(status)) != 0:
+        raise ValueError(lib.clair_host_last_error().decode())
+    return int(status.value), out[:n.value].tobytes(), int(crc.value)
+
+
+def inflate_bgzf(block):
+    """clair_host_inflate_bgzf: one whole BGZF block as the device kernel treats it -> (status, bytes)."""
+    lib = load()
+    src = np.frombuffer(bytes(block), dtype=np.uint8)
+    out = np.zeros(65537, dtype=np.uint8)
+    n, status = ctypes.c_int64(0), ctypes.c_int(0)
+    if lib.clair_host_inflate_bgzf(src.ctypes.data, len(src), out.ctypes.data, ctypes.byref(n), ctypes.byref(status)) != 0:
+        raise ValueError(lib.clair_host_last_error().decode())
+    return int(status.value), out[:n.value].tobytes()
+
+
 class BamError(ValueError):
     """The BAM, its index or the request cannot be read natively (callVarBam turns it into a message and a non-zero exit)."""
 
@@ -569,7 +601,7 @@ def bam_index_for(bam_fn):
 class BamReader(object):
     """clair_host_bam_*: the records of one contig / region of a BAM, read without samtools (callVarBam --bam_reader native).
 
-        r = BamReader(path, threads=4)
+        r = BamReader(path, threads=4)                   # inflate="device", device=0: BGZF blocks inflated on the GPU (callVarBam --bam_inflate)
         r.query("chr1", 1000, 2000)                      # 1-based inclusive; None, None = the whole contig
         n_bytes, n_records = r.readinto(buf, offsets)    # whole records, offsets[k] = where record k starts; 0, 0 at the end
         text = r.render(buf, offsets, n_records)         # what `samtools view -F 2316 <bam> <region>` prints for them (11 columns)
@@ -577,20 +609,40 @@ class BamReader(object):
     The records readinto() hands out are all those the index yields for the region; the view filter is the consumer's (the device's
     clair_frontend_add_bam or render())."""
 
-    def __init__(self, path, threads=4):
+    def __init__(self, path, threads=4, inflate="host", device=0):
         self._lib = load()
         if not 1 <= int(threads) <= 16:
             raise BamError("--bam_threads %d: 1 .. 16" % threads)
+        if inflate not in ("host", "device"):
+            raise BamError("--bam_inflate %s: host or device" % inflate)
         h = ctypes.c_void_p()
         if self._lib.clair_host_bam_open(path.encode(), int(threads), ctypes.byref(h)) != 0:
             raise BamError(self._lib.clair_host_last_error().decode())
         self._h, self.path = h, path
         self.tid, self.region, self.used_index = -1, (-1, -1), False
+        self._inflater = self._hook = None
+        if inflate == "device":                  # only a function pointer and its context pass between the two libraries
+            from clair_amd import _capi
+            try:
+                self._inflater = _capi.Inflater(device=device, max_blocks=INFLATE_BATCH)
+            except _capi.EngineError as e:
+                self.close()
+                raise BamError(str(e))
+            self.set_inflater(self._inflater.callback, self._inflater.handle, INFLATE_BATCH)
+
+    def set_inflater(self, fn, ctx=None, batch_blocks=INFLATE_BATCH):
+        """clair_host_bam_set_inflater: fn is a function pointer (an INFLATE_FN instance or an address), None = zlib again."""
+        self._hook = fn                          # keeps a Python callback alive
+        if self._lib.clair_host_bam_set_inflater(self._h, ctypes.cast(fn, ctypes.c_void_p) if fn is not None else None, ctx, int(batch_blocks)) != 0:
+            raise BamError(self._lib.clair_host_last_error().decode())
 
     def close(self):
         if getattr(self, "_h", None):
             self._lib.clair_host_bam_close(self._h)
             self._h = None
+        if getattr(self, "_inflater", None):
+            self._inflater.close()
+            self._inflater = None
 
     __del__ = close
 

@@ -25,7 +25,7 @@ that formulation reproduces exactly (CLAIR_FE_* in include/clair_reads.h, a tupl
 host stages above and says so.
 
 --bam_reader native reads the BAM without samtools (include/clair_host.h: clair_host_bam_*; docs/bam_reader.md): BGZF inflated on
---bam_threads host threads, the region's records found with the .bai, and with the device front end the binary records go to the GPU
+--bam_threads host threads (or on the GPU, a wave per block: --bam_inflate device), the region's records found with the .bai, and with the device front end the binary records go to the GPU
 as they are (clair_frontend_add_bam), which decodes them and applies the view's filter itself.  The host stages, and the device front
 end's fall-back, read the text `samtools view` would have printed, rendered from the records; the reference slice comes from the .fai.
 """
@@ -66,7 +66,8 @@ def native_reader(args, region):
     from . import _hostapi
     ctg, lo, hi = split_region(region)
     try:
-        reader = _hostapi.BamReader(args.bam_fn, threads=getattr(args, "bam_threads", 4))
+        reader = _hostapi.BamReader(args.bam_fn, threads=getattr(args, "bam_threads", 4), inflate=getattr(args, "bam_inflate", "host"),
+                                    device=getattr(args, "device", 0))
         if not reader.info()["eof_block"]:
             logging.warning("[W::bgzf] %s: no BGZF EOF marker; the file may be truncated" % args.bam_fn)
         if not reader.query(ctg, lo, hi):
@@ -725,6 +726,8 @@ def normalise(args):
         args.ctgStart = args.ctgEnd = None          # callVarBam.py:97-101
     if (args.ctgStart is None) != (args.ctgEnd is None):
         args.ctgStart = args.ctgEnd = None
+    if getattr(args, "bam_inflate", "host") == "device" and not native_input(args):
+        sys.exit("[ERROR] --bam_inflate device inflates the BGZF blocks the native reader reads: add --bam_reader native")
     if native_input(args):
         for name, given in (("--samtools_view_args", args.samtools_view_args is not None), ("--samtools_threads", (args.samtools_threads or 0) > 0),
                             ("--view_readers", (args.view_readers or 1) > 1)):
@@ -865,6 +868,9 @@ def build_parser():
              "(BGZF BAM with a .bai or none; the records are decoded on the GPU with the device front end).  CRAM, .csi indexes and extra view "
              "options need samtools")
     add('--bam_threads', type=int, default=4, help="with --bam_reader native: threads that inflate BGZF blocks (1 .. 16), default: %(default)s")
+    add('--bam_inflate', type=str, default="host", choices=("host", "device"),
+        help="with --bam_reader native: where BGZF blocks are inflated: zlib on --bam_threads host threads (default), or on the GPU --device names, "
+             "a wave per block (--bam_threads is then ignored)")
     add('--device', type=int, default=0, help="HIP device ordinal, default: %(default)s")
     add('--arith', type=str, default="legacy", choices=("legacy", "numpy2"),
         help="QUAL/AF arithmetic: float64 as under the reference's NumPy 1.x (legacy) or float32 (numpy2)")

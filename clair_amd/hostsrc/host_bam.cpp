@@ -3,6 +3,7 @@
 //
 // What `samtools view -F 2316 <bam> <region>` does before it formats text, restated for the one use this project makes of it:
 //   - BGZF: blocks inflated on N threads, each block's CRC32 and ISIZE checked; a missing EOF block is a warning (as htslib's);
+//     clair_host_bam_set_inflater hands the batches of a query to another inflater instead (the device's: callVarBam --bam_inflate device);
 //   - the BAM header: magic, text, the reference names and lengths;
 //   - region selection with the .bai: bins overlapping the region, chunks before the linear index's minimum offset dropped, the rest
 //     sorted and merged (htslib's hts_itr_query), or a scan from the first record without an index;
@@ -145,6 +146,11 @@ struct clair_bam {
     std::vector<uint8_t> cbuf;
     std::vector<Block> blocks;
     std::vector<uint8_t> obuf;
+    // another inflater for the batches (clair_host_bam_set_inflater); none: zlib on `threads` threads
+    clair_host_inflate_fn inflater = nullptr;
+    void *inflater_ctx = nullptr;
+    std::vector<int64_t> hook_in_at, hook_out_at;
+    std::vector<int32_t> hook_csize, hook_out_len, hook_status;
 
     ~clair_bam() { if (file) fclose(file); }
 
@@ -184,6 +190,7 @@ struct clair_bam {
         }
         next_coffset = coffset;
         obuf.resize(out + 1);
+        if (inflater && !blocks.empty()) return inflate_with_hook();
         auto inflate_one = [&](Block &b) {
             z_stream z{};
             if (inflateInit2(&z, -15) != Z_OK) { b.error = "inflateInit2 failed"; return; }
@@ -211,6 +218,29 @@ struct clair_bam {
         for (const Block &b : blocks)
             if (!b.error.empty())
                 return clair_host_fail("%s: BGZF block at compressed offset %llu: %s", path.c_str(), (unsigned long long)b.coffset, b.error.c_str());
+        return 0;
+    }
+
+    // the batch through the installed inflater; its first non-zero status becomes the message the zlib path gives for such a block
+    int inflate_with_hook() {
+        const size_t n = blocks.size();
+        hook_in_at.resize(n); hook_out_at.resize(n); hook_csize.resize(n); hook_out_len.resize(n);
+        hook_status.assign(n, 0);
+        for (size_t i = 0; i < n; ++i) {
+            hook_in_at[i] = (int64_t)blocks[i].in_at;
+            hook_csize[i] = (int32_t)blocks[i].csize;
+            hook_out_at[i] = (int64_t)blocks[i].out_at;
+            hook_out_len[i] = (int32_t)blocks[i].out_len;
+        }
+        if (inflater(inflater_ctx, cbuf.data(), (int64_t)cbuf.size(), (int)n, hook_in_at.data(), hook_csize.data(), hook_out_at.data(), hook_out_len.data(),
+                     obuf.data(), hook_status.data()) != 0)
+            return clair_host_fail("%s: the installed inflater failed on the %zu blocks from compressed offset %llu", path.c_str(), n,
+                                   (unsigned long long)blocks[0].coffset);
+        static const char *const what[] = {"corrupt deflate data", "inflated size differs from ISIZE", "CRC32 mismatch"};
+        for (size_t i = 0; i < n; ++i)
+            if (hook_status[i] != 0)
+                return clair_host_fail("%s: BGZF block at compressed offset %llu: %s", path.c_str(), (unsigned long long)blocks[i].coffset,
+                                       what[hook_status[i] >= 1 && hook_status[i] <= 3 ? hook_status[i] - 1 : 0]);
         return 0;
     }
 
@@ -327,6 +357,15 @@ int clair_host_bam_open(const char *path, int threads, clair_bam_t **out) {
 }
 
 void clair_host_bam_close(clair_bam_t *b) { delete b; }
+
+int clair_host_bam_set_inflater(clair_bam_t *b, clair_host_inflate_fn fn, void *ctx, int batch_blocks) {
+    if (!b) return clair_host_fail("BAM handle is NULL");
+    if (fn && (batch_blocks < 1 || batch_blocks > 16384)) return clair_host_fail("inflater batch of %d blocks: 1 .. 16384", batch_blocks);
+    b->inflater = fn;
+    b->inflater_ctx = fn ? ctx : nullptr;
+    b->batch_blocks = fn ? (size_t)batch_blocks : (size_t)std::max(16, 64 * b->threads);
+    return 0;
+}
 
 int clair_host_bam_info(const clair_bam_t *b, int64_t *info) {
     if (!b || !info) return clair_host_fail("NULL argument");

@@ -358,6 +358,23 @@ int clair_frontend_budget_inputs(clair_frontend_t *f, int64_t slab, uint64_t *re
 /* stats[0..5] = CLAIR_FE_* bits seen on the device, slabs, alignments, elements, candidates (-1: not yet), windows (-1: not yet) */
 int clair_frontend_stats(clair_frontend_t *f, int64_t *stats);
 
+/* -- BGZF inflate on the device (callVarBam --bam_inflate device; csrc/inflate.hip, docs/bam_reader.md).  A handle owns one stream and
+ * page-locked staging plus device buffers for max_blocks blocks (64 KiB each, both directions), reused by every call.
+ * _blocks: n <= max_blocks whole BGZF blocks (header and footer included) at cdata[in_at[i] .. + csize[i]), csize >= 26; block i's
+ * inflated bytes go to out[out_at[i] .. + out_len[i]) where out_len is the block's ISIZE (<= 65536) and every output range lies in
+ * [0, max_blocks * 65536).  status[i]: 0 ok, 1 corrupt deflate data, 2 inflated size differs from ISIZE, 3 CRC32 mismatch; the
+ * output range of a block whose status is not 0 is left untouched, and no block disturbs another.  Synchronous.  Returns 0 when the
+ * batch ran, whatever the statuses; non-zero for a bad argument (nothing is enqueued then) or a HIP error.
+ * _blocks_cb is the same function in the shape clair_host_bam_set_inflater takes (include/clair_host.h), the handle as its context. */
+typedef struct clair_inflate clair_inflate_t;
+int clair_inflate_create(int device, int max_blocks, clair_inflate_t **out);
+void clair_inflate_destroy(clair_inflate_t *h);
+const char *clair_inflate_last_error(const clair_inflate_t *h);        /* h may be NULL: failure of create */
+int clair_inflate_blocks(clair_inflate_t *h, const uint8_t *cdata, int64_t cbytes, int n, const int64_t *in_at, const int32_t *csize,
+                         const int64_t *out_at, const int32_t *out_len, uint8_t *out, int32_t *status);
+int clair_inflate_blocks_cb(void *handle, const uint8_t *cdata, int64_t cbytes, int n, const int64_t *in_at, const int32_t *csize,
+                            const int64_t *out_at, const int32_t *out_len, uint8_t *out, int32_t *status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -196,8 +196,16 @@ int clair_host_tuple_budget_binds(const struct clair_read *reads, const uint64_t
  *    (QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL; '*' for no CIGAR, no SEQ, QUAL 0xff; the CG:B:I CIGAR for the
  *    kSmN placeholder); *text is the handle's and valid until the next render.
  *    faidx: the bases of ctg:beg1-end1 (clamped; -1 -1 = whole contig) as `samtools faidx` prints them, case kept, line ends
- *    dropped; out NULL = *len only. */
+ *    dropped; out NULL = *len only.
+ *    set_inflater: from here on the BGZF blocks of a query are inflated by fn, batch_blocks (1 .. 16384) at a time, instead of by zlib
+ *    on the thread pool (fn NULL: back to zlib).  fn gets n whole blocks (header and footer included) at cdata[in_at[i] .. + csize[i]),
+ *    writes block i's out_len[i] (its ISIZE) bytes to out[out_at[i] ..] and sets status[i]: 0 ok, 1 corrupt deflate data, 2 inflated size
+ *    differs from ISIZE, 3 CRC32 mismatch; it returns non-zero when it could not run.  The first non-zero status becomes the message the
+ *    zlib path gives for that block, with its compressed offset.  libclair_amd's clair_inflate_blocks_cb is such a function (include/clair_amd.h,
+ *    its handle as ctx): this library does not link HIP.  The header blocks read at open are inflated by zlib. */
 typedef struct clair_bam clair_bam_t;
+typedef int (*clair_host_inflate_fn)(void *ctx, const uint8_t *cdata, int64_t cbytes, int n, const int64_t *in_at, const int32_t *csize,
+                                     const int64_t *out_at, const int32_t *out_len, uint8_t *out, int32_t *status);
 int clair_host_bam_open(const char *path, int threads, clair_bam_t **out);
 void clair_host_bam_close(clair_bam_t *b);
 int clair_host_bam_info(const clair_bam_t *b, int64_t *info);
@@ -209,6 +217,18 @@ int clair_host_bam_voffset(const clair_bam_t *b, int64_t k, uint64_t *voffset);
 int clair_host_bam_render(clair_bam_t *b, const uint8_t *records, const int64_t *offsets, int64_t n, int tid, int64_t beg1, int64_t end1,
                           const char **text, int64_t *len);
 int clair_host_faidx(const char *fasta, const char *ctg, int64_t beg1, int64_t end1, char *out, int64_t cap, int64_t *len);
+int clair_host_bam_set_inflater(clair_bam_t *b, clair_host_inflate_fn fn, void *ctx, int batch_blocks);
+
+/* -- the host twin of the device inflate (hostsrc/host_inflate.cpp): the RFC 1951 decoder of csrc/inflate_core.h, the code the GPU runs,
+ *    compiled for the host with its own CRC-32 (no zlib), so that it can be tested, fuzzed and run under the host sanitizer.  It accepts
+ *    exactly the streams zlib's inflate(Z_FINISH) with windowBits = -15 accepts.
+ *    _block: one raw deflate stream in[0 .. n_in) into out[0 .. cap); *status = 0 and *n_out, *crc32 (of the output) set when the final
+ *    block ended within cap bytes, *status = 1 otherwise (*n_out = 0).  Input after the final block is ignored.
+ *    _bgzf: one whole BGZF block (18-byte header, stream, CRC32, ISIZE <= 65536) as the device kernel treats it: out has room for
+ *    ISIZE + 1 bytes; *status as clair_host_bam_set_inflater's.
+ *    Both return non-zero only for bad arguments. */
+int clair_host_inflate_block(const uint8_t *in, int64_t n_in, uint8_t *out, int64_t cap, int64_t *n_out, uint32_t *crc32, int *status);
+int clair_host_inflate_bgzf(const uint8_t *block, int64_t csize, uint8_t *out, int64_t *n_out, int *status);
 
 #ifdef __cplusplus
 }

@@ -8,6 +8,10 @@ Synthesises a sorted BAM + .bai from a seed at user-sized shapes -- Illumina-lik
   device_fe_bam    read + add_bam + candidates + windows, end to end from the file;
   device_fe_text   the same alignments as the canonical text, already in memory, through clair_frontend_add_text (no samtools process:
                    the text path's upper bound), + candidates + windows.
+With --inflate the run measures the BGZF inflate legs instead (docs/bam_reader.md, "Device inflate"): per repeat, alternating, read + walk and
+the end-to-end device front end from the file with the host inflate at --bam_threads (`host`), on the GPU (`device`), or host at 4 threads,
+host at 16 and device in turn (`all`); every repeat is reported.  The inflate kernel's own time comes from
+`rocprofv3 --kernel-trace --stats -- python tools/gpu/bam_reader_bench.py --quick --inflate device`.
 The fe_bam_* kernel times come from a separate run under `rocprofv3 --kernel-trace --stats -- python tools/gpu/bam_reader_bench.py --quick`.
 
     python tools/gpu/bam_reader_bench.py [--illumina N] [--ont N] [--out DIR]
@@ -91,6 +95,52 @@ def synth_bam(path, n_reads, read_len, ref_len, seed, ont):
         f.write(bai)
     ref = "".join(np.array(list("ACGT"))[rng.integers(0, 4, ref_len)])
     return ref, len(stream) - len(header)
+
+
+def measure_inflate(path, ref, rec_bytes, n_reads, legs, repeats):
+    """legs: [(name, BamReader keywords)], run in turn `repeats` times: A B C A B C ..."""
+    from clair_amd import _capi, _hostapi
+    cap = 64 << 20
+    buf, off = np.empty(cap + 16, np.uint8), _hostapi.bam_offsets_for(cap)
+    out = dict(records=n_reads, record_mb=round(rec_bytes / 1e6, 1), legs={name: dict(read_walk=[], device_fe_bam=[]) for name, _ in legs})
+    sums = {}
+    for rep in range(repeats + 1):                           # repeat 0 warms up (module load, first allocations) and is not reported
+        for name, kw in legs:
+            r = _hostapi.BamReader(path, **kw)
+            r.query("chrB")
+            t0, n_bytes, crc = time.perf_counter(), 0, 0
+            while True:
+                n, k = r.readinto(buf, off, cap=cap)
+                if not k:
+                    break
+                n_bytes += n
+                if rep == 0:
+                    crc = zlib.crc32(buf[:n], crc)
+            dt = time.perf_counter() - t0
+            r.close()
+            f = _capi.Frontend(0, ref, 0, -64, len(ref) + 64)
+            t1 = time.perf_counter()
+            r = _hostapi.BamReader(path, **kw)
+            r.query("chrB")
+            f.bam_options(0)
+            while True:
+                n, k = r.readinto(buf, off, cap=cap)
+                if not k:
+                    break
+                f.add_bam(buf, n, off, k)
+            r.close()
+            t_feed = time.perf_counter() - t1
+            f.find_candidates(min_coverage=4, threshold=0.125)
+            n_win = f.build_windows(min_coverage=0, drop_non_iupac_centre=True)
+            total = time.perf_counter() - t1
+            f.close()
+            if rep == 0:
+                sums[name] = (n_bytes, crc, n_win)
+                continue
+            out["legs"][name]["read_walk"].append(dict(seconds=round(dt, 3), mb_per_s=round(n_bytes / dt / 1e6, 1)))
+            out["legs"][name]["device_fe_bam"].append(dict(seconds=round(total, 3), read_and_add_bam_seconds=round(t_feed, 3), windows=n_win))
+    out["same_bytes"] = len(set(sums.values())) == 1
+    return out
 
 
 def measure(path, ref, rec_bytes, n_reads, quick):
@@ -179,7 +229,13 @@ def main():
     p.add_argument("--seed", type=int, default=1)
     p.add_argument("--quick", action="store_true", help="small shapes, one thread count (the run under rocprofv3)")
     p.add_argument("--out", type=str, default=None, help="directory for the synthetic BAMs and results.json, default: a new temporary one")
+    p.add_argument("--inflate", choices=("host", "device", "all"), default=None,
+                   help="measure the BGZF inflate legs only: host (at --bam_threads), device, or all = host at 4 threads, host at 16, device in turn")
+    p.add_argument("--bam_threads", type=int, default=4, help="threads of the host inflate leg, default: %(default)s")
+    p.add_argument("--repeats", type=int, default=3, help="repeats of every inflate leg, default: %(default)s")
     a = p.parse_args()
+    legs = dict(host=[("host_%d" % a.bam_threads, dict(threads=a.bam_threads))], device=[("device", dict(inflate="device"))],
+                all=[("host_4", dict(threads=4)), ("host_16", dict(threads=16)), ("device", dict(inflate="device"))]).get(a.inflate)
     if a.out is None:
         import tempfile
         a.out = tempfile.mkdtemp(prefix="bam_reader_bench_")
@@ -194,7 +250,7 @@ def main():
         t0 = time.perf_counter()
         ref, rec_bytes = synth_bam(path, n, read_len, ref_len, a.seed, ont)
         res = dict(shape=name, synth_seconds=round(time.perf_counter() - t0, 1))
-        res.update(measure(path, ref, rec_bytes, n, a.quick))
+        res.update(measure_inflate(path, ref, rec_bytes, n, legs, a.repeats) if legs else measure(path, ref, rec_bytes, n, a.quick))
         print(json.dumps(res), flush=True)
         results.append(res)
         os.remove(path)
