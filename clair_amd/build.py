@@ -14,13 +14,13 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
 def csrc_digest(root=None):
-    """sha256 over the kernel sources and the launch code (csrc/*.hip.h + engine.hip; names and bytes, sorted): what a
-    measurement of "this build" is stamped with (profiles/pmc_traffic.json, bench.py)."""
+    """sha256 over the kernel sources and the launch code (csrc/*.hip.h + engine.hip and the two host headers it is written over;
+    names and bytes, sorted): what a measurement of "this build" is stamped with (profiles/pmc_traffic.json, bench.py)."""
     import hashlib
     root = root or os.path.join(HERE, "csrc")
     h = hashlib.sha256()
     for f in sorted(os.listdir(root)):
-        if f.endswith(".hip.h") or f == "engine.hip":
+        if f.endswith(".hip.h") or f in ("engine.hip", "weight_images.h", "device_buffer.h"):
             h.update(f.encode() + b"\0" + open(os.path.join(root, f), "rb").read() + b"\0")
     return h.hexdigest()[:16]
 

@@ -15,6 +15,7 @@
 #include <condition_variable>
 #include <cstring>
 #include <deque>
+#include <list>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -29,6 +30,8 @@
 #include "lstm32.hip.h"
 #include "lstm32_pair.hip.h"
 #include "lstm2_fused.hip.h"
+#include "device_buffer.h"
+#include "weight_images.h"
 
 using namespace clair;
 
@@ -37,9 +40,8 @@ namespace {
 thread_local std::string g_create_error;
 thread_local std::string *g_error_sink = nullptr;   // the staging worker: failures go to the slot they belong to, clair_wait reports them
 
-const int64_t TENSOR_COUNT[CLAIR_T_COUNT] = {
-    160 * 512, 512, 160 * 512, 512, 384 * 512, 512, 384 * 512, 512, 256 * 33 * 30, 256 * 30,
-    7680 * 192, 192, 4 * 192 * 96, 4 * 96, 96 * 21, 21, 96 * 3, 3, 96 * 33, 33, 96 * 33, 33};
+// the kernels' constants the weight images depend on (weight_images.h)
+constexpr LayerSizes LAYER_SIZES = {T_POS, F_IN, HID, L3_UNITS, L4_UNITS, L5_UNITS, L34_GROUPS, L34_KS, L34_CH, L32_X_SHIFT};
 
 struct TimedLaunch {
     int kernel;
@@ -50,11 +52,11 @@ struct TimedLaunch {
 // the chip (clair_engine_create: as many as the process has hardware queues to spare).
 struct Lane {
     hipStream_t stream = nullptr;
-    float *zx = nullptr;      // fragment-major x-projection, reused by both layers
-    unsigned short *a1 = nullptr;   // [2][33][max_pad][256] fp16: LSTM1 output as its 2-way split
-    float *a2 = nullptr;      // LSTM2 output, channel-group-major: [32 groups of 8 features][33][n_pad][8]
-    float *l4part = nullptr;  // [8 splits][max_pad rounded to 64][192] split-K partials in the accumulator layout (dense.hip.h)
-    unsigned *fuse_flags = nullptr;   // lstm2_fused.hip.h: [2][max_pad/32][33][8] ticket words, one error word, one claim word per workgroup
+    DeviceBuffer zx;          // float: fragment-major x-projection, reused by both layers
+    DeviceBuffer a1;          // unsigned short [2][33][max_pad][256] fp16: LSTM1 output as its 2-way split
+    DeviceBuffer a2;          // float: LSTM2 output, channel-group-major: [32 groups of 8 features][33][n_pad][8]
+    DeviceBuffer l4part;      // float [8 splits][max_pad rounded to 64][192] split-K partials in the accumulator layout (dense.hip.h)
+    DeviceBuffer fuse_flags;  // unsigned, lstm2_fused.hip.h: [2][max_pad/32][33][8] ticket words, one error word, one claim word per workgroup (only with the fused launch)
     unsigned fuse_ticket = 0;         // ticket of the last fused forward pass on this lane
     int last_n_pad = 0;
     std::mutex order;         // one forward pass is enqueued at a time (the submitting thread and the staging worker both enqueue)
@@ -73,20 +75,19 @@ struct Slot {
     int lane = 0;
     hipStream_t cin = nullptr, cout = nullptr;   // the streams the batch comes in on and the results go out on (copy_mode: whose they are)
     hipEvent_t ev_in = nullptr, ev_done = nullptr, ev_out = nullptr;   // input on the device / forward pass (and decode) finished / results on the host
-    float *d_x = nullptr;     // [max_pad][1056]
-    float *d_out = nullptr;   // [max_pad][90]
-    float *h_out = nullptr;   // pinned [max_batch][90], then (h_word_offset) the fused launch's error word
-    float *h_x = nullptr;     // pinned [max_batch][1056], allocated on first use
-    short *d_counts = nullptr;   // [max_pad][1056] raw counts, allocated on first use
-    char *d_records = nullptr;   // candidates copied with the caller's stride (binary tensor records as they lie), clair_submit_ex
-    size_t d_records_bytes = 0;
-    short *h_counts = nullptr;   // pinned [max_batch][1056]: staging of a caller's pageable count buffer (as h_x is for float input)
-    // device decode (clair_submit_ex): the candidates' centre bytes in, call records out
-    unsigned char *d_centre = nullptr, *h_centre = nullptr;   // [max_pad][2], pinned twin
-    clair_call_t *d_calls = nullptr, *h_calls = nullptr;      // [max_pad], pinned twin
-    clair_call_t *o_calls = nullptr;                          // caller's array of the pending submit (NULL: no decode requested)
-    // device scoring (clair_submit_eval, clair_eval): the candidates' true indices
-    unsigned char *d_labels = nullptr, *h_labels = nullptr;   // [max_pad][4], pinned twin
+    DeviceBuffer d_x;         // float [max_pad][1056]
+    DeviceBuffer d_out;       // float [max_pad][90]
+    PinnedBuffer h_out;       // float [max_batch][90], then (h_word_offset) the fused launch's error word
+    PinnedBuffer h_x;         // float [max_batch][1056], allocated on first use
+    DeviceBuffer d_counts;    // short [max_pad][1056] raw counts, allocated on first use
+    DeviceBuffer d_records;   // candidates copied with the caller's stride (binary tensor records as they lie), clair_submit_ex
+    PinnedBuffer h_counts;    // short [max_batch][1056]: staging of a caller's pageable count buffer (as h_x is for float input)
+    // device decode (clair_submit_ex): the candidates' centre bytes in, call records out; allocated together on first use
+    DeviceBuffer d_centre; PinnedBuffer h_centre;   // unsigned char [max_pad][2], pinned twin
+    DeviceBuffer d_calls; PinnedBuffer h_calls;     // clair_call_t [max_pad], pinned twin
+    clair_call_t *o_calls = nullptr;                // caller's array of the pending submit (NULL: no decode requested)
+    // device scoring (clair_submit_eval, clair_eval): the candidates' true indices, allocated on first use
+    DeviceBuffer d_labels; PinnedBuffer h_labels;   // unsigned char [max_pad][4], pinned twin
     // pending host outputs of a submit
     float *o_gt21 = nullptr, *o_gt = nullptr, *o_l1 = nullptr, *o_l2 = nullptr;
     int pending_n = 0;
@@ -124,7 +125,7 @@ struct clair_engine {
     bool l34_stamps = false;   // CLAIR_AMD_L34_STAMPS=1: l3l4_kernel writes its per-wave phase clocks into the (dead) zx workspace for clair_debug_read(5)
     bool tap_l3 = false;   // CLAIR_AMD_TAP_L3=1: l3l4_kernel also writes l3 into the (dead) zx workspace for clair_debug_read(4)
     std::string error;
-    std::vector<std::pair<char *, size_t>> pinned;   // page-locked host buffers handed to the caller (clair_pinned_alloc)
+    std::list<PinnedBuffer> pinned;                  // page-locked host buffers handed to the caller (clair_pinned_alloc)
     mutable std::mutex pinned_mu;                    // the staging workers look buffers up while the caller may allocate another
     std::vector<Slot> slots;
     std::vector<std::unique_ptr<Lane>> lanes;
@@ -149,14 +150,14 @@ struct clair_engine {
     bool wstop = false;
     std::vector<float> host_tensors[CLAIR_T_COUNT];
     // device weights
-    float *bx1 = nullptr, *bx2 = nullptr;   // gate-scaled biases [2][512] of the two layers
-    unsigned short *wh1s = nullptr, *wh2s = nullptr, *wx1s = nullptr, *w4s = nullptr, *w3s = nullptr;   // fp16 split MFMA fragment images (lstm32.hip.h, dense.hip.h)
-    unsigned short *wx2s = nullptr;   // [8][2][1024][32] fp16 planes of the gate-scaled Wx2
-    float *b4 = nullptr;
-    unsigned short *w5s = nullptr, *whs = nullptr;   // fp16 split A fragments of the L5 branches and the heads (dense.hip.h: tail_kernel)
-    float *b5 = nullptr, *bh = nullptr;
+    DeviceBuffer bx1, bx2;    // float: gate-scaled biases [2][512] of the two layers
+    DeviceBuffer wh1s, wh2s, wx1s, w4s, w3s;   // unsigned short: fp16 split MFMA fragment images (lstm32.hip.h, dense.hip.h)
+    DeviceBuffer wx2s;        // unsigned short [8][2][1024][32] fp16 planes of the gate-scaled Wx2
+    DeviceBuffer b4;          // float
+    DeviceBuffer w5s, whs;    // unsigned short: fp16 split A fragments of the L5 branches and the heads (dense.hip.h: tail_kernel)
+    DeviceBuffer b5, bh;      // float
     int w5_shift[4] = {0, 0, 0, 0}, wh_shift[4] = {0, 0, 0, 0};   // per-branch power-of-two image shifts of those tensors
-    unsigned long long *eval_counts = nullptr;   // [CLAIR_EVAL_COUNTS] confusion counters of evaluate.hip.h, allocated by the first clair_eval_* call
+    DeviceBuffer eval_counts; // unsigned long long [CLAIR_EVAL_COUNTS] confusion counters of evaluate.hip.h, allocated by the first clair_eval_* call
     double ms_sum[CLAIR_K_COUNT] = {0};
     int64_t launches[CLAIR_K_COUNT] = {0};
 };
@@ -180,108 +181,18 @@ int fail(clair_engine *e, const char *fmt, ...) {
             return fail((e), "%s failed: %s (%s:%d)", #call, hipGetErrorString(err__), __FILE__, __LINE__); \
     } while (0)
 
-int upload(clair_engine *e, float **dst, const std::vector<float> &src) {
-    HIP_TRY(e, hipMalloc((void **)dst, src.size() * sizeof(float)));
-    HIP_TRY(e, hipMemcpy(*dst, src.data(), src.size() * sizeof(float), hipMemcpyHostToDevice));
+// a weight image to the device, into an allocation of its own size
+template <typename T> int upload(clair_engine *e, DeviceBuffer &dst, const std::vector<T> &src) {
+    dst.reset();
+    HIP_TRY(e, dst.ensure(src.size() * sizeof(T)));
+    HIP_TRY(e, hipMemcpy(dst.p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
     return 0;
 }
 
-// host-side 2-way fp16 split (round to nearest even; _Float16 conversions are IEEE on the host compiler too)
-inline unsigned short f16_bits(_Float16 h) { unsigned short u; memcpy(&u, &h, 2); return u; }
-inline float f16_value(unsigned short u) { _Float16 h; memcpy(&h, &u, 2); return (float)h; }
-inline void split2_host(float x, unsigned short &hi, unsigned short &lo) {
-    const _Float16 h = (_Float16)x;
-    const _Float16 l = (_Float16)(x - (float)h);
-    hi = f16_bits(h);
-    lo = f16_bits(l);
-}
-
-// Factor folded into every LSTM gate column (and bias) so the MFMA result is the exp2 argument of the
-// gate's activation (lstm32.hip.h): columns are i | c~ | f | o, 128 each.
-inline float gate_scale(int col512) {
-    const float L2E = 1.44269504088896340736f;
-    return ((col512 >> 7) == 1) ? 2.0f * L2E : -L2E;
-}
-
-// Gate-row order of the recurrent kernels (lstm32.hip.h): row rho = 8a + 4h' + c of block b of wave w is
-// gate c (i | c~ | f | o) of hidden unit 32w + 8b + 4h' + a, i.e. column c*128 + unit of the reference's [K][512] kernel.
-inline int gate_col(int w, int b, int rho) {
-    const int a = rho >> 3, hq = (rho >> 2) & 1, c = rho & 3;
-    return c * 128 + 32 * w + 8 * b + 4 * hq + a;
-}
-
-// fp16 2-way split A fragments of W^T for v_mfma_f32_32x32x16_f16: [dir][wave][b][kk][plane][lane][8]:
-// W[k0 + 16*kk + 8*(lane/32) + j][gate_col(w, b, lane%32)] * gate_scale, kk < nkk
-// `pow2` is an extra power-of-two factor on the image (exact): see L32_X_SHIFT in lstm32.hip.h
-std::vector<unsigned short> pack_wt32(const std::vector<float> &fw, const std::vector<float> &bw, int k0, int nkk, float pow2 = 1.0f) {
-    std::vector<unsigned short> out((size_t)2 * 4 * 4 * nkk * 2 * 64 * 8);
-    for (int d = 0; d < 2; ++d) {
-        const std::vector<float> &src = d ? bw : fw;
-        for (int w = 0; w < 4; ++w)
-            for (int b = 0; b < 4; ++b)
-                for (int kk = 0; kk < nkk; ++kk)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < 8; ++j) {
-                            const int col = gate_col(w, b, lane & 31), k = k0 + 16 * kk + 8 * (lane >> 5) + j;
-                            unsigned short hi, lo;
-                            split2_host(src[(size_t)k * 512 + col] * gate_scale(col) * pow2, hi, lo);
-                            const size_t base = (((((size_t)(d * 4 + w) * 4 + b) * nkk + kk) * 2) * 64 + lane) * 8 + j;
-                            out[base] = hi;
-                            out[base + 64 * 8] = lo;
-                        }
-    }
-    return out;
-}
-// gate-scaled bias of both directions in gate-row order: [dir][wave][b][rho]  (= [..][a][h'][c] accumulator quads)
-std::vector<float> pack_bias32(const std::vector<float> &fb, const std::vector<float> &bb) {
-    std::vector<float> out(1024);
-    for (int d = 0; d < 2; ++d)
-        for (int w = 0; w < 4; ++w)
-            for (int b = 0; b < 4; ++b)
-                for (int rho = 0; rho < 32; ++rho) {
-                    const int col = gate_col(w, b, rho);
-                    out[((d * 4 + w) * 4 + b) * 32 + rho] = (d ? bb : fb)[col] * gate_scale(col);
-                }
-    return out;
-}
-int upload16(clair_engine *e, unsigned short **dst, const std::vector<unsigned short> &src) {
-    (void)hipFree(*dst); *dst = nullptr;
-    HIP_TRY(e, hipMalloc((void **)dst, src.size() * sizeof(unsigned short)));
-    HIP_TRY(e, hipMemcpy(*dst, src.data(), src.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
-    return 0;
-}
-
-void free_lane(Lane &l) {
-    if (l.stream) (void)hipStreamSynchronize(l.stream);
-    for (auto &t : l.timed) { (void)hipEventDestroy(t.start); (void)hipEventDestroy(t.stop); }
-    for (auto ev : l.free_events) (void)hipEventDestroy(ev);
-    (void)hipFree(l.zx); (void)hipFree(l.a1); (void)hipFree(l.a2); (void)hipFree(l.l4part); (void)hipFree(l.fuse_flags);
-    if (l.stream) (void)hipStreamDestroy(l.stream);
-}
-
-void free_slot(Slot &s) {
-    if (s.ev_out) (void)hipEventSynchronize(s.ev_out);
-    if (s.ev_in) (void)hipEventDestroy(s.ev_in);
-    if (s.ev_done) (void)hipEventDestroy(s.ev_done);
-    if (s.ev_out) (void)hipEventDestroy(s.ev_out);
-    (void)hipFree(s.d_x); (void)hipFree(s.d_out);
-    if (s.h_out) (void)hipHostFree(s.h_out);
-    if (s.h_x) (void)hipHostFree(s.h_x);
-    if (s.d_counts) (void)hipFree(s.d_counts);
-    if (s.d_records) (void)hipFree(s.d_records);
-    if (s.h_counts) (void)hipHostFree(s.h_counts);
-    if (s.d_centre) (void)hipFree(s.d_centre);
-    if (s.h_centre) (void)hipHostFree(s.h_centre);
-    if (s.d_calls) (void)hipFree(s.d_calls);
-    if (s.h_calls) (void)hipHostFree(s.h_calls);
-    if (s.d_labels) (void)hipFree(s.d_labels);
-    if (s.h_labels) (void)hipHostFree(s.h_labels);
-}
-
-hipEvent_t get_event(Lane &s) {
-    if (!s.free_events.empty()) {
-        hipEvent_t ev = s.free_events.back();
-        s.free_events.pop_back();
+hipEvent_t get_event(Lane &l) {
+    if (!l.free_events.empty()) {
+        hipEvent_t ev = l.free_events.back();
+        l.free_events.pop_back();
         return ev;
     }
     hipEvent_t ev = nullptr;
@@ -290,12 +201,12 @@ hipEvent_t get_event(Lane &s) {
 }
 
 struct KernelTimer {
-    clair_engine *e; Lane &s; int id; hipEvent_t start = nullptr, stop = nullptr;
-    KernelTimer(clair_engine *e_, Lane &s_, int id_) : e(e_), s(s_), id(id_) {
-        if ((e->timing_mask >> id) & 1u) { start = get_event(s); stop = get_event(s); (void)hipEventRecord(start, s.stream); }
+    clair_engine *e; Lane &l; int id; hipEvent_t start = nullptr, stop = nullptr;
+    KernelTimer(clair_engine *e_, Lane &l_, int id_) : e(e_), l(l_), id(id_) {
+        if ((e->timing_mask >> id) & 1u) { start = get_event(l); stop = get_event(l); (void)hipEventRecord(start, l.stream); }
     }
     ~KernelTimer() {
-        if (start) { (void)hipEventRecord(stop, s.stream); s.timed.push_back({id, start, stop}); }
+        if (start) { (void)hipEventRecord(stop, l.stream); l.timed.push_back({id, start, stop}); }
     }
 };
 
@@ -304,17 +215,17 @@ int quiesce(clair_engine *e);
 int drain_timers(clair_engine *e) {
     if (quiesce(e)) return 1;           // nothing is being enqueued (and timed) while the lists are read
     for (auto &lp : e->lanes) {
-        Lane &s = *lp;
-        HIP_TRY(e, hipStreamSynchronize(s.stream));
-        for (auto &t : s.timed) {
+        Lane &l = *lp;
+        HIP_TRY(e, hipStreamSynchronize(l.stream));
+        for (auto &t : l.timed) {
             float ms = 0.f;
             HIP_TRY(e, hipEventElapsedTime(&ms, t.start, t.stop));
             e->ms_sum[t.kernel] += ms;
             e->launches[t.kernel] += 1;
-            s.free_events.push_back(t.start);
-            s.free_events.push_back(t.stop);
+            l.free_events.push_back(t.start);
+            l.free_events.push_back(t.stop);
         }
-        s.timed.clear();
+        l.timed.clear();
     }
     return 0;
 }
@@ -331,62 +242,62 @@ bool use_lstm2_pair(const clair_engine *e, int ntiles) { return e->lstm2_pair < 
 
 // Enqueue the forward pass for n candidates whose input is at x_dev ([n_pad][1056], rows >= n
 // zero or any finite value) writing packed outputs to out_dev ([n][90]).
-int enqueue_forward(clair_engine *e, Lane &s, const float *x_dev, float *out_dev, int n, int slot_index) {
+int enqueue_forward(clair_engine *e, Lane &l, const float *x_dev, float *out_dev, int n, int slot_index) {
     const int n_pad = (n + 31) & ~31;
     const int ntiles = n_pad / L32_TILE;
     const int m_rows = T_POS * n_pad;
-    s.last_n_pad = n_pad;
+    l.last_n_pad = n_pad;
     {   // LSTM1 with its input projection fused in (no separate GEMM, no zx round trip), fp16 split products
-        KernelTimer kt(e, s, CLAIR_K_LSTM1);
-        Lstm32Args a{x_dev, e->wx1s, e->bx1, nullptr, e->wh1s, s.a1, nullptr, n_pad, ntiles, -1};
-        hipLaunchKernelGGL((lstm32_kernel<true>), dim3(ntiles * 2), dim3(256), 0, s.stream, a);
+        KernelTimer kt(e, l, CLAIR_K_LSTM1);
+        Lstm32Args a{x_dev, e->wx1s.as<unsigned short>(), e->bx1.as<float>(), nullptr, e->wh1s.as<unsigned short>(), l.a1.as<unsigned short>(), nullptr, n_pad, ntiles, -1};
+        hipLaunchKernelGGL((lstm32_kernel<true>), dim3(ntiles * 2), dim3(256), 0, l.stream, a);
     }
     if (use_lstm2_fused(e, ntiles)) {   // layer 2 in one launch: projection and recurrence side by side, zx through L2 (lstm2_fused.hip.h)
-        KernelTimer kt(e, s, CLAIR_K_LSTM2);
+        KernelTimer kt(e, l, CLAIR_K_LSTM2);
         const int groups = e->fused_groups;
-        if (++s.fuse_ticket == 0) s.fuse_ticket = 1;   // (a wrapped ticket could meet a 4-billion-passes-old word; the words are zero at most once)
-        Lstm2FusedArgs a{GemmSplitArgs{s.a1, e->wx2s, e->bx2, s.zx, n_pad, ntiles, m_rows, groups},
-                         Lstm32Args{nullptr, nullptr, nullptr, s.zx, e->wh2s, nullptr, s.a2, n_pad, ntiles, -1},
-                         FuseArgs{s.fuse_flags, s.fuse_ticket, s.fuse_flags + fuse_words(e->max_pad) + 1, s.fuse_flags + fuse_words(e->max_pad)}, 32 * groups};
+        if (++l.fuse_ticket == 0) l.fuse_ticket = 1;   // (a wrapped ticket could meet a 4-billion-passes-old word; the words are zero at most once)
+        Lstm2FusedArgs a{GemmSplitArgs{l.a1.as<unsigned short>(), e->wx2s.as<unsigned short>(), e->bx2.as<float>(), l.zx.as<float>(), n_pad, ntiles, m_rows, groups},
+                         Lstm32Args{nullptr, nullptr, nullptr, l.zx.as<float>(), e->wh2s.as<unsigned short>(), nullptr, l.a2.as<float>(), n_pad, ntiles, -1},
+                         FuseArgs{l.fuse_flags.as<unsigned>(), l.fuse_ticket, l.fuse_flags.as<unsigned>() + fuse_words(e->max_pad) + 1, l.fuse_flags.as<unsigned>() + fuse_words(e->max_pad)}, 32 * groups};
         const int consumers = 32 * ((ntiles / 2 + 7) / 8);
         const bool fault = ++e->fused_launches == e->fused_fault_at;
-        if (fault) HIP_TRY(e, hipMemsetD32Async((hipDeviceptr_t)a.f.claims, (int)s.fuse_ticket, 1, s.stream));
-        hipLaunchKernelGGL(lstm2_fused_kernel, dim3(32 * groups + consumers), dim3(256), 0, s.stream, a);
-        if (fault) HIP_TRY(e, hipMemsetAsync(s.a2, 0x7f, (size_t)T_POS * n_pad * 256 * sizeof(float), s.stream));
-        s.fused_runs.push_back({x_dev, out_dev, n, slot_index});
+        if (fault) HIP_TRY(e, hipMemsetD32Async((hipDeviceptr_t)a.f.claims, (int)l.fuse_ticket, 1, l.stream));
+        hipLaunchKernelGGL(lstm2_fused_kernel, dim3(32 * groups + consumers), dim3(256), 0, l.stream, a);
+        if (fault) HIP_TRY(e, hipMemsetAsync(l.a2.as<float>(), 0x7f, (size_t)T_POS * n_pad * 256 * sizeof(float), l.stream));
+        l.fused_runs.push_back({x_dev, out_dev, n, slot_index});
     } else {
         {   // LSTM2 input projection on the fp16 matrix cores, fp32-grade via the 2-way split; weight-stationary persistent workgroups
-            KernelTimer kt(e, s, CLAIR_K_PROJ2);
+            KernelTimer kt(e, l, CLAIR_K_PROJ2);
             const int x_tiles = (m_rows + GS_ROWS - 1) / GS_ROWS;
             const int groups = std::min(e->proj2_groups, (x_tiles + 7) / 8);
-            GemmSplitArgs a{s.a1, e->wx2s, e->bx2, s.zx, n_pad, ntiles, m_rows, groups};
-            hipLaunchKernelGGL(gemm_split_kernel, dim3(32 * groups), dim3(256), 0, s.stream, a);
+            GemmSplitArgs a{l.a1.as<unsigned short>(), e->wx2s.as<unsigned short>(), e->bx2.as<float>(), l.zx.as<float>(), n_pad, ntiles, m_rows, groups};
+            hipLaunchKernelGGL(gemm_split_kernel, dim3(32 * groups), dim3(256), 0, l.stream, a);
         }
         {
-            KernelTimer kt(e, s, CLAIR_K_LSTM2);
+            KernelTimer kt(e, l, CLAIR_K_LSTM2);
             if (use_lstm2_pair(e, ntiles)) {
-                Lstm32PairArgs a{s.zx, e->wh2s, s.a2, n_pad, ntiles};
-                hipLaunchKernelGGL(lstm32_pair_kernel, dim3(((ntiles + 1) / 2) * 2), dim3(256), 0, s.stream, a);
+                Lstm32PairArgs a{l.zx.as<float>(), e->wh2s.as<unsigned short>(), l.a2.as<float>(), n_pad, ntiles};
+                hipLaunchKernelGGL(lstm32_pair_kernel, dim3(((ntiles + 1) / 2) * 2), dim3(256), 0, l.stream, a);
             } else {
-                Lstm32Args a{nullptr, nullptr, nullptr, s.zx, e->wh2s, nullptr, s.a2, n_pad, ntiles, -1};
-                hipLaunchKernelGGL((lstm32_kernel<false>), dim3(ntiles * 2), dim3(256), 0, s.stream, a);
+                Lstm32Args a{nullptr, nullptr, nullptr, l.zx.as<float>(), e->wh2s.as<unsigned short>(), nullptr, l.a2.as<float>(), n_pad, ntiles, -1};
+                hipLaunchKernelGGL((lstm32_kernel<false>), dim3(ntiles * 2), dim3(256), 0, l.stream, a);
             }
         }
     }
     {   // L3 (slice dense) + L4 (split-K 8: a workgroup walks the four channel groups of its split), fused
-        KernelTimer kt(e, s, CLAIR_K_L4);
-        L3L4Args a{s.a2, e->w3s, e->w4s, s.l4part, n_pad, std::ldexp(1.0f, -e->w3_shift), e->tap_l3 ? s.zx : nullptr,
-                   e->l34_stamps ? (unsigned long long *)s.zx : nullptr};   // zx is dead by now
-        hipLaunchKernelGGL(l3l4_kernel, dim3(l34_grid((n_pad + L34_CAND - 1) / L34_CAND)), dim3(L34_THREADS), 0, s.stream, a);
+        KernelTimer kt(e, l, CLAIR_K_L4);
+        L3L4Args a{l.a2.as<float>(), e->w3s.as<unsigned short>(), e->w4s.as<unsigned short>(), l.l4part.as<float>(), n_pad, std::ldexp(1.0f, -e->w3_shift), e->tap_l3 ? l.zx.as<float>() : nullptr,
+                   e->l34_stamps ? l.zx.as<unsigned long long>() : nullptr};   // zx is dead by now
+        hipLaunchKernelGGL(l3l4_kernel, dim3(l34_grid((n_pad + L34_CAND - 1) / L34_CAND)), dim3(L34_THREADS), 0, l.stream, a);
     }
     {
-        KernelTimer kt(e, s, CLAIR_K_TAIL);
-        TailArgs a{s.l4part, e->b4, e->w5s, e->b5, e->whs, e->bh, out_dev, n_pad, n, std::ldexp(1.0f, -e->w4_shift) / L34_ACT_SCALE, {}, {}};
+        KernelTimer kt(e, l, CLAIR_K_TAIL);
+        TailArgs a{l.l4part.as<float>(), e->b4.as<float>(), e->w5s.as<unsigned short>(), e->b5.as<float>(), e->whs.as<unsigned short>(), e->bh.as<float>(), out_dev, n_pad, n, std::ldexp(1.0f, -e->w4_shift) / L34_ACT_SCALE, {}, {}};
         for (int k = 0; k < 4; ++k) {
             a.l5_scale[k] = std::ldexp(1.0f, -e->w5_shift[k]) / TAIL_ACT_SCALE;
             a.head_scale[k] = std::ldexp(1.0f, -e->wh_shift[k]) / TAIL_ACT_SCALE;
         }
-        hipLaunchKernelGGL(tail_kernel, dim3(n_pad / TAIL_TILE), dim3(TAIL_THREADS), 0, s.stream, a);
+        hipLaunchKernelGGL(tail_kernel, dim3(n_pad / TAIL_TILE), dim3(TAIL_THREADS), 0, l.stream, a);
     }
     HIP_TRY(e, hipGetLastError());
     return 0;
@@ -396,7 +307,29 @@ int enqueue_forward(clair_engine *e, Lane &s, const float *x_dev, float *out_dev
 // (clair_slot_input), whichever comes first: one allocation, under the lock the look-ups below take.
 int ensure_slot_input(clair_engine *e, Slot &s) {
     std::lock_guard<std::mutex> g(e->pinned_mu);
-    if (!s.h_x) HIP_TRY(e, hipHostMalloc((void **)&s.h_x, (size_t)e->max_batch * CLAIR_INPUT_FLOATS * sizeof(float), hipHostMallocDefault));
+    HIP_TRY(e, s.h_x.ensure((size_t)e->max_batch * CLAIR_INPUT_FLOATS * sizeof(float)));
+    return 0;
+}
+
+// The other buffers a slot has from their first use on (each keeps what it has once it has it): raw counts on the device and the
+// page-locked staging of a caller's pageable ones; records as they lie, `span` bytes of them, grown when a batch needs more, then to what
+// a full batch of this stride takes; the decode's centre bytes and call records, and the scoring's true indices, on both sides of the link.
+int ensure_slot_counts(clair_engine *e, Slot &s) { HIP_TRY(e, s.d_counts.ensure((size_t)e->max_pad * CLAIR_INPUT_FLOATS * sizeof(short))); return 0; }
+int ensure_slot_counts_staging(clair_engine *e, Slot &s) { HIP_TRY(e, s.h_counts.ensure((size_t)e->max_batch * CLAIR_INPUT_FLOATS * sizeof(short))); return 0; }
+int ensure_slot_records(clair_engine *e, Slot &s, size_t span, size_t stride) {
+    if (s.d_records.bytes < span) HIP_TRY(e, s.d_records.ensure(std::max(span, (size_t)e->max_batch * stride)));
+    return 0;
+}
+int ensure_slot_decode(clair_engine *e, Slot &s) {
+    HIP_TRY(e, s.d_centre.ensure((size_t)e->max_pad * 2));
+    HIP_TRY(e, s.h_centre.ensure((size_t)e->max_batch * 2));
+    HIP_TRY(e, s.d_calls.ensure((size_t)e->max_pad * sizeof(clair_call_t)));
+    HIP_TRY(e, s.h_calls.ensure((size_t)e->max_batch * sizeof(clair_call_t)));
+    return 0;
+}
+int ensure_slot_labels(clair_engine *e, Slot &s) {
+    HIP_TRY(e, s.d_labels.ensure((size_t)e->max_pad * 4));
+    HIP_TRY(e, s.h_labels.ensure((size_t)e->max_batch * 4));
     return 0;
 }
 
@@ -404,11 +337,10 @@ int ensure_slot_input(clair_engine *e, Slot &s) {
 bool in_pinned(const clair_engine *e, const void *p, size_t len) {
     std::lock_guard<std::mutex> g(e->pinned_mu);
     for (const auto &b : e->pinned)
-        if ((const char *)p >= b.first && (const char *)p + len <= b.first + b.second) return true;
+        if ((const char *)p >= b.as<char>() && (const char *)p + len <= b.as<char>() + b.bytes) return true;
     return false;
 }
 
-// n candidates of `row` bytes each, `stride` bytes apart in the caller's buffer (0: dense), into a dense staging buffer
 // memory of this process's HIP devices (hipMalloc), as opposed to anything the host allocated
 bool is_device_pointer(const void *p) {
     hipPointerAttribute_t attr;
@@ -416,6 +348,7 @@ bool is_device_pointer(const void *p) {
     return attr.type == hipMemoryTypeDevice;
 }
 
+// n candidates of `row` bytes each, `stride` bytes apart in the caller's buffer (0: dense), into a dense staging buffer
 void gather_rows(void *dst, const void *src, int n, size_t row, int64_t stride) {
     if (stride == 0 || (size_t)stride == row) { memcpy(dst, src, (size_t)n * row); return; }
     for (int i = 0; i < n; ++i) memcpy((char *)dst + (size_t)i * row, (const char *)src + (size_t)i * (size_t)stride, row);
@@ -424,7 +357,7 @@ void gather_rows(void *dst, const void *src, int n, size_t row, int64_t stride) 
 // The decode of the slot's batch on the device (decode.hip.h): probabilities in d_out + window in d_x + centre bytes -> call records.
 int enqueue_decode(clair_engine *e, Lane &l, Slot &s, int n) {
     KernelTimer kt(e, l, CLAIR_K_DECODE);
-    DecodeArgs a{s.d_x, s.d_out, s.d_centre, s.d_calls, n};
+    DecodeArgs a{s.d_x.as<float>(), s.d_out.as<float>(), s.d_centre.as<unsigned char>(), s.d_calls.as<clair_call_t>(), n};
     hipLaunchKernelGGL(decode_kernel, dim3((n + 3) / 4), dim3(256), 0, l.stream, a);
     HIP_TRY(e, hipGetLastError());
     return 0;
@@ -434,25 +367,17 @@ int enqueue_decode(clair_engine *e, Lane &l, Slot &s, int n) {
 // It has no id in enum clair_kernel_id (callers size arrays by CLAIR_K_COUNT), so clair_kernel_times does not see it.
 static_assert(EVAL_COUNTS == CLAIR_EVAL_COUNTS, "evaluate.hip.h and include/clair_amd.h disagree on the counter block");
 int enqueue_eval(clair_engine *e, Lane &l, Slot &s, int n) {
-    EvalArgs a{s.d_out, s.d_labels, e->eval_counts, n};
+    EvalArgs a{s.d_out.as<float>(), s.d_labels.as<unsigned char>(), e->eval_counts.as<unsigned long long>(), n};
     hipLaunchKernelGGL(eval_kernel, dim3((n + EVAL_CAND - 1) / EVAL_CAND), dim3(256), 0, l.stream, a);
     HIP_TRY(e, hipGetLastError());
     return 0;
 }
 
-int ensure_slot_labels(clair_engine *e, Slot &s) {
-    if (!s.d_labels) {
-        HIP_TRY(e, hipMalloc((void **)&s.d_labels, (size_t)e->max_pad * 4));
-        HIP_TRY(e, hipHostMalloc((void **)&s.h_labels, (size_t)e->max_batch * 4, hipHostMallocDefault));
-    }
-    return 0;
-}
-
 // the counter block exists (zeroed) from the first call that needs it
 int ensure_eval_counts(clair_engine *e) {
-    if (!e->eval_counts) {
-        HIP_TRY(e, hipMalloc((void **)&e->eval_counts, (size_t)CLAIR_EVAL_COUNTS * sizeof(unsigned long long)));
-        HIP_TRY(e, hipMemset(e->eval_counts, 0, (size_t)CLAIR_EVAL_COUNTS * sizeof(unsigned long long)));
+    if (!e->eval_counts.p) {
+        HIP_TRY(e, e->eval_counts.ensure((size_t)CLAIR_EVAL_COUNTS * sizeof(unsigned long long)));
+        HIP_TRY(e, hipMemset(e->eval_counts.p, 0, (size_t)CLAIR_EVAL_COUNTS * sizeof(unsigned long long)));
         HIP_TRY(e, hipStreamSynchronize(nullptr));   // a memset of device memory may return before it ran; the lanes' streams do not wait for the null stream
     }
     return 0;
@@ -477,7 +402,7 @@ int check_labels(clair_engine *e, const uint8_t *labels, int n) {
 // outputs again when they are waited for (Slot::refetch).
 int recover_fused(clair_engine *e, Lane &l, int current) {
     HIP_TRY(e, hipStreamSynchronize(l.stream));
-    HIP_TRY(e, hipMemsetAsync(l.fuse_flags + fuse_words(e->max_pad), 0, sizeof(unsigned), l.stream));
+    HIP_TRY(e, hipMemsetAsync(l.fuse_flags.as<unsigned>() + fuse_words(e->max_pad), 0, sizeof(unsigned), l.stream));
     if (e->lstm2_fused != 0)
         fprintf(stderr, "clair_amd: the fused layer-2 launch found its blocks placed differently from what it assumes (a logical id claimed twice, or "
                         "a bounded wait that ran out); re-running %d pass(es) on the two-launch path and keeping it for this handle\n", (int)l.fused_runs.size());
@@ -496,11 +421,11 @@ int recover_fused(clair_engine *e, Lane &l, int current) {
 int check_fused_placement(clair_engine *e) {
     for (auto &lp : e->lanes) {
         Lane &l = *lp;
-        if (!l.fuse_flags) continue;
+        if (!l.fuse_flags.p) continue;
         std::lock_guard<std::mutex> g(l.order);
         if (!l.fused_runs.empty()) {
             unsigned bad = 0;
-            HIP_TRY(e, hipMemcpy(&bad, l.fuse_flags + fuse_words(e->max_pad), sizeof bad, hipMemcpyDeviceToHost));
+            HIP_TRY(e, hipMemcpy(&bad, l.fuse_flags.as<unsigned>() + fuse_words(e->max_pad), sizeof bad, hipMemcpyDeviceToHost));
             if (bad && recover_fused(e, l, -1)) return 1;
         }
         l.fused_runs.clear();
@@ -531,8 +456,8 @@ __global__ __launch_bounds__(256) void counts_to_input_strided_kernel(const char
 // Where the fused launch's error word lives in a slot's page-locked output buffer, in floats: the first 16-byte boundary past the
 // last uint4 the result kernel below may write for a full batch (it copies the probabilities as WHOLE vectors: for an odd n the last
 // one reaches 8 bytes past n * 360), so that neither that vector nor the end of the allocation can touch the word.
-static inline size_t h_word_offset(int max_batch) { return ((((size_t)max_batch * OUT_FLOATS * sizeof(float) + 15) / 16) * 16) / sizeof(float); }
-static inline size_t h_out_floats(int max_batch) { return h_word_offset(max_batch) + 4; }
+inline size_t h_word_offset(int max_batch) { return ((((size_t)max_batch * OUT_FLOATS * sizeof(float) + 15) / 16) * 16) / sizeof(float); }
+inline size_t h_out_floats(int max_batch) { return h_word_offset(max_batch) + 4; }
 
 // results of a forward pass (and decode) to the slot's page-locked buffers, written by the GPU itself: no copy engine, no queue switch
 __global__ __launch_bounds__(256) void results_to_host_kernel(const uint4 *out, uint4 *h_out, int out_vec, const uint4 *calls, uint4 *h_calls, int call_vec,
@@ -546,15 +471,15 @@ __global__ __launch_bounds__(256) void results_to_host_kernel(const uint4 *out, 
 // The way back: call records, probabilities and the fused launch's error word into the slot's page-locked buffers, on the slot's
 // outgoing stream (which may be the lane's own), then the event clair_wait sleeps on.
 int enqueue_results(clair_engine *e, Lane &l, Slot &s, int n, bool calls, bool probs) {
-    unsigned *word = l.fuse_flags ? l.fuse_flags + fuse_words(e->max_pad) : nullptr;
-    unsigned *h_word = (unsigned *)(s.h_out + h_word_offset(e->max_batch));
+    unsigned *word = l.fuse_flags.p ? l.fuse_flags.as<unsigned>() + fuse_words(e->max_pad) : nullptr;
+    unsigned *h_word = (unsigned *)(s.h_out.as<float>() + h_word_offset(e->max_batch));
     if (e->d2h_kernel) {
         const int out_vec = probs ? (n * OUT_FLOATS * (int)sizeof(float) + 15) / 16 : 0, call_vec = calls ? n * (int)sizeof(clair_call_t) / 16 : 0;
-        hipLaunchKernelGGL(results_to_host_kernel, dim3((std::max(out_vec + call_vec, 1) + 255) / 256), dim3(256), 0, s.cout, (const uint4 *)s.d_out, (uint4 *)s.h_out, out_vec,
-                           (const uint4 *)s.d_calls, (uint4 *)s.h_calls, call_vec, word, h_word);
+        hipLaunchKernelGGL(results_to_host_kernel, dim3((std::max(out_vec + call_vec, 1) + 255) / 256), dim3(256), 0, s.cout, s.d_out.as<uint4>(), s.h_out.as<uint4>(), out_vec,
+                           s.d_calls.as<uint4>(), s.h_calls.as<uint4>(), call_vec, word, h_word);
     } else {
-        if (calls) HIP_TRY(e, hipMemcpyAsync(s.h_calls, s.d_calls, (size_t)n * sizeof(clair_call_t), hipMemcpyDeviceToHost, s.cout));
-        if (probs) HIP_TRY(e, hipMemcpyAsync(s.h_out, s.d_out, (size_t)n * OUT_FLOATS * sizeof(float), hipMemcpyDeviceToHost, s.cout));
+        if (calls) HIP_TRY(e, hipMemcpyAsync(s.h_calls.p, s.d_calls.p, (size_t)n * sizeof(clair_call_t), hipMemcpyDeviceToHost, s.cout));
+        if (probs) HIP_TRY(e, hipMemcpyAsync(s.h_out.p, s.d_out.p, (size_t)n * OUT_FLOATS * sizeof(float), hipMemcpyDeviceToHost, s.cout));
         if (word) HIP_TRY(e, hipMemcpyAsync(h_word, word, sizeof(unsigned), hipMemcpyDeviceToHost, s.cout));
     }
     HIP_TRY(e, hipEventRecord(s.ev_out, s.cout));
@@ -578,62 +503,52 @@ int enqueue_request(clair_engine *e, int slot_index, const clair_engine::Request
     const size_t stride = q.stride ? (size_t)q.stride : row_bytes;
     const size_t span = (size_t)(n - 1) * stride + row_bytes;
     const float *own_input;
-    { std::lock_guard<std::mutex> g(e->pinned_mu); own_input = s.h_x; }
+    { std::lock_guard<std::mutex> g(e->pinned_mu); own_input = s.h_x.as<float>(); }
     const bool direct = (q.input == (const void *)own_input && own_input && stride == row_bytes && !q.counts) || in_pinned(e, q.input, span);
     const bool on_device = !direct && is_device_pointer(q.input);   // e.g. the windows of clair_frontend_build_windows: no copy at all
     if (on_device && !q.counts) return fail(e, "a device pointer is taken for int16 counts only");
     enum { NONE, DENSE, STRIDED } convert = NONE;                    // the int16 -> float32 kernel the lane runs first
     const char *convert_from = nullptr;
     if (q.counts) {
-        if (!s.d_counts && !on_device) HIP_TRY(e, hipMalloc((void **)&s.d_counts, (size_t)e->max_pad * CLAIR_INPUT_FLOATS * sizeof(short)));
+        if (!on_device && ensure_slot_counts(e, s)) return 1;
         if (on_device) {
             convert = STRIDED; convert_from = (const char *)q.input;
         } else if (direct && stride != row_bytes) {   // records as they lie: ONE contiguous copy of the span, the conversion kernel skips what lies between the counts
-            if (s.d_records_bytes < span) {
-                (void)hipFree(s.d_records); s.d_records = nullptr; s.d_records_bytes = 0;
-                const size_t want = std::max(span, (size_t)e->max_batch * stride);
-                HIP_TRY(e, hipMalloc((void **)&s.d_records, want));
-                s.d_records_bytes = want;
-            }
-            HIP_TRY(e, hipMemcpyAsync(s.d_records, q.input, span, hipMemcpyHostToDevice, s.cin));
-            convert = STRIDED; convert_from = s.d_records;
+            if (ensure_slot_records(e, s, span, stride)) return 1;
+            HIP_TRY(e, hipMemcpyAsync(s.d_records.p, q.input, span, hipMemcpyHostToDevice, s.cin));
+            convert = STRIDED; convert_from = s.d_records.as<char>();
         } else {
             const void *src = q.input;
             if (!direct) {
-                if (!s.h_counts) HIP_TRY(e, hipHostMalloc((void **)&s.h_counts, (size_t)e->max_batch * CLAIR_INPUT_FLOATS * sizeof(short), hipHostMallocDefault));
-                gather_rows(s.h_counts, q.input, n, row_bytes, q.stride);
-                src = s.h_counts;
+                if (ensure_slot_counts_staging(e, s)) return 1;
+                gather_rows(s.h_counts.p, q.input, n, row_bytes, q.stride);
+                src = s.h_counts.p;
             }
-            HIP_TRY(e, hipMemcpyAsync(s.d_counts, src, (size_t)n * row_bytes, hipMemcpyHostToDevice, s.cin));
-            convert = DENSE; convert_from = (const char *)s.d_counts;
+            HIP_TRY(e, hipMemcpyAsync(s.d_counts.p, src, (size_t)n * row_bytes, hipMemcpyHostToDevice, s.cin));
+            convert = DENSE; convert_from = s.d_counts.as<char>();
         }
     } else if (direct && stride != row_bytes) {
-        HIP_TRY(e, hipMemcpy2DAsync(s.d_x, row_bytes, q.input, stride, row_bytes, (size_t)n, hipMemcpyHostToDevice, s.cin));
+        HIP_TRY(e, hipMemcpy2DAsync(s.d_x.p, row_bytes, q.input, stride, row_bytes, (size_t)n, hipMemcpyHostToDevice, s.cin));
     } else {
         const void *src = q.input;
         if (!direct) {
             if (ensure_slot_input(e, s)) return 1;
-            gather_rows(s.h_x, q.input, n, row_bytes, q.stride);
-            src = s.h_x;
+            gather_rows(s.h_x.p, q.input, n, row_bytes, q.stride);
+            src = s.h_x.p;
         }
-        HIP_TRY(e, hipMemcpyAsync(s.d_x, src, (size_t)n * row_bytes, hipMemcpyHostToDevice, s.cin));
+        HIP_TRY(e, hipMemcpyAsync(s.d_x.p, src, (size_t)n * row_bytes, hipMemcpyHostToDevice, s.cin));
     }
     if (n_pad > n)
-        HIP_TRY(e, hipMemsetAsync(s.d_x + (size_t)n * CLAIR_INPUT_FLOATS, 0, (size_t)(n_pad - n) * CLAIR_INPUT_FLOATS * sizeof(float), s.cin));
+        HIP_TRY(e, hipMemsetAsync(s.d_x.as<float>() + (size_t)n * CLAIR_INPUT_FLOATS, 0, (size_t)(n_pad - n) * CLAIR_INPUT_FLOATS * sizeof(float), s.cin));
     if (q.calls) {
-        if (!s.d_centre) {
-            HIP_TRY(e, hipMalloc((void **)&s.d_centre, (size_t)e->max_pad * 2));
-            HIP_TRY(e, hipHostMalloc((void **)&s.h_centre, (size_t)e->max_batch * 2, hipHostMallocDefault));
-            HIP_TRY(e, hipMalloc((void **)&s.d_calls, (size_t)e->max_pad * sizeof(clair_call_t)));
-            HIP_TRY(e, hipHostMalloc((void **)&s.h_calls, (size_t)e->max_batch * sizeof(clair_call_t), hipHostMallocDefault));
-        }
-        memcpy(s.h_centre, q.centre, (size_t)n * 2);
-        HIP_TRY(e, hipMemcpyAsync(s.d_centre, s.h_centre, (size_t)n * 2, hipMemcpyHostToDevice, s.cin));
+        if (ensure_slot_decode(e, s)) return 1;
+        memcpy(s.h_centre.p, q.centre, (size_t)n * 2);
+        HIP_TRY(e, hipMemcpyAsync(s.d_centre.p, s.h_centre.p, (size_t)n * 2, hipMemcpyHostToDevice, s.cin));
     }
     if (q.labels) {
         if (ensure_slot_labels(e, s)) return 1;
-        memcpy(s.h_labels, q.labels, (size_t)n * 4);
-        HIP_TRY(e, hipMemcpyAsync(s.d_labels, s.h_labels, (size_t)n * 4, hipMemcpyHostToDevice, s.cin));
+        memcpy(s.h_labels.p, q.labels, (size_t)n * 4);
+        HIP_TRY(e, hipMemcpyAsync(s.d_labels.p, s.h_labels.p, (size_t)n * 4, hipMemcpyHostToDevice, s.cin));
     }
     // int16 counts -> the float32 tensor.  On the LANE, in front of LSTM1 (default): a kernel of 1 056 small workgroups on the incoming stream has to
     // find CUs of its own among lanes whose recurrent workgroups hold whole CUs (one wave per SIMD, every register), and now and then it waits for
@@ -642,9 +557,9 @@ int enqueue_request(clair_engine *e, int slot_index, const clair_engine::Request
     auto launch_convert = [&](hipStream_t st) {
         const int n_quads = n * (CLAIR_INPUT_FLOATS / 4);
         if (convert == DENSE)
-            hipLaunchKernelGGL(counts_to_input_kernel, dim3((n_quads + 255) / 256), dim3(256), 0, st, (const short4 *)convert_from, (f32x4 *)s.d_x, n_quads);
+            hipLaunchKernelGGL(counts_to_input_kernel, dim3((n_quads + 255) / 256), dim3(256), 0, st, (const short4 *)convert_from, s.d_x.as<f32x4>(), n_quads);
         else if (convert == STRIDED)
-            hipLaunchKernelGGL(counts_to_input_strided_kernel, dim3((n_quads + 255) / 256), dim3(256), 0, st, convert_from, stride, (f32x4 *)s.d_x, n_quads);
+            hipLaunchKernelGGL(counts_to_input_strided_kernel, dim3((n_quads + 255) / 256), dim3(256), 0, st, convert_from, stride, s.d_x.as<f32x4>(), n_quads);
     };
     const bool convert_on_lane = e->convert_on_lane && !same_in;
     if (!convert_on_lane) launch_convert(s.cin);
@@ -654,7 +569,7 @@ int enqueue_request(clair_engine *e, int slot_index, const clair_engine::Request
         if (!same_in) g.lock();
         if (!same_in) HIP_TRY(e, hipStreamWaitEvent(l.stream, s.ev_in, 0));
         if (convert_on_lane) launch_convert(l.stream);
-        if (enqueue_forward(e, l, s.d_x, s.d_out, n, slot_index)) return 1;
+        if (enqueue_forward(e, l, s.d_x.as<float>(), s.d_out.as<float>(), n, slot_index)) return 1;
         if (q.calls && enqueue_decode(e, l, s, n)) return 1;
         if (q.labels && enqueue_eval(e, l, s, n)) return 1;
         if (same_out) return enqueue_results(e, l, s, n, q.calls != nullptr, want_probs);      // in line with the kernels, under the lane's lock
@@ -721,11 +636,46 @@ int quiesce(clair_engine *e) {
     return 0;
 }
 
-int check_slot(clair_engine *e, int slot) {
+int check_slot(clair_engine *e, int slot, bool need_weights = true) {
     if (!e) return fail(nullptr, "engine is NULL");
     if (slot < 0 || slot >= (int)e->slots.size()) return fail(e, "slot %d out of range [0,%d)", slot, (int)e->slots.size());
-    if (!e->weights_ready) return fail(e, "weights not loaded: call clair_set_tensor for all tensors, then clair_finalize_weights");
+    if (need_weights && !e->weights_ready) return fail(e, "weights not loaded: call clair_set_tensor for all tensors, then clair_finalize_weights");
     return 0;
+}
+
+int check_n(clair_engine *e, int n) {
+    if (n < 1 || n > e->max_batch) return fail(e, "n=%d out of range [1,%d]", n, e->max_batch);
+    return 0;
+}
+
+// What the four submit entry points ask of a request, in the order they have always asked it: the slot, the weights, n, then
+// `pointers_ok` with the entry point's own message (which pointers it insists on is its own business), the probability arrays (all four
+// or none) and the stride.
+int check_request(clair_engine *e, int slot, const clair_engine::Request &q, bool pointers_ok, const char *pointers_message) {
+    if (check_slot(e, slot) || check_n(e, q.n)) return 1;
+    if (!pointers_ok) return fail(e, "%s", pointers_message);
+    if ((q.gt21 || q.gt || q.l1 || q.l2) && !(q.gt21 && q.gt && q.l1 && q.l2)) return fail(e, "the four probability arrays come together or not at all");
+    return 0;
+}
+int check_stride(clair_engine *e, const clair_engine::Request &q) {
+    if (q.stride != 0 && q.stride < (int64_t)(CLAIR_INPUT_FLOATS * (q.counts ? sizeof(short) : sizeof(float))))
+        return fail(e, "input stride of %lld bytes is shorter than one candidate", (long long)q.stride);
+    return 0;
+}
+
+// The packed [n][90] rows the kernels exchange, from and to the four arrays callers hold: 21 | 3 | 33 | 33 floats (HEAD_SIZE).
+static_assert(HEAD_SIZE[0] + HEAD_SIZE[1] + HEAD_SIZE[2] + HEAD_SIZE[3] == OUT_FLOATS, "the four heads fill a packed row");
+void pack_rows(float *rows, const float *const (&heads)[4], int n) {
+    for (int i = 0; i < n; ++i) {
+        float *row = rows + (size_t)i * OUT_FLOATS;
+        for (int k = 0; k < 4; row += HEAD_SIZE[k], ++k) memcpy(row, heads[k] + (size_t)i * HEAD_SIZE[k], HEAD_SIZE[k] * sizeof(float));
+    }
+}
+void unpack_rows(const float *rows, float *const (&heads)[4], int n) {
+    for (int i = 0; i < n; ++i) {
+        const float *row = rows + (size_t)i * OUT_FLOATS;
+        for (int k = 0; k < 4; row += HEAD_SIZE[k], ++k) memcpy(heads[k] + (size_t)i * HEAD_SIZE[k], row, HEAD_SIZE[k] * sizeof(float));
+    }
 }
 
 }  // namespace
@@ -792,20 +742,20 @@ int clair_engine_create(int device, int max_batch, int n_slots, clair_engine_t *
     { const char *t = getenv("CLAIR_AMD_D2H"); if (t) e->d2h_kernel = !strcmp(t, "kernel"); }
     { const char *t = getenv("CLAIR_AMD_CONVERT"); if (t) e->convert_on_lane = strcmp(t, "copy") != 0; }
     for (int i = 0; i < n_lanes; ++i) e->lanes.emplace_back(new Lane());
-    e->slots.resize(n_slots);
+    e->slots = std::vector<Slot>(n_slots);   // (a Slot owns its buffers and does not move)
     const size_t mp = e->max_pad;
     hipError_t r = hipSuccess;
     for (auto &lp : e->lanes) {
         Lane &l = *lp;
         if (r == hipSuccess) r = hipStreamCreateWithFlags(&l.stream, hipStreamNonBlocking);
-        if (r == hipSuccess) r = hipMalloc((void **)&l.zx, (size_t)T_POS * mp * 1024 * sizeof(float));
-        if (r == hipSuccess) r = hipMalloc((void **)&l.a1, ((size_t)2 * T_POS * mp * 256 + 128 * 256) * sizeof(unsigned short));   // + slack rows read (never used) by gemm_split's ragged last tile
-        if (r == hipSuccess) r = hipMalloc((void **)&l.a2, (size_t)T_POS * mp * 256 * sizeof(float));
-        if (r == hipSuccess) r = hipMalloc((void **)&l.l4part, (size_t)L4_SPLITS * ((mp + L34_CAND - 1) / L34_CAND * L34_CAND) * L4_UNITS * sizeof(float));
+        if (r == hipSuccess) r = l.zx.ensure((size_t)T_POS * mp * 1024 * sizeof(float));
+        if (r == hipSuccess) r = l.a1.ensure(((size_t)2 * T_POS * mp * 256 + 128 * 256) * sizeof(unsigned short));   // + slack rows read (never used) by gemm_split's ragged last tile
+        if (r == hipSuccess) r = l.a2.ensure((size_t)T_POS * mp * 256 * sizeof(float));
+        if (r == hipSuccess) r = l.l4part.ensure((size_t)L4_SPLITS * ((mp + L34_CAND - 1) / L34_CAND * L34_CAND) * L4_UNITS * sizeof(float));
         if (r == hipSuccess && fused_possible(e)) {
             const size_t words = fuse_words(e->max_pad) + 1 + fuse_claims(e);   // tickets | error word | claims
-            r = hipMalloc((void **)&l.fuse_flags, words * sizeof(unsigned));
-            if (r == hipSuccess) r = hipMemset(l.fuse_flags, 0, words * sizeof(unsigned));
+            r = l.fuse_flags.ensure(words * sizeof(unsigned));
+            if (r == hipSuccess) r = hipMemset(l.fuse_flags.p, 0, words * sizeof(unsigned));
         }
     }
     for (size_t i = 0; i < e->slots.size(); ++i) {
@@ -836,10 +786,10 @@ int clair_engine_create(int device, int max_batch, int n_slots, clair_engine_t *
         if (r == hipSuccess) r = hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming);
         if (r == hipSuccess) r = hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming);
         if (r == hipSuccess) r = hipEventCreateWithFlags(&s.ev_out, hipEventDisableTiming);
-        if (r == hipSuccess) r = hipMalloc((void **)&s.d_x, mp * CLAIR_INPUT_FLOATS * sizeof(float));
-        if (r == hipSuccess) r = hipMemset(s.d_x, 0, mp * CLAIR_INPUT_FLOATS * sizeof(float));
-        if (r == hipSuccess) r = hipMalloc((void **)&s.d_out, mp * OUT_FLOATS * sizeof(float));
-        if (r == hipSuccess) r = hipHostMalloc((void **)&s.h_out, h_out_floats(max_batch) * sizeof(float), hipHostMallocDefault);   // + the fused launch's error word
+        if (r == hipSuccess) r = s.d_x.ensure(mp * CLAIR_INPUT_FLOATS * sizeof(float));
+        if (r == hipSuccess) r = hipMemset(s.d_x.p, 0, mp * CLAIR_INPUT_FLOATS * sizeof(float));
+        if (r == hipSuccess) r = s.d_out.ensure(mp * OUT_FLOATS * sizeof(float));
+        if (r == hipSuccess) r = s.h_out.ensure(h_out_floats(max_batch) * sizeof(float));   // + the fused launch's error word
     }
     if (r != hipSuccess) {
         fail(nullptr, "allocating workspaces for max_batch=%d, %d slot(s) failed: %s", max_batch, n_slots, hipGetErrorString(r));
@@ -861,16 +811,19 @@ void clair_engine_destroy(clair_engine_t *e) {
     (void)hipSetDevice(e->device);
     for (auto &lp : e->lanes) if (lp->stream) (void)hipStreamSynchronize(lp->stream);
     for (auto st : e->copy_streams) (void)hipStreamSynchronize(st);
-    for (auto &s : e->slots) free_slot(s);
-    for (auto st : e->copy_streams) (void)hipStreamDestroy(st);
-    for (auto &lp : e->lanes) free_lane(*lp);
-    for (auto &b : e->pinned) (void)hipHostFree(b.first);
-    float *w[] = {e->bx1, e->bx2, e->b4, e->b5, e->bh};
-    for (float *p : w) (void)hipFree(p);
-    (void)hipFree(e->w5s); (void)hipFree(e->whs);
-    (void)hipFree(e->eval_counts);
-    (void)hipFree(e->wx2s); (void)hipFree(e->wh1s); (void)hipFree(e->wh2s); (void)hipFree(e->wx1s); (void)hipFree(e->w4s); (void)hipFree(e->w3s);
-    delete e;
+    std::vector<hipStream_t> streams = e->copy_streams;
+    for (auto &s : e->slots) {
+        if (s.ev_out) (void)hipEventSynchronize(s.ev_out);
+        for (hipEvent_t ev : {s.ev_in, s.ev_done, s.ev_out}) if (ev) (void)hipEventDestroy(ev);
+    }
+    for (auto &lp : e->lanes) {
+        if (!lp->stream) continue;
+        for (auto &t : lp->timed) { (void)hipEventDestroy(t.start); (void)hipEventDestroy(t.stop); }
+        for (auto ev : lp->free_events) (void)hipEventDestroy(ev);
+        streams.push_back(lp->stream);
+    }
+    delete e;                                            // every buffer goes with its owner
+    for (auto st : streams) (void)hipStreamDestroy(st);
 }
 
 int clair_set_tensor(clair_engine_t *e, int id, const float *host, int64_t count) {
@@ -889,140 +842,27 @@ int clair_finalize_weights(clair_engine_t *e) {
         if ((int64_t)e->host_tensors[i].size() != TENSOR_COUNT[i]) return fail(e, "tensor %d has not been set", i);
     HIP_TRY(e, hipSetDevice(e->device));
     if (quiesce(e)) return 1;
-    float **dev[] = {&e->bx1, &e->bx2, &e->b4, &e->b5, &e->bh};
-    for (float **p : dev) { (void)hipFree(*p); *p = nullptr; }
-    auto &T = e->host_tensors;
-    if (upload(e, &e->bx1, pack_bias32(T[1], T[3])) || upload(e, &e->bx2, pack_bias32(T[5], T[7]))) return 1;
-    {   // Wx2^T (gate-scaled, gate-row order) as A fragments of the weight-stationary projection GEMM (gemm_split.hip.h):
-        // [gate tile][wm][mi][kk][plane][lane][8]
-        std::vector<unsigned short> w2s((size_t)8 * 2 * 2 * 16 * 2 * 64 * 8);
-        for (int gt = 0; gt < 8; ++gt)
-            for (int wm = 0; wm < 2; ++wm)
-                for (int mi = 0; mi < 2; ++mi)
-                    for (int kk = 0; kk < 16; ++kk)
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int j = 0; j < 8; ++j) {
-                                const int R = gt * 128 + wm * 64 + mi * 32 + (lane & 31), k = 16 * kk + 8 * (lane >> 5) + j;
-                                const int d = R >> 9, col = gate_col((R >> 7) & 3, (R >> 5) & 3, R & 31);
-                                unsigned short hi, lo;
-                                split2_host((d ? T[6] : T[4])[(size_t)k * 512 + col] * gate_scale(col), hi, lo);
-                                const size_t base = ((((((size_t)gt * 2 + wm) * 2 + mi) * 16 + kk) * 2) * 64 + lane) * 8 + j;
-                                w2s[base] = hi;
-                                w2s[base + 64 * 8] = lo;
-                            }
-        if (upload16(e, &e->wx2s, w2s)) return 1;
-    }
-    if (upload16(e, &e->wh1s, pack_wt32(T[0], T[2], F_IN, 8)) || upload16(e, &e->wh2s, pack_wt32(T[4], T[6], 2 * HID, 8)) ||
-        upload16(e, &e->wx1s, pack_wt32(T[0], T[2], 0, 2, (float)(1 << L32_X_SHIFT)))) return 1;
-    // Power-of-two image shift of a tensor: puts its largest magnitude into [2^13, 2^14).  A freshly initialised W4 has sigma = 0.011 and a
-    // trained one may be smaller still, i.e. residuals below the fp16 normal range -- the low plane would keep them to 3e-8 ABSOLUTE
-    // only (common.hip.h); the kernel that consumes the product multiplies by 2^-shift (exact).
-    auto image_shift = [](float vmax) {
-        if (!(vmax > 0.0f) || !std::isfinite(vmax)) return 0;
-        int ex = 0;
-        (void)std::frexp(vmax, &ex);              // vmax = m * 2^ex, m in [0.5, 1)
-        return std::max(-20, std::min(40, 14 - ex));
-    };
-    {   // L3 A fragments (dense.hip.h: l3l4_kernel): (W3[c]^T | b3[c]) * 2^w3_shift as fp16 split, [c][kk][plane][lane][8]: row u = lane%32,
-        // k = 16kk + 8(lane/32) + j: t for k < 33, the bias at k = 33 (the activation operand carries 1.0 there), zero beyond and for u >= 30
-        float vmax = 0.0f;
-        for (float v : T[8]) vmax = std::max(vmax, std::fabs(v));
-        for (float v : T[9]) vmax = std::max(vmax, std::fabs(v));
-        e->w3_shift = image_shift(vmax);
-        const float pow2 = std::ldexp(1.0f, e->w3_shift);
-        std::vector<unsigned short> w3s((size_t)256 * 3 * 2 * 64 * 8, 0);
-        for (int c = 0; c < 256; ++c)
-            for (int kk = 0; kk < 3; ++kk)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const int u = lane & 31, k = 16 * kk + 8 * (lane >> 5) + j;
-                        float v = 0.0f;
-                        if (u < L3_UNITS && k < T_POS) v = T[8][((size_t)c * T_POS + k) * L3_UNITS + u];
-                        else if (u < L3_UNITS && k == T_POS) v = T[9][(size_t)c * L3_UNITS + u];
-                        unsigned short hi, lo;
-                        split2_host(v * pow2, hi, lo);
-                        const size_t base = ((((size_t)c * 3 + kk) * 2) * 64 + lane) * 8 + j;
-                        w3s[base] = hi;
-                        w3s[base + 64 * 8] = lo;
-                    }
-        if (upload16(e, &e->w3s, w3s)) return 1;
-    }
-    {   // W4 as fp16 split B fragments of the fused L3/L4 kernel (dense.hip.h): [cg][ks][nb][plane][lane][8]: row (2ks + lane/32)*256 + cg*8 + j
-        // of W4 * 2^w4_shift, column nb*32 + lane%32; the kernel that reduces the split-K partials multiplies by 2^-w4_shift.
-        float w4max = 0.0f;
-        for (float v : T[10]) w4max = std::max(w4max, std::fabs(v));
-        e->w4_shift = image_shift(w4max);
-        const float w4_pow2 = std::ldexp(1.0f, e->w4_shift);
-        std::vector<unsigned short> w4s((size_t)L34_GROUPS * L34_KS * 6 * 2 * 64 * 8);
-        for (int cg = 0; cg < L34_GROUPS; ++cg)
-            for (int ks = 0; ks < L34_KS; ++ks)
-                for (int nb = 0; nb < 6; ++nb)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < 8; ++j) {
-                            const int u = 2 * ks + (lane >> 5), col = nb * 32 + (lane & 31);
-                            unsigned short hi, lo;
-                            split2_host(T[10][((size_t)u * 256 + cg * L34_CH + j) * L4_UNITS + col] * w4_pow2, hi, lo);
-                            const size_t base = (((((size_t)cg * L34_KS + ks) * 6 + nb) * 2) * 64 + lane) * 8 + j;
-                            w4s[base] = hi;
-                            w4s[base + 64 * 8] = lo;
-                        }
-        if (upload16(e, &e->w4s, w4s) || upload(e, &e->b4, T[11])) return 1;
-    }
-    {   // tail A fragments (dense.hip.h: tail_kernel): W5_k^T and Wh_k^T as fp16 split, each tensor shifted by its own power of two
-        const int sizes[4] = {21, 3, 33, 33};
-        std::vector<unsigned short> w5s((size_t)4 * 12 * 3 * 2 * 64 * 8), whs((size_t)4 * 6 * 2 * 2 * 64 * 8, 0);
-        std::vector<float> bh(4 * 64, 0.0f);
-        for (int k5 = 0; k5 < 4; ++k5) {
-            const float *W5 = T[12].data() + (size_t)k5 * L4_UNITS * L5_UNITS;
-            const std::vector<float> &Wh = T[14 + 2 * k5];
-            float m5 = 0.0f, mh = 0.0f;
-            for (int i = 0; i < L4_UNITS * L5_UNITS; ++i) m5 = std::max(m5, std::fabs(W5[i]));
-            for (float v : Wh) mh = std::max(mh, std::fabs(v));
-            e->w5_shift[k5] = image_shift(m5);
-            e->wh_shift[k5] = image_shift(mh);
-            const float p5 = std::ldexp(1.0f, e->w5_shift[k5]), ph = std::ldexp(1.0f, e->wh_shift[k5]);
-            for (int ks = 0; ks < 12; ++ks)
-                for (int nb = 0; nb < 3; ++nb)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < 8; ++j) {
-                            const int k = 16 * ks + 8 * (lane >> 5) + j, n = nb * 32 + (lane & 31);
-                            unsigned short hi, lo;
-                            split2_host(W5[(size_t)k * L5_UNITS + n] * p5, hi, lo);
-                            const size_t base = ((((((size_t)k5 * 12 + ks) * 3 + nb) * 2) * 64) + lane) * 8 + j;
-                            w5s[base] = hi;
-                            w5s[base + 64 * 8] = lo;
-                        }
-            for (int ks = 0; ks < 6; ++ks)
-                for (int nb = 0; nb < 2; ++nb)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < 8; ++j) {
-                            const int k = 16 * ks + 8 * (lane >> 5) + j, c = nb * 32 + (lane & 31);
-                            unsigned short hi = 0, lo = 0;
-                            if (c < sizes[k5]) split2_host(Wh[(size_t)k * sizes[k5] + c] * ph, hi, lo);
-                            const size_t base = ((((((size_t)k5 * 6 + ks) * 2 + nb) * 2) * 64) + lane) * 8 + j;
-                            whs[base] = hi;
-                            whs[base + 64 * 8] = lo;
-                        }
-            for (int j = 0; j < sizes[k5]; ++j) bh[k5 * 64 + j] = T[15 + 2 * k5][j];
-        }
-        if (upload16(e, &e->w5s, w5s) || upload16(e, &e->whs, whs) || upload(e, &e->b5, T[13]) || upload(e, &e->bh, bh)) return 1;
-    }
+    const WeightImages m = build_weight_images(LAYER_SIZES, e->host_tensors);
+    if (upload(e, e->bx1, m.bx1) || upload(e, e->bx2, m.bx2) || upload(e, e->wx2s, m.wx2s) || upload(e, e->wh1s, m.wh1s) || upload(e, e->wh2s, m.wh2s) ||
+        upload(e, e->wx1s, m.wx1s) || upload(e, e->w3s, m.w3s) || upload(e, e->w4s, m.w4s) || upload(e, e->b4, m.b4) || upload(e, e->w5s, m.w5s) ||
+        upload(e, e->whs, m.whs) || upload(e, e->b5, m.b5) || upload(e, e->bh, m.bh)) return 1;
+    e->w3_shift = m.w3_shift;
+    e->w4_shift = m.w4_shift;
+    for (int k = 0; k < 4; ++k) { e->w5_shift[k] = m.w5_shift[k]; e->wh_shift[k] = m.wh_shift[k]; }
     e->weights_ready = true;
     return 0;
 }
 
 int clair_submit(clair_engine_t *e, int slot, const float *x, int n, float *gt21, float *genotype, float *l1, float *l2) {
-    if (check_slot(e, slot)) return 1;
-    if (n < 1 || n > e->max_batch) return fail(e, "n=%d out of range [1,%d]", n, e->max_batch);
-    if (!x || !gt21 || !genotype || !l1 || !l2) return fail(e, "NULL input/output pointer");
-    return submit_request(e, slot, clair_engine::Request{x, false, 0, n, nullptr, nullptr, gt21, genotype, l1, l2});
+    const clair_engine::Request q{x, false, 0, n, nullptr, nullptr, gt21, genotype, l1, l2};
+    if (check_request(e, slot, q, x && gt21 && genotype && l1 && l2, "NULL input/output pointer")) return 1;
+    return submit_request(e, slot, q);
 }
 
 int clair_submit_counts(clair_engine_t *e, int slot, const int16_t *counts, int n, float *gt21, float *genotype, float *l1, float *l2) {
-    if (check_slot(e, slot)) return 1;
-    if (n < 1 || n > e->max_batch) return fail(e, "n=%d out of range [1,%d]", n, e->max_batch);
-    if (!counts || !gt21 || !genotype || !l1 || !l2) return fail(e, "NULL input/output pointer");
-    return submit_request(e, slot, clair_engine::Request{counts, true, 0, n, nullptr, nullptr, gt21, genotype, l1, l2});
+    const clair_engine::Request q{counts, true, 0, n, nullptr, nullptr, gt21, genotype, l1, l2};
+    if (check_request(e, slot, q, counts && gt21 && genotype && l1 && l2, "NULL input/output pointer")) return 1;
+    return submit_request(e, slot, q);
 }
 
 int clair_slot_input(clair_engine_t *e, int slot, float **x_pinned) {
@@ -1031,7 +871,7 @@ int clair_slot_input(clair_engine_t *e, int slot, float **x_pinned) {
     HIP_TRY(e, hipSetDevice(e->device));
     Slot &s = e->slots[slot];
     if (ensure_slot_input(e, s)) return 1;
-    *x_pinned = s.h_x;
+    *x_pinned = s.h_x.as<float>();
     return 0;
 }
 
@@ -1057,10 +897,10 @@ int clair_wait(clair_engine_t *e, int slot) {
     if (n) HIP_TRY(e, hipEventSynchronize(s.ev_out));
     bool again = s.refetch;
     s.refetch = false;
-    if (l.fuse_flags) {
+    if (l.fuse_flags.p) {
         std::lock_guard<std::mutex> g(l.order);
         unsigned bad;
-        memcpy(&bad, s.h_out + h_word_offset(e->max_batch), sizeof bad);
+        memcpy(&bad, s.h_out.as<float>() + h_word_offset(e->max_batch), sizeof bad);
         bool mine = false;
         for (const auto &r : l.fused_runs) mine = mine || r.slot == slot;
         if (n && bad && mine) {   // re-run on the two-launch path (d_x still holds the input), fetch the outputs again
@@ -1073,20 +913,13 @@ int clair_wait(clair_engine_t *e, int slot) {
         std::lock_guard<std::mutex> g(l.order);
         if (s.o_calls) {
             if (enqueue_decode(e, l, s, n)) { s.pending_n = 0; return 1; }
-            HIP_TRY(e, hipMemcpyAsync(s.h_calls, s.d_calls, (size_t)n * sizeof(clair_call_t), hipMemcpyDeviceToHost, l.stream));
+            HIP_TRY(e, hipMemcpyAsync(s.h_calls.p, s.d_calls.p, (size_t)n * sizeof(clair_call_t), hipMemcpyDeviceToHost, l.stream));
         }
-        if (s.o_gt21) HIP_TRY(e, hipMemcpyAsync(s.h_out, s.d_out, (size_t)n * OUT_FLOATS * sizeof(float), hipMemcpyDeviceToHost, l.stream));
+        if (s.o_gt21) HIP_TRY(e, hipMemcpyAsync(s.h_out.p, s.d_out.p, (size_t)n * OUT_FLOATS * sizeof(float), hipMemcpyDeviceToHost, l.stream));
         HIP_TRY(e, hipStreamSynchronize(l.stream));
     }
-    if (s.o_gt21)
-        for (int i = 0; i < n; ++i) {
-            const float *row = s.h_out + (size_t)i * OUT_FLOATS;
-            memcpy(s.o_gt21 + (size_t)i * 21, row, 21 * sizeof(float));
-            memcpy(s.o_gt + (size_t)i * 3, row + 21, 3 * sizeof(float));
-            memcpy(s.o_l1 + (size_t)i * 33, row + 24, 33 * sizeof(float));
-            memcpy(s.o_l2 + (size_t)i * 33, row + 57, 33 * sizeof(float));
-        }
-    if (s.o_calls) memcpy(s.o_calls, s.h_calls, (size_t)n * sizeof(clair_call_t));
+    if (s.o_gt21) unpack_rows(s.h_out.as<float>(), {s.o_gt21, s.o_gt, s.o_l1, s.o_l2}, n);
+    if (s.o_calls) memcpy(s.o_calls, s.h_calls.p, (size_t)n * sizeof(clair_call_t));
     s.o_calls = nullptr;
     s.pending_n = 0;
     return 0;
@@ -1096,51 +929,34 @@ int clair_wait(clair_engine_t *e, int slot) {
 // asks for the call records (centre: [n][2] bytes, required then); the four probability arrays are optional then (all or none).
 int clair_submit_ex(clair_engine_t *e, int slot, const void *input, int input_is_counts, int64_t input_stride_bytes, int n, const uint8_t *centre,
                     clair_call_t *calls, float *gt21, float *genotype, float *l1, float *l2) {
-    if (check_slot(e, slot)) return 1;
-    if (n < 1 || n > e->max_batch) return fail(e, "n=%d out of range [1,%d]", n, e->max_batch);
-    const bool want_probs = gt21 || genotype || l1 || l2;
-    if (!input) return fail(e, "NULL input pointer");
-    if (want_probs && !(gt21 && genotype && l1 && l2)) return fail(e, "the four probability arrays come together or not at all");
-    if (!want_probs && !calls) return fail(e, "nothing asked for: neither call records nor probabilities");
+    const clair_engine::Request q{input, input_is_counts != 0, input_stride_bytes, n, centre, calls, gt21, genotype, l1, l2};
+    if (check_request(e, slot, q, input != nullptr, "NULL input pointer")) return 1;
+    if (!(gt21 || genotype || l1 || l2) && !calls) return fail(e, "nothing asked for: neither call records nor probabilities");
     if (calls && !centre) return fail(e, "call records need the candidates' centre bytes");
-    if (input_stride_bytes != 0 && input_stride_bytes < (int64_t)(CLAIR_INPUT_FLOATS * (input_is_counts ? sizeof(short) : sizeof(float))))
-        return fail(e, "input stride of %lld bytes is shorter than one candidate", (long long)input_stride_bytes);
-    return submit_request(e, slot, clair_engine::Request{input, input_is_counts != 0, input_stride_bytes, n, centre, calls, gt21, genotype, l1, l2});
+    if (check_stride(e, q)) return 1;
+    return submit_request(e, slot, q);
 }
 
 // The decode alone, on probabilities the caller already has (call_var's --input_probabilities path, clair/call_var.py:1276-1309): synchronous.
 int clair_decode(clair_engine_t *e, int slot, const float *x, const float *gt21, const float *genotype, const float *l1, const float *l2, int n,
                  const uint8_t *centre, clair_call_t *calls) {
-    if (!e) return fail(nullptr, "engine is NULL");
-    if (slot < 0 || slot >= (int)e->slots.size()) return fail(e, "slot %d out of range [0,%d)", slot, (int)e->slots.size());
-    if (n < 1 || n > e->max_batch) return fail(e, "n=%d out of range [1,%d]", n, e->max_batch);
+    if (check_slot(e, slot, false) || check_n(e, n)) return 1;
     if (!x || !gt21 || !genotype || !l1 || !l2 || !centre || !calls) return fail(e, "NULL input/output pointer");
     HIP_TRY(e, hipSetDevice(e->device));
     Slot &s = e->slots[slot];
     if (s.pending_n) return fail(e, "slot %d still has a pending submit; call clair_wait first", slot);
-    if (!s.d_centre) {
-        HIP_TRY(e, hipMalloc((void **)&s.d_centre, (size_t)e->max_pad * 2));
-        HIP_TRY(e, hipHostMalloc((void **)&s.h_centre, (size_t)e->max_batch * 2, hipHostMallocDefault));
-        HIP_TRY(e, hipMalloc((void **)&s.d_calls, (size_t)e->max_pad * sizeof(clair_call_t)));
-        HIP_TRY(e, hipHostMalloc((void **)&s.h_calls, (size_t)e->max_batch * sizeof(clair_call_t), hipHostMallocDefault));
-    }
-    for (int i = 0; i < n; ++i) {   // the packed [n][90] rows the kernels exchange
-        float *row = s.h_out + (size_t)i * OUT_FLOATS;
-        memcpy(row, gt21 + (size_t)i * 21, 21 * sizeof(float));
-        memcpy(row + 21, genotype + (size_t)i * 3, 3 * sizeof(float));
-        memcpy(row + 24, l1 + (size_t)i * 33, 33 * sizeof(float));
-        memcpy(row + 57, l2 + (size_t)i * 33, 33 * sizeof(float));
-    }
-    memcpy(s.h_centre, centre, (size_t)n * 2);
+    if (ensure_slot_decode(e, s)) return 1;
+    pack_rows(s.h_out.as<float>(), {gt21, genotype, l1, l2}, n);
+    memcpy(s.h_centre.p, centre, (size_t)n * 2);
     Lane &l = *e->lanes[s.lane];
     std::lock_guard<std::mutex> g(l.order);
-    HIP_TRY(e, hipMemcpyAsync(s.d_x, x, (size_t)n * CLAIR_INPUT_FLOATS * sizeof(float), hipMemcpyHostToDevice, l.stream));
-    HIP_TRY(e, hipMemcpyAsync(s.d_out, s.h_out, (size_t)n * OUT_FLOATS * sizeof(float), hipMemcpyHostToDevice, l.stream));
-    HIP_TRY(e, hipMemcpyAsync(s.d_centre, s.h_centre, (size_t)n * 2, hipMemcpyHostToDevice, l.stream));
+    HIP_TRY(e, hipMemcpyAsync(s.d_x.p, x, (size_t)n * CLAIR_INPUT_FLOATS * sizeof(float), hipMemcpyHostToDevice, l.stream));
+    HIP_TRY(e, hipMemcpyAsync(s.d_out.p, s.h_out.p, (size_t)n * OUT_FLOATS * sizeof(float), hipMemcpyHostToDevice, l.stream));
+    HIP_TRY(e, hipMemcpyAsync(s.d_centre.p, s.h_centre.p, (size_t)n * 2, hipMemcpyHostToDevice, l.stream));
     if (enqueue_decode(e, l, s, n)) return 1;
-    HIP_TRY(e, hipMemcpyAsync(s.h_calls, s.d_calls, (size_t)n * sizeof(clair_call_t), hipMemcpyDeviceToHost, l.stream));
+    HIP_TRY(e, hipMemcpyAsync(s.h_calls.p, s.d_calls.p, (size_t)n * sizeof(clair_call_t), hipMemcpyDeviceToHost, l.stream));
     HIP_TRY(e, hipStreamSynchronize(l.stream));
-    memcpy(calls, s.h_calls, (size_t)n * sizeof(clair_call_t));
+    memcpy(calls, s.h_calls.p, (size_t)n * sizeof(clair_call_t));
     return 0;
 }
 
@@ -1150,53 +966,39 @@ int clair_eval_reset(clair_engine_t *e) {
     HIP_TRY(e, hipSetDevice(e->device));
     if (quiesce(e)) return 1;
     if (ensure_eval_counts(e)) return 1;
-    HIP_TRY(e, hipMemset(e->eval_counts, 0, (size_t)CLAIR_EVAL_COUNTS * sizeof(unsigned long long)));
+    HIP_TRY(e, hipMemset(e->eval_counts.p, 0, (size_t)CLAIR_EVAL_COUNTS * sizeof(unsigned long long)));
     HIP_TRY(e, hipStreamSynchronize(nullptr));
     return 0;
 }
 
 int clair_submit_eval(clair_engine_t *e, int slot, const void *input, int input_is_counts, int64_t input_stride_bytes, int n, const uint8_t *labels,
                       float *gt21, float *genotype, float *l1, float *l2) {
-    if (check_slot(e, slot)) return 1;
-    if (n < 1 || n > e->max_batch) return fail(e, "n=%d out of range [1,%d]", n, e->max_batch);
-    const bool want_probs = gt21 || genotype || l1 || l2;
-    if (!input || !labels) return fail(e, "NULL input or label pointer");
-    if (want_probs && !(gt21 && genotype && l1 && l2)) return fail(e, "the four probability arrays come together or not at all");
-    if (input_stride_bytes != 0 && input_stride_bytes < (int64_t)(CLAIR_INPUT_FLOATS * (input_is_counts ? sizeof(short) : sizeof(float))))
-        return fail(e, "input stride of %lld bytes is shorter than one candidate", (long long)input_stride_bytes);
+    clair_engine::Request q{input, input_is_counts != 0, input_stride_bytes, n, nullptr, nullptr, gt21, genotype, l1, l2};
+    q.labels = labels;
+    if (check_request(e, slot, q, input && labels, "NULL input or label pointer") || check_stride(e, q)) return 1;
     // a fused layer-2 launch (opt-in) may be re-run after the fact (recover_fused), which would count its batch twice
     if (fused_possible(e)) return fail(e, "clair_submit_eval runs on the two-launch layer-2 path only: unset CLAIR_AMD_LSTM2_FUSED");
     if (check_labels(e, labels, n)) return 1;
     HIP_TRY(e, hipSetDevice(e->device));
     if (ensure_eval_counts(e)) return 1;
-    clair_engine::Request q{input, input_is_counts != 0, input_stride_bytes, n, nullptr, nullptr, gt21, genotype, l1, l2};
-    q.labels = labels;
     return submit_request(e, slot, q);
 }
 
 // The scoring alone, on probabilities the caller holds: synchronous, needs no weights (the twin of clair_decode).
 int clair_eval(clair_engine_t *e, int slot, const float *gt21, const float *genotype, const float *l1, const float *l2, const uint8_t *labels, int n) {
-    if (!e) return fail(nullptr, "engine is NULL");
-    if (slot < 0 || slot >= (int)e->slots.size()) return fail(e, "slot %d out of range [0,%d)", slot, (int)e->slots.size());
-    if (n < 1 || n > e->max_batch) return fail(e, "n=%d out of range [1,%d]", n, e->max_batch);
+    if (check_slot(e, slot, false) || check_n(e, n)) return 1;
     if (!gt21 || !genotype || !l1 || !l2 || !labels) return fail(e, "NULL input pointer");
     if (check_labels(e, labels, n)) return 1;
     HIP_TRY(e, hipSetDevice(e->device));
     Slot &s = e->slots[slot];
     if (s.pending_n) return fail(e, "slot %d still has a pending submit; call clair_wait first", slot);
     if (ensure_eval_counts(e) || ensure_slot_labels(e, s)) return 1;
-    for (int i = 0; i < n; ++i) {   // the packed [n][90] rows the kernels exchange
-        float *row = s.h_out + (size_t)i * OUT_FLOATS;
-        memcpy(row, gt21 + (size_t)i * 21, 21 * sizeof(float));
-        memcpy(row + 21, genotype + (size_t)i * 3, 3 * sizeof(float));
-        memcpy(row + 24, l1 + (size_t)i * 33, 33 * sizeof(float));
-        memcpy(row + 57, l2 + (size_t)i * 33, 33 * sizeof(float));
-    }
-    memcpy(s.h_labels, labels, (size_t)n * 4);
+    pack_rows(s.h_out.as<float>(), {gt21, genotype, l1, l2}, n);
+    memcpy(s.h_labels.p, labels, (size_t)n * 4);
     Lane &l = *e->lanes[s.lane];
     std::lock_guard<std::mutex> g(l.order);
-    HIP_TRY(e, hipMemcpyAsync(s.d_out, s.h_out, (size_t)n * OUT_FLOATS * sizeof(float), hipMemcpyHostToDevice, l.stream));
-    HIP_TRY(e, hipMemcpyAsync(s.d_labels, s.h_labels, (size_t)n * 4, hipMemcpyHostToDevice, l.stream));
+    HIP_TRY(e, hipMemcpyAsync(s.d_out.p, s.h_out.p, (size_t)n * OUT_FLOATS * sizeof(float), hipMemcpyHostToDevice, l.stream));
+    HIP_TRY(e, hipMemcpyAsync(s.d_labels.p, s.h_labels.p, (size_t)n * 4, hipMemcpyHostToDevice, l.stream));
     if (enqueue_eval(e, l, s, n)) return 1;
     HIP_TRY(e, hipStreamSynchronize(l.stream));
     return 0;
@@ -1208,7 +1010,7 @@ int clair_eval_read(clair_engine_t *e, int64_t *counts) {
     HIP_TRY(e, hipSetDevice(e->device));
     if (quiesce(e)) return 1;
     if (ensure_eval_counts(e)) return 1;
-    HIP_TRY(e, hipMemcpy(counts, e->eval_counts, (size_t)CLAIR_EVAL_COUNTS * sizeof(int64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(e, hipMemcpy(counts, e->eval_counts.p, (size_t)CLAIR_EVAL_COUNTS * sizeof(int64_t), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -1254,8 +1056,7 @@ int clair_dataset_download(clair_engine_t *e, const void *out_dev, int64_t first
 }
 
 int clair_run_resident(clair_engine_t *e, int slot, const void *x_dev, void *out_dev, int64_t first, int n) {
-    if (check_slot(e, slot)) return 1;
-    if (n < 1 || n > e->max_batch) return fail(e, "n=%d out of range [1,%d]", n, e->max_batch);
+    if (check_slot(e, slot) || check_n(e, n)) return 1;
     HIP_TRY(e, hipSetDevice(e->device));
     Lane &l = *e->lanes[e->slots[slot].lane];
     std::lock_guard<std::mutex> g(l.order);
@@ -1320,13 +1121,11 @@ int clair_pinned_alloc(clair_engine_t *e, int64_t bytes, void **ptr) {
     if (!e) return fail(nullptr, "engine is NULL");
     if (!ptr || bytes < 1) return fail(e, "bad arguments to clair_pinned_alloc");
     HIP_TRY(e, hipSetDevice(e->device));
-    void *p = nullptr;
-    HIP_TRY(e, hipHostMalloc(&p, (size_t)bytes, hipHostMallocDefault));
-    {
-        std::lock_guard<std::mutex> g(e->pinned_mu);
-        e->pinned.emplace_back((char *)p, (size_t)bytes);
-    }
-    *ptr = p;
+    std::list<PinnedBuffer> one(1);
+    HIP_TRY(e, one.front().ensure((size_t)bytes));
+    *ptr = one.front().p;
+    std::lock_guard<std::mutex> g(e->pinned_mu);
+    e->pinned.splice(e->pinned.end(), one);
     return 0;
 }
 
@@ -1335,15 +1134,13 @@ int clair_pinned_free(clair_engine_t *e, void *ptr) {
     bool known = false;
     {
         std::lock_guard<std::mutex> g(e->pinned_mu);
-        for (const auto &b : e->pinned) known |= b.first == (char *)ptr;
+        for (const auto &b : e->pinned) known |= b.p == ptr;
     }
     if (!known) return fail(e, "clair_pinned_free: not a buffer of clair_pinned_alloc");
     HIP_TRY(e, hipSetDevice(e->device));
     if (quiesce(e)) return 1;   // no copy may still be reading it (and no staging worker is looking it up)
-    HIP_TRY(e, hipHostFree(ptr));
     std::lock_guard<std::mutex> g(e->pinned_mu);
-    for (size_t i = 0; i < e->pinned.size(); ++i)
-        if (e->pinned[i].first == (char *)ptr) { e->pinned.erase(e->pinned.begin() + (long)i); break; }
+    e->pinned.remove_if([ptr](const PinnedBuffer &b) { return b.p == ptr; });   // released with its entry
     return 0;
 }
 
@@ -1361,15 +1158,15 @@ int clair_debug_read(clair_engine_t *e, int slot, int which, float *host, int64_
     if (check_slot(e, slot)) return 1;
     HIP_TRY(e, hipSetDevice(e->device));
     if (quiesce(e)) return 1;
-    Lane &s = *e->lanes[e->slots[slot].lane];
+    Lane &l = *e->lanes[e->slots[slot].lane];
     const float *src = nullptr;
     int64_t avail = 0;
-    const int64_t np = s.last_n_pad;
+    const int64_t np = l.last_n_pad;
     if (which == 1) {   // LSTM1 output lives as two fp16 planes: hand back their fp32 sum
         avail = (int64_t)T_POS * np * 256;
         if (count > avail) return fail(e, "clair_debug_read: asked %lld floats, tap 1 holds %lld", (long long)count, (long long)avail);
         std::vector<unsigned short> planes((size_t)2 * avail);
-        HIP_TRY(e, hipMemcpy(planes.data(), s.a1, planes.size() * sizeof(unsigned short), hipMemcpyDeviceToHost));
+        HIP_TRY(e, hipMemcpy(planes.data(), l.a1.p, planes.size() * sizeof(unsigned short), hipMemcpyDeviceToHost));
         for (int64_t i = 0; i < count; ++i) host[i] = f16_value(planes[i]) + f16_value(planes[avail + i]);
         return 0;
     }
@@ -1377,7 +1174,7 @@ int clair_debug_read(clair_engine_t *e, int slot, int which, float *host, int64_
         avail = (int64_t)T_POS * np * 256;
         if (count > avail) return fail(e, "clair_debug_read: asked %lld floats, tap 2 holds %lld", (long long)count, (long long)avail);
         std::vector<float> raw((size_t)avail);
-        HIP_TRY(e, hipMemcpy(raw.data(), s.a2, raw.size() * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(e, hipMemcpy(raw.data(), l.a2.p, raw.size() * sizeof(float), hipMemcpyDeviceToHost));
         for (int64_t i = 0; i < count; ++i) {
             const int64_t t = i / (np * 256), n = (i / 256) % np, c = i % 256;
             host[i] = raw[(size_t)((((c / 8) * T_POS + t) * np + n) * 8 + c % 8)];
@@ -1386,15 +1183,15 @@ int clair_debug_read(clair_engine_t *e, int slot, int which, float *host, int64_
     }
     switch (which) {
         case 4: if (!e->tap_l3) return fail(e, "clair_debug_read: tap 4 needs CLAIR_AMD_TAP_L3=1 at engine creation");
-                src = s.zx; avail = np * L3_OUT; break;
+                src = l.zx.as<float>(); avail = np * L3_OUT; break;
         case 5: if (!e->l34_stamps) return fail(e, "clair_debug_read: tap 5 needs CLAIR_AMD_L34_STAMPS=1 at engine creation");
-                src = s.zx; avail = ((np + L34_CAND - 1) / L34_CAND) * L4_SPLITS * 8 * 16 * 2; break;   // uint64 pairs of floats
+                src = l.zx.as<float>(); avail = ((np + L34_CAND - 1) / L34_CAND) * L4_SPLITS * 8 * 16 * 2; break;   // uint64 pairs of floats
         case 3: {   // split-K partials live in the accumulator layout (dense.hip.h): hand them back as [8 splits][n_pad][192] in W4's own units
             avail = (int64_t)L4_SPLITS * np * L4_UNITS;
             if (count > avail) return fail(e, "clair_debug_read: asked %lld floats, tap 3 holds %lld", (long long)count, (long long)avail);
             const int64_t nblk = (np + L34_CAND - 1) / L34_CAND;
             std::vector<float> raw((size_t)L4_SPLITS * nblk * L34_CAND * L4_UNITS);
-            HIP_TRY(e, hipMemcpy(raw.data(), s.l4part, raw.size() * sizeof(float), hipMemcpyDeviceToHost));
+            HIP_TRY(e, hipMemcpy(raw.data(), l.l4part.p, raw.size() * sizeof(float), hipMemcpyDeviceToHost));
             const float inv = std::ldexp(1.0f, -e->w4_shift) / L34_ACT_SCALE;
             for (int64_t i = 0; i < count; ++i) {
                 const int64_t cg = i / (np * L4_UNITS), n = (i / L4_UNITS) % np, col = i % L4_UNITS;

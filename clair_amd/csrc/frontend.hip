@@ -18,6 +18,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "device_buffer.h"
+
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
@@ -69,26 +71,6 @@ struct Region {          // what every kernel needs to know about the tables and
 constexpr int PQ_BITS = 21;
 constexpr unsigned long long PQ_MASK = (1ull << PQ_BITS) - 1;
 __device__ inline uint32_t pq_field(unsigned long long w, int field) { return (uint32_t)((w >> (field * PQ_BITS)) & PQ_MASK); }
-
-// a device allocation that is freed with its owner: what the handle and its slabs hold (kernels take the plain views below)
-struct DeviceBuffer {
-    void *p = nullptr;
-    size_t bytes = 0;
-    DeviceBuffer() = default;
-    DeviceBuffer(const DeviceBuffer &) = delete;
-    DeviceBuffer &operator=(const DeviceBuffer &) = delete;
-    ~DeviceBuffer() { reset(); }
-    void reset() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-    hipError_t ensure(size_t n) {      // exactly n bytes (at least one): kept when it has them, freed and allocated anew when the size changes
-        n = std::max<size_t>(n, 1);
-        if (p && bytes == n) return hipSuccess;
-        reset();
-        const hipError_t e = hipMalloc(&p, n);
-        if (e == hipSuccess) bytes = n; else p = nullptr;
-        return e;
-    }
-    template <typename T> T *as() const { return (T *)p; }
-};
 
 struct Slab {
     DeviceBuffer reads, ops, op_elem, seq;   // clair_read_t, clair_op_t, uint32_t [n_ops + 1], uint8_t

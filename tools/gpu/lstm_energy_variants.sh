@@ -29,7 +29,7 @@ PY
       ;;
     esac
     sed -e 's|^int enqueue_forward(|static bool ablated(int id) { static const unsigned m = getenv("CLAIR_ABLATE") ? (unsigned)strtoul(getenv("CLAIR_ABLATE"), nullptr, 0) : 0u; return (m >> id) \& 1u; }\nint enqueue_forward(|' \
-        -e 's|^\(        *\)hipLaunchKernelGGL(\(.*s\.stream, a);\)|\1if (!ablated(kt.id)) hipLaunchKernelGGL(\2|' $d/engine.hip > $d/engine_ablate.hip
+        -e 's|^\(        *\)hipLaunchKernelGGL(\(.*l\.stream, a);\)|\1if (!ablated(kt.id)) hipLaunchKernelGGL(\2|' $d/engine.hip > $d/engine_ablate.hip
     grep -c "ablated(kt.id)" $d/engine_ablate.hip
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fno-slp-vectorize -std=c++17 -shared -fPIC $d/engine_ablate.hip $d/comm.hip -o exp/libclair_e_$v.so -ldl || exit 1
   done

@@ -24,8 +24,8 @@ assert old in s
 open(p,"w").write(s.replace(old, "        if (term == 1) asm volatile(\"s_nop 12\" ::: \"memory\"); else mfma32_vv(xacc[xb], wxa[xb & 1][kk][term == 0 ? 1 : 0], term == 1 ? xl[kk] : xh[kk]);", 1))'
 build anyorder '
 p="clair_amd/csrc/engine.hip"; s=open(p).read()
-old="        hipLaunchKernelGGL((lstm32_kernel<true>), dim3(ntiles * 2), dim3(256), 0, s.stream, a);"
+old="        hipLaunchKernelGGL((lstm32_kernel<true>), dim3(ntiles * 2), dim3(256), 0, l.stream, a);"
 assert old in s
-s=s.replace(old, "        static const bool anyorder = getenv(\"CLAIR_AMD_ANYORDER\") && getenv(\"CLAIR_AMD_ANYORDER\")[0] == 49;\n        if (anyorder && !(e->timing_mask)) hipExtLaunchKernelGGL((lstm32_kernel<true>), dim3(ntiles * 2), dim3(256), 0, s.stream, nullptr, nullptr, hipExtAnyOrderLaunch, a);\n        else hipLaunchKernelGGL((lstm32_kernel<true>), dim3(ntiles * 2), dim3(256), 0, s.stream, a);", 1)
+s=s.replace(old, "        static const bool anyorder = getenv(\"CLAIR_AMD_ANYORDER\") && getenv(\"CLAIR_AMD_ANYORDER\")[0] == 49;\n        if (anyorder && !(e->timing_mask)) hipExtLaunchKernelGGL((lstm32_kernel<true>), dim3(ntiles * 2), dim3(256), 0, l.stream, nullptr, nullptr, hipExtAnyOrderLaunch, a);\n        else hipLaunchKernelGGL((lstm32_kernel<true>), dim3(ntiles * 2), dim3(256), 0, l.stream, a);", 1)
 s=s.replace("#include <hip/hip_runtime.h>", "#include <hip/hip_runtime.h>\n#include <hip/hip_ext.h>", 1)
 open(p,"w").write(s)'
