@@ -27,7 +27,7 @@ SYMBOLS = (
     "clair_frontend_find_candidates", "clair_frontend_set_candidates", "clair_frontend_get_candidates", "clair_frontend_build_windows",
     "clair_frontend_build_windows_ex", "clair_frontend_window_info", "clair_frontend_window_counts", "clair_frontend_counts_device", "clair_frontend_budget_inputs",
     "clair_frontend_stats", "clair_frontend_text_options", "clair_frontend_add_text", "clair_frontend_text_stats", "clair_frontend_slab_reads",
-    "clair_frontend_bam_options", "clair_frontend_add_bam",
+    "clair_frontend_bam_options", "clair_frontend_add_bam", "clair_frontend_bam_lookup", "clair_frontend_indel_table",
     "clair_eval_reset", "clair_submit_eval", "clair_eval", "clair_eval_read",
     "clair_inflate_create", "clair_inflate_destroy", "clair_inflate_last_error", "clair_inflate_blocks", "clair_inflate_blocks_cb",
 )
@@ -144,6 +144,9 @@ def load(path=None):
         if hasattr(lib, "clair_frontend_add_bam") or not older_ok:
             lib.clair_frontend_bam_options.argtypes = [c_vp, c_int, c_int, c_int, c_int, c_i64, c_i64, c_i64, c_i64]
             lib.clair_frontend_add_bam.argtypes = [c_vp, c_vp, c_i64, c_vp, c_i64]
+        if hasattr(lib, "clair_frontend_indel_table") or not older_ok:
+            lib.clair_frontend_bam_lookup.argtypes = [c_vp, c_int]
+            lib.clair_frontend_indel_table.argtypes = [c_vp, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_vp]
     if not older_ok or hasattr(lib, "clair_inflate_create"):
         lib.clair_inflate_create.argtypes = [c_int, c_int, ctypes.POINTER(c_vp)]
         lib.clair_inflate_destroy.argtypes = [c_vp]
@@ -543,6 +546,22 @@ class Frontend(object):
         lo, hi = (-1, -1) if region is None else (int(region[0]), int(region[1]))
         self._check(self._lib.clair_frontend_bam_options(self._h, int(tid), int(dcov), int(evc_min_mq), int(pile_min_mq), a, b, lo, hi),
                     "clair_frontend_bam_options")
+
+    def bam_lookup(self, keep=True):
+        """clair_frontend_bam_lookup, after bam_options: keep and mark what the indel look-up counts (indel_table)."""
+        self._check(self._lib.clair_frontend_bam_lookup(self._h, 1 if keep else 0), "clair_frontend_bam_lookup")
+
+    def indel_table(self, positions, capacity=32):
+        """clair_frontend_indel_table: the indel tables of `positions` (1-based, strictly ascending) from the resident slabs, in one device
+        call -> entries [n][capacity] (clair_amd._hostapi.ENTRY_DTYPE), n_entries, depth (int32), status (uint32, CLAIR_LOOKUP_*)."""
+        from clair_amd._hostapi import ENTRY_DTYPE
+        positions = np.ascontiguousarray(positions, dtype=np.int64)
+        n = len(positions)
+        entries = np.zeros((n, int(capacity)), dtype=ENTRY_DTYPE)
+        n_entries, depth, status = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.uint32)
+        self._check(self._lib.clair_frontend_indel_table(self._h, _ptr(positions), n, _ptr(entries), int(capacity), _ptr(n_entries), _ptr(depth), _ptr(status)),
+                    "clair_frontend_indel_table")
+        return entries, n_entries, depth, status
 
     def add_bam(self, records, length, offsets, n_records):
         """Whole BAM records (clair_amd._hostapi.BamReader.readinto): records = address (int) or a uint8 array, offsets an int64 array of

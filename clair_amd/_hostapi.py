@@ -18,7 +18,8 @@ SYMBOLS = ("clair_host_abi_version", "clair_host_last_error", "clair_host_thread
            "clair_host_sampack_slab", "clair_host_sampack_reset", "clair_host_tuple_budget_binds",
            "clair_host_bam_open", "clair_host_bam_close", "clair_host_bam_info", "clair_host_bam_ref", "clair_host_bam_tid", "clair_host_bam_query",
            "clair_host_bam_next", "clair_host_bam_voffset", "clair_host_bam_render", "clair_host_faidx",
-           "clair_host_bam_set_inflater", "clair_host_inflate_block", "clair_host_inflate_bgzf")
+           "clair_host_bam_set_inflater", "clair_host_inflate_block", "clair_host_inflate_bgzf",
+           "clair_host_sampack_set_lookup", "clair_host_indel_table")
 N_VALUES = 1056
 _lib = None
 
@@ -77,6 +78,8 @@ def load():
         lib.clair_host_sampack_stats.argtypes = [vp, vp]
         lib.clair_host_sampack_slab.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]
         lib.clair_host_sampack_reset.argtypes = [vp]
+        lib.clair_host_sampack_set_lookup.argtypes = [vp, i32]
+        lib.clair_host_indel_table.argtypes = [vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, i32, vp, vp, vp]
         lib.clair_host_bam_open.argtypes = [ctypes.c_char_p, i32, ctypes.POINTER(vp)]
         lib.clair_host_bam_close.argtypes = [vp]
         lib.clair_host_bam_close.restype = None
@@ -496,19 +499,25 @@ class CandidateFinder(_LineSink):
 
 READ_DTYPE = np.dtype([("pos0", "<i8"), ("seq0", "<u4"), ("seq_len", "<u4"), ("op0", "<u4"), ("n_ops", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
 OP_DTYPE = np.dtype([("read", "<u4"), ("code_len", "<u4"), ("ref_off", "<i4"), ("q_off", "<u4")])
-READ_REVERSE, READ_EVC, READ_PILE, READ_FLUSH = 1, 2, 4, 8
+READ_REVERSE, READ_EVC, READ_PILE, READ_FLUSH, READ_LOOKUP = 1, 2, 4, 8, 16
+# clair_indel_entry_t (include/clair_reads.h): one distinct key of a queried position's indel table; `bases` reads back without its zero padding
+ENTRY_DTYPE = np.dtype([("sign", "i1"), ("length", "u1"), ("reserved", "<u2"), ("count", "<u4"), ("first_rank", "<u4"), ("bases", "S50"), ("pad", "u1", (2,))])
+LOOKUP_HITS, LOOKUP_ENTRIES = 1, 2          # CLAIR_LOOKUP_*
 
 
 class SamPacker(_LineSink):
     """clair_host_sampack_*: `samtools view` text -> slabs of packed alignments (include/clair_reads.h) for the device front end."""
 
-    def __init__(self, ctg_name, dcov=250, evc_min_mq=0, pile_min_mq=0, pile_region=None):
+    def __init__(self, ctg_name, dcov=250, evc_min_mq=0, pile_min_mq=0, pile_region=None, lookup=False):
+        """lookup: pack for the indel look-up too (clair_host_sampack_set_lookup): alignments neither stage walks stay, marked READ_LOOKUP."""
         self._lib = load()
         h = ctypes.c_void_p()
         a, b = (-1, -1) if pile_region is None else (int(pile_region[0]), int(pile_region[1]))
         if self._lib.clair_host_sampack_create(ctg_name.encode(), int(dcov), int(evc_min_mq), int(pile_min_mq), a, b, ctypes.byref(h)) != 0:
             raise ValueError("sampack: " + self._lib.clair_host_last_error().decode())
         self._h, self._feed = h, self._lib.clair_host_sampack_feed
+        if lookup and self._lib.clair_host_sampack_set_lookup(self._h, 1) != 0:
+            raise ValueError("sampack: " + self._lib.clair_host_last_error().decode())
 
     def close(self):
         if getattr(self, "_h", None):
@@ -540,6 +549,22 @@ class SamPacker(_LineSink):
 
     def reset(self):
         self._lib.clair_host_sampack_reset(self._h)
+
+
+def indel_table(slabs, positions, capacity=32):
+    """clair_host_indel_table: the indel tables of `positions` (1-based, strictly ascending) over slabs = [(reads, ops, op_elem, seq), ...] in
+    feed order (SamPacker(lookup=True).slab_arrays()).  -> entries [n][capacity] ENTRY_DTYPE, n_entries, depth (int32), status (uint32)."""
+    positions = np.ascontiguousarray(positions, dtype=np.int64)
+    n, k = len(positions), len(slabs)
+    keep = [(np.ascontiguousarray(s[0], dtype=READ_DTYPE), np.ascontiguousarray(s[1], dtype=OP_DTYPE), np.ascontiguousarray(s[3], dtype=np.uint8)) for s in slabs]
+    ptrs = lambda col: (ctypes.c_void_p * max(k, 1))(*[a[col].ctypes.data for a in keep])   # noqa: E731
+    sizes = lambda col: (ctypes.c_int64 * max(k, 1))(*[len(a[col]) for a in keep])           # noqa: E731
+    entries = np.zeros((n, int(capacity)), dtype=ENTRY_DTYPE)
+    n_entries, depth, status = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.uint32)
+    if load().clair_host_indel_table(ptrs(0), sizes(0), ptrs(1), sizes(1), ptrs(2), sizes(2), k, positions.ctypes.data, n, entries.ctypes.data,
+                                     int(capacity), n_entries.ctypes.data, depth.ctypes.data, status.ctypes.data) != 0:
+        raise ValueError(load().clair_host_last_error().decode())
+    return entries, n_entries, depth, status
 
 
 def tuple_budget_binds(reads, tuples, centres, window_tuples, state):

@@ -117,6 +117,10 @@ def native_input(args):
     return getattr(args, "bam_reader", "samtools") == "native"
 
 
+def native_lookup(args):
+    return getattr(args, "indel_lookup", "pysam") == "native"
+
+
 def reference_and_bed(args, search, not_loaded):
     """What both front ends start with: the reference slice of the region (widened by 1 Mbp: the two stages load the same one,
     ExtractVariantCandidates.py:228-236, CreateTensor.py:113-156) and, where candidates are searched for, the .fai looked for before it and the
@@ -393,6 +397,8 @@ class _NativeBam(object):
         from time import time
         from . import _capi, _hostapi
         f.bam_options(self.reader.tid, region=None if self.region[0] is None else self.region, **pack_kw)
+        if native_lookup(self.args):
+            f.bam_lookup(True)
         buf = pinned(BAM_CHUNK + 16)
         offsets = _hostapi.bam_offsets_for(BAM_CHUNK)
         t_dev = 0.0
@@ -546,7 +552,7 @@ class DeviceFrontEnd(object):
                     fill -= cut
                 pst = f.text_stats()
             else:
-                packer = _hostapi.SamPacker(args.ctgName, **pack_kw)
+                packer = _hostapi.SamPacker(args.ctgName, lookup=native_lookup(args) and native_input(args), **pack_kw)
 
                 def read(n):                                   # packing time is the feed loop's less what it waits for here
                     nonlocal t_pack
@@ -735,6 +741,12 @@ def normalise(args):
                 sys.exit("[ERROR] %s configures `samtools view`, which --bam_reader native does not run: drop one of the two" % name)
         if not 1 <= args.bam_threads <= 16:
             sys.exit("[ERROR] --bam_threads %d: 1 .. 16" % args.bam_threads)
+    if native_lookup(args):
+        if not native_input(args):
+            sys.exit("[ERROR] --indel_lookup native answers from the alignments the native reader feeds the device front end: add --bam_reader native")
+        if not wants_device_front_end(args):
+            sys.exit("[ERROR] --indel_lookup native answers from the alignments resident on the GPU: it needs the device front end "
+                     "(drop --front_end host / --front_end_workers)")
     return args
 
 
@@ -762,10 +774,16 @@ def call_region(args, m, prepared=None):
         is_haploid_precision_mode_enabled=args.haploid_precision,
         is_haploid_sensitive_mode_enabled=args.haploid_sensitive,
         is_output_for_ensemble=args.output_for_ensemble, quality_score_for_pass=args.qual)
-    lookup = cv.AlignmentLookup(args.bam_fn, args.ref_fn)
+    device_fe = prepared
+    if native_lookup(args):
+        # the tables come from the front end's slabs, which exist once it has run: the look-up asks for them through this handle
+        def tables(positions, capacity):
+            return device_fe.frontend.indel_table(positions, capacity)
+        lookup = cv.IndelTableLookup(tables, args.ref_fn)
+    else:
+        lookup = cv.AlignmentLookup(args.bam_fn, args.ref_fn)
     decoder = cv.VariantDecoder(config, lookup, always_use_bam=args.pysam_for_all_indel_bases, arith=args.arith)
     writer = cv.VcfWriter(args.call_fn, args.sampleName, args.ref_fn, args.output_for_ensemble)
-    device_fe = prepared
     try:
         batch = args.batch_size or param.engineBatchSize
         source = None
@@ -788,7 +806,13 @@ def call_region(args, m, prepared=None):
 
             def source(batch):
                 return tensor_batches(args, positions, batch)
+        if native_lookup(args) and (device_fe is None or device_fe.frontend is None):
+            sys.exit("[ERROR] --indel_lookup native: the device front end handed this region to the host stages (see the message above), so no "
+                     "alignments are resident on the GPU to look indels up in; --indel_lookup pysam works with every front end")
         cv.call_variants(args, m, decoder, writer, batch, generator=source(batch))
+        if native_lookup(args):
+            logging.info("indel look-up: %d positions in %d device calls (at most %d in one), lookup_over_depth %d, answered by the host twin %d"
+                         % (lookup.positions, lookup.calls, lookup.largest_call, lookup.over_depth, lookup.handed_over))
     finally:
         if device_fe is not None:
             device_fe.close()
@@ -834,7 +858,7 @@ def build_parser():
     add('--threads', type=int, default=None, help="host threads, optional")
     add('--delay', type=int, default=10, help="ignored: there is no TensorFlow start-up thread storm to stagger")
     add('--debug', action='store_true', help="debug lines in the VCF body")
-    add('--pysam_for_all_indel_bases', action='store_true', help="look every indel up in the BAM (needs pysam)")
+    add('--pysam_for_all_indel_bases', action='store_true', help="look every indel up in the BAM (needs pysam, or --indel_lookup native)")
     add('--haploid_precision', action='store_true', help="haploid calling: homozygous variants only")
     add('--haploid_sensitive', action='store_true', help="haploid calling: everything but multi-allelic variants")
     add('--activation_only', action='store_true', help="kept for flag compatibility (plotting is a dead path)")
@@ -871,6 +895,10 @@ def build_parser():
     add('--bam_inflate', type=str, default="host", choices=("host", "device"),
         help="with --bam_reader native: where BGZF blocks are inflated: zlib on --bam_threads host threads (default), or on the GPU --device names, "
              "a wave per block (--bam_threads is then ignored)")
+    add('--indel_lookup', type=str, default="pysam", choices=("pysam", "native"),
+        help="who answers the decode's questions to the BAM (indels of 16 bases or more, the second allele of Ins/Ins calls, every indel with "
+             "--pysam_for_all_indel_bases): pysam (default; every answer is empty where pysam is not installed), or native: the alignments the device "
+             "front end keeps on the GPU (needs --bam_reader native; docs/indel_lookup.md)")
     add('--device', type=int, default=0, help="HIP device ordinal, default: %(default)s")
     add('--arith', type=str, default="legacy", choices=("legacy", "numpy2"),
         help="QUAL/AF arithmetic: float64 as under the reference's NumPy 1.x (legacy) or float32 (numpy2)")

@@ -68,7 +68,7 @@ def commands(args):
         _opt("front_end", args.front_end), _opt("batch_size", args.batch_size), _opt("samtools_threads", args.samtools_threads), _opt("view_readers", args.view_readers),
         # as ONE token: a value that is a single option ("-x", "--no-PG") would otherwise be read as the next flag
         None if args.samtools_view_args is None else '--samtools_view_args="%s"' % args.samtools_view_args,
-        _opt("bam_reader", args.bam_reader), _opt("bam_threads", args.bam_threads), _opt("bam_inflate", args.bam_inflate),
+        _opt("bam_reader", args.bam_reader), _opt("bam_threads", args.bam_threads), _opt("bam_inflate", args.bam_inflate), _opt("indel_lookup", args.indel_lookup),
     ] if x is not None)
     out, k = [], 0
     commands.chunks = []           # (device, output file) per command, for --run
@@ -249,6 +249,7 @@ def build_parser():
     add('--bam_reader', type=str, default=None, choices=("samtools", "native"), help="passed on (callVarBam: read the BAM with samtools or natively)")
     add('--bam_threads', type=int, default=None, help="passed on (callVarBam: BGZF inflate threads of --bam_reader native)")
     add('--bam_inflate', type=str, default=None, choices=("host", "device"), help="passed on (callVarBam: BGZF inflate on the host or on the GPU)")
+    add('--indel_lookup', type=str, default=None, choices=("pysam", "native"), help="passed on (callVarBam: long-indel bases from pysam or from the GPU-resident alignments)")
     return parser
 
 

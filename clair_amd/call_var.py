@@ -142,6 +142,70 @@ class AlignmentLookup(object):
         return self._most_frequent(counts)
 
 
+class IndelTableLookup(object):
+    """AlignmentLookup's answers without pysam (callVarBam --indel_lookup native): from the table of distinct inserted sequences /
+    deleted lengths the look-up over the packed alignments returns per position (include/clair_reads.h, "the indel look-up";
+    docs/indel_lookup.md).  `tables` maps (ascending unique positions, capacity) to (entries, n_entries, depth, status): a
+    clair_amd._capi.Frontend's indel_table on the device, or clair_amd._hostapi.indel_table over host slabs.  prefetch() fetches the
+    tables of a whole batch in ONE call; insertion() / deletion() then only read them.  Deleted bases are the FASTA slice [p, p + n),
+    read natively.  Not restated: pysam's max_depth (positions deeper than 250 are counted in .over_depth) and its mate rules."""
+
+    CAPACITY = 32          # distinct keys per position fetched at first; a position with more is fetched again on its own
+    MAX_DEPTH = 250        # AlignmentLookup's max_depth
+
+    def __init__(self, tables, fasta_path=None):
+        self.sam = self                      # not None: the decoders send the candidates that consult the BAM here
+        self.fasta = self.fasta_path = fasta_path
+        self._tables = tables
+        self._cache = {}
+        self.calls = self.positions = self.largest_call = self.over_depth = self.handed_over = 0
+
+    def close(self):
+        self._cache.clear()
+
+    def prefetch(self, contig, positions):
+        need = sorted(set(int(p) for p in positions if (contig, int(p)) not in self._cache))
+        if not need:
+            return
+        entries, n_entries, depth, status = self._tables(np.asarray(need, dtype=np.int64), self.CAPACITY)
+        self.calls += 1
+        self.positions += len(need)
+        self.largest_call = max(self.largest_call, len(need))
+        for k, p in enumerate(need):
+            row, n = entries[k], int(n_entries[k])
+            if int(status[k]) & 2:           # CLAIR_LOOKUP_ENTRIES: more distinct keys than fetched
+                e1, n1, _, s1 = self._tables(np.asarray([p], dtype=np.int64), n)
+                self.calls += 1
+                row, n = e1[0], int(n1[0])
+                if int(s1[0]) & 2:
+                    raise RuntimeError("indel look-up at %s:%d: %d distinct keys did not fit a table of %d" % (contig, p, n, len(row)))
+            self.handed_over += int(status[k]) & 1
+            self.over_depth += int(depth[k]) > self.MAX_DEPTH
+            self._cache[(contig, p)] = [(int(e["sign"]), int(e["length"]), int(e["count"]), bytes(e["bases"]).decode("latin-1")) for e in row[:n]]
+
+    def _best(self, contig, position, sign, min_len, max_len, ignore=None):
+        """The first-seen key with the highest count among those the query admits: AlignmentLookup._most_frequent over its dict."""
+        self.prefetch(contig, [position])
+        best, best_n = None, 0
+        for s, length, count, bases in self._cache[(contig, int(position))]:
+            if s == sign and min_len <= length <= max_len and (ignore is None or bases != ignore) and count > best_n:
+                best, best_n = (length, bases), count
+        return best
+
+    def insertion(self, contig, position, min_len=1, max_len=LONG_INDEL_CAP, ignore=""):
+        best = self._best(contig, position, 1, min_len, max_len, ignore)
+        return best[1] if best else ""
+
+    def deletion(self, contig, position, min_len=1, max_len=LONG_INDEL_CAP):
+        if self.fasta_path is None:
+            return ""
+        best = self._best(contig, position, -1, min_len, max_len)
+        if not best:
+            return ""
+        from clair_amd import _hostapi
+        return _hostapi.faidx(self.fasta_path, contig, int(position) + 1, int(position) + best[0]) or ""
+
+
 # =============================================================================================
 # indel bases from the pileup tensor
 # =============================================================================================
@@ -441,6 +505,7 @@ class VariantDecoder(object):
                                                 self.arith == "numpy2", with_status=True)
             if self.lookup.sam is None or not (status & 2).any():
                 return rows
+            self._prefetch([infos[i] for i, st in enumerate(status) if st & 2])
             out, at = [], 0
             Y = [np.asarray(a, dtype=np.float32) for a in Y]
             for i, st in enumerate(status):
@@ -478,6 +543,7 @@ class VariantDecoder(object):
             return rows
         if Y is None:
             raise ValueError("decode_calls: candidates that consult the BAM need their probabilities")
+        self._prefetch([infos[i] for i, st in enumerate(status) if st & 2])
         out, at = [], 0
         Y = [np.asarray(a, dtype=np.float32) for a in Y]
         for i, st in enumerate(status):
@@ -488,8 +554,20 @@ class VariantDecoder(object):
             at += int(st & 1)
         return out
 
+    def _prefetch(self, infos):
+        """A look-up that answers from tables (IndelTableLookup) fetches those of all these candidates in one call."""
+        fetch = getattr(self.lookup, "prefetch", None)
+        if fetch is not None and len(infos):
+            by_contig = {}
+            for info in infos:
+                by_contig.setdefault(info[0], []).append(int(info[1]))
+            for contig, positions in by_contig.items():
+                fetch(contig, positions)
+
     def decode_batch_py(self, X, infos, Y):
         gt21, genotype, len1, len2 = [np.asarray(a, dtype=np.float32) for a in Y]
+        if self.bases.always_use_bam and len(infos) > 1:
+            self._prefetch(infos)
         if len(gt21) != len(infos):
             sys.exit("Inconsistent shape between input tensor and output predictions %d/%d" % (len(infos), len(gt21)))
         if self.cfg.is_output_for_ensemble:

@@ -78,6 +78,8 @@ struct Slab {
     int64_t n_reads = 0, n_ops = 0, n_elem = 0, seq_bytes = 0;
 };
 
+struct SlabHostCopy { std::vector<clair_read_t> reads; std::vector<clair_op_t> ops; std::vector<uint8_t> seq; };   // indel look-up, host fallback
+
 struct SlabView {
     const clair_read_t *reads;
     const clair_op_t *ops;
@@ -125,6 +127,7 @@ __global__ __launch_bounds__(256) void fe_tally_kernel(Region g, SlabView s) {
     if (e >= s.n_elem) return;
     const Element el = element_of(s, e);
     const bool evc = el.r.flags & CLAIR_READ_EVC, pile = el.r.flags & CLAIR_READ_PILE;
+    if (!evc && !pile) return;               // kept for the indel look-up only (CLAIR_READ_LOOKUP): neither stage walks it
     const int so = (el.r.flags & CLAIR_READ_REVERSE) ? 1 : 0;
     const int64_t t = el.rp - g.lo;
     const bool inside = t >= 0 && t < g.n;
@@ -220,7 +223,7 @@ __global__ __launch_bounds__(TT_THREADS) void fe_tally_tile_kernel(Region g, Sla
         const uint32_t i = base + (uint32_t)tid;
         if (i < rb) {
             const clair_read_t r = s.reads[i];
-            if (r.n_ops && r.pos0 < p_hi) {
+            if (r.n_ops && r.pos0 < p_hi && (r.flags & (CLAIR_READ_EVC | CLAIR_READ_PILE))) {     // (not what is kept for the indel look-up only)
                 // operations are ordered and their ends (start + length; an insertion counts as one position) never decrease: first one ending beyond p_lo
                 uint32_t a = 0, b = r.n_ops;
                 while (a < b) {
@@ -854,6 +857,7 @@ struct TextOptions {
     int ctg_len;
     int dcov, evc_min_mq, pile_min_mq;
     int64_t pile_start, pile_end;        // 1-based inclusive, -1 -1: none
+    int lookup;                          // clair_frontend_bam_lookup: keep and mark what the indel look-up counts (BAM records only)
 };
 
 struct TextLine {                        // what pass A learns about a line
@@ -861,9 +865,12 @@ struct TextLine {                        // what pass A learns about a line
     uint32_t cigar_off, cigar_len, seq_off, seq_len;
     uint32_t n_ops, n_elem;
     uint32_t flags;                      // CLAIR_READ_REVERSE | CLAIR_READ_EVC | TL_CANDIDATE | TL_ZERO_INDEL | TL_LONG_SPAN | TL_LEAD_INDEL
-    uint32_t pad;
+    uint32_t pad_mask;                   // TL_LOOKUP: clair_read_t.reserved (clair_reads.h)
 };
-enum { TL_CANDIDATE = 16, TL_ZERO_INDEL = 32, TL_LONG_SPAN = 64, TL_LEAD_INDEL = 128 };   // TL_LEAD_INDEL: an I / D while the reference cursor is still at POS
+// TL_LEAD_INDEL: an I / D while the reference cursor is still at POS.  The last three are set for BAM records only -- TL_BAM_NOSEQ: SEQ '*' (l_seq 0): the
+// slab holds the one byte '*' the text path stores; TL_LOOKUP: becomes CLAIR_READ_LOOKUP, counted by the indel look-up and kept whatever the stages think
+// of it; TL_OFFSETS: the part of TL_LONG_SPAN that is about 32-bit offsets, an anomaly for every kept alignment (the rest only where a stage walks it)
+enum { TL_CANDIDATE = 16, TL_ZERO_INDEL = 32, TL_LONG_SPAN = 64, TL_LEAD_INDEL = 128, TL_BAM_NOSEQ = 256, TL_LOOKUP = 512, TL_OFFSETS = 1024 };
 
 struct TextState {                       // carried from chunk to chunk (host copy in clair_frontend)
     int64_t prev_pos, depth_cap;         // CreateTensor.py:249-250, 277-287
@@ -895,6 +902,8 @@ struct CigarWalk {
     uint32_t n_ops = 0;
     uint64_t elems = 0;
     bool zero = false, lead = false;
+    uint32_t pad_mask = 0;               // I / D operations behind something the slab does not hold that is no M (clair_reads.h: CLAIR_READ_LOOKUP)
+    bool prev_pad = false, after_n = false;   // after_n: this walk does not advance over an N, so what follows one is not where the slab says
 
     template <bool EMIT>
     __device__ inline void op(int64_t adv, uint8_t ch, uint32_t read, clair_op_t *ops, uint32_t *op_elem, uint32_t elem0) {
@@ -904,7 +913,7 @@ struct CigarWalk {
         case 'M': case '=': case 'X': code = CLAIR_OP_M; break;
         case 'I': code = CLAIR_OP_I; break;
         case 'D': code = CLAIR_OP_D; break;
-        case 'N': rlen += adv; break;
+        case 'N': rlen += adv; after_n = after_n || adv > 0; break;
         default: break;
         }
         if (code >= 0) {
@@ -914,6 +923,7 @@ struct CigarWalk {
                     ops[n_ops] = clair_op_t{read, (uint32_t)len << 2 | (uint32_t)code, (int32_t)rp, (uint32_t)qp};
                     op_elem[n_ops] = elem0 + (uint32_t)elems;
                 }
+                if (code != CLAIR_OP_M && (prev_pad || after_n)) pad_mask |= 1u << (n_ops < 31 ? n_ops : 31);
                 ++n_ops;
                 elems += (uint64_t)len;
                 if (code != CLAIR_OP_M && rp == 0) lead = true;       // tallied at POS - 1 by the candidate search (EVC :326-336)
@@ -924,6 +934,7 @@ struct CigarWalk {
             if (code != CLAIR_OP_D) qp += adv;
         }
         total += adv;
+        prev_pad = adv == 0 || !(ch == 'M' || ch == '=' || ch == 'X' || ch == 'I' || ch == 'D' || ch == 'N' || ch == 'S');
     }
 };
 
@@ -1025,7 +1036,7 @@ __global__ __launch_bounds__(256) void fe_text_dcov_kernel(TextLine *lines, cons
 __global__ __launch_bounds__(256) void fe_text_keep_kernel(const TextLine *lines, int64_t n_lines, uint8_t *keep) {
     const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (k >= n_lines) return;
-    keep[k] = (lines[k].flags & (CLAIR_READ_EVC | CLAIR_READ_PILE)) ? 1 : 0;
+    keep[k] = (lines[k].flags & (CLAIR_READ_EVC | CLAIR_READ_PILE | TL_LOOKUP)) ? 1 : 0;
 }
 
 // one workgroup: exclusive sums of the kept lines' operation and element counts, sortedness, counters, the state for the next chunk
@@ -1052,7 +1063,7 @@ __global__ __launch_bounds__(256) void fe_text_offsets_kernel(const TextLine *li
             const int64_t before = i > 0 ? lines[kept[i - 1]].pos0 : (carry.have_last ? carry.last_pos : ln.pos0);
             if (ln.pos0 < before) anom |= CLAIR_FE_UNSORTED;
             if ((ln.flags & TL_ZERO_INDEL) && (ln.flags & CLAIR_READ_EVC)) anom |= CLAIR_FE_ZERO_INDEL;
-            if (ln.flags & TL_LONG_SPAN) anom |= CLAIR_FE_LONG_SPAN;
+            if (((ln.flags & TL_LONG_SPAN) && (ln.flags & (CLAIR_READ_EVC | CLAIR_READ_PILE))) || (ln.flags & TL_OFFSETS)) anom |= CLAIR_FE_LONG_SPAN;
             if (ln.flags & CLAIR_READ_EVC) {
                 atomicMax(&s_last_evc, (unsigned long long)(i + 1));
                 if (ln.flags & TL_LEAD_INDEL) {                                // rare: look back over the run of equal start positions for an accepted alignment
@@ -1138,7 +1149,6 @@ struct BamOptions {
     int tid;
     int64_t region_lo, region_hi;        // 1-based inclusive, what `samtools view <bam> ctg:lo-hi` selects; -1 -1: the whole contig
 };
-enum { TL_BAM_NOSEQ = 256 };             // SEQ '*' (l_seq 0): the slab holds the one byte '*' the text path stores
 constexpr uint16_t BAM_VIEW_FILTER = 2316;
 
 __device__ inline uint32_t bam_u32(const uint8_t *base, uint64_t off) {
@@ -1264,8 +1274,10 @@ __global__ __launch_bounds__(256) void fe_bam_records_kernel(const uint8_t *rec,
     out.n_ops = w.n_ops;
     out.n_elem = w.elems > 0xfffffff0ull ? 0xfffffff0u : (uint32_t)w.elems;
     out.flags = ((flag & 16) ? CLAIR_READ_REVERSE : 0) | (evc_ok ? CLAIR_READ_EVC : 0) | (candidate ? TL_CANDIDATE : 0) | (w.zero ? TL_ZERO_INDEL : 0)
-                | (w.lead ? TL_LEAD_INDEL : 0) | (l_seq == 0 ? TL_BAM_NOSEQ : 0)
-                | ((w.rp > (int64_t)seq_len + 100000 - 64 || w.rp > 0x7fffff00 || w.qp > 0x7fffff00) ? TL_LONG_SPAN : 0);
+                | (w.lead ? TL_LEAD_INDEL : 0) | (l_seq == 0 ? TL_BAM_NOSEQ : 0) | ((opt.lookup && n_ops_cigar > 0) ? TL_LOOKUP : 0)
+                | ((w.rp > (int64_t)seq_len + 100000 - 64 || w.rp > 0x7fffff00 || w.qp > 0x7fffff00) ? TL_LONG_SPAN : 0)
+                | ((w.rp > 0x7fffff00 || w.qp > 0x7fffff00) ? TL_OFFSETS : 0);
+    out.pad_mask = opt.lookup ? w.pad_mask : 0;
     all[k] = out;
     pass[k] = 1;
 }
@@ -1296,8 +1308,8 @@ __global__ __launch_bounds__(256) void fe_emit_kernel(const uint8_t *src, const 
     r.seq_len = ln.seq_len;
     r.op0 = op0[i];
     r.n_ops = ln.n_ops;
-    r.flags = ln.flags & (CLAIR_READ_REVERSE | CLAIR_READ_EVC | CLAIR_READ_PILE | CLAIR_READ_FLUSH);
-    r.reserved = 0;
+    r.flags = (ln.flags & (CLAIR_READ_REVERSE | CLAIR_READ_EVC | CLAIR_READ_PILE | CLAIR_READ_FLUSH)) | ((ln.flags & TL_LOOKUP) ? CLAIR_READ_LOOKUP : 0);
+    r.reserved = (ln.flags & TL_LOOKUP) ? ln.pad_mask : 0;
     reads[i] = r;
 }
 
@@ -1368,6 +1380,9 @@ struct clair_frontend {
     DeviceBuffer d2, fold;               // unsigned long long; --stop_consider_left_edge, pass 2 per operation: tuples per window as second differences over positions
     bool pass2_per_base = false;         // CLAIR_AMD_FE_PASS2=base when the handle was created: --stop_consider_left_edge's pass 2 by fe_windows_per_base_kernel
     bool tally_per_base = false;         // CLAIR_AMD_FE_TALLY=atomic when the handle was created: pass 1 by fe_tally_kernel (one device atomic per base)
+    // the indel look-up (indel_lookup.hip): queries, hits per query, tables; sized by the largest call so far
+    DeviceBuffer lk_pos, lk_views, lk_count, lk_hits, lk_entries, lk_n, lk_depth, lk_status;
+    std::deque<SlabHostCopy> lk_host;    // slabs copied back for the host fallback, once each (a slab never changes)
     std::string error;
 
     SlabView view(const Slab &s) const {
@@ -1675,7 +1690,7 @@ int clair_frontend_text_options(clair_frontend_t *f, const char *ctg_name, int d
     if (n) FE_TRY(f, hipMemcpy(f->ctg.p, ctg_name, n, hipMemcpyHostToDevice));
     FE_TRY(f, f->d_text_state.ensure(sizeof(TextState)));
     const bool have_region = pile_start >= 0 && pile_end >= 0;
-    f->text_opt = TextOptions{f->ctg.as<uint8_t>(), (int)n, dcov, evc_min_mq, pile_min_mq, have_region ? pile_start : -1, have_region ? pile_end : -1};
+    f->text_opt = TextOptions{f->ctg.as<uint8_t>(), (int)n, dcov, evc_min_mq, pile_min_mq, have_region ? pile_start : -1, have_region ? pile_end : -1, 0};
     f->text_state = TextState{};
     f->text_ready = true;
     return 0;
@@ -1730,11 +1745,19 @@ int clair_frontend_bam_options(clair_frontend_t *f, int tid, int dcov, int evc_m
     FE_TRY(f, hipSetDevice(f->device));
     FE_TRY(f, f->d_text_state.ensure(sizeof(TextState)));
     const bool have_pile = pile_start >= 0 && pile_end >= 0, have_region = region_lo >= 0 && region_hi >= 0;
-    f->text_opt = TextOptions{nullptr, 0, dcov, evc_min_mq, pile_min_mq, have_pile ? pile_start : -1, have_pile ? pile_end : -1};
+    f->text_opt = TextOptions{nullptr, 0, dcov, evc_min_mq, pile_min_mq, have_pile ? pile_start : -1, have_pile ? pile_end : -1, 0};
     f->bam_opt = BamOptions{tid, have_region ? region_lo : -1, have_region ? region_hi : -1};
     f->text_state = TextState{};
     f->text_ready = true;
     f->bam_mode = true;
+    return 0;
+}
+
+int clair_frontend_bam_lookup(clair_frontend_t *f, int keep) {
+    if (!f) return fe_fail(nullptr, "front end is NULL");
+    if (!f->text_ready || !f->bam_mode) return fe_fail(f, "call clair_frontend_bam_options first");
+    if (f->text_state.lines) return fe_fail(f, "the look-up option cannot change once records were added");
+    f->text_opt.lookup = keep != 0;
     return 0;
 }
 
@@ -2023,3 +2046,6 @@ int clair_frontend_stats(clair_frontend_t *f, int64_t *stats) {
 }
 
 }  // extern "C"
+
+// the indel look-up over the resident slabs: its kernels and clair_frontend_indel_table (part of this translation unit: it works on the handle's slabs)
+#include "indel_lookup.hip"

@@ -25,6 +25,7 @@ constexpr int64_t LOOKAHEAD = 100000;        // CreateTensor.py:275
 struct clair_sampack {
     std::string ctg;
     int dcov = 250, evc_min_mq = 0, pile_min_mq = 0;
+    bool lookup = false;                          // clair_host_sampack_set_lookup: keep and mark what the indel look-up counts
     bool have_region = false;
     int64_t region_start = 0, region_end = 0;     // 1-based inclusive: what `samtools view ctg:start-end` selects for the pileup
     // the slab being filled
@@ -64,10 +65,13 @@ struct clair_sampack {
         // the CIGAR, once: the operations, the aligned fraction of the candidate search (EVC :143-157), samtools' reference length
         const size_t op_first = ops.size();
         int64_t adv = 0, rp = 0, qp = 0, soft = 0, total = 0, rlen = 0;
+        uint32_t pad_mask = 0;                         // CLAIR_READ_LOOKUP: I / D operations behind something the slab does not hold that is no M (clair_reads.h)
+        bool prev_pad = false, after_n = false;        // after_n: the scripts' walk does not advance over an N (:296-316), so what follows one is not where the slab says
         bool zero_indel = false, lead_indel = false;   // lead_indel: an I / D while the reference cursor is still at POS (tallied at POS - 1, EVC :326-336)
         uint64_t elems = op_elem.back();
         const uint32_t read_index = (uint32_t)reads.size();
         auto push = [&](uint32_t code) {
+            if (code != CLAIR_OP_M && (prev_pad || after_n)) { const size_t k = ops.size() - op_first; pad_mask |= 1u << (k < 31 ? k : 31); }
             if (adv > 0x3fffffff) adv = 0x3fffffff;   // absurd; the span check below sends the run to the host path
             ops.push_back(clair_op_t{read_index, (uint32_t)adv << 2 | code, (int32_t)rp, (uint32_t)qp});
             elems += (uint64_t)adv;
@@ -90,10 +94,11 @@ struct clair_sampack {
                 if (adv) { push(CLAIR_OP_D); lead_indel |= rp == 0; } else zero_indel = true;
                 rp += adv; rlen += adv;
                 break;
-            case 'N': rlen += adv; break;
+            case 'N': rlen += adv; after_n |= adv > 0; break;
             default: break;
             }
             total += adv;
+            prev_pad = adv == 0 || !(ch == 'M' || ch == '=' || ch == 'X' || ch == 'I' || ch == 'D' || ch == 'N' || ch == 'S');
             adv = 0;
         }
         const bool evc_ok = same_ctg && mq >= evc_min_mq && !(cl == 1 && cigar[0] == '*') && !mostly_clipped(soft, total);
@@ -115,7 +120,8 @@ struct clair_sampack {
             flush = pile_ok && depth_cap == 0;
         }
         ++reads_total;
-        if (!evc_ok && !pile_ok) {   // neither stage looks at its bases
+        const bool lookup_ok = lookup && same_ctg && !(cl == 1 && cigar[0] == '*');
+        if (!evc_ok && !pile_ok && !lookup_ok) {   // neither stage looks at its bases
             ops.resize(op_first);
             op_elem.resize(op_first + 1);
             return 0;
@@ -129,7 +135,7 @@ struct clair_sampack {
             have_evc_last = true;
             evc_last_pos = pos;
         }
-        if (rp > (int64_t)sl + LOOKAHEAD - 64 || rp > 0x7fffff00 || qp > 0x7fffff00) anomalies |= CLAIR_FE_LONG_SPAN;   // the last two: offsets beyond 32 bits
+        if (((evc_ok || pile_ok) && rp > (int64_t)sl + LOOKAHEAD - 64) || rp > 0x7fffff00 || qp > 0x7fffff00) anomalies |= CLAIR_FE_LONG_SPAN;   // the last two: offsets beyond 32 bits
         if (elems > 0xfffffff0ull || seq.size() + sl > 0xfffffff0ull)
             return clair_host_fail("alignment line %lld: the slab is full (take it before feeding more)", (long long)line_no);
         clair_read_t r;
@@ -138,8 +144,9 @@ struct clair_sampack {
         r.seq_len = (uint32_t)sl;
         r.op0 = (uint32_t)op_first;
         r.n_ops = (uint32_t)(ops.size() - op_first);
-        r.flags = (flag & 16 ? CLAIR_READ_REVERSE : 0) | (evc_ok ? CLAIR_READ_EVC : 0) | (pile_ok ? CLAIR_READ_PILE : 0) | (flush ? CLAIR_READ_FLUSH : 0);
-        r.reserved = 0;
+        r.flags = (flag & 16 ? CLAIR_READ_REVERSE : 0) | (evc_ok ? CLAIR_READ_EVC : 0) | (pile_ok ? CLAIR_READ_PILE : 0) | (flush ? CLAIR_READ_FLUSH : 0)
+                  | (lookup_ok ? CLAIR_READ_LOOKUP : 0);
+        r.reserved = lookup_ok ? pad_mask : 0;
         reads.push_back(r);
         const size_t at = seq.size();
         seq.resize(at + sl);
@@ -175,6 +182,13 @@ int clair_host_sampack_create(const char *ctg_name, int dcov, int evc_min_mq, in
 }
 
 void clair_host_sampack_destroy(clair_sampack_t *p) { delete p; }
+
+int clair_host_sampack_set_lookup(clair_sampack_t *p, int keep) {
+    if (!p) return clair_host_fail("bad argument");
+    if (p->reads_total) return clair_host_fail("the look-up option is chosen before the first alignment");
+    p->lookup = keep != 0;
+    return 0;
+}
 
 int clair_host_sampack_feed(clair_sampack_t *p, const char *sam, int64_t len, int final, int64_t *bytes_consumed) { return feed_lines(p, sam, len, final, bytes_consumed); }
 

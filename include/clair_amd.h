@@ -336,6 +336,20 @@ int clair_frontend_slab_reads(clair_frontend_t *f, int64_t slab, struct clair_re
 int clair_frontend_bam_options(clair_frontend_t *f, int tid, int dcov, int evc_min_mq, int pile_min_mq, int64_t pile_start, int64_t pile_end,
                                int64_t region_lo, int64_t region_hi);
 int clair_frontend_add_bam(clair_frontend_t *f, const uint8_t *records, int64_t len, const int64_t *offsets, int64_t n_records);
+/* After _bam_options, before the first _add_bam: keep != 0 packs for the indel look-up (include/clair_reads.h, "the indel look-up") -- every
+ * record the view prints that has a CIGAR gets CLAIR_READ_LOOKUP and stays in the slab even when neither stage walks it (low MQ, beyond
+ * --dcov: pysam's pileup, which clair/call_var.py:102-170 reads, applies neither).  A sibling of _bam_options because that call's argument
+ * list is fixed.  Off: slabs as ever, byte for byte; on: the same candidates and windows (the stages skip what carries neither EVC nor PILE). */
+int clair_frontend_bam_lookup(clair_frontend_t *f, int keep);
+/* insertion_bases_using_pysam_from / deletion_bases_using_pysam_from (clair/call_var.py:102-170; asked for at :498-565 and :805-823) for n
+ * positions in ONE call, from the slabs resident on the device (csrc/indel_lookup.hip: one thread per I / D operation finds its query,
+ * one wave per query groups its hits by key).  positions[n]: 1-based, strictly ascending.  entries: [n][capacity] (capacity 1 .. 65536),
+ * n_entries[n], depth[n], status[n] (CLAIR_LOOKUP_*): the table defined in include/clair_reads.h, byte for byte what
+ * clair_host_indel_table (include/clair_host.h) writes for the same slabs -- a query the device cannot finish (CLAIR_LOOKUP_HITS) is
+ * answered by that code over the slabs copied back.  Works before and after the candidates are fixed.  Synchronous. */
+struct clair_indel_entry;
+int clair_frontend_indel_table(clair_frontend_t *f, const int64_t *positions, int64_t n, struct clair_indel_entry *entries, int capacity,
+                               int32_t *n_entries, int32_t *depth, uint32_t *status);
 /* The candidate filter over the tallies: arguments as clair_host_evc_create (include/clair_host.h). */
 int clair_frontend_find_candidates(clair_frontend_t *f, double min_coverage, double threshold, int64_t ctg_start, int64_t ctg_end,
                                    const int64_t *bed_start, const int64_t *bed_end, int64_t n_bed, int64_t *n_candidates);

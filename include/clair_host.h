@@ -173,6 +173,18 @@ int clair_host_sampack_stats(const clair_sampack_t *p, int64_t *stats);
 int clair_host_sampack_slab(const clair_sampack_t *p, const struct clair_read **reads, const struct clair_op **ops, const uint32_t **op_elem,
                             const uint8_t **seq);
 int clair_host_sampack_reset(clair_sampack_t *p);
+/* keep != 0: pack for the indel look-up (include/clair_reads.h, "the indel look-up") -- every alignment of the contig with a CIGAR gets
+ * CLAIR_READ_LOOKUP and stays in the slab even when neither stage walks it (low MQ, beyond --dcov: pysam's pileup applies neither,
+ * clair/call_var.py:102-170).  Before the first feed.  Off (the default): slabs as ever, byte for byte. */
+int clair_host_sampack_set_lookup(clair_sampack_t *p, int keep);
+/* The indel look-up on the host (hostsrc/host_indel.cpp; the work of clair/call_var.py:102-170 for n positions at once): the twin of
+ * clair_frontend_indel_table (include/clair_amd.h), same bytes, and what that function falls back to.  n_slabs slabs in feed order
+ * (reads[s], n_reads[s], ops[s], n_ops[s], seq[s], seq_bytes[s]); positions[n] 1-based, strictly ascending; entries [n][capacity],
+ * n_entries[n], depth[n], status[n] (CLAIR_LOOKUP_ENTRIES only).  Rows of `entries` beyond n_entries are zeroed. */
+struct clair_indel_entry;
+int clair_host_indel_table(const struct clair_read *const *reads, const int64_t *n_reads, const struct clair_op *const *ops, const int64_t *n_ops,
+                           const uint8_t *const *seq, const int64_t *seq_bytes, int64_t n_slabs, const int64_t *positions, int64_t n,
+                           struct clair_indel_entry *entries, int capacity, int32_t *n_entries, int32_t *depth, uint32_t *status);
 /* CreateTensor.py's count of free tuple slots (:181, 283-289, 369-373) replayed from what the device counted: alignments in stream
  * order with the tuples each appended, candidate centres ascending with the tuples their windows held when released.  state[0] =
  * free slots (start: 5 000 000), state[1] = first centre not released yet (start: 0); carried from slab to slab.  *binds = 1 when

@@ -25,14 +25,21 @@ typedef struct clair_read {
     uint32_t op0;        /* first operation in the slab's operation array */
     uint32_t n_ops;
     uint32_t flags;      /* CLAIR_READ_* */
-    uint32_t reserved;
+    uint32_t reserved;   /* 0, unless the slab was packed for the indel look-up: CLAIR_READ_LOOKUP below */
 } clair_read_t;          /* 32 bytes */
 
 enum {
     CLAIR_READ_REVERSE = 1,   /* FLAG & 16 (CreateTensor.py:264) */
     CLAIR_READ_EVC = 2,       /* passes the candidate search's filters: RNAME, MQ, CIGAR != "*", >= 55 % aligned (EVC :279-293) */
     CLAIR_READ_PILE = 4,      /* walked by the pileup: in the pileup's region, MQ, not beyond --dcov at its start (CT :266-287) */
-    CLAIR_READ_FLUSH = 8      /* first read the pileup walks at a new start position: windows left of it are complete (CT :369) */
+    CLAIR_READ_FLUSH = 8,     /* first read the pileup walks at a new start position: windows left of it are complete (CT :369) */
+    CLAIR_READ_LOOKUP = 16    /* counted by the indel look-up (below): on the contig, with a CIGAR, whatever its MQ and its rank under --dcov.  Set
+                               * only by a packer that was asked to (clair_host_sampack_set_lookup, clair_frontend_bam_lookup), which then also keeps
+                               * the alignments neither stage walks; both stages ignore an alignment without EVC / PILE.  `reserved` of such an
+                               * alignment marks the I / D operations that follow something the slab does not hold and that is no M / = / X (a P or
+                               * H, a zero-length operation), and every I / D after an N -- the scripts' walk does not advance over an N, so the slab
+                               * places what follows one where THEY see it, not where it lies: bit min(k, 31) for the alignment's k-th kept
+                               * operation.  The look-up skips them. */
 };
 
 typedef struct clair_op {
@@ -59,6 +66,33 @@ enum {
     CLAIR_FE_LEAD_INDEL = 512     /* an alignment the candidate search accepts begins with an I or D (tallied at POS - 1) and an earlier accepted alignment has
                                    * the same POS: the reference flushed POS - 1 after that one (EVC :316-345: positions < POS after EVERY alignment) and
                                    * evaluates the late tally on its own, which one sum per position cannot reproduce */
+};
+
+/* ---- the indel look-up: "the most frequent inserted / deleted sequence right after position p" answered from the slabs ----------
+ * (clair/call_var.py:78-170: insertion_bases_using_pysam_from / deletion_bases_using_pysam_from over pysam's pileup column p - 1.)
+ * Per queried position (1-based p) the table of DISTINCT keys among the I / D operations that count at p: the operation belongs to a
+ * CLAIR_READ_LOOKUP alignment, is 1 .. 50 long (CLAIR_LOOKUP_MAX_LEN: nothing longer is ever asked for, call_var.py:30), the kept
+ * operation before it in the same alignment is an M that ends where it starts (so no N, P, H, I or D lies between, and it does not open
+ * the alignment), and that M's last reference base is 0-based p - 1.  Key of an insertion: its bases, upper-cased; of a deletion: its
+ * length.  Entries come in the order their key was first seen (ascending first_rank; rank = index of the alignment over all slabs in
+ * feed order).  The caller applies min_len / max_len / ignore and takes the highest count, the first seen among equals -- the rule of
+ * the reference's max(dict, key=dict.get).  depth = CLAIR_READ_LOOKUP alignments with an M or D over 0-based p - 1. */
+#define CLAIR_LOOKUP_MAX_LEN 50
+typedef struct clair_indel_entry {
+    int8_t sign;             /* +1 insertion, -1 deletion */
+    uint8_t length;          /* 1 .. CLAIR_LOOKUP_MAX_LEN */
+    uint16_t reserved;       /* 0 */
+    uint32_t count;          /* operations with this key */
+    uint32_t first_rank;     /* rank of the first alignment that showed it */
+    uint8_t bases[50];       /* insertion: its bases, zero-padded; deletion: zeros (the host slices the FASTA) */
+    uint8_t pad[2];          /* 0 */
+} clair_indel_entry_t;       /* 64 bytes */
+
+enum {
+    CLAIR_LOOKUP_HITS = 1,       /* device only: more operations counted at this position than the device's hit list holds per query (512), or two keys
+                                  * shared a hash: the table of this query was computed by the host twin instead (same bytes) */
+    CLAIR_LOOKUP_ENTRIES = 2     /* more distinct keys than `capacity`: n_entries is the number there are, the first `capacity` were written; ask again
+                                  * with that capacity */
 };
 
 #ifdef __cplusplus
