@@ -11,9 +11,10 @@ SUBMODULES = {
     "ExtractVariantCandidates": "clair_amd.extract_variant_candidates",
     "GetTruth": "clair_amd.get_truth",
     "evaluate": "clair_amd.evaluate",
+    "ensemble": "clair_amd.ensemble",
 }
 NOT_COVERED = ("plot_tensor", "train", "train_clr", "PairWithNonVariants", "Tensor2Bin", "CombineBins",
-               "Bin2To3", "ensemble", "overlap_variant")
+               "Bin2To3", "overlap_variant")
 
 
 def main():

@@ -29,8 +29,10 @@ SYMBOLS = (
     "clair_frontend_stats", "clair_frontend_text_options", "clair_frontend_add_text", "clair_frontend_text_stats", "clair_frontend_slab_reads",
     "clair_frontend_bam_options", "clair_frontend_add_bam", "clair_frontend_bam_lookup", "clair_frontend_indel_table",
     "clair_eval_reset", "clair_submit_eval", "clair_eval", "clair_eval_read",
+    "clair_ensemble_models", "clair_ensemble_set_tensor", "clair_ensemble_finalize_weights", "clair_submit_ensemble", "clair_ensemble_average",
     "clair_inflate_create", "clair_inflate_destroy", "clair_inflate_last_error", "clair_inflate_blocks", "clair_inflate_blocks_cb",
 )
+ENSEMBLE_MAX_MODELS = 8                                      # CLAIR_ENSEMBLE_MAX_MODELS
 EVAL_COUNTS = 3 + 21 * 21 + 3 * 3 + 33 * 33 + 33 * 33      # CLAIR_EVAL_COUNTS: all, top1, top2, gt21, genotype, len1, len2
 KERNEL_NAMES = ("proj1", "lstm1", "proj2", "lstm2", "l3", "l4", "tail", "decode")
 
@@ -87,6 +89,12 @@ def load(path=None):
         lib.clair_submit_eval.argtypes = [c_vp, c_int, c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]
         lib.clair_eval.argtypes = [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int]
         lib.clair_eval_read.argtypes = [c_vp, c_vp]
+    if not older_ok or hasattr(lib, "clair_ensemble_models"):
+        lib.clair_ensemble_models.argtypes = [c_vp, c_int]
+        lib.clair_ensemble_set_tensor.argtypes = [c_vp, c_int, c_int, c_vp, c_i64]
+        lib.clair_ensemble_finalize_weights.argtypes = [c_vp, c_int]
+        lib.clair_submit_ensemble.argtypes = [c_vp, c_int, c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
+        lib.clair_ensemble_average.argtypes = [c_vp, c_int, c_vp, c_int, c_int, c_vp]
     lib.clair_wait.argtypes = [c_vp, c_int]
     lib.clair_slot_input.argtypes = [c_vp, c_int, ctypes.POINTER(c_vp)]
     lib.clair_submit_counts.argtypes = [c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]
@@ -188,6 +196,7 @@ class Engine(object):
             self._h = ctypes.c_void_p()
             raise EngineError("clair_engine_create failed: %s" % msg)
         self._pending = {}
+        self.n_models = 1
 
     def _check(self, rc, what):
         if rc != 0:
@@ -212,6 +221,23 @@ class Engine(object):
             a = np.ascontiguousarray(w[key], dtype=np.float32)
             self._check(self._lib.clair_set_tensor(self._h, tid, _ptr(a), a.size), "clair_set_tensor(%s)" % key)
         self._check(self._lib.clair_finalize_weights(self._h), "clair_finalize_weights")
+
+    def load_ensemble(self, list_of_weights):
+        """clair_ensemble_*: the checkpoints of an ensemble, 1 .. ENSEMBLE_MAX_MODELS dicts as load_weights takes them.  The first is
+        image 0, what predict / submit / submit_calls go on using alone; submit_ensemble runs them all, summed in this order."""
+        from clair_amd.weights import TENSOR_IDS, check_weights
+        ws = list(list_of_weights)
+        if not 1 <= len(ws) <= ENSEMBLE_MAX_MODELS:
+            raise ValueError("an ensemble has 1 .. %d checkpoints, got %d" % (ENSEMBLE_MAX_MODELS, len(ws)))
+        for w in ws:
+            check_weights(w)
+        self._check(self._lib.clair_ensemble_models(self._h, len(ws)), "clair_ensemble_models")
+        self.n_models = len(ws)
+        for model, w in enumerate(ws):
+            for key, tid in TENSOR_IDS.items():
+                a = np.ascontiguousarray(w[key], dtype=np.float32)
+                self._check(self._lib.clair_ensemble_set_tensor(self._h, model, tid, _ptr(a), a.size), "clair_ensemble_set_tensor(%d, %s)" % (model, key))
+            self._check(self._lib.clair_ensemble_finalize_weights(self._h, model), "clair_ensemble_finalize_weights(%d)" % model)
 
     # -- predict ---------------------------------------------------------------------------
     @staticmethod
@@ -252,35 +278,52 @@ class Engine(object):
         candidates may be a strided view, e.g. the counts column of an array of binary tensor records: no copy is made here);
         centre: uint8 [n,2] (clair_amd._hostapi.centre_bytes).  wait(slot) then returns the call records (structured array,
         _hostapi.CALL_DTYPE), or (records, [gt21, genotype, len1, len2]) with with_probabilities=True."""
+        self._submit_ex(self._lib.clair_submit_ex, "clair_submit_ex", slot, batch, centre, counts, with_probabilities)
+
+    def submit_ensemble(self, slot, batch, centre=None, counts=False, with_probabilities=False):
+        """clair_submit_ensemble: submit_calls with every checkpoint of load_ensemble -- the batch comes in once, the forward passes run
+        back to back, their probabilities are averaged on the device as the reference's text chain averages them (docs/ensemble.md)
+        and the averaged rows are decoded.  Same arguments and the same results from wait(slot) as submit_calls; centre=None asks for
+        no call records: wait(slot) then returns the averaged [gt21, genotype, len1, len2] alone."""
+        self._submit_ex(self._lib.clair_submit_ensemble, "clair_submit_ensemble", slot, batch, centre, counts, with_probabilities)
+
+    def _submit_ex(self, fn, what, slot, batch, centre, counts, with_probabilities):
         from clair_amd._hostapi import CALL_DTYPE
         if isinstance(batch, DeviceWindows):       # windows the device front end left in HBM: the address goes through as it is
-            n = len(batch)
+            keep, n = batch, len(batch)
+            ptr, is_counts, stride = ctypes.c_void_p(batch.address), 1, 0
+        else:
+            dtype = np.int16 if counts else np.float32
+            x = np.asarray(batch)
+            if x.ndim != 4 or x.shape[1:] != (33, 8, 4):
+                raise ValueError("batch must have shape [n,33,8,4], got %r" % (x.shape,))
+            n = x.shape[0]
+            inner_dense = x.dtype == dtype and n > 0 and x[0].flags.c_contiguous and x.strides[0] >= x[0].nbytes
+            if not inner_dense:
+                x = np.ascontiguousarray(x, dtype=dtype)
+            keep, ptr, is_counts, stride = x, _ptr(x), int(bool(counts)), 0 if x.flags.c_contiguous else int(x.strides[0])
+        c = calls = None
+        if centre is not None:
             c = np.ascontiguousarray(centre, dtype=np.uint8)
             if c.shape != (n, 2):
                 raise ValueError("centre must be uint8 [%d,2], got %r" % (n, c.shape))
             calls = np.zeros(n, dtype=CALL_DTYPE)
-            outs = self._alloc_out(n) if with_probabilities else None
-            ptrs = [_ptr(o) for o in outs] if outs else [None] * 4
-            self._check(self._lib.clair_submit_ex(self._h, int(slot), ctypes.c_void_p(batch.address), 1, 0, n, _ptr(c), _ptr(calls), *ptrs), "clair_submit_ex")
-            self._pending[slot] = ((batch, c), (calls, outs) if outs else calls)
-            return
-        dtype = np.int16 if counts else np.float32
-        x = np.asarray(batch)
-        if x.ndim != 4 or x.shape[1:] != (33, 8, 4):
-            raise ValueError("batch must have shape [n,33,8,4], got %r" % (x.shape,))
-        n = x.shape[0]
-        inner_dense = x.dtype == dtype and n > 0 and x[0].flags.c_contiguous and x.strides[0] >= x[0].nbytes
-        if not inner_dense:
-            x = np.ascontiguousarray(x, dtype=dtype)
-        stride = 0 if x.flags.c_contiguous else int(x.strides[0])
-        c = np.ascontiguousarray(centre, dtype=np.uint8)
-        if c.shape != (n, 2):
-            raise ValueError("centre must be uint8 [%d,2], got %r" % (n, c.shape))
-        calls = np.zeros(n, dtype=CALL_DTYPE)
-        outs = self._alloc_out(n) if with_probabilities else None
+        outs = self._alloc_out(n) if with_probabilities or calls is None else None
         ptrs = [_ptr(o) for o in outs] if outs else [None] * 4
-        self._check(self._lib.clair_submit_ex(self._h, int(slot), _ptr(x), int(bool(counts)), stride, n, _ptr(c), _ptr(calls), *ptrs), "clair_submit_ex")
-        self._pending[slot] = ((x, c), (calls, outs) if outs else calls)
+        self._check(fn(self._h, int(slot), ptr, is_counts, stride, n, _ptr(c) if c is not None else None, _ptr(calls) if calls is not None else None, *ptrs), what)
+        self._pending[slot] = ((keep, c), outs if calls is None else ((calls, outs) if outs else calls))
+
+    def ensemble_average(self, probs, slot=0):
+        """clair_ensemble_average: the device averaging alone.  probs: float32 [K, n, 90] packed rows of K models (or a list of K
+        [gt21, genotype, len1, len2] lists) -> the averaged rows [n, 90] (split_outputs gives the four arrays)."""
+        if isinstance(probs, (list, tuple)) and len(probs) and isinstance(probs[0], (list, tuple)):
+            probs = np.stack([np.concatenate([np.asarray(a, dtype=np.float32) for a in Y], axis=1) for Y in probs])
+        p = np.ascontiguousarray(probs, dtype=np.float32)
+        if p.ndim != 3 or p.shape[2] != 90:
+            raise ValueError("ensemble_average: probs must be [K, n, 90], got %r" % (p.shape,))
+        out = np.empty(p.shape[1:], dtype=np.float32)
+        self._check(self._lib.clair_ensemble_average(self._h, int(slot), _ptr(p), p.shape[0], p.shape[1], _ptr(out)), "clair_ensemble_average")
+        return out
 
     def pinned_buffer(self, nbytes):
         """A page-locked uint8 array of nbytes (clair_pinned_alloc): data placed in it -- e.g. read from a file with readinto -- goes to

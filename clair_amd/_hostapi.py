@@ -19,7 +19,8 @@ SYMBOLS = ("clair_host_abi_version", "clair_host_last_error", "clair_host_thread
            "clair_host_bam_open", "clair_host_bam_close", "clair_host_bam_info", "clair_host_bam_ref", "clair_host_bam_tid", "clair_host_bam_query",
            "clair_host_bam_next", "clair_host_bam_voffset", "clair_host_bam_render", "clair_host_faidx",
            "clair_host_bam_set_inflater", "clair_host_inflate_block", "clair_host_inflate_bgzf",
-           "clair_host_sampack_set_lookup", "clair_host_indel_table")
+           "clair_host_sampack_set_lookup", "clair_host_indel_table",
+           "clair_host_ensemble_average", "clair_host_ensemble_quantise", "clair_host_ensemble_value")
 N_VALUES = 1056
 _lib = None
 
@@ -94,6 +95,9 @@ def load():
         lib.clair_host_bam_set_inflater.argtypes = [vp, vp, vp, i32]
         lib.clair_host_inflate_block.argtypes = [vp, i64, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(i32)]
         lib.clair_host_inflate_bgzf.argtypes = [vp, i64, vp, ctypes.POINTER(i64), ctypes.POINTER(i32)]
+        lib.clair_host_ensemble_average.argtypes = [vp, i32, i64, vp]
+        lib.clair_host_ensemble_quantise.argtypes = [vp, i64, vp]
+        lib.clair_host_ensemble_value.argtypes = [vp, i64, vp]
         lib.clair_host_tuple_budget_binds.argtypes = [vp, vp, i64, vp, vp, i64, vp, ctypes.POINTER(i32)]
         if lib.clair_host_abi_version() != 6:
             raise RuntimeError("libclair_host.so has ABI version %d, expected 6: run `python -m clair_amd.build`"
@@ -782,3 +786,34 @@ def faidx(ref_fn, ctg_name, beg1=None, end1=None):
     if lib.clair_host_faidx(ref_fn.encode(), ctg_name.encode(), a, b, out, n.value, ctypes.byref(n)) != 0:
         return None
     return out.raw[:n.value].decode("latin-1")
+
+
+def ensemble_average(probs):
+    """clair_host_ensemble_average: probs float32 [K, ...] (K = 1 .. 8 models, in summation order) -> their average [...] float32 as the
+    reference's text chain gives it (six decimals out of every model, double sum, six decimals of the mean; docs/ensemble.md).  The CPU
+    twin of the device averaging (clair_amd._capi.Engine.ensemble_average, submit_ensemble)."""
+    p = np.ascontiguousarray(probs, dtype=np.float32)
+    if p.ndim < 1 or p.shape[0] < 1:
+        raise ValueError("ensemble_average: probs must be [K, ...] with K >= 1, got %r" % (p.shape,))
+    out = np.empty(p.shape[1:], dtype=np.float32)
+    if load().clair_host_ensemble_average(p.ctypes.data, p.shape[0], out.size, out.ctypes.data) != 0:
+        raise ValueError(load().clair_host_last_error().decode())
+    return out
+
+
+def ensemble_quantise(p):
+    """clair_host_ensemble_quantise: the millionths '{:0.6f}'.format(v) prints for each float32 v, as int32."""
+    p = np.ascontiguousarray(p, dtype=np.float32)
+    out = np.empty(p.shape, dtype=np.int32)
+    if load().clair_host_ensemble_quantise(p.ctypes.data, p.size, out.ctypes.data) != 0:
+        raise ValueError(load().clair_host_last_error().decode())
+    return out
+
+
+def ensemble_value(millionths):
+    """clair_host_ensemble_value: float32 of the six-decimal text of m millionths (0 .. 10^6)."""
+    m = np.ascontiguousarray(millionths, dtype=np.int32)
+    out = np.empty(m.shape, dtype=np.float32)
+    if load().clair_host_ensemble_value(m.ctypes.data, m.size, out.ctypes.data) != 0:
+        raise ValueError(load().clair_host_last_error().decode())
+    return out

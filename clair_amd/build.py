@@ -21,7 +21,7 @@ def csrc_digest(root=None):
     root = root or os.path.join(HERE, "csrc")
     h = hashlib.sha256()
     for f in sorted(os.listdir(root)):
-        if f.endswith(".hip.h") or f in ("engine.hip", "weight_images.h", "device_buffer.h"):
+        if f.endswith(".hip.h") or f in ("engine.hip", "weight_images.h", "device_buffer.h", "ensemble_core.h"):
             h.update(f.encode() + b"\0" + open(os.path.join(root, f), "rb").read() + b"\0")
     return h.hexdigest()[:16]
 
@@ -36,7 +36,7 @@ def needs_build():
 
 
 HOST_SRCS = [os.path.join(HERE, "hostsrc", f) for f in ("host_io.cpp", "host_decode.cpp", "host_pileup.cpp", "host_sampack.cpp",
-                                                              "host_bam.cpp", "host_inflate.cpp", "host_indel.cpp")]
+                                                              "host_bam.cpp", "host_inflate.cpp", "host_indel.cpp", "host_ensemble.cpp")]
 HOST_OUT = os.path.join(HERE, "libclair_host.so")
 CXX = os.environ.get("CXX", "g++")
 
@@ -48,6 +48,7 @@ def build_host(force=False):
     hdrs.append(os.path.join(HERE, "hostsrc", "sam_line.h"))
     hdrs.append(os.path.join(HERE, "csrc", "inflate_core.h"))       # the decoder host_inflate.cpp shares with the device (csrc/inflate.hip)
     hdrs.append(os.path.join(HERE, "csrc", "indel_lookup_core.h"))  # the table host_indel.cpp shares with the device library (csrc/indel_lookup.hip)
+    hdrs.append(os.path.join(HERE, "csrc", "ensemble_core.h"))      # the averaging rule host_ensemble.cpp shares with the device (csrc/ensemble.hip.h)
     if (force or not os.path.isfile(HOST_OUT)
             or max([os.path.getmtime(f) for f in HOST_SRCS + hdrs]) > os.path.getmtime(HOST_OUT)):
         # -ffp-contract=off: the decode restates float32 product chains bit for bit (no fused multiply-add)

@@ -741,6 +741,7 @@ def normalise(args):
                 sys.exit("[ERROR] %s configures `samtools view`, which --bam_reader native does not run: drop one of the two" % name)
         if not 1 <= args.bam_threads <= 16:
             sys.exit("[ERROR] --bam_threads %d: 1 .. 16" % args.bam_threads)
+    cv.check_ensemble_flags(args)
     if native_lookup(args):
         if not native_input(args):
             sys.exit("[ERROR] --indel_lookup native answers from the alignments the native reader feeds the device front end: add --bam_reader native")
@@ -756,7 +757,7 @@ def load_model(args):
     try:
         m = Clair(device=args.device, max_batch=batch, n_slots=param.pipeline_slots())
         m.init()
-        m.restore_parameters(os.path.abspath(args.chkpnt_fn))
+        cv.restore_checkpoints(m, args)
     except Exception as exc:
         sys.exit("[ERROR] %s" % exc)
     return m
@@ -900,6 +901,9 @@ def build_parser():
              "--pysam_for_all_indel_bases): pysam (default; every answer is empty where pysam is not installed), or native: the alignments the device "
              "front end keeps on the GPU (needs --bam_reader native; docs/indel_lookup.md)")
     add('--device', type=int, default=0, help="HIP device ordinal, default: %(default)s")
+    add('--ensemble_chkpnt_fn', type=str, action='append', default=None, metavar="PREFIX",
+        help="one more checkpoint to call with, repeatable (at most 7): the probabilities of --chkpnt_fn and of these are averaged on the GPU "
+             "exactly as the reference's call_var --output_for_ensemble | ensemble | call_var --input_probabilities averages them")
     add('--arith', type=str, default="legacy", choices=("legacy", "numpy2"),
         help="QUAL/AF arithmetic: float64 as under the reference's NumPy 1.x (legacy) or float32 (numpy2)")
     return parser

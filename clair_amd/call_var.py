@@ -737,6 +737,10 @@ def call_variants(args, m, decoder, writer, batch_size=None, generator=None):
     device_decode = (use_async and hasattr(m, "submit_calls") and getattr(decoder, "native_applies", lambda: False)()
                      and os.environ.get("CLAIR_AMD_DEVICE_DECODE", "1") != "0")
     keep_probabilities = device_decode and decoder.lookup.sam is not None      # candidates that consult the BAM are decoded again from them
+    # --ensemble_chkpnt_fn: the model holds several checkpoints.  Every submit runs them all over the batch and averages their probabilities
+    # on the device as the reference's text chain does (clair/post_processing/ensemble.py:10-75; docs/ensemble.md); what comes back -- call
+    # records, probabilities or both -- has the shape it has with one model, and everything downstream goes on as it does today.
+    ensemble = use_async and getattr(m, "n_models", 1) > 1 and hasattr(m, "submit_ensemble")
     pool = None
     if generator is None:      # with the decode on the device nobody on the host reads the float32 tensor (unless a BAM is consulted)
         lean = device_decode and not keep_probabilities
@@ -830,8 +834,10 @@ def call_variants(args, m, decoder, writer, batch_size=None, generator=None):
             has_counts = len(current) > 2 and current[2] is not None
             if device_decode:
                 from clair_amd import _hostapi
-                m.submit_calls(slot, current[2] if has_counts else current[0], _hostapi.centre_bytes(current[1]), counts=has_counts,
-                               with_probabilities=keep_probabilities)
+                (m.submit_ensemble if ensemble else m.submit_calls)(slot, current[2] if has_counts else current[0], _hostapi.centre_bytes(current[1]),
+                                                                    counts=has_counts, with_probabilities=keep_probabilities)
+            elif ensemble:         # the host decodes (--debug, a float --qual, --pysam_for_all_indel_bases): from the averaged probabilities
+                m.submit_ensemble(slot, current[2] if has_counts else current[0], None, counts=has_counts)
             elif has_counts and hasattr(m, "submit_counts"):
                 m.submit_counts(slot, current[2])
             else:
@@ -888,6 +894,7 @@ def Run(args):
         is_haploid_precision_mode_enabled=args.haploid_precision,
         is_haploid_sensitive_mode_enabled=args.haploid_sensitive,
         is_output_for_ensemble=args.output_for_ensemble, quality_score_for_pass=args.qual)
+    check_ensemble_flags(args)
     lookup = AlignmentLookup(args.bam_fn, args.ref_fn)
     decoder = VariantDecoder(config, lookup, always_use_bam=args.pysam_for_all_indel_bases, arith=args.arith)
     writer = VcfWriter(args.call_fn, args.sampleName, args.ref_fn, args.output_for_ensemble)
@@ -904,7 +911,7 @@ def Run(args):
         try:
             m = Clair(device=args.device, max_batch=batch, n_slots=param.pipeline_slots())
             m.init()
-            m.restore_parameters(os.path.abspath(args.chkpnt_fn))
+            restore_checkpoints(m, args)
         except Exception as exc:   # C-ABI errors surface as messages + non-zero exit
             sys.exit("[ERROR] %s" % exc)
         try:
@@ -916,8 +923,30 @@ def Run(args):
         lookup.close()
 
 
+def check_ensemble_flags(args):
+    """--ensemble_chkpnt_fn replaces the text chain; with either end of that chain it would average twice, or not at all."""
+    if getattr(args, "ensemble_chkpnt_fn", None):
+        if args.output_for_ensemble:
+            sys.exit("[ERROR] --ensemble_chkpnt_fn averages the checkpoints in this process; --output_for_ensemble writes one model's "
+                     "probabilities for the `ensemble` submodule to average: use one of the two")
+        if getattr(args, "input_probabilities", False):
+            sys.exit("[ERROR] --ensemble_chkpnt_fn runs the checkpoints over tensors; --input_probabilities decodes probabilities that are "
+                     "already there (and already averaged): use one of the two")
+        if args.chkpnt_fn is None:
+            sys.exit("[ERROR] --ensemble_chkpnt_fn adds checkpoints to --chkpnt_fn, which is model 0: give --chkpnt_fn as well")
+
+
+def restore_checkpoints(m, args):
+    """--chkpnt_fn alone: restore_parameters, as ever.  With --ensemble_chkpnt_fn: model 0 = --chkpnt_fn, then those in command-line order."""
+    more = getattr(args, "ensemble_chkpnt_fn", None) or []
+    if more:
+        m.restore_ensemble([os.path.abspath(f) for f in [args.chkpnt_fn] + list(more)])
+    else:
+        m.restore_parameters(os.path.abspath(args.chkpnt_fn))
+
+
 def build_parser():
-    """Same flags and defaults as call_var.py:1370-1429, plus --batch_size / --device / --arith."""
+    """Same flags and defaults as call_var.py:1370-1429, plus --batch_size / --device / --arith / --ensemble_chkpnt_fn."""
     parser = ArgumentParser(description="Call variants using a trained model and tensors of candididate variants")
     parser.add_argument('--tensor_fn', type=str, default="PIPE", help="Tensor input, use PIPE for standard input")
     parser.add_argument('--chkpnt_fn', type=str, default=None, help="Input a checkpoint for testing")
@@ -954,6 +983,9 @@ def build_parser():
     parser.add_argument('--device', type=int, default=0, help="HIP device ordinal, default: %(default)s")
     parser.add_argument('--arith', type=str, default="legacy", choices=("legacy", "numpy2"),
                         help="QUAL/AF arithmetic: float64 as under the reference's NumPy 1.x (legacy) or float32 (numpy2)")
+    parser.add_argument('--ensemble_chkpnt_fn', type=str, action='append', default=None, metavar="PREFIX",
+                        help="one more checkpoint to call with, repeatable (at most 7): the probabilities of --chkpnt_fn and of these are averaged "
+                             "on the GPU exactly as --output_for_ensemble | ensemble | --input_probabilities averages them")
     return parser
 
 

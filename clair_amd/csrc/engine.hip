@@ -26,6 +26,7 @@
 #include "dense.hip.h"
 #include "decode.hip.h"
 #include "evaluate.hip.h"
+#include "ensemble.hip.h"
 #include "gemm_split.hip.h"
 #include "lstm32.hip.h"
 #include "lstm32_pair.hip.h"
@@ -88,6 +89,8 @@ struct Slot {
     clair_call_t *o_calls = nullptr;                // caller's array of the pending submit (NULL: no decode requested)
     // device scoring (clair_submit_eval, clair_eval): the candidates' true indices, allocated on first use
     DeviceBuffer d_labels; PinnedBuffer h_labels;   // unsigned char [max_pad][4], pinned twin
+    // ensemble calling (clair_submit_ensemble, clair_ensemble_average): the running sums of ensemble.hip.h, allocated on first use
+    DeviceBuffer d_acc;       // double [max_pad][90]
     // pending host outputs of a submit
     float *o_gt21 = nullptr, *o_gt = nullptr, *o_l1 = nullptr, *o_l2 = nullptr;
     int pending_n = 0;
@@ -97,13 +100,28 @@ struct Slot {
     std::string worker_error;
 };
 
+// One checkpoint on the device: the tensors as the caller handed them over and the images the kernels read (weight_images.h).  A handle
+// has one (image 0: clair_set_tensor, clair_finalize_weights) unless clair_ensemble_models asked for more.
+struct ModelWeights {
+    bool ready = false;
+    std::vector<float> host_tensors[CLAIR_T_COUNT];
+    DeviceBuffer bx1, bx2;    // float: gate-scaled biases [2][512] of the two layers
+    DeviceBuffer wh1s, wh2s, wx1s, w4s, w3s;   // unsigned short: fp16 split MFMA fragment images (lstm32.hip.h, dense.hip.h)
+    DeviceBuffer wx2s;        // unsigned short [8][2][1024][32] fp16 planes of the gate-scaled Wx2
+    DeviceBuffer b4;          // float
+    DeviceBuffer w5s, whs;    // unsigned short: fp16 split A fragments of the L5 branches and the heads (dense.hip.h: tail_kernel)
+    DeviceBuffer b5, bh;      // float
+    int w4_shift = 0;          // the W4 image is W4 * 2^w4_shift (finalize_model)
+    int w3_shift = 0;          // the (W3 | b3) image is the tensor * 2^w3_shift
+    int w5_shift[4] = {0, 0, 0, 0}, wh_shift[4] = {0, 0, 0, 0};   // per-branch power-of-two image shifts of those tensors
+};
+
 }  // namespace
 
 struct clair_engine {
     int device = 0;
     int max_batch = 0;
     int max_pad = 0;
-    bool weights_ready = false;
     unsigned timing_mask = 0;   // bit k: kernel id k is bracketed by HIP events (clair_timing_enable)
     int lstm2_pair = -1;       // LSTM2 as two tiles per workgroup (lstm32_pair.hip.h): -1 = from 64 tiles (2048 candidates) on, where it wins
                                // 1-2 % (profiles/r02_lstm2_pair_by_batch.txt; at 1024 the kernel's own latency, 128 vs 81 us, costs 5 %); CLAIR_AMD_LSTM2_PAIR=0/1 forces
@@ -120,8 +138,6 @@ struct clair_engine {
                                   // raises its error word itself) and its a2 is poisoned afterwards, so only a real re-run gives right outputs
     int fused_recoveries = 0;     // passes re-run on the two-launch path after a fused launch raised its error word
     int proj2_groups = 8;      // persistent workgroup groups per XCD of the projection GEMM: 8 XCDs x 4 gate tiles x groups workgroups (see clair_engine_create)
-    int w4_shift = 0;          // the W4 image is W4 * 2^w4_shift (clair_finalize_weights)
-    int w3_shift = 0;          // the (W3 | b3) image is the tensor * 2^w3_shift
     bool l34_stamps = false;   // CLAIR_AMD_L34_STAMPS=1: l3l4_kernel writes its per-wave phase clocks into the (dead) zx workspace for clair_debug_read(5)
     bool tap_l3 = false;   // CLAIR_AMD_TAP_L3=1: l3l4_kernel also writes l3 into the (dead) zx workspace for clair_debug_read(4)
     std::string error;
@@ -140,6 +156,7 @@ struct clair_engine {
         const void *input; bool counts; int64_t stride; int n;
         const uint8_t *centre; clair_call_t *calls; float *gt21, *gt, *l1, *l2;
         const uint8_t *labels = nullptr;   // clair_submit_eval: [n][4] true indices, scored behind the forward pass
+        int models = 0;                    // clair_submit_ensemble: this many forward passes, one per weight image, averaged (0: image 0 alone, as it is)
     };
     int staging_threads = 2;            // CLAIR_AMD_STAGING_THREADS (0: everything on the submitting thread): a 4.3 MB batch takes one core ~100 us
                                         // to copy, 75 % of the 135 us the GPU needs for it
@@ -148,15 +165,8 @@ struct clair_engine {
     std::condition_variable wcv, wdone;
     std::deque<std::pair<int, Request>> wqueue;
     bool wstop = false;
-    std::vector<float> host_tensors[CLAIR_T_COUNT];
-    // device weights
-    DeviceBuffer bx1, bx2;    // float: gate-scaled biases [2][512] of the two layers
-    DeviceBuffer wh1s, wh2s, wx1s, w4s, w3s;   // unsigned short: fp16 split MFMA fragment images (lstm32.hip.h, dense.hip.h)
-    DeviceBuffer wx2s;        // unsigned short [8][2][1024][32] fp16 planes of the gate-scaled Wx2
-    DeviceBuffer b4;          // float
-    DeviceBuffer w5s, whs;    // unsigned short: fp16 split A fragments of the L5 branches and the heads (dense.hip.h: tail_kernel)
-    DeviceBuffer b5, bh;      // float
-    int w5_shift[4] = {0, 0, 0, 0}, wh_shift[4] = {0, 0, 0, 0};   // per-branch power-of-two image shifts of those tensors
+    // weight images: models[0] is the handle's own checkpoint; clair_ensemble_models adds up to CLAIR_ENSEMBLE_MAX_MODELS - 1 more
+    std::vector<std::unique_ptr<ModelWeights>> models;
     DeviceBuffer eval_counts; // unsigned long long [CLAIR_EVAL_COUNTS] confusion counters of evaluate.hip.h, allocated by the first clair_eval_* call
     double ms_sum[CLAIR_K_COUNT] = {0};
     int64_t launches[CLAIR_K_COUNT] = {0};
@@ -242,22 +252,22 @@ bool use_lstm2_pair(const clair_engine *e, int ntiles) { return e->lstm2_pair < 
 
 // Enqueue the forward pass for n candidates whose input is at x_dev ([n_pad][1056], rows >= n
 // zero or any finite value) writing packed outputs to out_dev ([n][90]).
-int enqueue_forward(clair_engine *e, Lane &l, const float *x_dev, float *out_dev, int n, int slot_index) {
+int enqueue_forward(clair_engine *e, Lane &l, const ModelWeights &w, const float *x_dev, float *out_dev, int n, int slot_index) {
     const int n_pad = (n + 31) & ~31;
     const int ntiles = n_pad / L32_TILE;
     const int m_rows = T_POS * n_pad;
     l.last_n_pad = n_pad;
     {   // LSTM1 with its input projection fused in (no separate GEMM, no zx round trip), fp16 split products
         KernelTimer kt(e, l, CLAIR_K_LSTM1);
-        Lstm32Args a{x_dev, e->wx1s.as<unsigned short>(), e->bx1.as<float>(), nullptr, e->wh1s.as<unsigned short>(), l.a1.as<unsigned short>(), nullptr, n_pad, ntiles, -1};
+        Lstm32Args a{x_dev, w.wx1s.as<unsigned short>(), w.bx1.as<float>(), nullptr, w.wh1s.as<unsigned short>(), l.a1.as<unsigned short>(), nullptr, n_pad, ntiles, -1};
         hipLaunchKernelGGL((lstm32_kernel<true>), dim3(ntiles * 2), dim3(256), 0, l.stream, a);
     }
     if (use_lstm2_fused(e, ntiles)) {   // layer 2 in one launch: projection and recurrence side by side, zx through L2 (lstm2_fused.hip.h)
         KernelTimer kt(e, l, CLAIR_K_LSTM2);
         const int groups = e->fused_groups;
         if (++l.fuse_ticket == 0) l.fuse_ticket = 1;   // (a wrapped ticket could meet a 4-billion-passes-old word; the words are zero at most once)
-        Lstm2FusedArgs a{GemmSplitArgs{l.a1.as<unsigned short>(), e->wx2s.as<unsigned short>(), e->bx2.as<float>(), l.zx.as<float>(), n_pad, ntiles, m_rows, groups},
-                         Lstm32Args{nullptr, nullptr, nullptr, l.zx.as<float>(), e->wh2s.as<unsigned short>(), nullptr, l.a2.as<float>(), n_pad, ntiles, -1},
+        Lstm2FusedArgs a{GemmSplitArgs{l.a1.as<unsigned short>(), w.wx2s.as<unsigned short>(), w.bx2.as<float>(), l.zx.as<float>(), n_pad, ntiles, m_rows, groups},
+                         Lstm32Args{nullptr, nullptr, nullptr, l.zx.as<float>(), w.wh2s.as<unsigned short>(), nullptr, l.a2.as<float>(), n_pad, ntiles, -1},
                          FuseArgs{l.fuse_flags.as<unsigned>(), l.fuse_ticket, l.fuse_flags.as<unsigned>() + fuse_words(e->max_pad) + 1, l.fuse_flags.as<unsigned>() + fuse_words(e->max_pad)}, 32 * groups};
         const int consumers = 32 * ((ntiles / 2 + 7) / 8);
         const bool fault = ++e->fused_launches == e->fused_fault_at;
@@ -270,32 +280,32 @@ int enqueue_forward(clair_engine *e, Lane &l, const float *x_dev, float *out_dev
             KernelTimer kt(e, l, CLAIR_K_PROJ2);
             const int x_tiles = (m_rows + GS_ROWS - 1) / GS_ROWS;
             const int groups = std::min(e->proj2_groups, (x_tiles + 7) / 8);
-            GemmSplitArgs a{l.a1.as<unsigned short>(), e->wx2s.as<unsigned short>(), e->bx2.as<float>(), l.zx.as<float>(), n_pad, ntiles, m_rows, groups};
+            GemmSplitArgs a{l.a1.as<unsigned short>(), w.wx2s.as<unsigned short>(), w.bx2.as<float>(), l.zx.as<float>(), n_pad, ntiles, m_rows, groups};
             hipLaunchKernelGGL(gemm_split_kernel, dim3(32 * groups), dim3(256), 0, l.stream, a);
         }
         {
             KernelTimer kt(e, l, CLAIR_K_LSTM2);
             if (use_lstm2_pair(e, ntiles)) {
-                Lstm32PairArgs a{l.zx.as<float>(), e->wh2s.as<unsigned short>(), l.a2.as<float>(), n_pad, ntiles};
+                Lstm32PairArgs a{l.zx.as<float>(), w.wh2s.as<unsigned short>(), l.a2.as<float>(), n_pad, ntiles};
                 hipLaunchKernelGGL(lstm32_pair_kernel, dim3(((ntiles + 1) / 2) * 2), dim3(256), 0, l.stream, a);
             } else {
-                Lstm32Args a{nullptr, nullptr, nullptr, l.zx.as<float>(), e->wh2s.as<unsigned short>(), nullptr, l.a2.as<float>(), n_pad, ntiles, -1};
+                Lstm32Args a{nullptr, nullptr, nullptr, l.zx.as<float>(), w.wh2s.as<unsigned short>(), nullptr, l.a2.as<float>(), n_pad, ntiles, -1};
                 hipLaunchKernelGGL((lstm32_kernel<false>), dim3(ntiles * 2), dim3(256), 0, l.stream, a);
             }
         }
     }
     {   // L3 (slice dense) + L4 (split-K 8: a workgroup walks the four channel groups of its split), fused
         KernelTimer kt(e, l, CLAIR_K_L4);
-        L3L4Args a{l.a2.as<float>(), e->w3s.as<unsigned short>(), e->w4s.as<unsigned short>(), l.l4part.as<float>(), n_pad, std::ldexp(1.0f, -e->w3_shift), e->tap_l3 ? l.zx.as<float>() : nullptr,
+        L3L4Args a{l.a2.as<float>(), w.w3s.as<unsigned short>(), w.w4s.as<unsigned short>(), l.l4part.as<float>(), n_pad, std::ldexp(1.0f, -w.w3_shift), e->tap_l3 ? l.zx.as<float>() : nullptr,
                    e->l34_stamps ? l.zx.as<unsigned long long>() : nullptr};   // zx is dead by now
         hipLaunchKernelGGL(l3l4_kernel, dim3(l34_grid((n_pad + L34_CAND - 1) / L34_CAND)), dim3(L34_THREADS), 0, l.stream, a);
     }
     {
         KernelTimer kt(e, l, CLAIR_K_TAIL);
-        TailArgs a{l.l4part.as<float>(), e->b4.as<float>(), e->w5s.as<unsigned short>(), e->b5.as<float>(), e->whs.as<unsigned short>(), e->bh.as<float>(), out_dev, n_pad, n, std::ldexp(1.0f, -e->w4_shift) / L34_ACT_SCALE, {}, {}};
+        TailArgs a{l.l4part.as<float>(), w.b4.as<float>(), w.w5s.as<unsigned short>(), w.b5.as<float>(), w.whs.as<unsigned short>(), w.bh.as<float>(), out_dev, n_pad, n, std::ldexp(1.0f, -w.w4_shift) / L34_ACT_SCALE, {}, {}};
         for (int k = 0; k < 4; ++k) {
-            a.l5_scale[k] = std::ldexp(1.0f, -e->w5_shift[k]) / TAIL_ACT_SCALE;
-            a.head_scale[k] = std::ldexp(1.0f, -e->wh_shift[k]) / TAIL_ACT_SCALE;
+            a.l5_scale[k] = std::ldexp(1.0f, -w.w5_shift[k]) / TAIL_ACT_SCALE;
+            a.head_scale[k] = std::ldexp(1.0f, -w.wh_shift[k]) / TAIL_ACT_SCALE;
         }
         hipLaunchKernelGGL(tail_kernel, dim3(n_pad / TAIL_TILE), dim3(TAIL_THREADS), 0, l.stream, a);
     }
@@ -373,6 +383,16 @@ int enqueue_eval(clair_engine *e, Lane &l, Slot &s, int n) {
     return 0;
 }
 
+// The averaging step of ensemble calling (ensemble.hip.h) behind one of the K forward passes of the slot's batch: d_out -> the slot's sums, or
+// (last) sums -> d_out.  No id in enum clair_kernel_id, like the scoring.
+int ensure_slot_ensemble(clair_engine *e, Slot &s) { HIP_TRY(e, s.d_acc.ensure((size_t)e->max_pad * OUT_FLOATS * sizeof(double))); return 0; }
+int enqueue_ensemble(clair_engine *e, Lane &l, Slot &s, int n, int models, bool first, bool last) {
+    EnsembleArgs a{s.d_out.as<float>(), s.d_acc.as<double>(), n * OUT_FLOATS / 2, models, first ? 1 : 0, last ? 1 : 0};
+    hipLaunchKernelGGL(ensemble_kernel, dim3((a.n_pairs + 255) / 256), dim3(256), 0, l.stream, a);
+    HIP_TRY(e, hipGetLastError());
+    return 0;
+}
+
 // the counter block exists (zeroed) from the first call that needs it
 int ensure_eval_counts(clair_engine *e) {
     if (!e->eval_counts.p) {
@@ -410,7 +430,7 @@ int recover_fused(clair_engine *e, Lane &l, int current) {
     std::vector<Lane::FusedRun> runs;
     runs.swap(l.fused_runs);
     for (const auto &r : runs) {
-        if (enqueue_forward(e, l, r.x, r.out, r.n, r.slot)) return 1;
+        if (enqueue_forward(e, l, *e->models[0], r.x, r.out, r.n, r.slot)) return 1;   // (a handle with the fused launch runs no ensembles)
         if (r.slot >= 0 && r.slot != current) e->slots[r.slot].refetch = true;
         ++e->fused_recoveries;
     }
@@ -545,6 +565,7 @@ int enqueue_request(clair_engine *e, int slot_index, const clair_engine::Request
         memcpy(s.h_centre.p, q.centre, (size_t)n * 2);
         HIP_TRY(e, hipMemcpyAsync(s.d_centre.p, s.h_centre.p, (size_t)n * 2, hipMemcpyHostToDevice, s.cin));
     }
+    if (q.models && ensure_slot_ensemble(e, s)) return 1;
     if (q.labels) {
         if (ensure_slot_labels(e, s)) return 1;
         memcpy(s.h_labels.p, q.labels, (size_t)n * 4);
@@ -569,7 +590,12 @@ int enqueue_request(clair_engine *e, int slot_index, const clair_engine::Request
         if (!same_in) g.lock();
         if (!same_in) HIP_TRY(e, hipStreamWaitEvent(l.stream, s.ev_in, 0));
         if (convert_on_lane) launch_convert(l.stream);
-        if (enqueue_forward(e, l, s.d_x.as<float>(), s.d_out.as<float>(), n, slot_index)) return 1;
+        if (q.models) {   // K passes over the same input back to back, each folded into the slot's sums; the last leaves the averaged rows in d_out
+            for (int k = 0; k < q.models; ++k) {
+                if (enqueue_forward(e, l, *e->models[k], s.d_x.as<float>(), s.d_out.as<float>(), n, slot_index)) return 1;
+                if (enqueue_ensemble(e, l, s, n, q.models, k == 0, k == q.models - 1)) return 1;
+            }
+        } else if (enqueue_forward(e, l, *e->models[0], s.d_x.as<float>(), s.d_out.as<float>(), n, slot_index)) return 1;
         if (q.calls && enqueue_decode(e, l, s, n)) return 1;
         if (q.labels && enqueue_eval(e, l, s, n)) return 1;
         if (same_out) return enqueue_results(e, l, s, n, q.calls != nullptr, want_probs);      // in line with the kernels, under the lane's lock
@@ -639,7 +665,7 @@ int quiesce(clair_engine *e) {
 int check_slot(clair_engine *e, int slot, bool need_weights = true) {
     if (!e) return fail(nullptr, "engine is NULL");
     if (slot < 0 || slot >= (int)e->slots.size()) return fail(e, "slot %d out of range [0,%d)", slot, (int)e->slots.size());
-    if (need_weights && !e->weights_ready) return fail(e, "weights not loaded: call clair_set_tensor for all tensors, then clair_finalize_weights");
+    if (need_weights && !e->models[0]->ready) return fail(e, "weights not loaded: call clair_set_tensor for all tensors, then clair_finalize_weights");
     return 0;
 }
 
@@ -660,6 +686,38 @@ int check_request(clair_engine *e, int slot, const clair_engine::Request &q, boo
 int check_stride(clair_engine *e, const clair_engine::Request &q) {
     if (q.stride != 0 && q.stride < (int64_t)(CLAIR_INPUT_FLOATS * (q.counts ? sizeof(short) : sizeof(float))))
         return fail(e, "input stride of %lld bytes is shorter than one candidate", (long long)q.stride);
+    return 0;
+}
+
+// clair_set_tensor / clair_finalize_weights for weight image `model` (0: the handle's own checkpoint)
+int set_model_tensor(clair_engine *e, int model, int id, const float *host, int64_t count) {
+    if (!e) return fail(nullptr, "engine is NULL");
+    if (model < 0 || model >= (int)e->models.size()) return fail(e, "model %d out of range [0,%d): call clair_ensemble_models first", model, (int)e->models.size());
+    if (id < 0 || id >= CLAIR_T_COUNT) return fail(e, "tensor id %d out of range", id);
+    if (!host) return fail(e, "tensor %d: host pointer is NULL", id);
+    if (count != TENSOR_COUNT[id]) return fail(e, "tensor %d: got %lld floats, expected %lld", id, (long long)count, (long long)TENSOR_COUNT[id]);
+    ModelWeights &w = *e->models[model];
+    w.host_tensors[id].assign(host, host + count);
+    w.ready = false;
+    return 0;
+}
+
+int finalize_model(clair_engine *e, int model) {
+    if (!e) return fail(nullptr, "engine is NULL");
+    if (model < 0 || model >= (int)e->models.size()) return fail(e, "model %d out of range [0,%d): call clair_ensemble_models first", model, (int)e->models.size());
+    ModelWeights &w = *e->models[model];
+    for (int i = 0; i < CLAIR_T_COUNT; ++i)
+        if ((int64_t)w.host_tensors[i].size() != TENSOR_COUNT[i]) return fail(e, "tensor %d has not been set", i);
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (quiesce(e)) return 1;
+    const WeightImages m = build_weight_images(LAYER_SIZES, w.host_tensors);
+    if (upload(e, w.bx1, m.bx1) || upload(e, w.bx2, m.bx2) || upload(e, w.wx2s, m.wx2s) || upload(e, w.wh1s, m.wh1s) || upload(e, w.wh2s, m.wh2s) ||
+        upload(e, w.wx1s, m.wx1s) || upload(e, w.w3s, m.w3s) || upload(e, w.w4s, m.w4s) || upload(e, w.b4, m.b4) || upload(e, w.w5s, m.w5s) ||
+        upload(e, w.whs, m.whs) || upload(e, w.b5, m.b5) || upload(e, w.bh, m.bh)) return 1;
+    w.w3_shift = m.w3_shift;
+    w.w4_shift = m.w4_shift;
+    for (int k = 0; k < 4; ++k) { w.w5_shift[k] = m.w5_shift[k]; w.wh_shift[k] = m.wh_shift[k]; }
+    w.ready = true;
     return 0;
 }
 
@@ -741,6 +799,7 @@ int clair_engine_create(int device, int max_batch, int n_slots, clair_engine_t *
     { const char *t = getenv("CLAIR_AMD_COPY_STREAMS"); if (t) e->copy_mode = !strcmp(t, "slot") ? 0 : !strcmp(t, "two") ? 1 : !strcmp(t, "lane") ? 2 : 3; }
     { const char *t = getenv("CLAIR_AMD_D2H"); if (t) e->d2h_kernel = !strcmp(t, "kernel"); }
     { const char *t = getenv("CLAIR_AMD_CONVERT"); if (t) e->convert_on_lane = strcmp(t, "copy") != 0; }
+    e->models.emplace_back(new ModelWeights());
     for (int i = 0; i < n_lanes; ++i) e->lanes.emplace_back(new Lane());
     e->slots = std::vector<Slot>(n_slots);   // (a Slot owns its buffers and does not move)
     const size_t mp = e->max_pad;
@@ -826,32 +885,9 @@ void clair_engine_destroy(clair_engine_t *e) {
     for (auto st : streams) (void)hipStreamDestroy(st);
 }
 
-int clair_set_tensor(clair_engine_t *e, int id, const float *host, int64_t count) {
-    if (!e) return fail(nullptr, "engine is NULL");
-    if (id < 0 || id >= CLAIR_T_COUNT) return fail(e, "tensor id %d out of range", id);
-    if (!host) return fail(e, "tensor %d: host pointer is NULL", id);
-    if (count != TENSOR_COUNT[id]) return fail(e, "tensor %d: got %lld floats, expected %lld", id, (long long)count, (long long)TENSOR_COUNT[id]);
-    e->host_tensors[id].assign(host, host + count);
-    e->weights_ready = false;
-    return 0;
-}
+int clair_set_tensor(clair_engine_t *e, int id, const float *host, int64_t count) { return set_model_tensor(e, 0, id, host, count); }
 
-int clair_finalize_weights(clair_engine_t *e) {
-    if (!e) return fail(nullptr, "engine is NULL");
-    for (int i = 0; i < CLAIR_T_COUNT; ++i)
-        if ((int64_t)e->host_tensors[i].size() != TENSOR_COUNT[i]) return fail(e, "tensor %d has not been set", i);
-    HIP_TRY(e, hipSetDevice(e->device));
-    if (quiesce(e)) return 1;
-    const WeightImages m = build_weight_images(LAYER_SIZES, e->host_tensors);
-    if (upload(e, e->bx1, m.bx1) || upload(e, e->bx2, m.bx2) || upload(e, e->wx2s, m.wx2s) || upload(e, e->wh1s, m.wh1s) || upload(e, e->wh2s, m.wh2s) ||
-        upload(e, e->wx1s, m.wx1s) || upload(e, e->w3s, m.w3s) || upload(e, e->w4s, m.w4s) || upload(e, e->b4, m.b4) || upload(e, e->w5s, m.w5s) ||
-        upload(e, e->whs, m.whs) || upload(e, e->b5, m.b5) || upload(e, e->bh, m.bh)) return 1;
-    e->w3_shift = m.w3_shift;
-    e->w4_shift = m.w4_shift;
-    for (int k = 0; k < 4; ++k) { e->w5_shift[k] = m.w5_shift[k]; e->wh_shift[k] = m.wh_shift[k]; }
-    e->weights_ready = true;
-    return 0;
-}
+int clair_finalize_weights(clair_engine_t *e) { return finalize_model(e, 0); }
 
 int clair_submit(clair_engine_t *e, int slot, const float *x, int n, float *gt21, float *genotype, float *l1, float *l2) {
     const clair_engine::Request q{x, false, 0, n, nullptr, nullptr, gt21, genotype, l1, l2};
@@ -1014,6 +1050,59 @@ int clair_eval_read(clair_engine_t *e, int64_t *counts) {
     return 0;
 }
 
+// -- ensemble calling: K checkpoints over one batch, averaged on the device (ensemble.hip.h; clair/post_processing/ensemble.py:10-75) ----
+int clair_ensemble_models(clair_engine_t *e, int models) {
+    if (!e) return fail(nullptr, "engine is NULL");
+    if (models < 1 || models > CLAIR_ENSEMBLE_MAX_MODELS) return fail(e, "clair_ensemble_models: %d models, 1 .. %d", models, CLAIR_ENSEMBLE_MAX_MODELS);
+    if (fused_possible(e)) return fail(e, "ensemble calling runs on the two-launch layer-2 path only: unset CLAIR_AMD_LSTM2_FUSED");
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (quiesce(e)) return 1;           // nothing in flight reads an image that goes away
+    while ((int)e->models.size() > models) e->models.pop_back();
+    while ((int)e->models.size() < models) e->models.emplace_back(new ModelWeights());
+    return 0;
+}
+
+int clair_ensemble_set_tensor(clair_engine_t *e, int model, int tensor_id, const float *host, int64_t count) { return set_model_tensor(e, model, tensor_id, host, count); }
+
+int clair_ensemble_finalize_weights(clair_engine_t *e, int model) { return finalize_model(e, model); }
+
+int clair_submit_ensemble(clair_engine_t *e, int slot, const void *input, int input_is_counts, int64_t input_stride_bytes, int n, const uint8_t *centre,
+                          clair_call_t *calls, float *gt21, float *genotype, float *l1, float *l2) {
+    clair_engine::Request q{input, input_is_counts != 0, input_stride_bytes, n, centre, calls, gt21, genotype, l1, l2};
+    if (check_request(e, slot, q, input != nullptr, "NULL input pointer")) return 1;
+    if (!(gt21 || genotype || l1 || l2) && !calls) return fail(e, "nothing asked for: neither call records nor probabilities");
+    if (calls && !centre) return fail(e, "call records need the candidates' centre bytes");
+    if (check_stride(e, q)) return 1;
+    // a fused layer-2 launch (opt-in) may be re-run after the fact (recover_fused), and a re-run knows one weight image
+    if (fused_possible(e)) return fail(e, "clair_submit_ensemble runs on the two-launch layer-2 path only: unset CLAIR_AMD_LSTM2_FUSED");
+    q.models = (int)e->models.size();
+    for (int k = 0; k < q.models; ++k)
+        if (!e->models[k]->ready) return fail(e, "weights of model %d not loaded: clair_ensemble_set_tensor for all tensors, then clair_ensemble_finalize_weights", k);
+    return submit_request(e, slot, q);
+}
+
+// The averaging alone, on probabilities the caller holds: synchronous, needs no weights (the twin of clair_decode and clair_eval).
+int clair_ensemble_average(clair_engine_t *e, int slot, const float *probs, int models, int n, float *out) {
+    if (check_slot(e, slot, false) || check_n(e, n)) return 1;
+    if (models < 1 || models > CLAIR_ENSEMBLE_MAX_MODELS) return fail(e, "clair_ensemble_average: %d models, 1 .. %d", models, CLAIR_ENSEMBLE_MAX_MODELS);
+    if (!probs || !out) return fail(e, "NULL input/output pointer");
+    if (fused_possible(e)) return fail(e, "clair_ensemble_average is not available on a handle with the fused layer-2 launch: unset CLAIR_AMD_LSTM2_FUSED");
+    HIP_TRY(e, hipSetDevice(e->device));
+    Slot &s = e->slots[slot];
+    if (s.pending_n) return fail(e, "slot %d still has a pending submit; call clair_wait first", slot);
+    if (ensure_slot_ensemble(e, s)) return 1;
+    const size_t row_bytes = (size_t)n * OUT_FLOATS * sizeof(float);
+    Lane &l = *e->lanes[s.lane];
+    std::lock_guard<std::mutex> g(l.order);
+    for (int k = 0; k < models; ++k) {
+        HIP_TRY(e, hipMemcpyAsync(s.d_out.p, (const char *)probs + (size_t)k * row_bytes, row_bytes, hipMemcpyHostToDevice, l.stream));
+        if (enqueue_ensemble(e, l, s, n, models, k == 0, k == models - 1)) return 1;
+    }
+    HIP_TRY(e, hipMemcpyAsync(out, s.d_out.p, row_bytes, hipMemcpyDeviceToHost, l.stream));
+    HIP_TRY(e, hipStreamSynchronize(l.stream));
+    return 0;
+}
+
 int clair_predict(clair_engine_t *e, const float *x, int n, float *gt21, float *genotype, float *l1, float *l2) {
     if (clair_submit(e, 0, x, n, gt21, genotype, l1, l2)) return 1;
     return clair_wait(e, 0);
@@ -1060,7 +1149,7 @@ int clair_run_resident(clair_engine_t *e, int slot, const void *x_dev, void *out
     HIP_TRY(e, hipSetDevice(e->device));
     Lane &l = *e->lanes[e->slots[slot].lane];
     std::lock_guard<std::mutex> g(l.order);
-    return enqueue_forward(e, l, (const float *)x_dev + (size_t)first * CLAIR_INPUT_FLOATS, (float *)out_dev + (size_t)first * OUT_FLOATS, n, -1);
+    return enqueue_forward(e, l, *e->models[0], (const float *)x_dev + (size_t)first * CLAIR_INPUT_FLOATS, (float *)out_dev + (size_t)first * OUT_FLOATS, n, -1);
 }
 
 int clair_sync(clair_engine_t *e) {
@@ -1192,7 +1281,7 @@ int clair_debug_read(clair_engine_t *e, int slot, int which, float *host, int64_
             const int64_t nblk = (np + L34_CAND - 1) / L34_CAND;
             std::vector<float> raw((size_t)L4_SPLITS * nblk * L34_CAND * L4_UNITS);
             HIP_TRY(e, hipMemcpy(raw.data(), l.l4part.p, raw.size() * sizeof(float), hipMemcpyDeviceToHost));
-            const float inv = std::ldexp(1.0f, -e->w4_shift) / L34_ACT_SCALE;
+            const float inv = std::ldexp(1.0f, -e->models[0]->w4_shift) / L34_ACT_SCALE;
             for (int64_t i = 0; i < count; ++i) {
                 const int64_t cg = i / (np * L4_UNITS), n = (i / L4_UNITS) % np, col = i % L4_UNITS;
                 const int64_t blk = n / 64, row = n % 64, mb = row / 32, a = (row % 32) / 8, hq = (row % 8) / 4, r = row % 4;

@@ -54,6 +54,20 @@ class Clair(object):
         self._engine.load_weights(w)
         self._weights_loaded = True
 
+    def restore_ensemble(self, file_names):
+        """restore_parameters for an ensemble: the reference makes one Clair and one call_var run per checkpoint and averages their
+        --output_for_ensemble rows (clair/post_processing/ensemble.py:10-75); here one engine holds them all and submit_ensemble runs
+        them over each batch.  The first prefix is the model predict / submit go on using alone."""
+        self.set_ensemble([weights.load_weights(f) for f in file_names])
+
+    def set_ensemble(self, list_of_weights):
+        self._engine.load_ensemble(list_of_weights)
+        self._weights_loaded = True
+
+    @property
+    def n_models(self):
+        return self._engine.n_models
+
     def predict(self, batchX):
         """clair/model.py:946-966: list of four float32 arrays; kept in ``self.prediction``."""
         x = np.asarray(batchX)
@@ -93,6 +107,11 @@ class Clair(object):
         """Forward pass + decode on the device (include/clair_amd.h: clair_submit_ex): wait(slot) returns the call records of
         include/clair_call.h -- or (records, probabilities) -- instead of the probabilities."""
         self._engine.submit_calls(slot, batch, centre, counts=counts, with_probabilities=with_probabilities)
+
+    def submit_ensemble(self, slot, batch, centre=None, counts=False, with_probabilities=False):
+        """submit_calls over every checkpoint of restore_ensemble, averaged on the device (include/clair_amd.h: clair_submit_ensemble);
+        centre=None: no decode, wait(slot) returns the averaged probabilities."""
+        self._engine.submit_ensemble(slot, batch, centre, counts=counts, with_probabilities=with_probabilities)
 
     def pinned_buffer(self, nbytes):
         """Page-locked host memory of the engine (include/clair_amd.h: clair_pinned_alloc) as a uint8 array."""

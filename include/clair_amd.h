@@ -207,6 +207,37 @@ int clair_eval(clair_engine_t *e, int slot, const float *gt21, const float *geno
 /* Wait for all slots' device work, then copy the block to counts[CLAIR_EVAL_COUNTS] (what evaluate.py:136-163 prints from). */
 int clair_eval_read(clair_engine_t *e, int64_t *counts);
 
+/* -- ensemble calling: K checkpoints over the same candidates, averaged on the device ----------------------------------------------
+ * The reference's accuracy lever after training (docs/POST_PROCESSING.md): call_var --output_for_ensemble once per model
+ * (clair/call_var.py:950-1000), clair/post_processing/ensemble.py to average the rows of a site (:10-75), call_var
+ * --input_probabilities to decode the averages (clair/call_var.py:1276-1309) -- K + 2 processes and 3 KB of text per candidate and
+ * model.  Here a handle holds up to CLAIR_ENSEMBLE_MAX_MODELS weight images; one submit brings the batch in once, runs the K forward
+ * passes back to back on the slot's lane, folds each into a per-slot accumulator (clair_amd/csrc/ensemble.hip.h) and decodes the
+ * averaged rows.  The average is the text chain's, value for value: every probability rounded to six decimals as '{:0.6f}' prints it,
+ * re-read as double, summed in model order, divided by K, rounded to six decimals again as '{:.6f}' prints a double (NOT
+ * rint(mean * 1e6): docs/ensemble.md), read as float32.  K = 1 therefore is not the identity: it rounds to six decimals, as the chain
+ * with one model does.  NaN is out of scope.  Added without an ABI bump and without a kernel id, as clair_eval_* was.
+ * Not available on a handle that opted into the fused layer-2 launch (CLAIR_AMD_LSTM2_FUSED=1): a pass re-run after a misplaced
+ * launch knows one weight image.  A handle that never calls clair_ensemble_models behaves exactly as before. */
+#define CLAIR_ENSEMBLE_MAX_MODELS 8
+/* Clair() once per model (clair/model.py:58-192): the handle holds `models` weight images from here on, 1 .. 8.  Image 0 is the one
+ * clair_set_tensor / clair_finalize_weights load; images beyond `models` are released.  Waits for the handle's streams. */
+int clair_ensemble_models(clair_engine_t *e, int models);
+/* Clair.restore_parameters() of model `model` (clair/model.py:1016-1020): as clair_set_tensor / clair_finalize_weights, per image. */
+int clair_ensemble_set_tensor(clair_engine_t *e, int model, int tensor_id, const float *host, int64_t count);
+int clair_ensemble_finalize_weights(clair_engine_t *e, int model);
+/* m.predict of every model + ensemble.py:33-43, :67 + the decode (clair/call_var.py:1331-1352 per model, :1276-1309), pipelined:
+ * arguments and input forms exactly those of clair_submit_ex (host or device address, float32 tensor or raw int16 counts, strided;
+ * calls and / or the four probability arrays), every image finalized.  The probabilities handed back are the AVERAGED rows, the
+ * call records their decode.  Models are summed in image order.  Pair with clair_wait(slot). */
+int clair_submit_ensemble(clair_engine_t *e, int slot, const void *input, int input_is_counts, int64_t input_stride_bytes, int n,
+                          const uint8_t *centre, clair_call_t *calls, float *gt21, float *genotype, float *indel_len1, float *indel_len2);
+/* The averaging alone (ensemble.py:33-43, :67 and the two text conversions around it), on probabilities the caller holds: probs
+ * [models][n][90] packed rows (gt21 | genotype | len1 | len2) -> out [n][90].  Synchronous, needs no weights -- the twin of
+ * clair_decode / clair_eval, and how crafted rows (exact half-way means) reach the kernel.  clair_host_ensemble_average
+ * (include/clair_host.h) is its CPU twin, bit for bit. */
+int clair_ensemble_average(clair_engine_t *e, int slot, const float *probs, int models, int n, float *out);
+
 /* -- device-resident candidate sets (benchmark / multi-GPU shard driver) ------------------------
  * The candidate set lives in HBM: x_dev [N,33,8,4]; outputs out_dev [N,90] rows laid out
  * gt21(21) | genotype(3) | len1(33) | len2(33).  clair_run_resident enqueues the forward pass

@@ -242,6 +242,19 @@ int clair_host_bam_set_inflater(clair_bam_t *b, clair_host_inflate_fn fn, void *
 int clair_host_inflate_block(const uint8_t *in, int64_t n_in, uint8_t *out, int64_t cap, int64_t *n_out, uint32_t *crc32, int *status);
 int clair_host_inflate_bgzf(const uint8_t *block, int64_t csize, uint8_t *out, int64_t *n_out, int *status);
 
+/* -- the host twin of the device ensemble averaging (hostsrc/host_ensemble.cpp): csrc/ensemble_core.h, the code the GPU runs after each of
+ *    the K forward passes of clair_submit_ensemble (include/clair_amd.h), compiled for the host.  It restates the reference's text chain
+ *    value for value: '{:0.6f}' of every float32 probability (clair/call_var.py:950-1000), float() of those digits, the sum in input order
+ *    and the division in double, '{:.6f}' of the mean (clair/post_processing/ensemble.py:33-43, :67), float32 of those digits
+ *    (clair/call_var.py:1291).  docs/ensemble.md has the rule and why rint(mean * 1e6) is not it.
+ *    _average: probs [models][count] float32, model order = summation order, 1 <= models <= 8 -> out [count].  models = 1 is not the
+ *    identity: it rounds to six decimals, as the chain with one model does.
+ *    _quantise: the integer of millionths '{:0.6f}' prints for each float32 (ties to even).  _value: float32 of "m / 10^6" for 0 <= m <= 10^6.
+ *    NaN is out of scope. */
+int clair_host_ensemble_average(const float *probs, int models, int64_t count, float *out);
+int clair_host_ensemble_quantise(const float *p, int64_t count, int32_t *millionths);
+int clair_host_ensemble_value(const int32_t *millionths, int64_t count, float *out);
+
 #ifdef __cplusplus
 }
 #endif
