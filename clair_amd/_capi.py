@@ -31,8 +31,10 @@ SYMBOLS = (
     "clair_eval_reset", "clair_submit_eval", "clair_eval", "clair_eval_read",
     "clair_ensemble_models", "clair_ensemble_set_tensor", "clair_ensemble_finalize_weights", "clair_submit_ensemble", "clair_ensemble_average",
     "clair_inflate_create", "clair_inflate_destroy", "clair_inflate_last_error", "clair_inflate_blocks", "clair_inflate_blocks_cb",
+    "clair_overlap_keep", "clair_overlap_last_error",
 )
 ENSEMBLE_MAX_MODELS = 8                                      # CLAIR_ENSEMBLE_MAX_MODELS
+OVERLAP_SCAN_BLOCK = 2048                                    # clair_ov::BLOCK (csrc/overlap.hip): rows per workgroup of the head scan
 EVAL_COUNTS = 3 + 21 * 21 + 3 * 3 + 33 * 33 + 33 * 33      # CLAIR_EVAL_COUNTS: all, top1, top2, gt21, genotype, len1, len2
 KERNEL_NAMES = ("proj1", "lstm1", "proj2", "lstm2", "l3", "l4", "tail", "decode")
 
@@ -163,13 +165,17 @@ def load(path=None):
         lib.clair_inflate_last_error.restype = ctypes.c_char_p
         lib.clair_inflate_blocks.argtypes = [c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
         lib.clair_inflate_blocks_cb.argtypes = lib.clair_inflate_blocks.argtypes
+    if not older_ok or hasattr(lib, "clair_overlap_keep"):
+        lib.clair_overlap_keep.argtypes = [c_int, c_vp, c_i64, c_vp]
+        lib.clair_overlap_last_error.argtypes = []
+        lib.clair_overlap_last_error.restype = ctypes.c_char_p
     for name in SYMBOLS:
         if older_ok and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
         if name not in ("clair_last_error", "clair_engine_destroy", "clair_comm_last_error", "clair_comm_destroy",
                         "clair_frontend_last_error", "clair_frontend_destroy", "clair_frontend_counts_device",
-                        "clair_inflate_last_error", "clair_inflate_destroy"):
+                        "clair_inflate_last_error", "clair_inflate_destroy", "clair_overlap_last_error"):
             fn.restype = c_int
     if path is None:
         _lib = lib
@@ -757,3 +763,15 @@ class Inflater(object):
         if rc != 0:
             raise EngineError("clair_inflate_blocks failed: %s" % self._lib.clair_inflate_last_error(self._h).decode())
         return out, status
+
+
+def overlap_keep(spans, device=0):
+    """clair_overlap_keep: spans (clair_amd._hostapi.SPAN_DTYPE [n], input order) -> uint8 [n], 1 for the rows the overlap filter prints, worked
+    out on the device (csrc/overlap.hip).  clair_amd._hostapi.overlap_keep gives the same bytes on the CPU."""
+    from clair_amd._hostapi import SPAN_DTYPE
+    lib = load()
+    s = np.ascontiguousarray(spans, dtype=SPAN_DTYPE)
+    keep = np.zeros(len(s), dtype=np.uint8)
+    if lib.clair_overlap_keep(int(device), _ptr(s), len(s), _ptr(keep)) != 0:
+        raise EngineError("clair_overlap_keep failed: %s" % lib.clair_overlap_last_error().decode())
+    return keep

@@ -20,7 +20,8 @@ SYMBOLS = ("clair_host_abi_version", "clair_host_last_error", "clair_host_thread
            "clair_host_bam_next", "clair_host_bam_voffset", "clair_host_bam_render", "clair_host_faidx",
            "clair_host_bam_set_inflater", "clair_host_inflate_block", "clair_host_inflate_bgzf",
            "clair_host_sampack_set_lookup", "clair_host_indel_table",
-           "clair_host_ensemble_average", "clair_host_ensemble_quantise", "clair_host_ensemble_value")
+           "clair_host_ensemble_average", "clair_host_ensemble_quantise", "clair_host_ensemble_value",
+           "clair_host_overlap_keep")
 N_VALUES = 1056
 _lib = None
 
@@ -98,6 +99,7 @@ def load():
         lib.clair_host_ensemble_average.argtypes = [vp, i32, i64, vp]
         lib.clair_host_ensemble_quantise.argtypes = [vp, i64, vp]
         lib.clair_host_ensemble_value.argtypes = [vp, i64, vp]
+        lib.clair_host_overlap_keep.argtypes = [vp, i64, vp]
         lib.clair_host_tuple_budget_binds.argtypes = [vp, vp, i64, vp, vp, i64, vp, ctypes.POINTER(i32)]
         if lib.clair_host_abi_version() != 6:
             raise RuntimeError("libclair_host.so has ABI version %d, expected 6: run `python -m clair_amd.build`"
@@ -817,3 +819,19 @@ def ensemble_value(millionths):
     if load().clair_host_ensemble_value(m.ctypes.data, m.size, out.ctypes.data) != 0:
         raise ValueError(load().clair_host_last_error().decode())
     return out
+
+
+# clair_overlap_span (clair_amd/csrc/overlap_core.h): one VCF row as the overlap filter sees it; flags bit 0 = OVERLAP_SNP
+SPAN_DTYPE = np.dtype([("pos", "<i8"), ("ctg", "<i4"), ("qual", "<i4"), ("del", "<i4"), ("flags", "<u4")])
+assert SPAN_DTYPE.itemsize == 24
+OVERLAP_SNP = 1
+
+
+def overlap_keep(spans):
+    """clair_host_overlap_keep: spans (SPAN_DTYPE [n], input order) -> uint8 [n], 1 for the rows the overlap filter prints.  The CPU twin of
+    clair_amd._capi.overlap_keep."""
+    s = np.ascontiguousarray(spans, dtype=SPAN_DTYPE)
+    keep = np.zeros(len(s), dtype=np.uint8)
+    if load().clair_host_overlap_keep(s.ctypes.data, len(s), keep.ctypes.data) != 0:
+        raise ValueError(load().clair_host_last_error().decode())
+    return keep

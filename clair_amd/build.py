@@ -9,7 +9,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # (csrc/indel_lookup.hip is part of frontend.hip's translation unit: it works on that handle's slabs)
-SRCS = [os.path.join(HERE, "csrc", f) for f in ("engine.hip", "comm.hip", "frontend.hip", "inflate.hip")]
+SRCS = [os.path.join(HERE, "csrc", f) for f in ("engine.hip", "comm.hip", "frontend.hip", "inflate.hip", "overlap.hip")]
 OUT = os.path.join(HERE, "libclair_amd.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
@@ -36,7 +36,7 @@ def needs_build():
 
 
 HOST_SRCS = [os.path.join(HERE, "hostsrc", f) for f in ("host_io.cpp", "host_decode.cpp", "host_pileup.cpp", "host_sampack.cpp",
-                                                              "host_bam.cpp", "host_inflate.cpp", "host_indel.cpp", "host_ensemble.cpp")]
+                                                              "host_bam.cpp", "host_inflate.cpp", "host_indel.cpp", "host_ensemble.cpp", "host_overlap.cpp")]
 HOST_OUT = os.path.join(HERE, "libclair_host.so")
 CXX = os.environ.get("CXX", "g++")
 
@@ -49,6 +49,7 @@ def build_host(force=False):
     hdrs.append(os.path.join(HERE, "csrc", "inflate_core.h"))       # the decoder host_inflate.cpp shares with the device (csrc/inflate.hip)
     hdrs.append(os.path.join(HERE, "csrc", "indel_lookup_core.h"))  # the table host_indel.cpp shares with the device library (csrc/indel_lookup.hip)
     hdrs.append(os.path.join(HERE, "csrc", "ensemble_core.h"))      # the averaging rule host_ensemble.cpp shares with the device (csrc/ensemble.hip.h)
+    hdrs.append(os.path.join(HERE, "csrc", "overlap_core.h"))       # the pair rule and the walk host_overlap.cpp shares with the device (csrc/overlap.hip)
     if (force or not os.path.isfile(HOST_OUT)
             or max([os.path.getmtime(f) for f in HOST_SRCS + hdrs]) > os.path.getmtime(HOST_OUT)):
         # -ffp-contract=off: the decode restates float32 product chains bit for bit (no fused multiply-add)

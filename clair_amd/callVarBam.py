@@ -742,6 +742,7 @@ def normalise(args):
         if not 1 <= args.bam_threads <= 16:
             sys.exit("[ERROR] --bam_threads %d: 1 .. 16" % args.bam_threads)
     cv.check_ensemble_flags(args)
+    cv.check_overlap_flags(args)
     if native_lookup(args):
         if not native_input(args):
             sys.exit("[ERROR] --indel_lookup native answers from the alignments the native reader feeds the device front end: add --bam_reader native")
@@ -784,7 +785,7 @@ def call_region(args, m, prepared=None):
     else:
         lookup = cv.AlignmentLookup(args.bam_fn, args.ref_fn)
     decoder = cv.VariantDecoder(config, lookup, always_use_bam=args.pysam_for_all_indel_bases, arith=args.arith)
-    writer = cv.VcfWriter(args.call_fn, args.sampleName, args.ref_fn, args.output_for_ensemble)
+    writer = cv.writer_for(args)
     try:
         batch = args.batch_size or param.engineBatchSize
         source = None
@@ -826,7 +827,7 @@ def Run(args):
     logging.basicConfig(format="%(message)s", level=logging.INFO)
     cv.ingest.setup_environment()
     if args.activation_only:
-        cv.VcfWriter(args.call_fn, args.sampleName, args.ref_fn, args.output_for_ensemble).close()
+        cv.writer_for(args).close()
         return
     m = load_model(args)
     try:
@@ -906,6 +907,9 @@ def build_parser():
              "exactly as the reference's call_var --output_for_ensemble | ensemble | call_var --input_probabilities averages them")
     add('--arith', type=str, default="legacy", choices=("legacy", "numpy2"),
         help="QUAL/AF arithmetic: float64 as under the reference's NumPy 1.x (legacy) or float32 (numpy2)")
+    add('--overlap_filter', type=str, default="off", choices=("off", "host", "device"),
+        help="pass the finished VCF through the overlap filter (python -m clair_amd.overlap_variant: of two calls one of whose deletion covers "
+             "the other, the one with the higher QUAL stays), with its walk on the host or on the GPU --device names; default: %(default)s")
     return parser
 
 

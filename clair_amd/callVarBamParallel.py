@@ -69,6 +69,7 @@ def commands(args):
         # as ONE token: a value that is a single option ("-x", "--no-PG") would otherwise be read as the next flag
         None if args.samtools_view_args is None else '--samtools_view_args="%s"' % args.samtools_view_args,
         _opt("bam_reader", args.bam_reader), _opt("bam_threads", args.bam_threads), _opt("bam_inflate", args.bam_inflate), _opt("indel_lookup", args.indel_lookup),
+        _opt("overlap_filter", args.overlap_filter),
     ] + [_opt("ensemble_chkpnt_fn", os.path.abspath(f)) for f in (args.ensemble_chkpnt_fn or [])] if x is not None)
     out, k = [], 0
     commands.chunks = []           # (device, output file) per command, for --run
@@ -250,6 +251,8 @@ def build_parser():
     add('--bam_threads', type=int, default=None, help="passed on (callVarBam: BGZF inflate threads of --bam_reader native)")
     add('--bam_inflate', type=str, default=None, choices=("host", "device"), help="passed on (callVarBam: BGZF inflate on the host or on the GPU)")
     add('--indel_lookup', type=str, default=None, choices=("pysam", "native"), help="passed on (callVarBam: long-indel bases from pysam or from the GPU-resident alignments)")
+    add('--overlap_filter', type=str, default=None, choices=("off", "host", "device"),
+        help="passed on (callVarBam: every chunk's VCF through the overlap filter, on the host or on the GPU; the chunks are not merged)")
     add('--ensemble_chkpnt_fn', type=str, action='append', default=None, metavar="PREFIX",
         help="passed on, repeatable (callVarBam: one more checkpoint whose probabilities are averaged with --chkpnt_fn's on the GPU)")
     return parser

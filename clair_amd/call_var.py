@@ -678,11 +678,14 @@ HEADER_LINES = (
 class VcfWriter(object):
     """Output side of output_utilties_from (call_var.py:223-341): header + rows to --call_fn."""
 
-    def __init__(self, output_file_path, sample_name="SAMPLE", reference_file_path=None, is_output_for_ensemble=False):
+    def __init__(self, output_file_path, sample_name="SAMPLE", reference_file_path=None, is_output_for_ensemble=False, overlap_filter="off", device=0):
+        """overlap_filter: "host" / "device" pass the finished file through clair_amd.overlap_variant when it is closed (--overlap_filter)."""
+        self.path = output_file_path
         self.fp = open(output_file_path, "w")
         self.sample_name = sample_name
         self.reference_file_path = reference_file_path
         self.is_output_for_ensemble = is_output_for_ensemble
+        self.overlap_filter, self.device = overlap_filter, device
 
     def write(self, text):
         print(text, file=self.fp)
@@ -709,7 +712,22 @@ class VcfWriter(object):
         self.write('#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t%s' % self.sample_name)
 
     def close(self):
+        if self.fp.closed:
+            return
         self.fp.close()
+        if self.overlap_filter != "off" and not self.is_output_for_ensemble:
+            # exactly what `overlap_variant < file` prints for the file written so far: same header, re-rendered rows (docs/overlap_variant.md)
+            from clair_amd import overlap_variant
+            with open(self.path) as f:
+                text = f.read()
+            filtered = overlap_variant.filter_vcf_text(text, self.overlap_filter, self.device)
+            with open(self.path, "w") as f:
+                f.write(filtered)
+
+
+def writer_for(args):
+    """The VcfWriter a caller's arguments ask for (call_var, callVarBam)."""
+    return VcfWriter(args.call_fn, args.sampleName, args.ref_fn, args.output_for_ensemble, getattr(args, "overlap_filter", "off"), args.device)
 
 
 # =============================================================================================
@@ -895,9 +913,10 @@ def Run(args):
         is_haploid_sensitive_mode_enabled=args.haploid_sensitive,
         is_output_for_ensemble=args.output_for_ensemble, quality_score_for_pass=args.qual)
     check_ensemble_flags(args)
+    check_overlap_flags(args)
     lookup = AlignmentLookup(args.bam_fn, args.ref_fn)
     decoder = VariantDecoder(config, lookup, always_use_bam=args.pysam_for_all_indel_bases, arith=args.arith)
-    writer = VcfWriter(args.call_fn, args.sampleName, args.ref_fn, args.output_for_ensemble)
+    writer = writer_for(args)
     try:
         if args.input_probabilities:
             call_variants_with_probabilities_input(args, decoder, writer)
@@ -936,6 +955,12 @@ def check_ensemble_flags(args):
             sys.exit("[ERROR] --ensemble_chkpnt_fn adds checkpoints to --chkpnt_fn, which is model 0: give --chkpnt_fn as well")
 
 
+def check_overlap_flags(args):
+    """--overlap_filter filters VCF rows; --output_for_ensemble writes none."""
+    if getattr(args, "overlap_filter", "off") != "off" and args.output_for_ensemble:
+        sys.exit("[ERROR] --overlap_filter drops overlapping calls from a VCF; --output_for_ensemble writes probabilities, not calls: use one of the two")
+
+
 def restore_checkpoints(m, args):
     """--chkpnt_fn alone: restore_parameters, as ever.  With --ensemble_chkpnt_fn: model 0 = --chkpnt_fn, then those in command-line order."""
     more = getattr(args, "ensemble_chkpnt_fn", None) or []
@@ -946,7 +971,7 @@ def restore_checkpoints(m, args):
 
 
 def build_parser():
-    """Same flags and defaults as call_var.py:1370-1429, plus --batch_size / --device / --arith / --ensemble_chkpnt_fn."""
+    """Same flags and defaults as call_var.py:1370-1429, plus --batch_size / --device / --arith / --ensemble_chkpnt_fn / --overlap_filter."""
     parser = ArgumentParser(description="Call variants using a trained model and tensors of candididate variants")
     parser.add_argument('--tensor_fn', type=str, default="PIPE", help="Tensor input, use PIPE for standard input")
     parser.add_argument('--chkpnt_fn', type=str, default=None, help="Input a checkpoint for testing")
@@ -986,6 +1011,9 @@ def build_parser():
     parser.add_argument('--ensemble_chkpnt_fn', type=str, action='append', default=None, metavar="PREFIX",
                         help="one more checkpoint to call with, repeatable (at most 7): the probabilities of --chkpnt_fn and of these are averaged "
                              "on the GPU exactly as --output_for_ensemble | ensemble | --input_probabilities averages them")
+    parser.add_argument('--overlap_filter', type=str, default="off", choices=("off", "host", "device"),
+                        help="pass the finished VCF through the overlap filter (python -m clair_amd.overlap_variant: of two calls one of whose "
+                             "deletion covers the other, the one with the higher QUAL stays), with its walk on the host or on the GPU; default: %(default)s")
     return parser
 
 

@@ -420,6 +420,20 @@ int clair_inflate_blocks(clair_inflate_t *h, const uint8_t *cdata, int64_t cbyte
 int clair_inflate_blocks_cb(void *handle, const uint8_t *cdata, int64_t cbytes, int n, const int64_t *in_at, const int32_t *csize,
                             const int64_t *out_at, const int32_t *out_len, uint8_t *out, int32_t *status);
 
+/* -- the overlap filter on the device (call_var / callVarBam --overlap_filter device; csrc/overlap.hip, docs/overlap_variant.md).
+ * The walk of clair/post_processing/overlap_variant.py:237-267 over n rows reduced to 24-byte spans (csrc/overlap_core.h lays the
+ * record out and holds the pair rule): spans [n] in input order, host memory -> keep [n], host memory, 1 for every row the filter
+ * prints.  Exact for every input, unsorted ones included: rows no earlier row of their contig run can overlap are found with a
+ * segmented max-scan, and one lane walks each stretch between two of them with the sequential rule.  Synchronous; the device memory
+ * lives for the call.  Returns non-zero for a bad argument, a missing device or a HIP error, with a message in _last_error (one per
+ * process).  clair_host_overlap_keep (include/clair_host.h) gives the same bytes on the CPU. */
+#ifndef CLAIR_OVERLAP_SPAN_T
+#define CLAIR_OVERLAP_SPAN_T
+typedef struct clair_overlap_span clair_overlap_span_t;
+#endif
+int clair_overlap_keep(int device, const clair_overlap_span_t *spans, int64_t n, uint8_t *keep);
+const char *clair_overlap_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -255,6 +255,16 @@ int clair_host_ensemble_average(const float *probs, int models, int64_t count, f
 int clair_host_ensemble_quantise(const float *p, int64_t count, int32_t *millionths);
 int clair_host_ensemble_value(const int32_t *millionths, int64_t count, float *out);
 
+/* -- the host twin of the device overlap filter (hostsrc/host_overlap.cpp): the walk of clair/post_processing/overlap_variant.py:237-267
+ *    over rows reduced to spans, with the pair rule of csrc/overlap_core.h (which also lays the 24-byte span record out), the code the
+ *    GPU runs inside clair_overlap_keep (include/clair_amd.h).  spans [n] in input order -> keep [n]: 1 for the rows the filter prints,
+ *    0 for those it drops.  The text on either side is clair_amd/overlap_variant.py's; docs/overlap_variant.md has the rule. */
+#ifndef CLAIR_OVERLAP_SPAN_T
+#define CLAIR_OVERLAP_SPAN_T
+typedef struct clair_overlap_span clair_overlap_span_t;
+#endif
+int clair_host_overlap_keep(const clair_overlap_span_t *spans, int64_t n, uint8_t *keep);
+
 #ifdef __cplusplus
 }
 #endif
