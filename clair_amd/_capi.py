@@ -8,31 +8,106 @@ import os
 
 import numpy as np
 
+from clair_amd._hostapi import Handle
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CLAIR_AMD_LIB") or os.path.join(_HERE, "libclair_amd.so")   # override: debugging builds only
 
-# every symbol include/clair_amd.h declares (tests/test_abi.py checks header <-> this list <-> .so)
-SYMBOLS = (
-    "clair_abi_version", "clair_device_count", "clair_device_pci_bus_id", "clair_last_error",
-    "clair_engine_create", "clair_engine_destroy",
-    "clair_set_tensor", "clair_finalize_weights",
-    "clair_predict", "clair_submit", "clair_wait", "clair_slot_input", "clair_submit_counts", "clair_submit_ex", "clair_decode", "clair_pinned_alloc", "clair_pinned_free",
-    "clair_dataset_alloc", "clair_dataset_free", "clair_dataset_upload", "clair_dataset_download",
-    "clair_run_resident", "clair_sync",
-    "clair_timing_enable", "clair_kernel_times", "clair_timing_reset", "clair_kernel_workgroups",
-    "clair_debug_read", "clair_engine_counter",
-    "clair_comm_preflight", "clair_comm_unique_id", "clair_comm_create", "clair_comm_create_timed", "clair_comm_destroy", "clair_comm_abort", "clair_comm_last_error", "clair_comm_barrier",
-    "clair_comm_allreduce_f64", "clair_comm_broadcast", "clair_comm_allgather", "clair_comm_allgather_device",
-    "clair_frontend_create", "clair_frontend_destroy", "clair_frontend_last_error", "clair_frontend_add_reads",
-    "clair_frontend_find_candidates", "clair_frontend_set_candidates", "clair_frontend_get_candidates", "clair_frontend_build_windows",
-    "clair_frontend_build_windows_ex", "clair_frontend_window_info", "clair_frontend_window_counts", "clair_frontend_counts_device", "clair_frontend_budget_inputs",
-    "clair_frontend_stats", "clair_frontend_text_options", "clair_frontend_add_text", "clair_frontend_text_stats", "clair_frontend_slab_reads",
-    "clair_frontend_bam_options", "clair_frontend_add_bam", "clair_frontend_bam_lookup", "clair_frontend_indel_table",
-    "clair_eval_reset", "clair_submit_eval", "clair_eval", "clair_eval_read",
-    "clair_ensemble_models", "clair_ensemble_set_tensor", "clair_ensemble_finalize_weights", "clair_submit_ensemble", "clair_ensemble_average",
-    "clair_inflate_create", "clair_inflate_destroy", "clair_inflate_last_error", "clair_inflate_blocks", "clair_inflate_blocks_cb",
-    "clair_overlap_keep", "clair_overlap_last_error",
-)
+c_int, c_i64, c_vp, c_cp, c_dbl = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_double
+p_vp, p_i64 = ctypes.POINTER(c_vp), ctypes.POINTER(c_i64)
+
+
+def _sig(*argtypes, **kw):
+    """One row of SIGNATURES: (restype, argtypes); a function returns int unless restype= says otherwise."""
+    return kw.get("restype", c_int), list(argtypes)
+
+
+_SUBMIT_EX = (c_vp, c_int, c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp)
+_INFLATE_BLOCKS = (c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp)
+# every function include/clair_amd.h declares, with its prototype there as ctypes states it (tests/test_abi.py checks header <-> this table <-> .so):
+# the one place to add an entry point
+SIGNATURES = {
+    "clair_abi_version": _sig(),
+    "clair_device_count": _sig(),
+    "clair_device_pci_bus_id": _sig(c_int, c_cp, c_int),
+    "clair_last_error": _sig(c_vp, restype=c_cp),
+    "clair_engine_create": _sig(c_int, c_int, c_int, p_vp),
+    "clair_engine_destroy": _sig(c_vp, restype=None),
+    "clair_set_tensor": _sig(c_vp, c_int, c_vp, c_i64),
+    "clair_finalize_weights": _sig(c_vp),
+    "clair_predict": _sig(c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp),
+    "clair_submit": _sig(c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp),
+    "clair_wait": _sig(c_vp, c_int),
+    "clair_slot_input": _sig(c_vp, c_int, p_vp),
+    "clair_submit_counts": _sig(c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp),
+    "clair_submit_ex": _sig(*_SUBMIT_EX),
+    "clair_decode": _sig(c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp),
+    "clair_pinned_alloc": _sig(c_vp, c_i64, p_vp),
+    "clair_pinned_free": _sig(c_vp, c_vp),
+    "clair_eval_reset": _sig(c_vp),
+    "clair_submit_eval": _sig(c_vp, c_int, c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp),
+    "clair_eval": _sig(c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int),
+    "clair_eval_read": _sig(c_vp, c_vp),
+    "clair_ensemble_models": _sig(c_vp, c_int),
+    "clair_ensemble_set_tensor": _sig(c_vp, c_int, c_int, c_vp, c_i64),
+    "clair_ensemble_finalize_weights": _sig(c_vp, c_int),
+    "clair_submit_ensemble": _sig(*_SUBMIT_EX),
+    "clair_ensemble_average": _sig(c_vp, c_int, c_vp, c_int, c_int, c_vp),
+    "clair_dataset_alloc": _sig(c_vp, c_i64, p_vp, p_vp),
+    "clair_dataset_free": _sig(c_vp, c_vp, c_vp),
+    "clair_dataset_upload": _sig(c_vp, c_vp, c_i64, c_vp, c_i64),
+    "clair_dataset_download": _sig(c_vp, c_vp, c_i64, c_vp, c_i64),
+    "clair_run_resident": _sig(c_vp, c_int, c_vp, c_vp, c_i64, c_int),
+    "clair_sync": _sig(c_vp),
+    "clair_timing_enable": _sig(c_vp, c_int),
+    "clair_kernel_times": _sig(c_vp, c_vp, c_vp),
+    "clair_timing_reset": _sig(c_vp),
+    "clair_kernel_workgroups": _sig(c_vp, c_int, c_vp),
+    "clair_engine_counter": _sig(c_vp, c_int, p_i64),
+    "clair_debug_read": _sig(c_vp, c_int, c_int, c_vp, c_i64),
+    "clair_comm_preflight": _sig(c_int),
+    "clair_comm_unique_id": _sig(c_vp),
+    "clair_comm_create": _sig(c_int, c_int, c_int, c_vp, p_vp),
+    "clair_comm_create_timed": _sig(c_int, c_int, c_int, c_vp, c_int, p_vp),
+    "clair_comm_destroy": _sig(c_vp, restype=None),
+    "clair_comm_abort": _sig(c_vp, restype=None),
+    "clair_comm_last_error": _sig(c_vp, restype=c_cp),
+    "clair_comm_barrier": _sig(c_vp),
+    "clair_comm_allreduce_f64": _sig(c_vp, c_vp, c_int, c_int),
+    "clair_comm_broadcast": _sig(c_vp, c_vp, c_i64, c_int),
+    "clair_comm_allgather": _sig(c_vp, c_vp, c_vp, c_i64),
+    "clair_comm_allgather_device": _sig(c_vp, c_vp, c_vp, c_i64),
+    "clair_frontend_create": _sig(c_int, c_cp, c_i64, c_i64, c_i64, c_i64, p_vp),
+    "clair_frontend_destroy": _sig(c_vp, restype=None),
+    "clair_frontend_last_error": _sig(c_vp, restype=c_cp),
+    "clair_frontend_add_reads": _sig(c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64),
+    "clair_frontend_text_options": _sig(c_vp, c_cp, c_int, c_int, c_int, c_i64, c_i64),
+    "clair_frontend_add_text": _sig(c_vp, c_vp, c_i64),
+    "clair_frontend_text_stats": _sig(c_vp, c_vp),
+    "clair_frontend_slab_reads": _sig(c_vp, c_i64, c_vp, c_i64, p_i64),
+    "clair_frontend_bam_options": _sig(c_vp, c_int, c_int, c_int, c_int, c_i64, c_i64, c_i64, c_i64),
+    "clair_frontend_add_bam": _sig(c_vp, c_vp, c_i64, c_vp, c_i64),
+    "clair_frontend_bam_lookup": _sig(c_vp, c_int),
+    "clair_frontend_indel_table": _sig(c_vp, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_vp),
+    "clair_frontend_find_candidates": _sig(c_vp, c_dbl, c_dbl, c_i64, c_i64, c_vp, c_vp, c_i64, p_i64),
+    "clair_frontend_set_candidates": _sig(c_vp, c_vp, c_i64, p_i64),
+    "clair_frontend_get_candidates": _sig(c_vp, c_vp),
+    "clair_frontend_build_windows": _sig(c_vp, c_int, c_int, p_i64),
+    "clair_frontend_build_windows_ex": _sig(c_vp, c_int, c_int, c_int, p_i64),
+    "clair_frontend_window_info": _sig(c_vp, c_i64, c_i64, c_vp, c_vp),
+    "clair_frontend_window_counts": _sig(c_vp, c_i64, c_i64, c_vp),
+    "clair_frontend_counts_device": _sig(c_vp, c_i64, restype=c_vp),
+    "clair_frontend_budget_inputs": _sig(c_vp, c_i64, c_vp, c_vp, c_vp),
+    "clair_frontend_stats": _sig(c_vp, c_vp),
+    "clair_inflate_create": _sig(c_int, c_int, p_vp),
+    "clair_inflate_destroy": _sig(c_vp, restype=None),
+    "clair_inflate_last_error": _sig(c_vp, restype=c_cp),
+    "clair_inflate_blocks": _sig(*_INFLATE_BLOCKS),
+    "clair_inflate_blocks_cb": _sig(*_INFLATE_BLOCKS),
+    "clair_overlap_keep": _sig(c_int, c_vp, c_i64, c_vp),
+    "clair_overlap_last_error": _sig(restype=c_cp),
+}
+SYMBOLS = tuple(SIGNATURES)
 ENSEMBLE_MAX_MODELS = 8                                      # CLAIR_ENSEMBLE_MAX_MODELS
 OVERLAP_SCAN_BLOCK = 2048                                    # clair_ov::BLOCK (csrc/overlap.hip): rows per workgroup of the head scan
 EVAL_COUNTS = 3 + 21 * 21 + 3 * 3 + 33 * 33 + 33 * 33      # CLAIR_EVAL_COUNTS: all, top1, top2, gt21, genotype, len1, len2
@@ -44,11 +119,6 @@ _libs = {}
 
 class EngineError(RuntimeError):
     pass
-
-
-def older_ok_early(path):
-    """An OLDER build of the same sources, named explicitly (A/B timing, tools/gpu/ab_libs.sh), may predate the newest entry points."""
-    return path is not None or bool(os.environ.get("CLAIR_AMD_LIB"))
 
 
 def load(path=None):
@@ -66,117 +136,13 @@ def load(path=None):
             "%s not found: build the HIP extension first (python -m clair_amd.build, or "
             "__graft_entry__.build()). There is no CPU fallback." % lib_path)
     lib = ctypes.CDLL(lib_path)
-    c_int, c_i64, c_vp = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
-    lib.clair_abi_version.restype = c_int
-    lib.clair_device_count.restype = c_int
-    if not older_ok_early(path) or hasattr(lib, "clair_device_pci_bus_id"):
-        lib.clair_device_pci_bus_id.argtypes = [c_int, ctypes.c_char_p, c_int]
-    lib.clair_last_error.restype = ctypes.c_char_p
-    lib.clair_last_error.argtypes = [c_vp]
-    lib.clair_engine_create.argtypes = [c_int, c_int, c_int, ctypes.POINTER(c_vp)]
-    lib.clair_engine_destroy.argtypes = [c_vp]
-    lib.clair_engine_destroy.restype = None
-    lib.clair_set_tensor.argtypes = [c_vp, c_int, c_vp, c_i64]
-    lib.clair_finalize_weights.argtypes = [c_vp]
-    lib.clair_predict.argtypes = [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]
-    lib.clair_submit.argtypes = [c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]
+    # an OLDER build of the same sources, named explicitly (A/B timing, tools/gpu/ab_libs.sh), may predate the newest entry points: those stay unbound
     older_ok = path is not None or bool(os.environ.get("CLAIR_AMD_LIB"))
-    if not older_ok or hasattr(lib, "clair_submit_ex"):     # an OLDER build named by `path` (A/B timing, tools/gpu/ab_libs.sh) may predate these
-        lib.clair_submit_ex.argtypes = [c_vp, c_int, c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
-        lib.clair_decode.argtypes = [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp]
-        lib.clair_pinned_alloc.argtypes = [c_vp, c_i64, ctypes.POINTER(c_vp)]
-        lib.clair_pinned_free.argtypes = [c_vp, c_vp]
-    if not older_ok or hasattr(lib, "clair_eval_reset"):
-        lib.clair_eval_reset.argtypes = [c_vp]
-        lib.clair_submit_eval.argtypes = [c_vp, c_int, c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]
-        lib.clair_eval.argtypes = [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int]
-        lib.clair_eval_read.argtypes = [c_vp, c_vp]
-    if not older_ok or hasattr(lib, "clair_ensemble_models"):
-        lib.clair_ensemble_models.argtypes = [c_vp, c_int]
-        lib.clair_ensemble_set_tensor.argtypes = [c_vp, c_int, c_int, c_vp, c_i64]
-        lib.clair_ensemble_finalize_weights.argtypes = [c_vp, c_int]
-        lib.clair_submit_ensemble.argtypes = [c_vp, c_int, c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
-        lib.clair_ensemble_average.argtypes = [c_vp, c_int, c_vp, c_int, c_int, c_vp]
-    lib.clair_wait.argtypes = [c_vp, c_int]
-    lib.clair_slot_input.argtypes = [c_vp, c_int, ctypes.POINTER(c_vp)]
-    lib.clair_submit_counts.argtypes = [c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]
-    lib.clair_dataset_alloc.argtypes = [c_vp, c_i64, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp)]
-    lib.clair_dataset_free.argtypes = [c_vp, c_vp, c_vp]
-    lib.clair_dataset_upload.argtypes = [c_vp, c_vp, c_i64, c_vp, c_i64]
-    lib.clair_dataset_download.argtypes = [c_vp, c_vp, c_i64, c_vp, c_i64]
-    lib.clair_run_resident.argtypes = [c_vp, c_int, c_vp, c_vp, c_i64, c_int]
-    lib.clair_sync.argtypes = [c_vp]
-    lib.clair_timing_enable.argtypes = [c_vp, c_int]
-    lib.clair_kernel_times.argtypes = [c_vp, c_vp, c_vp]
-    lib.clair_timing_reset.argtypes = [c_vp]
-    lib.clair_kernel_workgroups.argtypes = [c_vp, c_int, c_vp]
-    lib.clair_debug_read.argtypes = [c_vp, c_int, c_int, c_vp, c_i64]
-    lib.clair_engine_counter.argtypes = [c_vp, c_int, ctypes.POINTER(c_i64)]
-    lib.clair_comm_preflight.argtypes = [c_int]
-    lib.clair_comm_unique_id.argtypes = [c_vp]
-    lib.clair_comm_create.argtypes = [c_int, c_int, c_int, c_vp, ctypes.POINTER(c_vp)]
-    if not older_ok or hasattr(lib, "clair_comm_create_timed"):
-        lib.clair_comm_create_timed.argtypes = [c_int, c_int, c_int, c_vp, c_int, ctypes.POINTER(c_vp)]
-    lib.clair_comm_destroy.argtypes = [c_vp]
-    lib.clair_comm_destroy.restype = None
-    if not older_ok or hasattr(lib, "clair_comm_abort"):
-        lib.clair_comm_abort.argtypes = [c_vp]
-        lib.clair_comm_abort.restype = None
-    lib.clair_comm_last_error.argtypes = [c_vp]
-    lib.clair_comm_last_error.restype = ctypes.c_char_p
-    lib.clair_comm_barrier.argtypes = [c_vp]
-    lib.clair_comm_allreduce_f64.argtypes = [c_vp, c_vp, c_int, c_int]
-    lib.clair_comm_broadcast.argtypes = [c_vp, c_vp, c_i64, c_int]
-    lib.clair_comm_allgather.argtypes = [c_vp, c_vp, c_vp, c_i64]
-    lib.clair_comm_allgather_device.argtypes = [c_vp, c_vp, c_vp, c_i64]
-    if not older_ok or hasattr(lib, "clair_frontend_create"):
-        lib.clair_frontend_create.argtypes = [c_int, ctypes.c_char_p, c_i64, c_i64, c_i64, c_i64, ctypes.POINTER(c_vp)]
-        lib.clair_frontend_destroy.argtypes = [c_vp]
-        lib.clair_frontend_destroy.restype = None
-        lib.clair_frontend_last_error.argtypes = [c_vp]
-        lib.clair_frontend_last_error.restype = ctypes.c_char_p
-        lib.clair_frontend_add_reads.argtypes = [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64]
-        lib.clair_frontend_find_candidates.argtypes = [c_vp, ctypes.c_double, ctypes.c_double, c_i64, c_i64, c_vp, c_vp, c_i64, ctypes.POINTER(c_i64)]
-        lib.clair_frontend_set_candidates.argtypes = [c_vp, c_vp, c_i64, ctypes.POINTER(c_i64)]
-        lib.clair_frontend_get_candidates.argtypes = [c_vp, c_vp]
-        lib.clair_frontend_build_windows.argtypes = [c_vp, c_int, c_int, ctypes.POINTER(c_i64)]
-        lib.clair_frontend_build_windows_ex.argtypes = [c_vp, c_int, c_int, c_int, ctypes.POINTER(c_i64)]
-        lib.clair_frontend_window_info.argtypes = [c_vp, c_i64, c_i64, c_vp, c_vp]
-        lib.clair_frontend_window_counts.argtypes = [c_vp, c_i64, c_i64, c_vp]
-        lib.clair_frontend_counts_device.argtypes = [c_vp, c_i64]
-        lib.clair_frontend_counts_device.restype = c_vp
-        lib.clair_frontend_budget_inputs.argtypes = [c_vp, c_i64, c_vp, c_vp, c_vp]
-        lib.clair_frontend_stats.argtypes = [c_vp, c_vp]
-        lib.clair_frontend_text_options.argtypes = [c_vp, ctypes.c_char_p, c_int, c_int, c_int, c_i64, c_i64]
-        lib.clair_frontend_add_text.argtypes = [c_vp, c_vp, c_i64]
-        lib.clair_frontend_text_stats.argtypes = [c_vp, c_vp]
-        lib.clair_frontend_slab_reads.argtypes = [c_vp, c_i64, c_vp, c_i64, ctypes.POINTER(c_i64)]
-        if hasattr(lib, "clair_frontend_add_bam") or not older_ok:
-            lib.clair_frontend_bam_options.argtypes = [c_vp, c_int, c_int, c_int, c_int, c_i64, c_i64, c_i64, c_i64]
-            lib.clair_frontend_add_bam.argtypes = [c_vp, c_vp, c_i64, c_vp, c_i64]
-        if hasattr(lib, "clair_frontend_indel_table") or not older_ok:
-            lib.clair_frontend_bam_lookup.argtypes = [c_vp, c_int]
-            lib.clair_frontend_indel_table.argtypes = [c_vp, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_vp]
-    if not older_ok or hasattr(lib, "clair_inflate_create"):
-        lib.clair_inflate_create.argtypes = [c_int, c_int, ctypes.POINTER(c_vp)]
-        lib.clair_inflate_destroy.argtypes = [c_vp]
-        lib.clair_inflate_destroy.restype = None
-        lib.clair_inflate_last_error.argtypes = [c_vp]
-        lib.clair_inflate_last_error.restype = ctypes.c_char_p
-        lib.clair_inflate_blocks.argtypes = [c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
-        lib.clair_inflate_blocks_cb.argtypes = lib.clair_inflate_blocks.argtypes
-    if not older_ok or hasattr(lib, "clair_overlap_keep"):
-        lib.clair_overlap_keep.argtypes = [c_int, c_vp, c_i64, c_vp]
-        lib.clair_overlap_last_error.argtypes = []
-        lib.clair_overlap_last_error.restype = ctypes.c_char_p
-    for name in SYMBOLS:
-        if older_ok and not hasattr(lib, name):
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name, None) if older_ok else getattr(lib, name)    # AttributeError: this tree's own build lacks a declared entry point
+        if fn is None:
             continue
-        fn = getattr(lib, name)
-        if name not in ("clair_last_error", "clair_engine_destroy", "clair_comm_last_error", "clair_comm_destroy",
-                        "clair_frontend_last_error", "clair_frontend_destroy", "clair_frontend_counts_device",
-                        "clair_inflate_last_error", "clair_inflate_destroy", "clair_overlap_last_error"):
-            fn.restype = c_int
+        fn.restype, fn.argtypes = restype, argtypes
     if path is None:
         _lib = lib
     else:
@@ -188,36 +154,45 @@ def _ptr(a):
     return ctypes.c_void_p(a.ctypes.data)
 
 
-class Engine(object):
+def prepare_batch(batch, counts):
+    """What clair_submit_ex / clair_submit_eval / clair_submit_ensemble take of a batch -> (keep_alive, address, is_counts, stride_bytes, n).
+    batch: [n,33,8,4] float32, or int16 with counts=True -- a strided view whose candidates are dense (the counts column of an array of
+    binary tensor records) goes through as it lies, anything else is copied to a contiguous array of the right dtype; or windows already in
+    device memory as int16 counts, a DeviceWindows or an (address, n) tuple: the address goes through as it is."""
+    if isinstance(batch, DeviceWindows):
+        return batch, ctypes.c_void_p(batch.address), 1, 0, len(batch)
+    if isinstance(batch, tuple):
+        return None, ctypes.c_void_p(int(batch[0])), 1, 0, int(batch[1])
+    dtype = np.int16 if counts else np.float32
+    x = np.asarray(batch)
+    if x.ndim != 4 or x.shape[1:] != (33, 8, 4):
+        raise ValueError("batch must have shape [n,33,8,4], got %r" % (x.shape,))
+    n = x.shape[0]
+    inner_dense = x.dtype == dtype and n > 0 and x[0].flags.c_contiguous and x.strides[0] >= x[0].nbytes
+    if not inner_dense:
+        x = np.ascontiguousarray(x, dtype=dtype)
+    return x, _ptr(x), int(bool(counts)), 0 if x.flags.c_contiguous else int(x.strides[0]), n
+
+
+class DeviceHandle(Handle):
+    """A handle of this library: its last-error function takes the handle (NULL after a failed create), failures are EngineError."""
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise EngineError("%s failed: %s" % (what, self._last_error(self._h).decode()))
+
+
+class Engine(DeviceHandle):
     """Thin object wrapper over one clair_engine_t."""
 
     def __init__(self, device=0, max_batch=1024, n_slots=1, lib_path=None):
         self._lib = load(lib_path)
-        self._h = ctypes.c_void_p()
         self.max_batch = int(max_batch)
         self.n_slots = int(n_slots)
-        rc = self._lib.clair_engine_create(int(device), int(max_batch), int(n_slots), ctypes.byref(self._h))
-        if rc != 0:
-            msg = self._lib.clair_last_error(None).decode()
-            self._h = ctypes.c_void_p()
-            raise EngineError("clair_engine_create failed: %s" % msg)
+        out = self._own(self._lib.clair_engine_destroy, self._lib.clair_last_error)
+        self._check(self._lib.clair_engine_create(int(device), int(max_batch), int(n_slots), out), "clair_engine_create")
         self._pending = {}
         self.n_models = 1
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise EngineError("%s failed: %s" % (what, self._lib.clair_last_error(self._h).decode()))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.clair_engine_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # -- weights ---------------------------------------------------------------------------
     def load_weights(self, w):
@@ -295,19 +270,7 @@ class Engine(object):
 
     def _submit_ex(self, fn, what, slot, batch, centre, counts, with_probabilities):
         from clair_amd._hostapi import CALL_DTYPE
-        if isinstance(batch, DeviceWindows):       # windows the device front end left in HBM: the address goes through as it is
-            keep, n = batch, len(batch)
-            ptr, is_counts, stride = ctypes.c_void_p(batch.address), 1, 0
-        else:
-            dtype = np.int16 if counts else np.float32
-            x = np.asarray(batch)
-            if x.ndim != 4 or x.shape[1:] != (33, 8, 4):
-                raise ValueError("batch must have shape [n,33,8,4], got %r" % (x.shape,))
-            n = x.shape[0]
-            inner_dense = x.dtype == dtype and n > 0 and x[0].flags.c_contiguous and x.strides[0] >= x[0].nbytes
-            if not inner_dense:
-                x = np.ascontiguousarray(x, dtype=dtype)
-            keep, ptr, is_counts, stride = x, _ptr(x), int(bool(counts)), 0 if x.flags.c_contiguous else int(x.strides[0])
+        keep, ptr, is_counts, stride, n = prepare_batch(batch, counts)
         c = calls = None
         if centre is not None:
             c = np.ascontiguousarray(centre, dtype=np.uint8)
@@ -367,20 +330,7 @@ class Engine(object):
         """clair_submit_eval: forward pass + scoring against `labels` (uint8 [n,4]) on the device.  batch as submit_calls takes it
         ([n,33,8,4] float32, raw int16 counts with counts=True, or (device address, n) of int16 counts).  wait(slot) returns None, or
         [gt21, genotype, len1, len2] with with_probabilities=True; the counters come from eval_read()."""
-        if isinstance(batch, tuple):                # (device address of dense int16 counts, n): nothing is copied
-            address, n = int(batch[0]), int(batch[1])
-            x, ptr, is_counts, stride = None, ctypes.c_void_p(address), 1, 0
-        else:
-            dtype = np.int16 if counts else np.float32
-            x = np.asarray(batch)
-            if x.ndim != 4 or x.shape[1:] != (33, 8, 4):
-                raise ValueError("batch must have shape [n,33,8,4], got %r" % (x.shape,))
-            n = x.shape[0]
-            inner_dense = x.dtype == dtype and n > 0 and x[0].flags.c_contiguous and x.strides[0] >= x[0].nbytes
-            if not inner_dense:
-                x = np.ascontiguousarray(x, dtype=dtype)
-            stride = 0 if x.flags.c_contiguous else int(x.strides[0])
-            ptr, is_counts = _ptr(x), int(bool(counts))
+        x, ptr, is_counts, stride, n = prepare_batch(batch, counts)
         lab = self._prep_labels(labels, n)
         outs = self._alloc_out(n) if with_probabilities else None
         ptrs = [_ptr(o) for o in outs] if outs else [None] * 4
@@ -508,34 +458,16 @@ class DeviceWindows(object):
         return self.frontend.window_counts(self.first, self.n)
 
 
-class Frontend(object):
+class Frontend(DeviceHandle):
     """Thin object wrapper over one clair_frontend_t (include/clair_amd.h, "front end on the device")."""
 
     def __init__(self, device, reference_sequence, reference_start_0_based, span_lo, span_hi, lib_path=None):
         self._lib = load(lib_path)
         ref = reference_sequence.encode("latin-1") if isinstance(reference_sequence, str) else bytes(reference_sequence)
-        self._h = ctypes.c_void_p()
-        rc = self._lib.clair_frontend_create(int(device), ref, len(ref), int(reference_start_0_based), int(span_lo), int(span_hi), ctypes.byref(self._h))
-        if rc != 0:
-            msg = self._lib.clair_frontend_last_error(None).decode()
-            self._h = ctypes.c_void_p()
-            raise EngineError("clair_frontend_create failed: %s" % msg)
+        out = self._own(self._lib.clair_frontend_destroy, self._lib.clair_frontend_last_error)
+        self._check(self._lib.clair_frontend_create(int(device), ref, len(ref), int(reference_start_0_based), int(span_lo), int(span_hi), out),
+                    "clair_frontend_create")
         self.slab_reads = []                # host copies of each slab's read records: the budget replay walks them
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise EngineError("%s failed: %s" % (what, self._lib.clair_frontend_last_error(self._h).decode()))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.clair_frontend_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def add_slab(self, packer):
         """Send the slab a clair_amd._hostapi.SamPacker is holding to the device and start the next one."""
@@ -575,7 +507,7 @@ class Frontend(object):
         before = self.stats()["slabs"]
         rc = self._lib.clair_frontend_add_text(self._h, address, int(length))
         if rc == 2:
-            raise MalformedText(self._lib.clair_frontend_last_error(self._h).decode())
+            raise MalformedText(self._last_error(self._h).decode())
         self._check(rc, "clair_frontend_add_text")
         self._keep_slab_reads(before)
 
@@ -621,7 +553,7 @@ class Frontend(object):
         rc = self._lib.clair_frontend_add_bam(self._h, address, int(length), _ptr(offsets), int(n_records))
         if rc == 2:
             import re
-            msg = self._lib.clair_frontend_last_error(self._h).decode()
+            msg = self._last_error(self._h).decode()
             m = re.search(r"record (\d+)", msg)
             raise MalformedRecord(msg, int(m.group(1)) if m else 0)
         self._check(rc, "clair_frontend_add_bam")
@@ -715,7 +647,7 @@ class Frontend(object):
         return centres, window_tuples
 
 
-class Inflater(object):
+class Inflater(DeviceHandle):
     """clair_inflate_*: BGZF blocks inflated on the device, a wave per block (csrc/inflate.hip).
 
         inf = Inflater(device=0, max_blocks=2048)
@@ -727,11 +659,8 @@ class Inflater(object):
 
     def __init__(self, device=0, max_blocks=2048):
         self._lib = load()
-        self._h = ctypes.c_void_p()
-        if self._lib.clair_inflate_create(int(device), int(max_blocks), ctypes.byref(self._h)) != 0:
-            msg = self._lib.clair_inflate_last_error(None).decode()
-            self._h = None
-            raise EngineError("clair_inflate_create failed: %s" % msg)
+        out = self._own(self._lib.clair_inflate_destroy, self._lib.clair_inflate_last_error)
+        self._check(self._lib.clair_inflate_create(int(device), int(max_blocks), out), "clair_inflate_create")
         self.max_blocks = int(max_blocks)
 
     @property
@@ -742,13 +671,6 @@ class Inflater(object):
     def callback(self):
         return ctypes.cast(self._lib.clair_inflate_blocks_cb, ctypes.c_void_p)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.clair_inflate_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
     def blocks(self, cdata, in_at, csize, out_at, out_len, out=None, cbytes=None):
         """-> (out, status): out is a uint8 array (given, or zeros up to the last output range)."""
         cdata = np.frombuffer(cdata, dtype=np.uint8) if not isinstance(cdata, np.ndarray) else cdata
@@ -758,10 +680,8 @@ class Inflater(object):
         if out is None:
             out = np.zeros(int((out_at + out_len).max()) if n else 0, dtype=np.uint8)
         status = np.full(n, -1, dtype=np.int32)
-        rc = self._lib.clair_inflate_blocks(self._h, _ptr(cdata), len(cdata) if cbytes is None else int(cbytes), n, _ptr(in_at), _ptr(csize), _ptr(out_at),
-                                            _ptr(out_len), _ptr(out), _ptr(status))
-        if rc != 0:
-            raise EngineError("clair_inflate_blocks failed: %s" % self._lib.clair_inflate_last_error(self._h).decode())
+        self._check(self._lib.clair_inflate_blocks(self._h, _ptr(cdata), len(cdata) if cbytes is None else int(cbytes), n, _ptr(in_at), _ptr(csize),
+                                                   _ptr(out_at), _ptr(out_len), _ptr(out), _ptr(status)), "clair_inflate_blocks")
         return out, status
 
 

@@ -6,22 +6,79 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libclair_host.so")
-SYMBOLS = ("clair_host_abi_version", "clair_host_last_error", "clair_host_threads", "clair_host_crc32c", "clair_host_parse_tensors",
-           "clair_host_counts_to_input_i16", "clair_host_counts_to_input_i32",
-           "clair_host_decode_rows", "clair_host_decode_rows_ex", "clair_host_resolve_calls", "clair_host_format_calls", "clair_host_format_calls_records", "clair_host_centre_bytes",
-           "clair_host_pileup_create", "clair_host_pileup_destroy", "clair_host_pileup_feed", "clair_host_pileup_finish",
-           "clair_host_pileup_pending", "clair_host_pileup_take", "clair_host_pileup_take_text", "clair_host_pileup_stats",
-           "clair_host_pileup_set_order", "clair_host_pyset_order",
-           "clair_host_evc_create", "clair_host_evc_destroy", "clair_host_evc_feed", "clair_host_evc_finish",
-           "clair_host_evc_pending", "clair_host_evc_reads", "clair_host_evc_take", "clair_host_evc_take_text",
-           "clair_host_sampack_create", "clair_host_sampack_destroy", "clair_host_sampack_feed", "clair_host_sampack_stats",
-           "clair_host_sampack_slab", "clair_host_sampack_reset", "clair_host_tuple_budget_binds",
-           "clair_host_bam_open", "clair_host_bam_close", "clair_host_bam_info", "clair_host_bam_ref", "clair_host_bam_tid", "clair_host_bam_query",
-           "clair_host_bam_next", "clair_host_bam_voffset", "clair_host_bam_render", "clair_host_faidx",
-           "clair_host_bam_set_inflater", "clair_host_inflate_block", "clair_host_inflate_bgzf",
-           "clair_host_sampack_set_lookup", "clair_host_indel_table",
-           "clair_host_ensemble_average", "clair_host_ensemble_quantise", "clair_host_ensemble_value",
-           "clair_host_overlap_keep")
+vp, cp, i32, i64, f64 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double
+p_vp, p_i32, p_i64 = ctypes.POINTER(vp), ctypes.POINTER(i32), ctypes.POINTER(i64)
+
+
+def _sig(*argtypes, **kw):
+    """One row of SIGNATURES: (restype, argtypes); a function returns int unless restype= says otherwise."""
+    return kw.get("restype", i32), list(argtypes)
+
+
+_DECODE_ROWS = (vp, vp, vp, vp, vp, cp, vp, i32, i32, i32, i32, i32, i32, vp, i64, p_i64, p_i32)
+_FEED = (vp, vp, i64, i32, p_i64)
+# every function include/clair_host.h declares, with its prototype there as ctypes states it (tests/test_host.py checks header <-> this table
+# <-> .so): the one place to add an entry point
+SIGNATURES = {
+    "clair_host_abi_version": _sig(),
+    "clair_host_last_error": _sig(restype=cp),
+    "clair_host_threads": _sig(i32),
+    "clair_host_crc32c": _sig(cp, i64, restype=ctypes.c_uint32),
+    "clair_host_counts_to_input_i16": _sig(vp, i64, vp),
+    "clair_host_counts_to_input_i32": _sig(vp, i64, vp),
+    "clair_host_parse_tensors": _sig(vp, i64, i32, i32, vp, vp, p_i32, p_i32, p_i64),
+    "clair_host_decode_rows": _sig(*_DECODE_ROWS),
+    "clair_host_decode_rows_ex": _sig(*_DECODE_ROWS + (vp,)),
+    "clair_host_resolve_calls": _sig(vp, vp, vp, vp, vp, vp, i32, vp),
+    "clair_host_format_calls": _sig(vp, cp, vp, i32, i32, i32, i32, i32, i32, vp, i64, p_i64, p_i32, vp),
+    "clair_host_centre_bytes": _sig(cp, vp, i32, vp),
+    "clair_host_format_calls_records": _sig(vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i64, p_i64, p_i32, vp),
+    "clair_host_pileup_create": _sig(cp, i64, i64, vp, i64, i32, i32, i32, i32, i64, i32, p_vp),
+    "clair_host_pileup_destroy": _sig(vp, restype=None),
+    "clair_host_pileup_set_order": _sig(vp, i32),
+    "clair_host_pyset_order": _sig(vp, i64, vp, i64, p_i64),
+    "clair_host_pileup_feed": _sig(*_FEED),
+    "clair_host_pileup_finish": _sig(vp),
+    "clair_host_pileup_pending": _sig(vp, restype=i64),
+    "clair_host_pileup_take": _sig(vp, i64, vp, vp, vp, p_i64),
+    "clair_host_pileup_take_text": _sig(vp, cp, vp, i64, p_i64, p_i64),
+    "clair_host_pileup_stats": _sig(vp, vp),
+    "clair_host_evc_create": _sig(cp, cp, i64, i64, i64, i64, vp, vp, i64, f64, f64, i32, p_vp),
+    "clair_host_evc_destroy": _sig(vp, restype=None),
+    "clair_host_evc_feed": _sig(*_FEED),
+    "clair_host_evc_finish": _sig(vp),
+    "clair_host_evc_pending": _sig(vp, restype=i64),
+    "clair_host_evc_reads": _sig(vp, restype=i64),
+    "clair_host_evc_take": _sig(vp, i64, vp, p_i64),
+    "clair_host_evc_take_text": _sig(vp, vp, i64, p_i64, p_i64),
+    "clair_host_sampack_create": _sig(cp, i32, i32, i32, i64, i64, p_vp),
+    "clair_host_sampack_destroy": _sig(vp, restype=None),
+    "clair_host_sampack_feed": _sig(*_FEED),
+    "clair_host_sampack_stats": _sig(vp, vp),
+    "clair_host_sampack_slab": _sig(vp, p_vp, p_vp, p_vp, p_vp),
+    "clair_host_sampack_reset": _sig(vp),
+    "clair_host_sampack_set_lookup": _sig(vp, i32),
+    "clair_host_indel_table": _sig(vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, i32, vp, vp, vp),
+    "clair_host_tuple_budget_binds": _sig(vp, vp, i64, vp, vp, i64, vp, p_i32),
+    "clair_host_bam_open": _sig(cp, i32, p_vp),
+    "clair_host_bam_close": _sig(vp, restype=None),
+    "clair_host_bam_info": _sig(vp, vp),
+    "clair_host_bam_ref": _sig(vp, i32, ctypes.POINTER(cp), p_i64),
+    "clair_host_bam_tid": _sig(vp, cp),
+    "clair_host_bam_query": _sig(vp, cp, i32, i64, i64),
+    "clair_host_bam_next": _sig(vp, vp, i64, vp, i64, p_i64, p_i64),
+    "clair_host_bam_voffset": _sig(vp, i64, ctypes.POINTER(ctypes.c_uint64)),
+    "clair_host_bam_render": _sig(vp, vp, vp, i64, i32, i64, i64, p_vp, p_i64),
+    "clair_host_faidx": _sig(cp, cp, i64, i64, vp, i64, p_i64),
+    "clair_host_bam_set_inflater": _sig(vp, vp, vp, i32),
+    "clair_host_inflate_block": _sig(vp, i64, vp, i64, p_i64, ctypes.POINTER(ctypes.c_uint32), p_i32),
+    "clair_host_inflate_bgzf": _sig(vp, i64, vp, p_i64, p_i32),
+    "clair_host_ensemble_average": _sig(vp, i32, i64, vp),
+    "clair_host_ensemble_quantise": _sig(vp, i64, vp),
+    "clair_host_ensemble_value": _sig(vp, i64, vp),
+    "clair_host_overlap_keep": _sig(vp, i64, vp),
+}
+SYMBOLS = tuple(SIGNATURES)
 N_VALUES = 1056
 _lib = None
 
@@ -32,80 +89,41 @@ def load():
         if not os.path.isfile(LIB_PATH):
             raise RuntimeError("%s not found: run `python -m clair_amd.build`" % LIB_PATH)
         lib = ctypes.CDLL(LIB_PATH)
-        vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-        lib.clair_host_abi_version.restype = i32
-        lib.clair_host_last_error.restype = ctypes.c_char_p
-        lib.clair_host_crc32c.restype = ctypes.c_uint32
-        lib.clair_host_crc32c.argtypes = [ctypes.c_char_p, i64]
-        lib.clair_host_parse_tensors.argtypes = [vp, i64, i32, i32, vp, vp, ctypes.POINTER(i32), ctypes.POINTER(i32),
-                                                 ctypes.POINTER(i64)]
-        lib.clair_host_decode_rows.argtypes = [vp, vp, vp, vp, vp, ctypes.c_char_p, vp, i32, i32, i32, i32, i32, i32, vp, i64,
-                                               ctypes.POINTER(i64), ctypes.POINTER(i32)]
-        lib.clair_host_decode_rows_ex.argtypes = lib.clair_host_decode_rows.argtypes + [vp]
-        lib.clair_host_resolve_calls.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp]
-        lib.clair_host_format_calls.argtypes = [vp, ctypes.c_char_p, vp, i32, i32, i32, i32, i32, i32, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i32), vp]
-        lib.clair_host_centre_bytes.argtypes = [ctypes.c_char_p, vp, i32, vp]
-        lib.clair_host_format_calls_records.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i64, ctypes.POINTER(i64),
-                                                        ctypes.POINTER(i32), vp]
-        lib.clair_host_pileup_create.argtypes = [ctypes.c_char_p, i64, i64, vp, i64, i32, i32, i32, i32, i64, i32, ctypes.POINTER(vp)]
-        lib.clair_host_pileup_destroy.argtypes = [vp]
-        lib.clair_host_pileup_destroy.restype = None
-        lib.clair_host_pileup_set_order.argtypes = [vp, i32]
-        lib.clair_host_pyset_order.argtypes = [vp, i64, vp, i64, ctypes.POINTER(i64)]
-        lib.clair_host_pileup_feed.argtypes = [vp, vp, i64, i32, ctypes.POINTER(i64)]
-        lib.clair_host_pileup_finish.argtypes = [vp]
-        lib.clair_host_pileup_pending.argtypes = [vp]
-        lib.clair_host_pileup_pending.restype = i64
-        lib.clair_host_pileup_take.argtypes = [vp, i64, vp, vp, vp, ctypes.POINTER(i64)]
-        lib.clair_host_pileup_take_text.argtypes = [vp, ctypes.c_char_p, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)]
-        lib.clair_host_pileup_stats.argtypes = [vp, vp]
-        lib.clair_host_evc_create.argtypes = [ctypes.c_char_p, ctypes.c_char_p, i64, i64, i64, i64, vp, vp, i64, ctypes.c_double,
-                                              ctypes.c_double, i32, ctypes.POINTER(vp)]
-        lib.clair_host_evc_destroy.argtypes = [vp]
-        lib.clair_host_evc_destroy.restype = None
-        lib.clair_host_evc_feed.argtypes = [vp, vp, i64, i32, ctypes.POINTER(i64)]
-        lib.clair_host_evc_finish.argtypes = [vp]
-        lib.clair_host_evc_pending.argtypes = [vp]
-        lib.clair_host_evc_pending.restype = i64
-        lib.clair_host_evc_reads.argtypes = [vp]
-        lib.clair_host_evc_reads.restype = i64
-        lib.clair_host_evc_take.argtypes = [vp, i64, vp, ctypes.POINTER(i64)]
-        lib.clair_host_evc_take_text.argtypes = [vp, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)]
-        lib.clair_host_counts_to_input_i16.argtypes = [vp, i64, vp]
-        lib.clair_host_counts_to_input_i32.argtypes = [vp, i64, vp]
-        lib.clair_host_sampack_create.argtypes = [ctypes.c_char_p, i32, i32, i32, i64, i64, ctypes.POINTER(vp)]
-        lib.clair_host_sampack_destroy.argtypes = [vp]
-        lib.clair_host_sampack_destroy.restype = None
-        lib.clair_host_sampack_feed.argtypes = [vp, vp, i64, i32, ctypes.POINTER(i64)]
-        lib.clair_host_sampack_stats.argtypes = [vp, vp]
-        lib.clair_host_sampack_slab.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]
-        lib.clair_host_sampack_reset.argtypes = [vp]
-        lib.clair_host_sampack_set_lookup.argtypes = [vp, i32]
-        lib.clair_host_indel_table.argtypes = [vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, i32, vp, vp, vp]
-        lib.clair_host_bam_open.argtypes = [ctypes.c_char_p, i32, ctypes.POINTER(vp)]
-        lib.clair_host_bam_close.argtypes = [vp]
-        lib.clair_host_bam_close.restype = None
-        lib.clair_host_bam_info.argtypes = [vp, vp]
-        lib.clair_host_bam_ref.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(i64)]
-        lib.clair_host_bam_tid.argtypes = [vp, ctypes.c_char_p]
-        lib.clair_host_bam_query.argtypes = [vp, ctypes.c_char_p, i32, i64, i64]
-        lib.clair_host_bam_next.argtypes = [vp, vp, i64, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)]
-        lib.clair_host_bam_voffset.argtypes = [vp, i64, ctypes.POINTER(ctypes.c_uint64)]
-        lib.clair_host_bam_render.argtypes = [vp, vp, vp, i64, i32, i64, i64, ctypes.POINTER(vp), ctypes.POINTER(i64)]
-        lib.clair_host_faidx.argtypes = [ctypes.c_char_p, ctypes.c_char_p, i64, i64, vp, i64, ctypes.POINTER(i64)]
-        lib.clair_host_bam_set_inflater.argtypes = [vp, vp, vp, i32]
-        lib.clair_host_inflate_block.argtypes = [vp, i64, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(i32)]
-        lib.clair_host_inflate_bgzf.argtypes = [vp, i64, vp, ctypes.POINTER(i64), ctypes.POINTER(i32)]
-        lib.clair_host_ensemble_average.argtypes = [vp, i32, i64, vp]
-        lib.clair_host_ensemble_quantise.argtypes = [vp, i64, vp]
-        lib.clair_host_ensemble_value.argtypes = [vp, i64, vp]
-        lib.clair_host_overlap_keep.argtypes = [vp, i64, vp]
-        lib.clair_host_tuple_budget_binds.argtypes = [vp, vp, i64, vp, vp, i64, vp, ctypes.POINTER(i32)]
+        for name, (restype, argtypes) in SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
         if lib.clair_host_abi_version() != 6:
             raise RuntimeError("libclair_host.so has ABI version %d, expected 6: run `python -m clair_amd.build`"
                                % lib.clair_host_abi_version())
         _lib = lib
     return _lib
+
+
+class Handle(object):
+    """One native handle and the two functions of its library that go with it.  A subclass calls _own() and hands what it returns to its create
+    function; close() may be repeated, __del__ never raises, _check() turns a non-zero return code into the subclass's exception."""
+    _h = None
+    _error = ValueError
+
+    def _own(self, destroy, last_error):
+        self._destroy, self._last_error = destroy, last_error
+        self._h = ctypes.c_void_p()
+        return ctypes.byref(self._h)
+
+    def _check(self, rc, what=""):
+        if rc != 0:
+            raise self._error(what + self._last_error().decode())
+
+    def close(self):
+        if self._h:
+            self._destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def crc32c(data):
@@ -329,7 +347,7 @@ def pyset_order(ops):
     return keys[:n.value].tolist()
 
 
-class _LineSink(object):
+class _LineSink(Handle):
     """A native consumer of `samtools view` text.  A subclass sets _lib, _h (its handle) and _feed (its clair_host_*_feed)."""
 
     def feed(self, sam, final=False):
@@ -374,23 +392,14 @@ class PileupBuilder(_LineSink):
         self.ctg = ctg_name
         ref = reference_sequence.encode("latin-1") if isinstance(reference_sequence, str) else bytes(reference_sequence)
         cands = np.ascontiguousarray(candidates, dtype=np.int64)
-        h = ctypes.c_void_p()
-        rc = self._lib.clair_host_pileup_create(ref, len(ref), int(reference_start_0_based), cands.ctypes.data, len(cands),
-                                                int(bool(consider_left_edge)), int(dcov), int(min_coverage), int(min_mq),
-                                                int(available_slots), int(bool(force_general_path)), ctypes.byref(h))
-        if rc != 0:
-            raise ValueError("pileup: " + self._lib.clair_host_last_error().decode())
-        self._h, self._feed = h, self._lib.clair_host_pileup_feed
+        out = self._own(self._lib.clair_host_pileup_destroy, self._lib.clair_host_last_error)
+        self._check(self._lib.clair_host_pileup_create(ref, len(ref), int(reference_start_0_based), cands.ctypes.data, len(cands),
+                                                       int(bool(consider_left_edge)), int(dcov), int(min_coverage), int(min_mq),
+                                                       int(available_slots), int(bool(force_general_path)), out), "pileup: ")
+        self._feed = self._lib.clair_host_pileup_feed
         self._text = None
-        if set_order == "cpython" and self._lib.clair_host_pileup_set_order(self._h, 1) != 0:
-            raise ValueError("pileup: " + self._lib.clair_host_last_error().decode())
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.clair_host_pileup_destroy(self._h)
-            self._h = None
-
-    __del__ = close
+        if set_order == "cpython":
+            self._check(self._lib.clair_host_pileup_set_order(self._h, 1), "pileup: ")
 
     def finish(self):
         self._lib.clair_host_pileup_finish(self._h)
@@ -455,22 +464,13 @@ class CandidateFinder(_LineSink):
             bs = np.ascontiguousarray([b[0] for b in bed], dtype=np.int64)
             be = np.ascontiguousarray([b[1] for b in bed], dtype=np.int64)
             n_bed = len(bs)
-        h = ctypes.c_void_p()
-        rc = self._lib.clair_host_evc_create(ctg_name.encode(), ref, len(ref), int(reference_start_0_based),
-                                             int(ctg_start) if have_range else -1, int(ctg_end) if have_range else -1,
-                                             bs.ctypes.data, be.ctypes.data, n_bed, float(min_coverage), float(threshold),
-                                             int(min_mq), ctypes.byref(h))
-        if rc != 0:
-            raise ValueError("candidates: " + self._lib.clair_host_last_error().decode())
-        self._h, self._feed = h, self._lib.clair_host_evc_feed
+        out = self._own(self._lib.clair_host_evc_destroy, self._lib.clair_host_last_error)
+        self._check(self._lib.clair_host_evc_create(ctg_name.encode(), ref, len(ref), int(reference_start_0_based),
+                                                    int(ctg_start) if have_range else -1, int(ctg_end) if have_range else -1,
+                                                    bs.ctypes.data, be.ctypes.data, n_bed, float(min_coverage), float(threshold),
+                                                    int(min_mq), out), "candidates: ")
+        self._feed = self._lib.clair_host_evc_feed
         self._text = None
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.clair_host_evc_destroy(self._h)
-            self._h = None
-
-    __del__ = close
 
     @property
     def reads(self):
@@ -517,20 +517,12 @@ class SamPacker(_LineSink):
     def __init__(self, ctg_name, dcov=250, evc_min_mq=0, pile_min_mq=0, pile_region=None, lookup=False):
         """lookup: pack for the indel look-up too (clair_host_sampack_set_lookup): alignments neither stage walks stay, marked READ_LOOKUP."""
         self._lib = load()
-        h = ctypes.c_void_p()
         a, b = (-1, -1) if pile_region is None else (int(pile_region[0]), int(pile_region[1]))
-        if self._lib.clair_host_sampack_create(ctg_name.encode(), int(dcov), int(evc_min_mq), int(pile_min_mq), a, b, ctypes.byref(h)) != 0:
-            raise ValueError("sampack: " + self._lib.clair_host_last_error().decode())
-        self._h, self._feed = h, self._lib.clair_host_sampack_feed
-        if lookup and self._lib.clair_host_sampack_set_lookup(self._h, 1) != 0:
-            raise ValueError("sampack: " + self._lib.clair_host_last_error().decode())
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.clair_host_sampack_destroy(self._h)
-            self._h = None
-
-    __del__ = close
+        out = self._own(self._lib.clair_host_sampack_destroy, self._lib.clair_host_last_error)
+        self._check(self._lib.clair_host_sampack_create(ctg_name.encode(), int(dcov), int(evc_min_mq), int(pile_min_mq), a, b, out), "sampack: ")
+        self._feed = self._lib.clair_host_sampack_feed
+        if lookup:
+            self._check(self._lib.clair_host_sampack_set_lookup(self._h, 1), "sampack: ")
 
     def stats(self):
         v = (ctypes.c_int64 * 8)()
@@ -629,7 +621,7 @@ def bam_index_for(bam_fn):
     return None, None
 
 
-class BamReader(object):
+class BamReader(Handle):
     """clair_host_bam_*: the records of one contig / region of a BAM, read without samtools (callVarBam --bam_reader native).
 
         r = BamReader(path, threads=4)                   # inflate="device", device=0: BGZF blocks inflated on the GPU (callVarBam --bam_inflate)
@@ -639,6 +631,8 @@ class BamReader(object):
 
     The records readinto() hands out are all those the index yields for the region; the view filter is the consumer's (the device's
     clair_frontend_add_bam or render())."""
+    _error = BamError
+    _inflater = None
 
     def __init__(self, path, threads=4, inflate="host", device=0):
         self._lib = load()
@@ -646,10 +640,9 @@ class BamReader(object):
             raise BamError("--bam_threads %d: 1 .. 16" % threads)
         if inflate not in ("host", "device"):
             raise BamError("--bam_inflate %s: host or device" % inflate)
-        h = ctypes.c_void_p()
-        if self._lib.clair_host_bam_open(path.encode(), int(threads), ctypes.byref(h)) != 0:
-            raise BamError(self._lib.clair_host_last_error().decode())
-        self._h, self.path = h, path
+        out = self._own(self._lib.clair_host_bam_close, self._lib.clair_host_last_error)
+        self._check(self._lib.clair_host_bam_open(path.encode(), int(threads), out))
+        self.path = path
         self.tid, self.region, self.used_index = -1, (-1, -1), False
         self._inflater = self._hook = None
         if inflate == "device":                  # only a function pointer and its context pass between the two libraries
@@ -664,18 +657,13 @@ class BamReader(object):
     def set_inflater(self, fn, ctx=None, batch_blocks=INFLATE_BATCH):
         """clair_host_bam_set_inflater: fn is a function pointer (an INFLATE_FN instance or an address), None = zlib again."""
         self._hook = fn                          # keeps a Python callback alive
-        if self._lib.clair_host_bam_set_inflater(self._h, ctypes.cast(fn, ctypes.c_void_p) if fn is not None else None, ctx, int(batch_blocks)) != 0:
-            raise BamError(self._lib.clair_host_last_error().decode())
+        self._check(self._lib.clair_host_bam_set_inflater(self._h, ctypes.cast(fn, ctypes.c_void_p) if fn is not None else None, ctx, int(batch_blocks)))
 
     def close(self):
-        if getattr(self, "_h", None):
-            self._lib.clair_host_bam_close(self._h)
-            self._h = None
-        if getattr(self, "_inflater", None):
+        Handle.close(self)
+        if self._inflater:
             self._inflater.close()
             self._inflater = None
-
-    __del__ = close
 
     def info(self):
         v = (ctypes.c_int64 * 4)()
@@ -703,8 +691,7 @@ class BamReader(object):
                 raise BamError("%s has only a .csi index, which the native reader does not read: use --bam_reader samtools" % self.path)
         self.tid = tid
         self.region = (-1, -1) if beg1 is None or end1 is None else (int(beg1), int(end1))
-        if self._lib.clair_host_bam_query(self._h, None if index is None else index.encode(), tid, self.region[0], self.region[1]) != 0:
-            raise BamError(self._lib.clair_host_last_error().decode())
+        self._check(self._lib.clair_host_bam_query(self._h, None if index is None else index.encode(), tid, self.region[0], self.region[1]))
         self.used_index = index is not None
         return self.used_index
 
@@ -713,23 +700,20 @@ class BamReader(object):
         (bytes, records); (0, 0) when the query is exhausted."""
         cap = len(buf) if cap is None else int(cap)
         n_bytes, n_rec = ctypes.c_int64(0), ctypes.c_int64(0)
-        if self._lib.clair_host_bam_next(self._h, buf.ctypes.data, cap, offsets.ctypes.data, len(offsets), ctypes.byref(n_bytes), ctypes.byref(n_rec)) != 0:
-            raise BamError(self._lib.clair_host_last_error().decode())
+        self._check(self._lib.clair_host_bam_next(self._h, buf.ctypes.data, cap, offsets.ctypes.data, len(offsets), ctypes.byref(n_bytes), ctypes.byref(n_rec)))
         return int(n_bytes.value), int(n_rec.value)
 
     def voffset(self, k):
         """BGZF virtual offset of record k of the last chunk readinto() handed out."""
         v = ctypes.c_uint64(0)
-        if self._lib.clair_host_bam_voffset(self._h, int(k), ctypes.byref(v)) != 0:
-            raise BamError(self._lib.clair_host_last_error().decode())
+        self._check(self._lib.clair_host_bam_voffset(self._h, int(k), ctypes.byref(v)))
         return int(v.value)
 
     def render(self, buf, offsets, n_records):
         """The lines `samtools view -F 2316` prints for those of the n_records records that are on the queried contig and overlap the region."""
         text, n = ctypes.c_void_p(), ctypes.c_int64(0)
-        if self._lib.clair_host_bam_render(self._h, buf.ctypes.data, offsets.ctypes.data, int(n_records), self.tid, self.region[0], self.region[1],
-                                           ctypes.byref(text), ctypes.byref(n)) != 0:
-            raise BamError(self._lib.clair_host_last_error().decode())
+        self._check(self._lib.clair_host_bam_render(self._h, buf.ctypes.data, offsets.ctypes.data, int(n_records), self.tid, self.region[0], self.region[1],
+                                                    ctypes.byref(text), ctypes.byref(n)))
         return ctypes.string_at(text.value, n.value) if n.value else b""
 
 

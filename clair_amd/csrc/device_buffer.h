@@ -1,4 +1,4 @@
-// Allocations that are freed with their owner: what the handles of engine.hip and frontend.hip hold.  Host side only; kernels take
+// Allocations that are freed with their owner: what the handles of engine.hip, frontend.hip and inflate.hip hold.  Host side only; kernels take
 // plain pointers (as<T>()).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #define CLAIR_INF_FN __device__ inline
+#include "device_buffer.h"
 #include "inflate_core.h"
 
 namespace clair_inf {
@@ -159,8 +160,8 @@ struct clair_inflate {
     int max_blocks = 0;
     int64_t cap = 0;                             // bytes of each data buffer: max_blocks * BLOCK_MAX
     hipStream_t stream = nullptr;
-    uint8_t *h_in = nullptr, *h_out = nullptr, *h_meta = nullptr;      // page-locked
-    uint8_t *d_in = nullptr, *d_out = nullptr, *d_meta = nullptr;
+    PinnedBuffer h_in, h_out, h_meta;
+    DeviceBuffer d_in, d_out, d_meta;
     std::string error;
 };
 
@@ -190,13 +191,13 @@ int inflate_init(clair_inflate *h) {
     INF_TRY(nullptr, hipSetDevice(h->device));
     INF_TRY(nullptr, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     const size_t meta = (size_t)h->max_blocks * META_PER_BLOCK;
-    INF_TRY(nullptr, hipHostMalloc((void **)&h->h_in, (size_t)h->cap, hipHostMallocDefault));
-    INF_TRY(nullptr, hipHostMalloc((void **)&h->h_out, (size_t)h->cap, hipHostMallocDefault));
-    INF_TRY(nullptr, hipHostMalloc((void **)&h->h_meta, meta, hipHostMallocDefault));
-    INF_TRY(nullptr, hipMalloc((void **)&h->d_in, (size_t)h->cap + 32));      // the kernel reads whole 16-byte pieces around each stream
-    INF_TRY(nullptr, hipMalloc((void **)&h->d_out, (size_t)h->cap));
-    INF_TRY(nullptr, hipMalloc((void **)&h->d_meta, meta));
-    INF_TRY(nullptr, hipMemset(h->d_in, 0, (size_t)h->cap + 32));
+    INF_TRY(nullptr, h->h_in.ensure((size_t)h->cap));
+    INF_TRY(nullptr, h->h_out.ensure((size_t)h->cap));
+    INF_TRY(nullptr, h->h_meta.ensure(meta));
+    INF_TRY(nullptr, h->d_in.ensure((size_t)h->cap + 32));      // the kernel reads whole 16-byte pieces around each stream
+    INF_TRY(nullptr, h->d_out.ensure((size_t)h->cap));
+    INF_TRY(nullptr, h->d_meta.ensure(meta));
+    INF_TRY(nullptr, hipMemset(h->d_in.p, 0, (size_t)h->cap + 32));
     return 0;
 }
 
@@ -230,12 +231,8 @@ void clair_inflate_destroy(clair_inflate_t *h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->d_in) (void)hipFree(h->d_in);
-    if (h->d_out) (void)hipFree(h->d_out);
-    if (h->d_meta) (void)hipFree(h->d_meta);
-    if (h->h_in) (void)hipHostFree(h->h_in);
-    if (h->h_out) (void)hipHostFree(h->h_out);
-    if (h->h_meta) (void)hipHostFree(h->h_meta);
+    for (DeviceBuffer *b : {&h->d_in, &h->d_out, &h->d_meta}) b->reset();     // before the stream goes, not in ~clair_inflate
+    for (PinnedBuffer *b : {&h->h_in, &h->h_out, &h->h_meta}) b->reset();
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -258,28 +255,28 @@ int clair_inflate_blocks(clair_inflate_t *h, const uint8_t *cdata, int64_t cbyte
     }
     INF_TRY(h, hipSetDevice(h->device));
     const size_t N = (size_t)h->max_blocks;
-    int64_t *m_in_at = (int64_t *)h->h_meta, *m_out_at = m_in_at + N;
+    int64_t *m_in_at = h->h_meta.as<int64_t>(), *m_out_at = m_in_at + N;
     int32_t *m_csize = (int32_t *)(m_out_at + N), *m_out_len = m_csize + N, *m_status = m_out_len + N;
-    memcpy(h->h_in, cdata, (size_t)cbytes);
+    uint8_t *h_in = h->h_in.as<uint8_t>(), *h_out = h->h_out.as<uint8_t>(), *d_in = h->d_in.as<uint8_t>(), *d_out = h->d_out.as<uint8_t>();
+    memcpy(h_in, cdata, (size_t)cbytes);
     memcpy(m_in_at, in_at, (size_t)n * 8);
     memcpy(m_out_at, out_at, (size_t)n * 8);
     memcpy(m_csize, csize, (size_t)n * 4);
     memcpy(m_out_len, out_len, (size_t)n * 4);
-    uint8_t *dm = h->d_meta;
-    const int64_t *d_in_at = (const int64_t *)dm, *d_out_at = d_in_at + N;
+    const int64_t *d_in_at = h->d_meta.as<int64_t>(), *d_out_at = d_in_at + N;
     const int32_t *d_csize = (const int32_t *)(d_out_at + N), *d_out_len = d_csize + N;
     int32_t *d_status = (int32_t *)(d_out_len + N);
-    INF_TRY(h, hipMemcpyAsync(h->d_in, h->h_in, (size_t)cbytes, hipMemcpyHostToDevice, h->stream));
-    INF_TRY(h, hipMemcpyAsync(h->d_meta, h->h_meta, N * (2 * 8 + 2 * 4), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(clair_inf::inflate_bgzf_kernel, dim3((unsigned)n), dim3(64), 0, h->stream, (const uint8_t *)h->d_in, n, d_in_at, d_csize, d_out_at,
-                       d_out_len, h->d_out, d_status);
+    INF_TRY(h, hipMemcpyAsync(d_in, h_in, (size_t)cbytes, hipMemcpyHostToDevice, h->stream));
+    INF_TRY(h, hipMemcpyAsync(h->d_meta.p, h->h_meta.p, N * (2 * 8 + 2 * 4), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(clair_inf::inflate_bgzf_kernel, dim3((unsigned)n), dim3(64), 0, h->stream, (const uint8_t *)d_in, n, d_in_at, d_csize, d_out_at,
+                       d_out_len, d_out, d_status);
     INF_TRY(h, hipGetLastError());
-    if (out_hi > out_lo) INF_TRY(h, hipMemcpyAsync(h->h_out + out_lo, h->d_out + out_lo, (size_t)(out_hi - out_lo), hipMemcpyDeviceToHost, h->stream));
+    if (out_hi > out_lo) INF_TRY(h, hipMemcpyAsync(h_out + out_lo, d_out + out_lo, (size_t)(out_hi - out_lo), hipMemcpyDeviceToHost, h->stream));
     INF_TRY(h, hipMemcpyAsync(m_status, d_status, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
     INF_TRY(h, hipStreamSynchronize(h->stream));
     for (int i = 0; i < n; ++i) {
         status[i] = m_status[i];
-        if (m_status[i] == 0 && out_len[i]) memcpy(out + out_at[i], h->h_out + out_at[i], (size_t)out_len[i]);
+        if (m_status[i] == 0 && out_len[i]) memcpy(out + out_at[i], h_out + out_at[i], (size_t)out_len[i]);
     }
     return 0;
 }

@@ -4,6 +4,7 @@ import gzip
 import io
 import os
 import re
+import sys
 from contextlib import redirect_stderr
 
 import numpy as np
@@ -12,6 +13,8 @@ import pytest
 from clair_amd import _hostapi, synth, utils
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from test_abi import check_table_against_header, header_prototypes  # noqa: E402
 
 
 def test_host_header_symbols_are_exported():
@@ -22,6 +25,12 @@ def test_host_header_symbols_are_exported():
     for name in declared:
         assert hasattr(lib, name)
     assert lib.clair_host_abi_version() == 6
+
+
+def test_host_signature_table_matches_header():
+    protos = header_prototypes(os.path.join(ROOT, "include", "clair_host.h"), pointer_typedefs=("clair_host_inflate_fn",))
+    check_table_against_header(_hostapi.SIGNATURES, protos)
+    assert _hostapi.SYMBOLS == tuple(_hostapi.SIGNATURES)
 
 
 def _collect(gen, path, batch):
