@@ -53,6 +53,16 @@ SIGNATURES = {
     "clair_ensemble_finalize_weights": _sig(c_vp, c_int),
     "clair_submit_ensemble": _sig(*_SUBMIT_EX),
     "clair_ensemble_average": _sig(c_vp, c_int, c_vp, c_int, c_int, c_vp),
+    "clair_sites_create": _sig(c_vp, p_vp),
+    "clair_sites_destroy": _sig(c_vp, restype=None),
+    "clair_sites_begin_source": _sig(c_vp, c_vp, c_i64, p_i64),
+    "clair_submit_sites": _sig(c_vp, c_int, c_vp, c_i64, c_vp, c_int, c_i64, c_int, c_vp, c_vp),
+    "clair_sites_add_rows": _sig(c_vp, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_vp),
+    "clair_sites_finish": _sig(c_vp, c_int, c_int, p_i64),
+    "clair_sites_info": _sig(c_vp, c_i64, c_i64, c_vp, c_vp, c_vp),
+    "clair_sites_rows": _sig(c_vp, c_i64, c_i64, c_vp),
+    "clair_sites_windows": _sig(c_vp, c_i64, c_i64, c_vp),
+    "clair_submit_site_calls": _sig(c_vp, c_int, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp),
     "clair_dataset_alloc": _sig(c_vp, c_i64, p_vp, p_vp),
     "clair_dataset_free": _sig(c_vp, c_vp, c_vp),
     "clair_dataset_upload": _sig(c_vp, c_vp, c_i64, c_vp, c_i64),
@@ -193,6 +203,15 @@ class Engine(DeviceHandle):
         self._check(self._lib.clair_engine_create(int(device), int(max_batch), int(n_slots), out), "clair_engine_create")
         self._pending = {}
         self.n_models = 1
+        self._tables = []                   # weak references to the site tables of this handle: they go before it does
+
+    def close(self):
+        for ref in getattr(self, "_tables", []):
+            table = ref()
+            if table is not None:
+                table.close()
+        self._tables = []
+        DeviceHandle.close(self)
 
     # -- weights ---------------------------------------------------------------------------
     def load_weights(self, w):
@@ -293,6 +312,37 @@ class Engine(DeviceHandle):
         out = np.empty(p.shape[1:], dtype=np.float32)
         self._check(self._lib.clair_ensemble_average(self._h, int(slot), _ptr(p), p.shape[0], p.shape[1], _ptr(out)), "clair_ensemble_average")
         return out
+
+    # -- ensemble across BAMs (include/clair_amd.h: clair_sites_*) --------------------------------------
+    def site_table(self):
+        """clair_sites_create: a SiteTable of this handle."""
+        import weakref
+        table = SiteTable(self)
+        self._tables.append(weakref.ref(table))
+        return table
+
+    def submit_sites(self, slot, table, first, batch, centre, seq, counts=False):
+        """clair_submit_sites: every checkpoint of the handle over the batch (as submit_calls takes it), folded into `table` as candidates
+        [first, first + n) of its current source; centre uint8 [n,2], seq uint8 [n,33] / [n,34].  wait(slot) returns None."""
+        from clair_amd._hostapi import site_seq_bytes
+        keep, ptr, is_counts, stride, n = prepare_batch(batch, counts)
+        c = np.ascontiguousarray(centre, dtype=np.uint8)
+        q = site_seq_bytes(seq)
+        if c.shape != (n, 2) or q.shape != (n, 33):
+            raise ValueError("centre must be uint8 [%d,2] and seq uint8 [%d,33], got %r and %r" % (n, n, c.shape, q.shape))
+        self._check(self._lib.clair_submit_sites(self._h, int(slot), table._h, int(first), ptr, is_counts, stride, n, _ptr(c), _ptr(q)), "clair_submit_sites")
+        self._pending[slot] = ((keep, c, q, table), None)
+
+    def submit_site_calls(self, slot, table, first, n, with_calls=True, with_probabilities=False):
+        """clair_submit_site_calls: the decode of entries [first, first + n) of the table's output list.  wait(slot) returns what it returns
+        after submit_ensemble: the call records, (records, [gt21, genotype, len1, len2]), or the four arrays alone with with_calls=False."""
+        from clair_amd._hostapi import CALL_DTYPE
+        calls = np.zeros(n, dtype=CALL_DTYPE) if with_calls else None
+        outs = self._alloc_out(n) if with_probabilities or calls is None else None
+        ptrs = [_ptr(o) for o in outs] if outs else [None] * 4
+        self._check(self._lib.clair_submit_site_calls(self._h, int(slot), table._h, int(first), int(n), _ptr(calls) if calls is not None else None, *ptrs),
+                    "clair_submit_site_calls")
+        self._pending[slot] = ((table,), outs if calls is None else ((calls, outs) if outs else calls))
 
     def pinned_buffer(self, nbytes):
         """A page-locked uint8 array of nbytes (clair_pinned_alloc): data placed in it -- e.g. read from a file with readinto -- goes to
@@ -424,6 +474,61 @@ class Engine(DeviceHandle):
         out = np.empty(shape, dtype=np.float32)
         self._check(self._lib.clair_debug_read(self._h, int(slot), int(which), _ptr(out), out.size), "clair_debug_read")
         return out
+
+
+class SiteTable(DeviceHandle):
+    """clair_sites_*: the site table of ensemble calling across BAMs, in device memory (csrc/sites.hip.h; docs/ensemble.md).  Made by
+    Engine.site_table(); its errors are the engine's.  Same methods as clair_amd._hostapi.HostSiteTable, its CPU twin; the batches of a run
+    go in through Engine.submit_sites, the decode of the output list comes out of Engine.submit_site_calls."""
+
+    def __init__(self, engine):
+        self._lib = engine._lib
+        self._engine = engine
+        out = self._own(self._lib.clair_sites_destroy, self._lib.clair_last_error)
+        engine._check(self._lib.clair_sites_create(engine._h, out), "clair_sites_create")
+        self.n_out = 0
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise EngineError("%s failed: %s" % (what, self._last_error(self._engine._h).decode()))
+
+    def begin_source(self, positions):
+        """-> how many of the positions (int64, strictly ascending) the table did not have"""
+        p = np.ascontiguousarray(positions, dtype=np.int64)
+        n_new = ctypes.c_int64(0)
+        self._check(self._lib.clair_sites_begin_source(self._h, _ptr(p), len(p), ctypes.byref(n_new)), "clair_sites_begin_source")
+        return int(n_new.value)
+
+    def add_rows(self, first, probs, x=None, centre=None, seq=None):
+        """clair_sites_add_rows: one run's packed rows [n,90] for candidates [first, first + n) of the current source (n <= max_batch)."""
+        from clair_amd._hostapi import site_rows_arguments
+        n = len(probs)
+        p, x, centre, seq = site_rows_arguments(n, probs, x, centre, seq)
+        self._check(self._lib.clair_sites_add_rows(self._engine._h, self._h, int(first), _ptr(p), n, *[_ptr(a) if a is not None else None for a in (x, centre, seq)]),
+                    "clair_sites_add_rows")
+
+    def finish(self, min_count=0, order="chain"):
+        from clair_amd._hostapi import SITE_ORDERS
+        n_out = ctypes.c_int64(0)
+        self._check(self._lib.clair_sites_finish(self._h, int(min_count), SITE_ORDERS.index(order), ctypes.byref(n_out)), "clair_sites_finish")
+        self.n_out = int(n_out.value)
+        return self.n_out
+
+    def info(self, first, n):
+        """-> (positions int64 [n], counts int32 [n], seq uint8 [n,34] NUL-terminated) of entries [first, first + n) of the output list"""
+        positions, counts, seq = np.empty(n, np.int64), np.empty(n, np.int32), np.zeros((n, 33), np.uint8)
+        self._check(self._lib.clair_sites_info(self._h, int(first), int(n), _ptr(positions), _ptr(counts), _ptr(seq)), "clair_sites_info")
+        return positions, counts, np.concatenate([seq, np.zeros((n, 1), np.uint8)], axis=1)
+
+    def rows(self, first, n):
+        out = np.empty((n, 90), dtype=np.float32)
+        self._check(self._lib.clair_sites_rows(self._h, int(first), int(n), _ptr(out)), "clair_sites_rows")
+        return out
+
+    def windows(self, first, n):
+        x = np.empty((n, 33, 8, 4), dtype=np.float32)
+        self._check(self._lib.clair_sites_windows(self._h, int(first), int(n), _ptr(x)), "clair_sites_windows")
+        return x
 
 
 def split_outputs(packed):

@@ -77,6 +77,14 @@ SIGNATURES = {
     "clair_host_ensemble_quantise": _sig(vp, i64, vp),
     "clair_host_ensemble_value": _sig(vp, i64, vp),
     "clair_host_overlap_keep": _sig(vp, i64, vp),
+    "clair_host_sites_create": _sig(p_vp),
+    "clair_host_sites_destroy": _sig(vp, restype=None),
+    "clair_host_sites_begin_source": _sig(vp, vp, i64, p_i64),
+    "clair_host_sites_add_rows": _sig(vp, i64, vp, i64, vp, vp, vp),
+    "clair_host_sites_finish": _sig(vp, i32, i32, p_i64),
+    "clair_host_sites_info": _sig(vp, i64, i64, vp, vp, vp),
+    "clair_host_sites_rows": _sig(vp, i64, i64, vp),
+    "clair_host_sites_windows": _sig(vp, i64, i64, vp),
 }
 SYMBOLS = tuple(SIGNATURES)
 N_VALUES = 1056
@@ -803,6 +811,90 @@ def ensemble_value(millionths):
     if load().clair_host_ensemble_value(m.ctypes.data, m.size, out.ctypes.data) != 0:
         raise ValueError(load().clair_host_last_error().decode())
     return out
+
+
+SITE_ORDERS = ("chain", "position")                          # CLAIR_SITES_ORDER_CHAIN, CLAIR_SITES_ORDER_POSITION (include/clair_amd.h)
+
+
+def site_rows_arguments(n, probs, x, centre, seq):
+    """What the add_rows of either site table takes for n candidates -> (probs [n,90], x [n,1056] or None, centre [n,2] or None, seq [n,33] or
+    None), contiguous; seq may be uint8 [n,33] / [n,34] (NUL-padded) or a list of str."""
+    p = np.ascontiguousarray(probs, dtype=np.float32)
+    if p.shape != (n, 90):
+        raise ValueError("probs must be float32 [%d,90], got %r" % (n, p.shape))
+    if x is not None:
+        x = np.ascontiguousarray(x, dtype=np.float32).reshape(len(x), -1)
+        if x.shape != (n, N_VALUES):
+            raise ValueError("x must hold %d windows of 1056 floats, got %r" % (n, x.shape))
+    if centre is not None:
+        centre = np.ascontiguousarray(centre, dtype=np.uint8)
+        if centre.shape != (n, 2):
+            raise ValueError("centre must be uint8 [%d,2], got %r" % (n, centre.shape))
+    if seq is not None:
+        seq = site_seq_bytes(seq)
+        if seq.shape != (n, 33):
+            raise ValueError("seq must hold %d reference windows, got %r" % (n, seq.shape))
+    return p, x, centre, seq
+
+
+def site_seq_bytes(seq):
+    """Reference windows as the site tables keep them: uint8 [n,33], NUL-padded (from [n,33], [n,34] or a list of str)."""
+    if isinstance(seq, np.ndarray) and seq.dtype == np.uint8 and seq.ndim == 2 and seq.shape[1] in (33, 34):
+        return np.ascontiguousarray(seq[:, :33])
+    out = np.zeros((len(seq), 33), dtype=np.uint8)
+    for i, text in enumerate(seq):
+        raw = (text.encode("latin-1") if isinstance(text, str) else bytes(text))[:33]
+        out[i, :len(raw)] = np.frombuffer(raw, dtype=np.uint8)
+    return out
+
+
+class HostSiteTable(Handle):
+    """clair_host_sites_*: the site table of ensemble calling across BAMs on the CPU, the twin of clair_amd._capi.SiteTable (same methods, same
+    bits).
+
+        t = HostSiteTable()
+        for each source:  t.begin_source(positions);  for each run:  t.add_rows(first, probs, x, centre, seq)
+        n_out = t.finish(min_count, "chain");  t.info(0, n_out), t.rows(0, n_out), t.windows(0, n_out)"""
+
+    def __init__(self):
+        self._lib = load()
+        out = self._own(self._lib.clair_host_sites_destroy, self._lib.clair_host_last_error)
+        self._check(self._lib.clair_host_sites_create(out))
+        self.n_out = 0
+
+    def begin_source(self, positions):
+        """-> how many of the positions (int64, strictly ascending) the table did not have"""
+        p = np.ascontiguousarray(positions, dtype=np.int64)
+        n_new = i64(0)
+        self._check(self._lib.clair_host_sites_begin_source(self._h, p.ctypes.data, len(p), ctypes.byref(n_new)))
+        return int(n_new.value)
+
+    def add_rows(self, first, probs, x=None, centre=None, seq=None):
+        n = len(probs)
+        p, x, centre, seq = site_rows_arguments(n, probs, x, centre, seq)
+        self._check(self._lib.clair_host_sites_add_rows(self._h, int(first), p.ctypes.data, n, *[a.ctypes.data if a is not None else None for a in (x, centre, seq)]))
+
+    def finish(self, min_count=0, order="chain"):
+        n_out = i64(0)
+        self._check(self._lib.clair_host_sites_finish(self._h, int(min_count), SITE_ORDERS.index(order), ctypes.byref(n_out)))
+        self.n_out = int(n_out.value)
+        return self.n_out
+
+    def info(self, first, n):
+        """-> (positions int64 [n], counts int32 [n], seq uint8 [n,34] NUL-terminated) of entries [first, first + n) of the output list"""
+        positions, counts, seq = np.empty(n, np.int64), np.empty(n, np.int32), np.zeros((n, 33), np.uint8)
+        self._check(self._lib.clair_host_sites_info(self._h, int(first), int(n), positions.ctypes.data, counts.ctypes.data, seq.ctypes.data))
+        return positions, counts, np.concatenate([seq, np.zeros((n, 1), np.uint8)], axis=1)
+
+    def rows(self, first, n):
+        out = np.empty((n, 90), dtype=np.float32)
+        self._check(self._lib.clair_host_sites_rows(self._h, int(first), int(n), out.ctypes.data))
+        return out
+
+    def windows(self, first, n):
+        x = np.empty((n, 33, 8, 4), dtype=np.float32)
+        self._check(self._lib.clair_host_sites_windows(self._h, int(first), int(n), x.ctypes.data))
+        return x
 
 
 # clair_overlap_span (clair_amd/csrc/overlap_core.h): one VCF row as the overlap filter sees it; flags bit 0 = OVERLAP_SNP

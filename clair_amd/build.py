@@ -36,7 +36,7 @@ def needs_build():
 
 
 HOST_SRCS = [os.path.join(HERE, "hostsrc", f) for f in ("host_io.cpp", "host_decode.cpp", "host_pileup.cpp", "host_sampack.cpp",
-                                                              "host_bam.cpp", "host_inflate.cpp", "host_indel.cpp", "host_ensemble.cpp", "host_overlap.cpp")]
+                                                              "host_bam.cpp", "host_inflate.cpp", "host_indel.cpp", "host_ensemble.cpp", "host_overlap.cpp", "host_sites.cpp")]
 HOST_OUT = os.path.join(HERE, "libclair_host.so")
 CXX = os.environ.get("CXX", "g++")
 

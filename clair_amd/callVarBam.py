@@ -743,6 +743,7 @@ def normalise(args):
             sys.exit("[ERROR] --bam_threads %d: 1 .. 16" % args.bam_threads)
     cv.check_ensemble_flags(args)
     cv.check_overlap_flags(args)
+    check_site_flags(args)
     if native_lookup(args):
         if not native_input(args):
             sys.exit("[ERROR] --indel_lookup native answers from the alignments the native reader feeds the device front end: add --bam_reader native")
@@ -750,6 +751,33 @@ def normalise(args):
             sys.exit("[ERROR] --indel_lookup native answers from the alignments resident on the GPU: it needs the device front end "
                      "(drop --front_end host / --front_end_workers)")
     return args
+
+
+MAX_ENSEMBLE_BAMS = 7      # --ensemble_bam_fn: CLAIR_SITES_MAX_BAMS less --bam_fn
+
+
+def check_site_flags(args):
+    """--ensemble_bam_fn replaces the text chain over several BAMs; what only makes sense with it, and what cannot go with it."""
+    more = getattr(args, "ensemble_bam_fn", None) or []
+    if not more:
+        if getattr(args, "minimum_count_to_output", 0):
+            sys.exit("[ERROR] --minimum_count_to_output counts the (BAM, checkpoint) runs of a site across --ensemble_bam_fn BAMs: give --ensemble_bam_fn as well")
+        return
+    if len(more) > MAX_ENSEMBLE_BAMS:
+        sys.exit("[ERROR] --ensemble_bam_fn: %d BAMs, at most %d" % (len(more), MAX_ENSEMBLE_BAMS))
+    if args.output_for_ensemble:
+        sys.exit("[ERROR] --ensemble_bam_fn merges and averages the BAMs' sites in this process; --output_for_ensemble writes one run's "
+                 "probabilities for the `ensemble` submodule to average: use one of the two")
+    if args.minimum_count_to_output < 0:
+        sys.exit("[ERROR] --minimum_count_to_output %d: 0 or more" % args.minimum_count_to_output)
+    if getattr(args, "overlap_filter", "off") != "off" and args.ensemble_order != "position":
+        sys.exit("[ERROR] --overlap_filter walks rows sorted by position; --ensemble_bam_fn writes them in the text chain's order unless "
+                 "--ensemble_order position is given: add it")
+    if (args.front_end_workers or 1) != 1:
+        sys.exit("[ERROR] --ensemble_bam_fn runs every BAM through the device front end or the single-pass host stages: drop --front_end_workers")
+    for path in more:
+        if not os.path.isfile(path):
+            sys.exit("[ERROR] file %s not found" % path)
 
 
 def load_model(args):
@@ -786,6 +814,21 @@ def call_region(args, m, prepared=None):
         lookup = cv.AlignmentLookup(args.bam_fn, args.ref_fn)
     decoder = cv.VariantDecoder(config, lookup, always_use_bam=args.pysam_for_all_indel_bases, arith=args.arith)
     writer = cv.writer_for(args)
+    if getattr(args, "ensemble_bam_fn", None):
+        def first_front_end(fe):            # BAM 0's front end is this function's to close, like the single BAM's: the native look-up asks it
+            nonlocal device_fe
+            device_fe = fe
+        try:
+            call_sites(args, m, decoder, lookup, writer, prepared, first_front_end)
+            if native_lookup(args):
+                logging.info("indel look-up: %d positions in %d device calls (at most %d in one), lookup_over_depth %d, answered by the host twin %d"
+                             % (lookup.positions, lookup.calls, lookup.largest_call, lookup.over_depth, lookup.handed_over))
+        finally:
+            if device_fe is not None:
+                device_fe.close()
+            writer.close()
+            lookup.close()
+        return
     try:
         batch = args.batch_size or param.engineBatchSize
         source = None
@@ -820,6 +863,122 @@ def call_region(args, m, prepared=None):
             device_fe.close()
         writer.close()
         lookup.close()
+
+
+def call_sites(args, m, decoder, lookup, writer, prepared=None, first_front_end=None):
+    """--ensemble_bam_fn: one region from B BAMs with the K checkpoints of the model, merged per site and averaged on the GPU (the site table,
+    include/clair_amd.h: clair_sites_*; docs/ensemble.md).  Per BAM: the front end (on the device, or the host stages where it hands the
+    region back), the table told of all the BAM's window positions at once, then the batches through submit_sites, as many in flight as the
+    model has slots.  Then the table is finished and its output list decoded batch by batch into the existing decoder and writer.
+    first_front_end(fe): told of BAM 0's device front end, which the caller closes after the last row is decoded (the native indel look-up
+    asks it until then); every other BAM's is closed here when its windows have been consumed."""
+    import copy
+    from time import time
+    from . import _capi, _hostapi
+    t0 = time()
+    batch = args.batch_size or param.engineBatchSize
+    n_slots = max(1, int(getattr(m, "n_slots", 2)))
+    bams = [args.bam_fn] + list(args.ensemble_bam_fn)
+    table = m.site_table()
+    buffers = {}
+
+    def pinned(nbytes):                            # one page-locked feed buffer for all the BAMs: a front end reads it only while it is fed
+        if nbytes not in buffers:
+            buffers[nbytes] = m.pinned_buffer(nbytes)
+        return buffers[nbytes]
+    try:
+        for b, bam in enumerate(bams):
+            sub = copy.copy(args)
+            sub.bam_fn = bam
+            if b > 0:
+                sub.indel_lookup = "pysam"         # only BAM 0 is ever asked: the other front ends keep nothing for the look-up
+            fe = None
+            try:
+                if wants_device_front_end(sub):
+                    if b == 0 and prepared is not None:
+                        fe = prepared
+                    else:
+                        fe = DeviceFrontEnd(sub, args.device, pinned=pinned if hasattr(m, "pinned_buffer") else None)
+                        if b == 0 and first_front_end is not None:
+                            first_front_end(fe)
+                        fe.run()
+                    if fe.frontend is None:
+                        fe = None
+                if b == 0 and native_lookup(args) and fe is None:
+                    sys.exit("[ERROR] --indel_lookup native: the device front end handed this region to the host stages (see the message above), so no "
+                             "alignments are resident on the GPU to look indels up in; --indel_lookup pysam works with every front end")
+                if fe is not None:
+                    f, n_windows = fe.frontend, fe.n_windows
+                    centres, seqs = f.window_info(0, n_windows) if n_windows else (np.zeros(0, np.int64), np.zeros((0, 34), np.uint8))
+
+                    def pieces():
+                        for first in range(0, n_windows, batch):
+                            n = min(batch, n_windows - first)
+                            q = seqs[first:first + n]
+                            yield first, _capi.DeviceWindows(f, first, n), True, np.stack([q[:, 16], np.minimum((q[:, :33] != 0).sum(axis=1), 255)], axis=1).astype(np.uint8), q
+                else:
+                    positions = candidate_positions(sub)
+                    logging.info("%d candidate sites" % len(positions))
+                    # the table wants every position of the BAM before its first batch: the batches are held, as int16 counts where they fit
+                    held = [(infos, small if small is not None else x, small is not None) for x, infos, small in tensor_batches(sub, positions, batch)]
+                    centres = np.array([int(info[1]) for infos, _, _ in held for info in infos], dtype=np.int64)
+
+                    def pieces():
+                        first = 0
+                        for infos, windows, is_counts in held:
+                            yield first, windows, is_counts, _hostapi.centre_bytes(infos), [info[2] for info in infos]
+                            first += len(infos)
+                n_new = table.begin_source(centres)
+                logging.info("%s: %d windows, %d sites the earlier BAMs did not have" % (bam, len(centres), n_new))
+                inflight = []
+                try:
+                    for k, (first, windows, is_counts, centre, seq) in enumerate(pieces()):
+                        if len(inflight) == n_slots:
+                            m.wait(inflight.pop(0))
+                        m.submit_sites(k % n_slots, table, first, windows, centre, seq, counts=is_counts)
+                        inflight.append(k % n_slots)
+                finally:
+                    failed = sys.exc_info()[0] is not None
+                    for slot in inflight:
+                        try:
+                            m.wait(slot)
+                        except Exception:
+                            if not failed:
+                                raise
+            finally:
+                if fe is not None and b > 0:
+                    fe.close()
+        n_out = table.finish(args.minimum_count_to_output, args.ensemble_order)
+        logging.info("%d sites of %d BAMs x %d checkpoints to call" % (n_out, len(bams), getattr(m, "n_models", 1)))
+        writer.write_header()
+        logging.info("Calling variants ...")
+        device_decode = decoder.native_applies() and os.environ.get("CLAIR_AMD_DEVICE_DECODE", "1") != "0"
+        keep_probabilities = device_decode and lookup.sam is not None      # candidates that consult the BAM are decoded again from them
+        inflight = []
+
+        def retire():
+            slot, first, n = inflight.pop(0)
+            prediction = m.wait(slot)
+            positions, _, seqs = table.info(first, n)
+            infos = window_infos(args.ctgName, positions, seqs)
+            if device_decode:
+                calls, probabilities = prediction if keep_probabilities else (prediction, None)
+                x = table.windows(first, n) if keep_probabilities else None
+                writer.write_rows(decoder.decode_calls(x, infos, calls, probabilities))
+            else:
+                writer.write_rows(decoder.decode_batch(table.windows(first, n), infos, prediction))
+
+        for k, first in enumerate(range(0, n_out, batch)):
+            if len(inflight) == n_slots:
+                retire()
+            n = min(batch, n_out - first)
+            m.submit_site_calls(k % n_slots, table, first, n, with_calls=device_decode, with_probabilities=keep_probabilities)
+            inflight.append((k % n_slots, first, n))
+        while inflight:
+            retire()
+        logging.info("Total time elapsed: %.2f s" % (time() - t0))
+    finally:
+        table.close()
 
 
 def Run(args):
@@ -905,6 +1064,17 @@ def build_parser():
     add('--ensemble_chkpnt_fn', type=str, action='append', default=None, metavar="PREFIX",
         help="one more checkpoint to call with, repeatable (at most 7): the probabilities of --chkpnt_fn and of these are averaged on the GPU "
              "exactly as the reference's call_var --output_for_ensemble | ensemble | call_var --input_probabilities averages them")
+    add('--ensemble_bam_fn', type=str, action='append', default=None, metavar="BAM",
+        help="one more BAM of the same sample and region (e.g. a down-sampled one), repeatable (at most %d): every BAM is called with every "
+             "checkpoint, the sites are merged and their probabilities averaged on the GPU exactly as `cat` of the runs' --output_for_ensemble "
+             "rows | ensemble | call_var --input_probabilities does.  --bam_fn is BAM 0: window and reference of a site are those of the first "
+             "BAM that has it, and the decode's questions to a BAM (pysam, --indel_lookup native) go to --bam_fn" % MAX_ENSEMBLE_BAMS)
+    add('--minimum_count_to_output', type=int, default=0,
+        help="with --ensemble_bam_fn: call a site only when at least this many (BAM, checkpoint) runs produced it (the `ensemble` filter's "
+             "option of the same name), default: %(default)s")
+    add('--ensemble_order', type=str, default="chain", choices=("chain", "position"),
+        help="with --ensemble_bam_fn: rows in the order the text chain yields (all sites of --bam_fn ascending, then those only later BAMs "
+             "have, BAM by BAM), or sorted by position; default: %(default)s")
     add('--arith', type=str, default="legacy", choices=("legacy", "numpy2"),
         help="QUAL/AF arithmetic: float64 as under the reference's NumPy 1.x (legacy) or float32 (numpy2)")
     add('--overlap_filter', type=str, default="off", choices=("off", "host", "device"),

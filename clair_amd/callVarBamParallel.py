@@ -70,7 +70,9 @@ def commands(args):
         None if args.samtools_view_args is None else '--samtools_view_args="%s"' % args.samtools_view_args,
         _opt("bam_reader", args.bam_reader), _opt("bam_threads", args.bam_threads), _opt("bam_inflate", args.bam_inflate), _opt("indel_lookup", args.indel_lookup),
         _opt("overlap_filter", args.overlap_filter),
-    ] + [_opt("ensemble_chkpnt_fn", os.path.abspath(f)) for f in (args.ensemble_chkpnt_fn or [])] if x is not None)
+    ] + [_opt("ensemble_chkpnt_fn", os.path.abspath(f)) for f in (args.ensemble_chkpnt_fn or [])]
+      + [_opt("ensemble_bam_fn", os.path.abspath(f)) for f in (args.ensemble_bam_fn or [])]
+      + [_opt("minimum_count_to_output", args.minimum_count_to_output), _opt("ensemble_order", args.ensemble_order)] if x is not None)
     out, k = [], 0
     commands.chunks = []           # (device, output file) per command, for --run
     with open(fai_fn) as fai:
@@ -255,6 +257,10 @@ def build_parser():
         help="passed on (callVarBam: every chunk's VCF through the overlap filter, on the host or on the GPU; the chunks are not merged)")
     add('--ensemble_chkpnt_fn', type=str, action='append', default=None, metavar="PREFIX",
         help="passed on, repeatable (callVarBam: one more checkpoint whose probabilities are averaged with --chkpnt_fn's on the GPU)")
+    add('--ensemble_bam_fn', type=str, action='append', default=None, metavar="BAM",
+        help="passed on, repeatable (callVarBam: one more BAM of the same sample whose sites are merged with --bam_fn's and averaged on the GPU)")
+    add('--minimum_count_to_output', type=int, default=None, help="passed on (callVarBam: with --ensemble_bam_fn, the runs a site needs to be called)")
+    add('--ensemble_order', type=str, default=None, choices=("chain", "position"), help="passed on (callVarBam: with --ensemble_bam_fn, the order of the rows)")
     return parser
 
 

@@ -31,6 +31,7 @@
 #include "lstm32.hip.h"
 #include "lstm32_pair.hip.h"
 #include "lstm2_fused.hip.h"
+#include "sites.hip.h"
 #include "device_buffer.h"
 #include "weight_images.h"
 
@@ -91,6 +92,8 @@ struct Slot {
     DeviceBuffer d_labels; PinnedBuffer h_labels;   // unsigned char [max_pad][4], pinned twin
     // ensemble calling (clair_submit_ensemble, clair_ensemble_average): the running sums of ensemble.hip.h, allocated on first use
     DeviceBuffer d_acc;       // double [max_pad][90]
+    // ensemble across BAMs (clair_submit_sites, clair_sites_add_rows): the candidates' reference windows on their way into the site table
+    DeviceBuffer d_seq; PinnedBuffer h_seq;         // unsigned char [max_pad][33], pinned twin
     // pending host outputs of a submit
     float *o_gt21 = nullptr, *o_gt = nullptr, *o_l1 = nullptr, *o_l2 = nullptr;
     int pending_n = 0;
@@ -117,6 +120,26 @@ struct ModelWeights {
 };
 
 }  // namespace
+
+// The site table of ensemble calling across BAMs (sites.hip.h; include/clair_amd.h: clair_sites_*).  It belongs to the engine handle: its
+// kernels run on the handle's lanes, its errors are the handle's, and what is left of it goes with the handle.
+struct clair_sites {
+    clair_engine *e = nullptr;
+    int64_t n_sites = 0, capacity = 0;      // rows in use / allocated
+    DeviceBuffer key, count, acc, x, centre, seq;       // per row: int64, int, double [90], float [1056], 2 bytes, 33 bytes
+    DeviceBuffer idx_key[2], idx_row[2];                // (key, row) sorted by key; `cur` is the one in use
+    int cur = 0;
+    // the current source
+    int64_t src_n = -1;                                 // its positions (-1: no source begun)
+    DeviceBuffer pos, lb, is_new, before, row_of;       // int64 [n], int64 [n], uint32 [n], uint32 [n + 1], int64 [n]
+    DeviceBuffer overflow;                              // int: a site was given a 65th row
+    // after clair_sites_finish
+    bool finished = false;
+    int64_t n_out = 0;
+    DeviceBuffer keep, out_before, out_row, out_key, out_count, out_seq, avg;   // uint32 [n_sites], uint32 [n_sites + 1]; int64, int64, int, [33], float [90] per output
+    DeviceBuffer gathered;                              // clair_sites_windows: the windows of a range, dense
+    SiteRows rows() const { return SiteRows{key.as<int64_t>(), count.as<int>(), acc.as<double>(), x.as<float>(), centre.as<unsigned char>(), seq.as<unsigned char>()}; }
+};
 
 struct clair_engine {
     int device = 0;
@@ -157,6 +180,9 @@ struct clair_engine {
         const uint8_t *centre; clair_call_t *calls; float *gt21, *gt, *l1, *l2;
         const uint8_t *labels = nullptr;   // clair_submit_eval: [n][4] true indices, scored behind the forward pass
         int models = 0;                    // clair_submit_ensemble: this many forward passes, one per weight image, averaged (0: image 0 alone, as it is)
+        clair_sites *sites = nullptr;      // clair_submit_sites: the passes are folded into this table's rows of candidates [sites_first, sites_first + n) of its source
+        int64_t sites_first = 0;
+        const uint8_t *seq = nullptr;      // their reference windows, [n][33]
     };
     int staging_threads = 2;            // CLAIR_AMD_STAGING_THREADS (0: everything on the submitting thread): a 4.3 MB batch takes one core ~100 us
                                         // to copy, 75 % of the 135 us the GPU needs for it
@@ -168,6 +194,7 @@ struct clair_engine {
     // weight images: models[0] is the handle's own checkpoint; clair_ensemble_models adds up to CLAIR_ENSEMBLE_MAX_MODELS - 1 more
     std::vector<std::unique_ptr<ModelWeights>> models;
     DeviceBuffer eval_counts; // unsigned long long [CLAIR_EVAL_COUNTS] confusion counters of evaluate.hip.h, allocated by the first clair_eval_* call
+    std::list<std::unique_ptr<clair_sites>> tables;   // site tables of clair_sites_create not yet destroyed
     double ms_sum[CLAIR_K_COUNT] = {0};
     int64_t launches[CLAIR_K_COUNT] = {0};
 };
@@ -393,6 +420,27 @@ int enqueue_ensemble(clair_engine *e, Lane &l, Slot &s, int n, int models, bool 
     return 0;
 }
 
+// The site table's steps behind a forward pass of the slot's batch (sites.hip.h): window, centre and seq into the rows that are new, then d_out
+// into the rows' sums.  `first`: where the batch begins in the table's current source.  No id in enum clair_kernel_id, like the averaging.
+int ensure_slot_sites(clair_engine *e, Slot &s) {
+    HIP_TRY(e, s.d_seq.ensure((size_t)e->max_pad * SITE_SEQ));
+    HIP_TRY(e, s.h_seq.ensure((size_t)e->max_batch * SITE_SEQ));
+    return 0;
+}
+int enqueue_sites_adopt(clair_engine *e, Lane &l, Slot &s, clair_sites *t, int64_t first, int n, bool with_x) {
+    hipLaunchKernelGGL(sites_adopt_kernel, dim3((n + 3) / 4), dim3(256), 0, l.stream, t->rows(), t->row_of.as<int64_t>() + first, n,
+                       with_x ? s.d_x.as<float>() : nullptr, s.d_centre.as<unsigned char>(), s.d_seq.as<unsigned char>());
+    HIP_TRY(e, hipGetLastError());
+    return 0;
+}
+int enqueue_sites_accumulate(clair_engine *e, Lane &l, Slot &s, clair_sites *t, int64_t first, int n) {
+    const int n_pairs = n * OUT_FLOATS / 2;
+    hipLaunchKernelGGL(sites_accumulate_kernel, dim3((n_pairs + 255) / 256), dim3(256), 0, l.stream, t->rows(), t->row_of.as<int64_t>() + first, n_pairs,
+                       s.d_out.as<float>(), t->overflow.as<int>());
+    HIP_TRY(e, hipGetLastError());
+    return 0;
+}
+
 // the counter block exists (zeroed) from the first call that needs it
 int ensure_eval_counts(clair_engine *e) {
     if (!e->eval_counts.p) {
@@ -565,7 +613,14 @@ int enqueue_request(clair_engine *e, int slot_index, const clair_engine::Request
         memcpy(s.h_centre.p, q.centre, (size_t)n * 2);
         HIP_TRY(e, hipMemcpyAsync(s.d_centre.p, s.h_centre.p, (size_t)n * 2, hipMemcpyHostToDevice, s.cin));
     }
-    if (q.models && ensure_slot_ensemble(e, s)) return 1;
+    if (q.models && !q.sites && ensure_slot_ensemble(e, s)) return 1;
+    if (q.sites) {
+        if (ensure_slot_decode(e, s) || ensure_slot_sites(e, s)) return 1;
+        memcpy(s.h_centre.p, q.centre, (size_t)n * 2);
+        memcpy(s.h_seq.p, q.seq, (size_t)n * SITE_SEQ);
+        HIP_TRY(e, hipMemcpyAsync(s.d_centre.p, s.h_centre.p, (size_t)n * 2, hipMemcpyHostToDevice, s.cin));
+        HIP_TRY(e, hipMemcpyAsync(s.d_seq.p, s.h_seq.p, (size_t)n * SITE_SEQ, hipMemcpyHostToDevice, s.cin));
+    }
     if (q.labels) {
         if (ensure_slot_labels(e, s)) return 1;
         memcpy(s.h_labels.p, q.labels, (size_t)n * 4);
@@ -590,7 +645,13 @@ int enqueue_request(clair_engine *e, int slot_index, const clair_engine::Request
         if (!same_in) g.lock();
         if (!same_in) HIP_TRY(e, hipStreamWaitEvent(l.stream, s.ev_in, 0));
         if (convert_on_lane) launch_convert(l.stream);
-        if (q.models) {   // K passes over the same input back to back, each folded into the slot's sums; the last leaves the averaged rows in d_out
+        if (q.sites) {    // K passes over the same input back to back, each folded into the table's rows; the first brings the new rows their windows
+            for (int k = 0; k < q.models; ++k) {
+                if (enqueue_forward(e, l, *e->models[k], s.d_x.as<float>(), s.d_out.as<float>(), n, slot_index)) return 1;
+                if (k == 0 && enqueue_sites_adopt(e, l, s, q.sites, q.sites_first, n, true)) return 1;
+                if (enqueue_sites_accumulate(e, l, s, q.sites, q.sites_first, n)) return 1;
+            }
+        } else if (q.models) {   // K passes over the same input back to back, each folded into the slot's sums; the last leaves the averaged rows in d_out
             for (int k = 0; k < q.models; ++k) {
                 if (enqueue_forward(e, l, *e->models[k], s.d_x.as<float>(), s.d_out.as<float>(), n, slot_index)) return 1;
                 if (enqueue_ensemble(e, l, s, n, q.models, k == 0, k == q.models - 1)) return 1;
@@ -912,7 +973,7 @@ int clair_slot_input(clair_engine_t *e, int slot, float **x_pinned) {
 }
 
 int clair_wait(clair_engine_t *e, int slot) {
-    if (check_slot(e, slot)) return 1;
+    if (check_slot(e, slot, false)) return 1;      // what a submit needs it has checked itself; clair_submit_site_calls needs no weights
     HIP_TRY(e, hipSetDevice(e->device));
     Slot &s = e->slots[slot];
     Lane &l = *e->lanes[s.lane];
@@ -1100,6 +1161,292 @@ int clair_ensemble_average(clair_engine_t *e, int slot, const float *probs, int 
     }
     HIP_TRY(e, hipMemcpyAsync(out, s.d_out.p, row_bytes, hipMemcpyDeviceToHost, l.stream));
     HIP_TRY(e, hipStreamSynchronize(l.stream));
+    return 0;
+}
+
+// -- ensemble across BAMs: the site table (sites.hip.h; clair/post_processing/ensemble.py:10-75 over runs whose sites differ) ----------------
+namespace {
+
+// a buffer grown to new_bytes with its first old_bytes kept
+int grow_buffer(clair_engine *e, DeviceBuffer &b, size_t old_bytes, size_t new_bytes) {
+    DeviceBuffer fresh;
+    HIP_TRY(e, fresh.ensure(new_bytes));
+    if (old_bytes) HIP_TRY(e, hipMemcpy(fresh.p, b.p, old_bytes, hipMemcpyDeviceToDevice));
+    std::swap(b.p, fresh.p);
+    std::swap(b.bytes, fresh.bytes);
+    return 0;
+}
+
+int check_sites(clair_sites *t, const char *what, bool open_only) {
+    if (!t) return fail(nullptr, "%s: the site table is NULL", what);
+    if (open_only && t->finished) return fail(t->e, "%s: the site table has been finished: it takes no more rows", what);
+    return 0;
+}
+
+int check_source_range(clair_sites *t, const char *what, int64_t first, int64_t n) {
+    if (t->src_n < 0) return fail(t->e, "%s: no source begun: call clair_sites_begin_source first", what);
+    if (first < 0 || n < 1 || first > t->src_n - n) return fail(t->e, "%s: rows [%lld, %lld) lie outside the current source of %lld", what, (long long)first,
+                                                                (long long)(first + n), (long long)t->src_n);
+    return 0;
+}
+
+int check_output_range(clair_sites *t, const char *what, int64_t first, int64_t n) {
+    if (!t->finished) return fail(t->e, "%s: call clair_sites_finish first", what);
+    if (first < 0 || n < 0 || first > t->n_out - n) return fail(t->e, "%s: rows [%lld, %lld) lie outside the output list of %lld", what, (long long)first,
+                                                                (long long)(first + n), (long long)t->n_out);
+    return 0;
+}
+
+int read_overflow(clair_sites *t, const char *what) {
+    int flag = 0;
+    HIP_TRY(t->e, hipMemcpy(&flag, t->overflow.p, sizeof flag, hipMemcpyDeviceToHost));
+    if (flag) return fail(t->e, "%s: a site was given more than %d rows", what, SITE_MAX_ROWS);
+    return 0;
+}
+
+}  // namespace
+
+int clair_sites_create(clair_engine_t *e, clair_sites_t **out) {
+    if (!e) return fail(nullptr, "engine is NULL");
+    if (!out) return fail(e, "out is NULL");
+    if (fused_possible(e)) return fail(e, "clair_sites_create: the site table runs on the two-launch layer-2 path only: unset CLAIR_AMD_LSTM2_FUSED");
+    HIP_TRY(e, hipSetDevice(e->device));
+    std::unique_ptr<clair_sites> t(new clair_sites());
+    t->e = e;
+    HIP_TRY(e, t->overflow.ensure(sizeof(int)));
+    HIP_TRY(e, hipMemset(t->overflow.p, 0, sizeof(int)));
+    HIP_TRY(e, hipStreamSynchronize(nullptr));
+    *out = t.get();
+    e->tables.push_back(std::move(t));
+    return 0;
+}
+
+void clair_sites_destroy(clair_sites_t *t) {
+    if (!t) return;
+    clair_engine *e = t->e;
+    (void)hipSetDevice(e->device);
+    (void)quiesce(e);
+    e->tables.remove_if([t](const std::unique_ptr<clair_sites> &p) { return p.get() == t; });
+}
+
+int clair_sites_begin_source(clair_sites_t *t, const int64_t *positions, int64_t n, int64_t *n_new) {
+    if (check_sites(t, "clair_sites_begin_source", true)) return 1;
+    clair_engine *e = t->e;
+    if (n < 0 || n > INT32_MAX || (n > 0 && !positions)) return fail(e, "clair_sites_begin_source: bad arguments");
+    for (int64_t i = 1; i < n; ++i)
+        if (positions[i] <= positions[i - 1])
+            return fail(e, "clair_sites_begin_source: positions are not strictly ascending (%lld after %lld at %lld)", (long long)positions[i], (long long)positions[i - 1], (long long)i);
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (quiesce(e)) return 1;                     // every slot drained: nothing in flight reads row_of or the rows that move
+    Lane &l = *e->lanes[0];
+    std::lock_guard<std::mutex> g(l.order);
+    uint32_t fresh = 0;
+    if (n > 0) {
+        const int64_t ns = t->n_sites;
+        HIP_TRY(e, t->pos.ensure((size_t)n * sizeof(int64_t)));
+        HIP_TRY(e, t->lb.ensure((size_t)n * sizeof(int64_t)));
+        HIP_TRY(e, t->row_of.ensure((size_t)n * sizeof(int64_t)));
+        HIP_TRY(e, t->is_new.ensure((size_t)n * sizeof(uint32_t)));
+        HIP_TRY(e, t->before.ensure((size_t)(n + 1) * sizeof(uint32_t)));
+        HIP_TRY(e, hipMemcpyAsync(t->pos.p, positions, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, l.stream));
+        hipLaunchKernelGGL(sites_search_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, l.stream, t->pos.as<int64_t>(), n, t->idx_key[t->cur].as<int64_t>(),
+                           t->idx_row[t->cur].as<int64_t>(), ns, t->lb.as<int64_t>(), t->is_new.as<uint32_t>(), t->row_of.as<int64_t>());
+        hipLaunchKernelGGL(sites_scan_kernel, dim3(1), dim3(256), 0, l.stream, t->is_new.as<uint32_t>(), n, t->before.as<uint32_t>());
+        HIP_TRY(e, hipGetLastError());
+        HIP_TRY(e, hipMemcpyAsync(&fresh, t->before.as<uint32_t>() + n, sizeof fresh, hipMemcpyDeviceToHost, l.stream));
+        HIP_TRY(e, hipStreamSynchronize(l.stream));
+        if (ns + fresh > t->capacity) {           // room for every position of the source, so that a source of known sites never grows anything
+            const size_t from = (size_t)ns, to = (size_t)(ns + n);
+            if (grow_buffer(e, t->key, from * sizeof(int64_t), to * sizeof(int64_t)) || grow_buffer(e, t->count, from * sizeof(int), to * sizeof(int)) ||
+                grow_buffer(e, t->acc, from * OUT_FLOATS * sizeof(double), to * OUT_FLOATS * sizeof(double)) ||
+                grow_buffer(e, t->x, from * SITE_X * sizeof(float), to * SITE_X * sizeof(float)) || grow_buffer(e, t->centre, from * 2, to * 2) ||
+                grow_buffer(e, t->seq, from * SITE_SEQ, to * SITE_SEQ)) return 1;
+            for (int k = 0; k < 2; ++k) {
+                const size_t keep = k == t->cur ? from * sizeof(int64_t) : 0;
+                if (grow_buffer(e, t->idx_key[k], keep, to * sizeof(int64_t)) || grow_buffer(e, t->idx_row[k], keep, to * sizeof(int64_t))) return 1;
+            }
+            t->capacity = (int64_t)to;
+        }
+        if (fresh) {
+            const int other = t->cur ^ 1;
+            hipLaunchKernelGGL(sites_assign_kernel, dim3((unsigned)((n + ns + 255) / 256)), dim3(256), 0, l.stream, t->pos.as<int64_t>(), n, t->lb.as<int64_t>(),
+                               t->is_new.as<uint32_t>(), t->before.as<uint32_t>(), t->idx_key[t->cur].as<int64_t>(), t->idx_row[t->cur].as<int64_t>(), ns,
+                               t->idx_key[other].as<int64_t>(), t->idx_row[other].as<int64_t>(), t->row_of.as<int64_t>(), t->key.as<int64_t>(), t->count.as<int>());
+            HIP_TRY(e, hipGetLastError());
+            HIP_TRY(e, hipMemsetAsync(t->acc.as<double>() + (size_t)ns * OUT_FLOATS, 0, (size_t)fresh * OUT_FLOATS * sizeof(double), l.stream));
+            // window, centre and seq of a new row are zeros until a run brings its own (clair_sites_add_rows may bring none)
+            HIP_TRY(e, hipMemsetAsync(t->x.as<float>() + (size_t)ns * SITE_X, 0, (size_t)fresh * SITE_X * sizeof(float), l.stream));
+            HIP_TRY(e, hipMemsetAsync(t->centre.as<unsigned char>() + (size_t)ns * 2, 0, (size_t)fresh * 2, l.stream));
+            HIP_TRY(e, hipMemsetAsync(t->seq.as<unsigned char>() + (size_t)ns * SITE_SEQ, 0, (size_t)fresh * SITE_SEQ, l.stream));
+            HIP_TRY(e, hipStreamSynchronize(l.stream));
+            t->cur = other;
+            t->n_sites = ns + fresh;
+        }
+    }
+    t->src_n = n;
+    if (n_new) *n_new = fresh;
+    return 0;
+}
+
+int clair_submit_sites(clair_engine_t *e, int slot, clair_sites_t *t, int64_t first, const void *input, int input_is_counts, int64_t input_stride_bytes, int n,
+                       const uint8_t *centre, const uint8_t *seq) {
+    if (check_sites(t, "clair_submit_sites", true)) return 1;
+    if (e != t->e) return fail(e, "clair_submit_sites: the site table belongs to another engine");
+    clair_engine::Request q{input, input_is_counts != 0, input_stride_bytes, n, centre, nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (check_request(e, slot, q, input && centre && seq, "NULL input, centre or seq pointer") || check_stride(e, q)) return 1;
+    if (check_source_range(t, "clair_submit_sites", first, n)) return 1;
+    if (fused_possible(e)) return fail(e, "clair_submit_sites runs on the two-launch layer-2 path only: unset CLAIR_AMD_LSTM2_FUSED");
+    q.models = (int)e->models.size();
+    for (int k = 0; k < q.models; ++k)
+        if (!e->models[k]->ready) return fail(e, "weights of model %d not loaded: clair_ensemble_set_tensor for all tensors, then clair_ensemble_finalize_weights", k);
+    q.sites = t;
+    q.sites_first = first;
+    q.seq = seq;
+    return submit_request(e, slot, q);
+}
+
+// One run's rows alone, on probabilities the caller holds: synchronous, needs no weights (the twin of clair_ensemble_average).  x, centre
+// and seq (each optional) are what the rows that are new take along, as after the first pass of clair_submit_sites.
+int clair_sites_add_rows(clair_engine_t *e, clair_sites_t *t, int64_t first, const float *probs, int n, const float *x, const uint8_t *centre, const uint8_t *seq) {
+    if (check_sites(t, "clair_sites_add_rows", true)) return 1;
+    if (e != t->e) return fail(e, "clair_sites_add_rows: the site table belongs to another engine");
+    if (check_slot(e, 0, false) || check_n(e, n)) return 1;
+    if (!probs) return fail(e, "NULL input pointer");
+    if (check_source_range(t, "clair_sites_add_rows", first, n)) return 1;
+    if (fused_possible(e)) return fail(e, "clair_sites_add_rows is not available on a handle with the fused layer-2 launch: unset CLAIR_AMD_LSTM2_FUSED");
+    HIP_TRY(e, hipSetDevice(e->device));
+    Slot &s = e->slots[0];
+    if (s.pending_n) return fail(e, "slot 0 still has a pending submit; call clair_wait first");
+    if (ensure_slot_decode(e, s) || ensure_slot_sites(e, s)) return 1;
+    Lane &l = *e->lanes[s.lane];
+    std::lock_guard<std::mutex> g(l.order);
+    HIP_TRY(e, hipMemcpyAsync(s.d_out.p, probs, (size_t)n * OUT_FLOATS * sizeof(float), hipMemcpyHostToDevice, l.stream));
+    if (x) HIP_TRY(e, hipMemcpyAsync(s.d_x.p, x, (size_t)n * SITE_X * sizeof(float), hipMemcpyHostToDevice, l.stream));
+    // rows without a centre or a seq of their own take zeros
+    if (centre) HIP_TRY(e, hipMemcpyAsync(s.d_centre.p, centre, (size_t)n * 2, hipMemcpyHostToDevice, l.stream));
+    else HIP_TRY(e, hipMemsetAsync(s.d_centre.p, 0, (size_t)n * 2, l.stream));
+    if (seq) HIP_TRY(e, hipMemcpyAsync(s.d_seq.p, seq, (size_t)n * SITE_SEQ, hipMemcpyHostToDevice, l.stream));
+    else HIP_TRY(e, hipMemsetAsync(s.d_seq.p, 0, (size_t)n * SITE_SEQ, l.stream));
+    if (enqueue_sites_adopt(e, l, s, t, first, n, x != nullptr) || enqueue_sites_accumulate(e, l, s, t, first, n)) return 1;
+    HIP_TRY(e, hipStreamSynchronize(l.stream));
+    return read_overflow(t, "clair_sites_add_rows");
+}
+
+int clair_sites_finish(clair_sites_t *t, int min_count, int order, int64_t *n_out) {
+    if (check_sites(t, "clair_sites_finish", false)) return 1;
+    clair_engine *e = t->e;
+    if (order != CLAIR_SITES_ORDER_CHAIN && order != CLAIR_SITES_ORDER_POSITION) return fail(e, "clair_sites_finish: order %d is neither chain (0) nor position (1)", order);
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (quiesce(e)) return 1;
+    if (read_overflow(t, "clair_sites_finish")) return 1;
+    Lane &l = *e->lanes[0];
+    std::lock_guard<std::mutex> g(l.order);
+    const int64_t ns = t->n_sites;
+    uint32_t kept = 0;
+    if (ns > 0) {
+        const int64_t *idx_row = order == CLAIR_SITES_ORDER_POSITION ? t->idx_row[t->cur].as<int64_t>() : nullptr;
+        const unsigned blocks = (unsigned)((ns + 255) / 256);
+        HIP_TRY(e, t->keep.ensure((size_t)ns * sizeof(uint32_t)));
+        HIP_TRY(e, t->out_before.ensure((size_t)(ns + 1) * sizeof(uint32_t)));
+        // a site is a position some run produced: a row begun but never fed (count 0) is none, whatever the minimum
+        hipLaunchKernelGGL(sites_keep_kernel, dim3(blocks), dim3(256), 0, l.stream, t->count.as<int>(), idx_row, ns, std::max(min_count, 1), t->keep.as<uint32_t>());
+        hipLaunchKernelGGL(sites_scan_kernel, dim3(1), dim3(256), 0, l.stream, t->keep.as<uint32_t>(), ns, t->out_before.as<uint32_t>());
+        HIP_TRY(e, hipGetLastError());
+        HIP_TRY(e, hipMemcpyAsync(&kept, t->out_before.as<uint32_t>() + ns, sizeof kept, hipMemcpyDeviceToHost, l.stream));
+        HIP_TRY(e, hipStreamSynchronize(l.stream));
+        if (kept) {
+            HIP_TRY(e, t->out_row.ensure((size_t)kept * sizeof(int64_t)));
+            HIP_TRY(e, t->out_key.ensure((size_t)kept * sizeof(int64_t)));
+            HIP_TRY(e, t->out_count.ensure((size_t)kept * sizeof(int)));
+            HIP_TRY(e, t->out_seq.ensure((size_t)kept * SITE_SEQ));
+            HIP_TRY(e, t->avg.ensure((size_t)kept * OUT_FLOATS * sizeof(float)));
+            hipLaunchKernelGGL(sites_compact_kernel, dim3(blocks), dim3(256), 0, l.stream, t->rows(), idx_row, ns, t->keep.as<uint32_t>(), t->out_before.as<uint32_t>(),
+                               t->out_row.as<int64_t>(), t->out_key.as<int64_t>(), t->out_count.as<int>(), t->out_seq.as<unsigned char>());
+            const int64_t n_values = (int64_t)kept * OUT_FLOATS;
+            hipLaunchKernelGGL(sites_average_kernel, dim3((unsigned)((n_values + 255) / 256)), dim3(256), 0, l.stream, t->rows(), t->out_row.as<int64_t>(), n_values,
+                               t->avg.as<float>());
+            HIP_TRY(e, hipGetLastError());
+            HIP_TRY(e, hipStreamSynchronize(l.stream));
+        }
+    }
+    t->finished = true;
+    t->n_out = kept;
+    if (n_out) *n_out = kept;
+    return 0;
+}
+
+int clair_sites_info(clair_sites_t *t, int64_t first, int64_t n, int64_t *positions, int32_t *counts, uint8_t *seq) {
+    if (check_sites(t, "clair_sites_info", false) || check_output_range(t, "clair_sites_info", first, n)) return 1;
+    clair_engine *e = t->e;
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (n == 0) return 0;
+    if (positions) HIP_TRY(e, hipMemcpy(positions, t->out_key.as<int64_t>() + first, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (counts) HIP_TRY(e, hipMemcpy(counts, t->out_count.as<int>() + first, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    if (seq) HIP_TRY(e, hipMemcpy(seq, t->out_seq.as<unsigned char>() + (size_t)first * SITE_SEQ, (size_t)n * SITE_SEQ, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int clair_sites_rows(clair_sites_t *t, int64_t first, int64_t n, float *out) {
+    if (check_sites(t, "clair_sites_rows", false) || check_output_range(t, "clair_sites_rows", first, n)) return 1;
+    clair_engine *e = t->e;
+    if (n > 0 && !out) return fail(e, "clair_sites_rows: out is NULL");
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (n > 0) HIP_TRY(e, hipMemcpy(out, t->avg.as<float>() + (size_t)first * OUT_FLOATS, (size_t)n * OUT_FLOATS * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int clair_sites_windows(clair_sites_t *t, int64_t first, int64_t n, float *x) {
+    if (check_sites(t, "clair_sites_windows", false) || check_output_range(t, "clair_sites_windows", first, n)) return 1;
+    clair_engine *e = t->e;
+    if (n > INT32_MAX || (n > 0 && !x)) return fail(e, "clair_sites_windows: bad arguments");
+    if (n == 0) return 0;
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (quiesce(e)) return 1;
+    Lane &l = *e->lanes[0];
+    std::lock_guard<std::mutex> g(l.order);
+    if (t->gathered.bytes < (size_t)n * SITE_X * sizeof(float)) HIP_TRY(e, t->gathered.ensure((size_t)n * SITE_X * sizeof(float)));
+    hipLaunchKernelGGL(sites_gather_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, l.stream, t->rows(), t->out_row.as<int64_t>(), t->avg.as<float>(), first, (int)n,
+                       t->gathered.as<float>(), (unsigned char *)nullptr, (float *)nullptr);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, hipMemcpyAsync(x, t->gathered.p, (size_t)n * SITE_X * sizeof(float), hipMemcpyDeviceToHost, l.stream));
+    HIP_TRY(e, hipStreamSynchronize(l.stream));
+    return 0;
+}
+
+// The decode of entries [first, first + n) of the output list: a gather into the slot, then what clair_submit_ensemble leaves behind its
+// last pass -- decode_kernel and the result copy, unchanged.  Pair with clair_wait(slot).
+int clair_submit_site_calls(clair_engine_t *e, int slot, clair_sites_t *t, int64_t first, int n, clair_call_t *calls, float *gt21, float *genotype, float *l1, float *l2) {
+    if (check_sites(t, "clair_submit_site_calls", false)) return 1;
+    if (e != t->e) return fail(e, "clair_submit_site_calls: the site table belongs to another engine");
+    if (check_slot(e, slot, false) || check_n(e, n)) return 1;
+    if ((gt21 || genotype || l1 || l2) && !(gt21 && genotype && l1 && l2)) return fail(e, "the four probability arrays come together or not at all");
+    if (!gt21 && !calls) return fail(e, "nothing asked for: neither call records nor probabilities");
+    if (check_output_range(t, "clair_submit_site_calls", first, n)) return 1;
+    if (fused_possible(e)) return fail(e, "clair_submit_site_calls runs on the two-launch layer-2 path only: unset CLAIR_AMD_LSTM2_FUSED");
+    HIP_TRY(e, hipSetDevice(e->device));
+    Slot &s = e->slots[slot];
+    if (s.pending_n) return fail(e, "slot %d still has a pending submit; call clair_wait first", slot);
+    if (ensure_slot_decode(e, s)) return 1;
+    Lane &l = *e->lanes[s.lane];
+    s.o_gt21 = gt21; s.o_gt = genotype; s.o_l1 = l1; s.o_l2 = l2;
+    s.o_calls = calls;
+    s.refetch = false;
+    s.staged = 0;
+    const bool same_out = s.cout == l.stream;
+    {
+        std::lock_guard<std::mutex> g(l.order);
+        hipLaunchKernelGGL(sites_gather_kernel, dim3((n + 3) / 4), dim3(256), 0, l.stream, t->rows(), t->out_row.as<int64_t>(), t->avg.as<float>(), first, n, s.d_x.as<float>(),
+                           s.d_centre.as<unsigned char>(), s.d_out.as<float>());
+        HIP_TRY(e, hipGetLastError());
+        if (calls && enqueue_decode(e, l, s, n)) return 1;
+        if (same_out) { if (enqueue_results(e, l, s, n, calls != nullptr, gt21 != nullptr)) return 1; }
+        else HIP_TRY(e, hipEventRecord(s.ev_done, l.stream));
+    }
+    if (!same_out) {
+        HIP_TRY(e, hipStreamWaitEvent(s.cout, s.ev_done, 0));
+        if (enqueue_results(e, l, s, n, calls != nullptr, gt21 != nullptr)) return 1;
+    }
+    s.pending_n = n;
     return 0;
 }
 

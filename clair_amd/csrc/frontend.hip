@@ -18,6 +18,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "block_scan.hip.h"
 #include "device_buffer.h"
 
 #include <algorithm>
@@ -403,22 +404,7 @@ __global__ __launch_bounds__(256) void fe_given_flags_kernel(const int64_t *posi
 // line feeds of the text), and for 64-bit inclusive running sums (the candidate prefix; the second differences of pass 2, in place).
 constexpr int SCAN_ITEMS = 16, SCAN_BLOCK = 256 * SCAN_ITEMS;
 
-template <typename T> __device__ inline T block_exclusive_scan(T v, T *total) {   // 256 threads
-    __shared__ T wave_sum[4];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    T x = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const T y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) wave_sum[w] = x;
-    __syncthreads();
-    T before = 0, all = 0;
-    for (int i = 0; i < 4; ++i) { if (i < w) before += wave_sum[i]; all += wave_sum[i]; }
-    __syncthreads();
-    *total = all;
-    return before + x - v;
-}
+// (block_exclusive_scan: block_scan.hip.h, shared with the site table of engine.hip)
 
 // how an item is loaded: an In widened to the Sum the scan runs in (signed sums in two's complement) ...
 template <typename In, typename Sum> struct ScanValues {

@@ -14,7 +14,8 @@ Same rows, byte for byte (tests/golden/ensemble_small.json.gz, minted from the r
   * sites with fewer than --minimum_count_to_output rows are left out (:58-59); no arguments at all prints the help, exit 1 (:98-100).
 
 K models over ONE set of candidates need none of this text: call_var / callVarBam --ensemble_chkpnt_fn run the K forward passes and the
-same arithmetic on the GPU (docs/ensemble.md).  This filter stays for what that cannot do -- runs whose sites differ (model x BAM).
+same arithmetic on the GPU, and callVarBam --ensemble_bam_fn merges runs whose sites differ (model x BAM) in a site table there
+(docs/ensemble.md).  This filter stays for rows that were written elsewhere, and as the yardstick of both.
 """
 import sys
 from argparse import ArgumentParser

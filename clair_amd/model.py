@@ -113,6 +113,18 @@ class Clair(object):
         centre=None: no decode, wait(slot) returns the averaged probabilities."""
         self._engine.submit_ensemble(slot, batch, centre, counts=counts, with_probabilities=with_probabilities)
 
+    def site_table(self):
+        """A site table of the engine for ensemble calling across BAMs (include/clair_amd.h: clair_sites_*; docs/ensemble.md)."""
+        return self._engine.site_table()
+
+    def submit_sites(self, slot, table, first, batch, centre, seq, counts=False):
+        """Every checkpoint over the batch, folded into `table` as candidates [first, first + n) of its current source."""
+        self._engine.submit_sites(slot, table, first, batch, centre, seq, counts=counts)
+
+    def submit_site_calls(self, slot, table, first, n, with_calls=True, with_probabilities=False):
+        """The decode of entries [first, first + n) of the table's output list; wait(slot) returns what it returns after submit_ensemble."""
+        self._engine.submit_site_calls(slot, table, first, n, with_calls=with_calls, with_probabilities=with_probabilities)
+
     def pinned_buffer(self, nbytes):
         """Page-locked host memory of the engine (include/clair_amd.h: clair_pinned_alloc) as a uint8 array."""
         return self._engine.pinned_buffer(nbytes)

@@ -129,6 +129,8 @@ int clair_submit(clair_engine_t *e, int slot, const float *x, int n, float *gt21
 /* (A batch in pageable memory is copied to the slot's page-locked buffer, and its transfers and kernels are enqueued, by a staging
  * thread of the engine: clair_submit returns at once and clair_wait reports a failure of that work.  This is why x must stay valid
  * until clair_wait, as the reference's predict thread leaves loading and output to two others, clair/call_var.py:1331-1352.) */
+/* (clair_wait itself asks for no weights: every submit has checked what it needs, and clair_submit_site_calls needs none.  On a slot
+ * with nothing pending it returns 0.) */
 int clair_wait(clair_engine_t *e, int slot);
 /* The slot's own page-locked input buffer, [max_batch][33][8][4] float32.  A producer that writes its batch there and passes
  * this pointer as `x` to clair_submit gets a direct DMA transfer (pageable memory goes through the runtime's staging copies at
@@ -237,6 +239,59 @@ int clair_submit_ensemble(clair_engine_t *e, int slot, const void *input, int in
  * clair_decode / clair_eval, and how crafted rows (exact half-way means) reach the kernel.  clair_host_ensemble_average
  * (include/clair_host.h) is its CPU twin, bit for bit. */
 int clair_ensemble_average(clair_engine_t *e, int slot, const float *probs, int models, int n, float *out);
+
+/* -- ensemble across BAMs: sites merged and averaged on the device ------------------------------------------------------------------
+ * The reference's post-processing recipe is "many models with many BAMs": the same region called from several (e.g. down-sampled) BAMs
+ * with several checkpoints, every run printed with --output_for_ensemble, the rows of a site averaged by
+ * clair/post_processing/ensemble.py:10-75.  Different BAMs yield different candidate sites, so beyond the averaging of
+ * clair_submit_ensemble this needs a table keyed by position: a SITE TABLE (clair_amd/csrc/sites.hip.h), owned by the engine handle,
+ * that holds per site the number of (BAM, model) runs that produced it, the sum of their re-read probabilities in run order (double),
+ * and window, centre bytes and reference window of the FIRST run that had it.  Sites are rows in first-seen order -- the order the text
+ * chain prints.
+ *   for each BAM (a SOURCE):  clair_sites_begin_source with all its candidate positions, strictly ascending, then its batches through
+ *                             clair_submit_sites + clair_wait (any slot, any order), every model of the handle over each;
+ *   clair_sites_finish:       sites with at least min_count runs (ensemble.py:58-59), in chain or position order, averaged with the
+ *                             site's own count as divisor (the rule of csrc/ensemble_core.h);
+ *   clair_submit_site_calls:  the decode of a range of the output list, results as from clair_submit_ensemble.
+ * A site takes at most CLAIR_SITES_MAX_ROWS runs.  Errors (non-zero, message from clair_last_error of the engine): positions not
+ * strictly ascending, a row range outside the current source or the output list, rows after clair_sites_finish, a 65th run of a site
+ * (reported by clair_sites_add_rows and clair_sites_finish), a handle with the fused layer-2 launch.  clair_host_sites_*
+ * (include/clair_host.h) is the CPU twin, bit for bit.  Added without an ABI bump, as clair_ensemble_* was. */
+#define CLAIR_SITES_MAX_BAMS 8
+#define CLAIR_SITES_MAX_ROWS 64 /* CLAIR_SITES_MAX_BAMS * CLAIR_ENSEMBLE_MAX_MODELS */
+#define CLAIR_SITES_ORDER_CHAIN 0    /* first-seen order over "for each BAM, for each model": what `cat runs | ensemble` prints */
+#define CLAIR_SITES_ORDER_POSITION 1 /* the same rows sorted by position */
+typedef struct clair_sites clair_sites_t;
+/* A table of the engine; what is not destroyed goes with the engine (destroy tables BEFORE clair_engine_destroy, or not at all). */
+int clair_sites_create(clair_engine_t *e, clair_sites_t **out);
+void clair_sites_destroy(clair_sites_t *t);
+/* Begin the next source: positions [n] strictly ascending (n = 0: an empty source).  Waits for every slot, looks the positions up,
+ * gives those not yet in the table rows n_sites .. in ascending order, and leaves the row of every position on the device for the
+ * source's batches.  *n_new (optional): how many were new. */
+int clair_sites_begin_source(clair_sites_t *t, const int64_t *positions, int64_t n, int64_t *n_new);
+/* Candidates [first, first + n) of the current source: input, input_is_counts, input_stride_bytes exactly as for clair_submit_ex
+ * (float32 tensor or raw int16 counts, host or device address, strided); centre [n][2] as there, seq [n][33] the reference windows
+ * (NUL-padded).  Every weight image of the handle runs over the batch (one without clair_ensemble_models); each pass is added to the
+ * sites' sums and counts, and sites nobody wrote before take window, centre and seq of this batch.  Nothing comes back: pair with
+ * clair_wait(slot); the buffers must stay valid until it returns. */
+int clair_submit_sites(clair_engine_t *e, int slot, clair_sites_t *t, int64_t first, const void *input, int input_is_counts,
+                       int64_t input_stride_bytes, int n, const uint8_t *centre, const uint8_t *seq);
+/* One run's rows alone, on probabilities the caller holds: probs [n][90] packed rows for candidates [first, first + n) of the current
+ * source; x [n][33][8][4] float32, centre [n][2], seq [n][33]: each optional, what new sites take along (zeros for what is not given).  Synchronous, slot 0's
+ * buffers, needs no weights -- the twin of clair_ensemble_average, and how crafted rows reach the table. */
+int clair_sites_add_rows(clair_engine_t *e, clair_sites_t *t, int64_t first, const float *probs, int n, const float *x,
+                         const uint8_t *centre, const uint8_t *seq);
+/* Close the table and make its output list; may be repeated with another min_count or order.  *n_out: sites in the list. */
+int clair_sites_finish(clair_sites_t *t, int min_count, int order, int64_t *n_out);
+/* Entries [first, first + n) of the output list: positions [n], counts [n], seq [n][33] (each optional); the averaged rows [n][90];
+ * the windows [n][33][8][4] float32. */
+int clair_sites_info(clair_sites_t *t, int64_t first, int64_t n, int64_t *positions, int32_t *counts, uint8_t *seq);
+int clair_sites_rows(clair_sites_t *t, int64_t first, int64_t n, float *out);
+int clair_sites_windows(clair_sites_t *t, int64_t first, int64_t n, float *x);
+/* Decode entries [first, first + n) of the output list on slot `slot`: call records and / or the averaged probabilities, exactly as
+ * clair_submit_ensemble hands them back.  Needs no weights.  Pair with clair_wait(slot). */
+int clair_submit_site_calls(clair_engine_t *e, int slot, clair_sites_t *t, int64_t first, int n, clair_call_t *calls, float *gt21,
+                            float *genotype, float *indel_len1, float *indel_len2);
 
 /* -- device-resident candidate sets (benchmark / multi-GPU shard driver) ------------------------
  * The candidate set lives in HBM: x_dev [N,33,8,4]; outputs out_dev [N,90] rows laid out

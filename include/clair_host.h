@@ -255,6 +255,26 @@ int clair_host_ensemble_average(const float *probs, int models, int64_t count, f
 int clair_host_ensemble_quantise(const float *p, int64_t count, int32_t *millionths);
 int clair_host_ensemble_value(const int32_t *millionths, int64_t count, float *out);
 
+/* -- the host twin of the device site table (hostsrc/host_sites.cpp): ensemble calling across BAMs, clair_sites_* of include/clair_amd.h in
+ *    plain C++ over the same csrc/ensemble_core.h.  A table keyed by position: per site the number of runs that produced it, the sum of
+ *    their re-read probabilities in run order (double), and window, centre bytes and seq of the first run that had it; sites are rows in
+ *    first-seen order.  _begin_source: all positions of the next source, strictly ascending (*n_new: how many the table did not have).
+ *    _add_rows: one run's packed rows probs [n][90] for candidates [first, first + n) of the current source; x [n][1056] float32,
+ *    centre [n][2], seq [n][33] optional, taken by sites nobody wrote before.  _finish: the output list -- sites with at least min_count
+ *    rows (clair/post_processing/ensemble.py:58-59), order 0 = first-seen (what the text filter prints), 1 = by position; may be repeated.
+ *    _info / _rows / _windows: entries [first, first + n) of that list; _rows gives clair_ens_finish(sum, count) as float32 [n][90].
+ *    Errors: positions not strictly ascending, a row range outside the current source or the output list, rows after _finish, a 65th row
+ *    of a site. */
+typedef struct clair_host_sites clair_host_sites_t;
+int clair_host_sites_create(clair_host_sites_t **out);
+void clair_host_sites_destroy(clair_host_sites_t *t);
+int clair_host_sites_begin_source(clair_host_sites_t *t, const int64_t *positions, int64_t n, int64_t *n_new);
+int clair_host_sites_add_rows(clair_host_sites_t *t, int64_t first, const float *probs, int64_t n, const float *x, const uint8_t *centre, const uint8_t *seq);
+int clair_host_sites_finish(clair_host_sites_t *t, int min_count, int order, int64_t *n_out);
+int clair_host_sites_info(clair_host_sites_t *t, int64_t first, int64_t n, int64_t *positions, int32_t *counts, uint8_t *seq);
+int clair_host_sites_rows(clair_host_sites_t *t, int64_t first, int64_t n, float *out);
+int clair_host_sites_windows(clair_host_sites_t *t, int64_t first, int64_t n, float *x);
+
 /* -- the host twin of the device overlap filter (hostsrc/host_overlap.cpp): the walk of clair/post_processing/overlap_variant.py:237-267
  *    over rows reduced to spans, with the pair rule of csrc/overlap_core.h (which also lays the 24-byte span record out), the code the
  *    GPU runs inside clair_overlap_keep (include/clair_amd.h).  spans [n] in input order -> keep [n]: 1 for the rows the filter prints,
