@@ -116,6 +116,17 @@ SIGNATURES = {
     "clair_inflate_blocks_cb": _sig(*_INFLATE_BLOCKS),
     "clair_overlap_keep": _sig(c_int, c_vp, c_i64, c_vp),
     "clair_overlap_last_error": _sig(restype=c_cp),
+    "clair_train_create": _sig(c_int, c_int, c_int, c_int, p_vp),
+    "clair_train_destroy": _sig(c_vp, restype=None),
+    "clair_train_last_error": _sig(c_vp, restype=c_cp),
+    "clair_train_set_tensor": _sig(c_vp, c_int, c_int, c_vp, c_i64),
+    "clair_train_get_tensor": _sig(c_vp, c_int, c_int, c_vp, c_i64),
+    "clair_train_config": _sig(c_vp, c_vp, c_vp, c_vp, c_i64),
+    "clair_train_zero_grad": _sig(c_vp),
+    "clair_train_accumulate": _sig(c_vp, c_vp, c_vp, c_int, c_i64, c_int, c_vp),
+    "clair_train_step": _sig(c_vp, c_dbl, c_dbl, c_vp),
+    "clair_train_read_mask": _sig(c_vp, c_int, c_vp, c_i64),
+    "clair_train_probabilities": _sig(c_vp, c_vp),
 }
 SYMBOLS = tuple(SIGNATURES)
 ENSEMBLE_MAX_MODELS = 8                                      # CLAIR_ENSEMBLE_MAX_MODELS
@@ -788,6 +799,83 @@ class Inflater(DeviceHandle):
         self._check(self._lib.clair_inflate_blocks(self._h, _ptr(cdata), len(cdata) if cbytes is None else int(cbytes), n, _ptr(in_at), _ptr(csize),
                                                    _ptr(out_at), _ptr(out_len), _ptr(out), _ptr(status)), "clair_inflate_blocks")
         return out, status
+
+
+class Trainer(DeviceHandle):
+    """clair_train_*: the training handle (csrc/train.hip; docs/train.md) -- float32 weights, gradients and optimizer state of the 22 tensors on
+    the device, forward + loss + backward over one micro-batch at a time, Adam / momentum steps.  Needs no Engine."""
+    OPTIMIZERS = ("Adam", "SGDM")
+    LOSSES = ("FocalLoss", "CrossEntropy")
+    SETS = ("weights", "gradients", "m", "v")
+    MASK_SHAPES = ((33, 256), (192,), (96,), (96,), (96,), (96,))        # per row: LSTM2 (stored [33][n][256]), L4, L5_1..4
+
+    def __init__(self, device=0, micro_batch=1024, optimizer="Adam", loss="FocalLoss", lib_path=None):
+        self._lib = load(lib_path)
+        self.micro_batch = int(micro_batch)
+        self.last_n = 0
+        out = self._own(self._lib.clair_train_destroy, self._lib.clair_train_last_error)
+        self._check(self._lib.clair_train_create(int(device), int(micro_batch), self.OPTIMIZERS.index(optimizer), self.LOSSES.index(loss), out),
+                    "clair_train_create")
+
+    def set_tensors(self, w, which="weights"):
+        from clair_amd.weights import TENSOR_IDS, check_weights
+        check_weights(w)
+        for key, tid in TENSOR_IDS.items():
+            a = np.ascontiguousarray(w[key], dtype=np.float32)
+            self._check(self._lib.clair_train_set_tensor(self._h, self.SETS.index(which), tid, _ptr(a), a.size), "clair_train_set_tensor(%s)" % key)
+
+    def get_tensors(self, which="weights"):
+        from collections import OrderedDict
+        from clair_amd.weights import TENSOR_IDS, TENSOR_TABLE
+        out = OrderedDict()
+        for key, tid in TENSOR_IDS.items():
+            a = np.empty(TENSOR_TABLE[key], dtype=np.float32)
+            self._check(self._lib.clair_train_get_tensor(self._h, self.SETS.index(which), tid, _ptr(a), a.size), "clair_train_get_tensor(%s)" % key)
+            out[key] = a
+        return out
+
+    def config(self, task_loss_weights=None, class_weights=None, dropout_rates=None, seed=0):
+        """task_loss_weights [5], class_weights [90], dropout_rates [6] (LSTM2, L4, L5_1..4); None keeps what the handle has."""
+        arrays = []
+        for a, size in ((task_loss_weights, 5), (class_weights, 90), (dropout_rates, 6)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.shape != (size,):
+                    raise ValueError("config: an array of %d values expected, got shape %r" % (size, a.shape))
+            arrays.append(a)
+        self._check(self._lib.clair_train_config(self._h, *([_ptr(a) if a is not None else None for a in arrays] + [int(seed)])), "clair_train_config")
+
+    def zero_grad(self):
+        self._check(self._lib.clair_train_zero_grad(self._h), "clair_train_zero_grad")
+
+    def accumulate(self, x, labels, first_row=0, training=True):
+        """One micro-batch (n <= micro_batch): x [n,33,8,4], labels uint8 [n,4] -> float64 [4], the heads' losses summed over the rows."""
+        x = Engine._prep_x(x)
+        lab = Engine._prep_labels(labels, x.shape[0])
+        losses = np.zeros(4, dtype=np.float64)
+        self._check(self._lib.clair_train_accumulate(self._h, _ptr(x), _ptr(lab), x.shape[0], int(first_row), int(bool(training)), _ptr(losses)),
+                    "clair_train_accumulate")
+        self.last_n = x.shape[0]
+        return losses
+
+    def step(self, learning_rate, l2_lambda):
+        """-> (l2 loss without lambda of the weights before the update, global gradient norm before clipping)"""
+        stats = np.zeros(2, dtype=np.float64)
+        self._check(self._lib.clair_train_step(self._h, float(learning_rate), float(l2_lambda), _ptr(stats)), "clair_train_step")
+        return float(stats[0]), float(stats[1])
+
+    def read_mask(self, layer):
+        """The mask of the last training accumulate: layer 0 -> uint8 [33,n,256], 1 -> [n,192], 2..5 -> [n,96]."""
+        n = self.last_n
+        shape = (33, n, 256) if layer == 0 else (n,) + self.MASK_SHAPES[layer]
+        out = np.zeros(shape, dtype=np.uint8)
+        self._check(self._lib.clair_train_read_mask(self._h, int(layer), _ptr(out), out.size), "clair_train_read_mask")
+        return out
+
+    def probabilities(self):
+        out = np.empty((self.last_n, 90), dtype=np.float32)
+        self._check(self._lib.clair_train_probabilities(self._h, _ptr(out)), "clair_train_probabilities")
+        return out
 
 
 def overlap_keep(spans, device=0):

@@ -9,19 +9,20 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # (csrc/indel_lookup.hip is part of frontend.hip's translation unit: it works on that handle's slabs)
-SRCS = [os.path.join(HERE, "csrc", f) for f in ("engine.hip", "comm.hip", "frontend.hip", "inflate.hip", "overlap.hip")]
+SRCS = [os.path.join(HERE, "csrc", f) for f in ("engine.hip", "comm.hip", "frontend.hip", "inflate.hip", "overlap.hip", "train.hip")]
 OUT = os.path.join(HERE, "libclair_amd.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
 def csrc_digest(root=None):
     """sha256 over the kernel sources and the launch code (csrc/*.hip.h + engine.hip and the two host headers it is written over;
-    names and bytes, sorted): what a measurement of "this build" is stamped with (profiles/pmc_traffic.json, bench.py)."""
+    names and bytes, sorted): what a measurement of "this build" is stamped with (profiles/pmc_traffic.json, bench.py).  The training
+    kernels (train.hip, train_*.hip.h) are no part of it: nothing the stamped measurements run includes them."""
     import hashlib
     root = root or os.path.join(HERE, "csrc")
     h = hashlib.sha256()
     for f in sorted(os.listdir(root)):
-        if f.endswith(".hip.h") or f in ("engine.hip", "weight_images.h", "device_buffer.h", "ensemble_core.h"):
+        if (f.endswith(".hip.h") and not f.startswith("train_")) or f in ("engine.hip", "weight_images.h", "device_buffer.h", "ensemble_core.h"):
             h.update(f.encode() + b"\0" + open(os.path.join(root, f), "rb").read() + b"\0")
     return h.hexdigest()[:16]
 

@@ -1,6 +1,6 @@
 """Tensor geometry and batch defaults (counterpart of /root/reference/shared/param.py:1-16).
 
-Only the values the inference path reads are kept; training hyper-parameters are out of scope.
+Inference geometry first, then the training hyper-parameters of shared/param.py:4-37 that clair_amd.train and Clair.train read.
 """
 REPO_NAME = "Clair"
 NUM_THREADS = 12            # shared/param.py:3 (host-side threads; the GPU engine ignores it)
@@ -11,6 +11,22 @@ predictBatchSize = 1000     # shared/param.py:16
 engineBatchSize = 4096      # candidates per forward pass when --batch_size is not given: results do not depend on it, and at the reference's 1 000 the
                             # host side of call_var (queues, ctypes calls, one NumPy view per batch) keeps the engine at half its rate
                             # (3.0-4.1 against 5.3-6.7 M candidates/s inside call_variants, profiles/r04_e2e_binary.txt)
+# training (shared/param.py)
+parameterOutputPlaceHolder = 6      # :4   digits of the epoch number in a checkpoint name
+bloscBlockSize = 500                # :12  rows of one shuffling block
+trainBatchSize = 10000              # :15
+initialLearningRate = 1e-3          # :17
+learningRateDecay = 0.1             # :18
+maxLearningRateSwitch = 3           # :19
+trainingDatasetPercentage = 0.9     # :20
+l2RegularizationLambda = 0.005      # :23
+l2RegularizationLambdaDecay = 1     # :24
+default_optimizer = "Adam"          # :28  Adam / SGDM
+default_loss_function = "FocalLoss"  # :29  CrossEntropy / FocalLoss
+momentum = 0.9                      # :36
+maxEpoch = 30                       # :37
+RANDOM_SEED = None                  # :47
+trainMicroBatchSize = 1024          # rows per forward + backward pass on the device (about 0.59 MB of workspace each, docs/train.md)
 no_of_positions = 2 * flankingBaseNum + 1
 input_tensor_size = no_of_positions * matrixRow * matrixNum  # 1056
 

@@ -489,6 +489,37 @@ typedef struct clair_overlap_span clair_overlap_span_t;
 int clair_overlap_keep(int device, const clair_overlap_span_t *spans, int64_t n, uint8_t *keep);
 const char *clair_overlap_last_error(void);
 
+/* -- training on the device (python -m clair_amd.train, Clair.train / validate; csrc/train.hip, docs/train.md).
+ * A trainer is its own handle and needs no engine: float32 copies of the 22 tensors of enum clair_tensor_id in four sets (0 weights,
+ * 1 gradients, 2 Adam m | momentum accumulator, 3 Adam v), and the workspace of one micro-batch of at most `micro_batch` rows (the gates,
+ * cell states and dropout masks of both LSTM layers over 33 steps: about 0.59 MB a row).  optimizer: 0 Adam, 1 momentum SGD (0.9, no
+ * Nesterov).  loss: 0 focal loss (clair/model.py:784-805), 1 weighted cross entropy (:247-263).  Every call is synchronous.
+ * _set_tensor / _get_tensor: one tensor of one set, `count` floats, shapes as enum clair_tensor_id.
+ * _config: task_loss_weights [5] (gt21, genotype, len1, len2, l2), class_weights [90] (cross entropy; packed as the outputs are),
+ *   dropout_rates [6] (LSTM2, L4, L5_1..4) -- a NULL array keeps what the handle has -- and the seed of the dropout masks.
+ * _accumulate: one micro-batch, x [n,33,8,4] and labels [n,4] true indices, n <= micro_batch; first_row is the position of its first row
+ *   in the whole batch (a dropout mask is a hash of seed, optimizer step, layer, row of the whole batch and element, so it does not
+ *   depend on how the batch is cut).  training = 0: the forward pass without dropout and the loss (validate).  training = 1: dropout,
+ *   and the backward pass ADDS into the gradient set.  losses [4]: the heads' losses summed over the rows, without task weights.
+ * _step: adds task_loss_weights[4] * l2_lambda * w to the gradients of the 11 kernels, clips by the global norm of all 22 at 5.0 and applies
+ *   the optimizer as TensorFlow 1.x does; stats [2]: sum w^2 / 2 over the kernels before the update, the global norm before clipping.
+ *   The gradient set is left holding the regularised, unclipped gradients; _zero_grad clears it.
+ * _read_mask: the mask bytes of the last training accumulate, layer 0 LSTM2 [33][n][256], 1 L4 [n][192], 2..5 L5_1..4 [n][96].
+ * _probabilities: the packed rows [n,90] of the last accumulate.
+ * Non-zero on failure, message from clair_train_last_error (NULL handle: the failure of create). */
+typedef struct clair_trainer clair_trainer_t;
+int clair_train_create(int device, int micro_batch, int optimizer, int loss, clair_trainer_t **out);
+void clair_train_destroy(clair_trainer_t *t);
+const char *clair_train_last_error(const clair_trainer_t *t);
+int clair_train_set_tensor(clair_trainer_t *t, int set, int tensor_id, const float *host, int64_t count);
+int clair_train_get_tensor(clair_trainer_t *t, int set, int tensor_id, float *host, int64_t count);
+int clair_train_config(clair_trainer_t *t, const double *task_loss_weights, const double *class_weights, const double *dropout_rates, int64_t seed);
+int clair_train_zero_grad(clair_trainer_t *t);
+int clair_train_accumulate(clair_trainer_t *t, const float *x, const uint8_t *labels, int n, int64_t first_row, int training, double *losses);
+int clair_train_step(clair_trainer_t *t, double learning_rate, double l2_lambda, double *stats);
+int clair_train_read_mask(clair_trainer_t *t, int layer, uint8_t *host, int64_t count);
+int clair_train_probabilities(clair_trainer_t *t, float *out);
+
 #ifdef __cplusplus
 }
 #endif
