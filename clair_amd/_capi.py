@@ -107,6 +107,10 @@ SIGNATURES = {
     "clair_frontend_window_info": _sig(c_vp, c_i64, c_i64, c_vp, c_vp),
     "clair_frontend_window_counts": _sig(c_vp, c_i64, c_i64, c_vp),
     "clair_frontend_counts_device": _sig(c_vp, c_i64, restype=c_vp),
+    "clair_frontend_sample_candidates": _sig(c_vp, c_dbl, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_dbl, c_dbl, c_i64, c_int, p_i64, p_i64, p_i64),
+    "clair_frontend_pair": _sig(c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_dbl, c_i64, c_vp),
+    "clair_frontend_train_set_info": _sig(c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp),
+    "clair_frontend_train_set_counts": _sig(c_vp, c_i64, c_i64, c_vp),
     "clair_frontend_budget_inputs": _sig(c_vp, c_i64, c_vp, c_vp, c_vp),
     "clair_frontend_stats": _sig(c_vp, c_vp),
     "clair_inflate_create": _sig(c_int, c_int, p_vp),
@@ -722,6 +726,49 @@ class Frontend(DeviceHandle):
     def window_counts(self, first, n):
         counts = np.empty((n, 33, 8, 4), dtype=np.int16)
         self._check(self._lib.clair_frontend_window_counts(self._h, int(first), int(n), _ptr(counts)), "clair_frontend_window_counts")
+        return counts
+
+    @staticmethod
+    def _bed_arrays(bed):
+        if bed is None:
+            z = np.zeros(0, dtype=np.int64)
+            return z, z, -1
+        return (np.ascontiguousarray([b[0] for b in bed], dtype=np.int64), np.ascontiguousarray([b[1] for b in bed], dtype=np.int64), len(bed))
+
+    def sample_candidates(self, truth, p_near, p_outside, key, min_coverage=4, ctg_start=None, ctg_end=None, bed=None, add_truth=True):
+        """clair_frontend_sample_candidates in place of find_candidates: the sampled sites (and the truth sites of the range) become the
+        candidate list -> (n_candidates, n_near, n_outside).  truth: 1-based, ascending; key: _hostapi.train_set_key(ctg, seed, 1)."""
+        have_range = ctg_start is not None and ctg_end is not None
+        bs, be, n_bed = self._bed_arrays(bed)
+        t = np.ascontiguousarray(truth, dtype=np.int64)
+        n, near, outside = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        self._check(self._lib.clair_frontend_sample_candidates(self._h, float(min_coverage), int(ctg_start) if have_range else -1, int(ctg_end) if have_range else -1,
+                                                               _ptr(bs), _ptr(be), n_bed, _ptr(t), len(t), float(p_near), float(p_outside), int(key),
+                                                               int(bool(add_truth)), ctypes.byref(n), ctypes.byref(near), ctypes.byref(outside)),
+                    "clair_frontend_sample_candidates")
+        return int(n.value), int(near.value), int(outside.value)
+
+    def pair(self, truth, truth_labels, amp, key, bed=None):
+        """clair_frontend_pair over the windows of build_windows -> dict(v, c, kept_var, kept_non, in_set); key of stage 2."""
+        bs, be, n_bed = self._bed_arrays(bed)
+        t = np.ascontiguousarray(truth, dtype=np.int64)
+        tl = np.ascontiguousarray(truth_labels, dtype=np.uint8).reshape(len(t), 4)
+        stats = np.zeros(5, dtype=np.int64)
+        self._check(self._lib.clair_frontend_pair(self._h, _ptr(t), _ptr(tl), len(t), _ptr(bs), _ptr(be), n_bed, float(amp), int(key), _ptr(stats)),
+                    "clair_frontend_pair")
+        return dict(zip(("v", "c", "kept_var", "kept_non", "in_set"), stats.tolist()))
+
+    def train_set_info(self, first, n):
+        """-> (centres int64 [n], refseq uint8 [n,34] NUL-padded, labels uint8 [n,4], in_set uint8 [n]) of rows of the kept list"""
+        centres, seqs = np.empty(n, dtype=np.int64), np.zeros((n, 34), dtype=np.uint8)
+        labels, in_set = np.zeros((n, 4), dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        self._check(self._lib.clair_frontend_train_set_info(self._h, int(first), int(n), _ptr(centres), _ptr(seqs), _ptr(labels), _ptr(in_set)),
+                    "clair_frontend_train_set_info")
+        return centres, seqs, labels, in_set
+
+    def train_set_counts(self, first, n):
+        counts = np.empty((n, 33, 8, 4), dtype=np.int16)
+        self._check(self._lib.clair_frontend_train_set_counts(self._h, int(first), int(n), _ptr(counts)), "clair_frontend_train_set_counts")
         return counts
 
     def counts_address(self, first):

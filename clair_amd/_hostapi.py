@@ -77,6 +77,12 @@ SIGNATURES = {
     "clair_host_ensemble_quantise": _sig(vp, i64, vp),
     "clair_host_ensemble_value": _sig(vp, i64, vp),
     "clair_host_overlap_keep": _sig(vp, i64, vp),
+    "clair_host_train_set_key": _sig(cp, i64, i32, p_i64),
+    "clair_host_train_set_sample": _sig(vp, i64, vp, i64, f64, f64, i64, vp, vp, vp, p_i64, p_i64),
+    "clair_host_train_set_pair_count": _sig(vp, i64, vp, i64, vp, vp, i64, p_i64, p_i64),
+    "clair_host_train_set_ratio": _sig(i64, f64, i64, ctypes.POINTER(f64)),
+    "clair_host_train_set_pair_keep": _sig(vp, i64, vp, i64, vp, vp, i64, f64, i64, vp, p_i64, p_i64),
+    "clair_host_train_set_labels": _sig(vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp),
     "clair_host_sites_create": _sig(p_vp),
     "clair_host_sites_destroy": _sig(vp, restype=None),
     "clair_host_sites_begin_source": _sig(vp, vp, i64, p_i64),
@@ -911,3 +917,91 @@ def overlap_keep(spans):
     if load().clair_host_overlap_keep(s.ctypes.data, len(s), keep.ctypes.data) != 0:
         raise ValueError(load().clair_host_last_error().decode())
     return keep
+
+
+# ---- the training-set builder's rules over arrays (clair_host_train_set_*, csrc/train_set_core.h): the CPU twin of _capi.Frontend.sample_candidates / .pair
+TS_OUTSIDE, TS_NEAR, TS_TRUTH = 0, 1, 2
+TS_STAGE_SAMPLE, TS_STAGE_PAIR = 1, 2
+
+
+def _ts_check(rc):
+    if rc != 0:
+        raise ValueError(load().clair_host_last_error().decode())
+
+
+def merged_bed(bed):
+    """[(start, end), ...] of one contig or None -> (starts int64, ends int64, n or -1): sorted, empty intervals widened by one, merged
+    (extract_variant_candidates.BedRegions, shared/interval_tree.py)."""
+    if bed is None:
+        z = np.zeros(0, dtype=np.int64)
+        return z, z, -1
+    from .extract_variant_candidates import BedRegions
+    r = BedRegions(bed)
+    return np.array(r.start, dtype=np.int64), np.array(r.end, dtype=np.int64), len(r.start)
+
+
+def train_set_key(ctg_name, seed, stage):
+    """key(seed, ctg, stage) as a signed 64-bit integer (the bits are what counts)."""
+    key = ctypes.c_int64(0)
+    _ts_check(load().clair_host_train_set_key(ctg_name.encode(), ctypes.c_int64(int(seed) & (2 ** 64 - 1)).value, int(stage), ctypes.byref(key)))
+    return key.value
+
+
+def train_set_sample(positions, truth, p_near, p_outside, key):
+    """-> (class uint8 [n], draw uint64 [n], sampled uint8 [n], n_near, n_outside) of 1-based positions against ascending truth positions."""
+    p = np.ascontiguousarray(positions, dtype=np.int64)
+    t = np.ascontiguousarray(truth, dtype=np.int64)
+    cls, draws, sampled = np.zeros(len(p), np.uint8), np.zeros(len(p), np.uint64), np.zeros(len(p), np.uint8)
+    near, outside = ctypes.c_int64(0), ctypes.c_int64(0)
+    _ts_check(load().clair_host_train_set_sample(p.ctypes.data, len(p), t.ctypes.data, len(t), float(p_near), float(p_outside), int(key), cls.ctypes.data,
+                                                 draws.ctypes.data, sampled.ctypes.data, ctypes.byref(near), ctypes.byref(outside)))
+    return cls, draws, sampled, near.value, outside.value
+
+
+def train_set_pair_count(centres, truth, bed):
+    """-> (v, c): windows at a truth position, usable non-variant windows (bed: intervals of the contig or None)."""
+    p = np.ascontiguousarray(centres, dtype=np.int64)
+    t = np.ascontiguousarray(truth, dtype=np.int64)
+    bs, be, nb = merged_bed(bed)
+    v, c = ctypes.c_int64(0), ctypes.c_int64(0)
+    _ts_check(load().clair_host_train_set_pair_count(p.ctypes.data, len(p), t.ctypes.data, len(t), bs.ctypes.data, be.ctypes.data, nb, ctypes.byref(v), ctypes.byref(c)))
+    return v.value, c.value
+
+
+def train_set_ratio(v, amp, c):
+    r = f64(0)
+    _ts_check(load().clair_host_train_set_ratio(int(v), float(amp), int(c), ctypes.byref(r)))
+    return r.value
+
+
+def train_set_pair_keep(centres, truth, bed, r, key):
+    """-> (indices int64 of the kept windows: variant ones first, each part in input order; how many of them are variant windows)"""
+    p = np.ascontiguousarray(centres, dtype=np.int64)
+    t = np.ascontiguousarray(truth, dtype=np.int64)
+    bs, be, nb = merged_bed(bed)
+    kept = np.zeros(max(len(p), 1), dtype=np.int64)
+    kv, kn = ctypes.c_int64(0), ctypes.c_int64(0)
+    _ts_check(load().clair_host_train_set_pair_keep(p.ctypes.data, len(p), t.ctypes.data, len(t), bs.ctypes.data, be.ctypes.data, nb, float(r), int(key),
+                                                    kept.ctypes.data, ctypes.byref(kv), ctypes.byref(kn)))
+    return kept[:kv.value + kn.value], kv.value
+
+
+def train_set_pair(centres, truth, bed, amp, key):
+    """The pairing of one contig's windows -> (kept indices, stats dict v, c, r, kept_var, kept_non)."""
+    v, c = train_set_pair_count(centres, truth, bed)
+    r = train_set_ratio(v, amp, c)
+    kept, kv = train_set_pair_keep(centres, truth, bed, r, key)
+    return kept, dict(v=v, c=c, r=r, kept_var=kv, kept_non=len(kept) - kv)
+
+
+def train_set_labels(centres, centre_base, truth, truth_labels, bed):
+    """-> (labels uint8 [n,4], in_set uint8 [n]); centre_base uint8 [n] = refseq[16] of each window, truth_labels uint8 [n_truth,4]."""
+    p = np.ascontiguousarray(centres, dtype=np.int64)
+    b = np.ascontiguousarray(centre_base, dtype=np.uint8)
+    t = np.ascontiguousarray(truth, dtype=np.int64)
+    tl = np.ascontiguousarray(truth_labels, dtype=np.uint8).reshape(len(t), 4)
+    bs, be, nb = merged_bed(bed)
+    labels, in_set = np.zeros((len(p), 4), np.uint8), np.zeros(len(p), np.uint8)
+    _ts_check(load().clair_host_train_set_labels(p.ctypes.data, b.ctypes.data, len(p), t.ctypes.data, tl.ctypes.data, len(t), bs.ctypes.data, be.ctypes.data, nb,
+                                                 labels.ctypes.data, in_set.ctypes.data))
+    return labels, in_set

@@ -37,7 +37,7 @@ def needs_build():
 
 
 HOST_SRCS = [os.path.join(HERE, "hostsrc", f) for f in ("host_io.cpp", "host_decode.cpp", "host_pileup.cpp", "host_sampack.cpp",
-                                                              "host_bam.cpp", "host_inflate.cpp", "host_indel.cpp", "host_ensemble.cpp", "host_overlap.cpp", "host_sites.cpp")]
+                                                              "host_bam.cpp", "host_inflate.cpp", "host_indel.cpp", "host_ensemble.cpp", "host_overlap.cpp", "host_sites.cpp", "host_train_set.cpp")]
 HOST_OUT = os.path.join(HERE, "libclair_host.so")
 CXX = os.environ.get("CXX", "g++")
 
@@ -51,6 +51,7 @@ def build_host(force=False):
     hdrs.append(os.path.join(HERE, "csrc", "indel_lookup_core.h"))  # the table host_indel.cpp shares with the device library (csrc/indel_lookup.hip)
     hdrs.append(os.path.join(HERE, "csrc", "ensemble_core.h"))      # the averaging rule host_ensemble.cpp shares with the device (csrc/ensemble.hip.h)
     hdrs.append(os.path.join(HERE, "csrc", "overlap_core.h"))       # the pair rule and the walk host_overlap.cpp shares with the device (csrc/overlap.hip)
+    hdrs.append(os.path.join(HERE, "csrc", "train_set_core.h"))     # the sampling, pairing and label rules host_train_set.cpp shares with the device (csrc/train_set.hip)
     if (force or not os.path.isfile(HOST_OUT)
             or max([os.path.getmtime(f) for f in HOST_SRCS + hdrs]) > os.path.getmtime(HOST_OUT)):
         # -ffp-contract=off: the decode restates float32 product chains bit for bit (no fused multiply-add)

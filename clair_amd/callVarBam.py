@@ -437,10 +437,14 @@ class DeviceFrontEnd(object):
     """Both pileup stages on the GPU for one contig / region.  run() -> number of windows, or None when the run has to take the host
     path (reason logged); batches() then yields what tensor_batches yields, with the counts as clair_amd._capi.DeviceWindows."""
 
-    def __init__(self, args, device, pinned=None):
+    def __init__(self, args, device, pinned=None, candidate_step=None, window_kw=None):
         """pinned: nbytes -> page-locked uint8 array (Clair.pinned_buffer): the text is then read straight into it and parsed on the
-        device; without it (or with CLAIR_AMD_FE_PACK=host) the host packer (clair_host_sampack_*) makes the slabs."""
+        device; without it (or with CLAIR_AMD_FE_PACK=host) the host packer (clair_host_sampack_*) makes the slabs.
+        candidate_step(frontend, bed intervals or None) -> number of candidates: fixes the candidate list in place of find_candidates
+        (clair_amd.make_train_set samples it); window_kw: build_windows' drop rules where they are not the caller's (the same module)."""
         self.args, self.device, self.pinned = args, device, pinned
+        self.candidate_step = candidate_step
+        self.window_kw = dict(min_coverage=0, drop_non_iupac_centre=True) if window_kw is None else window_kw
         self.frontend = None
         self.n_windows = 0
 
@@ -579,12 +583,15 @@ class DeviceFrontEnd(object):
             if pst["evc_reads"] == 0:
                 print("No read has been process, either the genome region you specified has no read cover, or please check the correctness of your BAM input (%s)."
                       % args.bam_fn, file=sys.stderr)
-            n_cand = f.find_candidates(min_coverage=int(args.minCoverage), threshold=args.threshold,     # callVarBam.py:75: int() before it reaches the extractor
-                                       ctg_start=args.ctgStart if have_range else None, ctg_end=args.ctgEnd if have_range else None, bed=bed)
+            if self.candidate_step is not None:
+                n_cand = self.candidate_step(f, bed)
+            else:
+                n_cand = f.find_candidates(min_coverage=int(args.minCoverage), threshold=args.threshold,     # callVarBam.py:75: int() before it reaches the extractor
+                                           ctg_start=args.ctgStart if have_range else None, ctg_end=args.ctgEnd if have_range else None, bed=bed)
         else:
             f.set_candidates(given)
             n_cand = len(given)
-        n = f.build_windows(min_coverage=0, drop_non_iupac_centre=True, consider_left_edge=not args.stop_consider_left_edge)
+        n = f.build_windows(consider_left_edge=not args.stop_consider_left_edge, **self.window_kw)
         bits = pst["anomalies"] | f.stats()["anomalies"]
         if not bits and f.budget_binds():
             bits = 128

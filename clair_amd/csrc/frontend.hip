@@ -1337,6 +1337,12 @@ struct CandidateBuffers {
     DeviceBuffer kept;                           // int64_t
     DeviceBuffer block_sum;                      // uint32_t
     DeviceBuffer counts, out_centre, out_refseq; // short4, int64_t, uint8_t: sized by the kept windows of the last build
+    // the paired training set over those windows (train_set.hip: clair_frontend_pair)
+    DeviceBuffer ts_flags, ts_kept;              // uint8_t [3][windows + 1]: at a truth position, usable, kept non-variant; int64_t: indices of the kept windows
+    DeviceBuffer ts_block_sum, ts_total;         // uint32_t
+    DeviceBuffer ts_centre, ts_refseq, ts_labels, ts_in_set;   // per kept row: int64_t, uint8_t [34], uint8_t [4], uint8_t
+    DeviceBuffer ts_stage;                       // the rows clair_frontend_train_set_counts gathers before they go to the host
+    int64_t ts_n_kept = -1;
 };
 
 struct clair_frontend {
@@ -1451,6 +1457,31 @@ int finish_candidates(clair_frontend *f, int64_t *n_candidates) {
         return 1;
     f->n_candidates = n;
     *n_candidates = n;
+    return 0;
+}
+
+// the bed intervals of the contig for membership only (shared/interval_tree.py:30-32, 45-57): sorted, empty intervals widened by one, merged; on the
+// device in f->bed until the next call
+int upload_bed(clair_frontend *f, const int64_t *bed_start, const int64_t *bed_end, int64_t n_bed, const int64_t **d_start, const int64_t **d_end, int64_t *n_merged) {
+    std::vector<std::pair<int64_t, int64_t>> iv;
+    for (int64_t i = 0; i < n_bed; ++i) iv.emplace_back(bed_start[i], bed_end[i] == bed_start[i] ? bed_end[i] + 1 : bed_end[i]);
+    std::sort(iv.begin(), iv.end());
+    std::vector<int64_t> st, en;
+    for (auto &x : iv) {
+        if (x.second <= x.first) continue;
+        if (!st.empty() && x.first <= en.back()) en.back() = std::max(en.back(), x.second);
+        else { st.push_back(x.first); en.push_back(x.second); }
+    }
+    const size_t m = st.size();
+    FE_TRY(f, f->bed.ensure(2 * m * sizeof(int64_t)));
+    int64_t *d_bed = f->bed.as<int64_t>();
+    if (m) {
+        FE_TRY(f, hipMemcpy(d_bed, st.data(), m * sizeof(int64_t), hipMemcpyHostToDevice));
+        FE_TRY(f, hipMemcpy(d_bed + m, en.data(), m * sizeof(int64_t), hipMemcpyHostToDevice));
+    }
+    *d_start = d_bed;
+    *d_end = d_bed + m;
+    *n_merged = (int64_t)m;
     return 0;
 }
 
@@ -1829,27 +1860,7 @@ int clair_frontend_find_candidates(clair_frontend_t *f, double min_coverage, dou
     if (n_bed > 0 && (!bed_start || !bed_end)) return fe_fail(f, "bed intervals missing");
     FE_TRY(f, hipSetDevice(f->device));
     CandidateRule rule{min_coverage, threshold, ctg_start >= 0 && ctg_end >= 0 ? ctg_start : -1, ctg_end, nullptr, nullptr, n_bed < 0 ? -1 : 0};
-    if (n_bed > 0) {   // membership only (shared/interval_tree.py:30-32, 45-57): sort, widen empty intervals by one, merge
-        std::vector<std::pair<int64_t, int64_t>> iv;
-        for (int64_t i = 0; i < n_bed; ++i) iv.emplace_back(bed_start[i], bed_end[i] == bed_start[i] ? bed_end[i] + 1 : bed_end[i]);
-        std::sort(iv.begin(), iv.end());
-        std::vector<int64_t> st, en;
-        for (auto &x : iv) {
-            if (x.second <= x.first) continue;
-            if (!st.empty() && x.first <= en.back()) en.back() = std::max(en.back(), x.second);
-            else { st.push_back(x.first); en.push_back(x.second); }
-        }
-        const size_t m = st.size();
-        FE_TRY(f, f->bed.ensure(2 * m * sizeof(int64_t)));
-        int64_t *d_bed = f->bed.as<int64_t>();
-        if (m) {
-            FE_TRY(f, hipMemcpy(d_bed, st.data(), m * sizeof(int64_t), hipMemcpyHostToDevice));
-            FE_TRY(f, hipMemcpy(d_bed + m, en.data(), m * sizeof(int64_t), hipMemcpyHostToDevice));
-        }
-        rule.bed_start = d_bed;
-        rule.bed_end = d_bed + m;
-        rule.n_bed = (int64_t)m;
-    }
+    if (n_bed > 0 && upload_bed(f, bed_start, bed_end, n_bed, &rule.bed_start, &rule.bed_end, &rule.n_bed)) return 1;
     hipLaunchKernelGGL(fe_candidate_flags_kernel, dim3(blocks_for(f->g.n, 256)), dim3(256), 0, f->stream, f->g, rule, f->flags.as<uint8_t>());
     FE_TRY(f, hipGetLastError());
     return finish_candidates(f, n_candidates);
@@ -1967,6 +1978,7 @@ int clair_frontend_build_windows_ex(clair_frontend_t *f, int min_coverage, int d
     FE_TRY(f, hipGetLastError());
     FE_TRY(f, hipStreamSynchronize(f->stream));
     f->n_windows = kept;
+    cb.ts_n_kept = -1;           // a paired set is one of the windows it was made over
     *n_windows = kept;
     return 0;
 }
@@ -2035,3 +2047,6 @@ int clair_frontend_stats(clair_frontend_t *f, int64_t *stats) {
 
 // the indel look-up over the resident slabs: its kernels and clair_frontend_indel_table (part of this translation unit: it works on the handle's slabs)
 #include "indel_lookup.hip"
+
+// the training-set builder over the tallies and the windows: clair_frontend_sample_candidates / _pair / _train_set_* (part of this translation unit too)
+#include "train_set.hip"

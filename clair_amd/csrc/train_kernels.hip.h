@@ -5,6 +5,8 @@
 
 #include <cstdint>
 
+#include "train_set_core.h"
+
 namespace clair_train {
 
 constexpr int T_STEPS = 33, HID = 128;
@@ -12,12 +14,7 @@ constexpr float SELU_ALPHA = 1.6732632423543772848170429916717f, SELU_SCALE = 1.
 constexpr double DROPOUT_SELU_ALPHA = -1.7580993408473766;      // clair/selu.py:39
 
 // ---- dropout masks: a counter-based hash of (seed, optimizer step, layer) -> key, then (row of the whole batch, element) ----------------
-__host__ __device__ inline uint64_t mix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+__host__ __device__ inline uint64_t mix64(uint64_t z) { return clair_mix64(z); }     // train_set_core.h: the training-set draws hash with it too
 inline uint64_t mask_key(int64_t seed, int64_t step, int layer) { return mix64(mix64((uint64_t)seed) ^ mix64((uint64_t)step * 8 + (uint64_t)layer)); }
 // kept when the 24-bit draw is below keep * 2^24
 __device__ inline uint8_t mask_bit(uint64_t key, int64_t row, int64_t elem, uint32_t threshold) {

@@ -2,6 +2,7 @@
 
     python -m clair_amd GetTruth --vcf_fn truth.vcf.gz --ref_fn ref.fa --ctgName chr20 --var_fn truth.var
     python -m clair_amd evaluate --chkpnt_fn model --tensor_fn tensors.gz --var_fn truth.var [--bed_fn confident.bed]
+    python -m clair_amd evaluate --chkpnt_fn model --set_fn chr20.npz [--set_fn chr21.npz]      (sets of clair_amd.make_train_set)
 
 The data set is the one clair/utils.py:133-220 (get_training_array) builds from text, streamed instead of held:
   * bed filter as written there -- is_region_in(tree, chrom, int(coord)): membership of the position number AS IT STANDS IN THE
@@ -221,6 +222,9 @@ def build_parser():
     # additions of this implementation
     parser.add_argument('--batch_size', type=int, default=None, help="Candidates per forward pass, default: %d" % param.engineBatchSize)
     parser.add_argument('--device', type=int, default=0, help="HIP device ordinal, default: %(default)s")
+    parser.add_argument('--set_fn', type=str, action='append', default=None, metavar="NPZ",
+                        help="Training set written by make_train_set --set_fn, repeatable (the rows are concatenated); tensor_fn, var_fn and bed_fn "
+                             "will be ignored")
     parser.add_argument('--score_on', type=str, default="device", choices=("device", "host"),
                         help="Where the confusion counters are accumulated: behind the forward pass on the device, or in NumPy on "
                              "downloaded probabilities, default: %(default)s")
@@ -253,12 +257,17 @@ def main():
     try:
         print("[INFO] Loading dataset...", file=sys.stderr)
         print("[INFO] Testing on the training and validation dataset ...", file=sys.stderr)
-        counts, total = evaluate_counts(m, labelled_batches(args.tensor_fn, args.var_fn, args.bed_fn, batch), args.score_on)
+        if args.set_fn:
+            from clair_amd.make_train_set import set_batches
+            batches = set_batches(args.set_fn, batch)
+        else:
+            batches = labelled_batches(args.tensor_fn, args.var_fn, args.bed_fn, batch)
+        counts, total = evaluate_counts(m, batches, args.score_on)
         print("[INFO] The size of dataset: %d" % total, file=sys.stderr)
     finally:
         m.close()
     if total == 0:
-        sys.exit("[ERROR] no tensor of %s is part of the data set" % args.tensor_fn)
+        sys.exit("[ERROR] no tensor of %s is part of the data set" % (", ".join(args.set_fn) if args.set_fn else args.tensor_fn))
     sys.stdout.write("\n".join(report_lines(counts)) + "\n")
 
 

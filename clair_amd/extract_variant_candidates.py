@@ -7,8 +7,9 @@ observation (another base, "an insertion starts after here", "a deletion starts 
 (ExtractVariantCandidates.py:357-371).  The tallying runs in libclair_host.so (clair_host_evc_*); `CandidateFinderPy` is the
 same algorithm in plain Python, the checker the native code is pinned against (tests/test_pileup.py).
 
-Not restated: the training-set switches --gen4Training / --var_fn / --outputProb (they thin the candidates with Python's
-`random` module; the build has no training path) -- they are accepted and rejected with a message.
+Not restated here: the training-set switches --gen4Training / --var_fn / --outputProb (they thin the candidates with Python's
+`random` module) -- they are accepted and rejected with a message that names clair_amd.make_train_set, which samples the
+training sites with counter-based draws instead (docs/train_set.md).
 """
 import bisect
 import shlex
@@ -214,7 +215,8 @@ def load_reference(samtools, ref_fn, region, native=False):
 def make_candidates(args, native=True):
     """make_candidates (ExtractVariantCandidates.py:160-405), inference mode."""
     if args.gen4Training or args.var_fn is not None:
-        sys.exit("[ERROR] --gen4Training / --var_fn build training sets by random sampling; this build covers variant calling only.")
+        sys.exit("[ERROR] --gen4Training / --var_fn build training sets by random sampling; this module covers variant calling only: "
+                 "`python -m clair_amd.make_train_set` samples, pairs and labels the training sites.")
     if not isfile("%s.fai" % args.ref_fn):
         print("Fasta index %s.fai doesn't exist." % args.ref_fn, file=sys.stderr)
         sys.exit(1)

@@ -3,7 +3,8 @@
 The behaviour of the flags, the per-epoch log lines, the checkpoint names (prefix-%06d, the epoch number continued from
 --chkpnt_fn[-6:]), the learning-rate schedule and the block shuffle are the reference's (clair/train.py:18-76, 191-259), restated.  What differs:
   * the data set is the text one of clair_amd.evaluate.labelled_batches (get_training_array, clair/utils.py:133-220), held in host
-    memory, shuffled once as get_training_array does by default; the blosc binaries (--bin_fn, --train_bin_fn, --validation_bin_fn)
+    memory, shuffled once as get_training_array does by default -- or the same rows from the sets of clair_amd.make_train_set
+    (--set_fn, repeatable); the blosc binaries (--bin_fn, --train_bin_fn, --validation_bin_fn)
     are not read;
   * the first int(N * 0.9) rows train in batches of --batch_size, the rest validate in batches of param.predictBatchSize; between epochs
     the first int(n_train / 500) blocks of 500 rows are permuted (permute_leading_blocks);
@@ -74,16 +75,21 @@ def row_order(block_index_list, dataset_size):
     return np.concatenate([np.arange(b * size, min((b + 1) * size, dataset_size)) for b in block_index_list]) if dataset_size else np.zeros(0, dtype=int)
 
 
-def load_dataset(tensor_fn, var_fn, bed_fn):
-    """get_training_array (clair/utils.py:133-220): -> (X float32 [N,33,8,4], labels uint8 [N,4]), shuffled once."""
-    from clair_amd.evaluate import labelled_batches
-    xs, ys = [], []
-    for X, _keys, labels in labelled_batches(tensor_fn, var_fn, bed_fn, param.engineBatchSize):
-        xs.append(np.array(X, dtype=np.float32))
-        ys.append(labels)
-    if not xs:
-        return np.zeros((0, 33, 8, 4), dtype=np.float32), np.zeros((0, 4), dtype=np.uint8)
-    X, Y = np.concatenate(xs, axis=0), np.concatenate(ys, axis=0)
+def load_dataset(tensor_fn, var_fn, bed_fn, set_fn=None):
+    """get_training_array (clair/utils.py:133-220): -> (X float32 [N,33,8,4], labels uint8 [N,4]), shuffled once.  set_fn: the sets
+    make_train_set wrote for the same sites, in place of the text (the same rows, the same bits)."""
+    if set_fn:
+        from clair_amd.make_train_set import load_sets
+        X, _keys, Y = load_sets(set_fn)
+    else:
+        from clair_amd.evaluate import labelled_batches
+        xs, ys = [], []
+        for X, _keys, labels in labelled_batches(tensor_fn, var_fn, bed_fn, param.engineBatchSize):
+            xs.append(np.array(X, dtype=np.float32))
+            ys.append(labels)
+        if not xs:
+            return np.zeros((0, 33, 8, 4), dtype=np.float32), np.zeros((0, 4), dtype=np.uint8)
+        X, Y = np.concatenate(xs, axis=0), np.concatenate(ys, axis=0)
     order = np.random.permutation(len(X))
     return X[order], Y[order]
 
@@ -178,6 +184,9 @@ def build_parser():
         parser.add_argument(flag, action="store_true", help=text)
     for flag, kind, default, text in OPTIONS:
         parser.add_argument(flag, type=kind, default=default, help=text)
+    parser.add_argument("--set_fn", type=str, action="append", default=None, metavar="NPZ",
+                        help="training set written by make_train_set --set_fn, repeatable (the rows are concatenated); --tensor_fn, --var_fn and "
+                             "--bed_fn are ignored then")
     return parser
 
 
@@ -221,12 +230,12 @@ def main():
         sys.exit("[ERROR] %s" % exc)
     try:
         logging.info("[INFO] Loading dataset...")
-        X, Y = load_dataset(args.tensor_fn, args.var_fn, args.bed_fn)
+        X, Y = load_dataset(args.tensor_fn, args.var_fn, args.bed_fn, args.set_fn)
         logging.info("[INFO] The size of dataset: %d" % len(X))
         n_train, n_validation, _ = split_sizes(len(X))
         if n_train == 0 or n_validation == 0:
             sys.exit("[ERROR] %d tensors of %s make the data set: too few to split %d%% / %d%%"
-                     % (len(X), args.tensor_fn, round(param.trainingDatasetPercentage * 100), round((1 - param.trainingDatasetPercentage) * 100)))
+                     % (len(X), ", ".join(args.set_fn) if args.set_fn else args.tensor_fn, round(param.trainingDatasetPercentage * 100), round((1 - param.trainingDatasetPercentage) * 100)))
         history = train_model(m, X, Y, args.learning_rate, args.lambd, args.ochk_prefix, args.chkpnt_fn, args.batch_size, args.max_epochs)
         best_epoch = min(history)[1]        # the smallest validation total; the earlier epoch of equal ones
         logging.info("[INFO] Best validation loss at epoch: %d" % best_epoch)

@@ -452,6 +452,27 @@ int clair_frontend_build_windows_ex(clair_frontend_t *f, int min_coverage, int d
 int clair_frontend_window_info(clair_frontend_t *f, int64_t first, int64_t n, int64_t *centres, char *refseq /*[n][34], NUL-padded*/);
 int clair_frontend_window_counts(clair_frontend_t *f, int64_t first, int64_t n, int16_t *counts /*[n][33][8][4], host*/);
 const int16_t *clair_frontend_counts_device(clair_frontend_t *f, int64_t first);   /* device address of window `first`; NULL before build_windows */
+/* -- the training set (python -m clair_amd.make_train_set; csrc/train_set.hip, the rules in csrc/train_set_core.h, docs/train_set.md).
+ * _sample_candidates takes the place of _find_candidates: the eligible positions are those of its rule with threshold 0 (what
+ * ExtractVariantCandidates.py --gen4Training makes of it); one that is no truth position stays when its draw u(key, position) <=
+ * p_near (its nearest truth position is 15 or 16 away) or p_outside (every other one).  truth_positions [n_truth]: 1-based, ascending,
+ * duplicates allowed.  add_truth != 0 adds the truth positions inside [ctg_start, ctg_end] to the list.  n_near / n_outside: the
+ * sampled sites per class, the reference's two log counters.  key: clair_host_train_set_key(ctg, seed, 1) (include/clair_host.h).
+ * _pair, after _build_windows: PairWithNonVariants.py over those windows -- v windows at a truth position, c usable non-variant
+ * windows (position, as it stands, inside the bed; n_bed < 0: no bed file), r = min(1, v amp / c), kept: the v windows, then the usable
+ * ones with u(key, position) < r (key of stage 2), each part in position order -- and get_training_array's labels: truth_labels
+ * [n_truth][4] true indices per truth row (the last row of a position wins), homozygous reference of the centre base elsewhere; a row
+ * is in the data set when its position is inside the bed and its centre base is one of ACGTU.
+ * stats[5] = v, c, kept variant windows, kept non-variant windows, rows in the data set.
+ * _train_set_info / _train_set_counts: rows [first, first + n) of the kept list, the counts gathered on the device.
+ * clair_host_train_set_* (include/clair_host.h) gives the same bytes on the CPU. */
+int clair_frontend_sample_candidates(clair_frontend_t *f, double min_coverage, int64_t ctg_start, int64_t ctg_end, const int64_t *bed_start, const int64_t *bed_end,
+                                     int64_t n_bed, const int64_t *truth_positions, int64_t n_truth, double p_near, double p_outside, int64_t key, int add_truth,
+                                     int64_t *n_candidates, int64_t *n_near, int64_t *n_outside);
+int clair_frontend_pair(clair_frontend_t *f, const int64_t *truth_positions, const uint8_t *truth_labels, int64_t n_truth, const int64_t *bed_start,
+                        const int64_t *bed_end, int64_t n_bed, double amp, int64_t key, int64_t *stats);
+int clair_frontend_train_set_info(clair_frontend_t *f, int64_t first, int64_t n, int64_t *centres, char *refseq, uint8_t *labels, uint8_t *in_set);
+int clair_frontend_train_set_counts(clair_frontend_t *f, int64_t first, int64_t n, int16_t *counts);
 /* What the budget replay needs: tuples appended per alignment of slab `slab` (read_tuples, may be NULL), all candidate centres and
  * the tuples each window held (0 for a window no alignment opened); either pair may be NULL. */
 int clair_frontend_budget_inputs(clair_frontend_t *f, int64_t slab, uint64_t *read_tuples, int64_t *centres, uint64_t *window_tuples);

@@ -285,6 +285,25 @@ typedef struct clair_overlap_span clair_overlap_span_t;
 #endif
 int clair_host_overlap_keep(const clair_overlap_span_t *spans, int64_t n, uint8_t *keep);
 
+/* -- the host twin of the device training-set builder (hostsrc/host_train_set.cpp; docs/train_set.md), with the rules of
+ *    csrc/train_set_core.h, the code the GPU runs inside clair_frontend_sample_candidates / clair_frontend_pair (include/clair_amd.h).
+ *    Positions are 1-based; truth [n_truth] ascending (duplicates allowed); bed intervals of the contig sorted, merged, 0-based half-open,
+ *    n_bed < 0 = no bed file.  _key: the key of a contig's draws, stage 1 = site sampling, 2 = pairing.  _sample: per position its class
+ *    (0 outside, 1 near, 2 truth), its 53-bit draw and whether it is sampled (any of the three may be NULL), and the two counters of the
+ *    sampled sites.  _pair_count: v = windows at a truth position, c = usable non-variant windows; _ratio: r = min(1, v amp / c), 1 for
+ *    c == 0; _pair_keep: indices of the kept windows, the variant ones first, each part in input order.  _labels: the four true indices
+ *    and the data-set flag per window (truth_labels [n_truth][4]; the last row of a position wins). */
+int clair_host_train_set_key(const char *ctg_name, int64_t seed, int stage, int64_t *key);
+int clair_host_train_set_sample(const int64_t *positions, int64_t n, const int64_t *truth, int64_t n_truth, double p_near, double p_outside, int64_t key,
+                                uint8_t *cls, uint64_t *draws, uint8_t *sampled, int64_t *n_near, int64_t *n_outside);
+int clair_host_train_set_pair_count(const int64_t *centres, int64_t n, const int64_t *truth, int64_t n_truth, const int64_t *bed_start, const int64_t *bed_end,
+                                    int64_t n_bed, int64_t *v, int64_t *c);
+int clair_host_train_set_ratio(int64_t v, double amp, int64_t c, double *r);
+int clair_host_train_set_pair_keep(const int64_t *centres, int64_t n, const int64_t *truth, int64_t n_truth, const int64_t *bed_start, const int64_t *bed_end,
+                                   int64_t n_bed, double r, int64_t key, int64_t *kept, int64_t *n_kept_var, int64_t *n_kept_non);
+int clair_host_train_set_labels(const int64_t *centres, const uint8_t *centre_base, int64_t n, const int64_t *truth, const uint8_t *truth_labels, int64_t n_truth,
+                                const int64_t *bed_start, const int64_t *bed_end, int64_t n_bed, uint8_t *labels, uint8_t *in_set);
+
 #ifdef __cplusplus
 }
 #endif
