@@ -131,6 +131,7 @@ SIGNATURES = {
     "clair_train_step": _sig(c_vp, c_dbl, c_dbl, c_vp),
     "clair_train_read_mask": _sig(c_vp, c_int, c_vp, c_i64),
     "clair_train_probabilities": _sig(c_vp, c_vp),
+    "clair_train_accuracy": _sig(c_vp, c_vp),
 }
 SYMBOLS = tuple(SIGNATURES)
 ENSEMBLE_MAX_MODELS = 8                                      # CLAIR_ENSEMBLE_MAX_MODELS
@@ -923,6 +924,13 @@ class Trainer(DeviceHandle):
         out = np.empty((self.last_n, 90), dtype=np.float32)
         self._check(self._lib.clair_train_probabilities(self._h, _ptr(out)), "clair_train_probabilities")
         return out
+
+    def accuracy(self):
+        """-> int64 [4]: rows of the last accumulate each head gets right (gt21, genotype, smaller and larger of the sorted indel-length pair),
+        counted on the device; clair_amd.model.accuracy_counts is the NumPy twin."""
+        tp = np.zeros(4, dtype=np.int64)
+        self._check(self._lib.clair_train_accuracy(self._h, _ptr(tp)), "clair_train_accuracy")
+        return tp
 
 
 def overlap_keep(spans, device=0):

@@ -7,7 +7,8 @@
 // their pre-activation gradients in place by the backward pass), cell states c [dir][33][n][128].
 //
 // The recurrence is one GEMM launch (z_t += h_prev . K_h) and one pointwise launch per step and direction, forward and backward: 264 small
-// launches per pass and layer pair.  Everything else is tgemm (csrc/train_gemm.hip.h) and the kernels of csrc/train_kernels.hip.h.
+// launches per pass and layer pair.  Everything else is tgemm (csrc/train_gemm.hip.h), the kernels of csrc/train_kernels.hip.h and the accuracy
+// count of csrc/train_accuracy.hip.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -18,6 +19,7 @@
 
 #include "../../include/clair_amd.h"
 #include "device_buffer.h"
+#include "train_accuracy.hip.h"
 #include "train_gemm.hip.h"
 #include "train_kernels.hip.h"
 
@@ -48,7 +50,7 @@ struct clair_trainer {
     int last_n = 0, last_training = 0;
     DeviceBuffer sets[4];                                  // weights, gradients, m | momentum, v
     DeviceBuffer x, xt, z1, c1, a1, z2, c2, a2, a2d, da2, da1, dhrec, dc, l3, dl3, y4, d4, dd4, y5, d5, dd5, lg, probs, dz;
-    DeviceBuffer m_lstm2, m4, m5, labels, row_loss, sums, partial, stats;
+    DeviceBuffer m_lstm2, m4, m5, labels, row_loss, sums, partial, stats, tp;
     std::string error;
 };
 
@@ -104,6 +106,7 @@ int train_init(clair_trainer *t) {
     TRAIN_TRY(nullptr, t->sums.ensure(4 * sizeof(double)));
     TRAIN_TRY(nullptr, t->partial.ensure(2 * RED_BLOCKS * sizeof(double)));
     TRAIN_TRY(nullptr, t->stats.ensure(3 * sizeof(double)));
+    TRAIN_TRY(nullptr, t->tp.ensure(4 * sizeof(int64_t)));
     for (double &w : t->class_weights) w = 1.0;
     return 0;
 }
@@ -431,6 +434,18 @@ int clair_train_probabilities(clair_trainer_t *t, float *out) {
     if (!t->last_n) return train_fail(t, "no accumulate to read probabilities of");
     TRAIN_TRY(t, hipSetDevice(t->device));
     TRAIN_TRY(t, hipMemcpyAsync(out, t->probs.p, (size_t)t->last_n * 90 * 4, hipMemcpyDeviceToHost, t->stream));
+    TRAIN_TRY(t, hipStreamSynchronize(t->stream));
+    return 0;
+}
+
+int clair_train_accuracy(clair_trainer_t *t, int64_t *tp) {
+    if (!t) return train_fail(nullptr, "trainer handle is NULL");
+    if (!tp) return train_fail(t, "tp is NULL");
+    if (!t->last_n) return train_fail(t, "no accumulate to count the accuracy of");
+    TRAIN_TRY(t, hipSetDevice(t->device));
+    TRAIN_TRY(t, hipMemsetAsync(t->tp.p, 0, 4 * sizeof(int64_t), t->stream));
+    LAUNCH(t, accuracy_kernel, t->last_n, t->probs.as<float>(), t->labels.as<uint8_t>(), t->last_n, t->tp.as<unsigned long long>());
+    TRAIN_TRY(t, hipMemcpyAsync(tp, t->tp.p, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, t->stream));
     TRAIN_TRY(t, hipStreamSynchronize(t->stream));
     return 0;
 }

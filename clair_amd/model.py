@@ -11,6 +11,8 @@ Mirrors the members call_var / evaluate / train use on the reference class
   .prediction                  :964
   .close() / __del__           :872-876, 1149-1152
   .train(batchX, batchY)       :913-944  one optimizer step on the batch -> training_loss_on_one_batch
+  .lr_train(batchX, batchY)    :878-911  train() that keeps the training pass's prediction and its accuracy (docs/train_clr.md)
+  .clr(step, step_size, max_lr, mode)  :1086-1103  the cyclical learning rate, advanced once per batch
   .validate(batchX, batchY)    :968-1008 the loss members of one batch
   .save_parameters(prefix)     :1010-1014 a checkpoint under the reference's variable names
   .set_learning_rate / decay_learning_rate / set_l2_regularization_lambda / decay_l2_regularization_lambda / set_task_loss_weights
@@ -43,6 +45,26 @@ def training_defaults():
         optimizer_name=param.default_optimizer,
         loss_function=param.default_loss_function,
     )
+
+
+def accuracy_counts(probabilities, labels):
+    """The learning-rate finder's accuracy rule (clair/learning_rate_finder.py:21-73) as counts: probabilities [n,90] packed as the outputs
+    are, labels [n,4] true indices -> int64 [4], the rows whose gt21 arg-max is the label, whose genotype arg-max is, and -- the two
+    indel-length heads taken as sorted pairs -- whose smaller arg-max is the smaller label and whose larger is the larger.  np.argmax: the
+    lowest index among equal values.  The NumPy twin of clair_train_accuracy (csrc/train_accuracy.hip.h)."""
+    p, y = np.asarray(probabilities), np.asarray(labels).astype(np.int64)
+    if p.ndim != 2 or p.shape[1] != 90 or y.shape != (p.shape[0], 4):
+        raise ValueError("probabilities [n,90] and labels [n,4] expected, got %r and %r" % (p.shape, y.shape))
+    top = np.stack([np.argmax(p[:, a:b], axis=1) for a, b in ((0, 21), (21, 24), (24, 57), (57, 90))], axis=1).reshape(-1, 4)
+    hits = [top[:, 0] == y[:, 0], top[:, 1] == y[:, 1],
+            top[:, 2:].min(axis=1) == y[:, 2:].min(axis=1), top[:, 2:].max(axis=1) == y[:, 2:].max(axis=1)]
+    return np.array([int(h.sum()) for h in hits], dtype=np.int64)
+
+
+def accuracy_from_counts(tp, n):
+    """The reference's arithmetic in its order (clair/learning_rate_finder.py:68-72): the mean of the four heads' hit rates over n rows."""
+    n = n + 0.0
+    return (tp[0] / n + tp[1] / n + tp[2] / n + tp[3] / n) / 4
 
 
 class Clair(object):
@@ -147,34 +169,55 @@ class Clair(object):
             return np.ascontiguousarray(y, dtype=np.uint8)
         raise ValueError("batchY must be [n,90] one-hot rows or [n,4] indices, got shape %r" % (y.shape,))
 
-    def _accumulate(self, batchX, batchY, training):
+    def _accumulate(self, batchX, batchY, training, accuracy=False):
+        """-> (trainer, losses [4], probabilities of each micro-batch -- kept for validation and when `accuracy` is asked for --, tp int64 [4]:
+        the accuracy counts of the micro-batches added up on the way, zeros unless asked for)"""
         t = self._configure_trainer()
         x, lab = np.asarray(batchX), self.label_indices(batchY)
-        losses, probabilities = np.zeros(4), []
+        losses, probabilities, tp = np.zeros(4), [], np.zeros(4, dtype=np.int64)
         for first in range(0, x.shape[0], self.micro_batch):
             losses += t.accumulate(x[first:first + self.micro_batch], lab[first:first + self.micro_batch], first_row=first, training=training)
-            if not training:
+            if accuracy:
+                tp += t.accuracy()
+            if accuracy or not training:
                 probabilities.append(t.probabilities())
-        return t, losses, probabilities
+        return t, losses, probabilities, tp
 
     def train(self, batchX, batchY):
         """clair/model.py:913-944: one optimizer step on the batch, cut into micro-batches whose gradients are summed.
         training_loss_on_one_batch is the weighted total with lambda * L2 (:697-709)."""
         t = self.trainer
         t.zero_grad()
-        t, losses, _ = self._accumulate(batchX, batchY, True)
+        t, losses, _, _ = self._accumulate(batchX, batchY, True)
+        return self._step(t, losses), None
+
+    def lr_train(self, batchX, batchY):
+        """clair/model.py:878-911: train() that also keeps what the training forward pass (dropout on) predicted, for the learning-rate finder.
+        `prediction`: the four heads' probabilities, shaped as validation_prediction; `training_tp`: int64 [4], the rows each head gets right
+        under the finder's rule, counted on the device per micro-batch (clair_train_accuracy) and added up; `training_accuracy`: the
+        accuracy of those counts (accuracy_from_counts).  -> (prediction, training_loss_on_one_batch, None)"""
+        t = self.trainer
+        t.zero_grad()
+        t, losses, probabilities, tp = self._accumulate(batchX, batchY, True, accuracy=True)
+        self.prediction = _capi.split_outputs(np.concatenate(probabilities, axis=0))
+        self.training_tp = tp
+        self.training_accuracy = accuracy_from_counts(tp, len(self.prediction[0]))
+        return self.prediction, self._step(t, losses), None
+
+    def _step(self, t, losses):
+        """The optimizer step after the micro-batches of a batch -> training_loss_on_one_batch"""
         l2, norm = t.step(self.learning_rate_value, self.l2_regularization_lambda_value)
         self._host_stale = self._engine_stale = True
         self._l2 = None
         self.gradient_norm_on_one_batch = norm
         self.training_loss_on_one_batch = float(np.dot(self.task_loss_weights[:4], losses) + self.task_loss_weights[4] * l2 * self.l2_regularization_lambda_value)
         self.training_summary_on_one_batch = None
-        return self.training_loss_on_one_batch, None
+        return self.training_loss_on_one_batch
 
     def validate(self, batchX, batchY):
         """clair/model.py:968-1008: the forward pass without dropout; lambda is fed as 0 there, so the total has no L2 part, and l2_loss is
         the L2 sum times param.l2RegularizationLambda."""
-        t, losses, probabilities = self._accumulate(batchX, batchY, False)
+        t, losses, probabilities, _ = self._accumulate(batchX, batchY, False)
         self.validation_prediction = _capi.split_outputs(np.concatenate(probabilities, axis=0))
         self.validation_loss_on_one_batch = float(np.dot(self.task_loss_weights[:4], losses))
         self.gt21_loss, self.genotype_loss, self.indel_length_loss_1, self.indel_length_loss_2 = (float(v) for v in losses)
@@ -213,6 +256,20 @@ class Clair(object):
     def decay_learning_rate(self):
         self.learning_rate_value = self.learning_rate_value * self.learning_rate_decay_rate
         return self.learning_rate_value
+
+    def clr(self, global_step, step_size, max_lr, mode="tri"):
+        """clair/model.py:1086-1103, the cyclical learning rate: one call per batch.  The rate climbs from param.clr_min_lr to max_lr over
+        step_size calls and back over the next step_size; the call after that (the one whose 1 + step / (2 step_size) passes 2) starts the
+        next cycle at the floor, with max_lr halved (tri2), times param.clrGamma (exp) or as it was (tri).
+        -> (learning_rate_value, global_step, max_lr): the caller carries the last two into its next call.  The arithmetic is the
+        reference's, operation by operation, so the rates are equal as float64 values."""
+        global_step += 1
+        if 1 + global_step / (2 * step_size) > 2:
+            global_step = 0
+            max_lr = max_lr / 2 if mode == "tri2" else max_lr * param.clrGamma ** 1 if mode == "exp" else max_lr
+        x = global_step / step_size
+        self.learning_rate_value = param.clr_min_lr + (max_lr - param.clr_min_lr) * np.maximum(0, x if x <= 1 else 2 - x)
+        return self.learning_rate_value, global_step, max_lr
 
     def set_l2_regularization_lambda(self, l2_regularization_lambda):
         self.l2_regularization_lambda_value = l2_regularization_lambda

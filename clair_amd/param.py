@@ -23,8 +23,15 @@ l2RegularizationLambda = 0.005      # :23
 l2RegularizationLambdaDecay = 1     # :24
 default_optimizer = "Adam"          # :28  Adam / SGDM
 default_loss_function = "FocalLoss"  # :29  CrossEntropy / FocalLoss
+clr_max_lr = 3e-2                   # :32  train_clr: the rate a cycle rises to (before tri2 / exp decay it)
+clr_min_lr = 1e-4                   # :33  the floor of every cyclical rate, the finder's sweep included
+stepsizeConstant = 1                # :34  half a cycle, in epochs' worth of batches
+clrGamma = 0.95                     # :35  exp mode: max_lr is multiplied by it after each cycle
 momentum = 0.9                      # :36
 maxEpoch = 30                       # :37
+min_lr = 1e-6                       # :40  learning_rate_finder: only logged (the sweep starts from clr_min_lr)
+max_lr = 1e-1                       # :41  learning_rate_finder: the top of the sweep
+lr_finder_max_epoch = 1             # :42
 RANDOM_SEED = None                  # :47
 trainMicroBatchSize = 1024          # rows per forward + backward pass on the device (about 0.59 MB of workspace each, docs/train.md)
 no_of_positions = 2 * flankingBaseNum + 1

@@ -98,25 +98,36 @@ def checkpoint_name(prefix, epoch):
     return "%s-%0*d" % (prefix, param.parameterOutputPlaceHolder, epoch)
 
 
-def run_epoch(m, X, Y, rows, n_train, batch_size):
+def run_epoch(m, X, Y, rows, n_train, batch_size, before_batch=None, train_batch=None):
     """One pass: optimizer steps over the first n_train rows of `rows`, then validation over the rest.
-    -> (training total, [validation total, gt21, genotype, indel 1, indel 2])"""
+    -> (training total, [validation total, gt21, genotype, indel 1, indel 2])
+    The two hooks are train_clr's and learning_rate_finder's: before_batch() runs before every batch, training or validation, and
+    train_batch(x, y) takes a training batch in place of m.train."""
+    train_batch = train_batch or m.train
     trained = 0.0
     for at in range(0, n_train, batch_size):
         pick = rows[at:min(at + batch_size, n_train)]
-        m.train(X[pick], Y[pick])
+        if before_batch is not None:
+            before_batch()
+        train_batch(X[pick], Y[pick])
         trained += m.training_loss_on_one_batch
     validated = np.zeros(5)
     for at in range(n_train, len(rows), param.predictBatchSize):
         pick = rows[at:at + param.predictBatchSize]
+        if before_batch is not None:
+            before_batch()
         m.validate(X[pick], Y[pick])
         validated += (m.validation_loss_on_one_batch, m.gt21_loss, m.genotype_loss, m.indel_length_loss_1, m.indel_length_loss_2)
     return trained, validated
 
 
-def train_model(m, X, Y, learning_rate, lambd, prefix, start_from, batch_size, max_epochs):
+def train_model(m, X, Y, learning_rate, lambd, prefix, start_from, batch_size, max_epochs, last_epoch=None, before_batch=None, train_batch=None,
+                after_epoch=None):
     """The epoch loop -> [(validation total, epoch), ...].  Log lines, checkpoint names and the schedule are the reference's
-    (clair/train.py:94-96, 191-235); the loop also ends after max_epochs."""
+    (clair/train.py:94-96, 191-235); the loop also ends after max_epochs.
+    train_clr and learning_rate_finder run the same loop with a rate of their own: last_epoch (an absolute epoch number) bounds it in
+    place of max_epochs and takes the learning-rate switches and the early stop out, before_batch / train_batch are run_epoch's hooks,
+    and after_epoch(epoch) runs once the epoch's checkpoint is written."""
     first_epoch = 1
     if start_from is not None:
         m.restore_parameters(os.path.abspath(start_from))
@@ -130,20 +141,22 @@ def train_model(m, X, Y, learning_rate, lambd, prefix, start_from, batch_size, m
     blocks = np.arange(-(-len(X) // param.bloscBlockSize))
     history, totals = [], []
     switches_left, epochs_at_this_rate = param.maxLearningRateSwitch, 0
-    for epoch in range(first_epoch, first_epoch + max_epochs):
+    for epoch in range(first_epoch, first_epoch + max_epochs if last_epoch is None else last_epoch + 1):
         if epoch > first_epoch:
             blocks = permute_leading_blocks(blocks, n_train_blocks)
             logging.info("[INFO] Shuffled: " + " ".join(str(b) for b in np.append(blocks[:5], blocks[-5:])))
         epoch_started = time()
-        trained, validated = run_epoch(m, X, Y, row_order(blocks, len(X)), n_train, batch_size)
+        trained, validated = run_epoch(m, X, Y, row_order(blocks, len(X)), n_train, batch_size, before_batch, train_batch)
         logging.info("%d Training loss: %s" % (epoch, trained / n_train))
         logging.info("%d Validation loss (Total/Base/Genotype/Indel_1_2):\t%s" % (epoch, "\t".join(str(v / n_validation) for v in validated)))
         logging.info("[INFO] Epoch time elapsed: %.2f s" % (time() - epoch_started))
         history.append((validated[0], epoch))
         totals.append(validated[0])
         m.save_parameters(os.path.abspath(checkpoint_name(prefix, epoch)))
+        if after_epoch is not None:
+            after_epoch(epoch)
         epochs_at_this_rate += 1
-        if learning_rate_is_due(epochs_at_this_rate, totals):
+        if last_epoch is None and learning_rate_is_due(epochs_at_this_rate, totals):
             switches_left -= 1
             if switches_left == 0:
                 break
@@ -178,12 +191,14 @@ OPTIONS = (
 )
 
 
-def build_parser():
-    parser = ArgumentParser(description="Train a model on the GPU from text tensors and truth rows")
+def build_parser(description="Train a model on the GPU from text tensors and truth rows", leave_out=()):
+    """leave_out: flags of OPTIONS a sibling command does not take (learning_rate_finder)."""
+    parser = ArgumentParser(description=description)
     for flag, text in SWITCHES:
         parser.add_argument(flag, action="store_true", help=text)
     for flag, kind, default, text in OPTIONS:
-        parser.add_argument(flag, type=kind, default=default, help=text)
+        if flag not in leave_out:
+            parser.add_argument(flag, type=kind, default=default, help=text)
     parser.add_argument("--set_fn", type=str, action="append", default=None, metavar="NPZ",
                         help="training set written by make_train_set --set_fn, repeatable (the rows are concatenated); --tensor_fn, --var_fn and "
                              "--bed_fn are ignored then")
@@ -200,14 +215,9 @@ def check_arguments(args):
         sys.exit("[ERROR] --batch_size, --micro_batch and --max_epochs are at least 1")
 
 
-def main():
-    logging.basicConfig(format='%(message)s', level=logging.INFO)
-    parser = build_parser()
-    args = parser.parse_args()
-    if len(sys.argv) == 1:
-        parser.print_help()
-        sys.exit(1)
-    check_arguments(args)
+def run_command(args, loop):
+    """What main() does once the arguments are read and checked, shared with train_clr and learning_rate_finder: seed, model, data set,
+    loop(m, X, Y) -> [(validation total, epoch), ...], then the best epoch restored and evaluate's report printed."""
     seed = args.seed if args.seed is not None else param.RANDOM_SEED
     random.seed(seed)
     np.random.seed(seed)
@@ -236,7 +246,7 @@ def main():
         if n_train == 0 or n_validation == 0:
             sys.exit("[ERROR] %d tensors of %s make the data set: too few to split %d%% / %d%%"
                      % (len(X), ", ".join(args.set_fn) if args.set_fn else args.tensor_fn, round(param.trainingDatasetPercentage * 100), round((1 - param.trainingDatasetPercentage) * 100)))
-        history = train_model(m, X, Y, args.learning_rate, args.lambd, args.ochk_prefix, args.chkpnt_fn, args.batch_size, args.max_epochs)
+        history = loop(m, X, Y)
         best_epoch = min(history)[1]        # the smallest validation total; the earlier epoch of equal ones
         logging.info("[INFO] Best validation loss at epoch: %d" % best_epoch)
         m.restore_parameters(os.path.abspath(checkpoint_name(args.ochk_prefix, best_epoch)))
@@ -245,6 +255,17 @@ def main():
     finally:
         m.close()
     sys.stdout.write("\n".join(evaluate.report_lines(counts)) + "\n")
+
+
+def main():
+    logging.basicConfig(format='%(message)s', level=logging.INFO)
+    parser = build_parser()
+    args = parser.parse_args()
+    if len(sys.argv) == 1:
+        parser.print_help()
+        sys.exit(1)
+    check_arguments(args)
+    run_command(args, lambda m, X, Y: train_model(m, X, Y, args.learning_rate, args.lambd, args.ochk_prefix, args.chkpnt_fn, args.batch_size, args.max_epochs))
 
 
 if __name__ == "__main__":

@@ -527,6 +527,10 @@ const char *clair_overlap_last_error(void);
  *   The gradient set is left holding the regularised, unclipped gradients; _zero_grad clears it.
  * _read_mask: the mask bytes of the last training accumulate, layer 0 LSTM2 [33][n][256], 1 L4 [n][192], 2..5 L5_1..4 [n][96].
  * _probabilities: the packed rows [n,90] of the last accumulate.
+ * _accuracy: tp [4], how many rows of the last accumulate (either mode) each head gets right under the learning-rate finder's rule
+ *   (clair/learning_rate_finder.py:21-73), counted on the device from the probabilities and labels where they lie (csrc/train_accuracy.hip.h):
+ *   tp[0] arg-max of the 21 gt21 probabilities = label, tp[1] the same for the genotype; the indel lengths as sorted pairs -- tp[2] the smaller
+ *   of the two arg-maxes = the smaller of the two labels, tp[3] the larger = the larger.  Arg-max is the lowest index among equal values.
  * Non-zero on failure, message from clair_train_last_error (NULL handle: the failure of create). */
 typedef struct clair_trainer clair_trainer_t;
 int clair_train_create(int device, int micro_batch, int optimizer, int loss, clair_trainer_t **out);
@@ -540,6 +544,7 @@ int clair_train_accumulate(clair_trainer_t *t, const float *x, const uint8_t *la
 int clair_train_step(clair_trainer_t *t, double learning_rate, double l2_lambda, double *stats);
 int clair_train_read_mask(clair_trainer_t *t, int layer, uint8_t *host, int64_t count);
 int clair_train_probabilities(clair_trainer_t *t, float *out);
+int clair_train_accuracy(clair_trainer_t *t, int64_t *tp);
 
 #ifdef __cplusplus
 }

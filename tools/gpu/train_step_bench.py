@@ -5,7 +5,10 @@ A step is Clair.train on one batch: --batch rows (default 10000) cut into micro-
 backward on each with dropout on, then the optimizer step (Adam, focal loss).  Median of --steps (default 10) after --warmup (default 3),
 one JSON line with every step's time.  The input upload from pageable host memory is part of the step, as it is in clair_amd.train.
 
-    python tools/gpu/train_step_bench.py [--batch 10000] [--micro_batch 1024] [--steps 10] [--warmup 3]
+    python tools/gpu/train_step_bench.py [--batch 10000] [--micro_batch 1024] [--steps 10] [--warmup 3] [--lr_train]
+
+--lr_train times Clair.lr_train instead: the same step plus, per micro-batch, the accuracy count on the device and the download of the
+probabilities (docs/train_clr.md).
 
 The per-kernel split comes from a separate, shorter run under the profiler, summed by kernel and grid (a tgemm shape is told by its grid):
 
@@ -50,6 +53,7 @@ def main():
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--optimizer", default="Adam", choices=("Adam", "SGDM"))
     p.add_argument("--loss", default="FocalLoss", choices=("FocalLoss", "CrossEntropy"))
+    p.add_argument("--lr_train", action="store_true", help="time Clair.lr_train (the learning-rate finder's step) instead of Clair.train")
     p.add_argument("--trace", default=None, help="summarise a rocprofv3 kernel-trace CSV instead of running")
     a = p.parse_args()
     if a.trace:
@@ -62,13 +66,13 @@ def main():
     m = Clair(max_batch=16, n_slots=1, micro_batch=a.micro_batch, optimizer_name=a.optimizer, loss_function=a.loss, seed=1)
     try:
         m.init()
-        times = []
+        times, step = [], m.lr_train if a.lr_train else m.train
         for k in range(a.warmup + a.steps):
             t0 = time.perf_counter()
-            m.train(x, labels)
+            step(x, labels)
             times.append(time.perf_counter() - t0)
         measured = times[a.warmup:]
-        print(json.dumps(dict(batch=a.batch, micro_batch=a.micro_batch, optimizer=a.optimizer, loss=a.loss, warmup=a.warmup,
+        print(json.dumps(dict(member="lr_train" if a.lr_train else "train", batch=a.batch, micro_batch=a.micro_batch, optimizer=a.optimizer, loss=a.loss, warmup=a.warmup,
                               step_seconds=[round(t, 5) for t in measured], median_step_seconds=round(float(np.median(measured)), 5),
                               rows_per_second=round(a.batch / float(np.median(measured)), 1), last_loss_per_row=m.training_loss_on_one_batch / a.batch,
                               gradient_norm=m.gradient_norm_on_one_batch)))
