@@ -98,6 +98,7 @@ SIGNATURES = {
     "clair_frontend_bam_options": _sig(c_vp, c_int, c_int, c_int, c_int, c_i64, c_i64, c_i64, c_i64),
     "clair_frontend_add_bam": _sig(c_vp, c_vp, c_i64, c_vp, c_i64),
     "clair_frontend_bam_lookup": _sig(c_vp, c_int),
+    "clair_frontend_bam_subsample": _sig(c_vp, c_i64, c_dbl),
     "clair_frontend_indel_table": _sig(c_vp, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_vp),
     "clair_frontend_find_candidates": _sig(c_vp, c_dbl, c_dbl, c_i64, c_i64, c_vp, c_vp, c_i64, p_i64),
     "clair_frontend_set_candidates": _sig(c_vp, c_vp, c_i64, p_i64),
@@ -652,6 +653,11 @@ class Frontend(DeviceHandle):
     def bam_lookup(self, keep=True):
         """clair_frontend_bam_lookup, after bam_options: keep and mark what the indel look-up counts (indel_table)."""
         self._check(self._lib.clair_frontend_bam_lookup(self._h, 1 if keep else 0), "clair_frontend_bam_lookup")
+
+    def bam_subsample(self, seed, frac):
+        """clair_frontend_bam_subsample, after bam_options and before the first record: add_bam also drops what `samtools view -s` would
+        (docs/subsample.md); frac <= 0: off."""
+        self._check(self._lib.clair_frontend_bam_subsample(self._h, int(seed), float(frac)), "clair_frontend_bam_subsample")
 
     def indel_table(self, positions, capacity=32):
         """clair_frontend_indel_table: the indel tables of `positions` (1-based, strictly ascending) from the resident slabs, in one device

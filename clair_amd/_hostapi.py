@@ -71,6 +71,8 @@ SIGNATURES = {
     "clair_host_bam_render": _sig(vp, vp, vp, i64, i32, i64, i64, p_vp, p_i64),
     "clair_host_faidx": _sig(cp, cp, i64, i64, vp, i64, p_i64),
     "clair_host_bam_set_inflater": _sig(vp, vp, vp, i32),
+    "clair_host_bam_set_subsample": _sig(vp, i64, f64),
+    "clair_host_subsample_keeps": _sig(vp, i64, i64, f64),
     "clair_host_inflate_block": _sig(vp, i64, vp, i64, p_i64, ctypes.POINTER(ctypes.c_uint32), p_i32),
     "clair_host_inflate_bgzf": _sig(vp, i64, vp, p_i64, p_i32),
     "clair_host_ensemble_average": _sig(vp, i32, i64, vp),
@@ -673,6 +675,10 @@ class BamReader(Handle):
         self._hook = fn                          # keeps a Python callback alive
         self._check(self._lib.clair_host_bam_set_inflater(self._h, ctypes.cast(fn, ctypes.c_void_p) if fn is not None else None, ctx, int(batch_blocks)))
 
+    def set_subsample(self, seed, frac):
+        """clair_host_bam_set_subsample: render() also drops what `samtools view -s` would (docs/subsample.md); frac <= 0: off."""
+        self._check(self._lib.clair_host_bam_set_subsample(self._h, int(seed), float(frac)))
+
     def close(self):
         Handle.close(self)
         if self._inflater:
@@ -729,6 +735,16 @@ class BamReader(Handle):
         self._check(self._lib.clair_host_bam_render(self._h, buf.ctypes.data, offsets.ctypes.data, int(n_records), self.tid, self.region[0], self.region[1],
                                                     ctypes.byref(text), ctypes.byref(n)))
         return ctypes.string_at(text.value, n.value) if n.value else b""
+
+
+def subsample_keeps(name, seed, frac):
+    """clair_host_subsample_keeps: the subsampling rule for one read name (bytes; it ends at a NUL) -> True when a record of that name stays."""
+    name = bytes(name)
+    src = np.frombuffer(name + b"\0", dtype=np.uint8)
+    rc = load().clair_host_subsample_keeps(src.ctypes.data, len(name), int(seed), float(frac))
+    if rc < 0:
+        raise ValueError(load().clair_host_last_error().decode())
+    return rc == 1
 
 
 BAM_CHUNK = 64 << 20       # bytes of whole records per BamReader.readinto (the page-locked buffer the device front end reads them from)

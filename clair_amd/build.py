@@ -52,6 +52,7 @@ def build_host(force=False):
     hdrs.append(os.path.join(HERE, "csrc", "ensemble_core.h"))      # the averaging rule host_ensemble.cpp shares with the device (csrc/ensemble.hip.h)
     hdrs.append(os.path.join(HERE, "csrc", "overlap_core.h"))       # the pair rule and the walk host_overlap.cpp shares with the device (csrc/overlap.hip)
     hdrs.append(os.path.join(HERE, "csrc", "train_set_core.h"))     # the sampling, pairing and label rules host_train_set.cpp shares with the device (csrc/train_set.hip)
+    hdrs.append(os.path.join(HERE, "csrc", "subsample_core.h"))     # the read-name rule host_bam.cpp shares with the device (csrc/frontend.hip)
     if (force or not os.path.isfile(HOST_OUT)
             or max([os.path.getmtime(f) for f in HOST_SRCS + hdrs]) > os.path.getmtime(HOST_OUT)):
         # -ffp-contract=off: the decode restates float32 product chains bit for bit (no fused multiply-add)

@@ -28,6 +28,8 @@ host stages above and says so.
 --bam_threads host threads (or on the GPU, a wave per block: --bam_inflate device), the region's records found with the .bai, and with the device front end the binary records go to the GPU
 as they are (clair_frontend_add_bam), which decodes them and applies the view's filter itself.  The host stages, and the device front
 end's fall-back, read the text `samtools view` would have printed, rendered from the records; the reference slice comes from the .fai.
+--subsample FRAC / --ensemble_subsample FRAC[:SEED] add what `samtools view -s` adds to that view, on the GPU or in the renderer: --bam_fn
+at a fraction of its reads, as the BAM itself or as further sources of the ensemble across BAMs (docs/subsample.md).
 """
 import logging
 import os
@@ -72,6 +74,9 @@ def native_reader(args, region):
             logging.warning("[W::bgzf] %s: no BGZF EOF marker; the file may be truncated" % args.bam_fn)
         if not reader.query(ctg, lo, hi):
             logging.info("%s has no .bai index: reading it from the first record" % args.bam_fn)
+        if subsample_of(args) is not None:              # for the text it renders: the host stages' and the device front end's hand-back
+            frac, seed = subsample_of(args)
+            reader.set_subsample(seed, frac)
     except _hostapi.BamError as exc:
         sys.exit("[ERROR] %s" % exc)
     return reader
@@ -119,6 +124,47 @@ def native_input(args):
 
 def native_lookup(args):
     return getattr(args, "indel_lookup", "pysam") == "native"
+
+
+def subsample_of(args):
+    """--subsample / --subsample_seed -> (fraction, seed) of the reads --bam_fn is read at, or None for all of them (docs/subsample.md)"""
+    frac = getattr(args, "subsample", None)
+    return None if frac is None else (float(frac), int(getattr(args, "subsample_seed", 0) or 0))
+
+
+def check_subsample_fraction(flag, frac, seed):
+    if not 0.0 < frac <= 1.0:                       # (NaN fails both)
+        sys.exit("[ERROR] %s %r: a fraction of the reads, 0 < FRAC <= 1" % (flag, frac))
+    if not 0 <= seed <= 0xffffffff:
+        sys.exit("[ERROR] %s: seed %d: 0 .. 4294967295" % (flag, seed))
+
+
+def check_subsample_flags(args):
+    """--subsample, --subsample_seed, --ensemble_subsample: what they need; args.ensemble_subsample becomes [(fraction, seed), ...]."""
+    seed = int(getattr(args, "subsample_seed", 0) or 0)
+    virtual = []
+    for text in getattr(args, "ensemble_subsample", None) or []:
+        if isinstance(text, tuple):                 # normalised before
+            virtual.append(text)
+            continue
+        frac, colon, own = text.partition(":")
+        try:
+            virtual.append((float(frac), int(own) if colon else seed))
+        except ValueError:
+            sys.exit("[ERROR] --ensemble_subsample %s: FRAC or FRAC:SEED, a fraction and an integer" % text)
+        check_subsample_fraction("--ensemble_subsample %s" % text, *virtual[-1])
+    args.ensemble_subsample = virtual or None
+    if subsample_of(args) is not None:
+        check_subsample_fraction("--subsample", *subsample_of(args))
+    elif not virtual and not seed:
+        return
+    check_subsample_fraction("--subsample_seed", 1.0, seed)
+    if not native_input(args):
+        sys.exit("[ERROR] --subsample, --subsample_seed and --ensemble_subsample select reads in the native reader's view: add --bam_reader native "
+                 "(for a single BAM, --samtools_view_args \"-s SEED.FRAC\" already hands the job to samtools)")
+    if subsample_of(args) is not None and not native_lookup(args):
+        sys.exit("[ERROR] --subsample with --indel_lookup pysam: pysam would look indels up in the whole file while the call is made from a "
+                 "subset of its reads; --indel_lookup native answers from the alignments the front end kept: add it")
 
 
 def reference_and_bed(args, search, not_loaded):
@@ -399,6 +445,9 @@ class _NativeBam(object):
         f.bam_options(self.reader.tid, region=None if self.region[0] is None else self.region, **pack_kw)
         if native_lookup(self.args):
             f.bam_lookup(True)
+        if subsample_of(self.args) is not None:
+            frac, seed = subsample_of(self.args)
+            f.bam_subsample(seed, frac)
         buf = pinned(BAM_CHUNK + 16)
         offsets = _hostapi.bam_offsets_for(BAM_CHUNK)
         t_dev = 0.0
@@ -750,6 +799,7 @@ def normalise(args):
             sys.exit("[ERROR] --bam_threads %d: 1 .. 16" % args.bam_threads)
     cv.check_ensemble_flags(args)
     cv.check_overlap_flags(args)
+    check_subsample_flags(args)
     check_site_flags(args)
     if native_lookup(args):
         if not native_input(args):
@@ -763,15 +813,25 @@ def normalise(args):
 MAX_ENSEMBLE_BAMS = 7      # --ensemble_bam_fn: CLAIR_SITES_MAX_BAMS less --bam_fn
 
 
+def site_sources(args):
+    """The BAMs call_sites reads after --bam_fn, in order: the --ensemble_bam_fn files whole, then --bam_fn again at every --ensemble_subsample
+    (normalised: (fraction, seed)) -> [(path, None or (fraction, seed)), ...]; empty for a run that is no ensemble across BAMs."""
+    return ([(path, None) for path in getattr(args, "ensemble_bam_fn", None) or []]
+            + [(args.bam_fn, virtual) for virtual in getattr(args, "ensemble_subsample", None) or []])
+
+
 def check_site_flags(args):
-    """--ensemble_bam_fn replaces the text chain over several BAMs; what only makes sense with it, and what cannot go with it."""
+    """--ensemble_bam_fn / --ensemble_subsample replace the text chain over several BAMs; what only makes sense with them, and what cannot go
+    with them."""
     more = getattr(args, "ensemble_bam_fn", None) or []
-    if not more:
+    n_more = len(site_sources(args))
+    if not n_more:
         if getattr(args, "minimum_count_to_output", 0):
-            sys.exit("[ERROR] --minimum_count_to_output counts the (BAM, checkpoint) runs of a site across --ensemble_bam_fn BAMs: give --ensemble_bam_fn as well")
+            sys.exit("[ERROR] --minimum_count_to_output counts the (BAM, checkpoint) runs of a site across --ensemble_bam_fn BAMs: give --ensemble_bam_fn "
+                     "(or --ensemble_subsample) as well")
         return
-    if len(more) > MAX_ENSEMBLE_BAMS:
-        sys.exit("[ERROR] --ensemble_bam_fn: %d BAMs, at most %d" % (len(more), MAX_ENSEMBLE_BAMS))
+    if n_more > MAX_ENSEMBLE_BAMS:
+        sys.exit("[ERROR] --ensemble_bam_fn and --ensemble_subsample: %d BAMs, at most %d" % (n_more, MAX_ENSEMBLE_BAMS))
     if args.output_for_ensemble:
         sys.exit("[ERROR] --ensemble_bam_fn merges and averages the BAMs' sites in this process; --output_for_ensemble writes one run's "
                  "probabilities for the `ensemble` submodule to average: use one of the two")
@@ -821,7 +881,7 @@ def call_region(args, m, prepared=None):
         lookup = cv.AlignmentLookup(args.bam_fn, args.ref_fn)
     decoder = cv.VariantDecoder(config, lookup, always_use_bam=args.pysam_for_all_indel_bases, arith=args.arith)
     writer = cv.writer_for(args)
-    if getattr(args, "ensemble_bam_fn", None):
+    if site_sources(args):
         def first_front_end(fe):            # BAM 0's front end is this function's to close, like the single BAM's: the native look-up asks it
             nonlocal device_fe
             device_fe = fe
@@ -873,7 +933,8 @@ def call_region(args, m, prepared=None):
 
 
 def call_sites(args, m, decoder, lookup, writer, prepared=None, first_front_end=None):
-    """--ensemble_bam_fn: one region from B BAMs with the K checkpoints of the model, merged per site and averaged on the GPU (the site table,
+    """--ensemble_bam_fn / --ensemble_subsample: one region from B BAMs (files, or --bam_fn at a fraction of its reads: docs/subsample.md)
+    with the K checkpoints of the model, merged per site and averaged on the GPU (the site table,
     include/clair_amd.h: clair_sites_*; docs/ensemble.md).  Per BAM: the front end (on the device, or the host stages where it hands the
     region back), the table told of all the BAM's window positions at once, then the batches through submit_sites, as many in flight as the
     model has slots.  Then the table is finished and its output list decoded batch by batch into the existing decoder and writer.
@@ -885,7 +946,8 @@ def call_sites(args, m, decoder, lookup, writer, prepared=None, first_front_end=
     t0 = time()
     batch = args.batch_size or param.engineBatchSize
     n_slots = max(1, int(getattr(m, "n_slots", 2)))
-    bams = [args.bam_fn] + list(args.ensemble_bam_fn)
+    # --bam_fn (at --subsample if given), the --ensemble_bam_fn files whole, then the virtual BAMs: --bam_fn at each --ensemble_subsample
+    bams = [(args.bam_fn, subsample_of(args))] + site_sources(args)
     table = m.site_table()
     buffers = {}
 
@@ -894,9 +956,12 @@ def call_sites(args, m, decoder, lookup, writer, prepared=None, first_front_end=
             buffers[nbytes] = m.pinned_buffer(nbytes)
         return buffers[nbytes]
     try:
-        for b, bam in enumerate(bams):
+        for b, (bam, virtual) in enumerate(bams):
             sub = copy.copy(args)
             sub.bam_fn = bam
+            sub.subsample, sub.subsample_seed = virtual if virtual is not None else (None, 0)
+            if virtual is not None:
+                bam = "%s at %g (seed %d)" % ((bam,) + virtual)
             if b > 0:
                 sub.indel_lookup = "pysam"         # only BAM 0 is ever asked: the other front ends keep nothing for the look-up
             fe = None
@@ -1076,6 +1141,15 @@ def build_parser():
              "checkpoint, the sites are merged and their probabilities averaged on the GPU exactly as `cat` of the runs' --output_for_ensemble "
              "rows | ensemble | call_var --input_probabilities does.  --bam_fn is BAM 0: window and reference of a site are those of the first "
              "BAM that has it, and the decode's questions to a BAM (pysam, --indel_lookup native) go to --bam_fn" % MAX_ENSEMBLE_BAMS)
+    add('--subsample', type=float, default=None, metavar="FRAC",
+        help="read --bam_fn at this fraction of its reads (0 < FRAC <= 1), chosen by read name as `samtools view -s` chooses them, in the native "
+             "reader's view on the GPU: no down-sampled copy on disk (needs --bam_reader native and --indel_lookup native; docs/subsample.md)")
+    add('--subsample_seed', type=int, default=0, metavar="INT",
+        help="the 32-bit word the read name's hash is XORed with (0 .. 4294967295), default: %(default)s; with 0 the subset is the one "
+             "`samtools view -s 0.FRAC` keeps, a non-zero seed is not scrambled as samtools scrambles it")
+    add('--ensemble_subsample', type=str, action='append', default=None, metavar="FRAC[:SEED]",
+        help="one more virtual BAM, repeatable: --bam_fn at this fraction (SEED: --subsample_seed unless given), called and averaged like an "
+             "--ensemble_bam_fn file, after those; --bam_fn and all of both kinds: at most %d (needs --bam_reader native)" % (MAX_ENSEMBLE_BAMS + 1))
     add('--minimum_count_to_output', type=int, default=0,
         help="with --ensemble_bam_fn: call a site only when at least this many (BAM, checkpoint) runs produced it (the `ensemble` filter's "
              "option of the same name), default: %(default)s")

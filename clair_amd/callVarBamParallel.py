@@ -72,7 +72,9 @@ def commands(args):
         _opt("overlap_filter", args.overlap_filter),
     ] + [_opt("ensemble_chkpnt_fn", os.path.abspath(f)) for f in (args.ensemble_chkpnt_fn or [])]
       + [_opt("ensemble_bam_fn", os.path.abspath(f)) for f in (args.ensemble_bam_fn or [])]
-      + [_opt("minimum_count_to_output", args.minimum_count_to_output), _opt("ensemble_order", args.ensemble_order)] if x is not None)
+      + [_opt("minimum_count_to_output", args.minimum_count_to_output), _opt("ensemble_order", args.ensemble_order),
+         _opt("subsample", args.subsample), _opt("subsample_seed", args.subsample_seed)]
+      + [_opt("ensemble_subsample", v) for v in (args.ensemble_subsample or [])] if x is not None)
     out, k = [], 0
     commands.chunks = []           # (device, output file) per command, for --run
     with open(fai_fn) as fai:
@@ -261,6 +263,10 @@ def build_parser():
         help="passed on, repeatable (callVarBam: one more BAM of the same sample whose sites are merged with --bam_fn's and averaged on the GPU)")
     add('--minimum_count_to_output', type=int, default=None, help="passed on (callVarBam: with --ensemble_bam_fn, the runs a site needs to be called)")
     add('--ensemble_order', type=str, default=None, choices=("chain", "position"), help="passed on (callVarBam: with --ensemble_bam_fn, the order of the rows)")
+    add('--subsample', type=float, default=None, metavar="FRAC", help="passed on (callVarBam: read --bam_fn at this fraction of its reads, chosen on the GPU)")
+    add('--subsample_seed', type=int, default=None, metavar="INT", help="passed on (callVarBam: the seed of --subsample and --ensemble_subsample)")
+    add('--ensemble_subsample', type=str, action='append', default=None, metavar="FRAC[:SEED]",
+        help="passed on, repeatable (callVarBam: one more virtual BAM, --bam_fn at this fraction, averaged with the others on the GPU)")
     return parser
 
 

@@ -20,6 +20,7 @@
 
 #include "block_scan.hip.h"
 #include "device_buffer.h"
+#include "subsample_core.h"
 
 #include <algorithm>
 #include <cstdarg>
@@ -1128,12 +1129,15 @@ __global__ __launch_bounds__(256) void fe_text_seq_kernel(const uint8_t *text, c
 // ---- BAM records decoded on the device (clair_frontend_bam_options / _add_bam): the binary twin of the text path above ------------------
 // The host inflates BGZF and walks the records' block_size fields (hostsrc/host_bam.cpp); the chunk comes here as it was inflated, with the
 // start of every record.  fe_bam_records_kernel decodes a record into the TextLine the text path fills for the line `samtools view` would
-// print for it, and applies the view's own filter first (-F 2316, the contig, the region); the records the view drops are compacted out
+// print for it, and applies the view's own filter first (-F 2316, the contig, the region, and `-s` where clair_frontend_bam_subsample asked
+// for it: subsample_core.h); the records the view drops are compacted out
 // before anything counts lines, so that --dcov, the kept lines, the counters and the slab are the text path's kernels on the same lines.
 // Records start at any byte: fields are read as two aligned dwords and v_alignbyte (the buffer is allocated 16 bytes longer).
 struct BamOptions {
     int tid;
     int64_t region_lo, region_hi;        // 1-based inclusive, what `samtools view <bam> ctg:lo-hi` selects; -1 -1: the whole contig
+    uint32_t seed;                       // clair_frontend_bam_subsample: what `samtools view -s` adds to the view (subsample_core.h); frac <= 0: off
+    double frac;
 };
 constexpr uint16_t BAM_VIEW_FILTER = 2316;
 
@@ -1197,6 +1201,22 @@ __device__ inline bool bam_real_cigar(const uint8_t *rec, uint64_t aux, uint64_t
     return false;
 }
 
+// subsample_hash of the read name at `off`: n bytes, or up to an earlier NUL.  A dword at a time like every other field, never a byte load
+// near the end of the buffer; the bytes of a dword go through the shared rule one by one.
+__device__ inline uint32_t bam_name_hash(const uint8_t *rec, uint64_t off, uint32_t n) {
+    uint32_t h = 0;
+    for (uint32_t i = 0; i < n; i += 4) {
+        const uint32_t w = bam_u32(rec, off + i), left = n - i;
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+            const uint8_t c = (uint8_t)(w >> (8 * j));
+            if (j >= left || c == 0) return h;
+            h = subsample_hash(&c, 1, h);
+        }
+    }
+    return h;
+}
+
 // one thread per record: all[k] = the line the text path would have parsed, pass[k] = 1 when `samtools view -F 2316 <bam> <region>` prints it
 __global__ __launch_bounds__(256) void fe_bam_records_kernel(const uint8_t *rec, int64_t len, const int64_t *offsets, int64_t n, TextOptions opt, BamOptions bo,
                                                              TextLine *all, uint8_t *pass, TextState *state) {
@@ -1245,6 +1265,7 @@ __global__ __launch_bounds__(256) void fe_bam_records_kernel(const uint8_t *rec,
         const int64_t end1 = pos1 + (w.rlen > 0 ? w.rlen : 1) - 1;          // bam_endpos
         view = pos1 <= bo.region_hi && end1 >= bo.region_lo;
     }
+    if (view && bo.frac > 0.0) view = subsample_keeps(bam_name_hash(rec, name_off, l_read_name - 1), bo.seed, bo.frac);
     if (!view) { all[k] = out; return; }
     const uint32_t seq_len = l_seq > 0 ? (uint32_t)l_seq : 1u;               // SEQ '*' is one byte of text
     const bool evc_ok = (int64_t)mq >= opt.evc_min_mq && n_ops_cigar > 0 && !(1.0 - (double)w.soft / (double)(w.total + 1) < 0.55);
@@ -1767,6 +1788,16 @@ int clair_frontend_bam_options(clair_frontend_t *f, int tid, int dcov, int evc_m
     f->text_state = TextState{};
     f->text_ready = true;
     f->bam_mode = true;
+    return 0;
+}
+
+int clair_frontend_bam_subsample(clair_frontend_t *f, int64_t seed, double frac) {
+    if (!f) return fe_fail(nullptr, "front end is NULL");
+    if (!f->text_ready || !f->bam_mode) return fe_fail(f, "call clair_frontend_bam_options first");
+    if (f->text_state.lines) return fe_fail(f, "the subsample option cannot change once records were added");
+    if (seed < 0 || seed > 0xffffffffll) return fe_fail(f, "subsample seed %lld: 0 .. 4294967295", (long long)seed);
+    f->bam_opt.seed = (uint32_t)seed;
+    f->bam_opt.frac = frac > 0.0 ? frac : 0.0;
     return 0;
 }
 

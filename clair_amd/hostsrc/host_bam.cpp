@@ -11,8 +11,9 @@
 //     the contig that starts past the region (hts_itr_next).
 // The binary records go to the device as they are (clair_frontend_add_bam, csrc/frontend.hip).  clair_host_bam_render turns them into the
 // 11 mandatory columns samtools prints -- the text the host stages and the device front end's fall-back read -- and clair_host_faidx
-// is `samtools faidx` for one region.
+// is `samtools faidx` for one region.  clair_host_bam_set_subsample adds `-s` to that view (csrc/subsample_core.h, docs/subsample.md).
 #include "../../include/clair_host.h"
+#include "../csrc/subsample_core.h"
 
 #include <zlib.h>
 
@@ -151,6 +152,9 @@ struct clair_bam {
     void *inflater_ctx = nullptr;
     std::vector<int64_t> hook_in_at, hook_out_at;
     std::vector<int32_t> hook_csize, hook_out_len, hook_status;
+    // clair_host_bam_set_subsample: one more clause of render's view; frac <= 0: off
+    uint32_t subsample_seed = 0;
+    double subsample_frac = 0.0;
 
     ~clair_bam() { if (file) fclose(file); }
 
@@ -367,6 +371,20 @@ int clair_host_bam_set_inflater(clair_bam_t *b, clair_host_inflate_fn fn, void *
     return 0;
 }
 
+int clair_host_bam_set_subsample(clair_bam_t *b, int64_t seed, double frac) {
+    if (!b) return clair_host_fail("BAM handle is NULL");
+    if (seed < 0 || seed > 0xffffffffll) return clair_host_fail("subsample seed %lld: 0 .. 4294967295", (long long)seed);
+    b->subsample_seed = (uint32_t)seed;
+    b->subsample_frac = frac > 0.0 ? frac : 0.0;
+    return 0;
+}
+
+int clair_host_subsample_keeps(const uint8_t *name, int64_t n, int64_t seed, double frac) {
+    if (n < 0 || (n > 0 && !name) || seed < 0 || seed > 0xffffffffll) { clair_host_fail("subsample_keeps: bad name or seed"); return -1; }
+    const int64_t len = n > 0 ? (int64_t)strnlen((const char *)name, (size_t)n) : 0;
+    return subsample_keeps(subsample_hash(name, len), (uint32_t)seed, frac) ? 1 : 0;
+}
+
 int clair_host_bam_info(const clair_bam_t *b, int64_t *info) {
     if (!b || !info) return clair_host_fail("NULL argument");
     info[0] = (int64_t)b->names.size();
@@ -559,6 +577,9 @@ int clair_host_bam_render(clair_bam_t *b, const uint8_t *records, const int64_t 
             const int64_t end_1 = (int64_t)pos + rlen;           // bam_endpos, 1-based inclusive
             if (!((int64_t)pos + 1 <= end1 && end_1 >= beg1)) continue;
         }
+        if (b->subsample_frac > 0.0
+            && !subsample_keeps(subsample_hash(r + 36, (int64_t)strnlen((const char *)r + 36, l_read_name - 1)), b->subsample_seed, b->subsample_frac))
+            continue;
         const auto ref_name = [&](int32_t id) -> const std::string * {
             return id >= 0 && id < (int32_t)b->names.size() ? &b->names[(size_t)id] : nullptr;
         };

@@ -177,20 +177,25 @@ def write_set(path, args, centres, seqs, counts, labels, in_set, stats, p_near, 
     rows = in_set != 0
     meta = dict(seed=args.seed, sampling=args.sampling, p_near=p_near, p_outside=p_outside, amp=args.amp, v=stats["v"], c=stats["c"], r=stats["r"],
                 n_near=stats["n_near"], n_outside=stats["n_outside"])
+    if args.subsample is not None:              # only then: a set of all the reads is the same file as before the flag existed
+        meta.update(subsample=args.subsample, subsample_seed=args.subsample_seed)
     save_set(path, dict(counts=counts[rows], labels=labels[rows], positions=centres[rows],
                         refseq=np.ascontiguousarray(seqs[rows][:, :33]).view("S33").ravel(), ctg=np.array(args.ctgName), meta=np.array(json.dumps(meta, sort_keys=True))))
 
 
 def load_sets(paths):
     """--set_fn of train / evaluate: the rows of the files, concatenated -> (X float32 [n,33,8,4] (channels 1..3 minus channel 0), keys
-    [`ctg:pos`, ...], labels uint8 [n,4]); the first row of a `ctg:pos` wins, as in the text data set."""
+    [`ctg:pos`, ...], labels uint8 [n,4]); the first row of a `ctg:pos` wins, as in the text data set -- among the sets of one depth: a set
+    made with --subsample FRAC (its meta says so) is keyed by `FRAC:SEED` as well, so that a site stays once per depth it was made at."""
     from clair_amd import _hostapi
     xs, ys, keys, seen = [], [], [], set()
     for path in paths:
         with np.load(path, allow_pickle=False) as z:
             ctg, positions, counts, labels = str(z["ctg"]), z["positions"], z["counts"], z["labels"]
-        new = np.array([(ctg, int(p)) not in seen for p in positions], dtype=bool)
-        seen.update((ctg, int(p)) for p in positions)
+            meta = json.loads(str(z["meta"])) if "meta" in z.files else {}
+        tag = "%r:%d" % (float(meta["subsample"]), int(meta.get("subsample_seed", 0))) if "subsample" in meta else ""
+        new = np.array([(ctg, int(p), tag) not in seen for p in positions], dtype=bool)
+        seen.update((ctg, int(p), tag) for p in positions)
         xs.append(_hostapi.counts_to_input(np.ascontiguousarray(counts[new], dtype=np.int16)).reshape(-1, 33, 8, 4))
         ys.append(labels[new].astype(np.uint8).reshape(-1, 4))
         keys += ["%s:%d" % (ctg, p) for p in positions[new]]
@@ -235,6 +240,10 @@ def build_parser():
              "host stages, with a message, where the device formulation does not reproduce them exactly) or on the host")
     add('--bam_reader', type=str, default="samtools", choices=("samtools", "native"), help="how the alignments and the reference slice are read")
     add('--bam_threads', type=int, default=4, help="with --bam_reader native: threads that inflate BGZF blocks (1 .. 16), default: %(default)s")
+    add('--subsample', type=float, default=None, metavar="FRAC",
+        help="make the set from this fraction of the BAM's reads (0 < FRAC <= 1), chosen by read name as `samtools view -s` chooses them, in the "
+             "native reader's view: one run per depth, no down-sampled copy on disk (needs --bam_reader native; docs/subsample.md)")
+    add('--subsample_seed', type=int, default=0, metavar="INT", help="the 32-bit word the read name's hash is XORed with, default: %(default)s")
     add('--samtools', type=str, default="samtools", help="samtools executable")
     add('--device', type=int, default=0, help="HIP device ordinal, default: %(default)s")
     # what callVarBam's front end reads from its options and this module does not offer
@@ -251,6 +260,13 @@ def Run(args):
         sys.exit("[ERROR] the truth comes from --var_fn (GetTruth's rows) or from --vcf_fn: give one of the two")
     if (args.ctgStart is None) != (args.ctgEnd is None) or (args.ctgStart is not None and args.ctgStart > args.ctgEnd):
         args.ctgStart = args.ctgEnd = None
+    if args.subsample is not None or args.subsample_seed:
+        from clair_amd import callVarBam as cvb
+        if args.subsample is not None:
+            cvb.check_subsample_fraction("--subsample", args.subsample, args.subsample_seed)
+        cvb.check_subsample_fraction("--subsample_seed", 1.0, args.subsample_seed)
+        if not cvb.native_input(args):
+            sys.exit("[ERROR] --subsample and --subsample_seed select reads in the native reader's view: add --bam_reader native")
     from clair_amd import _hostapi
     truth, truth_labels = truth_table(truth_rows_of(args))
     args.vcf_fn = None          # from here on the options are the front end's, where --vcf_fn means "windows at these sites only"

@@ -427,6 +427,13 @@ int clair_frontend_add_bam(clair_frontend_t *f, const uint8_t *records, int64_t 
  * --dcov: pysam's pileup, which clair/call_var.py:102-170 reads, applies neither).  A sibling of _bam_options because that call's argument
  * list is fixed.  Off: slabs as ever, byte for byte; on: the same candidates and windows (the stages skip what carries neither EVC nor PILE). */
 int clair_frontend_bam_lookup(clair_frontend_t *f, int keep);
+/* After _bam_options, before the first _add_bam (afterwards an error, as _bam_lookup's): one more clause of the view, what `samtools view -s`
+ * adds to it -- a record the rest of the view prints is dropped when the hash of its read name, XORed with the 32-bit word `seed`
+ * (0 .. 2^32 - 1) and mixed, falls at or above `frac` (csrc/subsample_core.h, docs/subsample.md; the host twin is
+ * clair_host_bam_set_subsample).  frac <= 0 turns the rule off, frac >= 1 keeps every record.  It runs in the thread that decodes the
+ * record, before --dcov, _text_stats and everything downstream, which see fewer lines; a malformed record is reported whether or not the
+ * rule would have dropped it.  _bam_options resets it to off. */
+int clair_frontend_bam_subsample(clair_frontend_t *f, int64_t seed, double frac);
 /* insertion_bases_using_pysam_from / deletion_bases_using_pysam_from (clair/call_var.py:102-170; asked for at :498-565 and :805-823) for n
  * positions in ONE call, from the slabs resident on the device (csrc/indel_lookup.hip: one thread per I / D operation finds its query,
  * one wave per query groups its hits by key).  positions[n]: 1-based, strictly ascending.  entries: [n][capacity] (capacity 1 .. 65536),

@@ -230,6 +230,12 @@ int clair_host_bam_render(clair_bam_t *b, const uint8_t *records, const int64_t 
                           const char **text, int64_t *len);
 int clair_host_faidx(const char *fasta, const char *ctg, int64_t beg1, int64_t end1, char *out, int64_t cap, int64_t *len);
 int clair_host_bam_set_inflater(clair_bam_t *b, clair_host_inflate_fn fn, void *ctx, int batch_blocks);
+/*    set_subsample: from here on render also drops what `samtools view -s` would (csrc/subsample_core.h, docs/subsample.md: the hash of the
+ *    read name, XORed with the 32-bit word `seed` (0 .. 2^32 - 1) and mixed, at or above `frac`); frac <= 0 turns the rule off, frac >= 1
+ *    keeps every record.  The twin of clair_frontend_bam_subsample (include/clair_amd.h); next frames records and is unchanged.
+ *    subsample_keeps: the rule for one name -- name[0 .. n), or up to an earlier NUL -- -> 1 kept, 0 dropped, -1 for bad arguments. */
+int clair_host_bam_set_subsample(clair_bam_t *b, int64_t seed, double frac);
+int clair_host_subsample_keeps(const uint8_t *name, int64_t n, int64_t seed, double frac);
 
 /* -- the host twin of the device inflate (hostsrc/host_inflate.cpp): the RFC 1951 decoder of csrc/inflate_core.h, the code the GPU runs,
  *    compiled for the host with its own CRC-32 (no zlib), so that it can be tested, fuzzed and run under the host sanitizer.  It accepts
