@@ -15,6 +15,7 @@ SUBMODULES = {
     "make_train_set": "clair_amd.make_train_set",
     "PairWithNonVariants": "clair_amd.pair_with_non_variants",
     "train_clr": "clair_amd.train_clr",
+    "merge_vcf": "clair_amd.merge_vcf",
 }
 NOT_COVERED = ("plot_tensor", "train", "Tensor2Bin", "CombineBins", "Bin2To3", "overlap_variant")
 

@@ -119,6 +119,10 @@ SIGNATURES = {
     "clair_inflate_last_error": _sig(c_vp, restype=c_cp),
     "clair_inflate_blocks": _sig(*_INFLATE_BLOCKS),
     "clair_inflate_blocks_cb": _sig(*_INFLATE_BLOCKS),
+    "clair_deflate_create": _sig(c_int, c_int, p_vp),
+    "clair_deflate_destroy": _sig(c_vp, restype=None),
+    "clair_deflate_last_error": _sig(c_vp, restype=c_cp),
+    "clair_deflate_blocks": _sig(c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp),
     "clair_overlap_keep": _sig(c_int, c_vp, c_i64, c_vp),
     "clair_overlap_last_error": _sig(restype=c_cp),
     "clair_train_create": _sig(c_int, c_int, c_int, c_int, p_vp),
@@ -853,6 +857,33 @@ class Inflater(DeviceHandle):
         self._check(self._lib.clair_inflate_blocks(self._h, _ptr(cdata), len(cdata) if cbytes is None else int(cbytes), n, _ptr(in_at), _ptr(csize),
                                                    _ptr(out_at), _ptr(out_len), _ptr(out), _ptr(status)), "clair_inflate_blocks")
         return out, status
+
+
+class Deflater(DeviceHandle):
+    """clair_deflate_*: BGZF blocks compressed on the device, a wave per block (csrc/deflate.hip).
+
+        d = Deflater(device=0, max_blocks=256)
+        out, csize = d.blocks(data, in_at, in_len)       # out uint8 [n, 65536]: block i is out[i, :csize[i]]
+
+    The bytes are those of clair_amd._hostapi.deflate_bgzf for the same payload."""
+
+    def __init__(self, device=0, max_blocks=256):
+        self._lib = load()
+        out = self._own(self._lib.clair_deflate_destroy, self._lib.clair_deflate_last_error)
+        self._check(self._lib.clair_deflate_create(int(device), int(max_blocks), out), "clair_deflate_create")
+        self.max_blocks = int(max_blocks)
+
+    def blocks(self, data, in_at, in_len):
+        data = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+        in_at, in_len = np.ascontiguousarray(in_at, dtype=np.int64), np.ascontiguousarray(in_len, dtype=np.int32)
+        n = len(in_at)
+        if len(in_len) != n:
+            raise ValueError("%d offsets for %d lengths" % (n, len(in_len)))
+        out = np.zeros((n, 65536), dtype=np.uint8)
+        csize = np.zeros(n, dtype=np.int32)
+        self._check(self._lib.clair_deflate_blocks(self._h, _ptr(data) if len(data) else None, len(data), n, _ptr(in_at), _ptr(in_len), _ptr(out), _ptr(csize)),
+                    "clair_deflate_blocks")
+        return out, csize
 
 
 class Trainer(DeviceHandle):

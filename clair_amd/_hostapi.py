@@ -75,6 +75,7 @@ SIGNATURES = {
     "clair_host_subsample_keeps": _sig(vp, i64, i64, f64),
     "clair_host_inflate_block": _sig(vp, i64, vp, i64, p_i64, ctypes.POINTER(ctypes.c_uint32), p_i32),
     "clair_host_inflate_bgzf": _sig(vp, i64, vp, p_i64, p_i32),
+    "clair_host_deflate_bgzf": _sig(vp, i64, vp, p_i64),
     "clair_host_ensemble_average": _sig(vp, i32, i64, vp),
     "clair_host_ensemble_quantise": _sig(vp, i64, vp),
     "clair_host_ensemble_value": _sig(vp, i64, vp),
@@ -620,6 +621,21 @@ def inflate_bgzf(block):
     if lib.clair_host_inflate_bgzf(src.ctypes.data, len(src), out.ctypes.data, ctypes.byref(n), ctypes.byref(status)) != 0:
         raise ValueError(lib.clair_host_last_error().decode())
     return int(status.value), out[:n.value].tobytes()
+
+
+DEFLATE_MAX_IN = 65280     # bgzip's payload per block (0xff00)
+
+
+def deflate_bgzf(data):
+    """clair_host_deflate_bgzf: at most DEFLATE_MAX_IN bytes -> one whole BGZF block (bytes), the bytes the device compressor writes
+    (clair_amd._capi.Deflater).  The call releases the GIL: a thread pool runs blocks side by side."""
+    lib = load()
+    data = bytes(data)
+    out = ctypes.create_string_buffer(65536)
+    n = ctypes.c_int64(0)
+    if lib.clair_host_deflate_bgzf(ctypes.cast(ctypes.c_char_p(data), ctypes.c_void_p), len(data), out, ctypes.byref(n)) != 0:
+        raise ValueError(lib.clair_host_last_error().decode())
+    return out.raw[:n.value]
 
 
 class BamError(ValueError):

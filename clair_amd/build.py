@@ -9,7 +9,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # (csrc/indel_lookup.hip is part of frontend.hip's translation unit: it works on that handle's slabs)
-SRCS = [os.path.join(HERE, "csrc", f) for f in ("engine.hip", "comm.hip", "frontend.hip", "inflate.hip", "overlap.hip", "train.hip")]
+SRCS = [os.path.join(HERE, "csrc", f) for f in ("engine.hip", "comm.hip", "frontend.hip", "inflate.hip", "deflate.hip", "overlap.hip", "train.hip")]
 OUT = os.path.join(HERE, "libclair_amd.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
@@ -37,7 +37,7 @@ def needs_build():
 
 
 HOST_SRCS = [os.path.join(HERE, "hostsrc", f) for f in ("host_io.cpp", "host_decode.cpp", "host_pileup.cpp", "host_sampack.cpp",
-                                                              "host_bam.cpp", "host_inflate.cpp", "host_indel.cpp", "host_ensemble.cpp", "host_overlap.cpp", "host_sites.cpp", "host_train_set.cpp")]
+                                                              "host_bam.cpp", "host_inflate.cpp", "host_deflate.cpp", "host_indel.cpp", "host_ensemble.cpp", "host_overlap.cpp", "host_sites.cpp", "host_train_set.cpp")]
 HOST_OUT = os.path.join(HERE, "libclair_host.so")
 CXX = os.environ.get("CXX", "g++")
 
@@ -48,6 +48,7 @@ def build_host(force=False):
     hdrs = [os.path.join(HERE, "..", "include", h) for h in ("clair_host.h", "clair_reads.h", "clair_call.h", "clair_amd.h")]
     hdrs.append(os.path.join(HERE, "hostsrc", "sam_line.h"))
     hdrs.append(os.path.join(HERE, "csrc", "inflate_core.h"))       # the decoder host_inflate.cpp shares with the device (csrc/inflate.hip)
+    hdrs.append(os.path.join(HERE, "csrc", "deflate_core.h"))       # the compressor host_deflate.cpp shares with the device (csrc/deflate.hip)
     hdrs.append(os.path.join(HERE, "csrc", "indel_lookup_core.h"))  # the table host_indel.cpp shares with the device library (csrc/indel_lookup.hip)
     hdrs.append(os.path.join(HERE, "csrc", "ensemble_core.h"))      # the averaging rule host_ensemble.cpp shares with the device (csrc/ensemble.hip.h)
     hdrs.append(os.path.join(HERE, "csrc", "overlap_core.h"))       # the pair rule and the walk host_overlap.cpp shares with the device (csrc/overlap.hip)

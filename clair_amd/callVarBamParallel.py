@@ -205,7 +205,21 @@ def run(args, lines):
         codes = [p.wait() for p in procs]
     if any(codes):
         sys.exit("[ERROR] callVarBamParallel --run: worker exit codes %r" % codes)
+    if args.merged_fn is not None:
+        merge(args)
     return 0
+
+
+def merge(args):
+    """--merged_fn: every worker has exited with 0; the chunks' VCFs, in the order of the commands, become one file (clair_amd.merge_vcf).
+    This process opens the GPU only now, and only for --merge_overlap_filter / --merge_bgzf_deflate device."""
+    from . import merge_vcf
+    vcfs = [vcf for _, vcf in commands.chunks if os.path.isfile(vcf)]          # a chunk without a candidate site may have left no file
+    if len(vcfs) < len(commands.chunks):
+        print("[INFO] --merged_fn: %d of %d chunks left no VCF" % (len(commands.chunks) - len(vcfs), len(commands.chunks)), file=sys.stderr)
+    merge_vcf.main(["--ref_fn", args.ref_fn, "--merged_fn", args.merged_fn, "--overlap_filter", args.merge_overlap_filter,
+                    "--bgzf_deflate", args.merge_bgzf_deflate, "--threads", str(max(1, min(64, args.tensorflowThreads)))]
+                   + vcfs)
 
 
 def build_parser():
@@ -267,6 +281,13 @@ def build_parser():
     add('--subsample_seed', type=int, default=None, metavar="INT", help="passed on (callVarBam: the seed of --subsample and --ensemble_subsample)")
     add('--ensemble_subsample', type=str, action='append', default=None, metavar="FRAC[:SEED]",
         help="passed on, repeatable (callVarBam: one more virtual BAM, --bam_fn at this fraction, averaged with the others on the GPU)")
+    add('--merged_fn', type=str, default=None, metavar="FILE",
+        help="with --run: after every chunk has been called, merge the chunks' VCFs into this one file (clair_amd.merge_vcf; *.gz: BGZF and a .tbi)")
+    add('--merge_overlap_filter', type=str, default="off", choices=("off", "python", "host", "device"),
+        help="with --merged_fn: the merged rows through the overlap filter, which then also sees pairs that straddle two chunks, default: %(default)s")
+    add('--merge_bgzf_deflate', type=str, default="host", choices=("zlib", "host", "device"),
+        help="with --merged_fn: who compresses the BGZF blocks (the GPU compresses faster, but opening it costs this process more than it saves "
+             "on one genome's VCF: docs/merge_vcf.md), default: %(default)s")
     return parser
 
 
@@ -277,6 +298,10 @@ def main(argv=None):
         parser.print_help()
         sys.exit(1)
     args = parser.parse_args(argv)
+    if args.merged_fn is not None and not args.run and args.worker is None:
+        sys.exit("[ERROR] --merged_fn needs --run: the printed commands run side by side under your scheduler, and a merge among them would run "
+                 "before the chunks are there.  After they have finished, run: python -m clair_amd.merge_vcf --output_prefix %s --ref_fn %s --merged_fn %s"
+                 % (args.output_prefix, args.ref_fn, args.merged_fn))
     if args.worker is not None:
         import json
         spec = json.load(open(args.worker))

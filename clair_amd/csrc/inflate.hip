@@ -197,7 +197,8 @@ int inflate_init(clair_inflate *h) {
     INF_TRY(nullptr, h->d_in.ensure((size_t)h->cap + 32));      // the kernel reads whole 16-byte pieces around each stream
     INF_TRY(nullptr, h->d_out.ensure((size_t)h->cap));
     INF_TRY(nullptr, h->d_meta.ensure(meta));
-    INF_TRY(nullptr, hipMemset(h->d_in.p, 0, (size_t)h->cap + 32));
+    // on the handle's own (non-blocking) stream: a fill on the null stream is not ordered before this stream's first copy into the buffer
+    INF_TRY(nullptr, hipMemsetAsync(h->d_in.p, 0, (size_t)h->cap + 32, h->stream));
     return 0;
 }
 

@@ -503,6 +503,19 @@ int clair_inflate_blocks(clair_inflate_t *h, const uint8_t *cdata, int64_t cbyte
 int clair_inflate_blocks_cb(void *handle, const uint8_t *cdata, int64_t cbytes, int n, const int64_t *in_at, const int32_t *csize,
                             const int64_t *out_at, const int32_t *out_len, uint8_t *out, int32_t *status);
 
+/* -- BGZF deflate on the device (merge_vcf --bgzf_deflate device; csrc/deflate.hip, docs/merge_vcf.md).  The writer's side of the above: a
+ * handle owns one stream, page-locked staging and device buffers for max_blocks (1 .. 16384) blocks, reused by every call.
+ * _blocks: n <= max_blocks payloads data[in_at[i] .. + in_len[i]), 0 <= in_len <= 65280, every range inside data[0 .. bytes) -> block i as
+ * one whole BGZF block (18-byte header with BSIZE, raw deflate stream, CRC-32, ISIZE) in out[i * 65536 .. + csize[i]); the rest of its
+ * 65536-byte slot is zeroed.  A wave per block; the bytes are those clair_host_deflate_bgzf (include/clair_host.h) gives for the same
+ * payload.  Synchronous.  Returns non-zero for a bad argument (nothing is enqueued then) or a HIP error. */
+typedef struct clair_deflate clair_deflate_t;
+int clair_deflate_create(int device, int max_blocks, clair_deflate_t **out);
+void clair_deflate_destroy(clair_deflate_t *h);
+const char *clair_deflate_last_error(const clair_deflate_t *h);        /* h may be NULL: failure of create */
+int clair_deflate_blocks(clair_deflate_t *h, const uint8_t *data, int64_t bytes, int n, const int64_t *in_at, const int32_t *in_len,
+                         uint8_t *out, int32_t *csize);
+
 /* -- the overlap filter on the device (call_var / callVarBam --overlap_filter device; csrc/overlap.hip, docs/overlap_variant.md).
  * The walk of clair/post_processing/overlap_variant.py:237-267 over n rows reduced to 24-byte spans (csrc/overlap_core.h lays the
  * record out and holds the pair rule): spans [n] in input order, host memory -> keep [n], host memory, 1 for every row the filter

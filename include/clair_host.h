@@ -248,6 +248,13 @@ int clair_host_subsample_keeps(const uint8_t *name, int64_t n, int64_t seed, dou
 int clair_host_inflate_block(const uint8_t *in, int64_t n_in, uint8_t *out, int64_t cap, int64_t *n_out, uint32_t *crc32, int *status);
 int clair_host_inflate_bgzf(const uint8_t *block, int64_t csize, uint8_t *out, int64_t *n_out, int *status);
 
+/* -- the host twin of the device deflate (hostsrc/host_deflate.cpp): the compressor of csrc/deflate_core.h, the code the GPU runs inside
+ *    clair_deflate_blocks (include/clair_amd.h), compiled for the host (no zlib).  in[0 .. n_in), n_in <= 65280 (bgzip's block payload) ->
+ *    one whole BGZF block in out[0 .. *n_out): 18-byte header with BSIZE, a raw deflate stream (dynamic Huffman blocks, or one stored block
+ *    when that is not smaller), CRC-32, ISIZE.  out has room for 65536 bytes; the bytes beyond *n_out are zero.  The same input gives the
+ *    same bytes here and on the device.  Returns non-zero only for bad arguments.  Re-entrant. */
+int clair_host_deflate_bgzf(const uint8_t *in, int64_t n_in, uint8_t *out, int64_t *n_out);
+
 /* -- the host twin of the device ensemble averaging (hostsrc/host_ensemble.cpp): csrc/ensemble_core.h, the code the GPU runs after each of
  *    the K forward passes of clair_submit_ensemble (include/clair_amd.h), compiled for the host.  It restates the reference's text chain
  *    value for value: '{:0.6f}' of every float32 probability (clair/call_var.py:950-1000), float() of those digits, the sum in input order
