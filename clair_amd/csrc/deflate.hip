@@ -68,64 +68,21 @@ __global__ __launch_bounds__(64) void deflate_bgzf_kernel(const uint8_t *__restr
 
 }  // namespace clair_def
 
-// -- the handle: one stream, page-locked staging for both directions and the device buffers, sized from max_blocks at creation and reused
-#include <cstdarg>
-#include <cstdio>
+// -- the handle: a StagedStream sized from max_blocks at creation
 #include <cstring>
-#include <string>
+
+#include "staged_stream.h"
+
+struct clair_deflate : StagedStream {};
 
 namespace {
 
 constexpr int64_t DEF_MAX_IN = clair_def::MAX_IN, DEF_SLOT = clair_def::SLOT;
-std::string g_def_error;
-
-}  // namespace
-
-struct clair_deflate {
-    int device = 0;
-    int max_blocks = 0;
-    hipStream_t stream = nullptr;
-    PinnedBuffer h_in, h_out, h_meta;
-    DeviceBuffer d_in, d_out, d_meta;
-    std::string error;
-};
-
-namespace {
-
-int def_fail(clair_deflate *h, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (h) h->error = buf; else g_def_error = buf;
-    return 1;
-}
-
-#define DEF_TRY(h, call)                                                                                   \
-    do {                                                                                                   \
-        hipError_t err__ = (call);                                                                         \
-        if (err__ != hipSuccess)                                                                           \
-            return def_fail((h), "%s failed: %s (%s:%d)", #call, hipGetErrorString(err__), __FILE__, __LINE__); \
-    } while (0)
-
 // per block: in_at, in_len, csize (int32)
 constexpr int64_t DEF_META_PER_BLOCK = 3 * 4;
 
-int deflate_init(clair_deflate *h) {
-    DEF_TRY(nullptr, hipSetDevice(h->device));
-    DEF_TRY(nullptr, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    const size_t in_cap = (size_t)h->max_blocks * DEF_MAX_IN + 16, out_cap = (size_t)h->max_blocks * DEF_SLOT;
-    const size_t meta = (size_t)h->max_blocks * DEF_META_PER_BLOCK;
-    DEF_TRY(nullptr, h->h_in.ensure(in_cap));
-    DEF_TRY(nullptr, h->h_out.ensure(out_cap));
-    DEF_TRY(nullptr, h->h_meta.ensure(meta));
-    DEF_TRY(nullptr, h->d_in.ensure(in_cap));                // the kernel reads whole dwords
-    DEF_TRY(nullptr, h->d_out.ensure(out_cap));
-    DEF_TRY(nullptr, h->d_meta.ensure(meta));
-    DEF_TRY(nullptr, hipMemsetAsync(h->d_in.p, 0, in_cap, h->stream));       // on the handle's own stream: ordered before its first copy
-    return 0;
-}
+std::string g_def_error;
+inline HipFail def_fail(clair_deflate *h) { return {h ? h->error : g_def_error}; }
 
 }  // namespace
 
@@ -134,17 +91,13 @@ extern "C" {
 const char *clair_deflate_last_error(const clair_deflate_t *h) { return h ? h->error.c_str() : g_def_error.c_str(); }
 
 int clair_deflate_create(int device, int max_blocks, clair_deflate_t **out) {
-    if (!out) return def_fail(nullptr, "out is NULL");
+    if (!out) return def_fail(nullptr)("out is NULL");
     *out = nullptr;
-    if (max_blocks < 1 || max_blocks > 16384) return def_fail(nullptr, "max_blocks %d: 1 .. 16384", max_blocks);
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1)
-        return def_fail(nullptr, "no HIP device is visible: the device deflate runs on an MI355X only (the host deflate is --bgzf_deflate host)");
-    if (device < 0 || device >= n_dev) return def_fail(nullptr, "device %d out of range [0,%d)", device, n_dev);
+    if (max_blocks < 1 || max_blocks > 16384) return def_fail(nullptr)("max_blocks %d: 1 .. 16384", max_blocks);
+    if (hip_device_check(def_fail(nullptr), device, "the device deflate runs on an MI355X only (the host deflate is --bgzf_deflate host)")) return 1;
     clair_deflate *h = new clair_deflate;
-    h->device = device;
-    h->max_blocks = max_blocks;
-    if (deflate_init(h)) {
+    const size_t in_cap = (size_t)max_blocks * DEF_MAX_IN + 16;      // (+ 16: the kernel reads whole dwords)
+    if (h->open(def_fail(nullptr), device, max_blocks, in_cap, (size_t)max_blocks * DEF_SLOT, (size_t)max_blocks * DEF_META_PER_BLOCK, in_cap)) {
         clair_deflate_destroy(h);
         return 1;
     }
@@ -154,26 +107,22 @@ int clair_deflate_create(int device, int max_blocks, clair_deflate_t **out) {
 
 void clair_deflate_destroy(clair_deflate_t *h) {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (DeviceBuffer *b : {&h->d_in, &h->d_out, &h->d_meta}) b->reset();     // before the stream goes, not in ~clair_deflate
-    for (PinnedBuffer *b : {&h->h_in, &h->h_out, &h->h_meta}) b->reset();
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    h->close();
     delete h;
 }
 
 int clair_deflate_blocks(clair_deflate_t *h, const uint8_t *data, int64_t bytes, int n, const int64_t *in_at, const int32_t *in_len,
                          uint8_t *out, int32_t *csize) {
-    if (!h) return def_fail(nullptr, "deflate handle is NULL");
-    if (n < 0 || n > h->max_blocks) return def_fail(h, "%d blocks in a batch: 0 .. max_blocks = %d", n, h->max_blocks);
+    if (!h) return def_fail(nullptr)("deflate handle is NULL");
+    if (n < 0 || n > h->max_blocks) return def_fail(h)("%d blocks in a batch: 0 .. max_blocks = %d", n, h->max_blocks);
     if (n == 0) return 0;
-    if (!in_at || !in_len || !out || !csize || (!data && bytes > 0)) return def_fail(h, "NULL argument");
-    if (bytes < 0) return def_fail(h, "%lld bytes of data", (long long)bytes);
+    if (!in_at || !in_len || !out || !csize || (!data && bytes > 0)) return def_fail(h)("NULL argument");
+    if (bytes < 0) return def_fail(h)("%lld bytes of data", (long long)bytes);
     for (int i = 0; i < n; ++i) {
-        if (in_len[i] < 0 || in_len[i] > DEF_MAX_IN) return def_fail(h, "block %d: %d bytes (0 .. 65280)", i, in_len[i]);
-        if (in_at[i] < 0 || in_at[i] > bytes - in_len[i]) return def_fail(h, "block %d: bytes [%lld, +%d) outside the %lld given", i, (long long)in_at[i], in_len[i], (long long)bytes);
+        if (in_len[i] < 0 || in_len[i] > DEF_MAX_IN) return def_fail(h)("block %d: %d bytes (0 .. 65280)", i, in_len[i]);
+        if (in_at[i] < 0 || in_at[i] > bytes - in_len[i]) return def_fail(h)("block %d: bytes [%lld, +%d) outside the %lld given", i, (long long)in_at[i], in_len[i], (long long)bytes);
     }
-    DEF_TRY(h, hipSetDevice(h->device));
+    CLAIR_HIP_TRY(def_fail(h), hipSetDevice(h->device));
     const size_t N = (size_t)h->max_blocks;
     int32_t *m_at = h->h_meta.as<int32_t>(), *m_len = m_at + N, *m_csize = m_len + N;
     uint8_t *h_in = h->h_in.as<uint8_t>(), *h_out = h->h_out.as<uint8_t>();
@@ -185,17 +134,17 @@ int clair_deflate_blocks(clair_deflate_t *h, const uint8_t *data, int64_t bytes,
         total += ((int64_t)in_len[i] + 3) & ~(int64_t)3;
     }
     int32_t *d_at = h->d_meta.as<int32_t>(), *d_len = d_at + N, *d_csize = d_len + N;
-    if (total) DEF_TRY(h, hipMemcpyAsync(h->d_in.p, h_in, (size_t)total, hipMemcpyHostToDevice, h->stream));
-    DEF_TRY(h, hipMemcpyAsync(h->d_meta.p, h->h_meta.p, N * 2 * 4, hipMemcpyHostToDevice, h->stream));
+    if (total) CLAIR_HIP_TRY(def_fail(h), hipMemcpyAsync(h->d_in.p, h_in, (size_t)total, hipMemcpyHostToDevice, h->stream));
+    CLAIR_HIP_TRY(def_fail(h), hipMemcpyAsync(h->d_meta.p, h->h_meta.p, N * 2 * 4, hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(clair_def::deflate_bgzf_kernel, dim3((unsigned)n), dim3(64), 0, h->stream, h->d_in.as<const uint8_t>(), n, (const int32_t *)d_at,
                        (const int32_t *)d_len, h->d_out.as<uint8_t>(), d_csize);
-    DEF_TRY(h, hipGetLastError());
-    DEF_TRY(h, hipMemcpyAsync(h_out, h->d_out.p, (size_t)n * DEF_SLOT, hipMemcpyDeviceToHost, h->stream));
-    DEF_TRY(h, hipMemcpyAsync(m_csize, d_csize, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-    DEF_TRY(h, hipStreamSynchronize(h->stream));
+    CLAIR_HIP_TRY(def_fail(h), hipGetLastError());
+    CLAIR_HIP_TRY(def_fail(h), hipMemcpyAsync(h_out, h->d_out.p, (size_t)n * DEF_SLOT, hipMemcpyDeviceToHost, h->stream));
+    CLAIR_HIP_TRY(def_fail(h), hipMemcpyAsync(m_csize, d_csize, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+    CLAIR_HIP_TRY(def_fail(h), hipStreamSynchronize(h->stream));
     for (int i = 0; i < n; ++i) {
         const int32_t cs = m_csize[i];
-        if (cs < 26 || cs > DEF_SLOT) return def_fail(h, "block %d: the kernel reports %d bytes", i, cs);
+        if (cs < 26 || cs > DEF_SLOT) return def_fail(h)("block %d: the kernel reports %d bytes", i, cs);
         csize[i] = cs;
         memcpy(out + (size_t)i * DEF_SLOT, h_out + (size_t)i * DEF_SLOT, (size_t)cs);
         memset(out + (size_t)i * DEF_SLOT + cs, 0, (size_t)(DEF_SLOT - cs));

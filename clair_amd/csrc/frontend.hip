@@ -18,12 +18,12 @@
 
 #include <hip/hip_runtime.h>
 
-#include "block_scan.hip.h"
 #include "device_buffer.h"
+#include "device_scan.h"
+#include "hip_status.h"
 #include "subsample_core.h"
 
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <deque>
@@ -400,30 +400,17 @@ __global__ __launch_bounds__(256) void fe_given_flags_kernel(const int64_t *posi
     if (t >= 0 && t < n) flags[t] = 1;
 }
 
-// ---- the block scan: sums of 4096 items per workgroup, one workgroup over the block sums, then every workgroup writes ---------------
+// ---- the block scan (device_scan.h): sums of 4096 items per workgroup, one workgroup over the block sums, then every workgroup writes ----
 // Instantiated for flags -> exclusive prefix (uint32, n + 1 entries) and the list of flagged indices (candidates, kept windows, kept lines;
 // line feeds of the text), and for 64-bit inclusive running sums (the candidate prefix; the second differences of pass 2, in place).
 constexpr int SCAN_ITEMS = 16, SCAN_BLOCK = 256 * SCAN_ITEMS;
 
-// (block_exclusive_scan: block_scan.hip.h, shared with the site table of engine.hip)
-
-// how an item is loaded: an In widened to the Sum the scan runs in (signed sums in two's complement) ...
-template <typename In, typename Sum> struct ScanValues {
-    using in_t = In;
-    using sum_t = Sum;
-    static __device__ inline Sum value(In item) { return (Sum)item; }
-};
-using ScanU32 = ScanValues<uint32_t, unsigned long long>;
-using ScanU64 = ScanValues<unsigned long long, unsigned long long>;
-using ScanInt = ScanValues<int, long long>;
-// ... or a byte that counts one when it is set (NEWLINES: the bytes are text and a line feed is a set flag)
-template <bool NEWLINES> struct ScanBytes {
-    using in_t = uint8_t;
-    using sum_t = uint32_t;
-    static __device__ inline uint32_t value(uint8_t item) { return NEWLINES ? item == '\n' : item != 0; }
-};
-using ScanFlags = ScanBytes<false>;
-using ScanNewlines = ScanBytes<true>;
+using clair_scan::SumScan;
+using ScanU32 = SumScan<uint32_t, unsigned long long>;
+using ScanU64 = SumScan<unsigned long long, unsigned long long>;
+using ScanInt = SumScan<int, long long>;
+using ScanFlags = clair_scan::FlagScan<false>;
+using ScanNewlines = clair_scan::FlagScan<true>;
 
 // what is written for item i, `before` the sum of the items before it.  Flags: the exclusive prefix (optional; entry n = the total) and the list of set indices
 struct WriteCompact {
@@ -431,7 +418,7 @@ struct WriteCompact {
     uint32_t *prefix;
     int64_t *list, list_base;
     __device__ inline uint32_t seed() const { return 0; }
-    __device__ inline void write(int64_t i, int64_t n, uint32_t before, uint32_t item) const {
+    template <typename P> __device__ inline void write(const P &, int64_t i, int64_t n, uint32_t before, uint32_t item) const {
         if (prefix) prefix[i] = before;
         if (i < n && item) list[before] = list_base + i;
     }
@@ -444,45 +431,8 @@ struct WriteRunning {
     int second;
     int64_t lo;
     __device__ inline unsigned long long seed() const { return !fold ? 0 : second ? (unsigned long long)lo * fold[0] - fold[1] : fold[0]; }
-    __device__ inline void write(int64_t i, int64_t, unsigned long long before, unsigned long long item) const { out[i] = before + item; }
+    template <typename P> __device__ inline void write(const P &, int64_t i, int64_t, unsigned long long before, unsigned long long item) const { out[i] = before + item; }
 };
-
-template <typename L>
-__global__ __launch_bounds__(256) void fe_scan_sums_kernel(const typename L::in_t *v, int64_t n, typename L::sum_t *block_sum) {
-    const int64_t at = (int64_t)blockIdx.x * SCAN_BLOCK + (int64_t)threadIdx.x * SCAN_ITEMS;
-    typename L::sum_t c = 0, total;
-    for (int i = 0; i < SCAN_ITEMS; ++i) if (at + i < n) c += L::value(v[at + i]);
-    (void)block_exclusive_scan(c, &total);
-    if (threadIdx.x == 0) block_sum[blockIdx.x] = total;
-}
-
-// one workgroup walks n items 256 at a time: out[i] = the sum of the items before i (INCLUSIVE: and of item i); in place where out is v
-template <typename L, bool INCLUSIVE>
-__global__ __launch_bounds__(256) void fe_scan_serial_kernel(const typename L::in_t *v, int64_t n, typename L::sum_t *out, typename L::sum_t *grand_total) {
-    typename L::sum_t carry = 0, total;
-    for (int64_t at = 0; at < n; at += 256) {
-        const int64_t i = at + threadIdx.x;
-        const typename L::sum_t x = i < n ? L::value(v[i]) : 0;
-        const typename L::sum_t ex = block_exclusive_scan(x, &total);
-        if (i < n) out[i] = carry + ex + (INCLUSIVE ? x : 0);
-        carry += total;
-    }
-    if (grand_total && threadIdx.x == 0) *grand_total = carry;
-}
-
-template <typename L, typename W>
-__global__ __launch_bounds__(256) void fe_scan_write_kernel(const typename L::in_t *v, int64_t n, const typename L::sum_t *block_sum, W w) {
-    const int64_t at = (int64_t)blockIdx.x * SCAN_BLOCK + (int64_t)threadIdx.x * SCAN_ITEMS;
-    typename L::in_t f[SCAN_ITEMS];
-    typename L::sum_t c = 0, total;
-    for (int i = 0; i < SCAN_ITEMS; ++i) { f[i] = at + i < n ? v[at + i] : 0; c += L::value(f[i]); }
-    typename L::sum_t run = w.seed() + block_sum[blockIdx.x] + block_exclusive_scan(c, &total);
-    for (int i = 0; i < SCAN_ITEMS; ++i) {
-        if (at + i >= n + W::PAST_END) break;
-        w.write(at + i, n, run, L::value(f[i]));
-        run += L::value(f[i]);
-    }
-}
 
 // ---- pass 2: windows per read base (the tuple counts), inserted bases into their windows ---------------------------------------
 struct Candidates {
@@ -1069,9 +1019,10 @@ __global__ __launch_bounds__(256) void fe_text_offsets_kernel(const TextLine *li
             pile += (ln.flags & CLAIR_READ_PILE) ? 1 : 0;
         }
         uint32_t ta, tb, tc;
-        const uint32_t ea = block_exclusive_scan(a, &ta);
-        const uint32_t eb = block_exclusive_scan(b, &tb);
-        const uint32_t ec = block_exclusive_scan(c, &tc);
+        using Sum = SumScan<uint32_t, uint32_t>;
+        const uint32_t ea = clair_scan::block_exclusive<Sum>(a, &ta);
+        const uint32_t eb = clair_scan::block_exclusive<Sum>(b, &tb);
+        const uint32_t ec = clair_scan::block_exclusive<Sum>(c, &tc);
         if (i < n_kept) { op0[i] = (uint32_t)(carry_ops + ea); elem0[i] = (uint32_t)(carry_elems + eb); seq0[i] = (uint32_t)(carry_seq + ec); }
         carry_ops += ta;
         carry_elems += tb;
@@ -1341,8 +1292,6 @@ __global__ __launch_bounds__(256) void fe_bam_seq_kernel(const uint8_t *rec, con
     }
 }
 
-int fe_fail(clair_frontend *f, const char *fmt, ...);
-
 }  // namespace
 
 // what depends on the candidate list: replaced as a whole when the candidates are fixed again
@@ -1406,35 +1355,24 @@ struct clair_frontend {
 
 namespace {
 
-int fe_fail(clair_frontend *f, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (f) f->error = buf; else g_fe_error = buf;
-    return 1;
-}
-
-#define FE_TRY(f, call)                                                                                   \
-    do {                                                                                                  \
-        hipError_t err__ = (call);                                                                        \
-        if (err__ != hipSuccess)                                                                          \
-            return fe_fail((f), "%s failed: %s (%s:%d)", #call, hipGetErrorString(err__), __FILE__, __LINE__); \
-    } while (0)
+inline HipFail fe_fail(clair_frontend *f) { return {f ? f->error : g_fe_error}; }
 
 inline unsigned blocks_for(int64_t n, int64_t per_block) { return (unsigned)((n + per_block - 1) / per_block); }
 
 // flags[n] -> how many are set (block sums left scanned in block_sum for scan_write)
-int scan_count(clair_frontend *f, const uint8_t *flags, int64_t n, uint32_t *block_sum, uint32_t *d_count, int64_t *count, bool newlines = false) {
+template <typename Flags> void launch_count(clair_frontend *f, Flags flags, int64_t n, uint32_t *block_sum, uint32_t *d_count) {
     const unsigned nb = blocks_for(n, SCAN_BLOCK);
-    if (n > 0 && newlines) hipLaunchKernelGGL(fe_scan_sums_kernel<ScanNewlines>, dim3(nb), dim3(256), 0, f->stream, flags, n, block_sum);
-    else if (n > 0) hipLaunchKernelGGL(fe_scan_sums_kernel<ScanFlags>, dim3(nb), dim3(256), 0, f->stream, flags, n, block_sum);
-    hipLaunchKernelGGL((fe_scan_serial_kernel<ScanValues<uint32_t, uint32_t>, false>), dim3(1), dim3(256), 0, f->stream, (const uint32_t *)block_sum, (int64_t)nb, block_sum, d_count);
-    FE_TRY(f, hipGetLastError());
+    if (n > 0) hipLaunchKernelGGL((clair_scan::totals_kernel<Flags, SCAN_ITEMS>), dim3(nb), dim3(256), 0, f->stream, flags, n, block_sum);
+    hipLaunchKernelGGL((clair_scan::walk_kernel<SumScan<uint32_t, uint32_t>, false>), dim3(1), dim3(256), 0, f->stream, SumScan<uint32_t, uint32_t>{block_sum}, (int64_t)nb,
+                       block_sum, d_count);
+}
+int scan_count(clair_frontend *f, const uint8_t *flags, int64_t n, uint32_t *block_sum, uint32_t *d_count, int64_t *count, bool newlines = false) {
+    if (newlines) launch_count(f, ScanNewlines{{flags}}, n, block_sum, d_count);
+    else launch_count(f, ScanFlags{{flags}}, n, block_sum, d_count);
+    CLAIR_HIP_TRY(fe_fail(f), hipGetLastError());
     uint32_t total = 0;
-    FE_TRY(f, hipMemcpyAsync(&total, d_count, sizeof total, hipMemcpyDeviceToHost, f->stream));
-    FE_TRY(f, hipStreamSynchronize(f->stream));
+    CLAIR_HIP_TRY(fe_fail(f), hipMemcpyAsync(&total, d_count, sizeof total, hipMemcpyDeviceToHost, f->stream));
+    CLAIR_HIP_TRY(fe_fail(f), hipStreamSynchronize(f->stream));
     *count = total;
     return 0;
 }
@@ -1444,22 +1382,22 @@ int scan_write(clair_frontend *f, const uint8_t *flags, int64_t n, uint32_t *blo
                int64_t list_base, bool newlines = false) {
     // entry n of the prefix is written by the thread that owns index n: cover it with one more (empty) item
     const unsigned nb = blocks_for(n, SCAN_BLOCK), nbw = blocks_for(n + 1, SCAN_BLOCK);
-    if (nbw > nb) FE_TRY(f, hipMemcpyAsync(block_sum + nb, d_count, sizeof(uint32_t), hipMemcpyDeviceToDevice, f->stream));
+    if (nbw > nb) CLAIR_HIP_TRY(fe_fail(f), hipMemcpyAsync(block_sum + nb, d_count, sizeof(uint32_t), hipMemcpyDeviceToDevice, f->stream));
     const WriteCompact w{prefix, list, list_base};
-    if (newlines) hipLaunchKernelGGL((fe_scan_write_kernel<ScanNewlines, WriteCompact>), dim3(nbw), dim3(256), 0, f->stream, flags, n, (const uint32_t *)block_sum, w);
-    else hipLaunchKernelGGL((fe_scan_write_kernel<ScanFlags, WriteCompact>), dim3(nbw), dim3(256), 0, f->stream, flags, n, (const uint32_t *)block_sum, w);
-    FE_TRY(f, hipGetLastError());
+    const uint32_t *prefix_of_blocks = block_sum;
+    if (newlines) hipLaunchKernelGGL((clair_scan::write_kernel<ScanNewlines, SCAN_ITEMS, WriteCompact>), dim3(nbw), dim3(256), 0, f->stream, ScanNewlines{{flags}}, n, prefix_of_blocks, w);
+    else hipLaunchKernelGGL((clair_scan::write_kernel<ScanFlags, SCAN_ITEMS, WriteCompact>), dim3(nbw), dim3(256), 0, f->stream, ScanFlags{{flags}}, n, prefix_of_blocks, w);
+    CLAIR_HIP_TRY(fe_fail(f), hipGetLastError());
     return 0;
 }
 
 // v[n] -> its seeded inclusive running sum in 64 bits (w.out may be v); block_sum: one entry per SCAN_BLOCK items
 template <typename L>
-void running_sum(clair_frontend *f, const typename L::in_t *v, int64_t n, unsigned long long *block_sum, const WriteRunning &w) {
+void running_sum(clair_frontend *f, decltype(L::v) v, int64_t n, unsigned long long *block_sum, const WriteRunning &w) {
     const unsigned nb = blocks_for(n, SCAN_BLOCK);
-    hipLaunchKernelGGL(fe_scan_sums_kernel<L>, dim3(nb), dim3(256), 0, f->stream, v, n, block_sum);
-    hipLaunchKernelGGL((fe_scan_serial_kernel<ScanU64, false>), dim3(1), dim3(256), 0, f->stream, (const unsigned long long *)block_sum, (int64_t)nb, block_sum,
-                       (unsigned long long *)nullptr);
-    hipLaunchKernelGGL((fe_scan_write_kernel<L, WriteRunning>), dim3(nb), dim3(256), 0, f->stream, v, n, (const unsigned long long *)block_sum, w);
+    hipLaunchKernelGGL((clair_scan::totals_kernel<L, SCAN_ITEMS>), dim3(nb), dim3(256), 0, f->stream, L{v}, n, block_sum);
+    hipLaunchKernelGGL((clair_scan::walk_kernel<ScanU64, false>), dim3(1), dim3(256), 0, f->stream, ScanU64{block_sum}, (int64_t)nb, block_sum, (unsigned long long *)nullptr);
+    hipLaunchKernelGGL((clair_scan::write_kernel<L, SCAN_ITEMS, WriteRunning>), dim3(nb), dim3(256), 0, f->stream, L{v}, n, (const unsigned long long *)block_sum, w);
 }
 
 void free_candidates(clair_frontend *f) {
@@ -1473,7 +1411,7 @@ int finish_candidates(clair_frontend *f, int64_t *n_candidates) {
     free_candidates(f);
     int64_t n = 0;
     if (scan_count(f, f->flags.as<uint8_t>(), f->g.n, f->block_sum.as<uint32_t>(), f->total.as<uint32_t>(), &n)) return 1;
-    FE_TRY(f, f->cand->centre.ensure((size_t)n * sizeof(int64_t)));
+    CLAIR_HIP_TRY(fe_fail(f), f->cand->centre.ensure((size_t)n * sizeof(int64_t)));
     if (scan_write(f, f->flags.as<uint8_t>(), f->g.n, f->block_sum.as<uint32_t>(), f->total.as<uint32_t>(), f->before.as<uint32_t>(), f->cand->centre.as<int64_t>(), f->g.lo + 1))
         return 1;
     f->n_candidates = n;
@@ -1494,11 +1432,11 @@ int upload_bed(clair_frontend *f, const int64_t *bed_start, const int64_t *bed_e
         else { st.push_back(x.first); en.push_back(x.second); }
     }
     const size_t m = st.size();
-    FE_TRY(f, f->bed.ensure(2 * m * sizeof(int64_t)));
+    CLAIR_HIP_TRY(fe_fail(f), f->bed.ensure(2 * m * sizeof(int64_t)));
     int64_t *d_bed = f->bed.as<int64_t>();
     if (m) {
-        FE_TRY(f, hipMemcpy(d_bed, st.data(), m * sizeof(int64_t), hipMemcpyHostToDevice));
-        FE_TRY(f, hipMemcpy(d_bed + m, en.data(), m * sizeof(int64_t), hipMemcpyHostToDevice));
+        CLAIR_HIP_TRY(fe_fail(f), hipMemcpy(d_bed, st.data(), m * sizeof(int64_t), hipMemcpyHostToDevice));
+        CLAIR_HIP_TRY(fe_fail(f), hipMemcpy(d_bed + m, en.data(), m * sizeof(int64_t), hipMemcpyHostToDevice));
     }
     *d_start = d_bed;
     *d_end = d_bed + m;
@@ -1511,19 +1449,19 @@ int new_slab(clair_frontend *f, int64_t n_reads, int64_t n_ops, int64_t n_elem, 
     f->slabs.emplace_back();
     Slab &d = f->slabs.back();
     d.n_reads = n_reads; d.n_ops = n_ops; d.n_elem = n_elem; d.seq_bytes = seq_bytes;
-    FE_TRY(f, d.reads.ensure((size_t)n_reads * sizeof(clair_read_t)));
-    FE_TRY(f, d.ops.ensure((size_t)n_ops * sizeof(clair_op_t)));
-    FE_TRY(f, d.op_elem.ensure(((size_t)n_ops + 1) * sizeof(uint32_t)));
-    FE_TRY(f, d.seq.ensure((size_t)std::max<int64_t>(seq_bytes, 16)));
-    FE_TRY(f, d.tuples.ensure((size_t)n_reads * sizeof(uint64_t)));
-    FE_TRY(f, hipMemsetAsync(d.tuples.p, 0, (size_t)n_reads * sizeof(uint64_t), f->stream));
+    CLAIR_HIP_TRY(fe_fail(f), d.reads.ensure((size_t)n_reads * sizeof(clair_read_t)));
+    CLAIR_HIP_TRY(fe_fail(f), d.ops.ensure((size_t)n_ops * sizeof(clair_op_t)));
+    CLAIR_HIP_TRY(fe_fail(f), d.op_elem.ensure(((size_t)n_ops + 1) * sizeof(uint32_t)));
+    CLAIR_HIP_TRY(fe_fail(f), d.seq.ensure((size_t)std::max<int64_t>(seq_bytes, 16)));
+    CLAIR_HIP_TRY(fe_fail(f), d.tuples.ensure((size_t)n_reads * sizeof(uint64_t)));
+    CLAIR_HIP_TRY(fe_fail(f), hipMemsetAsync(d.tuples.p, 0, (size_t)n_reads * sizeof(uint64_t), f->stream));
     *out = &d;
     return 0;
 }
 
 // the part of clair_frontend_create that can fail on the device (the caller destroys the handle then)
 int frontend_init(clair_frontend *f, const char *ref_seq, int64_t ref_len) {
-    auto failed = [](const char *what, hipError_t err) { return err != hipSuccess && fe_fail(nullptr, "%s failed: %s", what, hipGetErrorString(err)); };
+    auto failed = [](const char *what, hipError_t err) { return err != hipSuccess && fe_fail(nullptr)("%s failed: %s", what, hipGetErrorString(err)); };
     if (failed("hipSetDevice", hipSetDevice(f->device))) return 1;
     if (failed("hipStreamCreate", hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking))) return 1;
     Region &g = f->g;
@@ -1555,15 +1493,12 @@ const char *clair_frontend_last_error(const clair_frontend_t *f) { return f ? f-
 
 int clair_frontend_create(int device, const char *ref_seq, int64_t ref_len, int64_t reference_start_0_based, int64_t span_lo, int64_t span_hi,
                           clair_frontend_t **out) {
-    if (!out) return fe_fail(nullptr, "out is NULL");
+    if (!out) return fe_fail(nullptr)("out is NULL");
     *out = nullptr;
-    if (!ref_seq || ref_len < 0) return fe_fail(nullptr, "reference sequence missing");
-    if (span_hi <= span_lo) return fe_fail(nullptr, "empty span [%lld, %lld)", (long long)span_lo, (long long)span_hi);
-    if (span_hi - span_lo > ((int64_t)1 << 32) - 8192) return fe_fail(nullptr, "span of %lld positions is beyond one front end (2^32)", (long long)(span_hi - span_lo));
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1)
-        return fe_fail(nullptr, "no HIP device is visible: the front end runs on an MI355X only (the host code is clair_host_evc_* / clair_host_pileup_*)");
-    if (device < 0 || device >= n_dev) return fe_fail(nullptr, "device %d out of range [0,%d)", device, n_dev);
+    if (!ref_seq || ref_len < 0) return fe_fail(nullptr)("reference sequence missing");
+    if (span_hi <= span_lo) return fe_fail(nullptr)("empty span [%lld, %lld)", (long long)span_lo, (long long)span_hi);
+    if (span_hi - span_lo > ((int64_t)1 << 32) - 8192) return fe_fail(nullptr)("span of %lld positions is beyond one front end (2^32)", (long long)(span_hi - span_lo));
+    if (hip_device_check(fe_fail(nullptr), device, "the front end runs on an MI355X only (the host code is clair_host_evc_* / clair_host_pileup_*)")) return 1;
     clair_frontend *f = new clair_frontend;
     { const char *t = getenv("CLAIR_AMD_FE_TALLY"); f->tally_per_base = t && !strcmp(t, "atomic"); }
     { const char *t = getenv("CLAIR_AMD_FE_PASS2"); f->pass2_per_base = t && !strcmp(t, "base"); }
@@ -1600,8 +1535,8 @@ static int launch_tally(clair_frontend *f, const Slab &d, int64_t p_first, int64
         hipLaunchKernelGGL(fe_tally_kernel, dim3(blocks_for(d.n_elem, 256)), dim3(256), 0, f->stream, f->g, f->view(d));
         return 0;
     }
-    FE_TRY(f, f->span.ensure(sizeof(uint32_t)));
-    FE_TRY(f, hipMemsetAsync(f->span.p, 0, sizeof(uint32_t), f->stream));
+    CLAIR_HIP_TRY(fe_fail(f), f->span.ensure(sizeof(uint32_t)));
+    CLAIR_HIP_TRY(fe_fail(f), hipMemsetAsync(f->span.p, 0, sizeof(uint32_t), f->stream));
     hipLaunchKernelGGL(fe_slab_span_kernel, dim3(blocks_for(d.n_reads, 256)), dim3(256), 0, f->stream, f->view(d), (uint32_t)d.n_reads, f->span.as<uint32_t>());
     const int64_t n_tiles = (f->g.n + TT_POS - 1) / TT_POS;
     const int64_t tile0 = std::min(std::max<int64_t>((p_first - f->g.lo) / TT_POS - (p_first < f->g.lo ? 1 : 0), 0), n_tiles - 1);
@@ -1626,37 +1561,37 @@ static int pack_lines(clair_frontend *f, DeviceTemp &tmp, const uint8_t *src, bo
     int64_t *cand = nullptr, *kept = nullptr;
     uint8_t *keep = nullptr;
     uint32_t *line_sum = nullptr;
-    FE_TRY(f, tmp.get((void **)&keep, (size_t)n_lines + 1));
-    FE_TRY(f, tmp.get((void **)&line_sum, ((size_t)blocks_for(n_lines + 1, SCAN_BLOCK) + 2) * sizeof(uint32_t)));
+    CLAIR_HIP_TRY(fe_fail(f), tmp.get((void **)&keep, (size_t)n_lines + 1));
+    CLAIR_HIP_TRY(fe_fail(f), tmp.get((void **)&line_sum, ((size_t)blocks_for(n_lines + 1, SCAN_BLOCK) + 2) * sizeof(uint32_t)));
     int64_t n_cand = 0, n_kept = 0;
     if (scan_count(f, is_cand, n_lines, line_sum, d_count + 1, &n_cand)) return 1;
-    FE_TRY(f, tmp.get((void **)&cand, (size_t)n_cand * sizeof(int64_t)));
+    CLAIR_HIP_TRY(fe_fail(f), tmp.get((void **)&cand, (size_t)n_cand * sizeof(int64_t)));
     if (scan_write(f, is_cand, n_lines, line_sum, d_count + 1, nullptr, cand, 0)) return 1;
     if (n_cand) hipLaunchKernelGGL(fe_text_dcov_kernel, dim3(blocks_for(n_cand, 256)), dim3(256), 0, f->stream, lines, (const int64_t *)cand, n_cand, f->text_opt.dcov, carry);
     hipLaunchKernelGGL(fe_text_keep_kernel, dim3(blocks_for(n_lines, 256)), dim3(256), 0, f->stream, (const TextLine *)lines, n_lines, keep);
-    FE_TRY(f, hipGetLastError());
+    CLAIR_HIP_TRY(fe_fail(f), hipGetLastError());
     if (scan_count(f, keep, n_lines, line_sum, d_count + 2, &n_kept)) return 1;
-    FE_TRY(f, tmp.get((void **)&kept, (size_t)n_kept * sizeof(int64_t)));
+    CLAIR_HIP_TRY(fe_fail(f), tmp.get((void **)&kept, (size_t)n_kept * sizeof(int64_t)));
     if (scan_write(f, keep, n_lines, line_sum, d_count + 2, nullptr, kept, 0)) return 1;
     uint32_t *op0 = nullptr, *elem0 = nullptr, *seq0 = nullptr;
     uint64_t *d_totals = nullptr;
-    FE_TRY(f, tmp.get((void **)&op0, (size_t)n_kept * sizeof(uint32_t)));
-    FE_TRY(f, tmp.get((void **)&elem0, (size_t)n_kept * sizeof(uint32_t)));
-    FE_TRY(f, tmp.get((void **)&seq0, (size_t)n_kept * sizeof(uint32_t)));
-    FE_TRY(f, tmp.get((void **)&d_totals, 5 * sizeof(uint64_t)));
+    CLAIR_HIP_TRY(fe_fail(f), tmp.get((void **)&op0, (size_t)n_kept * sizeof(uint32_t)));
+    CLAIR_HIP_TRY(fe_fail(f), tmp.get((void **)&elem0, (size_t)n_kept * sizeof(uint32_t)));
+    CLAIR_HIP_TRY(fe_fail(f), tmp.get((void **)&seq0, (size_t)n_kept * sizeof(uint32_t)));
+    CLAIR_HIP_TRY(fe_fail(f), tmp.get((void **)&d_totals, 5 * sizeof(uint64_t)));
     hipLaunchKernelGGL(fe_text_offsets_kernel, dim3(1), dim3(256), 0, f->stream, (const TextLine *)lines, n_lines, (const int64_t *)kept, n_kept, (const int64_t *)cand, n_cand,
                        op0, elem0, seq0, d_totals, carry, f->d_text_state.as<TextState>());
-    FE_TRY(f, hipGetLastError());
+    CLAIR_HIP_TRY(fe_fail(f), hipGetLastError());
     uint64_t totals[5] = {0, 0, 0, 0, 0};
     TextState after{};
-    FE_TRY(f, hipMemcpyAsync(totals, d_totals, sizeof totals, hipMemcpyDeviceToHost, f->stream));
-    FE_TRY(f, hipMemcpyAsync(&after, f->d_text_state.p, sizeof after, hipMemcpyDeviceToHost, f->stream));
-    FE_TRY(f, hipStreamSynchronize(f->stream));
+    CLAIR_HIP_TRY(fe_fail(f), hipMemcpyAsync(totals, d_totals, sizeof totals, hipMemcpyDeviceToHost, f->stream));
+    CLAIR_HIP_TRY(fe_fail(f), hipMemcpyAsync(&after, f->d_text_state.p, sizeof after, hipMemcpyDeviceToHost, f->stream));
+    CLAIR_HIP_TRY(fe_fail(f), hipStreamSynchronize(f->stream));
     if (after.malformed != 0xffffffffu) {
         *malformed = after.malformed;
         return 2;
     }
-    if (totals[0] > 0xfffffff0ull || totals[1] > 0xfffffff0ull || totals[4] > 0xfffffff0ull) return fe_fail(f, "chunk too dense for 32-bit offsets: feed smaller chunks");
+    if (totals[0] > 0xfffffff0ull || totals[1] > 0xfffffff0ull || totals[4] > 0xfffffff0ull) return fe_fail(f)("chunk too dense for 32-bit offsets: feed smaller chunks");
     after.malformed = 0;
     f->text_state = after;
     if (n_kept == 0 || totals[0] == 0) return 0;
@@ -1673,27 +1608,27 @@ static int pack_lines(clair_frontend *f, DeviceTemp &tmp, const uint8_t *src, bo
     // one: the word is cumulative, and a start below the previous slab's last is exactly such a case) the per-base kernel is used, as
     // clair_frontend_add_reads does -- an unsorted slab is flagged AND tallied correctly on both entry points
     if (launch_tally(f, d, (int64_t)totals[3], after.last_pos + (int64_t)totals[2], !(after.anomalies & CLAIR_FE_UNSORTED))) return 1;
-    FE_TRY(f, hipGetLastError());
-    FE_TRY(f, hipStreamSynchronize(f->stream));
+    CLAIR_HIP_TRY(fe_fail(f), hipGetLastError());
+    CLAIR_HIP_TRY(fe_fail(f), hipStreamSynchronize(f->stream));
     return 0;
 }
 
 int clair_frontend_add_reads(clair_frontend_t *f, const clair_read_t *reads, int64_t n_reads, const clair_op_t *ops, int64_t n_ops,
                              const uint32_t *op_elem, const uint8_t *seq, int64_t seq_bytes) {
-    if (!f) return fe_fail(nullptr, "front end is NULL");
-    if (n_reads < 0 || n_ops < 0 || seq_bytes < 0) return fe_fail(f, "negative slab size");
+    if (!f) return fe_fail(nullptr)("front end is NULL");
+    if (n_reads < 0 || n_ops < 0 || seq_bytes < 0) return fe_fail(f)("negative slab size");
     if (n_reads == 0 || n_ops == 0) return 0;
-    if (!reads || !ops || !op_elem || (!seq && seq_bytes > 0)) return fe_fail(f, "NULL slab array");
-    if (n_ops > 0xfffffff0ll || seq_bytes > 0xfffffff0ll) return fe_fail(f, "slab too large for 32-bit offsets");
-    if (f->n_candidates >= 0) return fe_fail(f, "reads cannot be added after the candidates were fixed");
-    FE_TRY(f, hipSetDevice(f->device));
+    if (!reads || !ops || !op_elem || (!seq && seq_bytes > 0)) return fe_fail(f)("NULL slab array");
+    if (n_ops > 0xfffffff0ll || seq_bytes > 0xfffffff0ll) return fe_fail(f)("slab too large for 32-bit offsets");
+    if (f->n_candidates >= 0) return fe_fail(f)("reads cannot be added after the candidates were fixed");
+    CLAIR_HIP_TRY(fe_fail(f), hipSetDevice(f->device));
     Slab *slab = nullptr;
     if (new_slab(f, n_reads, n_ops, op_elem[n_ops], seq_bytes, &slab)) return 1;
     const Slab &d = *slab;
-    FE_TRY(f, hipMemcpyAsync(d.reads.p, reads, (size_t)n_reads * sizeof(clair_read_t), hipMemcpyHostToDevice, f->stream));
-    FE_TRY(f, hipMemcpyAsync(d.ops.p, ops, (size_t)n_ops * sizeof(clair_op_t), hipMemcpyHostToDevice, f->stream));
-    FE_TRY(f, hipMemcpyAsync(d.op_elem.p, op_elem, ((size_t)n_ops + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, f->stream));
-    if (seq_bytes) FE_TRY(f, hipMemcpyAsync(d.seq.p, seq, (size_t)seq_bytes, hipMemcpyHostToDevice, f->stream));
+    CLAIR_HIP_TRY(fe_fail(f), hipMemcpyAsync(d.reads.p, reads, (size_t)n_reads * sizeof(clair_read_t), hipMemcpyHostToDevice, f->stream));
+    CLAIR_HIP_TRY(fe_fail(f), hipMemcpyAsync(d.ops.p, ops, (size_t)n_ops * sizeof(clair_op_t), hipMemcpyHostToDevice, f->stream));
+    CLAIR_HIP_TRY(fe_fail(f), hipMemcpyAsync(d.op_elem.p, op_elem, ((size_t)n_ops + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, f->stream));
+    if (seq_bytes) CLAIR_HIP_TRY(fe_fail(f), hipMemcpyAsync(d.seq.p, seq, (size_t)seq_bytes, hipMemcpyHostToDevice, f->stream));
     {   // where the slab lies, for the grid of the tiled tally: first and last start, the longest reach (host arrays: one look at every alignment's last operation)
         int64_t p_first = reads[0].pos0, p_last = reads[0].pos0, reach = 0;
         bool sorted = true;
@@ -1712,21 +1647,21 @@ int clair_frontend_add_reads(clair_frontend_t *f, const clair_read_t *reads, int
         if (!sorted) hipLaunchKernelGGL(fe_flag_kernel, dim3(1), dim3(1), 0, f->stream, f->g, (uint32_t)CLAIR_FE_UNSORTED);
         if (launch_tally(f, d, p_first, p_last + reach, sorted)) return 1;
     }
-    FE_TRY(f, hipGetLastError());
+    CLAIR_HIP_TRY(fe_fail(f), hipGetLastError());
     // the caller's arrays may be reused as soon as this returns (the packer's slab is reset): wait for the copies
-    FE_TRY(f, hipStreamSynchronize(f->stream));
+    CLAIR_HIP_TRY(fe_fail(f), hipStreamSynchronize(f->stream));
     return 0;
 }
 
 int clair_frontend_text_options(clair_frontend_t *f, const char *ctg_name, int dcov, int evc_min_mq, int pile_min_mq, int64_t pile_start, int64_t pile_end) {
-    if (!f) return fe_fail(nullptr, "front end is NULL");
-    if (!ctg_name) return fe_fail(f, "contig name missing");
-    if (!f->slabs.empty() && f->text_ready) return fe_fail(f, "text options cannot change once text was added");
-    FE_TRY(f, hipSetDevice(f->device));
+    if (!f) return fe_fail(nullptr)("front end is NULL");
+    if (!ctg_name) return fe_fail(f)("contig name missing");
+    if (!f->slabs.empty() && f->text_ready) return fe_fail(f)("text options cannot change once text was added");
+    CLAIR_HIP_TRY(fe_fail(f), hipSetDevice(f->device));
     const size_t n = strlen(ctg_name);
-    FE_TRY(f, f->ctg.ensure(n));
-    if (n) FE_TRY(f, hipMemcpy(f->ctg.p, ctg_name, n, hipMemcpyHostToDevice));
-    FE_TRY(f, f->d_text_state.ensure(sizeof(TextState)));
+    CLAIR_HIP_TRY(fe_fail(f), f->ctg.ensure(n));
+    if (n) CLAIR_HIP_TRY(fe_fail(f), hipMemcpy(f->ctg.p, ctg_name, n, hipMemcpyHostToDevice));
+    CLAIR_HIP_TRY(fe_fail(f), f->d_text_state.ensure(sizeof(TextState)));
     const bool have_region = pile_start >= 0 && pile_end >= 0;
     f->text_opt = TextOptions{f->ctg.as<uint8_t>(), (int)n, dcov, evc_min_mq, pile_min_mq, have_region ? pile_start : -1, have_region ? pile_end : -1, 0};
     f->text_state = TextState{};
@@ -1736,52 +1671,52 @@ int clair_frontend_text_options(clair_frontend_t *f, const char *ctg_name, int d
 
 // returns 2 (not 1) when a line of the text is malformed: clair_host_sampack_feed on the same text names the line and the column
 int clair_frontend_add_text(clair_frontend_t *f, const char *sam, int64_t len) {
-    if (!f) return fe_fail(nullptr, "front end is NULL");
-    if (!f->text_ready) return fe_fail(f, "call clair_frontend_text_options first");
-    if (f->bam_mode) return fe_fail(f, "clair_frontend_bam_options was called: records come through clair_frontend_add_bam");
-    if (len < 0 || (len > 0 && !sam)) return fe_fail(f, "bad text");
+    if (!f) return fe_fail(nullptr)("front end is NULL");
+    if (!f->text_ready) return fe_fail(f)("call clair_frontend_text_options first");
+    if (f->bam_mode) return fe_fail(f)("clair_frontend_bam_options was called: records come through clair_frontend_add_bam");
+    if (len < 0 || (len > 0 && !sam)) return fe_fail(f)("bad text");
     if (len == 0) return 0;
-    if (len > 0x7ffffff0ll) return fe_fail(f, "text chunk of %lld bytes: at most 2 GB at a time", (long long)len);
-    if (sam[len - 1] != '\n') return fe_fail(f, "the text must end at a line end");
-    if (f->n_candidates >= 0) return fe_fail(f, "reads cannot be added after the candidates were fixed");
-    FE_TRY(f, hipSetDevice(f->device));
+    if (len > 0x7ffffff0ll) return fe_fail(f)("text chunk of %lld bytes: at most 2 GB at a time", (long long)len);
+    if (sam[len - 1] != '\n') return fe_fail(f)("the text must end at a line end");
+    if (f->n_candidates >= 0) return fe_fail(f)("reads cannot be added after the candidates were fixed");
+    CLAIR_HIP_TRY(fe_fail(f), hipSetDevice(f->device));
     DeviceTemp tmp;
     uint8_t *d_text = nullptr;
     uint32_t *block_sum = nullptr, *d_count = nullptr;
-    FE_TRY(f, tmp.get((void **)&d_text, (size_t)len + 16));            // fe_text_seq_kernel reads whole dwords
-    FE_TRY(f, tmp.get((void **)&block_sum, ((size_t)blocks_for(len + 1, SCAN_BLOCK) + 2) * sizeof(uint32_t)));
-    FE_TRY(f, tmp.get((void **)&d_count, 4 * sizeof(uint32_t)));
-    FE_TRY(f, hipMemcpyAsync(d_text, sam, (size_t)len, hipMemcpyHostToDevice, f->stream));
+    CLAIR_HIP_TRY(fe_fail(f), tmp.get((void **)&d_text, (size_t)len + 16));            // fe_text_seq_kernel reads whole dwords
+    CLAIR_HIP_TRY(fe_fail(f), tmp.get((void **)&block_sum, ((size_t)blocks_for(len + 1, SCAN_BLOCK) + 2) * sizeof(uint32_t)));
+    CLAIR_HIP_TRY(fe_fail(f), tmp.get((void **)&d_count, 4 * sizeof(uint32_t)));
+    CLAIR_HIP_TRY(fe_fail(f), hipMemcpyAsync(d_text, sam, (size_t)len, hipMemcpyHostToDevice, f->stream));
     int64_t n_lines = 0;
     if (scan_count(f, d_text, len, block_sum, d_count, &n_lines, true)) return 1;
     int64_t *newline = nullptr;
     TextLine *lines = nullptr;
     uint8_t *is_cand = nullptr;
-    FE_TRY(f, tmp.get((void **)&newline, (size_t)n_lines * sizeof(int64_t)));
+    CLAIR_HIP_TRY(fe_fail(f), tmp.get((void **)&newline, (size_t)n_lines * sizeof(int64_t)));
     if (scan_write(f, d_text, len, block_sum, d_count, nullptr, newline, 0, true)) return 1;
-    FE_TRY(f, tmp.get((void **)&lines, (size_t)n_lines * sizeof(TextLine)));
-    FE_TRY(f, tmp.get((void **)&is_cand, (size_t)n_lines + 1));
+    CLAIR_HIP_TRY(fe_fail(f), tmp.get((void **)&lines, (size_t)n_lines * sizeof(TextLine)));
+    CLAIR_HIP_TRY(fe_fail(f), tmp.get((void **)&is_cand, (size_t)n_lines + 1));
     TextState carry = f->text_state;
     carry.malformed = 0xffffffffu;
-    FE_TRY(f, hipMemcpyAsync(f->d_text_state.p, &carry, sizeof carry, hipMemcpyHostToDevice, f->stream));
+    CLAIR_HIP_TRY(fe_fail(f), hipMemcpyAsync(f->d_text_state.p, &carry, sizeof carry, hipMemcpyHostToDevice, f->stream));
     hipLaunchKernelGGL(fe_text_lines_kernel, dim3(blocks_for(n_lines, 256)), dim3(256), 0, f->stream, (const uint8_t *)d_text, (const int64_t *)newline, n_lines,
                        f->text_opt, lines, is_cand, f->d_text_state.as<TextState>());
-    FE_TRY(f, hipGetLastError());
+    CLAIR_HIP_TRY(fe_fail(f), hipGetLastError());
     uint32_t malformed = 0;
     const int rc = pack_lines(f, tmp, d_text, false, lines, is_cand, n_lines, d_count, carry, &malformed);
     if (rc == 2)
-        fe_fail(f, "line %u of this chunk (%lld lines before it) is not an alignment line the scripts accept: clair_host_sampack_feed on the same text names "
+        fe_fail(f)("line %u of this chunk (%lld lines before it) is not an alignment line the scripts accept: clair_host_sampack_feed on the same text names "
                    "the column", malformed - 1, (long long)f->text_state.lines);
     return rc;
 }
 
 int clair_frontend_bam_options(clair_frontend_t *f, int tid, int dcov, int evc_min_mq, int pile_min_mq, int64_t pile_start, int64_t pile_end,
                                int64_t region_lo, int64_t region_hi) {
-    if (!f) return fe_fail(nullptr, "front end is NULL");
-    if (tid < 0) return fe_fail(f, "reference id %d", tid);
-    if (!f->slabs.empty() && f->text_ready) return fe_fail(f, "BAM options cannot change once records were added");
-    FE_TRY(f, hipSetDevice(f->device));
-    FE_TRY(f, f->d_text_state.ensure(sizeof(TextState)));
+    if (!f) return fe_fail(nullptr)("front end is NULL");
+    if (tid < 0) return fe_fail(f)("reference id %d", tid);
+    if (!f->slabs.empty() && f->text_ready) return fe_fail(f)("BAM options cannot change once records were added");
+    CLAIR_HIP_TRY(fe_fail(f), hipSetDevice(f->device));
+    CLAIR_HIP_TRY(fe_fail(f), f->d_text_state.ensure(sizeof(TextState)));
     const bool have_pile = pile_start >= 0 && pile_end >= 0, have_region = region_lo >= 0 && region_hi >= 0;
     f->text_opt = TextOptions{nullptr, 0, dcov, evc_min_mq, pile_min_mq, have_pile ? pile_start : -1, have_pile ? pile_end : -1, 0};
     f->bam_opt = BamOptions{tid, have_region ? region_lo : -1, have_region ? region_hi : -1};
@@ -1792,78 +1727,78 @@ int clair_frontend_bam_options(clair_frontend_t *f, int tid, int dcov, int evc_m
 }
 
 int clair_frontend_bam_subsample(clair_frontend_t *f, int64_t seed, double frac) {
-    if (!f) return fe_fail(nullptr, "front end is NULL");
-    if (!f->text_ready || !f->bam_mode) return fe_fail(f, "call clair_frontend_bam_options first");
-    if (f->text_state.lines) return fe_fail(f, "the subsample option cannot change once records were added");
-    if (seed < 0 || seed > 0xffffffffll) return fe_fail(f, "subsample seed %lld: 0 .. 4294967295", (long long)seed);
+    if (!f) return fe_fail(nullptr)("front end is NULL");
+    if (!f->text_ready || !f->bam_mode) return fe_fail(f)("call clair_frontend_bam_options first");
+    if (f->text_state.lines) return fe_fail(f)("the subsample option cannot change once records were added");
+    if (seed < 0 || seed > 0xffffffffll) return fe_fail(f)("subsample seed %lld: 0 .. 4294967295", (long long)seed);
     f->bam_opt.seed = (uint32_t)seed;
     f->bam_opt.frac = frac > 0.0 ? frac : 0.0;
     return 0;
 }
 
 int clair_frontend_bam_lookup(clair_frontend_t *f, int keep) {
-    if (!f) return fe_fail(nullptr, "front end is NULL");
-    if (!f->text_ready || !f->bam_mode) return fe_fail(f, "call clair_frontend_bam_options first");
-    if (f->text_state.lines) return fe_fail(f, "the look-up option cannot change once records were added");
+    if (!f) return fe_fail(nullptr)("front end is NULL");
+    if (!f->text_ready || !f->bam_mode) return fe_fail(f)("call clair_frontend_bam_options first");
+    if (f->text_state.lines) return fe_fail(f)("the look-up option cannot change once records were added");
     f->text_opt.lookup = keep != 0;
     return 0;
 }
 
 // returns 2 (not 1) when a record is malformed: the error names its index in this chunk (clair_host_bam_render on the same records says what)
 int clair_frontend_add_bam(clair_frontend_t *f, const uint8_t *records, int64_t len, const int64_t *offsets, int64_t n_records) {
-    if (!f) return fe_fail(nullptr, "front end is NULL");
-    if (!f->text_ready || !f->bam_mode) return fe_fail(f, "call clair_frontend_bam_options first");
-    if (len < 0 || n_records < 0 || (n_records > 0 && (!records || !offsets))) return fe_fail(f, "bad record chunk");
+    if (!f) return fe_fail(nullptr)("front end is NULL");
+    if (!f->text_ready || !f->bam_mode) return fe_fail(f)("call clair_frontend_bam_options first");
+    if (len < 0 || n_records < 0 || (n_records > 0 && (!records || !offsets))) return fe_fail(f)("bad record chunk");
     if (n_records == 0) return 0;
-    if (len > 0x7ffffff0ll) return fe_fail(f, "record chunk of %lld bytes: at most 2 GB at a time", (long long)len);
-    if (n_records > 0xfffffff0ll) return fe_fail(f, "%lld records in one chunk", (long long)n_records);
-    if (f->n_candidates >= 0) return fe_fail(f, "reads cannot be added after the candidates were fixed");
-    FE_TRY(f, hipSetDevice(f->device));
+    if (len > 0x7ffffff0ll) return fe_fail(f)("record chunk of %lld bytes: at most 2 GB at a time", (long long)len);
+    if (n_records > 0xfffffff0ll) return fe_fail(f)("%lld records in one chunk", (long long)n_records);
+    if (f->n_candidates >= 0) return fe_fail(f)("reads cannot be added after the candidates were fixed");
+    CLAIR_HIP_TRY(fe_fail(f), hipSetDevice(f->device));
     DeviceTemp tmp;
     uint8_t *d_rec = nullptr, *pass = nullptr, *is_cand = nullptr;
     int64_t *d_off = nullptr, *shown = nullptr;
     uint32_t *rec_sum = nullptr, *d_count = nullptr;
     TextLine *all = nullptr, *lines = nullptr;
-    FE_TRY(f, tmp.get((void **)&d_rec, (size_t)len + 16));               // fields and bases are read as whole dwords
-    FE_TRY(f, tmp.get((void **)&d_off, (size_t)n_records * sizeof(int64_t)));
-    FE_TRY(f, tmp.get((void **)&all, (size_t)n_records * sizeof(TextLine)));
-    FE_TRY(f, tmp.get((void **)&pass, (size_t)n_records + 1));
-    FE_TRY(f, tmp.get((void **)&rec_sum, ((size_t)blocks_for(n_records + 1, SCAN_BLOCK) + 2) * sizeof(uint32_t)));
-    FE_TRY(f, tmp.get((void **)&d_count, 4 * sizeof(uint32_t)));
-    FE_TRY(f, hipMemcpyAsync(d_rec, records, (size_t)len, hipMemcpyHostToDevice, f->stream));
-    FE_TRY(f, hipMemcpyAsync(d_off, offsets, (size_t)n_records * sizeof(int64_t), hipMemcpyHostToDevice, f->stream));
+    CLAIR_HIP_TRY(fe_fail(f), tmp.get((void **)&d_rec, (size_t)len + 16));               // fields and bases are read as whole dwords
+    CLAIR_HIP_TRY(fe_fail(f), tmp.get((void **)&d_off, (size_t)n_records * sizeof(int64_t)));
+    CLAIR_HIP_TRY(fe_fail(f), tmp.get((void **)&all, (size_t)n_records * sizeof(TextLine)));
+    CLAIR_HIP_TRY(fe_fail(f), tmp.get((void **)&pass, (size_t)n_records + 1));
+    CLAIR_HIP_TRY(fe_fail(f), tmp.get((void **)&rec_sum, ((size_t)blocks_for(n_records + 1, SCAN_BLOCK) + 2) * sizeof(uint32_t)));
+    CLAIR_HIP_TRY(fe_fail(f), tmp.get((void **)&d_count, 4 * sizeof(uint32_t)));
+    CLAIR_HIP_TRY(fe_fail(f), hipMemcpyAsync(d_rec, records, (size_t)len, hipMemcpyHostToDevice, f->stream));
+    CLAIR_HIP_TRY(fe_fail(f), hipMemcpyAsync(d_off, offsets, (size_t)n_records * sizeof(int64_t), hipMemcpyHostToDevice, f->stream));
     TextState carry = f->text_state;
     carry.malformed = 0xffffffffu;
-    FE_TRY(f, hipMemcpyAsync(f->d_text_state.p, &carry, sizeof carry, hipMemcpyHostToDevice, f->stream));
+    CLAIR_HIP_TRY(fe_fail(f), hipMemcpyAsync(f->d_text_state.p, &carry, sizeof carry, hipMemcpyHostToDevice, f->stream));
     hipLaunchKernelGGL(fe_bam_records_kernel, dim3(blocks_for(n_records, 256)), dim3(256), 0, f->stream, (const uint8_t *)d_rec, len, (const int64_t *)d_off,
                        n_records, f->text_opt, f->bam_opt, all, pass, f->d_text_state.as<TextState>());
-    FE_TRY(f, hipGetLastError());
+    CLAIR_HIP_TRY(fe_fail(f), hipGetLastError());
     int64_t n_lines = 0;                                                  // the records the view prints
     if (scan_count(f, pass, n_records, rec_sum, d_count + 3, &n_lines)) return 1;
     uint32_t malformed = 0;
     int rc = 0;
     if (n_lines == 0) {                                                   // nothing for the text path's kernels: the state is the carry's
         TextState after{};
-        FE_TRY(f, hipMemcpyAsync(&after, f->d_text_state.p, sizeof after, hipMemcpyDeviceToHost, f->stream));
-        FE_TRY(f, hipStreamSynchronize(f->stream));
+        CLAIR_HIP_TRY(fe_fail(f), hipMemcpyAsync(&after, f->d_text_state.p, sizeof after, hipMemcpyDeviceToHost, f->stream));
+        CLAIR_HIP_TRY(fe_fail(f), hipStreamSynchronize(f->stream));
         if (after.malformed != 0xffffffffu) { malformed = after.malformed; rc = 2; }
     } else {
-        FE_TRY(f, tmp.get((void **)&shown, (size_t)n_lines * sizeof(int64_t)));
+        CLAIR_HIP_TRY(fe_fail(f), tmp.get((void **)&shown, (size_t)n_lines * sizeof(int64_t)));
         if (scan_write(f, pass, n_records, rec_sum, d_count + 3, nullptr, shown, 0)) return 1;
-        FE_TRY(f, tmp.get((void **)&lines, (size_t)n_lines * sizeof(TextLine)));
-        FE_TRY(f, tmp.get((void **)&is_cand, (size_t)n_lines + 1));
+        CLAIR_HIP_TRY(fe_fail(f), tmp.get((void **)&lines, (size_t)n_lines * sizeof(TextLine)));
+        CLAIR_HIP_TRY(fe_fail(f), tmp.get((void **)&is_cand, (size_t)n_lines + 1));
         hipLaunchKernelGGL(fe_bam_gather_kernel, dim3(blocks_for(n_lines, 256)), dim3(256), 0, f->stream, (const TextLine *)all, (const int64_t *)shown, n_lines,
                            lines, is_cand);
-        FE_TRY(f, hipGetLastError());
+        CLAIR_HIP_TRY(fe_fail(f), hipGetLastError());
         rc = pack_lines(f, tmp, d_rec, true, lines, is_cand, n_lines, d_count, carry, &malformed);
     }
-    if (rc == 2) fe_fail(f, "record %u of this chunk is not a well-formed BAM record", malformed - 1);
+    if (rc == 2) fe_fail(f)("record %u of this chunk is not a well-formed BAM record", malformed - 1);
     return rc;
 }
 
 int clair_frontend_text_stats(clair_frontend_t *f, int64_t *stats) {
-    if (!f) return fe_fail(nullptr, "front end is NULL");
-    if (!stats) return fe_fail(f, "stats is NULL");
+    if (!f) return fe_fail(nullptr)("front end is NULL");
+    if (!stats) return fe_fail(f)("stats is NULL");
     stats[0] = f->text_state.lines;
     stats[1] = f->text_state.evc_reads;
     stats[2] = f->text_state.pile_reads;
@@ -1872,64 +1807,64 @@ int clair_frontend_text_stats(clair_frontend_t *f, int64_t *stats) {
 }
 
 int clair_frontend_slab_reads(clair_frontend_t *f, int64_t slab, struct clair_read *reads, int64_t capacity, int64_t *n_reads) {
-    if (!f) return fe_fail(nullptr, "front end is NULL");
-    if (slab < 0 || slab >= (int64_t)f->slabs.size()) return fe_fail(f, "slab %lld out of range [0, %lld)", (long long)slab, (long long)f->slabs.size());
-    if (!n_reads) return fe_fail(f, "n_reads is NULL");
+    if (!f) return fe_fail(nullptr)("front end is NULL");
+    if (slab < 0 || slab >= (int64_t)f->slabs.size()) return fe_fail(f)("slab %lld out of range [0, %lld)", (long long)slab, (long long)f->slabs.size());
+    if (!n_reads) return fe_fail(f)("n_reads is NULL");
     const Slab &s = f->slabs[(size_t)slab];
     *n_reads = s.n_reads;
     if (!reads) return 0;
-    if (capacity < s.n_reads) return fe_fail(f, "room for %lld alignments, the slab holds %lld", (long long)capacity, (long long)s.n_reads);
-    FE_TRY(f, hipSetDevice(f->device));
-    FE_TRY(f, hipMemcpy(reads, s.reads.p, (size_t)s.n_reads * sizeof(clair_read_t), hipMemcpyDeviceToHost));
+    if (capacity < s.n_reads) return fe_fail(f)("room for %lld alignments, the slab holds %lld", (long long)capacity, (long long)s.n_reads);
+    CLAIR_HIP_TRY(fe_fail(f), hipSetDevice(f->device));
+    CLAIR_HIP_TRY(fe_fail(f), hipMemcpy(reads, s.reads.p, (size_t)s.n_reads * sizeof(clair_read_t), hipMemcpyDeviceToHost));
     return 0;
 }
 
 int clair_frontend_find_candidates(clair_frontend_t *f, double min_coverage, double threshold, int64_t ctg_start, int64_t ctg_end,
                                    const int64_t *bed_start, const int64_t *bed_end, int64_t n_bed, int64_t *n_candidates) {
-    if (!f) return fe_fail(nullptr, "front end is NULL");
-    if (!n_candidates) return fe_fail(f, "n_candidates is NULL");
-    if (n_bed > 0 && (!bed_start || !bed_end)) return fe_fail(f, "bed intervals missing");
-    FE_TRY(f, hipSetDevice(f->device));
+    if (!f) return fe_fail(nullptr)("front end is NULL");
+    if (!n_candidates) return fe_fail(f)("n_candidates is NULL");
+    if (n_bed > 0 && (!bed_start || !bed_end)) return fe_fail(f)("bed intervals missing");
+    CLAIR_HIP_TRY(fe_fail(f), hipSetDevice(f->device));
     CandidateRule rule{min_coverage, threshold, ctg_start >= 0 && ctg_end >= 0 ? ctg_start : -1, ctg_end, nullptr, nullptr, n_bed < 0 ? -1 : 0};
     if (n_bed > 0 && upload_bed(f, bed_start, bed_end, n_bed, &rule.bed_start, &rule.bed_end, &rule.n_bed)) return 1;
     hipLaunchKernelGGL(fe_candidate_flags_kernel, dim3(blocks_for(f->g.n, 256)), dim3(256), 0, f->stream, f->g, rule, f->flags.as<uint8_t>());
-    FE_TRY(f, hipGetLastError());
+    CLAIR_HIP_TRY(fe_fail(f), hipGetLastError());
     return finish_candidates(f, n_candidates);
 }
 
 int clair_frontend_set_candidates(clair_frontend_t *f, const int64_t *positions, int64_t n_positions, int64_t *n_candidates) {
-    if (!f) return fe_fail(nullptr, "front end is NULL");
-    if (!n_candidates || (n_positions > 0 && !positions) || n_positions < 0) return fe_fail(f, "bad candidate list");
-    FE_TRY(f, hipSetDevice(f->device));
+    if (!f) return fe_fail(nullptr)("front end is NULL");
+    if (!n_candidates || (n_positions > 0 && !positions) || n_positions < 0) return fe_fail(f)("bad candidate list");
+    CLAIR_HIP_TRY(fe_fail(f), hipSetDevice(f->device));
     for (int64_t i = 1; i < n_positions; ++i)
         if (positions[i] <= positions[i - 1]) {     // the sequential code keeps list order (CreateTensor.py:86-109); this path needs it ascending
             uint32_t bit = CLAIR_FE_CANDIDATES, cur = 0;
-            FE_TRY(f, hipMemcpy(&cur, f->g.anomalies, sizeof cur, hipMemcpyDeviceToHost));
+            CLAIR_HIP_TRY(fe_fail(f), hipMemcpy(&cur, f->g.anomalies, sizeof cur, hipMemcpyDeviceToHost));
             cur |= bit;
-            FE_TRY(f, hipMemcpy(f->g.anomalies, &cur, sizeof cur, hipMemcpyHostToDevice));
+            CLAIR_HIP_TRY(fe_fail(f), hipMemcpy(f->g.anomalies, &cur, sizeof cur, hipMemcpyHostToDevice));
             break;
         }
-    FE_TRY(f, hipMemsetAsync(f->flags.p, 0, (size_t)f->g.n + 1, f->stream));
+    CLAIR_HIP_TRY(fe_fail(f), hipMemsetAsync(f->flags.p, 0, (size_t)f->g.n + 1, f->stream));
     if (n_positions) {
         DeviceBuffer d_pos;
-        FE_TRY(f, d_pos.ensure((size_t)n_positions * sizeof(int64_t)));
+        CLAIR_HIP_TRY(fe_fail(f), d_pos.ensure((size_t)n_positions * sizeof(int64_t)));
         hipError_t err = hipMemcpyAsync(d_pos.p, positions, (size_t)n_positions * sizeof(int64_t), hipMemcpyHostToDevice, f->stream);
         if (err == hipSuccess) {
             hipLaunchKernelGGL(fe_given_flags_kernel, dim3(blocks_for(n_positions, 256)), dim3(256), 0, f->stream, d_pos.as<const int64_t>(), n_positions, f->g.lo, f->g.n,
                                f->flags.as<uint8_t>());
             err = hipStreamSynchronize(f->stream);
         }
-        FE_TRY(f, err);
+        CLAIR_HIP_TRY(fe_fail(f), err);
     }
     return finish_candidates(f, n_candidates);
 }
 
 int clair_frontend_get_candidates(clair_frontend_t *f, int64_t *positions) {
-    if (!f) return fe_fail(nullptr, "front end is NULL");
-    if (f->n_candidates < 0) return fe_fail(f, "no candidates yet: call clair_frontend_find_candidates / _set_candidates first");
-    if (f->n_candidates && !positions) return fe_fail(f, "positions is NULL");
-    FE_TRY(f, hipSetDevice(f->device));
-    if (f->n_candidates) FE_TRY(f, hipMemcpy(positions, f->cand->centre.p, (size_t)f->n_candidates * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (!f) return fe_fail(nullptr)("front end is NULL");
+    if (f->n_candidates < 0) return fe_fail(f)("no candidates yet: call clair_frontend_find_candidates / _set_candidates first");
+    if (f->n_candidates && !positions) return fe_fail(f)("positions is NULL");
+    CLAIR_HIP_TRY(fe_fail(f), hipSetDevice(f->device));
+    if (f->n_candidates) CLAIR_HIP_TRY(fe_fail(f), hipMemcpy(positions, f->cand->centre.p, (size_t)f->n_candidates * sizeof(int64_t), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -1938,23 +1873,23 @@ int clair_frontend_build_windows(clair_frontend_t *f, int min_coverage, int drop
 }
 
 int clair_frontend_build_windows_ex(clair_frontend_t *f, int min_coverage, int drop_non_iupac_centre, int consider_left_edge, int64_t *n_windows) {
-    if (!f) return fe_fail(nullptr, "front end is NULL");
-    if (!n_windows) return fe_fail(f, "n_windows is NULL");
-    if (f->n_candidates < 0) return fe_fail(f, "no candidates yet: call clair_frontend_find_candidates / _set_candidates first");
-    FE_TRY(f, hipSetDevice(f->device));
+    if (!f) return fe_fail(nullptr)("front end is NULL");
+    if (!n_windows) return fe_fail(f)("n_windows is NULL");
+    if (f->n_candidates < 0) return fe_fail(f)("no candidates yet: call clair_frontend_find_candidates / _set_candidates first");
+    CLAIR_HIP_TRY(fe_fail(f), hipSetDevice(f->device));
     const int64_t nc = f->n_candidates, room = std::max<int64_t>(nc, 1);
     CandidateBuffers &cb = *f->cand;
-    FE_TRY(f, cb.ins.ensure((size_t)room * N_QUAD * sizeof(uint32_t)));
-    FE_TRY(f, cb.keep.ensure((size_t)room + 1));
-    FE_TRY(f, cb.window_tuples.ensure((size_t)room * sizeof(uint64_t)));
-    FE_TRY(f, cb.kept.ensure((size_t)room * sizeof(int64_t)));
-    FE_TRY(f, cb.block_sum.ensure(((size_t)blocks_for(room + 1, SCAN_BLOCK) + 1) * sizeof(uint32_t)));
-    FE_TRY(f, hipMemsetAsync(cb.ins.p, 0, cb.ins.bytes, f->stream));
+    CLAIR_HIP_TRY(fe_fail(f), cb.ins.ensure((size_t)room * N_QUAD * sizeof(uint32_t)));
+    CLAIR_HIP_TRY(fe_fail(f), cb.keep.ensure((size_t)room + 1));
+    CLAIR_HIP_TRY(fe_fail(f), cb.window_tuples.ensure((size_t)room * sizeof(uint64_t)));
+    CLAIR_HIP_TRY(fe_fail(f), cb.kept.ensure((size_t)room * sizeof(int64_t)));
+    CLAIR_HIP_TRY(fe_fail(f), cb.block_sum.ensure(((size_t)blocks_for(room + 1, SCAN_BLOCK) + 1) * sizeof(uint32_t)));
+    CLAIR_HIP_TRY(fe_fail(f), hipMemsetAsync(cb.ins.p, 0, cb.ins.bytes, f->stream));
     if (!consider_left_edge) {
-        FE_TRY(f, cb.late.ensure((size_t)room * N_POS * LATE_ROW * sizeof(uint32_t)));
-        FE_TRY(f, cb.tuple_diff.ensure(((size_t)room + 1) * sizeof(int)));
-        FE_TRY(f, hipMemsetAsync(cb.late.p, 0, cb.late.bytes, f->stream));
-        FE_TRY(f, hipMemsetAsync(cb.tuple_diff.p, 0, cb.tuple_diff.bytes, f->stream));
+        CLAIR_HIP_TRY(fe_fail(f), cb.late.ensure((size_t)room * N_POS * LATE_ROW * sizeof(uint32_t)));
+        CLAIR_HIP_TRY(fe_fail(f), cb.tuple_diff.ensure(((size_t)room + 1) * sizeof(int)));
+        CLAIR_HIP_TRY(fe_fail(f), hipMemsetAsync(cb.late.p, 0, cb.late.bytes, f->stream));
+        CLAIR_HIP_TRY(fe_fail(f), hipMemsetAsync(cb.tuple_diff.p, 0, cb.tuple_diff.bytes, f->stream));
     }
     uint32_t *late = consider_left_edge ? nullptr : cb.late.as<uint32_t>();
     const int64_t *centre = cb.centre.as<int64_t>();
@@ -1963,21 +1898,21 @@ int clair_frontend_build_windows_ex(clair_frontend_t *f, int min_coverage, int d
     const int64_t m2 = f->g.n + 2;
     if (per_op && nc) {      // the running sum of the candidate prefix: what lets pass 2 go operation by operation
         const int64_t m = f->g.n + 1;
-        FE_TRY(f, cb.before_sum.ensure((size_t)m * sizeof(unsigned long long)));
-        FE_TRY(f, cb.prefix_block_sum.ensure(((size_t)blocks_for(m2, SCAN_BLOCK) + 1) * sizeof(unsigned long long)));
+        CLAIR_HIP_TRY(fe_fail(f), cb.before_sum.ensure((size_t)m * sizeof(unsigned long long)));
+        CLAIR_HIP_TRY(fe_fail(f), cb.prefix_block_sum.ensure(((size_t)blocks_for(m2, SCAN_BLOCK) + 1) * sizeof(unsigned long long)));
         running_sum<ScanU32>(f, f->before.as<uint32_t>(), m, cb.prefix_block_sum.as<unsigned long long>(), WriteRunning{cb.before_sum.as<unsigned long long>(), nullptr, 0, 0});
         if (!consider_left_edge) {
-            FE_TRY(f, f->d2.ensure((size_t)m2 * sizeof(unsigned long long)));
-            FE_TRY(f, f->fold.ensure(2 * sizeof(unsigned long long)));
-            FE_TRY(f, hipMemsetAsync(f->d2.p, 0, f->d2.bytes, f->stream));
-            FE_TRY(f, hipMemsetAsync(f->fold.p, 0, f->fold.bytes, f->stream));
+            CLAIR_HIP_TRY(fe_fail(f), f->d2.ensure((size_t)m2 * sizeof(unsigned long long)));
+            CLAIR_HIP_TRY(fe_fail(f), f->fold.ensure(2 * sizeof(unsigned long long)));
+            CLAIR_HIP_TRY(fe_fail(f), hipMemsetAsync(f->d2.p, 0, f->d2.bytes, f->stream));
+            CLAIR_HIP_TRY(fe_fail(f), hipMemsetAsync(f->fold.p, 0, f->fold.bytes, f->stream));
         }
     }
     unsigned long long *d2 = f->d2.as<unsigned long long>();
     Candidates c{centre, f->before.as<uint32_t>(), cb.ins.as<uint32_t>(), cb.before_sum.as<unsigned long long>(), late,
                  consider_left_edge ? nullptr : cb.tuple_diff.as<int>(), d2, f->fold.as<unsigned long long>()};
     for (Slab &s : f->slabs) {
-        FE_TRY(f, hipMemsetAsync(s.tuples.p, 0, (size_t)s.n_reads * sizeof(uint64_t), f->stream));
+        CLAIR_HIP_TRY(fe_fail(f), hipMemsetAsync(s.tuples.p, 0, (size_t)s.n_reads * sizeof(uint64_t), f->stream));
         if (!s.n_elem || !nc) continue;
         if (consider_left_edge) hipLaunchKernelGGL(fe_windows_per_op_kernel, dim3(blocks_for(s.n_ops, 256)), dim3(256), 0, f->stream, f->g, f->view(s), c);
         else if (per_op) {
@@ -1992,22 +1927,23 @@ int clair_frontend_build_windows_ex(clair_frontend_t *f, int min_coverage, int d
     }
     WindowRule rule{min_coverage, drop_non_iupac_centre, late};
     if (nc && late && !per_op)           // per-base pass 2: tuples per window = the (signed) running sum of its range additions, by one workgroup
-        hipLaunchKernelGGL((fe_scan_serial_kernel<ScanInt, true>), dim3(1), dim3(256), 0, f->stream, cb.tuple_diff.as<const int>(), nc, (long long *)window_tuples, (long long *)nullptr);
+        hipLaunchKernelGGL((clair_scan::walk_kernel<ScanInt, true>), dim3(1), dim3(256), 0, f->stream, ScanInt{cb.tuple_diff.as<const int>()}, nc, (long long *)window_tuples,
+                           (long long *)nullptr);
     if (nc) hipLaunchKernelGGL(fe_window_flags_kernel, dim3(blocks_for(nc, 256)), dim3(256), 0, f->stream, f->g, centre, nc, rule, cb.keep.as<uint8_t>(), window_tuples);
-    FE_TRY(f, hipGetLastError());
+    CLAIR_HIP_TRY(fe_fail(f), hipGetLastError());
     int64_t kept = 0;
     uint32_t *d_kept_total = f->total.as<uint32_t>() + 1;
     if (scan_count(f, cb.keep.as<uint8_t>(), nc, cb.block_sum.as<uint32_t>(), d_kept_total, &kept)) return 1;
     if (scan_write(f, cb.keep.as<uint8_t>(), nc, cb.block_sum.as<uint32_t>(), d_kept_total, nullptr, cb.kept.as<int64_t>(), 0)) return 1;
     // + one engine batch of slack is the caller's business: clair_submit_ex reads exactly n windows
-    FE_TRY(f, cb.counts.ensure((size_t)kept * WINDOW_VALUES * sizeof(int16_t)));
-    FE_TRY(f, cb.out_centre.ensure((size_t)kept * sizeof(int64_t)));
-    FE_TRY(f, cb.out_refseq.ensure((size_t)kept * 34));
+    CLAIR_HIP_TRY(fe_fail(f), cb.counts.ensure((size_t)kept * WINDOW_VALUES * sizeof(int16_t)));
+    CLAIR_HIP_TRY(fe_fail(f), cb.out_centre.ensure((size_t)kept * sizeof(int64_t)));
+    CLAIR_HIP_TRY(fe_fail(f), cb.out_refseq.ensure((size_t)kept * 34));
     if (kept)
         hipLaunchKernelGGL(fe_assemble_kernel, dim3(blocks_for(kept * N_QUAD, 256)), dim3(256), 0, f->stream, f->g, centre, cb.kept.as<const int64_t>(), kept,
                            cb.ins.as<const uint32_t>(), (const uint32_t *)late, cb.counts.as<short4>(), cb.out_centre.as<int64_t>(), cb.out_refseq.as<uint8_t>());
-    FE_TRY(f, hipGetLastError());
-    FE_TRY(f, hipStreamSynchronize(f->stream));
+    CLAIR_HIP_TRY(fe_fail(f), hipGetLastError());
+    CLAIR_HIP_TRY(fe_fail(f), hipStreamSynchronize(f->stream));
     f->n_windows = kept;
     cb.ts_n_kept = -1;           // a paired set is one of the windows it was made over
     *n_windows = kept;
@@ -2015,25 +1951,25 @@ int clair_frontend_build_windows_ex(clair_frontend_t *f, int min_coverage, int d
 }
 
 int clair_frontend_window_info(clair_frontend_t *f, int64_t first, int64_t n, int64_t *centres, char *refseq) {
-    if (!f) return fe_fail(nullptr, "front end is NULL");
-    if (f->n_windows < 0) return fe_fail(f, "no windows yet: call clair_frontend_build_windows first");
-    if (first < 0 || n < 0 || first + n > f->n_windows) return fe_fail(f, "windows [%lld, %lld) out of range [0, %lld)", (long long)first, (long long)(first + n), (long long)f->n_windows);
+    if (!f) return fe_fail(nullptr)("front end is NULL");
+    if (f->n_windows < 0) return fe_fail(f)("no windows yet: call clair_frontend_build_windows first");
+    if (first < 0 || n < 0 || first + n > f->n_windows) return fe_fail(f)("windows [%lld, %lld) out of range [0, %lld)", (long long)first, (long long)(first + n), (long long)f->n_windows);
     if (n == 0) return 0;
-    if (!centres || !refseq) return fe_fail(f, "NULL output pointer");
-    FE_TRY(f, hipSetDevice(f->device));
-    FE_TRY(f, hipMemcpy(centres, f->cand->out_centre.as<int64_t>() + first, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
-    FE_TRY(f, hipMemcpy(refseq, f->cand->out_refseq.as<uint8_t>() + first * 34, (size_t)n * 34, hipMemcpyDeviceToHost));
+    if (!centres || !refseq) return fe_fail(f)("NULL output pointer");
+    CLAIR_HIP_TRY(fe_fail(f), hipSetDevice(f->device));
+    CLAIR_HIP_TRY(fe_fail(f), hipMemcpy(centres, f->cand->out_centre.as<int64_t>() + first, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
+    CLAIR_HIP_TRY(fe_fail(f), hipMemcpy(refseq, f->cand->out_refseq.as<uint8_t>() + first * 34, (size_t)n * 34, hipMemcpyDeviceToHost));
     return 0;
 }
 
 int clair_frontend_window_counts(clair_frontend_t *f, int64_t first, int64_t n, int16_t *counts) {
-    if (!f) return fe_fail(nullptr, "front end is NULL");
-    if (f->n_windows < 0) return fe_fail(f, "no windows yet: call clair_frontend_build_windows first");
-    if (first < 0 || n < 0 || first + n > f->n_windows) return fe_fail(f, "windows [%lld, %lld) out of range [0, %lld)", (long long)first, (long long)(first + n), (long long)f->n_windows);
+    if (!f) return fe_fail(nullptr)("front end is NULL");
+    if (f->n_windows < 0) return fe_fail(f)("no windows yet: call clair_frontend_build_windows first");
+    if (first < 0 || n < 0 || first + n > f->n_windows) return fe_fail(f)("windows [%lld, %lld) out of range [0, %lld)", (long long)first, (long long)(first + n), (long long)f->n_windows);
     if (n == 0) return 0;
-    if (!counts) return fe_fail(f, "NULL output pointer");
-    FE_TRY(f, hipSetDevice(f->device));
-    FE_TRY(f, hipMemcpy(counts, f->cand->counts.as<const int16_t>() + first * WINDOW_VALUES, (size_t)n * WINDOW_VALUES * sizeof(int16_t), hipMemcpyDeviceToHost));
+    if (!counts) return fe_fail(f)("NULL output pointer");
+    CLAIR_HIP_TRY(fe_fail(f), hipSetDevice(f->device));
+    CLAIR_HIP_TRY(fe_fail(f), hipMemcpy(counts, f->cand->counts.as<const int16_t>() + first * WINDOW_VALUES, (size_t)n * WINDOW_VALUES * sizeof(int16_t), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -2043,26 +1979,26 @@ const int16_t *clair_frontend_counts_device(clair_frontend_t *f, int64_t first) 
 }
 
 int clair_frontend_budget_inputs(clair_frontend_t *f, int64_t slab, uint64_t *read_tuples, int64_t *centres, uint64_t *window_tuples) {
-    if (!f) return fe_fail(nullptr, "front end is NULL");
-    if (f->n_windows < 0) return fe_fail(f, "no windows yet: call clair_frontend_build_windows first");
-    FE_TRY(f, hipSetDevice(f->device));
+    if (!f) return fe_fail(nullptr)("front end is NULL");
+    if (f->n_windows < 0) return fe_fail(f)("no windows yet: call clair_frontend_build_windows first");
+    CLAIR_HIP_TRY(fe_fail(f), hipSetDevice(f->device));
     if (read_tuples) {
-        if (slab < 0 || slab >= (int64_t)f->slabs.size()) return fe_fail(f, "slab %lld out of range [0, %lld)", (long long)slab, (long long)f->slabs.size());
+        if (slab < 0 || slab >= (int64_t)f->slabs.size()) return fe_fail(f)("slab %lld out of range [0, %lld)", (long long)slab, (long long)f->slabs.size());
         const Slab &s = f->slabs[(size_t)slab];
-        FE_TRY(f, hipMemcpy(read_tuples, s.tuples.p, (size_t)s.n_reads * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        CLAIR_HIP_TRY(fe_fail(f), hipMemcpy(read_tuples, s.tuples.p, (size_t)s.n_reads * sizeof(uint64_t), hipMemcpyDeviceToHost));
     }
-    if (centres && f->n_candidates) FE_TRY(f, hipMemcpy(centres, f->cand->centre.p, (size_t)f->n_candidates * sizeof(int64_t), hipMemcpyDeviceToHost));
-    if (window_tuples && f->n_candidates) FE_TRY(f, hipMemcpy(window_tuples, f->cand->window_tuples.p, (size_t)f->n_candidates * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (centres && f->n_candidates) CLAIR_HIP_TRY(fe_fail(f), hipMemcpy(centres, f->cand->centre.p, (size_t)f->n_candidates * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (window_tuples && f->n_candidates) CLAIR_HIP_TRY(fe_fail(f), hipMemcpy(window_tuples, f->cand->window_tuples.p, (size_t)f->n_candidates * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return 0;
 }
 
 int clair_frontend_stats(clair_frontend_t *f, int64_t *stats) {
-    if (!f) return fe_fail(nullptr, "front end is NULL");
-    if (!stats) return fe_fail(f, "stats is NULL");
-    FE_TRY(f, hipSetDevice(f->device));
+    if (!f) return fe_fail(nullptr)("front end is NULL");
+    if (!stats) return fe_fail(f)("stats is NULL");
+    CLAIR_HIP_TRY(fe_fail(f), hipSetDevice(f->device));
     uint32_t bits = 0;
-    FE_TRY(f, hipStreamSynchronize(f->stream));
-    FE_TRY(f, hipMemcpy(&bits, f->g.anomalies, sizeof bits, hipMemcpyDeviceToHost));
+    CLAIR_HIP_TRY(fe_fail(f), hipStreamSynchronize(f->stream));
+    CLAIR_HIP_TRY(fe_fail(f), hipMemcpy(&bits, f->g.anomalies, sizeof bits, hipMemcpyDeviceToHost));
     int64_t reads = 0, elems = 0;
     for (const Slab &s : f->slabs) { reads += s.n_reads; elems += s.n_elem; }
     stats[0] = (int64_t)(bits | f->text_state.anomalies);

@@ -142,9 +142,9 @@ int lookup_on_host(clair_frontend *f, const int64_t *positions, int64_t n, const
         const Slab &d = f->slabs[f->lk_host.size()];
         SlabHostCopy c;
         c.reads.resize((size_t)d.n_reads); c.ops.resize((size_t)d.n_ops); c.seq.resize((size_t)d.seq_bytes);
-        if (d.n_reads) FE_TRY(f, hipMemcpy(c.reads.data(), d.reads.p, c.reads.size() * sizeof(clair_read_t), hipMemcpyDeviceToHost));
-        if (d.n_ops) FE_TRY(f, hipMemcpy(c.ops.data(), d.ops.p, c.ops.size() * sizeof(clair_op_t), hipMemcpyDeviceToHost));
-        if (d.seq_bytes) FE_TRY(f, hipMemcpy(c.seq.data(), d.seq.p, c.seq.size(), hipMemcpyDeviceToHost));
+        if (d.n_reads) CLAIR_HIP_TRY(fe_fail(f), hipMemcpy(c.reads.data(), d.reads.p, c.reads.size() * sizeof(clair_read_t), hipMemcpyDeviceToHost));
+        if (d.n_ops) CLAIR_HIP_TRY(fe_fail(f), hipMemcpy(c.ops.data(), d.ops.p, c.ops.size() * sizeof(clair_op_t), hipMemcpyDeviceToHost));
+        if (d.seq_bytes) CLAIR_HIP_TRY(fe_fail(f), hipMemcpy(c.seq.data(), d.seq.p, c.seq.size(), hipMemcpyDeviceToHost));
         copied += c.reads.size() * sizeof(clair_read_t) + c.ops.size() * sizeof(clair_op_t) + c.seq.size();
         f->lk_host.push_back(std::move(c));
     }
@@ -166,33 +166,33 @@ int lookup_on_host(clair_frontend *f, const int64_t *positions, int64_t n, const
 
 extern "C" int clair_frontend_indel_table(clair_frontend_t *f, const int64_t *positions, int64_t n, clair_indel_entry_t *entries, int capacity, int32_t *n_entries,
                                           int32_t *depth, uint32_t *status) {
-    if (!f) return fe_fail(nullptr, "front end is NULL");
-    if (n < 0 || capacity < 1 || capacity > 65536) return fe_fail(f, "indel table: %lld positions, capacity %d (1 .. 65536)", (long long)n, capacity);
+    if (!f) return fe_fail(nullptr)("front end is NULL");
+    if (n < 0 || capacity < 1 || capacity > 65536) return fe_fail(f)("indel table: %lld positions, capacity %d (1 .. 65536)", (long long)n, capacity);
     if (n == 0) return 0;
-    if (!positions || !entries || !n_entries || !depth || !status) return fe_fail(f, "indel table: NULL array");
+    if (!positions || !entries || !n_entries || !depth || !status) return fe_fail(f)("indel table: NULL array");
     for (int64_t q = 1; q < n; ++q)
-        if (positions[q] <= positions[q - 1]) return fe_fail(f, "indel table: positions must ascend strictly (entry %lld)", (long long)q);
-    FE_TRY(f, hipSetDevice(f->device));
+        if (positions[q] <= positions[q - 1]) return fe_fail(f)("indel table: positions must ascend strictly (entry %lld)", (long long)q);
+    CLAIR_HIP_TRY(fe_fail(f), hipSetDevice(f->device));
     const size_t n_slabs = f->slabs.size();
     std::vector<SlabView> views(n_slabs);
     for (size_t s = 0; s < n_slabs; ++s) views[s] = f->view(f->slabs[s]);
-    FE_TRY(f, lk_room(f->lk_views, std::max<size_t>(n_slabs, 1) * sizeof(SlabView)));
-    if (n_slabs) FE_TRY(f, hipMemcpyAsync(f->lk_views.p, views.data(), n_slabs * sizeof(SlabView), hipMemcpyHostToDevice, f->stream));
+    CLAIR_HIP_TRY(fe_fail(f), lk_room(f->lk_views, std::max<size_t>(n_slabs, 1) * sizeof(SlabView)));
+    if (n_slabs) CLAIR_HIP_TRY(fe_fail(f), hipMemcpyAsync(f->lk_views.p, views.data(), n_slabs * sizeof(SlabView), hipMemcpyHostToDevice, f->stream));
     const size_t room = (size_t)std::min<int64_t>(n, LK_QUERIES);
-    FE_TRY(f, lk_room(f->lk_pos, room * sizeof(int64_t)));
-    FE_TRY(f, lk_room(f->lk_count, room * sizeof(uint32_t)));
-    FE_TRY(f, lk_room(f->lk_hits, room * LK_HITS * sizeof(LookupHit)));
-    FE_TRY(f, lk_room(f->lk_entries, room * (size_t)capacity * sizeof(clair_indel_entry_t)));
-    FE_TRY(f, lk_room(f->lk_n, room * sizeof(int32_t)));
-    FE_TRY(f, lk_room(f->lk_depth, room * sizeof(int32_t)));
-    FE_TRY(f, lk_room(f->lk_status, room * sizeof(uint32_t)));
+    CLAIR_HIP_TRY(fe_fail(f), lk_room(f->lk_pos, room * sizeof(int64_t)));
+    CLAIR_HIP_TRY(fe_fail(f), lk_room(f->lk_count, room * sizeof(uint32_t)));
+    CLAIR_HIP_TRY(fe_fail(f), lk_room(f->lk_hits, room * LK_HITS * sizeof(LookupHit)));
+    CLAIR_HIP_TRY(fe_fail(f), lk_room(f->lk_entries, room * (size_t)capacity * sizeof(clair_indel_entry_t)));
+    CLAIR_HIP_TRY(fe_fail(f), lk_room(f->lk_n, room * sizeof(int32_t)));
+    CLAIR_HIP_TRY(fe_fail(f), lk_room(f->lk_depth, room * sizeof(int32_t)));
+    CLAIR_HIP_TRY(fe_fail(f), lk_room(f->lk_status, room * sizeof(uint32_t)));
     bool handed_over = false;
     for (int64_t q0 = 0; q0 < n; q0 += LK_QUERIES) {
         const int nq = (int)std::min<int64_t>(n - q0, LK_QUERIES);
-        FE_TRY(f, hipMemcpyAsync(f->lk_pos.p, positions + q0, (size_t)nq * sizeof(int64_t), hipMemcpyHostToDevice, f->stream));
-        FE_TRY(f, hipMemsetAsync(f->lk_count.p, 0, (size_t)nq * sizeof(uint32_t), f->stream));
-        FE_TRY(f, hipMemsetAsync(f->lk_depth.p, 0, (size_t)nq * sizeof(int32_t), f->stream));
-        FE_TRY(f, hipMemsetAsync(f->lk_entries.p, 0, (size_t)nq * (size_t)capacity * sizeof(clair_indel_entry_t), f->stream));
+        CLAIR_HIP_TRY(fe_fail(f), hipMemcpyAsync(f->lk_pos.p, positions + q0, (size_t)nq * sizeof(int64_t), hipMemcpyHostToDevice, f->stream));
+        CLAIR_HIP_TRY(fe_fail(f), hipMemsetAsync(f->lk_count.p, 0, (size_t)nq * sizeof(uint32_t), f->stream));
+        CLAIR_HIP_TRY(fe_fail(f), hipMemsetAsync(f->lk_depth.p, 0, (size_t)nq * sizeof(int32_t), f->stream));
+        CLAIR_HIP_TRY(fe_fail(f), hipMemsetAsync(f->lk_entries.p, 0, (size_t)nq * (size_t)capacity * sizeof(clair_indel_entry_t), f->stream));
         uint32_t rank0 = 0;
         for (size_t s = 0; s < n_slabs; ++s) {
             const Slab &d = f->slabs[s];
@@ -203,12 +203,12 @@ extern "C" int clair_frontend_indel_table(clair_frontend_t *f, const int64_t *po
         }
         hipLaunchKernelGGL(fe_lookup_group_kernel, dim3((unsigned)nq), dim3(64), 0, f->stream, f->lk_views.as<const SlabView>(), f->lk_count.as<const uint32_t>(),
                            f->lk_hits.as<const LookupHit>(), nq, capacity, f->lk_entries.as<clair_indel_entry_t>(), f->lk_n.as<int32_t>(), f->lk_status.as<uint32_t>());
-        FE_TRY(f, hipGetLastError());
-        FE_TRY(f, hipMemcpyAsync(entries + (size_t)q0 * (size_t)capacity, f->lk_entries.p, (size_t)nq * (size_t)capacity * sizeof(clair_indel_entry_t), hipMemcpyDeviceToHost, f->stream));
-        FE_TRY(f, hipMemcpyAsync(n_entries + q0, f->lk_n.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, f->stream));
-        FE_TRY(f, hipMemcpyAsync(depth + q0, f->lk_depth.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, f->stream));
-        FE_TRY(f, hipMemcpyAsync(status + q0, f->lk_status.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost, f->stream));
-        FE_TRY(f, hipStreamSynchronize(f->stream));
+        CLAIR_HIP_TRY(fe_fail(f), hipGetLastError());
+        CLAIR_HIP_TRY(fe_fail(f), hipMemcpyAsync(entries + (size_t)q0 * (size_t)capacity, f->lk_entries.p, (size_t)nq * (size_t)capacity * sizeof(clair_indel_entry_t), hipMemcpyDeviceToHost, f->stream));
+        CLAIR_HIP_TRY(fe_fail(f), hipMemcpyAsync(n_entries + q0, f->lk_n.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, f->stream));
+        CLAIR_HIP_TRY(fe_fail(f), hipMemcpyAsync(depth + q0, f->lk_depth.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, f->stream));
+        CLAIR_HIP_TRY(fe_fail(f), hipMemcpyAsync(status + q0, f->lk_status.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost, f->stream));
+        CLAIR_HIP_TRY(fe_fail(f), hipStreamSynchronize(f->stream));
         for (int i = 0; i < nq; ++i) handed_over = handed_over || (status[q0 + i] & CLAIR_LOOKUP_HITS);
     }
     if (handed_over) {

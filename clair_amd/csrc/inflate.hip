@@ -142,65 +142,23 @@ __global__ __launch_bounds__(64) void inflate_bgzf_kernel(const uint8_t *__restr
 
 }  // namespace clair_inf
 
-// -- the handle: one stream, page-locked staging for both directions and the device buffers, sized from max_blocks at creation and reused
-#include <cstdarg>
-#include <cstdio>
+// -- the handle: a StagedStream sized from max_blocks at creation
 #include <cstring>
-#include <string>
 
-namespace {
+#include "staged_stream.h"
 
-constexpr int64_t BLOCK_MAX = 65536;             // a BGZF block, compressed or inflated
-std::string g_inf_error;
-
-}  // namespace
-
-struct clair_inflate {
-    int device = 0;
-    int max_blocks = 0;
+struct clair_inflate : StagedStream {
     int64_t cap = 0;                             // bytes of each data buffer: max_blocks * BLOCK_MAX
-    hipStream_t stream = nullptr;
-    PinnedBuffer h_in, h_out, h_meta;
-    DeviceBuffer d_in, d_out, d_meta;
-    std::string error;
 };
 
 namespace {
 
-int inf_fail(clair_inflate *h, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (h) h->error = buf; else g_inf_error = buf;
-    return 1;
-}
-
-#define INF_TRY(h, call)                                                                                   \
-    do {                                                                                                   \
-        hipError_t err__ = (call);                                                                         \
-        if (err__ != hipSuccess)                                                                           \
-            return inf_fail((h), "%s failed: %s (%s:%d)", #call, hipGetErrorString(err__), __FILE__, __LINE__); \
-    } while (0)
-
+constexpr int64_t BLOCK_MAX = 65536;             // a BGZF block, compressed or inflated
 // per block: in_at, out_at (int64), csize, out_len, status (int32)
 constexpr int64_t META_PER_BLOCK = 2 * 8 + 3 * 4;
 
-int inflate_init(clair_inflate *h) {
-    INF_TRY(nullptr, hipSetDevice(h->device));
-    INF_TRY(nullptr, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    const size_t meta = (size_t)h->max_blocks * META_PER_BLOCK;
-    INF_TRY(nullptr, h->h_in.ensure((size_t)h->cap));
-    INF_TRY(nullptr, h->h_out.ensure((size_t)h->cap));
-    INF_TRY(nullptr, h->h_meta.ensure(meta));
-    INF_TRY(nullptr, h->d_in.ensure((size_t)h->cap + 32));      // the kernel reads whole 16-byte pieces around each stream
-    INF_TRY(nullptr, h->d_out.ensure((size_t)h->cap));
-    INF_TRY(nullptr, h->d_meta.ensure(meta));
-    // on the handle's own (non-blocking) stream: a fill on the null stream is not ordered before this stream's first copy into the buffer
-    INF_TRY(nullptr, hipMemsetAsync(h->d_in.p, 0, (size_t)h->cap + 32, h->stream));
-    return 0;
-}
+std::string g_inf_error;
+inline HipFail inf_fail(clair_inflate *h) { return {h ? h->error : g_inf_error}; }
 
 }  // namespace
 
@@ -209,18 +167,15 @@ extern "C" {
 const char *clair_inflate_last_error(const clair_inflate_t *h) { return h ? h->error.c_str() : g_inf_error.c_str(); }
 
 int clair_inflate_create(int device, int max_blocks, clair_inflate_t **out) {
-    if (!out) return inf_fail(nullptr, "out is NULL");
+    if (!out) return inf_fail(nullptr)("out is NULL");
     *out = nullptr;
-    if (max_blocks < 1 || max_blocks > 16384) return inf_fail(nullptr, "max_blocks %d: 1 .. 16384", max_blocks);
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1)
-        return inf_fail(nullptr, "no HIP device is visible: the device inflate runs on an MI355X only (the host inflate is --bam_inflate host)");
-    if (device < 0 || device >= n_dev) return inf_fail(nullptr, "device %d out of range [0,%d)", device, n_dev);
+    if (max_blocks < 1 || max_blocks > 16384) return inf_fail(nullptr)("max_blocks %d: 1 .. 16384", max_blocks);
+    if (hip_device_check(inf_fail(nullptr), device, "the device inflate runs on an MI355X only (the host inflate is --bam_inflate host)")) return 1;
     clair_inflate *h = new clair_inflate;
-    h->device = device;
-    h->max_blocks = max_blocks;
     h->cap = (int64_t)max_blocks * BLOCK_MAX;
-    if (inflate_init(h)) {
+    const size_t meta = (size_t)max_blocks * META_PER_BLOCK;
+    // (d_in + 32: the kernel reads whole 16-byte pieces around each stream)
+    if (h->open(inf_fail(nullptr), device, max_blocks, (size_t)h->cap, (size_t)h->cap, meta, (size_t)h->cap + 32)) {
         clair_inflate_destroy(h);
         return 1;
     }
@@ -230,31 +185,27 @@ int clair_inflate_create(int device, int max_blocks, clair_inflate_t **out) {
 
 void clair_inflate_destroy(clair_inflate_t *h) {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (DeviceBuffer *b : {&h->d_in, &h->d_out, &h->d_meta}) b->reset();     // before the stream goes, not in ~clair_inflate
-    for (PinnedBuffer *b : {&h->h_in, &h->h_out, &h->h_meta}) b->reset();
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    h->close();
     delete h;
 }
 
 int clair_inflate_blocks(clair_inflate_t *h, const uint8_t *cdata, int64_t cbytes, int n, const int64_t *in_at, const int32_t *csize,
                          const int64_t *out_at, const int32_t *out_len, uint8_t *out, int32_t *status) {
-    if (!h) return inf_fail(nullptr, "inflate handle is NULL");
-    if (n < 0 || n > h->max_blocks) return inf_fail(h, "%d blocks in a batch: 0 .. max_blocks = %d", n, h->max_blocks);
+    if (!h) return inf_fail(nullptr)("inflate handle is NULL");
+    if (n < 0 || n > h->max_blocks) return inf_fail(h)("%d blocks in a batch: 0 .. max_blocks = %d", n, h->max_blocks);
     if (n == 0) return 0;
-    if (!cdata || !in_at || !csize || !out_at || !out_len || !out || !status) return inf_fail(h, "NULL argument");
-    if (cbytes < 0 || cbytes > h->cap) return inf_fail(h, "%lld compressed bytes: 0 .. %lld", (long long)cbytes, (long long)h->cap);
+    if (!cdata || !in_at || !csize || !out_at || !out_len || !out || !status) return inf_fail(h)("NULL argument");
+    if (cbytes < 0 || cbytes > h->cap) return inf_fail(h)("%lld compressed bytes: 0 .. %lld", (long long)cbytes, (long long)h->cap);
     int64_t out_lo = INT64_MAX, out_hi = 0;
     for (int i = 0; i < n; ++i) {
-        if (csize[i] < 26 || csize[i] > BLOCK_MAX) return inf_fail(h, "block %d: csize %d (26 .. 65536)", i, csize[i]);
-        if (in_at[i] < 0 || in_at[i] > cbytes - csize[i]) return inf_fail(h, "block %d: compressed bytes [%lld, +%d) outside the %lld given", i, (long long)in_at[i], csize[i], (long long)cbytes);
-        if (out_len[i] < 0 || out_len[i] > BLOCK_MAX) return inf_fail(h, "block %d: out_len %d (0 .. 65536)", i, out_len[i]);
-        if (out_at[i] < 0 || out_at[i] > h->cap - out_len[i]) return inf_fail(h, "block %d: output [%lld, +%d) outside the handle's %lld bytes", i, (long long)out_at[i], out_len[i], (long long)h->cap);
+        if (csize[i] < 26 || csize[i] > BLOCK_MAX) return inf_fail(h)("block %d: csize %d (26 .. 65536)", i, csize[i]);
+        if (in_at[i] < 0 || in_at[i] > cbytes - csize[i]) return inf_fail(h)("block %d: compressed bytes [%lld, +%d) outside the %lld given", i, (long long)in_at[i], csize[i], (long long)cbytes);
+        if (out_len[i] < 0 || out_len[i] > BLOCK_MAX) return inf_fail(h)("block %d: out_len %d (0 .. 65536)", i, out_len[i]);
+        if (out_at[i] < 0 || out_at[i] > h->cap - out_len[i]) return inf_fail(h)("block %d: output [%lld, +%d) outside the handle's %lld bytes", i, (long long)out_at[i], out_len[i], (long long)h->cap);
         out_lo = std::min(out_lo, out_at[i]);
         out_hi = std::max(out_hi, out_at[i] + out_len[i]);
     }
-    INF_TRY(h, hipSetDevice(h->device));
+    CLAIR_HIP_TRY(inf_fail(h), hipSetDevice(h->device));
     const size_t N = (size_t)h->max_blocks;
     int64_t *m_in_at = h->h_meta.as<int64_t>(), *m_out_at = m_in_at + N;
     int32_t *m_csize = (int32_t *)(m_out_at + N), *m_out_len = m_csize + N, *m_status = m_out_len + N;
@@ -267,14 +218,14 @@ int clair_inflate_blocks(clair_inflate_t *h, const uint8_t *cdata, int64_t cbyte
     const int64_t *d_in_at = h->d_meta.as<int64_t>(), *d_out_at = d_in_at + N;
     const int32_t *d_csize = (const int32_t *)(d_out_at + N), *d_out_len = d_csize + N;
     int32_t *d_status = (int32_t *)(d_out_len + N);
-    INF_TRY(h, hipMemcpyAsync(d_in, h_in, (size_t)cbytes, hipMemcpyHostToDevice, h->stream));
-    INF_TRY(h, hipMemcpyAsync(h->d_meta.p, h->h_meta.p, N * (2 * 8 + 2 * 4), hipMemcpyHostToDevice, h->stream));
+    CLAIR_HIP_TRY(inf_fail(h), hipMemcpyAsync(d_in, h_in, (size_t)cbytes, hipMemcpyHostToDevice, h->stream));
+    CLAIR_HIP_TRY(inf_fail(h), hipMemcpyAsync(h->d_meta.p, h->h_meta.p, N * (2 * 8 + 2 * 4), hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(clair_inf::inflate_bgzf_kernel, dim3((unsigned)n), dim3(64), 0, h->stream, (const uint8_t *)d_in, n, d_in_at, d_csize, d_out_at,
                        d_out_len, d_out, d_status);
-    INF_TRY(h, hipGetLastError());
-    if (out_hi > out_lo) INF_TRY(h, hipMemcpyAsync(h_out + out_lo, d_out + out_lo, (size_t)(out_hi - out_lo), hipMemcpyDeviceToHost, h->stream));
-    INF_TRY(h, hipMemcpyAsync(m_status, d_status, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-    INF_TRY(h, hipStreamSynchronize(h->stream));
+    CLAIR_HIP_TRY(inf_fail(h), hipGetLastError());
+    if (out_hi > out_lo) CLAIR_HIP_TRY(inf_fail(h), hipMemcpyAsync(h_out + out_lo, d_out + out_lo, (size_t)(out_hi - out_lo), hipMemcpyDeviceToHost, h->stream));
+    CLAIR_HIP_TRY(inf_fail(h), hipMemcpyAsync(m_status, d_status, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+    CLAIR_HIP_TRY(inf_fail(h), hipStreamSynchronize(h->stream));
     for (int i = 0; i < n; ++i) {
         status[i] = m_status[i];
         if (m_status[i] == 0 && out_len[i]) memcpy(out + out_at[i], h_out + out_at[i], (size_t)out_len[i]);

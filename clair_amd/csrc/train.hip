@@ -12,13 +12,11 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
-#include <string>
 
 #include "../../include/clair_amd.h"
 #include "device_buffer.h"
+#include "hip_status.h"
 #include "train_accuracy.hip.h"
 #include "train_gemm.hip.h"
 #include "train_kernels.hip.h"
@@ -56,40 +54,25 @@ struct clair_trainer {
 
 namespace {
 
-int train_fail(clair_trainer *t, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (t) t->error = buf; else g_train_error = buf;
-    return 1;
-}
-
-#define TRAIN_TRY(t, call)                                                                                   \
-    do {                                                                                                     \
-        hipError_t err__ = (call);                                                                           \
-        if (err__ != hipSuccess)                                                                             \
-            return train_fail((t), "%s failed: %s (%s:%d)", #call, hipGetErrorString(err__), __FILE__, __LINE__); \
-    } while (0)
+inline HipFail train_fail(clair_trainer *t) { return {t ? t->error : g_train_error}; }
 
 inline dim3 blocks_for(int64_t count) { return dim3((unsigned)((count + 255) / 256)); }
 #define LAUNCH(t, kernel, count, ...)                                                        \
     do {                                                                                     \
         if ((count) > 0) {                                                                   \
             hipLaunchKernelGGL(kernel, blocks_for(count), dim3(256), 0, (t)->stream, __VA_ARGS__); \
-            TRAIN_TRY(t, hipGetLastError());                                                 \
+            CLAIR_HIP_TRY(train_fail(t), hipGetLastError());                                 \
         }                                                                                    \
     } while (0)
 
 int train_init(clair_trainer *t) {
-    TRAIN_TRY(nullptr, hipSetDevice(t->device));
-    TRAIN_TRY(nullptr, hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
+    CLAIR_HIP_TRY(train_fail(nullptr), hipSetDevice(t->device));
+    CLAIR_HIP_TRY(train_fail(nullptr), hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
     for (int i = 0; i < N_TENSORS; ++i) t->offset[i + 1] = t->offset[i] + TENSOR_COUNT[i];
     t->n_params = t->offset[N_TENSORS];
     for (DeviceBuffer &b : t->sets) {
-        TRAIN_TRY(nullptr, b.ensure((size_t)t->n_params * 4));
-        TRAIN_TRY(nullptr, hipMemset(b.p, 0, (size_t)t->n_params * 4));
+        CLAIR_HIP_TRY(train_fail(nullptr), b.ensure((size_t)t->n_params * 4));
+        CLAIR_HIP_TRY(train_fail(nullptr), hipMemset(b.p, 0, (size_t)t->n_params * 4));
     }
     const size_t cap = (size_t)t->cap, F = sizeof(float);
     struct { DeviceBuffer *b; size_t per_row; } plan[] = {
@@ -102,11 +85,11 @@ int train_init(clair_trainer *t) {
         {&t->lg, 90 * F}, {&t->probs, 90 * F}, {&t->dz, 90 * F},
         {&t->m_lstm2, T_STEPS * 256}, {&t->m4, 192}, {&t->m5, 384}, {&t->labels, 4}, {&t->row_loss, 4 * sizeof(double)},
     };
-    for (auto &e : plan) TRAIN_TRY(nullptr, e.b->ensure(cap * e.per_row));
-    TRAIN_TRY(nullptr, t->sums.ensure(4 * sizeof(double)));
-    TRAIN_TRY(nullptr, t->partial.ensure(2 * RED_BLOCKS * sizeof(double)));
-    TRAIN_TRY(nullptr, t->stats.ensure(3 * sizeof(double)));
-    TRAIN_TRY(nullptr, t->tp.ensure(4 * sizeof(int64_t)));
+    for (auto &e : plan) CLAIR_HIP_TRY(train_fail(nullptr), e.b->ensure(cap * e.per_row));
+    CLAIR_HIP_TRY(train_fail(nullptr), t->sums.ensure(4 * sizeof(double)));
+    CLAIR_HIP_TRY(train_fail(nullptr), t->partial.ensure(2 * RED_BLOCKS * sizeof(double)));
+    CLAIR_HIP_TRY(train_fail(nullptr), t->stats.ensure(3 * sizeof(double)));
+    CLAIR_HIP_TRY(train_fail(nullptr), t->tp.ensure(4 * sizeof(int64_t)));
     for (double &w : t->class_weights) w = 1.0;
     return 0;
 }
@@ -123,7 +106,7 @@ GemmArgs gemm(const float *A, int64_t sam, int64_t sak, const float *B, int64_t 
 
 int column_sum(clair_trainer *t, const float *x, int64_t rows, int cols, int64_t ld, float *out, int d = 1, int s1 = 1, int s2 = 0) {
     hipLaunchKernelGGL(column_sum_kernel, dim3((cols + 31) / 32), dim3(256), 0, t->stream, x, rows, cols, ld, out, d, s1, s2);
-    TRAIN_TRY(t, hipGetLastError());
+    CLAIR_HIP_TRY(train_fail(t), hipGetLastError());
     return 0;
 }
 
@@ -144,12 +127,12 @@ int lstm_forward(clair_trainer *t, int layer, const float *X, int n) {
     for (int dir = 0; dir < 2; ++dir) {
         const float *K = P + t->offset[L.kernel_id[dir]], *bias = P + t->offset[L.kernel_id[dir] + 1];
         float *z = L.z + (int64_t)dir * T_STEPS * n * 512, *c = L.c + (int64_t)dir * T_STEPS * n * HID, *a = L.a + dir * HID;
-        TRAIN_TRY(t, tgemm(t->stream, gemm(X, L.in, 1, K, 512, 1, z, 512, T_STEPS * n, 512, L.in, bias)));
+        CLAIR_HIP_TRY(train_fail(t), tgemm(t->stream, gemm(X, L.in, 1, K, 512, 1, z, 512, T_STEPS * n, 512, L.in, bias)));
         for (int s = 0; s < T_STEPS; ++s) {
             const int tt = dir == 0 ? s : T_STEPS - 1 - s, prev = dir == 0 ? tt - 1 : tt + 1;
             float *zt = z + (int64_t)tt * n * 512;
             if (s > 0)
-                TRAIN_TRY(t, tgemm(t->stream, gemm(a + (int64_t)prev * n * 256, 256, 1, K + (int64_t)L.in * 512, 512, 1, zt, 512, n, 512, HID, nullptr, 1)));
+                CLAIR_HIP_TRY(train_fail(t), tgemm(t->stream, gemm(a + (int64_t)prev * n * 256, 256, 1, K + (int64_t)L.in * 512, 512, 1, zt, 512, n, 512, HID, nullptr, 1)));
             LAUNCH(t, lstm_step_forward_kernel, (int64_t)n * HID, zt, s > 0 ? c + (int64_t)prev * n * HID : nullptr, c + (int64_t)tt * n * HID,
                    a + (int64_t)tt * n * 256, 256, n);
         }
@@ -174,16 +157,16 @@ int lstm_backward(clair_trainer *t, int layer, const float *X, const float *dA, 
             float *zt = z + (int64_t)tt * n * 512;
             LAUNCH(t, lstm_step_backward_kernel, (int64_t)n * HID, zt, c + (int64_t)tt * n * HID, has_prev ? c + (int64_t)prev * n * HID : nullptr,
                    dA + (int64_t)tt * n * 256 + dir * HID, 256, s > 0 ? dhrec : nullptr, dc, s == 0 ? 1 : 0, n);
-            if (has_prev) TRAIN_TRY(t, tgemm(t->stream, gemm(zt, 512, 1, Kh, 1, 512, dhrec, HID, n, HID, 512)));      // dz_t . K_h^T
+            if (has_prev) CLAIR_HIP_TRY(train_fail(t), tgemm(t->stream, gemm(zt, 512, 1, Kh, 1, 512, dhrec, HID, n, HID, 512)));      // dz_t . K_h^T
         }
         float *dK = G + t->offset[L.kernel_id[dir]];
         // dK = [x_t ; h_prev]^T . dz over all (t, n) rows: the x rows, then the h rows (the first step of the direction has no h_prev)
-        TRAIN_TRY(t, tgemm(t->stream, gemm(X, 1, L.in, z, 512, 1, dK, 512, L.in, 512, T_STEPS * n, nullptr, 1)));
+        CLAIR_HIP_TRY(train_fail(t), tgemm(t->stream, gemm(X, 1, L.in, z, 512, 1, dK, 512, L.in, 512, T_STEPS * n, nullptr, 1)));
         const float *h_prev = dir == 0 ? a : a + (int64_t)n * 256;
         const float *dz_next = dir == 0 ? z + (int64_t)n * 512 : z;
-        TRAIN_TRY(t, tgemm(t->stream, gemm(h_prev, 1, 256, dz_next, 512, 1, dK + (int64_t)L.in * 512, 512, HID, 512, (T_STEPS - 1) * n, nullptr, 1)));
+        CLAIR_HIP_TRY(train_fail(t), tgemm(t->stream, gemm(h_prev, 1, 256, dz_next, 512, 1, dK + (int64_t)L.in * 512, 512, HID, 512, (T_STEPS - 1) * n, nullptr, 1)));
         if (column_sum(t, z, (int64_t)T_STEPS * n, 512, 512, G + t->offset[L.kernel_id[dir] + 1])) return 1;
-        if (dX) TRAIN_TRY(t, tgemm(t->stream, gemm(z, 512, 1, K, 1, 512, dX, L.in, T_STEPS * n, L.in, 512, nullptr, dir)));
+        if (dX) CLAIR_HIP_TRY(train_fail(t), tgemm(t->stream, gemm(z, 512, 1, K, 1, 512, dX, L.in, T_STEPS * n, L.in, 512, nullptr, dir)));
     }
     return 0;
 }
@@ -211,22 +194,22 @@ int run_accumulate(clair_trainer *t, int n, int64_t first_row, int training, dou
         LAUNCH(t, dropout_forward_kernel, a_count, t->a2.as<float>(), a2d, t->m_lstm2.as<uint8_t>(), n, 256, first_row, mask_key(t->seed, t->step, 0),
                (uint32_t)std::llround((1.0 - t->rates[0]) * 16777216.0), inv_keep2);
     else if (training)
-        TRAIN_TRY(t, hipMemsetAsync(t->m_lstm2.p, 1, (size_t)a_count, t->stream));
+        CLAIR_HIP_TRY(train_fail(t), hipMemsetAsync(t->m_lstm2.p, 1, (size_t)a_count, t->stream));
     // L3 "ntc,ctu->nuc": a batch over the 256 channels; output column u * 256 + c
     {
         GemmArgs g = gemm(a2d, 256, (int64_t)n * 256, P + off[CLAIR_T_L3_KERNEL], 30, 1, t->l3.as<float>(), 7680, n, 30, T_STEPS, P + off[CLAIR_T_L3_BIAS]);
         g.scn = 256; g.ba = 1; g.bb = T_STEPS * 30; g.bc = 1; g.bbias = 30;
-        TRAIN_TRY(t, tgemm(t->stream, g, 256));
+        CLAIR_HIP_TRY(train_fail(t), tgemm(t->stream, g, 256));
     }
     LAUNCH(t, selu_kernel, (int64_t)n * 7680, t->l3.as<float>(), (int64_t)n * 7680);
-    TRAIN_TRY(t, tgemm(t->stream, gemm(t->l3.as<float>(), 7680, 1, P + off[CLAIR_T_L4_KERNEL], 192, 1, t->y4.as<float>(), 192, n, 192, 7680, P + off[CLAIR_T_L4_BIAS])));
+    CLAIR_HIP_TRY(train_fail(t), tgemm(t->stream, gemm(t->l3.as<float>(), 7680, 1, P + off[CLAIR_T_L4_KERNEL], 192, 1, t->y4.as<float>(), 192, n, 192, 7680, P + off[CLAIR_T_L4_BIAS])));
     const DropoutSelu k4 = dropout_selu_constants(t->rates[1]);
     LAUNCH(t, selu_dropout_forward_kernel, (int64_t)n * 192, t->y4.as<float>(), t->d4.as<float>(), t->m4.as<uint8_t>(), n, 192, first_row,
            mask_key(t->seed, t->step, 1), k4.threshold, k4.a, k4.b, training);
     {
         GemmArgs g = gemm(t->d4.as<float>(), 192, 1, P + off[CLAIR_T_L5_KERNEL], 96, 1, t->y5.as<float>(), 96, n, 96, 192, P + off[CLAIR_T_L5_BIAS]);
         g.bb = 192 * 96; g.bc = (int64_t)n * 96; g.bbias = 96;
-        TRAIN_TRY(t, tgemm(t->stream, g, 4));
+        CLAIR_HIP_TRY(train_fail(t), tgemm(t->stream, g, 4));
     }
     DropoutSelu k5[4];
     for (int k = 0; k < 4; ++k) {
@@ -234,7 +217,7 @@ int run_accumulate(clair_trainer *t, int n, int64_t first_row, int training, dou
         const int64_t at = (int64_t)k * n * 96;
         LAUNCH(t, selu_dropout_forward_kernel, (int64_t)n * 96, t->y5.as<float>() + at, t->d5.as<float>() + at, t->m5.as<uint8_t>() + at, n, 96, first_row,
                mask_key(t->seed, t->step, 2 + k), k5[k].threshold, k5[k].a, k5[k].b, training);
-        TRAIN_TRY(t, tgemm(t->stream, gemm(t->d5.as<float>() + at, 96, 1, P + off[CLAIR_T_HEAD_GT21_KERNEL + 2 * k], HEAD_SIZE[k], 1, t->lg.as<float>() + HEAD_OFF[k], 90,
+        CLAIR_HIP_TRY(train_fail(t), tgemm(t->stream, gemm(t->d5.as<float>() + at, 96, 1, P + off[CLAIR_T_HEAD_GT21_KERNEL + 2 * k], HEAD_SIZE[k], 1, t->lg.as<float>() + HEAD_OFF[k], 90,
                                             n, HEAD_SIZE[k], 96, P + off[CLAIR_T_HEAD_GT21_BIAS + 2 * k])));
     }
     LAUNCH(t, selu_kernel, (int64_t)n * 90, t->lg.as<float>(), (int64_t)n * 90);
@@ -247,11 +230,11 @@ int run_accumulate(clair_trainer *t, int n, int64_t first_row, int training, dou
         a.n = n; a.focal = t->loss == 0; a.training = training;
         LAUNCH(t, loss_kernel, (int64_t)n * 4, a);
         hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, t->stream, t->row_loss.as<double>(), n, t->sums.as<double>());
-        TRAIN_TRY(t, hipGetLastError());
+        CLAIR_HIP_TRY(train_fail(t), hipGetLastError());
     }
-    TRAIN_TRY(t, hipMemcpyAsync(losses, t->sums.p, 4 * sizeof(double), hipMemcpyDeviceToHost, t->stream));
+    CLAIR_HIP_TRY(train_fail(t), hipMemcpyAsync(losses, t->sums.p, 4 * sizeof(double), hipMemcpyDeviceToHost, t->stream));
     if (!training) {
-        TRAIN_TRY(t, hipStreamSynchronize(t->stream));
+        CLAIR_HIP_TRY(train_fail(t), hipStreamSynchronize(t->stream));
         return 0;
     }
     // ---- backward ----
@@ -259,34 +242,34 @@ int run_accumulate(clair_trainer *t, int n, int64_t first_row, int training, dou
     for (int k = 0; k < 4; ++k) {
         const int64_t at = (int64_t)k * n * 96;
         const int hk = CLAIR_T_HEAD_GT21_KERNEL + 2 * k;
-        TRAIN_TRY(t, tgemm(t->stream, gemm(t->d5.as<float>() + at, 1, 96, dz + HEAD_OFF[k], 90, 1, G + off[hk], HEAD_SIZE[k], 96, HEAD_SIZE[k], n, nullptr, 1)));
+        CLAIR_HIP_TRY(train_fail(t), tgemm(t->stream, gemm(t->d5.as<float>() + at, 1, 96, dz + HEAD_OFF[k], 90, 1, G + off[hk], HEAD_SIZE[k], 96, HEAD_SIZE[k], n, nullptr, 1)));
         if (column_sum(t, dz + HEAD_OFF[k], n, HEAD_SIZE[k], 90, G + off[hk + 1])) return 1;
-        TRAIN_TRY(t, tgemm(t->stream, gemm(dz + HEAD_OFF[k], 90, 1, P + off[hk], 1, HEAD_SIZE[k], t->dd5.as<float>() + at, 96, n, 96, HEAD_SIZE[k])));
+        CLAIR_HIP_TRY(train_fail(t), tgemm(t->stream, gemm(dz + HEAD_OFF[k], 90, 1, P + off[hk], 1, HEAD_SIZE[k], t->dd5.as<float>() + at, 96, n, 96, HEAD_SIZE[k])));
         LAUNCH(t, selu_dropout_backward_kernel, (int64_t)n * 96, t->dd5.as<float>() + at, t->y5.as<float>() + at, t->m5.as<uint8_t>() + at, (int64_t)n * 96, k5[k].a);
-        TRAIN_TRY(t, tgemm(t->stream, gemm(t->d4.as<float>(), 1, 192, t->dd5.as<float>() + at, 96, 1, G + off[CLAIR_T_L5_KERNEL] + (int64_t)k * 192 * 96, 96, 192, 96, n,
+        CLAIR_HIP_TRY(train_fail(t), tgemm(t->stream, gemm(t->d4.as<float>(), 1, 192, t->dd5.as<float>() + at, 96, 1, G + off[CLAIR_T_L5_KERNEL] + (int64_t)k * 192 * 96, 96, 192, 96, n,
                                             nullptr, 1)));
         if (column_sum(t, t->dd5.as<float>() + at, n, 96, 96, G + off[CLAIR_T_L5_BIAS] + k * 96)) return 1;
-        TRAIN_TRY(t, tgemm(t->stream, gemm(t->dd5.as<float>() + at, 96, 1, P + off[CLAIR_T_L5_KERNEL] + (int64_t)k * 192 * 96, 1, 96, t->dd4.as<float>(), 192, n, 192, 96,
+        CLAIR_HIP_TRY(train_fail(t), tgemm(t->stream, gemm(t->dd5.as<float>() + at, 96, 1, P + off[CLAIR_T_L5_KERNEL] + (int64_t)k * 192 * 96, 1, 96, t->dd4.as<float>(), 192, n, 192, 96,
                                             nullptr, k > 0)));
     }
     LAUNCH(t, selu_dropout_backward_kernel, (int64_t)n * 192, t->dd4.as<float>(), t->y4.as<float>(), t->m4.as<uint8_t>(), (int64_t)n * 192, k4.a);
-    TRAIN_TRY(t, tgemm(t->stream, gemm(t->l3.as<float>(), 1, 7680, t->dd4.as<float>(), 192, 1, G + off[CLAIR_T_L4_KERNEL], 192, 7680, 192, n, nullptr, 1)));
+    CLAIR_HIP_TRY(train_fail(t), tgemm(t->stream, gemm(t->l3.as<float>(), 1, 7680, t->dd4.as<float>(), 192, 1, G + off[CLAIR_T_L4_KERNEL], 192, 7680, 192, n, nullptr, 1)));
     if (column_sum(t, t->dd4.as<float>(), n, 192, 192, G + off[CLAIR_T_L4_BIAS])) return 1;
-    TRAIN_TRY(t, tgemm(t->stream, gemm(t->dd4.as<float>(), 192, 1, P + off[CLAIR_T_L4_KERNEL], 1, 192, t->dl3.as<float>(), 7680, n, 7680, 192)));
+    CLAIR_HIP_TRY(train_fail(t), tgemm(t->stream, gemm(t->dd4.as<float>(), 192, 1, P + off[CLAIR_T_L4_KERNEL], 1, 192, t->dl3.as<float>(), 7680, n, 7680, 192)));
     LAUNCH(t, selu_backward_kernel, (int64_t)n * 7680, t->dl3.as<float>(), t->l3.as<float>(), (int64_t)n * 7680);
     {   // L3: dW[c][t][u] += sum_n a2d[t][n][c] dz3[n][u*256+c];  da2d[t][n][c] = sum_u dz3[n][u*256+c] W[c][t][u];  db[c][u] += sum_n dz3
         GemmArgs g = gemm(a2d, (int64_t)n * 256, 256, t->dl3.as<float>(), 7680, 256, G + off[CLAIR_T_L3_KERNEL], 30, T_STEPS, 30, n, nullptr, 1);
         g.ba = 1; g.bb = 1; g.bc = T_STEPS * 30;
-        TRAIN_TRY(t, tgemm(t->stream, g, 256));
+        CLAIR_HIP_TRY(train_fail(t), tgemm(t->stream, g, 256));
         GemmArgs h = gemm(t->dl3.as<float>(), 7680, 256, P + off[CLAIR_T_L3_KERNEL], 1, 30, t->da2.as<float>(), 256, n, T_STEPS, 30);
         h.scn = (int64_t)n * 256; h.ba = 1; h.bb = T_STEPS * 30; h.bc = 1;
-        TRAIN_TRY(t, tgemm(t->stream, h, 256));
+        CLAIR_HIP_TRY(train_fail(t), tgemm(t->stream, h, 256));
         if (column_sum(t, t->dl3.as<float>(), n, 7680, 7680, G + off[CLAIR_T_L3_BIAS], 256, 1, 30)) return 1;
     }
     if (drop2) LAUNCH(t, dropout_backward_kernel, a_count, t->da2.as<float>(), t->m_lstm2.as<uint8_t>(), a_count, inv_keep2);
     if (lstm_backward(t, 2, t->a1.as<float>(), t->da2.as<float>(), t->da1.as<float>(), n)) return 1;
     if (lstm_backward(t, 1, t->xt.as<float>(), t->da1.as<float>(), nullptr, n)) return 1;
-    TRAIN_TRY(t, hipStreamSynchronize(t->stream));
+    CLAIR_HIP_TRY(train_fail(t), hipStreamSynchronize(t->stream));
     return 0;
 }
 
@@ -297,14 +280,12 @@ extern "C" {
 const char *clair_train_last_error(const clair_trainer_t *t) { return t ? t->error.c_str() : g_train_error.c_str(); }
 
 int clair_train_create(int device, int micro_batch, int optimizer, int loss, clair_trainer_t **out) {
-    if (!out) return train_fail(nullptr, "out is NULL");
+    if (!out) return train_fail(nullptr)("out is NULL");
     *out = nullptr;
-    if (micro_batch < 1 || micro_batch > MAX_MICRO_BATCH) return train_fail(nullptr, "micro_batch %d: 1 .. %d", micro_batch, MAX_MICRO_BATCH);
-    if (optimizer < 0 || optimizer > 1) return train_fail(nullptr, "optimizer %d: 0 (Adam) or 1 (SGDM)", optimizer);
-    if (loss < 0 || loss > 1) return train_fail(nullptr, "loss %d: 0 (focal loss) or 1 (cross entropy)", loss);
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) return train_fail(nullptr, "no HIP device is visible: training runs on an MI355X only");
-    if (device < 0 || device >= n_dev) return train_fail(nullptr, "device %d out of range [0,%d)", device, n_dev);
+    if (micro_batch < 1 || micro_batch > MAX_MICRO_BATCH) return train_fail(nullptr)("micro_batch %d: 1 .. %d", micro_batch, MAX_MICRO_BATCH);
+    if (optimizer < 0 || optimizer > 1) return train_fail(nullptr)("optimizer %d: 0 (Adam) or 1 (SGDM)", optimizer);
+    if (loss < 0 || loss > 1) return train_fail(nullptr)("loss %d: 0 (focal loss) or 1 (cross entropy)", loss);
+    if (hip_device_check(train_fail(nullptr), device, "training runs on an MI355X only")) return 1;
     clair_trainer *t = new clair_trainer;
     t->device = device; t->cap = micro_batch; t->optimizer = optimizer; t->loss = loss;
     if (train_init(t)) {
@@ -325,35 +306,35 @@ void clair_train_destroy(clair_trainer_t *t) {
 }
 
 static int tensor_range(clair_trainer *t, const char *what, int set, int tensor_id, const void *host, int64_t count) {
-    if (!t) return train_fail(nullptr, "trainer handle is NULL");
-    if (set < 0 || set > 3) return train_fail(t, "%s: set %d: 0 weights, 1 gradients, 2 Adam m | momentum, 3 Adam v", what, set);
-    if (tensor_id < 0 || tensor_id >= N_TENSORS) return train_fail(t, "%s: tensor id %d out of range [0,%d)", what, tensor_id, N_TENSORS);
-    if (!host) return train_fail(t, "%s: host is NULL", what);
-    if (count != TENSOR_COUNT[tensor_id]) return train_fail(t, "%s: tensor %d has %lld elements, got %lld", what, tensor_id, (long long)TENSOR_COUNT[tensor_id], (long long)count);
+    if (!t) return train_fail(nullptr)("trainer handle is NULL");
+    if (set < 0 || set > 3) return train_fail(t)("%s: set %d: 0 weights, 1 gradients, 2 Adam m | momentum, 3 Adam v", what, set);
+    if (tensor_id < 0 || tensor_id >= N_TENSORS) return train_fail(t)("%s: tensor id %d out of range [0,%d)", what, tensor_id, N_TENSORS);
+    if (!host) return train_fail(t)("%s: host is NULL", what);
+    if (count != TENSOR_COUNT[tensor_id]) return train_fail(t)("%s: tensor %d has %lld elements, got %lld", what, tensor_id, (long long)TENSOR_COUNT[tensor_id], (long long)count);
     return 0;
 }
 
 int clair_train_set_tensor(clair_trainer_t *t, int set, int tensor_id, const float *host, int64_t count) {
     if (tensor_range(t, "clair_train_set_tensor", set, tensor_id, host, count)) return 1;
-    TRAIN_TRY(t, hipSetDevice(t->device));
-    TRAIN_TRY(t, hipMemcpyAsync(t->sets[set].as<float>() + t->offset[tensor_id], host, (size_t)count * 4, hipMemcpyHostToDevice, t->stream));
-    TRAIN_TRY(t, hipStreamSynchronize(t->stream));
+    CLAIR_HIP_TRY(train_fail(t), hipSetDevice(t->device));
+    CLAIR_HIP_TRY(train_fail(t), hipMemcpyAsync(t->sets[set].as<float>() + t->offset[tensor_id], host, (size_t)count * 4, hipMemcpyHostToDevice, t->stream));
+    CLAIR_HIP_TRY(train_fail(t), hipStreamSynchronize(t->stream));
     return 0;
 }
 
 int clair_train_get_tensor(clair_trainer_t *t, int set, int tensor_id, float *host, int64_t count) {
     if (tensor_range(t, "clair_train_get_tensor", set, tensor_id, host, count)) return 1;
-    TRAIN_TRY(t, hipSetDevice(t->device));
-    TRAIN_TRY(t, hipMemcpyAsync(host, t->sets[set].as<float>() + t->offset[tensor_id], (size_t)count * 4, hipMemcpyDeviceToHost, t->stream));
-    TRAIN_TRY(t, hipStreamSynchronize(t->stream));
+    CLAIR_HIP_TRY(train_fail(t), hipSetDevice(t->device));
+    CLAIR_HIP_TRY(train_fail(t), hipMemcpyAsync(host, t->sets[set].as<float>() + t->offset[tensor_id], (size_t)count * 4, hipMemcpyDeviceToHost, t->stream));
+    CLAIR_HIP_TRY(train_fail(t), hipStreamSynchronize(t->stream));
     return 0;
 }
 
 int clair_train_config(clair_trainer_t *t, const double *task_loss_weights, const double *class_weights, const double *dropout_rates, int64_t seed) {
-    if (!t) return train_fail(nullptr, "trainer handle is NULL");
+    if (!t) return train_fail(nullptr)("trainer handle is NULL");
     if (dropout_rates)
         for (int i = 0; i < 6; ++i)
-            if (!(dropout_rates[i] >= 0.0 && dropout_rates[i] < 1.0)) return train_fail(t, "dropout rate %d is %g: 0 <= rate < 1", i, dropout_rates[i]);
+            if (!(dropout_rates[i] >= 0.0 && dropout_rates[i] < 1.0)) return train_fail(t)("dropout rate %d is %g: 0 <= rate < 1", i, dropout_rates[i]);
     if (task_loss_weights) for (int i = 0; i < 5; ++i) t->task_weights[i] = task_loss_weights[i];
     if (class_weights) for (int i = 0; i < 90; ++i) t->class_weights[i] = class_weights[i];
     if (dropout_rates) for (int i = 0; i < 6; ++i) t->rates[i] = dropout_rates[i];
@@ -362,24 +343,24 @@ int clair_train_config(clair_trainer_t *t, const double *task_loss_weights, cons
 }
 
 int clair_train_zero_grad(clair_trainer_t *t) {
-    if (!t) return train_fail(nullptr, "trainer handle is NULL");
-    TRAIN_TRY(t, hipSetDevice(t->device));
-    TRAIN_TRY(t, hipMemsetAsync(t->sets[1].p, 0, (size_t)t->n_params * 4, t->stream));
-    TRAIN_TRY(t, hipStreamSynchronize(t->stream));
+    if (!t) return train_fail(nullptr)("trainer handle is NULL");
+    CLAIR_HIP_TRY(train_fail(t), hipSetDevice(t->device));
+    CLAIR_HIP_TRY(train_fail(t), hipMemsetAsync(t->sets[1].p, 0, (size_t)t->n_params * 4, t->stream));
+    CLAIR_HIP_TRY(train_fail(t), hipStreamSynchronize(t->stream));
     return 0;
 }
 
 int clair_train_accumulate(clair_trainer_t *t, const float *x, const uint8_t *labels, int n, int64_t first_row, int training, double *losses) {
-    if (!t) return train_fail(nullptr, "trainer handle is NULL");
-    if (n < 1 || n > t->cap) return train_fail(t, "%d rows in a micro-batch: 1 .. micro_batch = %d", n, t->cap);
-    if (!x || !labels || !losses) return train_fail(t, "NULL argument");
-    if (first_row < 0) return train_fail(t, "first_row %lld is negative", (long long)first_row);
+    if (!t) return train_fail(nullptr)("trainer handle is NULL");
+    if (n < 1 || n > t->cap) return train_fail(t)("%d rows in a micro-batch: 1 .. micro_batch = %d", n, t->cap);
+    if (!x || !labels || !losses) return train_fail(t)("NULL argument");
+    if (first_row < 0) return train_fail(t)("first_row %lld is negative", (long long)first_row);
     for (int i = 0; i < n; ++i)
         for (int k = 0; k < 4; ++k)
-            if (labels[i * 4 + k] >= HEAD_SIZE[k]) return train_fail(t, "row %d: label %d of head %d: 0 .. %d", i, labels[i * 4 + k], k, HEAD_SIZE[k] - 1);
-    TRAIN_TRY(t, hipSetDevice(t->device));
-    TRAIN_TRY(t, hipMemcpyAsync(t->x.p, x, (size_t)n * T_STEPS * 32 * 4, hipMemcpyHostToDevice, t->stream));
-    TRAIN_TRY(t, hipMemcpyAsync(t->labels.p, labels, (size_t)n * 4, hipMemcpyHostToDevice, t->stream));
+            if (labels[i * 4 + k] >= HEAD_SIZE[k]) return train_fail(t)("row %d: label %d of head %d: 0 .. %d", i, labels[i * 4 + k], k, HEAD_SIZE[k] - 1);
+    CLAIR_HIP_TRY(train_fail(t), hipSetDevice(t->device));
+    CLAIR_HIP_TRY(train_fail(t), hipMemcpyAsync(t->x.p, x, (size_t)n * T_STEPS * 32 * 4, hipMemcpyHostToDevice, t->stream));
+    CLAIR_HIP_TRY(train_fail(t), hipMemcpyAsync(t->labels.p, labels, (size_t)n * 4, hipMemcpyHostToDevice, t->stream));
     t->last_n = 0;
     if (run_accumulate(t, n, first_row, training ? 1 : 0, losses)) return 1;
     t->last_n = n;
@@ -388,17 +369,17 @@ int clair_train_accumulate(clair_trainer_t *t, const float *x, const uint8_t *la
 }
 
 int clair_train_step(clair_trainer_t *t, double learning_rate, double l2_lambda, double *stats) {
-    if (!t) return train_fail(nullptr, "trainer handle is NULL");
-    if (!stats) return train_fail(t, "stats is NULL");
-    TRAIN_TRY(t, hipSetDevice(t->device));
+    if (!t) return train_fail(nullptr)("trainer handle is NULL");
+    if (!stats) return train_fail(t)("stats is NULL");
+    CLAIR_HIP_TRY(train_fail(t), hipSetDevice(t->device));
     Segments segs;
     for (int i = 0; i < N_TENSORS; ++i) segs.end[i] = t->offset[i + 1];
     float *w = t->sets[0].as<float>(), *g = t->sets[1].as<float>();
     hipLaunchKernelGGL(regularize_norm_kernel, dim3(RED_BLOCKS), dim3(256), 0, t->stream, w, g, t->n_params, segs, (float)(t->task_weights[4] * l2_lambda),
                        t->partial.as<double>());
-    TRAIN_TRY(t, hipGetLastError());
+    CLAIR_HIP_TRY(train_fail(t), hipGetLastError());
     hipLaunchKernelGGL(norm_finish_kernel, dim3(1), dim3(64), 0, t->stream, t->partial.as<double>(), t->stats.as<double>());
-    TRAIN_TRY(t, hipGetLastError());
+    CLAIR_HIP_TRY(train_fail(t), hipGetLastError());
     t->step += 1;
     if (t->optimizer == 0) {
         const float lr = (float)learning_rate;
@@ -409,44 +390,44 @@ int clair_train_step(clair_trainer_t *t, double learning_rate, double l2_lambda,
     } else {
         LAUNCH(t, momentum_kernel, t->n_params, w, g, t->sets[2].as<float>(), t->n_params, t->stats.as<double>(), (float)learning_rate);
     }
-    TRAIN_TRY(t, hipMemcpyAsync(stats, t->stats.p, 2 * sizeof(double), hipMemcpyDeviceToHost, t->stream));
-    TRAIN_TRY(t, hipStreamSynchronize(t->stream));
+    CLAIR_HIP_TRY(train_fail(t), hipMemcpyAsync(stats, t->stats.p, 2 * sizeof(double), hipMemcpyDeviceToHost, t->stream));
+    CLAIR_HIP_TRY(train_fail(t), hipStreamSynchronize(t->stream));
     return 0;
 }
 
 int clair_train_read_mask(clair_trainer_t *t, int layer, uint8_t *host, int64_t count) {
-    if (!t) return train_fail(nullptr, "trainer handle is NULL");
-    if (layer < 0 || layer > 5) return train_fail(t, "mask layer %d: 0 LSTM2, 1 L4, 2..5 L5_1..4", layer);
-    if (!host) return train_fail(t, "host is NULL");
-    if (!t->last_n || !t->last_training) return train_fail(t, "no training accumulate to read masks of");
+    if (!t) return train_fail(nullptr)("trainer handle is NULL");
+    if (layer < 0 || layer > 5) return train_fail(t)("mask layer %d: 0 LSTM2, 1 L4, 2..5 L5_1..4", layer);
+    if (!host) return train_fail(t)("host is NULL");
+    if (!t->last_n || !t->last_training) return train_fail(t)("no training accumulate to read masks of");
     const int64_t want = (int64_t)t->last_n * MASK_WIDTH[layer];
-    if (count != want) return train_fail(t, "mask of layer %d has %lld bytes for %d rows, got %lld", layer, (long long)want, t->last_n, (long long)count);
+    if (count != want) return train_fail(t)("mask of layer %d has %lld bytes for %d rows, got %lld", layer, (long long)want, t->last_n, (long long)count);
     const uint8_t *src = layer == 0 ? t->m_lstm2.as<uint8_t>() : layer == 1 ? t->m4.as<uint8_t>() : t->m5.as<uint8_t>() + (int64_t)(layer - 2) * t->last_n * 96;
-    TRAIN_TRY(t, hipSetDevice(t->device));
-    TRAIN_TRY(t, hipMemcpyAsync(host, src, (size_t)count, hipMemcpyDeviceToHost, t->stream));
-    TRAIN_TRY(t, hipStreamSynchronize(t->stream));
+    CLAIR_HIP_TRY(train_fail(t), hipSetDevice(t->device));
+    CLAIR_HIP_TRY(train_fail(t), hipMemcpyAsync(host, src, (size_t)count, hipMemcpyDeviceToHost, t->stream));
+    CLAIR_HIP_TRY(train_fail(t), hipStreamSynchronize(t->stream));
     return 0;
 }
 
 int clair_train_probabilities(clair_trainer_t *t, float *out) {
-    if (!t) return train_fail(nullptr, "trainer handle is NULL");
-    if (!out) return train_fail(t, "out is NULL");
-    if (!t->last_n) return train_fail(t, "no accumulate to read probabilities of");
-    TRAIN_TRY(t, hipSetDevice(t->device));
-    TRAIN_TRY(t, hipMemcpyAsync(out, t->probs.p, (size_t)t->last_n * 90 * 4, hipMemcpyDeviceToHost, t->stream));
-    TRAIN_TRY(t, hipStreamSynchronize(t->stream));
+    if (!t) return train_fail(nullptr)("trainer handle is NULL");
+    if (!out) return train_fail(t)("out is NULL");
+    if (!t->last_n) return train_fail(t)("no accumulate to read probabilities of");
+    CLAIR_HIP_TRY(train_fail(t), hipSetDevice(t->device));
+    CLAIR_HIP_TRY(train_fail(t), hipMemcpyAsync(out, t->probs.p, (size_t)t->last_n * 90 * 4, hipMemcpyDeviceToHost, t->stream));
+    CLAIR_HIP_TRY(train_fail(t), hipStreamSynchronize(t->stream));
     return 0;
 }
 
 int clair_train_accuracy(clair_trainer_t *t, int64_t *tp) {
-    if (!t) return train_fail(nullptr, "trainer handle is NULL");
-    if (!tp) return train_fail(t, "tp is NULL");
-    if (!t->last_n) return train_fail(t, "no accumulate to count the accuracy of");
-    TRAIN_TRY(t, hipSetDevice(t->device));
-    TRAIN_TRY(t, hipMemsetAsync(t->tp.p, 0, 4 * sizeof(int64_t), t->stream));
+    if (!t) return train_fail(nullptr)("trainer handle is NULL");
+    if (!tp) return train_fail(t)("tp is NULL");
+    if (!t->last_n) return train_fail(t)("no accumulate to count the accuracy of");
+    CLAIR_HIP_TRY(train_fail(t), hipSetDevice(t->device));
+    CLAIR_HIP_TRY(train_fail(t), hipMemsetAsync(t->tp.p, 0, 4 * sizeof(int64_t), t->stream));
     LAUNCH(t, accuracy_kernel, t->last_n, t->probs.as<float>(), t->labels.as<uint8_t>(), t->last_n, t->tp.as<unsigned long long>());
-    TRAIN_TRY(t, hipMemcpyAsync(tp, t->tp.p, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, t->stream));
-    TRAIN_TRY(t, hipStreamSynchronize(t->stream));
+    CLAIR_HIP_TRY(train_fail(t), hipMemcpyAsync(tp, t->tp.p, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, t->stream));
+    CLAIR_HIP_TRY(train_fail(t), hipStreamSynchronize(t->stream));
     return 0;
 }
 

@@ -181,6 +181,30 @@ def test_candidates_then_windows_equal_the_two_sequential_stages():
     assert np.array_equal(hc[keep], centres) and np.array_equal(hs[keep], seqs) and np.array_equal(hcounts[keep], counts)
 
 
+@pytest.mark.parametrize("n", [4095, 4096, 4097, 8192, 8193])
+def test_tables_that_end_at_a_scan_block(n):
+    """Tables of n positions with n and n + 1 on different sides of a 4096-item scan block (csrc/frontend.hip SCAN_BLOCK): entry n of the
+    per-position prefix, the total, is written by the thread that owns index n, in a workgroup of its own when n is a multiple of the block."""
+    block = 4096
+    case = fc.synth(500 + n, n_reads=300, ref_len=n - 128, read_len=(100, 1500), ins_rate=0.03, del_rate=0.03)
+    f = device_frontend(case, margin=64)
+    lo = case["ref0"] - 64                       # the tables cover the 1-based positions lo + 1 .. lo + n
+    assert len(case["ref"]) + 128 == n
+    inside = sorted({lo + 1, lo + n} | {lo + 1 + t for k in range(1, n // block + 1) for t in (k * block - 1, k * block) if t < n})
+    assert f.set_candidates(np.array([lo] + inside + [lo + n + 1], np.int64)) == len(inside)
+    assert np.array_equal(f.candidates(), np.array(inside, np.int64))
+    # candidates found on the tallies, then the windows at them: before[n] is what the windows of the last positions are counted from
+    want_pos = fc.host_candidates(case, min_coverage=4, threshold=0.125)
+    hc, hs, hcounts = fc.host_windows(case, candidates=want_pos)
+    keep = fe.PILE_ROW[hs[:, 16]] != 255
+    assert f.find_candidates(min_coverage=4, threshold=0.125) == len(want_pos) > 50 and np.array_equal(f.candidates(), want_pos)
+    f.build_windows(min_coverage=0, drop_non_iupac_centre=True)
+    assert f.stats()["anomalies"] == 0
+    centres, seqs, counts = windows_of(f)
+    assert np.array_equal(hc[keep], centres) and np.array_equal(hs[keep], seqs) and np.array_equal(hcounts[keep], counts)
+    f.close()
+
+
 def test_budget_that_binds_is_reported():
     case = fc.synth(31, n_reads=200, ref_len=1500, cand_step=(1, 4))
     f = device_frontend(case, slabs=2)

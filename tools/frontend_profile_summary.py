@@ -21,7 +21,7 @@ def main():
     elements, positions, windows = arg("--elements", 0), arg("--positions", 0), arg("--windows", 0)
     dur = {}
     for name, start, end, gx in trace.execute("select name, start, end, grid_x from kernels order by start"):
-        if "fe_" in name:
+        if "fe_" in name or "clair_scan::" in name:
             dur.setdefault(name, []).append(((end - start) / 1e3, gx))
 
     def counter(db, which):
@@ -36,9 +36,9 @@ def main():
         "fe_tally_tile_kernel": elements * (1 + 16 / 8.0) + positions * 64 * 2,               # SEQ byte + its share of an operation; the tile's 64 B of counters read and written once
         "fe_windows_per_base_kernel": elements * (1 + 16 / 8.0 + 4) + elements * 2 * 4,      # + two prefix look-ups
         "fe_candidate_flags_kernel": positions * (32 + 1),
-        # the block scan is one kernel family: the model is for its flag instantiations (candidate flags -> prefix and candidate list)
-        "fe_scan_sums_kernel<ScanBytes<false>>": positions * 1,
-        "fe_scan_write_kernel<ScanBytes<false>,WriteCompact>": positions * (1 + 4),
+        # the block scan (csrc/device_scan.h) is one kernel family: the model is for its flag instantiations (candidate flags -> prefix and candidate list)
+        "clair_scan::totals_kernel<clair_scan::FlagScan<false>,16>": positions * 1,
+        "clair_scan::write_kernel<clair_scan::FlagScan<false>,16,WriteCompact>": positions * (1 + 4),
         "fe_window_flags_kernel": windows * 35 * 32,
         "fe_assemble_kernel": windows * (2112 + 33 * (32 + 8) + 1056),
         "fe_text_lines_kernel": elements * 2.03,             # every byte of the text once (SEQ + QUAL + the rest ~ 2 bytes per aligned base)
@@ -47,7 +47,7 @@ def main():
     }
     print("%-52s %8s %10s %10s %12s %12s %12s %14s %10s" % ("kernel", "launches", "mean_us", "grid", "fetch_MB(x2)", "write_MB", "GB/s moved", "algorithmic_MB", "GB/s alg."))
     for name in sorted(dur, key=lambda k: -sum(d for d, _ in dur[k])):
-        m = re.search(r"(fe_\w+)(<[^(]*>)?", name.replace("(anonymous namespace)::", ""))
+        m = re.search(r"((?:clair_scan::|fe_)\w+)(<[^(]*>)?", name.replace("(anonymous namespace)::", ""))
         short = (m.group(1) + (m.group(2) or "")).replace(" ", "")      # with its template arguments: the instantiations are different kernels
         d = [x for x, _ in dur[name]]
         big = max(d)
