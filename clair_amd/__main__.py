@@ -16,6 +16,7 @@ SUBMODULES = {
     "PairWithNonVariants": "clair_amd.pair_with_non_variants",
     "train_clr": "clair_amd.train_clr",
     "merge_vcf": "clair_amd.merge_vcf",
+    "compare_vcf": "clair_amd.compare_vcf",
 }
 NOT_COVERED = ("plot_tensor", "train", "Tensor2Bin", "CombineBins", "Bin2To3", "overlap_variant")
 

@@ -125,6 +125,17 @@ SIGNATURES = {
     "clair_deflate_blocks": _sig(c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp),
     "clair_overlap_keep": _sig(c_int, c_vp, c_i64, c_vp),
     "clair_overlap_last_error": _sig(restype=c_cp),
+    "clair_compare_create": _sig(c_int, p_vp),
+    "clair_compare_destroy": _sig(c_vp, restype=None),
+    "clair_compare_last_error": _sig(c_vp, restype=c_cp),
+    "clair_compare_set_contigs": _sig(c_vp, c_vp, c_vp, c_int),
+    "clair_compare_set_regions": _sig(c_vp, c_vp, c_vp, c_vp, c_i64),
+    "clair_compare_parse": _sig(c_vp, c_int, c_vp, c_i64, c_vp),
+    "clair_compare_keys": _sig(c_vp, c_int, c_vp),
+    "clair_compare_permute": _sig(c_vp, c_int, c_vp),
+    "clair_compare_run": _sig(c_vp),
+    "clair_compare_counts": _sig(c_vp, c_vp),
+    "clair_compare_records": _sig(c_vp, c_int, c_vp, c_vp),
     "clair_train_create": _sig(c_int, c_int, c_int, c_int, p_vp),
     "clair_train_destroy": _sig(c_vp, restype=None),
     "clair_train_last_error": _sig(c_vp, restype=c_cp),
@@ -141,6 +152,7 @@ SIGNATURES = {
 SYMBOLS = tuple(SIGNATURES)
 ENSEMBLE_MAX_MODELS = 8                                      # CLAIR_ENSEMBLE_MAX_MODELS
 OVERLAP_SCAN_BLOCK = 2048                                    # clair_ov::BLOCK (csrc/overlap.hip): rows per workgroup of the head scan
+COMPARE_SCAN_BLOCK = 2048                                    # clair_cmp::BLOCK (csrc/compare.hip): text bytes / record slots per workgroup of a scan
 EVAL_COUNTS = 3 + 21 * 21 + 3 * 3 + 33 * 33 + 33 * 33      # CLAIR_EVAL_COUNTS: all, top1, top2, gt21, genotype, len1, len2
 KERNEL_NAMES = ("proj1", "lstm1", "proj2", "lstm2", "l3", "l4", "tail", "decode")
 

@@ -94,6 +94,16 @@ SIGNATURES = {
     "clair_host_sites_info": _sig(vp, i64, i64, vp, vp, vp),
     "clair_host_sites_rows": _sig(vp, i64, i64, vp),
     "clair_host_sites_windows": _sig(vp, i64, i64, vp),
+    "clair_host_compare_create": _sig(p_vp),
+    "clair_host_compare_destroy": _sig(vp, restype=None),
+    "clair_host_compare_set_contigs": _sig(vp, vp, vp, i32),
+    "clair_host_compare_set_regions": _sig(vp, vp, vp, vp, i64),
+    "clair_host_compare_parse": _sig(vp, i32, vp, i64, vp),
+    "clair_host_compare_keys": _sig(vp, i32, vp),
+    "clair_host_compare_permute": _sig(vp, i32, vp),
+    "clair_host_compare_run": _sig(vp),
+    "clair_host_compare_counts": _sig(vp, vp),
+    "clair_host_compare_records": _sig(vp, i32, vp, vp),
 }
 SYMBOLS = tuple(SIGNATURES)
 N_VALUES = 1056

@@ -566,6 +566,40 @@ int clair_train_read_mask(clair_trainer_t *t, int layer, uint8_t *host, int64_t 
 int clair_train_probabilities(clair_trainer_t *t, float *out);
 int clair_train_accuracy(clair_trainer_t *t, int64_t *tp);
 
+/* -- compare_vcf on the device (python -m clair_amd.compare_vcf --backend device; csrc/compare.hip, docs/compare_vcf.md has the rule and
+ * the tables).  One handle scores one call set against one truth set: both texts (VCF as plain bytes, each below 2^32 bytes) are copied to
+ * the device, parsed there into 32-byte allele records that point into them (csrc/compare_core.h lays the record out and holds the rule),
+ * joined and counted; only statistics, the counter block and, when asked for, the records cross the host link.  side: 0 calls, 1 truth.
+ * _set_contigs: the contig table, name k = names[offsets[k] .. offsets[k + 1]); a record's ctg is its index there.  Resets both sides.
+ * _set_regions: the confident regions, sorted and merged per contig, 0-based half-open: those of contig k are [first[k], first[k + 1])
+ *   of starts / ends, first [n_contigs + 1]; n_intervals < 0: none, everything is inside.
+ * _parse: stats [8] = lines, data rows, records, the drop counters symbolic, unknown_contig, too_long, sorted (1: the records are in
+ *   (contig, pos) order as they stand), 0.  Returns non-zero for a malformed row, with a message that names the side and the 1-based line.
+ * _keys: the 8-byte key (ctg << 32 | pos) of every record, in the order the records have.  _permute: record i becomes what record perm[i]
+ *   was (the stable permutation the host sorted the keys with).  _run refuses a side that is not in order.
+ * _run: duplicates, regions, join, the counters and the suffix sums.  _counts: CLAIR_COMPARE_COUNTS int64, laid out as the table in
+ *   docs/compare_vcf.md (counts [2][4][6], hist [4][3][1024], at_least [4][3][1024], drops [2][3]).
+ * _records: the records of a side and one outcome byte each (0 TP, 1 GT, 2 FP, 3 FN, 4 DUP, 5 OUTSIDE); either array may be NULL.
+ * Every call is synchronous.  Non-zero on failure, message from clair_compare_last_error (NULL handle: the failure of create).
+ * clair_host_compare_* (include/clair_host.h) gives the same integers on the CPU. */
+#define CLAIR_COMPARE_COUNTS 24630
+typedef struct clair_compare clair_compare_t;
+#ifndef CLAIR_COMPARE_RECORD_T
+#define CLAIR_COMPARE_RECORD_T
+typedef struct clair_compare_record clair_compare_record_t;
+#endif
+int clair_compare_create(int device, clair_compare_t **out);
+void clair_compare_destroy(clair_compare_t *h);
+const char *clair_compare_last_error(const clair_compare_t *h);
+int clair_compare_set_contigs(clair_compare_t *h, const uint8_t *names, const int64_t *offsets, int n_contigs);
+int clair_compare_set_regions(clair_compare_t *h, const int64_t *first, const int64_t *starts, const int64_t *ends, int64_t n_intervals);
+int clair_compare_parse(clair_compare_t *h, int side, const uint8_t *text, int64_t len, int64_t *stats);
+int clair_compare_keys(clair_compare_t *h, int side, int64_t *keys);
+int clair_compare_permute(clair_compare_t *h, int side, const int64_t *perm);
+int clair_compare_run(clair_compare_t *h);
+int clair_compare_counts(clair_compare_t *h, int64_t *counts);
+int clair_compare_records(clair_compare_t *h, int side, clair_compare_record_t *records, uint8_t *outcomes);
+
 #ifdef __cplusplus
 }
 #endif

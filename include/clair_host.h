@@ -317,6 +317,26 @@ int clair_host_train_set_pair_keep(const int64_t *centres, int64_t n, const int6
 int clair_host_train_set_labels(const int64_t *centres, const uint8_t *centre_base, int64_t n, const int64_t *truth, const uint8_t *truth_labels, int64_t n_truth,
                                 const int64_t *bed_start, const int64_t *bed_end, int64_t n_bed, uint8_t *labels, uint8_t *in_set);
 
+/* -- the host twin of compare_vcf on the device (hostsrc/host_compare.cpp; docs/compare_vcf.md), with the rule of csrc/compare_core.h, the
+ *    code the GPU runs inside clair_compare_* (include/clair_amd.h): the same entry points with the same arguments, statistics, counter
+ *    block (CLAIR_COMPARE_COUNTS int64) and 32-byte records, as sequential loops.  The text handed to _parse is borrowed, not copied: it
+ *    must stay where it is until the handle is destroyed or the side is parsed again.  Messages go to clair_host_last_error. */
+typedef struct clair_host_compare clair_host_compare_t;
+#ifndef CLAIR_COMPARE_RECORD_T
+#define CLAIR_COMPARE_RECORD_T
+typedef struct clair_compare_record clair_compare_record_t;
+#endif
+int clair_host_compare_create(clair_host_compare_t **out);
+void clair_host_compare_destroy(clair_host_compare_t *h);
+int clair_host_compare_set_contigs(clair_host_compare_t *h, const uint8_t *names, const int64_t *offsets, int n_contigs);
+int clair_host_compare_set_regions(clair_host_compare_t *h, const int64_t *first, const int64_t *starts, const int64_t *ends, int64_t n_intervals);
+int clair_host_compare_parse(clair_host_compare_t *h, int side, const uint8_t *text, int64_t len, int64_t *stats);
+int clair_host_compare_keys(clair_host_compare_t *h, int side, int64_t *keys);
+int clair_host_compare_permute(clair_host_compare_t *h, int side, const int64_t *perm);
+int clair_host_compare_run(clair_host_compare_t *h);
+int clair_host_compare_counts(clair_host_compare_t *h, int64_t *counts);
+int clair_host_compare_records(clair_host_compare_t *h, int side, clair_compare_record_t *records, uint8_t *outcomes);
+
 #ifdef __cplusplus
 }
 #endif
