@@ -1,5 +1,7 @@
-// The elementwise, loss and optimizer kernels of the training path (csrc/train.hip).  Everything is float32 except the reductions, which
-// sum in float64 in a fixed order (no atomics anywhere: the same inputs give the same bits).
+// The elementwise, loss and optimizer kernels of the training path (csrc/train.hip).  Everything is float32 except the loss and its row sums
+// and the optimizer's sums of squares, which are float64; column_sum_kernel (the bias gradients) sums in float32, as tgemm does (docs/train.md
+// holds both to the float32 oracle's error up to 150 rows).  Every reduction has a fixed order and none uses atomics: the same inputs give
+// the same bits.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -188,7 +190,7 @@ __global__ __launch_bounds__(256) void loss_reduce_kernel(const double *row_loss
     if (threadIdx.x < 4) sums[threadIdx.x] = part[threadIdx.x];
 }
 
-// out[(j / d) * s1 + (j % d) * s2] += sum over rows of x[row * ld + j], j < cols: 32 columns per workgroup, 8 partial sums per column
+// out[(j / d) * s1 + (j % d) * s2] += sum over rows of x[row * ld + j], j < cols: 32 columns per workgroup, 8 float32 partial sums per column
 __global__ __launch_bounds__(256) void column_sum_kernel(const float *x, int64_t rows, int cols, int64_t ld, float *out, int d, int s1, int s2) {
     __shared__ float part[8][33];
     const int cx = threadIdx.x & 31, ry = threadIdx.x >> 5;

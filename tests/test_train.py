@@ -79,6 +79,53 @@ def test_oracle_float32_is_close_to_float64(case):
         assert np.linalg.norm(r32["gradients"][k] - r64["gradients"][k]) <= 1e-5 * np.linalg.norm(r64["gradients"][k]), k
 
 
+def test_pre_activations_are_the_networks_own(case):
+    """selu of the heads' pre-activations is network()'s output, and the shapes are the documented ones"""
+    w, x, lab = case
+    z = R.pre_activations(w, x)
+    assert [(k, v.shape) for k, v in z.items()] == [("l3", (5, 30, 256)), ("l4", (5, 192)), ("l5_0", (5, 96)), ("head_gt21", (5, 21)), ("l5_1", (5, 96)),
+                                                    ("head_genotype", (5, 3)), ("l5_2", (5, 96)), ("head_len1", (5, 33)), ("l5_3", (5, 96)), ("head_len2", (5, 33))]
+    logits = torch.cat([R.selu(torch.tensor(z["head_%s" % name])) for name, _, _ in R.HEADS], dim=1)
+    _, probs = R.head_losses(logits, lab)
+    assert np.array_equal(probs.numpy(), R.loss_and_gradients(w, x, lab, dtype=torch.float64)["probabilities"])
+    assert all(v.dtype == np.float32 for v in R.pre_activations(w, x, dtype=torch.float32).values())
+
+
+@pytest.mark.parametrize("n,seed", [(130, 7), (70, 9)])
+def test_clear_of_the_selu_kink(n, seed):
+    """Fresh weights on these two batches (built as tests/test_train_gpu.py builds them) put one L3 unit so close to zero that the float32
+    and the float64 oracle disagree on its sign; SELU's derivative jumps there, and the float32 oracle's distance from float64 -- the yardstick
+    of the device tests -- grows from 1e-6 to 3e-4 and more.  After the preparation no unit is within the margin and the yardstick is back."""
+    torch.set_num_threads(4)
+    w = weights.synthetic_weights()
+    x, _ = synth.synthetic_input(n, seed=seed)
+    lab = _labels(n, seed + 1)
+
+    def yardsticks(w):
+        r64, r32 = (R.loss_and_gradients(w, x, lab, dtype=d)["gradients"] for d in (torch.float64, torch.float32))
+        return {k: np.linalg.norm(r32[k] - r64[k]) / np.linalg.norm(r64[k]) for k in r64}
+
+    z64, z32 = (R.pre_activations(w, x, dtype=d) for d in (torch.float64, torch.float32))
+    assert R.sign_disagreements(z32, z64) >= 1
+    before = max(yardsticks(w).values())
+    assert before > 1e-4
+    prepared, report = R.clear_of_the_selu_kink(w, x)
+    print("n=%d seed %d: yardstick %.3g before; margin %.3g, %d rounds, %d biases moved, smallest |z| %.3g" %
+          (n, seed, before, report["margin"], report["rounds"], report["moved"], report["smallest"]))
+    z64, z32 = (R.pre_activations(prepared, x, dtype=d) for d in (torch.float64, torch.float32))
+    assert R.sign_disagreements(z32, z64) == 0
+    assert all(np.abs(v).min() >= report["margin"] for v in z64.values()) and report["smallest"] >= report["margin"]
+    assert 1e-8 < report["margin"] < 1e-4 and 1 <= report["rounds"] <= 40 and report["moved"] >= 1
+    for k, err in yardsticks(prepared).items():
+        assert err <= 1e-5, (k, err)
+    for k in w:
+        assert prepared[k].dtype == np.float32 and prepared[k].shape == w[k].shape
+        assert k.endswith("_bias") or np.array_equal(prepared[k], w[k]), k
+    assert any(not np.array_equal(prepared[k], w[k]) for k in w)
+    again = weights.synthetic_weights()
+    assert all(np.array_equal(w[k], again[k]) for k in w)      # the argument is left as it was
+
+
 @pytest.mark.parametrize("rate", [0.5, 0.2])
 def test_dropout_selu_constants(rate):
     """clair/selu.py:64-66: a and b keep mean 0 and variance 1 of a unit-variance input"""

@@ -4,6 +4,8 @@ The network of clair/model.py written with explicit LSTM steps on the TF-layout 
 bias), the dropout masks handed in from outside, both losses (model.py:247-263 weighted cross entropy, :784-805 focal loss) and the
 lambda * L2 term (:689-709).  loss_and_gradients returns the loss parts and the 22 gradients in float32 or float64.  The TensorFlow-1.x
 Adam and Momentum updates and clip_by_global_norm are restated in NumPy float32 (adam_step, momentum_step, clip_by_global_norm).
+pre_activations returns the input of every SELU, and clear_of_the_selu_kink moves biases until none of them is near zero for a given
+batch, so that the float32 gradients are a fair yardstick for the float64 ones (docs/train.md, "The SELU kink").
 """
 from collections import OrderedDict
 
@@ -58,26 +60,91 @@ def _bilstm(X, w, layer):
     return torch.cat([fw, bw], dim=2)
 
 
-def network(w, x, masks=None, rates=DEFAULT_RATES):
-    """w: dict of torch tensors; x [n,33,8,4] torch; masks None (no dropout) or {0: [33,n,256], 1: [n,192], 2..5: [n,96]} of 0/1.
-    -> SELU'd logits [n,90]"""
+def _network(w, x, masks, rates):
+    """-> (SELU'd logits [n,90], the input of every SELU: l3 [n,30,256], l4 [n,192], l5_0..3 [n,96], head_<name> [n,size])"""
     n = x.shape[0]
+    z = OrderedDict()
     s = x.reshape(n, 33, 32).transpose(0, 1)
     a1 = _bilstm(s, w, 1)
     a2 = _bilstm(a1, w, 2)
     if masks is not None and rates[0] > 0:
         a2 = a2 * torch.as_tensor(np.asarray(masks[0]), dtype=x.dtype) / (1.0 - rates[0])     # tf.layers.dropout
-    l3 = selu(torch.einsum("tnc,ctu->nuc", a2, w["l3_kernel"]) + w["l3_bias"].t().unsqueeze(0))
-    l4 = selu(l3.reshape(n, 7680) @ w["l4_kernel"] + w["l4_bias"])
+    z["l3"] = torch.einsum("tnc,ctu->nuc", a2, w["l3_kernel"]) + w["l3_bias"].t().unsqueeze(0)
+    z["l4"] = selu(z["l3"]).reshape(n, 7680) @ w["l4_kernel"] + w["l4_bias"]
+    l4 = selu(z["l4"])
     if masks is not None:
         l4 = dropout_selu(l4, torch.as_tensor(np.asarray(masks[1]), dtype=x.dtype), rates[1])
     logits = []
     for k, (name, _, _) in enumerate(HEADS):
-        l5 = selu(l4 @ w["l5_kernel"][k] + w["l5_bias"][k])
+        z["l5_%d" % k] = l4 @ w["l5_kernel"][k] + w["l5_bias"][k]
+        l5 = selu(z["l5_%d" % k])
         if masks is not None:
             l5 = dropout_selu(l5, torch.as_tensor(np.asarray(masks[2 + k]), dtype=x.dtype), rates[2 + k])
-        logits.append(selu(l5 @ w["head_%s_kernel" % name] + w["head_%s_bias" % name]))
-    return torch.cat(logits, dim=1)
+        z["head_%s" % name] = l5 @ w["head_%s_kernel" % name] + w["head_%s_bias" % name]
+        logits.append(selu(z["head_%s" % name]))
+    return torch.cat(logits, dim=1), z
+
+
+def network(w, x, masks=None, rates=DEFAULT_RATES):
+    """w: dict of torch tensors; x [n,33,8,4] torch; masks None (no dropout) or {0: [33,n,256], 1: [n,192], 2..5: [n,96]} of 0/1.
+    -> SELU'd logits [n,90]"""
+    return _network(w, x, masks, rates)[0]
+
+
+def pre_activations(w, x, masks=None, rates=DEFAULT_RATES, dtype=torch.float64):
+    """the input of every SELU of network(), as arrays in dtype: l3 [n,30,256], l4 [n,192], l5_0..3 [n,96] and the four heads' logits
+    before their SELU (head_gt21 [n,21], head_genotype [n,3], head_len1, head_len2 [n,33])"""
+    torch.set_num_threads(4)
+    with torch.no_grad():
+        wt = {k: torch.tensor(np.asarray(v), dtype=dtype) for k, v in w.items()}
+        z = _network(wt, torch.tensor(np.asarray(x), dtype=dtype), masks, rates)[1]
+    return OrderedDict((k, v.numpy()) for k, v in z.items())
+
+
+def sign_disagreements(z32, z64):
+    """how many SELU inputs lie on different sides of zero in the two sets of pre_activations"""
+    return int(sum(np.count_nonzero((z32[k] >= 0) != (z64[k] >= 0)) for k in z64))
+
+
+def smallest_pre_activation(z):
+    return float(min(np.abs(v).min() for v in z.values()))
+
+
+def _bias_of(w, key):
+    """the bias tensor behind the pre-activations `key`, viewed so that its axes are the pre-activations' without the row axis"""
+    if key == "l3":
+        return w["l3_bias"].T                   # [c,u] -> [u,c]: a view, written through
+    if key.startswith("l5_"):
+        return w["l5_bias"][int(key[3:])]
+    return w[key + "_bias"]
+
+
+def clear_of_the_selu_kink(w, x, masks=None, rates=DEFAULT_RATES, factor=64, max_rounds=40):
+    """SELU's derivative jumps from scale to scale * alpha at zero, so one unit whose input the float32 and the float64 pass put on
+    different sides of zero moves whole gradient tensors by 1e-4 .. 1e-3 of their norm: the float32 oracle stops being a yardstick, and
+    a device that differs from both by rounding alone may flip a unit of its own.  -> (a copy of w in which only biases have moved,
+    until every SELU input of this batch is at least `margin` from zero, report)
+
+    margin = factor * max |z_f32 - z_f64| over all SELU inputs of this batch under w.  Each round adds 4 * margin to the bias of every
+    unit with |z_f64| < margin (a bias serves all rows, and an earlier layer's bias moves the later layers: hence rounds) and
+    recomputes.  report: margin, rounds, moved (bias elements that differ from w's), smallest (min |z_f64| afterwards)."""
+    w = OrderedDict((k, np.array(v, dtype=np.float32, copy=True)) for k, v in w.items())
+    before = {k: v.copy() for k, v in w.items() if k.endswith("_bias")}
+    z64 = pre_activations(w, x, masks, rates, torch.float64)
+    z32 = pre_activations(w, x, masks, rates, torch.float32)
+    margin = factor * max(float(np.abs(z32[k].astype(np.float64) - z64[k]).max()) for k in z64)
+    rounds = 0
+    while smallest_pre_activation(z64) < margin:
+        if rounds == max_rounds:
+            raise RuntimeError("clear_of_the_selu_kink: SELU inputs within %.3g of zero after %d rounds" % (margin, rounds))
+        rounds += 1
+        for k, z in z64.items():
+            near = (np.abs(z) < margin).any(axis=0)
+            if near.any():
+                _bias_of(w, k)[near] += np.float32(4 * margin)
+        z64 = pre_activations(w, x, masks, rates, torch.float64)
+    moved = int(sum(np.count_nonzero(w[k] != v) for k, v in before.items()))
+    return w, dict(margin=margin, rounds=rounds, moved=moved, smallest=smallest_pre_activation(z64))
 
 
 def head_losses(logits, labels, loss="FocalLoss", class_weights=None):
