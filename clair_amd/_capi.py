@@ -136,6 +136,9 @@ SIGNATURES = {
     "clair_compare_run": _sig(c_vp),
     "clair_compare_counts": _sig(c_vp, c_vp),
     "clair_compare_records": _sig(c_vp, c_int, c_vp, c_vp),
+    "clair_compare_set_reference": _sig(c_vp, c_vp, c_vp, c_int),
+    "clair_compare_left_align": _sig(c_vp, c_int, c_vp),
+    "clair_compare_allele_text": _sig(c_vp, c_int, c_vp),
     "clair_train_create": _sig(c_int, c_int, c_int, c_int, p_vp),
     "clair_train_destroy": _sig(c_vp, restype=None),
     "clair_train_last_error": _sig(c_vp, restype=c_cp),

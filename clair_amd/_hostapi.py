@@ -104,6 +104,9 @@ SIGNATURES = {
     "clair_host_compare_run": _sig(vp),
     "clair_host_compare_counts": _sig(vp, vp),
     "clair_host_compare_records": _sig(vp, i32, vp, vp),
+    "clair_host_compare_set_reference": _sig(vp, vp, vp, i32),
+    "clair_host_compare_left_align": _sig(vp, i32, vp),
+    "clair_host_compare_allele_text": _sig(vp, i32, vp),
 }
 SYMBOLS = tuple(SIGNATURES)
 N_VALUES = 1056

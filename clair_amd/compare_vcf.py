@@ -1,14 +1,15 @@
 """compare_vcf: score a call set against a truth set -- TP, FP, FN and genotype mismatches per variant type, precision, recall and F1,
 the same at every integer QUAL cut-off 0 .. 1023, and the cut-off with the best F1.
 
-    python -m clair_amd.compare_vcf --vcf_fn calls.vcf.gz --truth_vcf_fn truth.vcf.gz [--bed_fn confident.bed] [--ref_fn ref.fa]
+    python -m clair_amd.compare_vcf --vcf_fn calls.vcf.gz --truth_vcf_fn truth.vcf.gz [--bed_fn confident.bed] [--ref_fn ref.fa [--left_align]]
                                     [--ctgName chr20] [--backend auto|device|host] [--json_fn out.json] [--detail_fn out.tsv] [--min_qual Q]
 
 The reference has no such tool: what its README says about accuracy comes from an external comparison.  docs/compare_vcf.md states the rule
 this one follows.  Parsing, allele normalisation, the join and the counting are native: `device` runs them on the GPU (csrc/compare.hip),
 `host` in the sequential twin (hostsrc/host_compare.cpp), both over csrc/compare_core.h, and both give the same integers.  This module
 reads the files, builds the contig table and the merged regions, sorts the 8-byte keys when a side is out of order, and turns the integers
-into the report.
+into the report.  With --left_align it also reads the sequences of the contigs in use from --ref_fn, and both sides' indels are moved to
+their leftmost position before the join (docs/compare_vcf.md, "Left alignment"), natively again.
 """
 import ctypes
 import gzip
@@ -28,6 +29,7 @@ KINDS = ("tp", "gt", "fp")
 ROWS = (("SNP", ("SNP",)), ("INS", ("INS",)), ("DEL", ("DEL",)), ("INDEL", ("INS", "DEL")), ("MNP", ("MNP",)), ("ALL", TYPES))
 QUAL_BINS = 1024
 STATS = ("lines", "rows", "records", "symbolic", "unknown_contig", "too_long", "sorted")
+LEFT_ALIGN_STATS = ("examined", "shifted", "ref_mismatch", "at_contig_start", "no_sequence", "sorted", "arena_bytes")       # _left_align's stats[8]
 # the counter block (CLAIR_COMPARE_COUNTS, csrc/compare_core.h; the table in docs/compare_vcf.md)
 AT_COUNTS = 0
 AT_HIST = 2 * len(TYPES) * len(OUTCOMES)
@@ -84,6 +86,36 @@ def contigs_from_fai(ref_fn):
         raise ValueError("%s not found: --ref_fn is read through its .fai only" % fai)
     with open(fai) as f:
         return [row.split("\t")[0] for row in f if row.strip()]
+
+
+def load_reference(ref_fn, contigs):
+    """The sequences of `contigs` from a FASTA, read through its .fai -> {contig: bytes}: line ends removed, case kept.  A contig the .fai does
+    not have is left out (the native side then counts its indels as no_sequence)."""
+    fai = ref_fn + ".fai"
+    if not os.path.isfile(fai):
+        raise ValueError("%s not found: --ref_fn is read through its .fai only" % fai)
+    index = {}
+    with open(fai) as f:
+        for n, row in enumerate(f):
+            cols = row.rstrip("\n").split("\t")
+            if not row.strip():
+                continue
+            if len(cols) < 5 or not all(c.isdigit() for c in cols[1:5]) or int(cols[3]) < 1 or int(cols[4]) < int(cols[3]):
+                raise ValueError("%s line %d: not `name length offset linebases linewidth`" % (fai, n + 1))
+            index.setdefault(cols[0], tuple(int(c) for c in cols[1:5]))
+    out = {}
+    with open(ref_fn, "rb") as f:
+        for c in contigs:
+            if c not in index:
+                continue
+            length, offset, bases, width = index[c]
+            f.seek(offset)
+            raw = f.read(length // bases * width + length % bases)
+            seq = raw.replace(b"\n", b"").replace(b"\r", b"")
+            if len(seq) != length:
+                raise ValueError("%s: contig %s has %d bases where its .fai says %d" % (ref_fn, c, len(seq), length))
+            out[c] = seq
+    return out
 
 
 def merged_regions(bed_fn, contigs):
@@ -162,10 +194,12 @@ def pick_backend(backend):
     return "device" if _capi.load().clair_device_count() > 0 else "host"
 
 
-def compare(calls_text, truth_text, contigs, regions=None, backend="auto", device=0):
+def compare(calls_text, truth_text, contigs, regions=None, backend="auto", device=0, reference=None):
     """calls_text, truth_text: VCF as bytes; contigs: the names, whose order is the order of the records; regions: {contig: [(start, end)]}
     sorted and merged (merged_regions), or None for no bed file.  -> dict: backend; stats[side] (STATS, plus `permuted`); counts (int64
-    [N_COUNTS], the counter block); records[side] (RECORD_DTYPE, in (contig, pos, file) order) and outcomes[side] (uint8, OUTCOMES)."""
+    [N_COUNTS], the counter block); records[side] (RECORD_DTYPE, in (contig, pos, file) order) and outcomes[side] (uint8, OUTCOMES).
+    reference: None, or {contig: sequence as bytes} (load_reference) to left-align the indels of both sides first; then also
+    left_align[side] (LEFT_ALIGN_STATS) and alleles[side], the bytes the records' ref_off / alt_off index in place of the text."""
     backend = pick_backend(backend)
     texts = [np.frombuffer(t, dtype=np.uint8) for t in (calls_text, truth_text)]
     names = [c.encode("latin-1") for c in contigs]
@@ -187,12 +221,27 @@ def compare(calls_text, truth_text, contigs, regions=None, backend="auto", devic
             starts, ends = np.ascontiguousarray(flat[:, 0]), np.ascontiguousarray(flat[:, 1])
             native.call("set_regions", _address(first), _address(starts), _address(ends), len(starts))
         result = {"backend": backend, "stats": {}, "records": {}, "outcomes": {}}
+        if reference is not None:
+            sequences = [reference.get(c, b"") for c in contigs]
+            ref_offsets = np.zeros(len(names) + 1, dtype=np.int64)
+            ref_offsets[1:] = np.cumsum([len(q) for q in sequences])
+            ref_blob = np.frombuffer(b"".join(sequences) or b"\0", dtype=np.uint8)      # borrowed by the host twin until close()
+            native.call("set_reference", _address(ref_blob), _address(ref_offsets), len(names))
+            result["left_align"], result["alleles"] = {}, {}
         for side, text in enumerate(texts):
             stats = np.zeros(8, dtype=np.int64)
             native.call("parse", side, _address(text) if len(text) else None, len(text), _address(stats))
             st = dict(zip(STATS, (int(v) for v in stats)))
             st["permuted"] = 0
-            if not st["sorted"]:
+            in_order = st["sorted"]
+            if reference is not None:
+                native.call("left_align", side, _address(stats))
+                la = dict(zip(LEFT_ALIGN_STATS, (int(v) for v in stats)))
+                in_order = la["sorted"]                  # on the new positions: it supersedes the parse pass's
+                alleles = np.zeros(max(la["arena_bytes"], 1), dtype=np.uint8)
+                native.call("allele_text", side, _address(alleles))
+                result["left_align"][SIDES[side]], result["alleles"][SIDES[side]] = la, alleles[:la["arena_bytes"]].tobytes()
+            if not in_order:
                 keys = np.zeros(st["records"], dtype=np.int64)
                 native.call("keys", side, _address(keys))
                 perm = np.ascontiguousarray(np.argsort(keys, kind="stable"), dtype=np.int64)
@@ -262,17 +311,21 @@ def report_text(rows):
 def report_json(result, rows, contigs, min_qual):
     counts = result["counts"]
     by = counts[AT_COUNTS:AT_HIST].reshape(2, len(TYPES), len(OUTCOMES))
-    return {
+    out = {
         "min_qual": min_qual,
         "contigs": list(contigs),
         "stats": dict((s, dict((k, v) for k, v in result["stats"][s].items())) for s in SIDES),
         "counts": dict((s, dict((t, dict((o, int(by[i, j, k])) for k, o in enumerate(OUTCOMES))) for j, t in enumerate(TYPES))) for i, s in enumerate(SIDES)),
         "rows": rows,
     }
+    if "left_align" in result:
+        out["left_align"] = dict((s, dict(result["left_align"][s])) for s in SIDES)
+    return out
 
 
 def detail_lines(result, texts, contigs):
-    """One line per FP, FN or GT record: side ctg pos ref alt copies qual outcome, the alleles and the position the normalised ones."""
+    """One line per FP, FN or GT record: side ctg pos ref alt copies qual outcome, the alleles and the position the normalised ones.
+    texts: what the records' offsets index, per side: the parsed texts, or result["alleles"] after left alignment (upper-cased then)."""
     for side, text in zip(SIDES, texts):
         records, outcomes = result["records"][side], result["outcomes"][side]
         for i in np.flatnonzero((outcomes >= 1) & (outcomes <= 3)):
@@ -291,7 +344,10 @@ def build_parser():
     parser.add_argument('--truth_vcf_fn', type=str, default=None, help="The truth as a VCF (this or --var_fn)")
     parser.add_argument('--var_fn', type=str, default=None, help="The truth as GetTruth rows `ctg pos ref alt g1 g2` (this or --truth_vcf_fn)")
     parser.add_argument('--bed_fn', type=str, default=None, help="Confident regions; records outside are ignored, optional")
-    parser.add_argument('--ref_fn', type=str, default=None, help="Reference fasta; only its .fai is read, for the contig order, optional")
+    parser.add_argument('--ref_fn', type=str, default=None, help="Reference fasta; its .fai gives the contig order, and with --left_align the sequences "
+                        "of the contigs in use are read through it, optional")
+    parser.add_argument('--left_align', action="store_true", help="Move the indels of both sides to their leftmost position in the reference before the join "
+                        "(needs --ref_fn), so that one event written at two positions of a repeat matches, default: off")
     parser.add_argument('--ctgName', type=str, default=None, help="Restrict both sides to this contig, optional")
     parser.add_argument('--backend', type=str, default="auto", choices=BACKENDS, help="Where parsing, join and counting run: the GPU, the host twin, or the "
                         "GPU when one is visible; the report is the same, default: %(default)s")
@@ -315,7 +371,19 @@ def run(args, stdout=None):
     if args.ctgName is not None:
         contigs = [args.ctgName]
     regions = merged_regions(args.bed_fn, contigs) if args.bed_fn else None
-    result = compare(calls, truth, contigs, regions, backend=args.backend, device=args.device)
+    reference = None
+    if args.left_align:
+        if not args.ref_fn:
+            raise ValueError("--left_align needs --ref_fn")
+        named = set(contigs_of([calls, truth]))
+        reference = load_reference(args.ref_fn, [c for c in contigs if c in named])
+    result = compare(calls, truth, contigs, regions, backend=args.backend, device=args.device, reference=reference)
+    for side in SIDES if reference is not None else ():
+        la = result["left_align"][side]
+        if la["ref_mismatch"] or la["at_contig_start"] or la["no_sequence"]:
+            sys.stderr.write("[WARNING] %s: %d indel records not left-aligned: %d whose REF differs from the reference, %d at a contig start, %d on contigs "
+                             "without sequence\n" % (side, la["ref_mismatch"] + la["at_contig_start"] + la["no_sequence"], la["ref_mismatch"],
+                                                     la["at_contig_start"], la["no_sequence"]))
     rows = summary(result["counts"], args.min_qual)
     (stdout if stdout is not None else sys.stdout).write(report_text(rows))
     if args.json_fn:
@@ -324,7 +392,7 @@ def run(args, stdout=None):
             f.write("\n")
     if args.detail_fn:
         with open(args.detail_fn, "w") as f:
-            f.writelines(detail_lines(result, (calls, truth), contigs))
+            f.writelines(detail_lines(result, [result["alleles"][s] for s in SIDES] if reference is not None else (calls, truth), contigs))
     return result
 
 

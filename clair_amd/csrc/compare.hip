@@ -7,6 +7,11 @@
 //    record slots of its row (compare_core.h); drop counters and data rows are summed in LDS and flushed with one atomic each, the first
 //    malformed line is a 64-bit minimum.   3. the kept slots are compacted in file order with the same scan.   4. one thread per record
 //    clears the sortedness flag where its key is below its predecessor's.
+// _left_align, per side (docs/compare_vcf.md, "Left alignment"):   a. the records' arena slots: an exclusive sum of ref_len + alt_len with the same
+//    scan.   b. one thread per record decides its case (compare_core.h), copies the alleles of a record that stays to its slot and flags a
+//    candidate; the counters are summed in LDS.   c. the candidates are compacted in record order, again with the scan.   d. one wave per
+//    candidate: 64 steps to the left per ballot until a lane's bytes differ or the contig starts, then the lanes write the alleles to the slot
+//    and lane 0 the record.   e. the order flag on the new positions.
 // _permute: a gather.   _run:   5. one thread per truth record: duplicate, outside or pending; then one thread per call record: the same,
 //    and a pending call looks its truth record up (lower bound of its key, then the run of equal keys) and writes both outcomes -- plain
 //    byte stores, no two calls match one truth record once duplicates are out.   6. pending truth records become FN.   7. counts and QUAL
@@ -78,9 +83,99 @@ __global__ __launch_bounds__(256) void parse_kernel(const uint8_t *text, const i
     if (threadIdx.x < P_SUMS && local[threadIdx.x]) atomicAdd(&sums[threadIdx.x], (unsigned long long)local[threadIdx.x]);
 }
 
-__global__ __launch_bounds__(256) void sorted_kernel(const clair_compare_record *rec, int64_t n, unsigned long long *sums) {
+// *in_order was set to 1 before the launch
+__global__ __launch_bounds__(256) void sorted_kernel(const clair_compare_record *rec, int64_t n, unsigned long long *in_order) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i > 0 && i < n && clair_compare_key(rec[i - 1]) > clair_compare_key(rec[i])) sums[P_SORTED] = 0;      // every writer writes 0
+    if (i > 0 && i < n && clair_compare_key(rec[i - 1]) > clair_compare_key(rec[i])) *in_order = 0;      // every writer writes 0
+}
+
+// -- left alignment ----------------------------------------------------------------------------------------------------------------------------
+constexpr int LA_WAVES = 4;      // candidates per workgroup of shift_kernel: one wave each
+// what the pass sums (the first words of _left_align's stats, CLAIR_CMP_LA_*), then the sortedness flag
+enum { LA_SUMS = CLAIR_CMP_LA_NO_SEQUENCE + 1, LA_IN_ORDER = CLAIR_CMP_LA_SORTED, LA_WORDS };
+
+// the bytes a record takes in the arena; below 2^32 in all, as the alleles are parts of a text that is
+struct AlleleBytes : clair_scan::SumScan<uint8_t, uint32_t> {
+    const clair_compare_record *rec;
+    __device__ inline T item(int64_t i) const { return (T)rec[i].ref_len + rec[i].alt_len; }
+};
+using CandidateScan = clair_scan::FlagScan<false>;
+
+struct WriteSlots {
+    static constexpr int PAST_END = 0;
+    uint32_t *slot;
+    static __device__ inline uint32_t seed() { return 0; }
+    __device__ inline void write(const AlleleBytes &, int64_t i, int64_t, uint32_t before, uint32_t) const { slot[i] = before; }
+};
+
+struct WriteCandidates {
+    static constexpr int PAST_END = 0;
+    uint32_t *list;
+    static __device__ inline uint32_t seed() { return 0; }
+    __device__ inline void write(const CandidateScan &, int64_t i, int64_t, uint32_t before, uint32_t is_candidate) const {
+        if (is_candidate) list[before] = (uint32_t)i;
+    }
+};
+
+// One thread per record.  A record that stays is copied to its slot here and points there afterwards; a candidate is left to its wave.
+__global__ __launch_bounds__(256) void la_case_kernel(const uint8_t *text, clair_compare_reference ref, clair_compare_record *rec, int64_t n, const uint32_t *slot,
+                                                      uint8_t *arena, uint8_t *is_candidate, unsigned long long *sums) {
+    __shared__ unsigned local[LA_SUMS];
+    if (threadIdx.x < LA_SUMS) local[threadIdx.x] = 0;
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) {
+        const clair_compare_record r = rec[i];
+        clair_compare_event ev;
+        const int what = clair_compare_la_case(ref, text, r, &ev);
+        if (what != CLAIR_CMP_LA_UNTOUCHED) atomicAdd(&local[CLAIR_CMP_LA_EXAMINED], 1u);
+        if (what == CLAIR_CMP_LA_IS_NO_SEQUENCE) atomicAdd(&local[CLAIR_CMP_LA_NO_SEQUENCE], 1u);
+        if (what == CLAIR_CMP_LA_IS_REF_MISMATCH) atomicAdd(&local[CLAIR_CMP_LA_REF_MISMATCH], 1u);
+        is_candidate[i] = what == CLAIR_CMP_LA_CANDIDATE;
+        if (what != CLAIR_CMP_LA_CANDIDATE) {
+            const uint32_t mine = slot[i];
+            clair_compare_la_copy(text, r, mine, arena);
+            rec[i].ref_off = mine;
+            rec[i].alt_off = mine + r.ref_len;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < LA_SUMS && local[threadIdx.x]) atomicAdd(&sums[threadIdx.x], (unsigned long long)local[threadIdx.x]);
+}
+
+// One wave per candidate.  Lane l of round s asks whether the event stops after s + l steps to the left; the ballot's lowest set bit is the
+// answer, and as the ballot is the same in every lane, so is the loop's exit: all 64 lanes reach every ballot.  Every read of the reference
+// is at a position >= 1 of the record's own contig (compare_core.h); every store is to the record's own slot, or lane 0's to its record.
+__global__ __launch_bounds__(64 * LA_WAVES) void shift_kernel(const uint8_t *text, clair_compare_reference ref, clair_compare_record *rec, const uint32_t *slot,
+                                                              const uint32_t *list, int64_t n_candidates, uint8_t *arena, unsigned long long *sums) {
+    const int lane = threadIdx.x & 63;
+    const int64_t c = (int64_t)blockIdx.x * LA_WAVES + (threadIdx.x >> 6);
+    if (c >= n_candidates) return;                 // the whole wave
+    const uint32_t i = list[c];
+    const clair_compare_record r = rec[i];
+    clair_compare_event ev;
+    if (clair_compare_la_case(ref, text, r, &ev) != CLAIR_CMP_LA_CANDIDATE) return;      // cannot be: the same function flagged it; the whole wave
+    const uint8_t *contig = ref.seq + ref.off[r.ctg];
+    int64_t steps = 0;
+    for (;;) {
+        const unsigned long long stops = __ballot(clair_compare_la_stops(contig, text, ev, steps + lane));
+        if (stops) { steps += __ffsll(stops) - 1; break; }
+        steps += 64;
+    }
+    const uint32_t ref_len = r.ref_len;
+    const bool ins = ref_len < r.alt_len;
+    const uint32_t mine = slot[i], at_short = ins ? mine : mine + ref_len, at_long = ins ? mine + ref_len : mine;
+    for (uint32_t k = lane; k <= ev.len; k += 64) arena[at_long + k] = clair_compare_la_long_byte(contig, text, ev, steps, k);
+    if (lane == 0) {
+        arena[at_short] = clair_compare_la_short_byte(contig, text, ev, steps);
+        rec[i].ref_off = mine;
+        rec[i].alt_off = mine + ref_len;
+        if (ev.a - steps < 1) atomicAdd(&sums[CLAIR_CMP_LA_AT_CONTIG_START], 1ull);
+        else if (ev.a - steps != r.pos) {
+            rec[i].pos = (int32_t)(ev.a - steps);
+            atomicAdd(&sums[CLAIR_CMP_LA_SHIFTED], 1ull);
+        }
+    }
 }
 
 __global__ __launch_bounds__(256) void keys_kernel(const clair_compare_record *rec, int64_t n, int64_t *keys) {
@@ -167,11 +262,13 @@ struct clair_compare {
     std::string error;
     int n_contigs = -1;
     DeviceBuffer d_names, d_name_off, d_first, d_starts, d_ends, d_counts, d_sums, d_scan, d_slot_scan, d_line_start, d_slots, d_kept, d_perm;
-    bool have_regions = false, ran = false;
+    DeviceBuffer d_ref, d_ref_off, d_arena_slot, d_candidate, d_candidates;      // left alignment: the reference; per record its slot and flag; the list
+    bool have_regions = false, have_reference = false, ran = false;
     struct SideState {
         DeviceBuffer d_text, d_rec, d_other, d_outcome;      // d_other: what _permute gathers into, then swapped with d_rec
-        int64_t n = 0, drops[3] = {0, 0, 0};
-        bool parsed = false, sorted = false;
+        DeviceBuffer d_arena;                                // the alleles of a left-aligned side: what its records point into then
+        int64_t n = 0, drops[3] = {0, 0, 0}, arena_bytes = 0;
+        bool parsed = false, sorted = false, aligned = false;
     } side[2];
 };
 
@@ -214,7 +311,25 @@ int clair_compare_set_contigs(clair_compare_t *h, const uint8_t *names, const in
     if (bytes) CLAIR_HIP_TRY(cmp_fail(h), hipMemcpy(h->d_names.p, names, bytes, hipMemcpyHostToDevice));
     CLAIR_HIP_TRY(cmp_fail(h), hipMemcpy(h->d_name_off.p, offsets, (size_t)(n_contigs + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
     h->n_contigs = n_contigs;
-    h->side[0].parsed = h->side[1].parsed = h->have_regions = h->ran = false;      // ids mean something else now
+    h->side[0].parsed = h->side[1].parsed = h->have_regions = h->have_reference = h->ran = false;      // ids mean something else now
+    return 0;
+}
+
+int clair_compare_set_reference(clair_compare_t *h, const uint8_t *seq, const int64_t *offsets, int n_contigs) {
+    if (!h) return cmp_fail(nullptr)("compare handle is NULL");
+    if (!offsets) return cmp_fail(h)("set_reference: bad arguments");
+    if (h->n_contigs < 0) return cmp_fail(h)("set_reference: set the contigs first");
+    if (n_contigs != h->n_contigs) return cmp_fail(h)("set_reference: %d contigs, the contig table has %d", n_contigs, h->n_contigs);
+    for (int k = 0; k < n_contigs; ++k) if (offsets[0] != 0 || offsets[k] > offsets[k + 1]) return cmp_fail(h)("set_reference: offsets must ascend from 0");
+    const size_t bytes = (size_t)offsets[n_contigs];
+    if (bytes && !seq) return cmp_fail(h)("set_reference: NULL sequence");
+    h->have_reference = false;
+    CLAIR_HIP_TRY(cmp_fail(h), hipSetDevice(h->device));
+    CLAIR_HIP_TRY(cmp_fail(h), h->d_ref.ensure(bytes));
+    CLAIR_HIP_TRY(cmp_fail(h), h->d_ref_off.ensure((size_t)(n_contigs + 1) * sizeof(int64_t)));
+    if (bytes) CLAIR_HIP_TRY(cmp_fail(h), hipMemcpy(h->d_ref.p, seq, bytes, hipMemcpyHostToDevice));
+    CLAIR_HIP_TRY(cmp_fail(h), hipMemcpy(h->d_ref_off.p, offsets, (size_t)(n_contigs + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+    h->have_reference = true;
     return 0;
 }
 
@@ -252,7 +367,7 @@ int clair_compare_parse(clair_compare_t *h, int side, const uint8_t *text, int64
     if (h->n_contigs < 0) return cmp_fail(h)("parse: set the contigs first");
     if (len > (int64_t)UINT32_MAX) return cmp_fail(h)("parse: the %s text has %lld bytes, the limit is 2^32 - 1", SIDE_NAME[side], (long long)len);
     clair_compare::SideState &s = h->side[side];
-    s.parsed = false;
+    s.parsed = s.aligned = false;
     h->ran = false;
     s.n = 0;
     s.drops[0] = s.drops[1] = s.drops[2] = 0;
@@ -303,7 +418,7 @@ int clair_compare_parse(clair_compare_t *h, int side, const uint8_t *text, int64
         // 4. are they in order as they stand
         if (n_rec > 1)
             hipLaunchKernelGGL(sorted_kernel, dim3(blocks_of(n_rec, 256)), dim3(256), 0, nullptr, (const clair_compare_record *)s.d_rec.as<clair_compare_record>(),
-                               (int64_t)n_rec, h->d_sums.as<unsigned long long>());
+                               (int64_t)n_rec, h->d_sums.as<unsigned long long>() + P_SORTED);
         CLAIR_HIP_TRY(cmp_fail(h), hipGetLastError());
         CLAIR_HIP_TRY(cmp_fail(h), hipMemcpy(sums, h->d_sums.p, sizeof sums, hipMemcpyDeviceToHost));
         if (sums[P_BAD] != NO_BAD_LINE)
@@ -315,6 +430,92 @@ int clair_compare_parse(clair_compare_t *h, int side, const uint8_t *text, int64
     s.parsed = true;
     const int64_t out[CLAIR_CMP_STATS] = {n_lines, (int64_t)sums[P_ROWS], s.n, s.drops[0], s.drops[1], s.drops[2], s.sorted ? 1 : 0, 0};
     for (int i = 0; i < CLAIR_CMP_STATS; ++i) stats[i] = out[i];
+    return 0;
+}
+
+int clair_compare_left_align(clair_compare_t *h, int side, int64_t *stats) {
+    using namespace clair_cmp;
+    using clair_scan::totals_kernel; using clair_scan::walk_kernel; using clair_scan::write_kernel;
+    using Totals = clair_scan::SumScan<uint32_t, uint32_t>;
+    if (!h) return cmp_fail(nullptr)("compare handle is NULL");
+    if (side < 0 || side > 1 || !stats || !h->side[side].parsed) return cmp_fail(h)("left_align: no parsed text on that side");
+    if (!h->have_reference) return cmp_fail(h)("left_align: set the reference first");
+    clair_compare::SideState &s = h->side[side];
+    if (s.aligned) return cmp_fail(h)("left_align: the %s are left-aligned already", SIDE_NAME[side]);
+    h->ran = false;
+    unsigned long long sums[LA_WORDS] = {0, 0, 0, 0, 0, 1};
+    uint32_t arena_bytes = 0;
+    if (s.n > 0) {
+        CLAIR_HIP_TRY(cmp_fail(h), hipSetDevice(h->device));
+        CLAIR_HIP_TRY(cmp_fail(h), h->d_sums.ensure(sizeof sums));
+        CLAIR_HIP_TRY(cmp_fail(h), hipMemcpy(h->d_sums.p, sums, sizeof sums, hipMemcpyHostToDevice));
+        clair_compare_record *rec = s.d_rec.as<clair_compare_record>();
+        const uint8_t *text = s.d_text.as<uint8_t>();
+        const clair_compare_reference ref{h->d_ref.as<uint8_t>(), h->d_ref_off.as<int64_t>()};
+        // a. the slots
+        const int64_t nb = (s.n + BLOCK - 1) / BLOCK;
+        CLAIR_HIP_TRY(cmp_fail(h), h->d_scan.ensure((size_t)(nb + 1) * sizeof(uint32_t)));
+        CLAIR_HIP_TRY(cmp_fail(h), h->d_slot_scan.ensure((size_t)(nb + 1) * sizeof(uint32_t)));
+        CLAIR_HIP_TRY(cmp_fail(h), h->d_arena_slot.ensure((size_t)s.n * sizeof(uint32_t)));
+        CLAIR_HIP_TRY(cmp_fail(h), h->d_candidate.ensure((size_t)s.n));
+        uint32_t *d_scan = h->d_scan.as<uint32_t>();
+        AlleleBytes lengths;
+        lengths.v = nullptr;
+        lengths.rec = rec;
+        hipLaunchKernelGGL((totals_kernel<AlleleBytes, ITEMS>), dim3((unsigned)nb), dim3(256), 0, nullptr, lengths, s.n, d_scan);
+        hipLaunchKernelGGL((walk_kernel<Totals, false>), dim3(1), dim3(256), 0, nullptr, Totals{d_scan}, nb, d_scan, d_scan + nb);
+        hipLaunchKernelGGL((write_kernel<AlleleBytes, ITEMS, WriteSlots>), dim3((unsigned)nb), dim3(256), 0, nullptr, lengths, s.n, (const uint32_t *)d_scan,
+                           WriteSlots{h->d_arena_slot.as<uint32_t>()});
+        CLAIR_HIP_TRY(cmp_fail(h), hipGetLastError());
+        CLAIR_HIP_TRY(cmp_fail(h), hipMemcpy(&arena_bytes, d_scan + nb, sizeof arena_bytes, hipMemcpyDeviceToHost));
+        if (arena_bytes < (uint64_t)s.n || (uint64_t)arena_bytes > (uint64_t)s.n * 2 * 65535)
+            return cmp_fail(h)("left_align: %u allele bytes in %lld records: the slot scan is broken", arena_bytes, (long long)s.n);
+        CLAIR_HIP_TRY(cmp_fail(h), s.d_arena.ensure((size_t)arena_bytes));
+        // b. the cases; c. the candidates in record order
+        hipLaunchKernelGGL(la_case_kernel, dim3(blocks_of(s.n, 256)), dim3(256), 0, nullptr, text, ref, rec, s.n, (const uint32_t *)h->d_arena_slot.as<uint32_t>(),
+                           s.d_arena.as<uint8_t>(), h->d_candidate.as<uint8_t>(), h->d_sums.as<unsigned long long>());
+        d_scan = h->d_slot_scan.as<uint32_t>();
+        const CandidateScan flags{{h->d_candidate.as<uint8_t>()}};
+        hipLaunchKernelGGL((totals_kernel<CandidateScan, ITEMS>), dim3((unsigned)nb), dim3(256), 0, nullptr, flags, s.n, d_scan);
+        hipLaunchKernelGGL((walk_kernel<Totals, false>), dim3(1), dim3(256), 0, nullptr, Totals{d_scan}, nb, d_scan, d_scan + nb);
+        CLAIR_HIP_TRY(cmp_fail(h), hipGetLastError());
+        uint32_t n_candidates = 0;
+        CLAIR_HIP_TRY(cmp_fail(h), hipMemcpy(&n_candidates, d_scan + nb, sizeof n_candidates, hipMemcpyDeviceToHost));
+        if ((int64_t)n_candidates > s.n) return cmp_fail(h)("left_align: %u candidates among %lld records: the candidate scan is broken", n_candidates, (long long)s.n);
+        if (n_candidates) {
+            CLAIR_HIP_TRY(cmp_fail(h), h->d_candidates.ensure((size_t)n_candidates * sizeof(uint32_t)));
+            hipLaunchKernelGGL((write_kernel<CandidateScan, ITEMS, WriteCandidates>), dim3((unsigned)nb), dim3(256), 0, nullptr, flags, s.n, (const uint32_t *)d_scan,
+                               WriteCandidates{h->d_candidates.as<uint32_t>()});
+            // d. one wave per candidate
+            hipLaunchKernelGGL(shift_kernel, dim3(blocks_of(n_candidates, LA_WAVES)), dim3(64 * LA_WAVES), 0, nullptr, text, ref, rec,
+                               (const uint32_t *)h->d_arena_slot.as<uint32_t>(), (const uint32_t *)h->d_candidates.as<uint32_t>(), (int64_t)n_candidates,
+                               s.d_arena.as<uint8_t>(), h->d_sums.as<unsigned long long>());
+        }
+        // e. the order as it is now
+        if (s.n > 1)
+            hipLaunchKernelGGL(sorted_kernel, dim3(blocks_of(s.n, 256)), dim3(256), 0, nullptr, (const clair_compare_record *)rec, s.n,
+                               h->d_sums.as<unsigned long long>() + LA_IN_ORDER);
+        CLAIR_HIP_TRY(cmp_fail(h), hipGetLastError());
+        CLAIR_HIP_TRY(cmp_fail(h), hipMemcpy(sums, h->d_sums.p, sizeof sums, hipMemcpyDeviceToHost));
+    }
+    s.arena_bytes = arena_bytes;
+    s.aligned = true;
+    s.sorted = sums[LA_IN_ORDER] != 0;
+    for (int i = 0; i < LA_SUMS; ++i) stats[i] = (int64_t)sums[i];
+    stats[CLAIR_CMP_LA_SORTED] = s.sorted ? 1 : 0;
+    stats[CLAIR_CMP_LA_ARENA] = arena_bytes;
+    stats[7] = 0;
+    return 0;
+}
+
+int clair_compare_allele_text(clair_compare_t *h, int side, uint8_t *out) {
+    if (!h) return cmp_fail(nullptr)("compare handle is NULL");
+    if (side < 0 || side > 1 || !h->side[side].parsed || !h->side[side].aligned) return cmp_fail(h)("allele_text: that side was not left-aligned");
+    clair_compare::SideState &s = h->side[side];
+    if (s.arena_bytes == 0) return 0;
+    if (!out) return cmp_fail(h)("allele_text: NULL argument");
+    CLAIR_HIP_TRY(cmp_fail(h), hipSetDevice(h->device));
+    CLAIR_HIP_TRY(cmp_fail(h), hipMemcpy(out, s.d_arena.p, (size_t)s.arena_bytes, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -359,7 +560,7 @@ int clair_compare_permute(clair_compare_t *h, int side, const int64_t *perm) {
     hipLaunchKernelGGL(gather_kernel, dim3(blocks_of(s.n, 256)), dim3(256), 0, nullptr, (const clair_compare_record *)s.d_rec.as<clair_compare_record>(),
                        (const int64_t *)h->d_perm.as<int64_t>(), s.n, s.d_other.as<clair_compare_record>());
     hipLaunchKernelGGL(sorted_kernel, dim3(blocks_of(s.n, 256)), dim3(256), 0, nullptr, (const clair_compare_record *)s.d_other.as<clair_compare_record>(), s.n,
-                       h->d_sums.as<unsigned long long>());
+                       h->d_sums.as<unsigned long long>() + P_SORTED);
     CLAIR_HIP_TRY(cmp_fail(h), hipGetLastError());
     CLAIR_HIP_TRY(cmp_fail(h), hipMemcpy(sums, h->d_sums.p, sizeof sums, hipMemcpyDeviceToHost));
     std::swap(s.d_rec.p, s.d_other.p);
@@ -382,7 +583,7 @@ int clair_compare_run(clair_compare_t *h) {
     for (int k = 0; k < 2; ++k) {
         clair_compare::SideState &s = h->side[k];
         CLAIR_HIP_TRY(cmp_fail(h), s.d_outcome.ensure((size_t)s.n));
-        sd[k] = Side{s.d_text.as<uint8_t>(), s.d_rec.as<clair_compare_record>(), s.d_outcome.as<uint8_t>(), s.n};
+        sd[k] = Side{s.aligned ? s.d_arena.as<uint8_t>() : s.d_text.as<uint8_t>(), s.d_rec.as<clair_compare_record>(), s.d_outcome.as<uint8_t>(), s.n};
     }
     const Side calls = sd[CLAIR_CMP_CALLS], truth = sd[CLAIR_CMP_TRUTH];
     const clair_compare_regions regions{h->have_regions ? h->d_first.as<int64_t>() : nullptr, h->d_starts.as<int64_t>(), h->d_ends.as<int64_t>()};

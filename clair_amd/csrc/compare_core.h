@@ -1,6 +1,7 @@
 // The rule of compare_vcf (docs/compare_vcf.md), as the code both sides run: the device kernels of csrc/compare.hip and the sequential host
 // twin (hostsrc/host_compare.cpp).  Everything here works on the text where it lies -- a record holds offsets into its side's text, and
-// nothing is copied -- and in integers only.
+// nothing is copied -- and in integers only.  The one pass that copies is left alignment (the end of this file): a left-aligned allele is in
+// general no substring of the text, so after it a side's offsets index an allele arena instead, which the join receives as its `text`.
 #pragma once
 #include <stdint.h>
 
@@ -42,6 +43,10 @@ enum { CLAIR_CMP_ROW_SKIP = 0, CLAIR_CMP_ROW_DATA = 1, CLAIR_CMP_BAD_COLUMNS = 2
 // what became of a record slot of a row: none, kept, or dropped and counted
 enum { CLAIR_CMP_SLOT_NONE = 0, CLAIR_CMP_SLOT_KEPT = 1, CLAIR_CMP_SLOT_SYMBOLIC = 2, CLAIR_CMP_SLOT_CONTIG = 3, CLAIR_CMP_SLOT_LONG = 4 };
 enum { CLAIR_CMP_STATS = 8 };      // _parse: lines, rows, records, symbolic, unknown_contig, too_long, sorted, 0
+// _left_align: its stats[8], and what the pass makes of a record
+enum { CLAIR_CMP_LA_EXAMINED = 0, CLAIR_CMP_LA_SHIFTED = 1, CLAIR_CMP_LA_REF_MISMATCH = 2, CLAIR_CMP_LA_AT_CONTIG_START = 3, CLAIR_CMP_LA_NO_SEQUENCE = 4,
+       CLAIR_CMP_LA_SORTED = 5, CLAIR_CMP_LA_ARENA = 6 };
+enum { CLAIR_CMP_LA_UNTOUCHED = 0, CLAIR_CMP_LA_IS_NO_SEQUENCE = 1, CLAIR_CMP_LA_IS_REF_MISMATCH = 2, CLAIR_CMP_LA_COMPLEX = 3, CLAIR_CMP_LA_CANDIDATE = 4 };
 #define CLAIR_CMP_MAX_POS 2000000000
 
 CLAIR_CMP_HD const char *clair_compare_row_error(int code) {
@@ -271,4 +276,70 @@ CLAIR_CMP_HD int64_t clair_compare_find(const clair_compare_record *truth, int64
     for (; lo < n_truth && clair_compare_key(truth[lo]) == key; ++lo)
         if (clair_compare_same_alleles(truth_text, truth[lo], call_text, call)) return lo;
     return -1;
+}
+
+// -- left alignment (docs/compare_vcf.md, "Left alignment"): per record, after the trimming and before order, duplicates, regions and join ------
+// the sequences of the contig table one after the other: contig k = seq[off[k] .. off[k + 1]), an empty range = no sequence loaded
+struct clair_compare_reference {
+    const uint8_t *seq;
+    const int64_t *off;        // [n + 1]
+};
+// an indel whose shorter allele is one byte b, at text[b_off], and whose longer one is W of len + 1 bytes, at text[w_off]: the len event bytes X
+// start at text[x_off], and the anchor, the base before the event, is at the 1-based position a of the contig (0: before its first base).
+// With V = G[1 .. a] ++ X the event may move left while V[a + len - j] == V[a - j].
+struct clair_compare_event {
+    int64_t a;
+    uint32_t x_off, len, w_off, b_off;
+};
+
+// What the pass makes of a record.  Not an indel: not examined.  Then the first that applies: no sequence for its contig; REF differs from the
+// reference at pos, or lies outside the contig; the closed form does not apply (the literal loop of the docs leaves such a record as it is);
+// otherwise a candidate for the run search, with *ev set.
+CLAIR_CMP_HD int clair_compare_la_case(const clair_compare_reference &g, const uint8_t *t, const clair_compare_record &r, clair_compare_event *ev) {
+    const uint32_t ref_len = r.ref_len, alt_len = r.alt_len, ref_off = r.ref_off, alt_off = r.alt_off;
+    const int64_t pos = r.pos;
+    if (ref_len == alt_len) return CLAIR_CMP_LA_UNTOUCHED;
+    const int64_t at = g.off[r.ctg], len = g.off[r.ctg + 1] - at;
+    if (len == 0) return CLAIR_CMP_LA_IS_NO_SEQUENCE;
+    if (pos < 1 || pos - 1 + ref_len > len) return CLAIR_CMP_LA_IS_REF_MISMATCH;
+    for (uint32_t i = 0; i < ref_len; ++i)
+        if (clair_compare_upper(t[ref_off + i]) != clair_compare_upper(g.seq[at + pos - 1 + i])) return CLAIR_CMP_LA_IS_REF_MISMATCH;
+    const bool ins = ref_len < alt_len;
+    if ((ins ? ref_len : alt_len) != 1) return CLAIR_CMP_LA_COMPLEX;
+    const uint32_t w = ins ? alt_off : ref_off, n = (ins ? alt_len : ref_len) - 1u, b_off = ins ? ref_off : alt_off;
+    const uint8_t b = clair_compare_upper(t[b_off]);
+    const bool at_end = clair_compare_upper(t[w + n]) == b;      // W ends in b: X = W[0 .. n - 1] behind the anchor at pos - 1; else W begins with b
+    if (!at_end && clair_compare_upper(t[w]) != b) return CLAIR_CMP_LA_COMPLEX;
+    ev->a = pos - (at_end ? 1 : 0);
+    ev->x_off = w + (at_end ? 0u : 1u);
+    ev->len = n;
+    ev->w_off = w;
+    ev->b_off = b_off;
+    return CLAIR_CMP_LA_CANDIDATE;
+}
+
+// V[i], upper-cased, for 1 <= i <= a + len; contig = where the record's own contig starts in the reference, so no other contig is ever read
+CLAIR_CMP_HD uint8_t clair_compare_la_v(const uint8_t *contig, const uint8_t *t, const clair_compare_event &ev, int64_t i) {
+    return clair_compare_upper(i <= ev.a ? contig[i - 1] : t[ev.x_off + (i - ev.a - 1)]);
+}
+
+// does the event stop after j steps to the left: the contig's start is reached, or the bytes differ
+CLAIR_CMP_HD bool clair_compare_la_stops(const uint8_t *contig, const uint8_t *t, const clair_compare_event &ev, int64_t j) {
+    return ev.a - j < 1 || clair_compare_la_v(contig, t, ev, ev.a + ev.len - j) != clair_compare_la_v(contig, t, ev, ev.a - j);
+}
+
+// The alleles of a candidate that stopped after `steps`.  a - steps < 1 is at_contig_start: it keeps its own bytes.  Otherwise the anchor
+// G[a - steps] is the shorter allele and the first byte of the longer one, and the event bytes behind it are V[a - steps + 1 ..].
+CLAIR_CMP_HD uint8_t clair_compare_la_long_byte(const uint8_t *contig, const uint8_t *t, const clair_compare_event &ev, int64_t steps, uint32_t k) {
+    return ev.a - steps < 1 ? clair_compare_upper(t[ev.w_off + k]) : clair_compare_la_v(contig, t, ev, ev.a - steps + k);
+}
+CLAIR_CMP_HD uint8_t clair_compare_la_short_byte(const uint8_t *contig, const uint8_t *t, const clair_compare_event &ev, int64_t steps) {
+    return ev.a - steps < 1 ? clair_compare_upper(t[ev.b_off]) : clair_compare_la_v(contig, t, ev, ev.a - steps);
+}
+
+// a record the pass leaves as it is: its alleles go upper-cased to its slot of the arena, REF first, ALT behind it
+CLAIR_CMP_HD void clair_compare_la_copy(const uint8_t *t, const clair_compare_record &r, uint32_t slot, uint8_t *arena) {
+    const uint32_t ref_len = r.ref_len, alt_len = r.alt_len, ref_off = r.ref_off, alt_off = r.alt_off;
+    for (uint32_t i = 0; i < ref_len; ++i) arena[slot + i] = clair_compare_upper(t[ref_off + i]);
+    for (uint32_t i = 0; i < alt_len; ++i) arena[slot + ref_len + i] = clair_compare_upper(t[alt_off + i]);
 }

@@ -72,8 +72,11 @@ int train_init(clair_trainer *t) {
     t->n_params = t->offset[N_TENSORS];
     for (DeviceBuffer &b : t->sets) {
         CLAIR_HIP_TRY(train_fail(nullptr), b.ensure((size_t)t->n_params * 4));
-        CLAIR_HIP_TRY(train_fail(nullptr), hipMemset(b.p, 0, (size_t)t->n_params * 4));
+        // on the handle's own stream: it does not wait for the null stream, where a hipMemset could still be clearing the weights after
+        // the first clair_train_set_tensor has written them
+        CLAIR_HIP_TRY(train_fail(nullptr), hipMemsetAsync(b.p, 0, (size_t)t->n_params * 4, t->stream));
     }
+    CLAIR_HIP_TRY(train_fail(nullptr), hipStreamSynchronize(t->stream));
     const size_t cap = (size_t)t->cap, F = sizeof(float);
     struct { DeviceBuffer *b; size_t per_row; } plan[] = {
         {&t->x, T_STEPS * 32 * F}, {&t->xt, T_STEPS * 32 * F},

@@ -1,6 +1,7 @@
 // Host-side helpers of the Clair hot path (include/clair_host.h): compare_vcf's parse, join and counting, the twin of the device's
 // (clair_amd/csrc/compare.hip).  Plain C++17, no HIP.  The rule itself is csrc/compare_core.h, the code the kernels run; this is the same
-// passes as sequential loops, entry point for entry point.  The texts are borrowed: they stay the caller's until the handle is destroyed.
+// passes as sequential loops, entry point for entry point.  The texts and the reference are borrowed: they stay the caller's until the handle
+// is destroyed.
 #include "../../include/clair_host.h"
 #include "../csrc/compare_core.h"
 
@@ -14,8 +15,12 @@ struct clair_host_compare {
     std::vector<uint8_t> names;
     std::vector<int64_t> name_off, first, starts, ends;
     bool have_regions = false;
+    const uint8_t *ref_seq = nullptr;
+    std::vector<int64_t> ref_off;             // empty: no reference set
     struct Side {
-        const uint8_t *text = nullptr;
+        const uint8_t *text = nullptr;        // what the records point into: the parsed text, or the arena once the side is left-aligned
+        std::vector<uint8_t> arena;
+        bool aligned = false;
         std::vector<clair_compare_record> rec;
         std::vector<uint8_t> outcome;
         int64_t drops[3] = {0, 0, 0};
@@ -52,6 +57,18 @@ int clair_host_compare_set_contigs(clair_host_compare_t *h, const uint8_t *names
     h->name_off.assign(offsets, offsets + n_contigs + 1);
     h->names.assign(names, names + offsets[n_contigs]);
     h->side[0].parsed = h->side[1].parsed = h->have_regions = h->ran = false;      // ids mean something else now
+    h->ref_off.clear();
+    return 0;
+}
+
+int clair_host_compare_set_reference(clair_host_compare_t *h, const uint8_t *seq, const int64_t *offsets, int n_contigs) {
+    if (!h || !offsets) return clair_host_fail("compare set_reference: bad arguments");
+    if (h->name_off.empty()) return clair_host_fail("compare set_reference: set the contigs first");
+    if (n_contigs != (int)h->name_off.size() - 1) return clair_host_fail("compare set_reference: %d contigs, the contig table has %d", n_contigs, (int)h->name_off.size() - 1);
+    for (int k = 0; k < n_contigs; ++k) if (offsets[0] != 0 || offsets[k] > offsets[k + 1]) return clair_host_fail("compare set_reference: offsets must ascend from 0");
+    if (offsets[n_contigs] > 0 && !seq) return clair_host_fail("compare set_reference: NULL sequence");
+    h->ref_seq = seq;
+    h->ref_off.assign(offsets, offsets + n_contigs + 1);
     return 0;
 }
 
@@ -83,6 +100,8 @@ int clair_host_compare_parse(clair_host_compare_t *h, int side, const uint8_t *t
     s.parsed = false;
     h->ran = false;
     s.text = text;
+    s.aligned = false;
+    s.arena.clear();
     s.rec.clear();
     s.drops[0] = s.drops[1] = s.drops[2] = 0;
     const clair_compare_contigs contigs{h->names.data(), h->name_off.data(), (int32_t)h->name_off.size() - 1};
@@ -105,6 +124,63 @@ int clair_host_compare_parse(clair_host_compare_t *h, int side, const uint8_t *t
     s.parsed = true;
     const int64_t out[CLAIR_CMP_STATS] = {lines, rows, (int64_t)s.rec.size(), s.drops[0], s.drops[1], s.drops[2], s.sorted ? 1 : 0, 0};
     memcpy(stats, out, sizeof out);
+    return 0;
+}
+
+int clair_host_compare_left_align(clair_host_compare_t *h, int side, int64_t *stats) {
+    if (!h || side < 0 || side > 1 || !stats || !h->side[side].parsed) return clair_host_fail("compare left_align: no parsed text on that side");
+    if (h->ref_off.empty()) return clair_host_fail("compare left_align: set the reference first");
+    clair_host_compare::Side &s = h->side[side];
+    if (s.aligned) return clair_host_fail("compare left_align: the %s are left-aligned already", SIDE_NAME[side]);
+    h->ran = false;
+    const clair_compare_reference g{h->ref_seq, h->ref_off.data()};
+    int64_t out[CLAIR_CMP_STATS] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint64_t bytes = 0;
+    for (const clair_compare_record &r : s.rec) bytes += (uint64_t)r.ref_len + r.alt_len;
+    s.arena.assign((size_t)bytes, 0);
+    uint32_t slot = 0;
+    for (clair_compare_record &r : s.rec) {
+        const uint32_t mine = slot;
+        slot += (uint32_t)r.ref_len + r.alt_len;
+        clair_compare_event ev;
+        const int what = clair_compare_la_case(g, s.text, r, &ev);
+        out[CLAIR_CMP_LA_EXAMINED] += what != CLAIR_CMP_LA_UNTOUCHED;
+        out[CLAIR_CMP_LA_NO_SEQUENCE] += what == CLAIR_CMP_LA_IS_NO_SEQUENCE;
+        out[CLAIR_CMP_LA_REF_MISMATCH] += what == CLAIR_CMP_LA_IS_REF_MISMATCH;
+        const bool ins = r.ref_len < r.alt_len;
+        if (what != CLAIR_CMP_LA_CANDIDATE) clair_compare_la_copy(s.text, r, mine, s.arena.data());
+        else {
+            const uint8_t *contig = g.seq + g.off[r.ctg];
+            int64_t steps = 0;
+            while (!clair_compare_la_stops(contig, s.text, ev, steps)) ++steps;
+            const uint32_t at_short = ins ? mine : mine + r.ref_len, at_long = ins ? mine + r.ref_len : mine;
+            for (uint32_t k = 0; k <= ev.len; ++k) s.arena[at_long + k] = clair_compare_la_long_byte(contig, s.text, ev, steps, k);
+            s.arena[at_short] = clair_compare_la_short_byte(contig, s.text, ev, steps);
+            if (ev.a - steps < 1) ++out[CLAIR_CMP_LA_AT_CONTIG_START];
+            else {
+                out[CLAIR_CMP_LA_SHIFTED] += ev.a - steps != r.pos;
+                r.pos = (int32_t)(ev.a - steps);
+            }
+        }
+        r.ref_off = mine;
+        r.alt_off = mine + r.ref_len;
+    }
+    s.text = s.arena.data();
+    s.aligned = true;
+    s.sorted = keys_ascend(s.rec);
+    out[CLAIR_CMP_LA_SORTED] = s.sorted ? 1 : 0;
+    out[CLAIR_CMP_LA_ARENA] = (int64_t)bytes;
+    memcpy(stats, out, sizeof out);
+    return 0;
+}
+
+int clair_host_compare_allele_text(clair_host_compare_t *h, int side, uint8_t *out) {
+    if (!h || side < 0 || side > 1 || !h->side[side].parsed || !h->side[side].aligned) return clair_host_fail("compare allele_text: that side was not left-aligned");
+    const clair_host_compare::Side &s = h->side[side];
+    if (!s.arena.empty()) {
+        if (!out) return clair_host_fail("compare allele_text: NULL argument");
+        memcpy(out, s.arena.data(), s.arena.size());
+    }
     return 0;
 }
 

@@ -599,6 +599,18 @@ int clair_compare_permute(clair_compare_t *h, int side, const int64_t *perm);
 int clair_compare_run(clair_compare_t *h);
 int clair_compare_counts(clair_compare_t *h, int64_t *counts);
 int clair_compare_records(clair_compare_t *h, int side, clair_compare_record_t *records, uint8_t *outcomes);
+/* Left alignment of indels (compare_vcf --left_align; docs/compare_vcf.md, "Left alignment"), opt-in: without these calls nothing changes.
+ * _set_reference: the sequences of the contig table one after the other, contig k = seq[offsets[k] .. offsets[k + 1]), offsets
+ *   [n_contigs + 1] with n_contigs that of _set_contigs; an empty range: no sequence for that contig.  Copied to the device.  Any time after
+ *   _set_contigs and before _left_align.
+ * _left_align: after _parse of that side, before _keys / _permute / _run, once per parse.  Every record's alleles go upper-cased to an
+ *   allele arena the handle owns (record i of the order they have at slot sum_{j<i} (ref_len_j + alt_len_j), REF first), indels move to
+ *   their leftmost position, and from here on ref_off / alt_off index the arena.  stats [8] = examined, shifted, ref_mismatch,
+ *   at_contig_start, no_sequence, sorted (the order flag on the new positions: it supersedes _parse's), arena bytes, 0.
+ * _allele_text: the arena of a left-aligned side (stats[6] bytes). */
+int clair_compare_set_reference(clair_compare_t *h, const uint8_t *seq, const int64_t *offsets, int n_contigs);
+int clair_compare_left_align(clair_compare_t *h, int side, int64_t *stats);
+int clair_compare_allele_text(clair_compare_t *h, int side, uint8_t *out);
 
 #ifdef __cplusplus
 }

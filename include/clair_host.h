@@ -336,6 +336,10 @@ int clair_host_compare_permute(clair_host_compare_t *h, int side, const int64_t 
 int clair_host_compare_run(clair_host_compare_t *h);
 int clair_host_compare_counts(clair_host_compare_t *h, int64_t *counts);
 int clair_host_compare_records(clair_host_compare_t *h, int side, clair_compare_record_t *records, uint8_t *outcomes);
+/* left alignment, as clair_compare_set_reference / _left_align / _allele_text; the reference is borrowed like the texts */
+int clair_host_compare_set_reference(clair_host_compare_t *h, const uint8_t *seq, const int64_t *offsets, int n_contigs);
+int clair_host_compare_left_align(clair_host_compare_t *h, int side, int64_t *stats);
+int clair_host_compare_allele_text(clair_host_compare_t *h, int side, uint8_t *out);
 
 #ifdef __cplusplus
 }
