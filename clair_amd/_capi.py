@@ -151,6 +151,8 @@ SIGNATURES = {
     "clair_train_read_mask": _sig(c_vp, c_int, c_vp, c_i64),
     "clair_train_probabilities": _sig(c_vp, c_vp),
     "clair_train_accuracy": _sig(c_vp, c_vp),
+    "clair_train_debug_gemm": _sig(c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp),
+    "clair_train_debug_column_sum": _sig(c_vp, c_vp, c_i64, c_i64, c_int, c_i64, c_vp, c_i64, c_int, c_int, c_int),
 }
 SYMBOLS = tuple(SIGNATURES)
 ENSEMBLE_MAX_MODELS = 8                                      # CLAIR_ENSEMBLE_MAX_MODELS
@@ -983,6 +985,29 @@ class Trainer(DeviceHandle):
         tp = np.zeros(4, dtype=np.int64)
         self._check(self._lib.clair_train_accuracy(self._h, _ptr(tp)), "clair_train_accuracy")
         return tp
+
+    # -- kernel taps for tests (tests/test_train_kernels_gpu.py): the library checks every address before it launches anything ------------
+    def debug_gemm(self, a, b, c, dims, strides, bias=None):
+        """One tgemm launch: a, b, c (and bias) flat float32 arrays, dims (M, N, K, batch, accumulate), strides (sam, sak, sbk, sbn, scm, scn,
+        ba, bb, bc, bbias) in elements -> the whole of c after the launch, a new array (c itself is left as it is)."""
+        a, b = (np.ascontiguousarray(v, dtype=np.float32).ravel() for v in (a, b))
+        out = np.array(c, dtype=np.float32, order="C").ravel()
+        bias = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32).ravel()
+        dims, strides = np.ascontiguousarray(dims, dtype=np.int64), np.ascontiguousarray(strides, dtype=np.int64)
+        if dims.shape != (5,) or strides.shape != (10,):
+            raise ValueError("debug_gemm: 5 dims and 10 strides expected, got %r and %r" % (dims.shape, strides.shape))
+        self._check(self._lib.clair_train_debug_gemm(self._h, _ptr(a), a.size, _ptr(b), b.size, None if bias is None else _ptr(bias), 0 if bias is None else bias.size,
+                                                     _ptr(out), out.size, _ptr(dims), _ptr(strides)), "clair_train_debug_gemm")
+        return out
+
+    def debug_column_sum(self, x, rows, cols, ld, out, d=1, s1=1, s2=0):
+        """One column_sum_kernel launch: out[(j // d) * s1 + (j % d) * s2] += sum over r < rows of x[r * ld + j], j < cols; x and out flat
+        float32 arrays -> the whole of out after the launch, a new array."""
+        x = np.ascontiguousarray(x, dtype=np.float32).ravel()
+        got = np.array(out, dtype=np.float32, order="C").ravel()
+        self._check(self._lib.clair_train_debug_column_sum(self._h, _ptr(x), x.size, int(rows), int(cols), int(ld), _ptr(got), got.size, int(d), int(s1), int(s2)),
+                    "clair_train_debug_column_sum")
+        return got
 
 
 def overlap_keep(spans, device=0):

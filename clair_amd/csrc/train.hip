@@ -49,6 +49,7 @@ struct clair_trainer {
     DeviceBuffer sets[4];                                  // weights, gradients, m | momentum, v
     DeviceBuffer x, xt, z1, c1, a1, z2, c2, a2, a2d, da2, da1, dhrec, dc, l3, dl3, y4, d4, dd4, y5, d5, dd5, lg, probs, dz;
     DeviceBuffer m_lstm2, m4, m5, labels, row_loss, sums, partial, stats, tp;
+    DeviceBuffer dbg_a, dbg_b, dbg_bias, dbg_c;            // operands of clair_train_debug_gemm / _debug_column_sum, allocated on their first call
     std::string error;
 };
 
@@ -430,6 +431,90 @@ int clair_train_accuracy(clair_trainer_t *t, int64_t *tp) {
     CLAIR_HIP_TRY(train_fail(t), hipMemsetAsync(t->tp.p, 0, 4 * sizeof(int64_t), t->stream));
     LAUNCH(t, accuracy_kernel, t->last_n, t->probs.as<float>(), t->labels.as<uint8_t>(), t->last_n, t->tp.as<unsigned long long>());
     CLAIR_HIP_TRY(train_fail(t), hipMemcpyAsync(tp, t->tp.p, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, t->stream));
+    CLAIR_HIP_TRY(train_fail(t), hipStreamSynchronize(t->stream));
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- kernel taps for tests (include/clair_amd.h): these checks are all that stands between a test's typo and an access outside a buffer ----
+namespace {
+
+constexpr int64_t DEBUG_MAX_DIM = 1 << 20, DEBUG_MAX_BATCH = 65535, DEBUG_MAX_COUNT = 1 << 28;     // (extent - 1) * stride < 2^56: no index sum below can overflow
+
+int debug_range(clair_trainer *t, const char *what, const char *name, int64_t v, int64_t lo, int64_t hi) {
+    if (v < lo || v > hi) return train_fail(t)("%s: %s is %lld: %lld .. %lld", what, name, (long long)v, (long long)lo, (long long)hi);
+    return 0;
+}
+
+// the operand's largest element index, the sum over (extent - 1) * stride of its three axes, must lie inside its `count` elements
+int debug_operand(clair_trainer *t, const char *what, const char *name, const void *host, int64_t count, const int64_t (&extent)[3], const int64_t (&stride)[3],
+                  const char *const (&stride_name)[3]) {
+    if (!host) return train_fail(t)("%s: %s is NULL", what, name);
+    if (count < 1 || count > DEBUG_MAX_COUNT) return train_fail(t)("%s: %s has %lld elements: 1 .. %lld", what, name, (long long)count, (long long)DEBUG_MAX_COUNT);
+    int64_t last = 0;
+    for (int i = 0; i < 3; ++i) {
+        if (stride[i] < 0 || stride[i] > DEBUG_MAX_COUNT)
+            return train_fail(t)("%s: %s: stride %s is %lld: 0 .. %lld", what, name, stride_name[i], (long long)stride[i], (long long)DEBUG_MAX_COUNT);
+        last += (extent[i] - 1) * stride[i];
+    }
+    if (last >= count) return train_fail(t)("%s: %s: the largest element index %lld is outside its %lld elements", what, name, (long long)last, (long long)count);
+    return 0;
+}
+
+int debug_upload(clair_trainer *t, DeviceBuffer &buf, const float *host, int64_t count) {
+    CLAIR_HIP_TRY(train_fail(t), buf.ensure((size_t)count * 4));
+    CLAIR_HIP_TRY(train_fail(t), hipMemcpyAsync(buf.p, host, (size_t)count * 4, hipMemcpyHostToDevice, t->stream));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int clair_train_debug_gemm(clair_trainer_t *t, const float *a, int64_t a_count, const float *b, int64_t b_count, const float *bias, int64_t bias_count,
+                           float *c, int64_t c_count, const int64_t *dims, const int64_t *strides) {
+    const char *what = "clair_train_debug_gemm";
+    if (!t) return train_fail(nullptr)("trainer handle is NULL");
+    if (!dims) return train_fail(t)("%s: dims is NULL", what);
+    if (!strides) return train_fail(t)("%s: strides is NULL", what);
+    const int64_t M = dims[0], N = dims[1], K = dims[2], batch = dims[3], accumulate = dims[4];
+    if (debug_range(t, what, "M", M, 1, DEBUG_MAX_DIM) || debug_range(t, what, "N", N, 1, DEBUG_MAX_DIM) || debug_range(t, what, "K", K, 1, DEBUG_MAX_DIM) ||
+        debug_range(t, what, "batch", batch, 1, DEBUG_MAX_BATCH) || debug_range(t, what, "accumulate", accumulate, 0, 1))
+        return 1;
+    const int64_t sam = strides[0], sak = strides[1], sbk = strides[2], sbn = strides[3], scm = strides[4], scn = strides[5], ba = strides[6], bb = strides[7],
+                  bc = strides[8], bbias = strides[9];
+    if (debug_operand(t, what, "A", a, a_count, {M, K, batch}, {sam, sak, ba}, {"sam", "sak", "ba"})) return 1;
+    if (debug_operand(t, what, "B", b, b_count, {K, N, batch}, {sbk, sbn, bb}, {"sbk", "sbn", "bb"})) return 1;
+    if (debug_operand(t, what, "C", c, c_count, {M, N, batch}, {scm, scn, bc}, {"scm", "scn", "bc"})) return 1;
+    if (!bias && bias_count != 0) return train_fail(t)("%s: bias is NULL with bias_count %lld", what, (long long)bias_count);
+    if (bias ? debug_operand(t, what, "bias", bias, bias_count, {N, batch, 1}, {1, bbias, 0}, {"1", "bbias", "0"}) : debug_range(t, what, "bbias", bbias, 0, DEBUG_MAX_COUNT))
+        return 1;
+    CLAIR_HIP_TRY(train_fail(t), hipSetDevice(t->device));
+    if (debug_upload(t, t->dbg_a, a, a_count) || debug_upload(t, t->dbg_b, b, b_count) || debug_upload(t, t->dbg_c, c, c_count)) return 1;
+    if (bias && debug_upload(t, t->dbg_bias, bias, bias_count)) return 1;
+    GemmArgs g = gemm(t->dbg_a.as<float>(), sam, sak, t->dbg_b.as<float>(), sbk, sbn, t->dbg_c.as<float>(), scm, (int)M, (int)N, (int)K,
+                      bias ? t->dbg_bias.as<float>() : nullptr, (int)accumulate);
+    g.scn = scn; g.ba = ba; g.bb = bb; g.bc = bc; g.bbias = bbias;
+    CLAIR_HIP_TRY(train_fail(t), tgemm(t->stream, g, (int)batch));
+    CLAIR_HIP_TRY(train_fail(t), hipMemcpyAsync(c, t->dbg_c.p, (size_t)c_count * 4, hipMemcpyDeviceToHost, t->stream));
+    CLAIR_HIP_TRY(train_fail(t), hipStreamSynchronize(t->stream));
+    return 0;
+}
+
+int clair_train_debug_column_sum(clair_trainer_t *t, const float *x, int64_t x_count, int64_t rows, int cols, int64_t ld, float *out, int64_t out_count,
+                                 int d, int s1, int s2) {
+    const char *what = "clair_train_debug_column_sum";
+    if (!t) return train_fail(nullptr)("trainer handle is NULL");
+    if (debug_range(t, what, "rows", rows, 1, DEBUG_MAX_COUNT) || debug_range(t, what, "cols", cols, 1, DEBUG_MAX_DIM) || debug_range(t, what, "d", d, 1, DEBUG_MAX_COUNT))
+        return 1;
+    if (debug_operand(t, what, "x", x, x_count, {rows, cols, 1}, {ld, 1, 0}, {"ld", "1", "0"})) return 1;
+    // column j goes to (j / d) * s1 + (j % d) * s2: no j has a larger quotient than cols - 1 or a larger remainder than min(d, cols) - 1
+    if (debug_operand(t, what, "out", out, out_count, {(cols - 1) / d + 1, d < cols ? d : cols, 1}, {s1, s2, 0}, {"s1", "s2", "0"})) return 1;
+    CLAIR_HIP_TRY(train_fail(t), hipSetDevice(t->device));
+    if (debug_upload(t, t->dbg_a, x, x_count) || debug_upload(t, t->dbg_c, out, out_count)) return 1;
+    if (column_sum(t, t->dbg_a.as<float>(), rows, cols, ld, t->dbg_c.as<float>(), d, s1, s2)) return 1;
+    CLAIR_HIP_TRY(train_fail(t), hipMemcpyAsync(out, t->dbg_c.p, (size_t)out_count * 4, hipMemcpyDeviceToHost, t->stream));
     CLAIR_HIP_TRY(train_fail(t), hipStreamSynchronize(t->stream));
     return 0;
 }

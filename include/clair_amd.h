@@ -565,6 +565,21 @@ int clair_train_step(clair_trainer_t *t, double learning_rate, double l2_lambda,
 int clair_train_read_mask(clair_trainer_t *t, int layer, uint8_t *host, int64_t count);
 int clair_train_probabilities(clair_trainer_t *t, float *out);
 int clair_train_accuracy(clair_trainer_t *t, int64_t *tp);
+/* -- kernel taps for tests (tests/test_train_kernels_gpu.py; docs/train.md): one launch of tgemm (csrc/train_gemm.hip.h) or of
+ *    column_sum_kernel (csrc/train_kernels.hip.h) on host arrays, through the launch code the trainer itself uses and on its stream.  The
+ *    arrays are copied to buffers the handle owns -- C and out go up as well, since `accumulate` and the column sums' += read them and
+ *    elements the kernel does not address must come back as they went -- and C / out are copied back.  Synchronous.
+ * _debug_gemm: C[b] (+)= A[b] . B[b] (+ bias[b][col]) with A(m, k) = a[b * ba + m * sam + k * sak], B(k, n) = b[b * bb + k * sbk + n * sbn],
+ *   C(m, n) = c[b * bc + m * scm + n * scn], bias column n = bias[b * bbias + n].  dims [5] = M, N, K, batch, accumulate (0 | 1);
+ *   strides [10] = sam, sak, sbk, sbn, scm, scn, ba, bb, bc, bbias, in elements.  bias NULL with bias_count 0: no bias.
+ * _debug_column_sum: out[(j / d) * s1 + (j % d) * s2] += sum over r < rows of x[r * ld + j], j < cols.
+ * Nothing is launched unless every address is inside its array: M, N, K, cols 1 .. 2^20, batch 1 .. 65535, rows 1 .. 2^28, every count
+ *   1 .. 2^28, every stride, batch offset and ld 0 .. 2^28, d 1 .. 2^28, and the largest element index of each operand -- for A
+ *   (M-1)*sam + (K-1)*sak + (batch-1)*ba, and so on -- below its count; otherwise non-zero and a message that names the operand. */
+int clair_train_debug_gemm(clair_trainer_t *t, const float *a, int64_t a_count, const float *b, int64_t b_count, const float *bias, int64_t bias_count,
+                           float *c, int64_t c_count, const int64_t *dims, const int64_t *strides);
+int clair_train_debug_column_sum(clair_trainer_t *t, const float *x, int64_t x_count, int64_t rows, int cols, int64_t ld, float *out, int64_t out_count,
+                                 int d, int s1, int s2);
 
 /* -- compare_vcf on the device (python -m clair_amd.compare_vcf --backend device; csrc/compare.hip, docs/compare_vcf.md has the rule and
  * the tables).  One handle scores one call set against one truth set: both texts (VCF as plain bytes, each below 2^32 bytes) are copied to
