@@ -17,6 +17,7 @@ SUBMODULES = {
     "train_clr": "clair_amd.train_clr",
     "merge_vcf": "clair_amd.merge_vcf",
     "compare_vcf": "clair_amd.compare_vcf",
+    "index_bam": "clair_amd.index_bam",
 }
 NOT_COVERED = ("plot_tensor", "train", "Tensor2Bin", "CombineBins", "Bin2To3", "overlap_variant")
 

@@ -153,6 +153,14 @@ SIGNATURES = {
     "clair_train_accuracy": _sig(c_vp, c_vp),
     "clair_train_debug_gemm": _sig(c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp),
     "clair_train_debug_column_sum": _sig(c_vp, c_vp, c_i64, c_i64, c_int, c_i64, c_vp, c_i64, c_int, c_int, c_int),
+    "clair_bamidx_create": _sig(c_int, c_int, c_int, p_vp),
+    "clair_bamidx_destroy": _sig(c_vp, restype=None),
+    "clair_bamidx_last_error": _sig(c_vp, restype=c_cp),
+    "clair_bamidx_begin": _sig(c_vp, c_int, c_vp),
+    "clair_bamidx_batch": _sig(c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_vp, p_vp),
+    "clair_bamidx_finish": _sig(c_vp, c_vp, c_i64, c_vp),
+    "clair_bamidx_backend": _sig(c_vp, c_vp),
+    "clair_bamidx_debug_frame": _sig(c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp),
 }
 SYMBOLS = tuple(SIGNATURES)
 ENSEMBLE_MAX_MODELS = 8                                      # CLAIR_ENSEMBLE_MAX_MODELS

@@ -107,6 +107,17 @@ SIGNATURES = {
     "clair_host_compare_set_reference": _sig(vp, vp, vp, i32),
     "clair_host_compare_left_align": _sig(vp, i32, vp),
     "clair_host_compare_allele_text": _sig(vp, i32, vp),
+    "clair_host_bamidx_create": _sig(i32, i32, i32, p_vp),
+    "clair_host_bamidx_destroy": _sig(vp, restype=None),
+    "clair_host_bamidx_begin": _sig(vp, i32, vp),
+    "clair_host_bamidx_batch": _sig(vp, vp, i64, i32, vp, vp, vp, vp, i64, i64, i32, vp, p_vp),
+    "clair_host_bamidx_finish": _sig(vp, vp, i64, vp),
+    "clair_host_bamidx_backend": _sig(vp, vp),
+    "clair_host_bamidx_debug_frame": _sig(vp, i64, i64, i32, vp, i64, vp),
+    "clair_host_bamidx_build": _sig(cp, vp, i32, p_vp),
+    "clair_host_bamidx_result_info": _sig(vp, vp),
+    "clair_host_bamidx_result_copy": _sig(vp, vp, vp, vp),
+    "clair_host_bamidx_result_free": _sig(vp, restype=None),
 }
 SYMBOLS = tuple(SIGNATURES)
 N_VALUES = 1056

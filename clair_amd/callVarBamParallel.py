@@ -195,6 +195,8 @@ def run(args, lines):
     for line, (device, _) in zip(lines, commands.chunks):
         per_device.setdefault(device, []).append(line)
     os.makedirs(os.path.dirname(os.path.abspath(args.output_prefix)) or ".", exist_ok=True)
+    if args.build_bam_index and args.bam_reader == "native":
+        build_bam_index(os.path.abspath(args.bam_fn), args.bam_threads or 4)
     procs = []
     with tempfile.TemporaryDirectory() as tmp:
         for device, mine in sorted(per_device.items()):
@@ -208,6 +210,21 @@ def run(args, lines):
     if args.merged_fn is not None:
         merge(args)
     return 0
+
+
+def build_bam_index(bam_fn, threads):
+    """--build_bam_index: a BAM without an index next to it gets a .bai (clair_amd.index_bam) before the first chunk starts, so that no chunk
+    scans the file from its first record.  An index that is there, of either kind, is left alone."""
+    from . import index_bam
+    from ._hostapi import BamError, bam_index_for
+    if bam_index_for(bam_fn)[0] is not None:
+        return None
+    try:
+        r = index_bam.build_index(bam_fn, threads=threads)
+    except BamError as e:
+        sys.exit("[ERROR] callVarBamParallel --build_bam_index: %s" % e)
+    print("[INFO] --build_bam_index (%s): %s, %d records" % (r["backend"], r["path"], r["records"]), file=sys.stderr)
+    return r
 
 
 def merge(args):
@@ -281,6 +298,8 @@ def build_parser():
     add('--subsample_seed', type=int, default=None, metavar="INT", help="passed on (callVarBam: the seed of --subsample and --ensemble_subsample)")
     add('--ensemble_subsample', type=str, action='append', default=None, metavar="FRAC[:SEED]",
         help="passed on, repeatable (callVarBam: one more virtual BAM, --bam_fn at this fraction, averaged with the others on the GPU)")
+    add('--build_bam_index', action='store_true',
+        help="with --run and --bam_reader native: a BAM without a .bai gets one (clair_amd.index_bam) before the first chunk starts")
     add('--merged_fn', type=str, default=None, metavar="FILE",
         help="with --run: after every chunk has been called, merge the chunks' VCFs into this one file (clair_amd.merge_vcf; *.gz: BGZF and a .tbi)")
     add('--merge_overlap_filter', type=str, default="off", choices=("off", "python", "host", "device"),

@@ -142,6 +142,14 @@ __global__ __launch_bounds__(64) void inflate_bgzf_kernel(const uint8_t *__restr
 
 }  // namespace clair_inf
 
+#include "inflate_launch.h"
+
+hipError_t clair_inf::launch_bgzf(hipStream_t stream, const uint8_t *cdata, int n, const int64_t *in_at, const int32_t *csize, const int64_t *out_at,
+                                  const int32_t *out_len, uint8_t *out, int32_t *status) {
+    hipLaunchKernelGGL(inflate_bgzf_kernel, dim3((unsigned)n), dim3(64), 0, stream, cdata, n, in_at, csize, out_at, out_len, out, status);
+    return hipGetLastError();
+}
+
 // -- the handle: a StagedStream sized from max_blocks at creation
 #include <cstring>
 

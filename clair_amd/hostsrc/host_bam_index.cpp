@@ -1,0 +1,446 @@
+// index_bam on the CPU (include/clair_host.h: clair_host_bamidx_*; docs/index_bam.md).  Three things:
+//   - the host twin of csrc/bam_index.hip: the same batch interface and the rules of csrc/bam_index_core.h as sequential loops.  Blocks are
+//     inflated by zlib on a few threads; records are framed by the plain walk, or -- so that the parallel rule can be held against the walk
+//     on a machine without a GPU -- by a restatement of the segmented framing the device runs (jump table per segment, pointer jumping, the
+//     chain over the segments, counts, offsets);
+//   - the file driver both backends run under: the BAM header, the BGZF block headers (as host_bam.cpp walks them), the batches, the runs
+//     joined across batches;
+//   - the result the Python side writes the .bai from (clair_amd/index_bam.py).
+// Plain C++17 + zlib, no HIP.
+#include "../../include/clair_host.h"
+#include "../csrc/bam_index_core.h"
+
+#include <zlib.h>
+
+#include <algorithm>
+#include <climits>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <thread>
+#include <vector>
+
+int clair_host_fail(const char *fmt, ...);   // host_io.cpp
+
+namespace {
+
+using namespace clair_bix;
+
+constexpr int BGZF_HEADER = 18, BGZF_FOOTER = 8, BGZF_MAX_BLOCK = 65536;
+
+inline uint32_t u16(const uint8_t *p) { return (uint32_t)(p[0] | p[1] << 8); }
+inline uint32_t u32(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+
+// one BGZF block -> out_len bytes at out: 0, or what is wrong with it (the statuses of the device inflate, in its words)
+const char *inflate_block(const uint8_t *block, uint32_t csize, uint8_t *out, uint32_t out_len) {
+    z_stream z{};
+    if (inflateInit2(&z, -15) != Z_OK) return "inflateInit2 failed";
+    uint8_t spill = 0;
+    z.next_in = const_cast<uint8_t *>(block) + BGZF_HEADER;
+    z.avail_in = csize - BGZF_HEADER - BGZF_FOOTER;
+    z.next_out = out_len ? out : &spill;
+    z.avail_out = out_len;
+    int rc = inflate(&z, Z_FINISH);
+    if (rc != Z_STREAM_END && z.avail_out == 0) {            // room for one byte more: a block that inflates to more than ISIZE says so
+        z.next_out = &spill;
+        z.avail_out = 1;
+        rc = inflate(&z, Z_FINISH);
+        if (z.avail_out == 0) { inflateEnd(&z); return "inflated size differs from ISIZE"; }
+    }
+    const size_t got = z.total_out;
+    inflateEnd(&z);
+    if (rc != Z_STREAM_END) return "corrupt deflate data";
+    if (got != out_len) return "inflated size differs from ISIZE";
+    if ((uint32_t)crc32(0L, out, out_len) != u32(block + csize - 8)) return "CRC32 mismatch";
+    return nullptr;
+}
+
+// ---- framing.  Both give the record starts from `entry`, the tail (where the chain stops) and whether it stopped on a bad step.
+void frame_walk(const Bytes &m, int64_t len, int64_t entry, std::vector<int64_t> &starts, int64_t *tail, bool *bad) {
+    int64_t o = entry, next = 0;
+    int rc;
+    while ((rc = step(m, o, len, &next)) == STEP_NEXT) { starts.push_back(o); o = next; }
+    *tail = o;
+    *bad = rc == STEP_BAD;
+}
+
+// the device's rule, restated: what each kernel of csrc/bam_index.hip does, a loop per kernel
+void frame_segmented(const Bytes &m, int64_t len, int64_t entry, uint32_t seg, std::vector<int64_t> &starts, int64_t *tail, bool *bad) {
+    const int64_t n_seg = (len + seg - 1) / seg;
+    std::vector<uint32_t> exit((size_t)(n_seg * seg)), now(seg);
+    const int rounds = jump_rounds(seg);
+    for (int64_t s = 0; s < n_seg; ++s) {                    // exits_kernel: a workgroup per segment
+        uint32_t *e = exit.data() + s * seg;
+        for (uint32_t o = 0; o < seg; ++o) e[o] = seg_next(m, s * (int64_t)seg, o, len);
+        for (int r = 0; r < rounds; ++r) {
+            for (uint32_t o = 0; o < seg; ++o) now[o] = e[o] < seg ? e[e[o]] : e[o];     // every lane reads, a barrier, every lane writes
+            std::copy(now.begin(), now.end(), e);
+        }
+    }
+    std::vector<int64_t> seg_entry((size_t)n_seg), first((size_t)n_seg + 1, 0);
+    int64_t result[2];
+    chain_walk(m, len, entry, seg, n_seg, exit.data(), seg_entry.data(), result);        // chain_kernel: one thread
+    for (int64_t s = 0; s < n_seg; ++s)                      // count_kernel and the scan
+        first[(size_t)s + 1] = first[(size_t)s] + (seg_entry[(size_t)s] < 0 ? 0 : seg_records(m, len, seg, s, seg_entry[(size_t)s], nullptr, 0, 0));
+    const size_t before = starts.size();
+    starts.resize(before + (size_t)first[(size_t)n_seg]);
+    for (int64_t s = 0; s < n_seg; ++s)                      // emit_kernel
+        if (seg_entry[(size_t)s] >= 0) seg_records(m, len, seg, s, seg_entry[(size_t)s], starts.data() + before, first[(size_t)s], first[(size_t)n_seg]);
+    *tail = result[0];
+    *bad = result[1] != 0;
+}
+
+bool good_segment(int segment_bytes) {
+    return segment_bytes >= (int)SEG_MIN && segment_bytes <= (int)SEG_MAX && (segment_bytes & (segment_bytes - 1)) == 0;
+}
+
+}  // namespace
+
+struct clair_host_bamidx {
+    int threads = 4, max_blocks = 0;
+    uint32_t seg = 0;                            // 0: the sequential walk
+    int n_ref = -1;
+    std::vector<int64_t> first_window;           // n_ref + 1
+    std::vector<uint64_t> linear;
+    int64_t counts[3] = {0, 0, 0};
+    std::vector<uint8_t> stream, carry;
+    uint64_t carry_voff = 0;
+    std::vector<int64_t> at, starts;
+    std::vector<uint64_t> voff;
+    std::vector<clair_bamidx_run_t> runs;
+};
+
+struct clair_host_bamidx_result {
+    int64_t counts[3] = {0, 0, 0};
+    std::vector<int64_t> first_window;
+    std::vector<uint64_t> linear;
+    std::vector<clair_bamidx_run_t> runs;
+};
+
+extern "C" {
+
+int clair_host_bamidx_create(int threads, int max_blocks, int segment_bytes, clair_host_bamidx_t **out) {
+    if (!out) return clair_host_fail("out is NULL");
+    *out = nullptr;
+    if (threads < 1 || threads > 16) return clair_host_fail("BAM threads: %d (1 .. 16)", threads);
+    if (max_blocks < 1 || max_blocks > 16384) return clair_host_fail("max_blocks %d: 1 .. 16384", max_blocks);
+    if (segment_bytes != 0 && !good_segment(segment_bytes)) return clair_host_fail("segment_bytes %d: a power of two in %u .. %u, or 0", segment_bytes, SEG_MIN, SEG_MAX);
+    clair_host_bamidx *h = new clair_host_bamidx;
+    h->threads = threads;
+    h->max_blocks = max_blocks;
+    h->seg = (uint32_t)segment_bytes;
+    *out = h;
+    return 0;
+}
+
+void clair_host_bamidx_destroy(clair_host_bamidx_t *h) { delete h; }
+
+int clair_host_bamidx_begin(clair_host_bamidx_t *h, int n_ref, const int64_t *ref_len) {
+    if (!h || n_ref < 0 || (n_ref > 0 && !ref_len)) return clair_host_fail("bamidx begin: bad arguments");
+    h->first_window.assign((size_t)n_ref + 1, 0);
+    for (int r = 0; r < n_ref; ++r) h->first_window[(size_t)r + 1] = h->first_window[(size_t)r] + windows_of(ref_len[r]);
+    h->linear.assign((size_t)h->first_window[(size_t)n_ref], NO_OFFSET);
+    h->n_ref = n_ref;
+    h->counts[0] = h->counts[1] = h->counts[2] = 0;
+    h->carry.clear();
+    h->carry_voff = 0;
+    return 0;
+}
+
+int clair_host_bamidx_batch(clair_host_bamidx_t *h, const uint8_t *cdata, int64_t cbytes, int n, const int64_t *in_at, const int32_t *csize,
+                            const int32_t *out_len, const int64_t *coffset, int64_t end_coffset, int64_t entry, int last, int64_t *state,
+                            const clair_bamidx_run_t **runs) {
+    if (!h || !state || !runs) return clair_host_fail("bamidx batch: NULL argument");
+    if (h->n_ref < 0) return clair_host_fail("bamidx batch: begin first");
+    if (n < 0 || n > h->max_blocks) return clair_host_fail("%d blocks in a batch: 0 .. max_blocks = %d", n, h->max_blocks);
+    if (n > 0 && (!cdata || !in_at || !csize || !out_len || !coffset)) return clair_host_fail("bamidx batch: NULL argument");
+    if (cbytes < 0 || end_coffset < 0 || entry < 0) return clair_host_fail("bamidx batch: negative argument");
+    int64_t len = (int64_t)h->carry.size();
+    for (int i = 0; i < n; ++i) {
+        if (csize[i] < BGZF_HEADER + BGZF_FOOTER || csize[i] > BGZF_MAX_BLOCK) return clair_host_fail("block %d: csize %d (26 .. 65536)", i, csize[i]);
+        if (in_at[i] < 0 || in_at[i] > cbytes - csize[i]) return clair_host_fail("block %d: compressed bytes [%lld, +%d) outside the %lld given", i, (long long)in_at[i], csize[i], (long long)cbytes);
+        if (out_len[i] < 0 || out_len[i] > BGZF_MAX_BLOCK) return clair_host_fail("block %d: out_len %d (0 .. 65536)", i, out_len[i]);
+        if (coffset[i] < 0) return clair_host_fail("block %d: negative offset", i);
+        len += out_len[i];
+    }
+    if (entry > len) return clair_host_fail("bamidx batch: entry %lld beyond the %lld bytes of the batch", (long long)entry, (long long)len);
+    // 1. the stream and the table of its pieces
+    h->stream.resize((size_t)len);
+    h->at.clear();
+    h->voff.clear();
+    if (!h->carry.empty()) {
+        memcpy(h->stream.data(), h->carry.data(), h->carry.size());
+        h->at.push_back(0);
+        h->voff.push_back(h->carry_voff);
+    }
+    std::vector<const char *> why((size_t)n, nullptr);
+    int64_t pos = (int64_t)h->carry.size();
+    const size_t first_block = h->at.size();
+    for (int i = 0; i < n; ++i) {
+        h->at.push_back(pos);
+        h->voff.push_back((uint64_t)coffset[i] << 16);
+        pos += out_len[i];
+    }
+    h->at.push_back(len);
+    h->voff.push_back((uint64_t)end_coffset << 16);
+    auto inflate_one = [&](int i) { why[(size_t)i] = inflate_block(cdata + in_at[i], (uint32_t)csize[i], h->stream.data() + h->at[first_block + (size_t)i], (uint32_t)out_len[i]); };
+    const int nt = std::max(1, std::min(h->threads, n));
+    if (nt == 1) {
+        for (int i = 0; i < n; ++i) inflate_one(i);
+    } else {
+        std::vector<std::thread> pool;
+        for (int t = 0; t < nt; ++t) pool.emplace_back([&, t] { for (int i = t; i < n; i += nt) inflate_one(i); });
+        for (auto &th : pool) th.join();
+    }
+    for (int i = 0; i < n; ++i)
+        if (why[(size_t)i]) return clair_host_fail("BGZF block at compressed offset %lld: %s", (long long)coffset[i], why[(size_t)i]);
+    // 2. the record starts
+    const Bytes m{h->stream.data()};
+    const int n_tab = (int)h->at.size();
+    h->starts.clear();
+    int64_t tail = 0;
+    bool bad = false;
+    if (h->seg) frame_segmented(m, len, entry, h->seg, h->starts, &tail, &bad);
+    else frame_walk(m, len, entry, h->starts, &tail, &bad);
+    const int64_t n_rec = (int64_t)h->starts.size();
+    const auto voffset = [&](int64_t p) { return voffset_at(h->at.data(), h->voff.data(), n_tab, p); };
+    // 3 - 5. fields, runs, the linear index
+    h->runs.clear();
+    int32_t prev_tid = (int32_t)state[ST_PREV_TID], prev_pos = (int32_t)state[ST_PREV_POS];
+    for (int64_t k = 0; k < n_rec; ++k) {
+        const int64_t o = h->starts[(size_t)k];
+        Fields f = fields(m, o, h->n_ref);
+        if (f.verdict == V_OK && order_key(f.tid, f.pos) < order_key(prev_tid, prev_pos)) f.verdict = V_UNSORTED;
+        if (f.verdict != V_OK) {
+            const Detail d{state[ST_RECORDS_BEFORE] + k, f.tid, f.pos, prev_tid, prev_pos, f.end, voffset(o), m.le32(o), f.verdict};
+            char buf[400];
+            describe(buf, sizeof buf, d);
+            return clair_host_fail("%s", buf);
+        }
+        const uint64_t beg = voffset(o), end = voffset(k + 1 < n_rec ? h->starts[(size_t)k + 1] : tail);
+        h->counts[0] += 1;
+        if (f.tid < 0) h->counts[2] += 1;
+        else if (!(f.flag & 4)) h->counts[1] += 1;
+        if (f.tid >= 0) {
+            const int64_t n_win = h->first_window[(size_t)f.tid + 1] - h->first_window[(size_t)f.tid];
+            for (int64_t w = (f.pos > 0 ? f.pos : 0) >> WINDOW_SHIFT; w <= (f.end - 1) >> WINDOW_SHIFT && w < n_win; ++w) {
+                uint64_t &slot = h->linear[(size_t)(h->first_window[(size_t)f.tid] + w)];
+                slot = std::min(slot, beg);
+            }
+        }
+        if (h->runs.empty() || k == 0 || h->runs.back().tid != f.tid || h->runs.back().bin != f.bin) h->runs.push_back(clair_bamidx_run_t{f.tid, f.bin, beg, end});
+        else h->runs.back().end = end;
+        prev_tid = f.tid;
+        prev_pos = f.pos;
+    }
+    if (bad) {
+        char buf[200];
+        describe_bad_step(buf, sizeof buf, voffset(tail), m.le32(tail));
+        return clair_host_fail("%s", buf);
+    }
+    if (last && tail < len) {
+        char buf[200];
+        describe_cut(buf, sizeof buf, voffset(tail));
+        return clair_host_fail("%s", buf);
+    }
+    h->carry_voff = tail < len ? voffset(tail) : 0;
+    std::vector<uint8_t> keep(h->stream.begin() + (ptrdiff_t)tail, h->stream.end());
+    h->carry.swap(keep);
+    state[ST_N_RECORDS] = n_rec;
+    state[ST_N_RUNS] = (int64_t)h->runs.size();
+    state[ST_LAST_TID] = prev_tid;
+    state[ST_LAST_POS] = prev_pos;
+    state[ST_CARRY] = (int64_t)h->carry.size();
+    *runs = h->runs.data();
+    return 0;
+}
+
+int clair_host_bamidx_finish(clair_host_bamidx_t *h, uint64_t *linear, int64_t n_windows, int64_t *counts) {
+    if (!h || !counts || h->n_ref < 0) return clair_host_fail("bamidx finish: bad arguments");
+    if (n_windows != (int64_t)h->linear.size() || (n_windows > 0 && !linear)) return clair_host_fail("bamidx finish: %lld windows, the handle has %zu", (long long)n_windows, h->linear.size());
+    if (n_windows) memcpy(linear, h->linear.data(), (size_t)n_windows * 8);
+    for (int i = 0; i < 3; ++i) counts[i] = h->counts[i];
+    return 0;
+}
+
+static int twin_begin(void *ctx, int n_ref, const int64_t *ref_len) { return clair_host_bamidx_begin((clair_host_bamidx_t *)ctx, n_ref, ref_len); }
+static int twin_batch(void *ctx, const uint8_t *cdata, int64_t cbytes, int n, const int64_t *in_at, const int32_t *csize, const int32_t *out_len,
+                      const int64_t *coffset, int64_t end_coffset, int64_t entry, int last, int64_t *state, const clair_bamidx_run_t **runs) {
+    return clair_host_bamidx_batch((clair_host_bamidx_t *)ctx, cdata, cbytes, n, in_at, csize, out_len, coffset, end_coffset, entry, last, state, runs);
+}
+static int twin_finish(void *ctx, uint64_t *linear, int64_t n_windows, int64_t *counts) { return clair_host_bamidx_finish((clair_host_bamidx_t *)ctx, linear, n_windows, counts); }
+static const char *twin_last_error(const void *) { return clair_host_last_error(); }
+
+int clair_host_bamidx_backend(clair_host_bamidx_t *h, clair_bamidx_backend_t *out) {
+    if (!h || !out) return clair_host_fail("bamidx backend: NULL argument");
+    *out = clair_bamidx_backend_t{h, twin_begin, twin_batch, twin_finish, twin_last_error};
+    return 0;
+}
+
+int clair_host_bamidx_debug_frame(const uint8_t *stream, int64_t n, int64_t entry, int segment_bytes, int64_t *starts, int64_t cap, int64_t *result) {
+    if (n < 0 || (n > 0 && !stream) || entry < 0 || entry > n || cap < 0 || (cap > 0 && !starts) || !result) return clair_host_fail("debug_frame: bad arguments");
+    if (segment_bytes != 0 && !good_segment(segment_bytes)) return clair_host_fail("segment_bytes %d: a power of two in %u .. %u, or 0", segment_bytes, SEG_MIN, SEG_MAX);
+    std::vector<int64_t> found;
+    int64_t tail = 0;
+    bool bad = false;
+    if (segment_bytes) frame_segmented(Bytes{stream}, n, entry, (uint32_t)segment_bytes, found, &tail, &bad);
+    else frame_walk(Bytes{stream}, n, entry, found, &tail, &bad);
+    if ((int64_t)found.size() > cap) return clair_host_fail("debug_frame: %zu records, room for %lld", found.size(), (long long)cap);
+    std::copy(found.begin(), found.end(), starts);
+    result[FR_N_STARTS] = (int64_t)found.size();
+    result[FR_TAIL] = tail;
+    result[FR_BAD] = bad ? 1 : 0;
+    result[FR_SENTINELS] = 1;
+    return 0;
+}
+
+// ---- the file driver
+int clair_host_bamidx_build(const char *path, const clair_bamidx_backend_t *be, int max_blocks, clair_host_bamidx_result_t **out) {
+    if (!out) return clair_host_fail("out is NULL");
+    *out = nullptr;
+    if (!path || !be || !be->begin || !be->batch || !be->finish || !be->last_error) return clair_host_fail("bamidx build: NULL argument");
+    if (max_blocks < 1 || max_blocks > 16384) return clair_host_fail("max_blocks %d: 1 .. 16384", max_blocks);
+    FILE *file = fopen(path, "rb");
+    if (!file) return clair_host_fail("%s: cannot open", path);
+    struct Closer { FILE *f; ~Closer() { fclose(f); } } closer{file};
+    if (fseeko(file, 0, SEEK_END) != 0) return clair_host_fail("%s: cannot seek", path);
+    const int64_t file_size = (int64_t)ftello(file);
+    std::vector<uint8_t> cbuf;
+    // one block's header at coffset checked and its bytes appended to cbuf: -> csize, 0 on failure (message set)
+    const auto read_block = [&](int64_t coffset) -> uint32_t {
+        uint8_t hd[BGZF_HEADER];
+        const auto cut = [&] { clair_host_fail("%s: truncated BGZF block at compressed offset %lld", path, (long long)coffset); return 0u; };
+        if (coffset + BGZF_HEADER > file_size || fseeko(file, (off_t)coffset, SEEK_SET) != 0 || fread(hd, 1, BGZF_HEADER, file) != BGZF_HEADER) return cut();
+        if (hd[0] != 0x1f || hd[1] != 0x8b || hd[2] != 8 || !(hd[3] & 4) || u16(hd + 10) != 6 || hd[12] != 'B' || hd[13] != 'C' || u16(hd + 14) != 2) {
+            clair_host_fail("%s: not a BGZF block at compressed offset %lld", path, (long long)coffset);
+            return 0u;
+        }
+        const uint32_t csize = u16(hd + 16) + 1;
+        if (csize < BGZF_HEADER + BGZF_FOOTER || coffset + csize > file_size) return cut();
+        const size_t at = cbuf.size();
+        cbuf.resize(at + csize);
+        memcpy(cbuf.data() + at, hd, BGZF_HEADER);
+        if (fread(cbuf.data() + at + BGZF_HEADER, 1, csize - BGZF_HEADER, file) != csize - BGZF_HEADER) { cbuf.resize(at); return cut(); }
+        if (u32(cbuf.data() + at + csize - 4) > (uint32_t)BGZF_MAX_BLOCK) {
+            clair_host_fail("%s: BGZF block at compressed offset %lld claims %u bytes", path, (long long)coffset, u32(cbuf.data() + at + csize - 4));
+            return 0u;
+        }
+        return csize;
+    };
+    {
+        uint8_t magic[4] = {0, 0, 0, 0};
+        if (file_size < BGZF_HEADER || fseeko(file, 0, SEEK_SET) != 0 || fread(magic, 1, 4, file) != 4 || magic[0] != 0x1f || magic[1] != 0x8b || magic[2] != 8 || !(magic[3] & 4))
+            return clair_host_fail("%s is not a BGZF-compressed BAM (SAM text, CRAM and plain gzip have no .bai)", path);
+    }
+    // the header, block by block (zlib), with where each block's bytes start in it
+    std::vector<uint8_t> text;
+    std::vector<std::pair<int64_t, int64_t>> pieces;          // (position in text, coffset)
+    int64_t coffset = 0;
+    const auto need = [&](size_t bytes) -> int {
+        while (text.size() < bytes) {
+            if (coffset >= file_size) return clair_host_fail("%s: the BAM header is truncated", path);
+            cbuf.clear();
+            const uint32_t csize = read_block(coffset);
+            if (!csize) return 1;
+            const uint32_t isize = u32(cbuf.data() + csize - 4);
+            const size_t at = text.size();
+            text.resize(at + isize + 1);
+            const char *why = inflate_block(cbuf.data(), csize, text.data() + at, isize);
+            text.resize(at + isize);
+            if (why) return clair_host_fail("%s: BGZF block at compressed offset %lld: %s", path, (long long)coffset, why);
+            pieces.emplace_back((int64_t)at, coffset);
+            coffset += csize;
+        }
+        return 0;
+    };
+    if (need(12)) return 1;
+    if (memcmp(text.data(), "BAM\1", 4)) return clair_host_fail("%s: BGZF but not BAM (no BAM\\1 magic)", path);
+    const uint32_t l_text = u32(text.data() + 4);
+    if (need(12 + (size_t)l_text)) return 1;
+    size_t at = 8 + (size_t)l_text;
+    const int32_t n_ref = (int32_t)u32(text.data() + at);
+    if (n_ref < 0) return clair_host_fail("%s: negative n_ref in the BAM header", path);
+    at += 4;
+    std::vector<int64_t> ref_len;
+    for (int32_t i = 0; i < n_ref; ++i) {
+        if (need(at + 4)) return 1;
+        const uint32_t l_name = u32(text.data() + at);
+        if (l_name == 0 || l_name > (1u << 20)) return clair_host_fail("%s: bad reference name length in the BAM header", path);
+        if (need(at + 4 + l_name + 4)) return 1;
+        ref_len.push_back((int64_t)u32(text.data() + at + 4 + l_name));
+        at += 4 + (size_t)l_name + 4;
+    }
+    // the first record: in the last header block, or at the start of the block after it
+    int64_t entry = 0;
+    if (at < text.size()) {
+        size_t k = pieces.size() - 1;
+        while (pieces[k].first > (int64_t)at) --k;
+        coffset = pieces[k].second;
+        entry = (int64_t)at - pieces[k].first;
+    }
+    if (be->begin(be->ctx, n_ref, ref_len.data())) return clair_host_fail("%s: %s", path, be->last_error(be->ctx));
+    clair_host_bamidx_result *res = new clair_host_bamidx_result;
+    struct Guard { clair_host_bamidx_result *r; ~Guard() { delete r; } } guard{res};
+    std::vector<int64_t> in_at, offs;
+    std::vector<int32_t> csizes, out_lens;
+    int64_t state[STATE_WORDS] = {0, 0, INT32_MIN, 0, 0, 0, INT32_MIN, 0};
+    bool last = false;
+    while (!last) {
+        cbuf.clear(); in_at.clear(); offs.clear(); csizes.clear(); out_lens.clear();
+        while ((int)offs.size() < max_blocks && coffset < file_size) {
+            const size_t here = cbuf.size();
+            const uint32_t csize = read_block(coffset);
+            if (!csize) return 1;
+            in_at.push_back((int64_t)here);
+            offs.push_back(coffset);
+            csizes.push_back((int32_t)csize);
+            out_lens.push_back((int32_t)u32(cbuf.data() + here + csize - 4));
+            coffset += csize;
+        }
+        last = coffset >= file_size;
+        const clair_bamidx_run_t *runs = nullptr;
+        if (be->batch(be->ctx, cbuf.data(), (int64_t)cbuf.size(), (int)offs.size(), in_at.data(), csizes.data(), out_lens.data(), offs.data(), coffset, entry,
+                      last ? 1 : 0, state, &runs))
+            return clair_host_fail("%s: %s", path, be->last_error(be->ctx));
+        for (int64_t k = 0; k < state[ST_N_RUNS]; ++k) {
+            const clair_bamidx_run_t &r = runs[k];
+            if (r.tid < 0) continue;
+            if (k == 0 && !res->runs.empty() && res->runs.back().tid == r.tid && res->runs.back().bin == r.bin && res->runs.back().end == r.beg) res->runs.back().end = r.end;
+            else res->runs.push_back(r);
+        }
+        state[ST_RECORDS_BEFORE] += state[ST_N_RECORDS];
+        state[ST_PREV_TID] = state[ST_LAST_TID];
+        state[ST_PREV_POS] = state[ST_LAST_POS];
+        entry = 0;
+    }
+    res->first_window.assign((size_t)n_ref + 1, 0);
+    for (int r = 0; r < n_ref; ++r) res->first_window[(size_t)r + 1] = res->first_window[(size_t)r] + windows_of(ref_len[(size_t)r]);
+    res->linear.assign((size_t)res->first_window[(size_t)n_ref], NO_OFFSET);
+    if (be->finish(be->ctx, res->linear.data(), (int64_t)res->linear.size(), res->counts)) return clair_host_fail("%s: %s", path, be->last_error(be->ctx));
+    guard.r = nullptr;
+    *out = res;
+    return 0;
+}
+
+int clair_host_bamidx_result_info(const clair_host_bamidx_result_t *r, int64_t *info) {
+    if (!r || !info) return clair_host_fail("NULL argument");
+    info[0] = (int64_t)r->first_window.size() - 1;
+    info[1] = r->counts[0];
+    info[2] = r->counts[1];
+    info[3] = r->counts[2];
+    info[4] = (int64_t)r->runs.size();
+    info[5] = (int64_t)r->linear.size();
+    return 0;
+}
+
+int clair_host_bamidx_result_copy(const clair_host_bamidx_result_t *r, clair_bamidx_run_t *runs, uint64_t *linear, int64_t *first_window) {
+    if (!r) return clair_host_fail("NULL argument");
+    if (runs && !r->runs.empty()) memcpy(runs, r->runs.data(), r->runs.size() * sizeof(clair_bamidx_run_t));
+    if (linear && !r->linear.empty()) memcpy(linear, r->linear.data(), r->linear.size() * 8);
+    if (first_window) memcpy(first_window, r->first_window.data(), r->first_window.size() * 8);
+    return 0;
+}
+
+void clair_host_bamidx_result_free(clair_host_bamidx_result_t *r) { delete r; }
+
+}  // extern "C"

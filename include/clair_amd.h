@@ -627,6 +627,55 @@ int clair_compare_set_reference(clair_compare_t *h, const uint8_t *seq, const in
 int clair_compare_left_align(clair_compare_t *h, int side, int64_t *stats);
 int clair_compare_allele_text(clair_compare_t *h, int side, uint8_t *out);
 
+/* ---- index_bam: the .bai of a coordinate-sorted BAM, built on the device (csrc/bam_index.hip; docs/index_bam.md) ----
+ * One handle: one stream, the device buffers of a batch and the linear index.  segment_bytes: the framing segment, a power of two in
+ * 64 .. 8192, 0 for the default (8192).
+ * _begin: a new file with n_ref references of ref_len bases; the linear index (one uint64 per 16 KiB window of every reference, a
+ *   reference's windows after those of the one before it) is set to all-ones, the counters and the carried bytes are dropped.
+ * _batch: n <= max_blocks whole BGZF blocks (block i = cdata[in_at[i] .. + csize[i]), out_len[i] its ISIZE, coffset[i] its offset in the
+ *   file; end_coffset that of the block after the batch), whose headers the caller has walked.  The blocks are inflated behind the bytes the
+ *   batch before carried over, into one device buffer that never comes back; records are framed from `entry` (an offset into that stream: where
+ *   the first record starts), their fields, virtual offsets, runs and linear-index minima computed there.  Back come only the runs (*runs:
+ *   state[4] of them, the handle's until the next call) and state (CLAIR_BAMIDX_STATE).  The bytes from the first record that does not end
+ *   inside the batch are carried to the next; with last != 0 such bytes are an error.  The caller joins a batch's first run to the last of
+ *   the batch before when tid, bin and the offsets meet.
+ * _finish: the linear index (n_windows as _begin laid it out; all-ones: untouched) and counts [3] = records, mapped, unplaced.
+ * _backend: the three calls above with the handle, as clair_host_bamidx_build takes them.
+ * _debug_frame: the framing alone on a host byte stream (tests): starts [cap], result [4] = starts, tail, bad (the chain hit a
+ *   block_size that cannot be), sentinels intact (words behind the stream and behind the offsets array, checked after the kernels).
+ * Non-zero on failure, message from clair_bamidx_last_error (NULL handle: the failure of create); a failed batch leaves the handle fit for
+ * _begin.  clair_host_bamidx_* (include/clair_host.h) gives the same bytes on the CPU. */
+typedef struct clair_bamidx clair_bamidx_t;
+#ifndef CLAIR_BAMIDX_TYPES
+#define CLAIR_BAMIDX_TYPES
+/* one run of records next to each other in the file that share (tid, bin): one chunk of a .bai, [beg, end) as virtual offsets */
+typedef struct clair_bamidx_run {
+    int32_t tid;
+    uint32_t bin;
+    uint64_t beg, end;
+} clair_bamidx_run_t;      /* 24 bytes */
+/* the batch interface of an index build, as the file driver (clair_host_bamidx_build) calls it: the entry points of one backend with its handle */
+typedef struct clair_bamidx_backend {
+    void *ctx;
+    int (*begin)(void *ctx, int n_ref, const int64_t *ref_len);
+    int (*batch)(void *ctx, const uint8_t *cdata, int64_t cbytes, int n, const int64_t *in_at, const int32_t *csize, const int32_t *out_len,
+                 const int64_t *coffset, int64_t end_coffset, int64_t entry, int last, int64_t *state, const clair_bamidx_run_t **runs);
+    int (*finish)(void *ctx, uint64_t *linear, int64_t n_windows, int64_t *counts);
+    const char *(*last_error)(const void *ctx);
+} clair_bamidx_backend_t;
+#define CLAIR_BAMIDX_STATE 8   /* int64 words of `state`: in 0 records before the batch, 1 2 tid and pos of the record before it (0, INT32_MIN: none);
+                                * out 3 records, 4 runs, 5 6 tid and pos of the last record (1 2 when there is none), 7 bytes carried over */
+#endif
+int clair_bamidx_create(int device, int max_blocks, int segment_bytes, clair_bamidx_t **out);
+void clair_bamidx_destroy(clair_bamidx_t *h);
+const char *clair_bamidx_last_error(const clair_bamidx_t *h);
+int clair_bamidx_begin(clair_bamidx_t *h, int n_ref, const int64_t *ref_len);
+int clair_bamidx_batch(clair_bamidx_t *h, const uint8_t *cdata, int64_t cbytes, int n, const int64_t *in_at, const int32_t *csize, const int32_t *out_len,
+                       const int64_t *coffset, int64_t end_coffset, int64_t entry, int last, int64_t *state, const clair_bamidx_run_t **runs);
+int clair_bamidx_finish(clair_bamidx_t *h, uint64_t *linear, int64_t n_windows, int64_t *counts);
+int clair_bamidx_backend(clair_bamidx_t *h, clair_bamidx_backend_t *out);
+int clair_bamidx_debug_frame(clair_bamidx_t *h, const uint8_t *stream, int64_t n, int64_t entry, int64_t *starts, int64_t cap, int64_t *result);
+
 #ifdef __cplusplus
 }
 #endif

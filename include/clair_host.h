@@ -341,6 +341,52 @@ int clair_host_compare_set_reference(clair_host_compare_t *h, const uint8_t *seq
 int clair_host_compare_left_align(clair_host_compare_t *h, int side, int64_t *stats);
 int clair_host_compare_allele_text(clair_host_compare_t *h, int side, uint8_t *out);
 
+/* -- index_bam on the CPU (hostsrc/host_bam_index.cpp; docs/index_bam.md): the host twin of clair_bamidx_* (include/clair_amd.h) with the
+ *    rules of csrc/bam_index_core.h, and the file driver both backends run under.
+ *    _create .. _backend: the twin, the same calls with the same arguments and results; blocks are inflated by zlib on `threads` threads,
+ *      records framed by the sequential walk (segment_bytes 0) or by the segmented rule the device runs, restated (a power of two in 64 .. 8192).
+ *    _debug_frame: the framing alone, as clair_bamidx_debug_frame: segment_bytes 0 is the walk.
+ *    _build: the whole file through a backend: the BAM header (zlib), the BGZF block headers, batches of max_blocks blocks, the runs joined
+ *      across batches, the order and the end of the file checked.  -> a result: _result_info [6] = references, records, mapped, unplaced, runs,
+ *      windows of the linear index; _result_copy: the runs, the linear index (all-ones: an untouched window) and each reference's first window
+ *      (n_ref + 1 words).  Writing the .bai from these is clair_amd/index_bam.py.
+ *    Messages go to clair_host_last_error. */
+typedef struct clair_host_bamidx clair_host_bamidx_t;
+typedef struct clair_host_bamidx_result clair_host_bamidx_result_t;
+#ifndef CLAIR_BAMIDX_TYPES
+#define CLAIR_BAMIDX_TYPES
+/* one run of records next to each other in the file that share (tid, bin): one chunk of a .bai, [beg, end) as virtual offsets */
+typedef struct clair_bamidx_run {
+    int32_t tid;
+    uint32_t bin;
+    uint64_t beg, end;
+} clair_bamidx_run_t;      /* 24 bytes */
+/* the batch interface of an index build, as the file driver (clair_host_bamidx_build) calls it: the entry points of one backend with its handle */
+typedef struct clair_bamidx_backend {
+    void *ctx;
+    int (*begin)(void *ctx, int n_ref, const int64_t *ref_len);
+    int (*batch)(void *ctx, const uint8_t *cdata, int64_t cbytes, int n, const int64_t *in_at, const int32_t *csize, const int32_t *out_len,
+                 const int64_t *coffset, int64_t end_coffset, int64_t entry, int last, int64_t *state, const clair_bamidx_run_t **runs);
+    int (*finish)(void *ctx, uint64_t *linear, int64_t n_windows, int64_t *counts);
+    const char *(*last_error)(const void *ctx);
+} clair_bamidx_backend_t;
+#define CLAIR_BAMIDX_STATE 8   /* int64 words of `state`: in 0 records before the batch, 1 2 tid and pos of the record before it (0, INT32_MIN: none);
+                                * out 3 records, 4 runs, 5 6 tid and pos of the last record (1 2 when there is none), 7 bytes carried over */
+#endif
+int clair_host_bamidx_create(int threads, int max_blocks, int segment_bytes, clair_host_bamidx_t **out);
+void clair_host_bamidx_destroy(clair_host_bamidx_t *h);
+int clair_host_bamidx_begin(clair_host_bamidx_t *h, int n_ref, const int64_t *ref_len);
+int clair_host_bamidx_batch(clair_host_bamidx_t *h, const uint8_t *cdata, int64_t cbytes, int n, const int64_t *in_at, const int32_t *csize,
+                            const int32_t *out_len, const int64_t *coffset, int64_t end_coffset, int64_t entry, int last, int64_t *state,
+                            const clair_bamidx_run_t **runs);
+int clair_host_bamidx_finish(clair_host_bamidx_t *h, uint64_t *linear, int64_t n_windows, int64_t *counts);
+int clair_host_bamidx_backend(clair_host_bamidx_t *h, clair_bamidx_backend_t *out);
+int clair_host_bamidx_debug_frame(const uint8_t *stream, int64_t n, int64_t entry, int segment_bytes, int64_t *starts, int64_t cap, int64_t *result);
+int clair_host_bamidx_build(const char *path, const clair_bamidx_backend_t *backend, int max_blocks, clair_host_bamidx_result_t **out);
+int clair_host_bamidx_result_info(const clair_host_bamidx_result_t *r, int64_t *info);
+int clair_host_bamidx_result_copy(const clair_host_bamidx_result_t *r, clair_bamidx_run_t *runs, uint64_t *linear, int64_t *first_window);
+void clair_host_bamidx_result_free(clair_host_bamidx_result_t *r);
+
 #ifdef __cplusplus
 }
 #endif
