@@ -8,7 +8,7 @@ import os
 
 import numpy as np
 
-from clair_amd._hostapi import Handle
+from clair_amd._hostapi import INFLATE_STATUS, Handle
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CLAIR_AMD_LIB") or os.path.join(_HERE, "libclair_amd.so")   # override: debugging builds only
@@ -852,9 +852,9 @@ class Inflater(DeviceHandle):
         inf = Inflater(device=0, max_blocks=2048)
         out, status = inf.blocks(cdata, in_at, csize, out_at, out_len)       # whole BGZF blocks inside cdata -> bytes, status per block
 
-    status: 0 ok, 1 corrupt deflate data, 2 inflated size differs from ISIZE, 3 CRC32 mismatch.  `handle` and `callback` are what
+    status: an index into STATUS (_hostapi.INFLATE_STATUS), 0 ok.  `handle` and `callback` are what
     clair_host_bam_set_inflater takes (_hostapi.BamReader(inflate="device"))."""
-    STATUS = ("ok", "corrupt deflate data", "inflated size differs from ISIZE", "CRC32 mismatch")
+    STATUS = INFLATE_STATUS
 
     def __init__(self, device=0, max_blocks=2048):
         self._lib = load()

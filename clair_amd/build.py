@@ -47,6 +47,9 @@ def build_host(force=False):
     # every header a host source includes: clair_call.h is the 32-byte record host_decode.cpp shares bit for bit with the device decode
     hdrs = [os.path.join(HERE, "..", "include", h) for h in ("clair_host.h", "clair_reads.h", "clair_call.h", "clair_amd.h")]
     hdrs.append(os.path.join(HERE, "hostsrc", "sam_line.h"))
+    hdrs.append(os.path.join(HERE, "hostsrc", "bgzf_file.h"))       # BGZF blocks of a file, read and inflated: host_bam.cpp, host_bam_index.cpp
+    hdrs.append(os.path.join(HERE, "hostsrc", "bam_header.h"))      # the BAM header: the same two
+    hdrs.append(os.path.join(HERE, "csrc", "bam_record_core.h"))    # the rules of a BAM record they share with the device (csrc/frontend.hip, csrc/bam_index.hip)
     hdrs.append(os.path.join(HERE, "csrc", "inflate_core.h"))       # the decoder host_inflate.cpp shares with the device (csrc/inflate.hip)
     hdrs.append(os.path.join(HERE, "csrc", "deflate_core.h"))       # the compressor host_deflate.cpp shares with the device (csrc/deflate.hip)
     hdrs.append(os.path.join(HERE, "csrc", "indel_lookup_core.h"))  # the table host_indel.cpp shares with the device library (csrc/indel_lookup.hip)

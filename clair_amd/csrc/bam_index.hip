@@ -28,6 +28,7 @@
 #include "device_buffer.h"
 #include "device_scan.h"
 #include "hip_status.h"
+#include "inflate_core.h"
 #include "inflate_launch.h"
 
 namespace clair_bix {
@@ -194,7 +195,6 @@ struct clair_bamidx {
 
 namespace {
 
-constexpr int64_t BLOCK_MAX = 65536;
 constexpr int64_t PAD = 16;                      // behind the stream and the offsets array: room the kernels must leave alone
 
 std::string g_bix_error;
@@ -322,16 +322,13 @@ int clair_bamidx_batch(clair_bamidx_t *h, const uint8_t *cdata, int64_t cbytes, 
     if (!h) return bix_fail(nullptr)("bamidx handle is NULL");
     if (!state || !runs) return bix_fail(h)("batch: NULL argument");
     if (h->n_ref < 0) return bix_fail(h)("batch: begin first");
-    if (n < 0 || n > h->max_blocks) return bix_fail(h)("%d blocks in a batch: 0 .. max_blocks = %d", n, h->max_blocks);
     if (n > 0 && (!cdata || !in_at || !csize || !out_len || !coffset)) return bix_fail(h)("batch: NULL argument");
     if (cbytes < 0 || end_coffset < 0 || entry < 0) return bix_fail(h)("batch: negative argument");
     const int n_ref = h->n_ref;
     h->n_ref = -1;                               // a batch that fails leaves a handle that wants begin
+    if (clair_inf::check_blocks(bix_fail(h), n, h->max_blocks, cbytes, in_at, csize, out_len)) return 1;
     int64_t len = h->carry;
     for (int i = 0; i < n; ++i) {
-        if (csize[i] < 26 || csize[i] > BLOCK_MAX) return bix_fail(h)("block %d: csize %d (26 .. 65536)", i, csize[i]);
-        if (in_at[i] < 0 || in_at[i] > cbytes - csize[i]) return bix_fail(h)("block %d: compressed bytes [%lld, +%d) outside the %lld given", i, (long long)in_at[i], csize[i], (long long)cbytes);
-        if (out_len[i] < 0 || out_len[i] > BLOCK_MAX) return bix_fail(h)("block %d: out_len %d (0 .. 65536)", i, out_len[i]);
         if (coffset[i] < 0) return bix_fail(h)("block %d: negative offset", i);
         len += out_len[i];
     }
@@ -342,14 +339,13 @@ int clair_bamidx_batch(clair_bamidx_t *h, const uint8_t *cdata, int64_t cbytes, 
     CLAIR_HIP_TRY(bix_fail(h), at_least(h->d_stream[to], (size_t)(len + PAD)));
     uint8_t *d_stream = h->d_stream[to].as<uint8_t>();
     if (h->carry) CLAIR_HIP_TRY(bix_fail(h), hipMemcpyAsync(d_stream, h->d_stream[h->cur].as<uint8_t>() + h->carry_at, (size_t)h->carry, hipMemcpyDeviceToDevice, h->stream));
-    // meta, one copy: the table (at, voff: n_tab entries each), then per block in_at, out_at (int64), csize, out_len, status (int32)
+    // meta, one copy: the table (at, voff: n_tab entries each), then the blocks' arrays (inflate_launch.h)
     const int n_tab = n + 1 + (h->carry ? 1 : 0);
     const size_t N = (size_t)n, T = (size_t)n_tab;
-    h->meta.assign(T * 16 + N * (16 + 12), 0);
+    h->meta.assign(T * 16 + N * clair_inf::META_PER_BLOCK, 0);
     int64_t *m_at = (int64_t *)h->meta.data();
     uint64_t *m_voff = (uint64_t *)(m_at + T);
-    int64_t *m_in_at = (int64_t *)(m_voff + T), *m_out_at = m_in_at + N;
-    int32_t *m_csize = (int32_t *)(m_out_at + N), *m_out_len = m_csize + N;
+    const clair_inf::BlockMeta mb = clair_inf::carve_meta(m_voff + T, N);
     {
         int k = 0;
         int64_t pos = h->carry;
@@ -357,10 +353,10 @@ int clair_bamidx_batch(clair_bamidx_t *h, const uint8_t *cdata, int64_t cbytes, 
         for (int i = 0; i < n; ++i) {
             m_at[k] = pos;
             m_voff[k++] = (uint64_t)coffset[i] << 16;
-            m_in_at[i] = in_at[i];
-            m_out_at[i] = pos;
-            m_csize[i] = csize[i];
-            m_out_len[i] = out_len[i];
+            mb.in_at[i] = in_at[i];
+            mb.out_at[i] = pos;
+            mb.csize[i] = csize[i];
+            mb.out_len[i] = out_len[i];
             pos += out_len[i];
         }
         m_at[k] = len;
@@ -370,9 +366,7 @@ int clair_bamidx_batch(clair_bamidx_t *h, const uint8_t *cdata, int64_t cbytes, 
     CLAIR_HIP_TRY(bix_fail(h), hipMemcpyAsync(h->d_meta.p, h->meta.data(), h->meta.size(), hipMemcpyHostToDevice, h->stream));
     const int64_t *d_at = h->d_meta.as<int64_t>();
     const uint64_t *d_voff = (const uint64_t *)(d_at + T);
-    const int64_t *d_in_at = (const int64_t *)(d_voff + T), *d_out_at = d_in_at + N;
-    const int32_t *d_csize = (const int32_t *)(d_out_at + N), *d_out_len = d_csize + N;
-    int32_t *d_status = (int32_t *)(d_out_len + N);
+    const clair_inf::BlockMeta db = clair_inf::carve_meta(h->d_meta.as<int64_t>() + 2 * T, N);
     std::vector<int32_t> status(N, 0);
     if (n > 0) {
         // (the inflate kernel reads whole 16-byte pieces around each deflate stream)
@@ -381,17 +375,15 @@ int clair_bamidx_batch(clair_bamidx_t *h, const uint8_t *cdata, int64_t cbytes, 
             CLAIR_HIP_TRY(bix_fail(h), hipMemsetAsync(h->d_cdata.p, 0, h->d_cdata.bytes, h->stream));
         }
         CLAIR_HIP_TRY(bix_fail(h), hipMemcpyAsync(h->d_cdata.p, cdata, (size_t)cbytes, hipMemcpyHostToDevice, h->stream));
-        CLAIR_HIP_TRY(bix_fail(h), clair_inf::launch_bgzf(h->stream, h->d_cdata.as<uint8_t>(), n, d_in_at, d_csize, d_out_at, d_out_len, d_stream, d_status));
-        CLAIR_HIP_TRY(bix_fail(h), hipMemcpyAsync(status.data(), d_status, N * 4, hipMemcpyDeviceToHost, h->stream));
+        CLAIR_HIP_TRY(bix_fail(h), clair_inf::launch_bgzf(h->stream, h->d_cdata.as<uint8_t>(), n, db, d_stream));
+        CLAIR_HIP_TRY(bix_fail(h), hipMemcpyAsync(status.data(), db.status, N * 4, hipMemcpyDeviceToHost, h->stream));
     }
     // 2. the record starts (waits for the stream: the statuses are here with them)
     Framed fr;
     if (frame(h, d_stream, len, entry, &fr)) return 1;
     if (len == 0) CLAIR_HIP_TRY(bix_fail(h), hipStreamSynchronize(h->stream));
-    static const char *const what[] = {"corrupt deflate data", "inflated size differs from ISIZE", "CRC32 mismatch"};
     for (int i = 0; i < n; ++i)
-        if (status[(size_t)i] != 0)
-            return bix_fail(h)("BGZF block at compressed offset %lld: %s", (long long)coffset[i], what[status[(size_t)i] >= 1 && status[(size_t)i] <= 3 ? status[(size_t)i] - 1 : 0]);
+        if (status[(size_t)i] != 0) return bix_fail(h)("BGZF block at compressed offset %lld: %s", (long long)coffset[i], clair_inf::bgzf_status_text(status[(size_t)i]));
     const int64_t n_rec = fr.n_rec;
     const Bytes m{d_stream};
     const Table table{d_at, d_voff, n_tab, n_ref, h->d_first_window.as<int64_t>()};

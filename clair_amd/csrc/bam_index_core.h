@@ -1,7 +1,8 @@
 // The rules of index_bam (docs/index_bam.md) that the device (csrc/bam_index.hip) and its host twin (hostsrc/host_bam_index.cpp) share: the
 // frame step over a stream of BAM records, the fields of a record that a .bai is made of, the order check, the virtual offset of a stream
-// position and the wording of every verdict.  Plain C++17 over a small memory context (Bytes); CLAIR_BIX_FN is `__host__ __device__ inline`
-// in the device's translation unit.
+// position and the wording of every verdict.  The frame step itself, the size rule and the CIGAR span are a record's own rules
+// (csrc/bam_record_core.h).  Plain C++17 over a small memory context (Bytes); CLAIR_BIX_FN is `__host__ __device__ inline` in the device's
+// translation unit.
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -9,8 +10,14 @@
 #ifndef CLAIR_BIX_FN
 #define CLAIR_BIX_FN inline
 #endif
+#ifndef CLAIR_REC_FN
+#define CLAIR_REC_FN CLAIR_BIX_FN
+#endif
+#include "bam_record_core.h"
 
 namespace clair_bix {
+
+using namespace clair_rec;                   // Bytes, step and STEP_*, describe_bad_step, describe_cut
 
 constexpr uint32_t SEG_MIN = 64, SEG_MAX = 8192, SEG_DEFAULT = 8192;      // bytes of a framing segment: a power of two
 constexpr uint32_t MIN_RECORD = 36;                                      // 4 + block_size, block_size >= 32
@@ -23,25 +30,6 @@ constexpr int STATE_WORDS = 8;
 enum { ST_RECORDS_BEFORE = 0, ST_PREV_TID, ST_PREV_POS, ST_N_RECORDS, ST_N_RUNS, ST_LAST_TID, ST_LAST_POS, ST_CARRY };
 // what clair_*bamidx_debug_frame reports
 enum { FR_N_STARTS = 0, FR_TAIL, FR_BAD, FR_SENTINELS, FR_WORDS };
-
-struct Bytes {
-    const uint8_t *p;
-    CLAIR_BIX_FN uint32_t byte(int64_t at) const { return p[at]; }
-    CLAIR_BIX_FN uint32_t le16(int64_t at) const { return byte(at) | byte(at + 1) << 8; }
-    CLAIR_BIX_FN uint32_t le32(int64_t at) const { return byte(at) | byte(at + 1) << 8 | byte(at + 2) << 16 | byte(at + 3) << 24; }
-};
-
-// ---- the frame step.  A record at o is its size word and block_size bytes; the next one starts right behind it.  No address is ever formed
-// from a size word that was not checked: at an offset that is no record start the word is garbage, and that is the normal case.
-enum { STEP_NEXT = 0, STEP_BAD = 1, STEP_PAST = 2 };       // BAD: no record can start here; PAST: it would not end inside the stream
-CLAIR_BIX_FN int step(const Bytes &m, int64_t o, int64_t len, int64_t *next) {
-    if (o + 4 > len) return STEP_PAST;
-    const uint32_t block_size = m.le32(o);
-    if (block_size < 32 || (uint64_t)block_size + 4 > (uint64_t)INT32_MAX) return STEP_BAD;
-    if (o + 4 + (int64_t)block_size > len) return STEP_PAST;
-    *next = o + 4 + (int64_t)block_size;
-    return STEP_NEXT;
-}
 
 // the step seen from a segment that starts at `base`, as an offset from the base: >= seg, the chain leaves the segment there (a long record
 // may leave it by many segments); == o, the chain stops at o (bad or past the end: absorbing)
@@ -90,7 +78,7 @@ CLAIR_BIX_FN uint32_t seg_records(const Bytes &m, int64_t len, uint32_t seg, int
 }
 
 // ---- a record's fields
-enum { V_OK = 0, V_L_SEQ, V_FIELDS, V_TID, V_POS, V_TOO_FAR, V_UNSORTED };
+enum { V_OK = 0, V_L_SEQ = SIZES_L_SEQ, V_FIELDS = SIZES_FIELDS, V_TID, V_POS, V_TOO_FAR, V_UNSORTED };
 struct Fields {
     int32_t tid, pos;
     int64_t end;                 // bam_endpos: pos + max(reference span of the stored CIGAR, 1); span 0 for an unmapped record
@@ -118,18 +106,11 @@ CLAIR_BIX_FN Fields fields(const Bytes &m, int64_t o, int n_ref) {
     f.end = (int64_t)f.pos + 1;
     f.bin = 4680;
     f.verdict = V_OK;
-    if (l_seq < 0) { f.verdict = V_L_SEQ; return f; }
-    if (32ull + l_read_name + 4ull * n_cigar + ((uint64_t)l_seq + 1) / 2 + (uint64_t)l_seq > (uint64_t)block_size) { f.verdict = V_FIELDS; return f; }
+    const int sizes = sizes_verdict(block_size, l_read_name, n_cigar, l_seq);
+    if (sizes == SIZES_L_SEQ || sizes == SIZES_FIELDS) { f.verdict = sizes; return f; }     // (an empty read name does not trouble an index)
     if (f.tid < -1 || f.tid >= n_ref) { f.verdict = V_TID; return f; }
     if (f.pos < -1) { f.verdict = V_POS; return f; }
-    int64_t span = 0;
-    if (!(f.flag & 4)) {
-        const int64_t cigar = o + 36 + l_read_name;
-        for (uint32_t i = 0; i < n_cigar; ++i) {
-            const uint32_t c = m.le32(cigar + 4ll * i), op = c & 15;
-            if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) span += c >> 4;
-        }
-    }
+    const int64_t span = (f.flag & 4) ? 0 : cigar_span(m, o + 36 + l_read_name, n_cigar);
     f.end = (int64_t)f.pos + (span > 1 ? span : 1);
     if (f.tid >= 0) {
         if (f.end > POS_LIMIT) { f.verdict = V_TOO_FAR; return f; }
@@ -183,17 +164,7 @@ inline void describe(char *buf, size_t cap, const Detail &d) {
         break;
     default:
         snprintf(buf, cap, "record %lld at virtual offset %llu is malformed: %s", (long long)d.index, (unsigned long long)d.voffset,
-                 d.verdict == V_L_SEQ ? "negative l_seq" : d.verdict == V_FIELDS ? "fields longer than block_size"
-                 : d.verdict == V_TID ? "reference id not in the header" : "position below -1");
+                 d.verdict == V_L_SEQ || d.verdict == V_FIELDS ? sizes_text(d.verdict) : d.verdict == V_TID ? "reference id not in the header" : "position below -1");
     }
 }
-// the frame verdicts, in the wording of clair_host_bam_next
-inline void describe_bad_step(char *buf, size_t cap, uint64_t voffset, uint32_t block_size) {
-    if (block_size < 32) snprintf(buf, cap, "record at virtual offset %llu: block_size %u < 32", (unsigned long long)voffset, block_size);
-    else snprintf(buf, cap, "record at virtual offset %llu: block_size %u", (unsigned long long)voffset, block_size);
-}
-inline void describe_cut(char *buf, size_t cap, uint64_t voffset) {
-    snprintf(buf, cap, "the stream ends inside a record (virtual offset %llu)", (unsigned long long)voffset);
-}
-
 }  // namespace clair_bix

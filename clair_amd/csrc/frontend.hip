@@ -21,6 +21,8 @@
 #include "device_buffer.h"
 #include "device_scan.h"
 #include "hip_status.h"
+#define CLAIR_REC_FN __device__ inline
+#include "bam_record_core.h"
 #include "subsample_core.h"
 
 #include <algorithm>
@@ -1116,41 +1118,12 @@ __device__ inline CigarWalk walk_cigar_bam(const uint8_t *rec, uint64_t off, uin
     return w;
 }
 
-// A record whose stored CIGAR is the <l_seq>S<ref_len>N placeholder (more than 65 535 operations) keeps the real one in CG:B:I: htslib's
-// bam_tag2cigar substitutes it when it reads the record, so `samtools view` prints it.  -> true and its offset / length when it applies.
-__device__ inline bool bam_real_cigar(const uint8_t *rec, uint64_t aux, uint64_t end, uint32_t n_cigar, uint64_t *cg_off, uint32_t *cg_n) {
-    while (aux + 3 <= end) {
-        const uint8_t t0 = rec[aux], t1 = rec[aux + 1], type = rec[aux + 2];
-        const bool cg = t0 == 'C' && t1 == 'G';
-        const uint64_t v = aux + 3;
-        uint64_t size = 0;
-        switch (type) {
-        case 'A': case 'c': case 'C': size = 1; break;
-        case 's': case 'S': size = 2; break;
-        case 'i': case 'I': case 'f': size = 4; break;
-        case 'Z': case 'H': { uint64_t z = v; while (z < end && rec[z]) ++z; if (z >= end) return false; size = z - v + 1; break; }
-        case 'B': {
-            if (v + 5 > end) return false;
-            const uint8_t sub = rec[v];
-            const uint32_t count = bam_u32(rec, v + 1);
-            const uint64_t each = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : (sub == 'i' || sub == 'I' || sub == 'f') ? 4 : 0;
-            if (!each || (uint64_t)count * each > end - v - 5) return false;
-            if (cg) {
-                if (!(sub == 'I' || sub == 'i') || count < n_cigar || count >= (1u << 29)) return false;
-                *cg_off = v + 5;
-                *cg_n = count;
-                return true;
-            }
-            size = 5 + (uint64_t)count * each;
-            break;
-        }
-        default: return false;
-        }
-        if (cg) return false;
-        aux = v + size;
-    }
-    return false;
-}
+// the records as csrc/bam_record_core.h reads them: single bytes as they lie, 32-bit values as every other field here
+struct BamBytes {
+    const uint8_t *rec;
+    __device__ uint32_t byte(uint64_t at) const { return rec[at]; }
+    __device__ uint32_t le32(uint64_t at) const { return bam_u32(rec, at); }
+};
 
 // subsample_hash of the read name at `off`: n bytes, or up to an earlier NUL.  A dword at a time like every other field, never a byte load
 // near the end of the buffer; the bytes of a dword go through the shared rule one by one.
@@ -1192,8 +1165,7 @@ __global__ __launch_bounds__(256) void fe_bam_records_kernel(const uint8_t *rec,
         n_cigar = w4 & 0xffff;
         flag = w4 >> 16;
         l_seq = (int32_t)bam_u32(rec, at + 20);
-        bad = l_seq < 0 || l_read_name == 0
-              || 32ull + l_read_name + 4ull * n_cigar + ((uint64_t)l_seq + 1) / 2 + (uint64_t)l_seq > (uint64_t)block_size;
+        bad = clair_rec::sizes_verdict(block_size, l_read_name, n_cigar, l_seq) != clair_rec::SIZES_OK;
     }
     if (bad) {                                                                // the host renderer on the same records names the field
         atomicMin(&state->malformed, (uint32_t)(k + 1));
@@ -1206,8 +1178,8 @@ __global__ __launch_bounds__(256) void fe_bam_records_kernel(const uint8_t *rec,
     uint32_t n_ops_cigar = n_cigar;
     if (n_cigar > 0 && ref_id >= 0 && pos0 >= 0) {
         const uint32_t c0 = bam_u32(rec, cigar_stored);
-        if ((c0 & 15) == 4 && (c0 >> 4) == (uint32_t)l_seq)                  // rare: look for CG
-            bam_real_cigar(rec, seq_off + ((uint64_t)l_seq + 1) / 2 + (uint64_t)l_seq, rec_end, n_cigar, &cigar_off, &n_ops_cigar);
+        if ((c0 & 15) == 4 && (c0 >> 4) == (uint32_t)l_seq)                  // rare: look for CG:B:I (a stored CIGAR of more than 65 535 operations)
+            clair_rec::real_cigar(BamBytes{rec}, seq_off + ((uint64_t)l_seq + 1) / 2 + (uint64_t)l_seq, rec_end, n_cigar, &cigar_off, &n_ops_cigar);
     }
     const CigarWalk w = walk_cigar_bam<false>(rec, cigar_off, n_ops_cigar, 0, nullptr, nullptr, 0);
     const int64_t pos1 = (int64_t)pos0 + 1;

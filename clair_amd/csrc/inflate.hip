@@ -144,9 +144,9 @@ __global__ __launch_bounds__(64) void inflate_bgzf_kernel(const uint8_t *__restr
 
 #include "inflate_launch.h"
 
-hipError_t clair_inf::launch_bgzf(hipStream_t stream, const uint8_t *cdata, int n, const int64_t *in_at, const int32_t *csize, const int64_t *out_at,
-                                  const int32_t *out_len, uint8_t *out, int32_t *status) {
-    hipLaunchKernelGGL(inflate_bgzf_kernel, dim3((unsigned)n), dim3(64), 0, stream, cdata, n, in_at, csize, out_at, out_len, out, status);
+hipError_t clair_inf::launch_bgzf(hipStream_t stream, const uint8_t *cdata, int n, const BlockMeta &meta, uint8_t *out) {
+    hipLaunchKernelGGL(inflate_bgzf_kernel, dim3((unsigned)n), dim3(64), 0, stream, cdata, n, (const int64_t *)meta.in_at, (const int32_t *)meta.csize,
+                       (const int64_t *)meta.out_at, (const int32_t *)meta.out_len, out, meta.status);
     return hipGetLastError();
 }
 
@@ -162,8 +162,6 @@ struct clair_inflate : StagedStream {
 namespace {
 
 constexpr int64_t BLOCK_MAX = 65536;             // a BGZF block, compressed or inflated
-// per block: in_at, out_at (int64), csize, out_len, status (int32)
-constexpr int64_t META_PER_BLOCK = 2 * 8 + 3 * 4;
 
 std::string g_inf_error;
 inline HipFail inf_fail(clair_inflate *h) { return {h ? h->error : g_inf_error}; }
@@ -181,7 +179,7 @@ int clair_inflate_create(int device, int max_blocks, clair_inflate_t **out) {
     if (hip_device_check(inf_fail(nullptr), device, "the device inflate runs on an MI355X only (the host inflate is --bam_inflate host)")) return 1;
     clair_inflate *h = new clair_inflate;
     h->cap = (int64_t)max_blocks * BLOCK_MAX;
-    const size_t meta = (size_t)max_blocks * META_PER_BLOCK;
+    const size_t meta = (size_t)max_blocks * clair_inf::META_PER_BLOCK;
     // (d_in + 32: the kernel reads whole 16-byte pieces around each stream)
     if (h->open(inf_fail(nullptr), device, max_blocks, (size_t)h->cap, (size_t)h->cap, meta, (size_t)h->cap + 32)) {
         clair_inflate_destroy(h);
@@ -200,43 +198,34 @@ void clair_inflate_destroy(clair_inflate_t *h) {
 int clair_inflate_blocks(clair_inflate_t *h, const uint8_t *cdata, int64_t cbytes, int n, const int64_t *in_at, const int32_t *csize,
                          const int64_t *out_at, const int32_t *out_len, uint8_t *out, int32_t *status) {
     if (!h) return inf_fail(nullptr)("inflate handle is NULL");
-    if (n < 0 || n > h->max_blocks) return inf_fail(h)("%d blocks in a batch: 0 .. max_blocks = %d", n, h->max_blocks);
+    if (n > 0 && (!cdata || !in_at || !csize || !out_at || !out_len || !out || !status)) return inf_fail(h)("NULL argument");
+    if (n > 0 && (cbytes < 0 || cbytes > h->cap)) return inf_fail(h)("%lld compressed bytes: 0 .. %lld", (long long)cbytes, (long long)h->cap);
+    if (clair_inf::check_blocks(inf_fail(h), n, h->max_blocks, cbytes, in_at, csize, out_len)) return 1;
     if (n == 0) return 0;
-    if (!cdata || !in_at || !csize || !out_at || !out_len || !out || !status) return inf_fail(h)("NULL argument");
-    if (cbytes < 0 || cbytes > h->cap) return inf_fail(h)("%lld compressed bytes: 0 .. %lld", (long long)cbytes, (long long)h->cap);
     int64_t out_lo = INT64_MAX, out_hi = 0;
     for (int i = 0; i < n; ++i) {
-        if (csize[i] < 26 || csize[i] > BLOCK_MAX) return inf_fail(h)("block %d: csize %d (26 .. 65536)", i, csize[i]);
-        if (in_at[i] < 0 || in_at[i] > cbytes - csize[i]) return inf_fail(h)("block %d: compressed bytes [%lld, +%d) outside the %lld given", i, (long long)in_at[i], csize[i], (long long)cbytes);
-        if (out_len[i] < 0 || out_len[i] > BLOCK_MAX) return inf_fail(h)("block %d: out_len %d (0 .. 65536)", i, out_len[i]);
         if (out_at[i] < 0 || out_at[i] > h->cap - out_len[i]) return inf_fail(h)("block %d: output [%lld, +%d) outside the handle's %lld bytes", i, (long long)out_at[i], out_len[i], (long long)h->cap);
         out_lo = std::min(out_lo, out_at[i]);
         out_hi = std::max(out_hi, out_at[i] + out_len[i]);
     }
     CLAIR_HIP_TRY(inf_fail(h), hipSetDevice(h->device));
     const size_t N = (size_t)h->max_blocks;
-    int64_t *m_in_at = h->h_meta.as<int64_t>(), *m_out_at = m_in_at + N;
-    int32_t *m_csize = (int32_t *)(m_out_at + N), *m_out_len = m_csize + N, *m_status = m_out_len + N;
+    const clair_inf::BlockMeta m = clair_inf::carve_meta(h->h_meta.p, N), d = clair_inf::carve_meta(h->d_meta.p, N);
     uint8_t *h_in = h->h_in.as<uint8_t>(), *h_out = h->h_out.as<uint8_t>(), *d_in = h->d_in.as<uint8_t>(), *d_out = h->d_out.as<uint8_t>();
     memcpy(h_in, cdata, (size_t)cbytes);
-    memcpy(m_in_at, in_at, (size_t)n * 8);
-    memcpy(m_out_at, out_at, (size_t)n * 8);
-    memcpy(m_csize, csize, (size_t)n * 4);
-    memcpy(m_out_len, out_len, (size_t)n * 4);
-    const int64_t *d_in_at = h->d_meta.as<int64_t>(), *d_out_at = d_in_at + N;
-    const int32_t *d_csize = (const int32_t *)(d_out_at + N), *d_out_len = d_csize + N;
-    int32_t *d_status = (int32_t *)(d_out_len + N);
+    memcpy(m.in_at, in_at, (size_t)n * 8);
+    memcpy(m.out_at, out_at, (size_t)n * 8);
+    memcpy(m.csize, csize, (size_t)n * 4);
+    memcpy(m.out_len, out_len, (size_t)n * 4);
     CLAIR_HIP_TRY(inf_fail(h), hipMemcpyAsync(d_in, h_in, (size_t)cbytes, hipMemcpyHostToDevice, h->stream));
-    CLAIR_HIP_TRY(inf_fail(h), hipMemcpyAsync(h->d_meta.p, h->h_meta.p, N * (2 * 8 + 2 * 4), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(clair_inf::inflate_bgzf_kernel, dim3((unsigned)n), dim3(64), 0, h->stream, (const uint8_t *)d_in, n, d_in_at, d_csize, d_out_at,
-                       d_out_len, d_out, d_status);
-    CLAIR_HIP_TRY(inf_fail(h), hipGetLastError());
+    CLAIR_HIP_TRY(inf_fail(h), hipMemcpyAsync(h->d_meta.p, h->h_meta.p, N * clair_inf::META_FILLED, hipMemcpyHostToDevice, h->stream));
+    CLAIR_HIP_TRY(inf_fail(h), clair_inf::launch_bgzf(h->stream, d_in, n, d, d_out));
     if (out_hi > out_lo) CLAIR_HIP_TRY(inf_fail(h), hipMemcpyAsync(h_out + out_lo, d_out + out_lo, (size_t)(out_hi - out_lo), hipMemcpyDeviceToHost, h->stream));
-    CLAIR_HIP_TRY(inf_fail(h), hipMemcpyAsync(m_status, d_status, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+    CLAIR_HIP_TRY(inf_fail(h), hipMemcpyAsync(m.status, d.status, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
     CLAIR_HIP_TRY(inf_fail(h), hipStreamSynchronize(h->stream));
     for (int i = 0; i < n; ++i) {
-        status[i] = m_status[i];
-        if (m_status[i] == 0 && out_len[i]) memcpy(out + out_at[i], h_out + out_at[i], (size_t)out_len[i]);
+        status[i] = m.status[i];
+        if (m.status[i] == 0 && out_len[i]) memcpy(out + out_at[i], h_out + out_at[i], (size_t)out_len[i]);
     }
     return 0;
 }

@@ -382,5 +382,24 @@ CLAIR_INF_FN int bgzf_status(bool ended, uint32_t produced, uint32_t isize, uint
     return crc == want ? BGZF_OK : BGZF_CRC;
 }
 
+// (host side only, as what follows) the verdicts as words; a status that is none of them reads as the first
+inline const char *bgzf_status_text(int status) {
+    static const char *const what[] = {"corrupt deflate data", "inflated size differs from ISIZE", "CRC32 mismatch"};
+    return what[status >= BGZF_CORRUPT && status <= BGZF_CRC ? status - 1 : 0];
+}
+
+// A batch of block descriptors before anything reads through them: n within max_blocks, each block's csize and out_len those of a BGZF block
+// and its compressed bytes inside the cbytes given.  -> 0, or what `fail` (printf-style: a HipFail, clair_host_fail) returns for the first breach.
+template <class Fail>
+inline int check_blocks(const Fail &fail, int n, int max_blocks, int64_t cbytes, const int64_t *in_at, const int32_t *csize, const int32_t *out_len) {
+    if (n < 0 || n > max_blocks) return fail("%d blocks in a batch: 0 .. max_blocks = %d", n, max_blocks);
+    for (int i = 0; i < n; ++i) {
+        if (csize[i] < 26 || csize[i] > 65536) return fail("block %d: csize %d (26 .. 65536)", i, csize[i]);
+        if (in_at[i] < 0 || in_at[i] > cbytes - csize[i]) return fail("block %d: compressed bytes [%lld, +%d) outside the %lld given", i, (long long)in_at[i], csize[i], (long long)cbytes);
+        if (out_len[i] < 0 || out_len[i] > 65536) return fail("block %d: out_len %d (0 .. 65536)", i, out_len[i]);
+    }
+    return 0;
+}
+
 }  // namespace clair_inf
 #endif

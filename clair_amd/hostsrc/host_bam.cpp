@@ -2,41 +2,39 @@
 // Plain C++17 + zlib, no HIP.
 //
 // What `samtools view -F 2316 <bam> <region>` does before it formats text, restated for the one use this project makes of it:
-//   - BGZF: blocks inflated on N threads, each block's CRC32 and ISIZE checked; a missing EOF block is a warning (as htslib's);
-//     clair_host_bam_set_inflater hands the batches of a query to another inflater instead (the device's: callVarBam --bam_inflate device);
-//   - the BAM header: magic, text, the reference names and lengths;
+//   - BGZF: which blocks a query reads and how many to a batch; the block format and the zlib inflate (N threads, each block's CRC32 and
+//     ISIZE checked) are hostsrc/bgzf_file.h.  A missing EOF block is a warning (as htslib's); clair_host_bam_set_inflater hands the batches
+//     of a query to another inflater instead (the device's: callVarBam --bam_inflate device);
+//   - the BAM header (hostsrc/bam_header.h): the reference names and lengths;
 //   - region selection with the .bai: bins overlapping the region, chunks before the linear index's minimum offset dropped, the rest
 //     sorted and merged (htslib's hts_itr_query), or a scan from the first record without an index;
-//   - the record walker: whole records, framing checked (block_size >= 32, inside the stream), the walk ending at the first record of
-//     the contig that starts past the region (hts_itr_next).
+//   - the record walker: whole records, framed by the step every reader of records here takes (csrc/bam_record_core.h), the walk ending at
+//     the first record of the contig that starts past the region (hts_itr_next).
 // The binary records go to the device as they are (clair_frontend_add_bam, csrc/frontend.hip).  clair_host_bam_render turns them into the
-// 11 mandatory columns samtools prints -- the text the host stages and the device front end's fall-back read -- and clair_host_faidx
+// 11 mandatory columns samtools prints -- the text the host stages and the device front end's fall-back read; the size rule, the CIGAR
+// span and the walk to the real CIGAR are csrc/bam_record_core.h, the device decoder's own -- and clair_host_faidx
 // is `samtools faidx` for one region.  clair_host_bam_set_subsample adds `-s` to that view (csrc/subsample_core.h, docs/subsample.md).
 #include "../../include/clair_host.h"
 #include "../csrc/subsample_core.h"
-
-#include <zlib.h>
+#include "bam_header.h"
+#include "bgzf_file.h"
 
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <vector>
-
-int clair_host_fail(const char *fmt, ...);   // host_io.cpp
 
 namespace {
 
-constexpr int BGZF_HEADER = 18, BGZF_FOOTER = 8, BGZF_MAX_BLOCK = 65536;
+using namespace clair_rec;
+using namespace clair_bgzf;
+
 constexpr uint16_t VIEW_FILTER = 2316;       // shared/param.py:6: unmapped, mate unmapped, secondary, supplementary
-const uint8_t BGZF_EOF[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 const char NT16[] = "=ACMGRSVTWYHKDBN";
 const char CIGAR_OPS[] = "MIDNSHP=XB??????";
 
-inline uint16_t u16(const uint8_t *p) { return (uint16_t)(p[0] | p[1] << 8); }
-inline uint32_t u32(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
 inline int32_t i32(const uint8_t *p) { return (int32_t)u32(p); }
 inline uint64_t u64(const uint8_t *p) { return (uint64_t)u32(p) | (uint64_t)u32(p + 4) << 32; }
 
@@ -45,72 +43,28 @@ struct Block {                               // one compressed block of a batch
     uint32_t csize;                          // whole block, header and footer included
     size_t in_at;                            // where its bytes are in the batch's compressed buffer
     size_t out_at, out_len;                  // where its inflated bytes go
-    std::string error;
 };
 
 struct Chunk { uint64_t beg, end; };         // virtual offsets, [beg, end)
 
-// the size of a record's fixed and variable parts: 0 when they fit in block_size, else what is wrong
+// what is wrong with the sizes of a record's fixed and variable parts or with its read name, or nullptr
 const char *record_sizes(const uint8_t *r, uint32_t block_size) {
-    const uint32_t l_read_name = r[12], n_cigar = u16(r + 16);
-    const int32_t l_seq = i32(r + 20);
-    if (l_seq < 0) return "negative l_seq";
-    const uint64_t need = 32ull + l_read_name + 4ull * n_cigar + ((uint64_t)l_seq + 1) / 2 + (uint64_t)l_seq;
-    if (need > (uint64_t)block_size) return "fields longer than block_size";
-    if (l_read_name == 0 || r[4 + 32 + l_read_name - 1] != 0) return "read name not NUL-terminated";
-    return nullptr;
+    const uint32_t l_read_name = r[12];
+    int verdict = sizes_verdict(block_size, l_read_name, u16(r + 16), i32(r + 20));
+    if (verdict == SIZES_OK && r[4 + 32 + l_read_name - 1] != 0) verdict = SIZES_NAME;
+    return verdict == SIZES_OK ? nullptr : sizes_text(verdict);
 }
 
-// the CG:B:I tag of a record whose stored CIGAR is the kSmN placeholder (more than 65 535 operations: htslib's bam_tag2cigar):
-// -> pointer to the real operations and their count, or nullptr when the stored CIGAR stands
-const uint8_t *real_cigar(const uint8_t *r, uint32_t block_size, uint32_t *n_ops) {
+// the record's CIGAR as `samtools view` prints it: the stored one, or the one in CG:B:I behind the kSmN placeholder.  r: after record_sizes
+const uint8_t *printed_cigar(const uint8_t *r, uint32_t block_size, uint32_t *n_ops) {
     const uint32_t l_read_name = r[12], n_cigar = u16(r + 16);
     const int32_t ref_id = i32(r + 4), pos = i32(r + 8), l_seq = i32(r + 20);
-    const uint8_t *cigar = r + 36 + l_read_name;
-    if (n_cigar == 0 || ref_id < 0 || pos < 0) return nullptr;
-    if ((u32(cigar) & 15) != 4 || (u32(cigar) >> 4) != (uint32_t)l_seq) return nullptr;
-    const uint8_t *p = cigar + 4ull * n_cigar + ((uint64_t)l_seq + 1) / 2 + (uint64_t)l_seq, *end = r + 4 + block_size;
-    while (p + 3 <= end) {
-        const uint8_t type = p[2];
-        const uint8_t *v = p + 3;
-        const bool cg = p[0] == 'C' && p[1] == 'G';
-        size_t size = 0;
-        switch (type) {
-        case 'A': case 'c': case 'C': size = 1; break;
-        case 's': case 'S': size = 2; break;
-        case 'i': case 'I': case 'f': size = 4; break;
-        case 'Z': case 'H': { const uint8_t *z = v; while (z < end && *z) ++z; if (z >= end) return nullptr; size = (size_t)(z - v) + 1; break; }
-        case 'B': {
-            if (v + 5 > end) return nullptr;
-            const uint8_t sub = v[0];
-            const uint32_t count = u32(v + 1);
-            size_t each = sub == 'c' || sub == 'C' ? 1 : sub == 's' || sub == 'S' ? 2 : sub == 'i' || sub == 'I' || sub == 'f' ? 4 : 0;
-            if (!each) return nullptr;
-            if ((uint64_t)count * each > (uint64_t)(end - v - 5)) return nullptr;
-            if (cg) {
-                if (!(sub == 'I' || sub == 'i') || count < n_cigar || count >= (1u << 29)) return nullptr;
-                *n_ops = count;
-                return v + 5;
-            }
-            size = 5 + (size_t)count * each;
-            break;
-        }
-        default: return nullptr;
-        }
-        if (cg) return nullptr;              // a CG tag of another type: the stored CIGAR stands (bam_tag2cigar)
-        p = v + size;
-    }
-    return nullptr;
-}
-
-// reference span of a CIGAR (bam_cigar2rlen): M D N = X
-int64_t cigar_rlen(const uint8_t *cigar, uint32_t n) {
-    int64_t rlen = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        const uint32_t c = u32(cigar + 4ull * i), op = c & 15;
-        if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rlen += c >> 4;
-    }
-    return rlen;
+    const uint64_t cigar = 36 + l_read_name;
+    uint64_t cg = cigar;
+    *n_ops = n_cigar;
+    if (n_cigar > 0 && ref_id >= 0 && pos >= 0 && (u32(r + cigar) & 15) == 4 && (u32(r + cigar) >> 4) == (uint32_t)l_seq)
+        real_cigar(Bytes{r}, cigar + 4ull * n_cigar + ((uint64_t)l_seq + 1) / 2 + (uint64_t)l_seq, 4ull + block_size, n_cigar, &cg, n_ops);
+    return r + cg;
 }
 
 void append_uint(std::string &s, uint64_t v) { char b[24]; int n = snprintf(b, sizeof b, "%llu", (unsigned long long)v); s.append(b, (size_t)n); }
@@ -147,7 +101,7 @@ struct clair_bam {
     std::vector<uint8_t> cbuf;
     std::vector<Block> blocks;
     std::vector<uint8_t> obuf;
-    // another inflater for the batches (clair_host_bam_set_inflater); none: zlib on `threads` threads
+    // another inflater for the batches (clair_host_bam_set_inflater); none: zlib on `threads` threads.  hook_*: the batch as either takes it
     clair_host_inflate_fn inflater = nullptr;
     void *inflater_ctx = nullptr;
     std::vector<int64_t> hook_in_at, hook_out_at;
@@ -163,70 +117,26 @@ struct clair_bam {
         return fread(dst, 1, n, file) == n ? 0 : -1;
     }
 
-    // reads the compressed blocks from `coffset` while `more(coffset)` and the batch has room, inflates them on `threads` threads
+    // reads the compressed blocks from `coffset` up to the stop block while the batch has room, and inflates them
     int read_blocks(uint64_t coffset, size_t max_blocks, uint64_t stop_coffset, bool include_stop) {
         blocks.clear();
         cbuf.clear();
         size_t out = 0;
         while (blocks.size() < max_blocks && (coffset < stop_coffset || (include_stop && coffset == stop_coffset)) && coffset < file_size) {
-            uint8_t h[BGZF_HEADER];
-            if (coffset + BGZF_HEADER > file_size || read_at(coffset, h, BGZF_HEADER))
-                return clair_host_fail("%s: truncated BGZF block at compressed offset %llu", path.c_str(), (unsigned long long)coffset);
-            if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4) || u16(h + 10) != 6 || h[12] != 'B' || h[13] != 'C' || u16(h + 14) != 2)
-                return clair_host_fail("%s: not a BGZF block at compressed offset %llu", path.c_str(), (unsigned long long)coffset);
-            const uint32_t csize = (uint32_t)u16(h + 16) + 1;
-            if (csize < BGZF_HEADER + BGZF_FOOTER || coffset + csize > file_size)
-                return clair_host_fail("%s: truncated BGZF block at compressed offset %llu", path.c_str(), (unsigned long long)coffset);
-            Block b;
-            b.coffset = coffset;
-            b.csize = csize;
-            b.in_at = cbuf.size();
-            cbuf.resize(cbuf.size() + csize);
-            if (read_at(coffset, cbuf.data() + b.in_at, csize))
-                return clair_host_fail("%s: truncated BGZF block at compressed offset %llu", path.c_str(), (unsigned long long)coffset);
-            b.out_len = u32(cbuf.data() + b.in_at + csize - 4);
-            if (b.out_len > BGZF_MAX_BLOCK)
-                return clair_host_fail("%s: BGZF block at compressed offset %llu claims %zu bytes", path.c_str(), (unsigned long long)coffset, b.out_len);
-            b.out_at = out;
-            out += b.out_len;
-            blocks.push_back(b);
+            uint32_t csize = 0, isize = 0;
+            const size_t in_at = cbuf.size();
+            if (read_block(file, path.c_str(), file_size, coffset, cbuf, &csize, &isize)) return 1;
+            blocks.push_back(Block{coffset, csize, in_at, out, isize});
+            out += isize;
             coffset += csize;
         }
         next_coffset = coffset;
         obuf.resize(out + 1);
-        if (inflater && !blocks.empty()) return inflate_with_hook();
-        auto inflate_one = [&](Block &b) {
-            z_stream z{};
-            if (inflateInit2(&z, -15) != Z_OK) { b.error = "inflateInit2 failed"; return; }
-            z.next_in = cbuf.data() + b.in_at + BGZF_HEADER;
-            z.avail_in = b.csize - BGZF_HEADER - BGZF_FOOTER;
-            z.next_out = obuf.data() + b.out_at;
-            z.avail_out = (uInt)b.out_len + 1;       // one byte more: a block that inflates to more than ISIZE says so
-            const int rc = inflate(&z, Z_FINISH);
-            const size_t got = b.out_len + 1 - z.avail_out;
-            inflateEnd(&z);
-            if (rc != Z_STREAM_END) { b.error = "corrupt deflate data"; return; }
-            if (got != b.out_len) { b.error = "inflated size differs from ISIZE"; return; }
-            const uint32_t want = u32(cbuf.data() + b.in_at + b.csize - 8);
-            if ((uint32_t)crc32(0L, obuf.data() + b.out_at, (uInt)b.out_len) != want) b.error = "CRC32 mismatch";
-        };
-        const int nt = std::max(1, std::min<int>(threads, (int)blocks.size()));
-        if (nt == 1) {
-            for (Block &b : blocks) inflate_one(b);
-        } else {
-            std::vector<std::thread> pool;
-            for (int t = 0; t < nt; ++t)
-                pool.emplace_back([&, t] { for (size_t i = (size_t)t; i < blocks.size(); i += (size_t)nt) inflate_one(blocks[i]); });
-            for (auto &th : pool) th.join();
-        }
-        for (const Block &b : blocks)
-            if (!b.error.empty())
-                return clair_host_fail("%s: BGZF block at compressed offset %llu: %s", path.c_str(), (unsigned long long)b.coffset, b.error.c_str());
-        return 0;
+        return blocks.empty() ? 0 : inflate_batch();
     }
 
-    // the batch through the installed inflater; its first non-zero status becomes the message the zlib path gives for such a block
-    int inflate_with_hook() {
+    // the batch through zlib on `threads` threads or through the installed inflater; the first block with a status says what it is
+    int inflate_batch() {
         const size_t n = blocks.size();
         hook_in_at.resize(n); hook_out_at.resize(n); hook_csize.resize(n); hook_out_len.resize(n);
         hook_status.assign(n, 0);
@@ -236,15 +146,15 @@ struct clair_bam {
             hook_out_at[i] = (int64_t)blocks[i].out_at;
             hook_out_len[i] = (int32_t)blocks[i].out_len;
         }
-        if (inflater(inflater_ctx, cbuf.data(), (int64_t)cbuf.size(), (int)n, hook_in_at.data(), hook_csize.data(), hook_out_at.data(), hook_out_len.data(),
-                     obuf.data(), hook_status.data()) != 0)
+        if (!inflater)
+            inflate_blocks(threads, cbuf.data(), (int)n, hook_in_at.data(), hook_csize.data(), hook_out_at.data(), hook_out_len.data(), obuf.data(), hook_status.data());
+        else if (inflater(inflater_ctx, cbuf.data(), (int64_t)cbuf.size(), (int)n, hook_in_at.data(), hook_csize.data(), hook_out_at.data(), hook_out_len.data(),
+                          obuf.data(), hook_status.data()) != 0)
             return clair_host_fail("%s: the installed inflater failed on the %zu blocks from compressed offset %llu", path.c_str(), n,
                                    (unsigned long long)blocks[0].coffset);
-        static const char *const what[] = {"corrupt deflate data", "inflated size differs from ISIZE", "CRC32 mismatch"};
         for (size_t i = 0; i < n; ++i)
             if (hook_status[i] != 0)
-                return clair_host_fail("%s: BGZF block at compressed offset %llu: %s", path.c_str(), (unsigned long long)blocks[i].coffset,
-                                       what[hook_status[i] >= 1 && hook_status[i] <= 3 ? hook_status[i] - 1 : 0]);
+                return clair_host_fail("%s: BGZF block at compressed offset %llu: %s", path.c_str(), (unsigned long long)blocks[i].coffset, inflate_text(hook_status[i]));
         return 0;
     }
 
@@ -310,8 +220,7 @@ int clair_host_bam_open(const char *path, int threads, clair_bam_t **out) {
     if (fseeko(b->file, 0, SEEK_END) != 0) return bail(clair_host_fail("%s: cannot seek", path));
     b->file_size = (uint64_t)ftello(b->file);
     uint8_t magic[BGZF_HEADER] = {0};
-    if (b->file_size < BGZF_HEADER || b->read_at(0, magic, BGZF_HEADER) || magic[0] != 0x1f || magic[1] != 0x8b || magic[2] != 8 || !(magic[3] & 4)
-        || u16(magic + 10) != 6 || magic[12] != 'B' || magic[13] != 'C')
+    if (b->file_size < BGZF_HEADER || b->read_at(0, magic, BGZF_HEADER) || !gzip_with_extra(magic) || !bc_subfield(magic))
         return bail(clair_host_fail("%s is not a BGZF-compressed BAM (SAM text, CRAM and plain gzip are read by samtools): use --bam_reader samtools", path));
     if (b->file_size >= 28) {
         uint8_t tail[28];
@@ -331,26 +240,11 @@ int clair_host_bam_open(const char *path, int threads, clair_bam_t **out) {
         }
         return 0;
     };
-    if (need(12)) return bail(1);
-    const uint8_t *p = b->pending.data();
-    if (memcmp(p, "BAM\1", 4)) return bail(clair_host_fail("%s: BGZF but not BAM (no BAM\\1 magic): use --bam_reader samtools", path));
-    const uint32_t l_text = u32(p + 4);
-    if (need(12 + (size_t)l_text)) return bail(1);
-    size_t at = 8 + l_text;
-    const int32_t n_ref = i32(b->pending.data() + at);
-    if (n_ref < 0) return bail(clair_host_fail("%s: negative n_ref in the BAM header", path));
-    at += 4;
-    for (int32_t i = 0; i < n_ref; ++i) {
-        if (need(at + 4)) return bail(1);
-        const uint32_t l_name = u32(b->pending.data() + at);
-        if (l_name == 0 || l_name > (1u << 20)) return bail(clair_host_fail("%s: bad reference name length in the BAM header", path));
-        if (need(at + 4 + l_name + 4)) return bail(1);
-        const uint8_t *q = b->pending.data() + at + 4;
-        b->names.emplace_back((const char *)q, strnlen((const char *)q, l_name));
-        b->lengths.push_back(u32(q + l_name));
-        at += 4 + l_name + 4;
-    }
-    b->first_record = b->voffset_at(at);
+    BamHeader header;
+    if (parse_bam_header(path, ": use --bam_reader samtools", need, [&] { return (const uint8_t *)b->pending.data(); }, &header)) return bail(1);
+    b->names.swap(header.names);
+    b->lengths.swap(header.lengths);
+    b->first_record = b->voffset_at(header.end);
     b->batch_blocks = (size_t)std::max(16, 64 * threads);
     b->pending.clear();
     b->pending_at = 0;
@@ -500,24 +394,27 @@ int clair_host_bam_next(clair_bam_t *b, uint8_t *buf, int64_t cap, int64_t *offs
     b->rec_voffset.clear();
     int64_t fill = 0, n = 0;
     while (!b->done && n < max_records) {
-        size_t avail = b->pending.size() - b->pending_at;
-        if (avail < 4 || avail < 4 + (size_t)u32(b->pending.data() + b->pending_at)) {
+        int64_t next = 0;
+        const int rc = step(Bytes{b->pending.data()}, (int64_t)b->pending_at, (int64_t)b->pending.size(), &next);
+        char why[200];
+        if (rc == STEP_PAST) {                                   // the record is not all here yet
             size_t got = 0;
             if (b->fill(&got)) return 1;
-            if (!got) {
-                if (b->pending.size() > b->pending_at)
-                    return clair_host_fail("%s: the stream ends inside a record (virtual offset %llu)", b->path.c_str(),
-                                           (unsigned long long)b->voffset_at(b->pending_at));
-                b->done = true;
-                break;
+            if (got) continue;
+            if (b->pending.size() > b->pending_at) {
+                describe_cut(why, sizeof why, b->voffset_at(b->pending_at));
+                return clair_host_fail("%s: %s", b->path.c_str(), why);
             }
-            continue;
+            b->done = true;
+            break;
         }
         const uint8_t *r = b->pending.data() + b->pending_at;
         const uint32_t block_size = u32(r);
         const uint64_t voff = b->voffset_at(b->pending_at);
-        if (block_size < 32) return clair_host_fail("%s: record at virtual offset %llu: block_size %u < 32", b->path.c_str(), (unsigned long long)voff, block_size);
-        if ((uint64_t)block_size + 4 > (uint64_t)INT32_MAX) return clair_host_fail("%s: record at virtual offset %llu: block_size %u", b->path.c_str(), (unsigned long long)voff, block_size);
+        if (rc == STEP_BAD) {
+            describe_bad_step(why, sizeof why, voff, block_size);
+            return clair_host_fail("%s: %s", b->path.c_str(), why);
+        }
         const int32_t ref_id = i32(r + 4), pos = i32(r + 8);
         if (ref_id == b->tid) {
             b->seen_tid = true;
@@ -565,14 +462,13 @@ int clair_host_bam_render(clair_bam_t *b, const uint8_t *records, const int64_t 
         const int32_t ref_id = i32(r + 4), pos = i32(r + 8), next_ref = i32(r + 24), next_pos = i32(r + 28), tlen = i32(r + 32);
         const uint32_t l_read_name = r[12], mapq = r[13], n_cigar_stored = u16(r + 16), flag = u16(r + 18);
         const int32_t l_seq = i32(r + 20);
-        const uint8_t *cigar = r + 36 + l_read_name;
-        uint32_t n_cigar = n_cigar_stored;
-        if (const uint8_t *cg = real_cigar(r, block_size, &n_cigar)) cigar = cg;
+        uint32_t n_cigar = 0;
+        const uint8_t *cigar = printed_cigar(r, block_size, &n_cigar);
         // `samtools view -F 2316 <bam> <region>`
         if (flag & VIEW_FILTER) continue;
         if (ref_id != tid) continue;
         if (!whole) {
-            int64_t rlen = (flag & 4) ? 0 : cigar_rlen(cigar, n_cigar);
+            int64_t rlen = (flag & 4) ? 0 : cigar_span(Bytes{cigar}, 0, n_cigar);
             if (rlen == 0) rlen = 1;
             const int64_t end_1 = (int64_t)pos + rlen;           // bam_endpos, 1-based inclusive
             if (!((int64_t)pos + 1 <= end1 && end_1 >= beg1)) continue;

@@ -1,59 +1,28 @@
 // index_bam on the CPU (include/clair_host.h: clair_host_bamidx_*; docs/index_bam.md).  Three things:
 //   - the host twin of csrc/bam_index.hip: the same batch interface and the rules of csrc/bam_index_core.h as sequential loops.  Blocks are
-//     inflated by zlib on a few threads; records are framed by the plain walk, or -- so that the parallel rule can be held against the walk
+//     inflated by zlib on a few threads (hostsrc/bgzf_file.h); records are framed by the plain walk, or -- so that the parallel rule can be held against the walk
 //     on a machine without a GPU -- by a restatement of the segmented framing the device runs (jump table per segment, pointer jumping, the
 //     chain over the segments, counts, offsets);
-//   - the file driver both backends run under: the BAM header, the BGZF block headers (as host_bam.cpp walks them), the batches, the runs
-//     joined across batches;
+//   - the file driver both backends run under: the BAM header (hostsrc/bam_header.h), block after block of the file (hostsrc/bgzf_file.h) in
+//     batches of max_blocks, the runs joined across batches;
 //   - the result the Python side writes the .bai from (clair_amd/index_bam.py).
 // Plain C++17 + zlib, no HIP.
 #include "../../include/clair_host.h"
 #include "../csrc/bam_index_core.h"
-
-#include <zlib.h>
+#include "bam_header.h"
+#include "bgzf_file.h"
 
 #include <algorithm>
 #include <climits>
 #include <cstdio>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <vector>
-
-int clair_host_fail(const char *fmt, ...);   // host_io.cpp
 
 namespace {
 
 using namespace clair_bix;
-
-constexpr int BGZF_HEADER = 18, BGZF_FOOTER = 8, BGZF_MAX_BLOCK = 65536;
-
-inline uint32_t u16(const uint8_t *p) { return (uint32_t)(p[0] | p[1] << 8); }
-inline uint32_t u32(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
-
-// one BGZF block -> out_len bytes at out: 0, or what is wrong with it (the statuses of the device inflate, in its words)
-const char *inflate_block(const uint8_t *block, uint32_t csize, uint8_t *out, uint32_t out_len) {
-    z_stream z{};
-    if (inflateInit2(&z, -15) != Z_OK) return "inflateInit2 failed";
-    uint8_t spill = 0;
-    z.next_in = const_cast<uint8_t *>(block) + BGZF_HEADER;
-    z.avail_in = csize - BGZF_HEADER - BGZF_FOOTER;
-    z.next_out = out_len ? out : &spill;
-    z.avail_out = out_len;
-    int rc = inflate(&z, Z_FINISH);
-    if (rc != Z_STREAM_END && z.avail_out == 0) {            // room for one byte more: a block that inflates to more than ISIZE says so
-        z.next_out = &spill;
-        z.avail_out = 1;
-        rc = inflate(&z, Z_FINISH);
-        if (z.avail_out == 0) { inflateEnd(&z); return "inflated size differs from ISIZE"; }
-    }
-    const size_t got = z.total_out;
-    inflateEnd(&z);
-    if (rc != Z_STREAM_END) return "corrupt deflate data";
-    if (got != out_len) return "inflated size differs from ISIZE";
-    if ((uint32_t)crc32(0L, out, out_len) != u32(block + csize - 8)) return "CRC32 mismatch";
-    return nullptr;
-}
+using namespace clair_bgzf;
 
 // ---- framing.  Both give the record starts from `entry`, the tail (where the chain stops) and whether it stopped on a bad step.
 void frame_walk(const Bytes &m, int64_t len, int64_t entry, std::vector<int64_t> &starts, int64_t *tail, bool *bad) {
@@ -152,14 +121,11 @@ int clair_host_bamidx_batch(clair_host_bamidx_t *h, const uint8_t *cdata, int64_
                             const clair_bamidx_run_t **runs) {
     if (!h || !state || !runs) return clair_host_fail("bamidx batch: NULL argument");
     if (h->n_ref < 0) return clair_host_fail("bamidx batch: begin first");
-    if (n < 0 || n > h->max_blocks) return clair_host_fail("%d blocks in a batch: 0 .. max_blocks = %d", n, h->max_blocks);
     if (n > 0 && (!cdata || !in_at || !csize || !out_len || !coffset)) return clair_host_fail("bamidx batch: NULL argument");
     if (cbytes < 0 || end_coffset < 0 || entry < 0) return clair_host_fail("bamidx batch: negative argument");
+    if (clair_inf::check_blocks(clair_host_fail, n, h->max_blocks, cbytes, in_at, csize, out_len)) return 1;
     int64_t len = (int64_t)h->carry.size();
     for (int i = 0; i < n; ++i) {
-        if (csize[i] < BGZF_HEADER + BGZF_FOOTER || csize[i] > BGZF_MAX_BLOCK) return clair_host_fail("block %d: csize %d (26 .. 65536)", i, csize[i]);
-        if (in_at[i] < 0 || in_at[i] > cbytes - csize[i]) return clair_host_fail("block %d: compressed bytes [%lld, +%d) outside the %lld given", i, (long long)in_at[i], csize[i], (long long)cbytes);
-        if (out_len[i] < 0 || out_len[i] > BGZF_MAX_BLOCK) return clair_host_fail("block %d: out_len %d (0 .. 65536)", i, out_len[i]);
         if (coffset[i] < 0) return clair_host_fail("block %d: negative offset", i);
         len += out_len[i];
     }
@@ -173,7 +139,7 @@ int clair_host_bamidx_batch(clair_host_bamidx_t *h, const uint8_t *cdata, int64_
         h->at.push_back(0);
         h->voff.push_back(h->carry_voff);
     }
-    std::vector<const char *> why((size_t)n, nullptr);
+    std::vector<int32_t> status((size_t)n, 0);
     int64_t pos = (int64_t)h->carry.size();
     const size_t first_block = h->at.size();
     for (int i = 0; i < n; ++i) {
@@ -183,17 +149,9 @@ int clair_host_bamidx_batch(clair_host_bamidx_t *h, const uint8_t *cdata, int64_
     }
     h->at.push_back(len);
     h->voff.push_back((uint64_t)end_coffset << 16);
-    auto inflate_one = [&](int i) { why[(size_t)i] = inflate_block(cdata + in_at[i], (uint32_t)csize[i], h->stream.data() + h->at[first_block + (size_t)i], (uint32_t)out_len[i]); };
-    const int nt = std::max(1, std::min(h->threads, n));
-    if (nt == 1) {
-        for (int i = 0; i < n; ++i) inflate_one(i);
-    } else {
-        std::vector<std::thread> pool;
-        for (int t = 0; t < nt; ++t) pool.emplace_back([&, t] { for (int i = t; i < n; i += nt) inflate_one(i); });
-        for (auto &th : pool) th.join();
-    }
+    inflate_blocks(h->threads, cdata, n, in_at, csize, h->at.data() + first_block, out_len, h->stream.data(), status.data());
     for (int i = 0; i < n; ++i)
-        if (why[(size_t)i]) return clair_host_fail("BGZF block at compressed offset %lld: %s", (long long)coffset[i], why[(size_t)i]);
+        if (status[(size_t)i]) return clair_host_fail("BGZF block at compressed offset %lld: %s", (long long)coffset[i], inflate_text(status[(size_t)i]));
     // 2. the record starts
     const Bytes m{h->stream.data()};
     const int n_tab = (int)h->at.size();
@@ -306,30 +264,9 @@ int clair_host_bamidx_build(const char *path, const clair_bamidx_backend_t *be, 
     if (fseeko(file, 0, SEEK_END) != 0) return clair_host_fail("%s: cannot seek", path);
     const int64_t file_size = (int64_t)ftello(file);
     std::vector<uint8_t> cbuf;
-    // one block's header at coffset checked and its bytes appended to cbuf: -> csize, 0 on failure (message set)
-    const auto read_block = [&](int64_t coffset) -> uint32_t {
-        uint8_t hd[BGZF_HEADER];
-        const auto cut = [&] { clair_host_fail("%s: truncated BGZF block at compressed offset %lld", path, (long long)coffset); return 0u; };
-        if (coffset + BGZF_HEADER > file_size || fseeko(file, (off_t)coffset, SEEK_SET) != 0 || fread(hd, 1, BGZF_HEADER, file) != BGZF_HEADER) return cut();
-        if (hd[0] != 0x1f || hd[1] != 0x8b || hd[2] != 8 || !(hd[3] & 4) || u16(hd + 10) != 6 || hd[12] != 'B' || hd[13] != 'C' || u16(hd + 14) != 2) {
-            clair_host_fail("%s: not a BGZF block at compressed offset %lld", path, (long long)coffset);
-            return 0u;
-        }
-        const uint32_t csize = u16(hd + 16) + 1;
-        if (csize < BGZF_HEADER + BGZF_FOOTER || coffset + csize > file_size) return cut();
-        const size_t at = cbuf.size();
-        cbuf.resize(at + csize);
-        memcpy(cbuf.data() + at, hd, BGZF_HEADER);
-        if (fread(cbuf.data() + at + BGZF_HEADER, 1, csize - BGZF_HEADER, file) != csize - BGZF_HEADER) { cbuf.resize(at); return cut(); }
-        if (u32(cbuf.data() + at + csize - 4) > (uint32_t)BGZF_MAX_BLOCK) {
-            clair_host_fail("%s: BGZF block at compressed offset %lld claims %u bytes", path, (long long)coffset, u32(cbuf.data() + at + csize - 4));
-            return 0u;
-        }
-        return csize;
-    };
     {
         uint8_t magic[4] = {0, 0, 0, 0};
-        if (file_size < BGZF_HEADER || fseeko(file, 0, SEEK_SET) != 0 || fread(magic, 1, 4, file) != 4 || magic[0] != 0x1f || magic[1] != 0x8b || magic[2] != 8 || !(magic[3] & 4))
+        if (file_size < BGZF_HEADER || fseeko(file, 0, SEEK_SET) != 0 || fread(magic, 1, 4, file) != 4 || !gzip_with_extra(magic))
             return clair_host_fail("%s is not a BGZF-compressed BAM (SAM text, CRAM and plain gzip have no .bai)", path);
     }
     // the header, block by block (zlib), with where each block's bytes start in it
@@ -340,36 +277,22 @@ int clair_host_bamidx_build(const char *path, const clair_bamidx_backend_t *be, 
         while (text.size() < bytes) {
             if (coffset >= file_size) return clair_host_fail("%s: the BAM header is truncated", path);
             cbuf.clear();
-            const uint32_t csize = read_block(coffset);
-            if (!csize) return 1;
-            const uint32_t isize = u32(cbuf.data() + csize - 4);
+            uint32_t csize = 0, isize = 0;
+            if (read_block(file, path, (uint64_t)file_size, (uint64_t)coffset, cbuf, &csize, &isize)) return 1;
             const size_t at = text.size();
-            text.resize(at + isize + 1);
-            const char *why = inflate_block(cbuf.data(), csize, text.data() + at, isize);
             text.resize(at + isize);
-            if (why) return clair_host_fail("%s: BGZF block at compressed offset %lld: %s", path, (long long)coffset, why);
+            const int status = inflate_block(cbuf.data(), csize, text.data() + at, isize);
+            if (status) return clair_host_fail("%s: BGZF block at compressed offset %lld: %s", path, (long long)coffset, inflate_text(status));
             pieces.emplace_back((int64_t)at, coffset);
             coffset += csize;
         }
         return 0;
     };
-    if (need(12)) return 1;
-    if (memcmp(text.data(), "BAM\1", 4)) return clair_host_fail("%s: BGZF but not BAM (no BAM\\1 magic)", path);
-    const uint32_t l_text = u32(text.data() + 4);
-    if (need(12 + (size_t)l_text)) return 1;
-    size_t at = 8 + (size_t)l_text;
-    const int32_t n_ref = (int32_t)u32(text.data() + at);
-    if (n_ref < 0) return clair_host_fail("%s: negative n_ref in the BAM header", path);
-    at += 4;
-    std::vector<int64_t> ref_len;
-    for (int32_t i = 0; i < n_ref; ++i) {
-        if (need(at + 4)) return 1;
-        const uint32_t l_name = u32(text.data() + at);
-        if (l_name == 0 || l_name > (1u << 20)) return clair_host_fail("%s: bad reference name length in the BAM header", path);
-        if (need(at + 4 + l_name + 4)) return 1;
-        ref_len.push_back((int64_t)u32(text.data() + at + 4 + l_name));
-        at += 4 + (size_t)l_name + 4;
-    }
+    BamHeader header;
+    if (parse_bam_header(path, "", need, [&] { return (const uint8_t *)text.data(); }, &header)) return 1;
+    const int32_t n_ref = (int32_t)header.lengths.size();
+    const std::vector<int64_t> &ref_len = header.lengths;
+    const size_t at = header.end;
     // the first record: in the last header block, or at the start of the block after it
     int64_t entry = 0;
     if (at < text.size()) {
@@ -389,12 +312,12 @@ int clair_host_bamidx_build(const char *path, const clair_bamidx_backend_t *be, 
         cbuf.clear(); in_at.clear(); offs.clear(); csizes.clear(); out_lens.clear();
         while ((int)offs.size() < max_blocks && coffset < file_size) {
             const size_t here = cbuf.size();
-            const uint32_t csize = read_block(coffset);
-            if (!csize) return 1;
+            uint32_t csize = 0, isize = 0;
+            if (read_block(file, path, (uint64_t)file_size, (uint64_t)coffset, cbuf, &csize, &isize)) return 1;
             in_at.push_back((int64_t)here);
             offs.push_back(coffset);
             csizes.push_back((int32_t)csize);
-            out_lens.push_back((int32_t)u32(cbuf.data() + here + csize - 4));
+            out_lens.push_back((int32_t)isize);
             coffset += csize;
         }
         last = coffset >= file_size;

@@ -2,6 +2,7 @@
 // csrc/inflate_core.h compiled by the host compiler, with its own CRC-32.  No zlib here: this is the code that runs on the GPU, made
 // testable, fuzzable and sanitizable on a machine without one.  The reader's default path (host_bam.cpp) stays on zlib.
 #include "../../include/clair_host.h"
+#include "../csrc/bam_record_core.h"         // u32: the little-endian fields of the block's footer
 #include "../csrc/inflate_core.h"
 
 #include <cstring>
@@ -70,7 +71,7 @@ int clair_host_inflate_block(const uint8_t *in, int64_t n_in, uint8_t *out, int6
 int clair_host_inflate_bgzf(const uint8_t *block, int64_t csize, uint8_t *out, int64_t *n_out, int *status) {
     if (!block || !out || !n_out || !status) return clair_host_fail("NULL argument");
     if (csize < 26 || csize > 65536) return clair_host_fail("BGZF block of %lld bytes: 26 .. 65536", (long long)csize);
-    const auto u32 = [](const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; };
+    using clair_rec::u32;
     const uint32_t want = u32(block + csize - 8), isize = u32(block + csize - 4);
     if (isize > 65536) return clair_host_fail("BGZF block claims %u bytes", isize);
     HostCtx c{block + 18, (uint32_t)csize - 26, out, {}};

@@ -57,6 +57,7 @@ class Record(object):
         self.seq = [nt16(c) for c in seq]
         self.qual = None if col[10] == "*" or not seq else bytes(ord(c) - 33 for c in col[10])
         self.tags = col[11:]
+        self.raw_aux = b""                                  # bytes a test appends behind the encoded tags, as they are
 
     def end(self):
         """bam_endpos"""
@@ -84,7 +85,7 @@ class Record(object):
         qual = self.qual if self.qual is not None else b"\xff" * len(self.seq)
         body = struct.pack("<iiBBHHHiiii", self.tid, self.pos, len(name), self.mapq, reg2bin(max(self.pos, 0), self.end()) if self.tid >= 0 else 4680,
                            len(cigar), self.flag, len(self.seq), self.next_tid, self.next_pos, self.tlen)
-        body += name + b"".join(struct.pack("<I", n << 4 | op) for n, op in cigar) + seq + qual + aux
+        body += name + b"".join(struct.pack("<I", n << 4 | op) for n, op in cigar) + seq + qual + aux + self.raw_aux
         return struct.pack("<I", len(body)) + body
 
     def canonical(self, names):

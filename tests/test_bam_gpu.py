@@ -161,6 +161,34 @@ def test_anomalies_raise_the_same_bits(tmp_path):
     assert seen & 1 and seen & 2 and seen & 4
 
 
+def test_the_aux_walk_on_the_device_equals_the_host_renderer(tmp_path):
+    """the ten placeholder-CIGAR records of tests/aux_walk_cases.py in one chunk, starting at every offset modulo 4, the last one ending at
+    the chunk's last byte: the records on the device against the text path on the lines the host renderer prints for them"""
+    import aux_walk_cases as aw
+    bam, want = aw.bam()
+    path = str(tmp_path / "aux.bam")
+    bam.write(path)
+    r = _hostapi.BamReader(path, threads=1)
+    r.query(aw.CTG)
+    big, off = np.empty(1 << 16, np.uint8), np.empty(16, np.int64)
+    n, k = r.readinto(big, off)
+    assert k == 10 and {int(o) % 4 for o in off[:k]} == {0, 1, 2, 3}
+    chunk = big[:n].copy()                                                      # the last record ends with the buffer
+    assert off[k - 1] + 4 + int.from_bytes(chunk[off[k - 1]:off[k - 1] + 4].tobytes(), "little") == len(chunk) == n
+    text = r.render(chunk, off, k)
+    assert [l.split(b"\t")[5].decode() for l in text.splitlines()] == want
+    case = dict(ctg=aw.CTG, ref="".join("ACGT"[(i * 7) % 4] for i in range(aw.REF_LEN)), ref0=0)
+    f = frontend_of(case)
+    f.bam_options(r.tid)
+    f.add_bam(chunk, n, off, k)
+    g = feed_text(case, text)
+    r.close()
+    reads, _ = same_results(f, g, evc=dict(min_coverage=1, threshold=0.1))
+    assert reads > 0 and f.text_stats()["lines"] == 10
+    f.close()
+    g.close()
+
+
 def test_a_malformed_record_is_named(tmp_path):
     case = fc.synth(5, n_reads=40, ref_len=2000)
     bam_fn, _ = bam_of(str(tmp_path), case, extra_filtered=False)

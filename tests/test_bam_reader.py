@@ -111,6 +111,23 @@ def test_index_queries_equal_a_scan_and_the_text_view(mixed, region):
         assert want == "" and info["records"] == 0
 
 
+def test_the_aux_walk_to_the_real_cigar_branch_by_branch(tmp_path):
+    """ten records that store the placeholder CIGAR: the renderer's CIGAR column against the walk over the aux fields written out in
+    tests/aux_walk_cases.py, one record per branch of it"""
+    import aux_walk_cases as aw
+    bam, want = aw.bam()
+    assert len(want) == 10 and want.count(aw.PLACEHOLDER) == 7 and want[:3] == ["4M1I5M"] * 3
+    path = str(tmp_path / "aux.bam")
+    bam.write(path)
+    got, info = read_all(path, aw.CTG)
+    rows = [l.split("\t") for l in got.splitlines()]
+    assert [r[0] for r in rows] == [r.qname for r in bam.records] and info["records"] == 10
+    for row, cigar, (name, _) in zip(rows, want, aw.CASES):
+        assert row[5] == cigar, name
+    # every other column is the canonical one
+    assert ["\t".join(r[:5] + r[6:]) for r in rows] == ["\t".join(l.split("\t")[:5] + l.split("\t")[6:]) for l in bam.canonical().splitlines()]
+
+
 def test_the_walk_stops_at_the_first_record_past_the_region(mixed):
     bam, d, _ = mixed
     path = os.path.join(str(d), "s.bam")
