@@ -114,6 +114,9 @@ SIGNATURES = {
     "clair_frontend_train_set_counts": _sig(c_vp, c_i64, c_i64, c_vp),
     "clair_frontend_budget_inputs": _sig(c_vp, c_i64, c_vp, c_vp, c_vp),
     "clair_frontend_stats": _sig(c_vp, c_vp),
+    "clair_frontend_position_tallies": _sig(c_vp, c_i64, c_i64, c_vp),
+    "clair_frontend_gvcf_blocks": _sig(c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, p_i64),
+    "clair_frontend_gvcf_device_ms": _sig(c_vp, c_vp),
     "clair_inflate_create": _sig(c_int, c_int, p_vp),
     "clair_inflate_destroy": _sig(c_vp, restype=None),
     "clair_inflate_last_error": _sig(c_vp, restype=c_cp),
@@ -165,6 +168,7 @@ SIGNATURES = {
 SYMBOLS = tuple(SIGNATURES)
 ENSEMBLE_MAX_MODELS = 8                                      # CLAIR_ENSEMBLE_MAX_MODELS
 OVERLAP_SCAN_BLOCK = 2048                                    # clair_ov::BLOCK (csrc/overlap.hip): rows per workgroup of the head scan
+GVCF_SCAN_TILE = 2048                                        # clair_gv::TILE (csrc/gvcf.hip): positions per workgroup of the block scan
 COMPARE_SCAN_BLOCK = 2048                                    # clair_cmp::BLOCK (csrc/compare.hip): text bytes / record slots per workgroup of a scan
 EVAL_COUNTS = 3 + 21 * 21 + 3 * 3 + 33 * 33 + 33 * 33      # CLAIR_EVAL_COUNTS: all, top1, top2, gt21, genotype, len1, len2
 KERNEL_NAMES = ("proj1", "lstm1", "proj2", "lstm2", "l3", "l4", "tail", "decode")
@@ -586,6 +590,14 @@ class MalformedText(EngineError):
     pass
 
 
+class TalliesIncomplete(EngineError):
+    """clair_frontend_gvcf_blocks: the front end reported a CLAIR_FE_* bit, so the device does not band its tallies (the host twin runs)."""
+
+
+class BadArgument(EngineError):
+    """A verdict on an argument (return code 2): the handle stays usable; str() is the library's text, the same on both backends."""
+
+
 class MalformedRecord(EngineError):
     """clair_frontend_add_bam: a BAM record whose sizes do not fit its block_size; .index = its index in the chunk."""
 
@@ -817,6 +829,45 @@ class Frontend(DeviceHandle):
         v = (ctypes.c_int64 * 6)()
         self._check(self._lib.clair_frontend_stats(self._h, v), "clair_frontend_stats")
         return dict(zip(("anomalies", "slabs", "reads", "elements", "candidates", "windows"), [int(x) for x in v]))
+
+    def position_tallies(self, first, n):
+        """clair_frontend_position_tallies -> uint32 [n, 7]: A C G T I D N of the 0-based positions [first, first + n)"""
+        out = np.zeros((max(int(n), 0), 7), dtype=np.uint32)
+        rc = self._lib.clair_frontend_position_tallies(self._h, int(first), int(n), _ptr(out))
+        if rc == 2:
+            raise BadArgument(self._last_error(self._h).decode())
+        self._check(rc, "clair_frontend_position_tallies")
+        return out
+
+    def gvcf_blocks(self, costs, band_of_gq, iv_start, iv_end, guard=0):
+        """clair_frontend_gvcf_blocks -> records (clair_amd.gvcf.BLOCK_DTYPE).  costs = (c_match, c_err, c_half), band_of_gq uint8 [100], the
+        allowed intervals as two int64 arrays.  guard: that many further records behind the result, filled with 0xA5 bytes before the call
+        (tests look at them afterwards).  Raises BadArgument / TalliesIncomplete for the return codes 2 / 3."""
+        from clair_amd.gvcf import BLOCK_DTYPE
+        bands = np.ascontiguousarray(band_of_gq, dtype=np.uint8)
+        st, en = np.ascontiguousarray(iv_start, dtype=np.int64), np.ascontiguousarray(iv_end, dtype=np.int64)
+        if bands.shape != (100,) or st.shape != en.shape or st.ndim != 1:
+            raise ValueError("gvcf_blocks: a band table of 100 entries and two interval arrays of one length")
+        n = ctypes.c_int64(0)
+
+        def call(out, capacity):
+            rc = self._lib.clair_frontend_gvcf_blocks(self._h, int(costs[0]), int(costs[1]), int(costs[2]), _ptr(bands), _ptr(st), _ptr(en), len(st),
+                                                      None if out is None else _ptr(out), capacity, ctypes.byref(n))
+            if rc in (2, 3):
+                raise (BadArgument if rc == 2 else TalliesIncomplete)(self._last_error(self._h).decode())
+            self._check(rc, "clair_frontend_gvcf_blocks")
+        call(None, 0)
+        out = np.empty(n.value + int(guard), dtype=BLOCK_DTYPE)
+        out.view(np.uint8)[:] = 0xA5
+        if n.value:
+            call(out, n.value)
+        return out if guard else out[:n.value]
+
+    def gvcf_device_ms(self):
+        """clair_frontend_gvcf_device_ms: event time of the launches of the last gvcf_blocks computation"""
+        ms = ctypes.c_double(0.0)
+        self._check(self._lib.clair_frontend_gvcf_device_ms(self._h, ctypes.byref(ms)), "clair_frontend_gvcf_device_ms")
+        return ms.value
 
     def budget_binds(self, available_slots=5000000):
         """Replay CreateTensor's count of free tuple slots over everything added (clair_host_tuple_budget_binds)."""

@@ -118,6 +118,9 @@ SIGNATURES = {
     "clair_host_bamidx_result_info": _sig(vp, vp),
     "clair_host_bamidx_result_copy": _sig(vp, vp, vp, vp),
     "clair_host_bamidx_result_free": _sig(vp, restype=None),
+    "clair_host_gvcf_tally": _sig(vp, i64, vp, i64, vp, i64, i64, i64, vp, vp),
+    "clair_host_gvcf_blocks": _sig(vp, i64, i64, vp, i64, i64, i32, i32, i32, vp, vp, vp, i64, vp, i64, p_i64),
+    "clair_host_gvcf_format": _sig(vp, i64, i64, cp, vp, i64, i64, vp, i64, p_i64, vp),
 }
 SYMBOLS = tuple(SIGNATURES)
 N_VALUES = 1056

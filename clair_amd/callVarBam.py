@@ -524,18 +524,13 @@ class DeviceFrontEnd(object):
                 return self._fallback("not enough device memory for the region: %s" % exc)
             sys.exit("[ERROR] %s" % exc)
 
-    def _run(self):
-        from . import _capi, _hostapi
+    def tables(self, search=True):
+        """What a front end of this region is created over, and the region its alignments are read from -> (reference slice, its 0-based
+        start, bed intervals or None, table span lo, hi, samtools' region).  search: candidates are searched for (the .fai and the bed file
+        are then looked at, as the search looks at them)."""
         args = self.args
         have_range = args.ctgStart is not None and args.ctgEnd is not None
-        given = None
-        if args.vcf_fn is not None:
-            given = positions_from_vcf(args.vcf_fn, args.ctgName, args.ctgStart, args.ctgEnd)
-            if have_range:
-                given = given[(given >= args.ctgStart) & (given <= args.ctgEnd)]
-            if len(given) > 1 and not (np.diff(given) > 0).all():
-                return self._fallback(FE_REASONS[8][1])
-        seq, ref0, bed = reference_and_bed(args, given is None, "Failed to load reference seqeunce. Please check if the provided reference fasta %s "
+        seq, ref0, bed = reference_and_bed(args, search, "Failed to load reference seqeunce. Please check if the provided reference fasta %s "
                                            "and the ctgName %s are correct." % (args.ref_fn, args.ctgName))
         if have_range:
             lo, hi = args.ctgStart - 1 - TABLE_MARGIN, args.ctgEnd + TABLE_MARGIN
@@ -546,7 +541,16 @@ class DeviceFrontEnd(object):
         else:
             lo, hi = ref0 - TABLE_MARGIN, ref0 + len(seq) + TABLE_MARGIN
             region = args.ctgName
-        f = self.frontend = _capi.Frontend(self.device, seq, ref0, lo, hi)
+        self.table_info = dict(seq=seq, ref0=ref0, bed=bed, lo=lo, hi=hi)
+        return seq, ref0, bed, lo, hi, region
+
+    def feed(self, f, region):
+        """The alignments of `region` into f -- a clair_amd._capi.Frontend, or (without a page-locked buffer: through the host packer)
+        anything with its add_slab(packer), which clair_amd.gvcf's host backend uses -> (the packer's statistics, start time, seconds
+        packing on the host, seconds in the device calls)."""
+        from . import _capi, _hostapi
+        args = self.args
+        have_range = args.ctgStart is not None and args.ctgEnd is not None
         pack_kw = dict(dcov=args.dcov, evc_min_mq=0, pile_min_mq=0, pile_region=(args.ctgStart, args.ctgEnd) if have_range else None)
         readers = max(1, int(getattr(args, "view_readers", 1) or 1))
         span = (max(1, args.ctgStart - 2), args.ctgEnd + 2) if have_range else (1, contig_length(args.ref_fn, args.ctgName) or 0)
@@ -625,9 +629,28 @@ class DeviceFrontEnd(object):
         except BaseException:
             view.abort()
             raise
-        t0 = time()
         if view.finish() != 0:
             sys.exit("[ERROR] `samtools view` failed on %s" % args.bam_fn)
+        self.view_kind = ("packing the text on the host %.2f s" % t_pack if t_pack else
+                          ("BAM records decoded on the device" if isinstance(view, _NativeBam) else "text parsed on the device"))
+        return pst, t_start, t_pack, t_dev
+
+    def _run(self):
+        from time import time
+        from . import _capi
+        args = self.args
+        have_range = args.ctgStart is not None and args.ctgEnd is not None
+        given = None
+        if args.vcf_fn is not None:
+            given = positions_from_vcf(args.vcf_fn, args.ctgName, args.ctgStart, args.ctgEnd)
+            if have_range:
+                given = given[(given >= args.ctgStart) & (given <= args.ctgEnd)]
+            if len(given) > 1 and not (np.diff(given) > 0).all():
+                return self._fallback(FE_REASONS[8][1])
+        seq, ref0, bed, lo, hi, region = self.tables(given is None)
+        f = self.frontend = _capi.Frontend(self.device, seq, ref0, lo, hi)
+        pst, t_start, t_pack, t_dev = self.feed(f, region)
+        t0 = time()
         if given is None:
             if pst["evc_reads"] == 0:
                 print("No read has been process, either the genome region you specified has no read cover, or please check the correctness of your BAM input (%s)."
@@ -649,8 +672,7 @@ class DeviceFrontEnd(object):
         t_dev += time() - t0
         logging.info("%d candidate sites" % n_cand)
         logging.info("device front end: %d alignments, %d windows in %.2f s (%s, device %.2f s, the rest waiting for %s)"
-                     % (f.stats()["reads"], n, time() - t_start, "packing the text on the host %.2f s" % t_pack if t_pack else
-                        ("BAM records decoded on the device" if isinstance(view, _NativeBam) else "text parsed on the device"), t_dev,
+                     % (f.stats()["reads"], n, time() - t_start, self.view_kind, t_dev,
                         "the BAM reader" if native_input(args) else "`samtools view`"))
         self.n_windows = n
         return n
@@ -801,6 +823,7 @@ def normalise(args):
     cv.check_overlap_flags(args)
     check_subsample_flags(args)
     check_site_flags(args)
+    check_gvcf_flags(args)
     if native_lookup(args):
         if not native_input(args):
             sys.exit("[ERROR] --indel_lookup native answers from the alignments the native reader feeds the device front end: add --bam_reader native")
@@ -808,6 +831,21 @@ def normalise(args):
             sys.exit("[ERROR] --indel_lookup native answers from the alignments resident on the GPU: it needs the device front end "
                      "(drop --front_end host / --front_end_workers)")
     return args
+
+
+def check_gvcf_flags(args):
+    """--gvcf_fn: what it cannot go with (docs/gvcf.md, "out of scope"), and its two options checked before the model is loaded."""
+    if not getattr(args, "gvcf_fn", None):
+        return
+    for flag, given in (("--vcf_fn", args.vcf_fn is not None), ("--ensemble_bam_fn", bool(getattr(args, "ensemble_bam_fn", None))),
+                        ("--ensemble_subsample", bool(getattr(args, "ensemble_subsample", None))), ("--output_for_ensemble", args.output_for_ensemble)):
+        if given:
+            sys.exit("[ERROR] --gvcf_fn tiles the region between the calls of one BAM's own candidate search with reference-confidence blocks; "
+                     "with %s there is no such call set: drop one of the two" % flag)
+    if args.call_fn is None:
+        sys.exit("[ERROR] --gvcf_fn adds blocks to the rows of --call_fn: give --call_fn as well")
+    from . import gvcf
+    gvcf.check_options(args)
 
 
 MAX_ENSEMBLE_BAMS = 7      # --ensemble_bam_fn: CLAIR_SITES_MAX_BAMS less --bam_fn
@@ -925,6 +963,12 @@ def call_region(args, m, prepared=None):
         if native_lookup(args):
             logging.info("indel look-up: %d positions in %d device calls (at most %d in one), lookup_over_depth %d, answered by the host twin %d"
                          % (lookup.positions, lookup.calls, lookup.largest_call, lookup.over_depth, lookup.handed_over))
+        if getattr(args, "gvcf_fn", None):
+            # the call VCF is finished first (the overlap filter included): its rows are what the blocks leave out.  The front end is still
+            # alive, so the tallies of the region are in HBM and the BAM is not read again (docs/gvcf.md)
+            from . import gvcf
+            writer.close()
+            gvcf.after_calls(args, device_fe)
     finally:
         if device_fe is not None:
             device_fe.close()
@@ -1161,6 +1205,11 @@ def build_parser():
     add('--overlap_filter', type=str, default="off", choices=("off", "host", "device"),
         help="pass the finished VCF through the overlap filter (python -m clair_amd.overlap_variant: of two calls one of whose deletion covers "
              "the other, the one with the higher QUAL stays), with its walk on the host or on the GPU --device names; default: %(default)s")
+    add('--gvcf_fn', type=str, default=None, metavar="FILE",
+        help="also write a gVCF: the rows of --call_fn plus reference-confidence blocks banded by GQ that tile the rest of the region, from the "
+             "tallies the device front end still holds (docs/gvcf.md; not with --vcf_fn, --ensemble_bam_fn, --ensemble_subsample)")
+    from .gvcf import add_gvcf_options
+    add_gvcf_options(add)
     return parser
 
 

@@ -73,7 +73,8 @@ def commands(args):
     ] + [_opt("ensemble_chkpnt_fn", os.path.abspath(f)) for f in (args.ensemble_chkpnt_fn or [])]
       + [_opt("ensemble_bam_fn", os.path.abspath(f)) for f in (args.ensemble_bam_fn or [])]
       + [_opt("minimum_count_to_output", args.minimum_count_to_output), _opt("ensemble_order", args.ensemble_order),
-         _opt("subsample", args.subsample), _opt("subsample_seed", args.subsample_seed)]
+         _opt("subsample", args.subsample), _opt("subsample_seed", args.subsample_seed),
+         _opt("gvcf_error_rate", args.gvcf_error_rate if args.gvcf else None), _opt("gvcf_gq_bands", args.gvcf_gq_bands if args.gvcf else None)]
       + [_opt("ensemble_subsample", v) for v in (args.ensemble_subsample or [])] if x is not None)
     out, k = [], 0
     commands.chunks = []           # (device, output file) per command, for --run
@@ -91,6 +92,8 @@ def commands(args):
                     continue
                 tail = [_opt("ctgName", contig), _opt("ctgStart", start), _opt("ctgEnd", end),
                         _opt("call_fn", "%s.%s_%d_%d.vcf" % (args.output_prefix, contig, start, end)),
+                        # (not *.vcf: merge_vcf collects <prefix>.*.vcf)
+                        _opt("gvcf_fn", "%s.%s_%d_%d.gvcf" % (args.output_prefix, contig, start, end)) if args.gvcf else None,
                         _opt("bed_fn", bed_fn) if in_bed else None,
                         _opt("device", k % args.devices) if args.devices > 1 else None]
                 out.append(head + " " + " ".join(x for x in tail if x is not None))
@@ -288,6 +291,11 @@ def build_parser():
     add('--indel_lookup', type=str, default=None, choices=("pysam", "native"), help="passed on (callVarBam: long-indel bases from pysam or from the GPU-resident alignments)")
     add('--overlap_filter', type=str, default=None, choices=("off", "host", "device"),
         help="passed on (callVarBam: every chunk's VCF through the overlap filter, on the host or on the GPU; the chunks are not merged)")
+    add('--gvcf', action='store_true',
+        help="every chunk also writes <prefix>.<contig>_<start>_<end>.gvcf (callVarBam --gvcf_fn: the calls plus reference-confidence blocks, "
+             "docs/gvcf.md); the per-chunk gVCFs are not merged")
+    add('--gvcf_error_rate', type=float, default=None, help="passed on with --gvcf (callVarBam: the error rate of the reference-confidence model)")
+    add('--gvcf_gq_bands', type=str, default=None, help="passed on with --gvcf (callVarBam: the lower bounds of the GQ bands)")
     add('--ensemble_chkpnt_fn', type=str, action='append', default=None, metavar="PREFIX",
         help="passed on, repeatable (callVarBam: one more checkpoint whose probabilities are averaged with --chkpnt_fn's on the GPU)")
     add('--ensemble_bam_fn', type=str, action='append', default=None, metavar="BAM",

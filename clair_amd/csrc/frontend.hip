@@ -24,6 +24,8 @@
 #define CLAIR_REC_FN __device__ inline
 #include "bam_record_core.h"
 #include "subsample_core.h"
+#define CLAIR_GVCF_FN __device__ __host__ inline
+#include "gvcf_core.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -1287,6 +1289,20 @@ struct CandidateBuffers {
     int64_t ts_n_kept = -1;
 };
 
+// what the last clair_frontend_gvcf_blocks call computed (gvcf.hip), kept so that a second call with the same arguments and room for the
+// records only copies them
+struct GvcfHeld {
+    bool valid = false;
+    int cost[3] = {0, 0, 0};
+    uint8_t bands[CLAIR_GVCF_GQ_VALUES] = {};
+    std::vector<int64_t> iv;             // starts, then ends
+    int64_t n_blocks = 0;
+    DeviceBuffer records, cls, totals, intervals;
+    hipEvent_t began = nullptr, ended = nullptr;      // around the launches of the last computation (clair_frontend_gvcf_device_ms)
+    float device_ms = -1.0f;
+    ~GvcfHeld() { if (began) (void)hipEventDestroy(began); if (ended) (void)hipEventDestroy(ended); }
+};
+
 struct clair_frontend {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -1317,6 +1333,7 @@ struct clair_frontend {
     // the indel look-up (indel_lookup.hip): queries, hits per query, tables; sized by the largest call so far
     DeviceBuffer lk_pos, lk_views, lk_count, lk_hits, lk_entries, lk_n, lk_depth, lk_status;
     std::deque<SlabHostCopy> lk_host;    // slabs copied back for the host fallback, once each (a slab never changes)
+    GvcfHeld gvcf;
     std::string error;
 
     SlabView view(const Slab &s) const {
@@ -1419,6 +1436,7 @@ int upload_bed(clair_frontend *f, const int64_t *bed_start, const int64_t *bed_e
 // a slab of these sizes, owned by the handle from here on, its tuples zeroed (on the stream)
 int new_slab(clair_frontend *f, int64_t n_reads, int64_t n_ops, int64_t n_elem, int64_t seq_bytes, Slab **out) {
     f->slabs.emplace_back();
+    f->gvcf.valid = false;               // the tallies are about to change
     Slab &d = f->slabs.back();
     d.n_reads = n_reads; d.n_ops = n_ops; d.n_elem = n_elem; d.seq_bytes = seq_bytes;
     CLAIR_HIP_TRY(fe_fail(f), d.reads.ensure((size_t)n_reads * sizeof(clair_read_t)));
@@ -1989,3 +2007,7 @@ int clair_frontend_stats(clair_frontend_t *f, int64_t *stats) {
 
 // the training-set builder over the tallies and the windows: clair_frontend_sample_candidates / _pair / _train_set_* (part of this translation unit too)
 #include "train_set.hip"
+
+// the gVCF stage over the tallies: reference-confidence blocks banded by a segmented scan, clair_frontend_position_tallies / _gvcf_blocks (part of this
+// translation unit as well: the tallies are this handle's tables)
+#include "gvcf.hip"

@@ -486,6 +486,34 @@ int clair_frontend_budget_inputs(clair_frontend_t *f, int64_t slab, uint64_t *re
 /* stats[0..5] = CLAIR_FE_* bits seen on the device, slabs, alignments, elements, candidates (-1: not yet), windows (-1: not yet) */
 int clair_frontend_stats(clair_frontend_t *f, int64_t *stats);
 
+/* -- gVCF: reference-confidence blocks from the candidate search's tallies (csrc/gvcf.hip, rule in csrc/gvcf_core.h; docs/gvcf.md).
+ *    Stands for nothing in the reference, which writes no gVCF: the yardstick is the restatement in tests/gvcf_cases.py, the format is
+ *    GATK's (blocks written 0/0 with END, GQ, DP, MIN_DP, PL and banded by GQ).
+ *    _position_tallies: the seven tallies A C G T I D N of 0-based positions [first, first + n), which lie inside the tables, into out
+ *      [n][7] -- the numbers fe_candidate_flags_kernel tests (ExtractVariantCandidates.py:296-316), so that a wrong count can be told
+ *      from a wrong rule.
+ *    _gvcf_blocks: the costs c_match, c_err, c_half (1/1024 phred, each 1 .. 2^17 - 1), band_of_gq [100] (the band index of GQ 0 .. 99,
+ *      not decreasing) and the allowed set as n_iv sorted, disjoint, 0-based half-open intervals inside the tables.  *n_blocks = the
+ *      number of blocks; when capacity >= that number the records are copied to out (a second call with the same arguments only
+ *      copies).  Returns 2 with a verdict in clair_frontend_last_error for a bad argument (the handle stays usable; the host twin
+ *      clair_host_gvcf_blocks words it the same way), 3 when the front end reported a CLAIR_FE_* bit: its tallies may be incomplete,
+ *      the caller runs the host twin.
+ *    _gvcf_device_ms: milliseconds between two events around the launches of the last computation (class kernel, scan, record writer;
+ *      the host reads the block count in between), for docs/gvcf.md's numbers. */
+#ifndef CLAIR_GVCF_TYPES
+#define CLAIR_GVCF_TYPES
+typedef struct clair_gvcf_block {
+    int64_t start, end;      /* 0-based, half-open */
+    uint32_t min_dp, dp;     /* the smallest DP of the block; floor(sum of DP / length) */
+    int32_t gq;              /* the smallest GQ of the block */
+    int32_t pl[3];           /* per genotype 0/0, 0/1, 1/1 the smallest PL of the block */
+} clair_gvcf_block_t;        /* 40 bytes */
+#endif
+int clair_frontend_position_tallies(clair_frontend_t *f, int64_t first, int64_t n, uint32_t *out);
+int clair_frontend_gvcf_blocks(clair_frontend_t *f, int c_match, int c_err, int c_half, const uint8_t *band_of_gq, const int64_t *iv_start, const int64_t *iv_end,
+                               int64_t n_iv, clair_gvcf_block_t *out, int64_t capacity, int64_t *n_blocks);
+int clair_frontend_gvcf_device_ms(clair_frontend_t *f, double *ms);
+
 /* -- BGZF inflate on the device (callVarBam --bam_inflate device; csrc/inflate.hip, docs/bam_reader.md).  A handle owns one stream and
  * page-locked staging plus device buffers for max_blocks blocks (64 KiB each, both directions), reused by every call.
  * _blocks: n <= max_blocks whole BGZF blocks (header and footer included) at cdata[in_at[i] .. + csize[i]), csize >= 26; block i's

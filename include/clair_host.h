@@ -387,6 +387,33 @@ int clair_host_bamidx_result_info(const clair_host_bamidx_result_t *r, int64_t *
 int clair_host_bamidx_result_copy(const clair_host_bamidx_result_t *r, clair_bamidx_run_t *runs, uint64_t *linear, int64_t *first_window);
 void clair_host_bamidx_result_free(clair_host_bamidx_result_t *r);
 
+/* -- gVCF on the CPU (hostsrc/host_gvcf.cpp; docs/gvcf.md): the host twin of clair_frontend_position_tallies / _gvcf_blocks
+ *    (include/clair_amd.h) with the rule of csrc/gvcf_core.h, and the block rows' text.
+ *    _tally: adds one slab of the host packer (clair_host_sampack_slab) to tallies [n][7] = A C G T I D N of the 0-based positions
+ *      [lo, lo + n): only alignments flagged for the search (CLAIR_READ_EVC) count, I and D once per operation at the base before it,
+ *      exactly as fe_tally_kernel counts them (ExtractVariantCandidates.py:296-316).  *anomalies collects CLAIR_FE_SEQ_OVERRUN /
+ *      _BAD_BASE (such a base is not counted).
+ *    _blocks: the rule and a sequential segmentation over those tallies; arguments, results and verdicts (return 2) as
+ *      clair_frontend_gvcf_blocks.  ref: the reference bytes of [ref0, ref0 + ref_len).
+ *    _format: blocks [first, first + n) as VCF rows "CTG POS . REF <NON_REF> . . END=e GT:GQ:DP:MIN_DP:PL 0/0:gq:dp:min_dp:pl,pl,pl",
+ *      row_offsets [n + 1] their starts in out; *out_len is the length needed, written only when it fits out_cap. */
+#ifndef CLAIR_GVCF_TYPES
+#define CLAIR_GVCF_TYPES
+typedef struct clair_gvcf_block {
+    int64_t start, end;      /* 0-based, half-open */
+    uint32_t min_dp, dp;     /* the smallest DP of the block; floor(sum of DP / length) */
+    int32_t gq;              /* the smallest GQ of the block */
+    int32_t pl[3];           /* per genotype 0/0, 0/1, 1/1 the smallest PL of the block */
+} clair_gvcf_block_t;        /* 40 bytes */
+#endif
+int clair_host_gvcf_tally(const struct clair_read *reads, int64_t n_reads, const struct clair_op *ops, int64_t n_ops, const uint8_t *seq, int64_t seq_bytes,
+                          int64_t lo, int64_t n, uint32_t *tallies, uint32_t *anomalies);
+int clair_host_gvcf_blocks(const uint32_t *tallies, int64_t lo, int64_t n, const uint8_t *ref, int64_t ref_len, int64_t ref0, int c_match, int c_err, int c_half,
+                           const uint8_t *band_of_gq, const int64_t *iv_start, const int64_t *iv_end, int64_t n_iv, clair_gvcf_block_t *out, int64_t capacity,
+                           int64_t *n_blocks);
+int clair_host_gvcf_format(const clair_gvcf_block_t *blocks, int64_t first, int64_t n, const char *ctg_name, const uint8_t *ref, int64_t ref_len, int64_t ref0,
+                           char *out, int64_t out_cap, int64_t *out_len, int64_t *row_offsets);
+
 #ifdef __cplusplus
 }
 #endif
