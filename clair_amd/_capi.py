@@ -164,6 +164,18 @@ SIGNATURES = {
     "clair_bamidx_finish": _sig(c_vp, c_vp, c_i64, c_vp),
     "clair_bamidx_backend": _sig(c_vp, c_vp),
     "clair_bamidx_debug_frame": _sig(c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp),
+    "clair_bamsort_create": _sig(c_int, c_int, c_int, p_vp),
+    "clair_bamsort_destroy": _sig(c_vp, restype=None),
+    "clair_bamsort_last_error": _sig(c_vp, restype=c_cp),
+    "clair_bamsort_begin": _sig(c_vp, c_int, c_vp, c_i64),
+    "clair_bamsort_pass": _sig(c_vp, c_i64, c_i64, c_int),
+    "clair_bamsort_batch": _sig(c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_vp),
+    "clair_bamsort_histogram": _sig(c_vp, c_vp, c_i64),
+    "clair_bamsort_sort": _sig(c_vp, c_int, c_vp),
+    "clair_bamsort_emit": _sig(c_vp, c_i64, c_int, c_int, c_vp, c_vp),
+    "clair_bamsort_backend": _sig(c_vp, c_vp),
+    "clair_bamsort_debug_sort": _sig(c_vp, c_vp, c_i64, c_vp),
+    "clair_bamsort_debug_gather": _sig(c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64),
 }
 SYMBOLS = tuple(SIGNATURES)
 ENSEMBLE_MAX_MODELS = 8                                      # CLAIR_ENSEMBLE_MAX_MODELS

@@ -1,6 +1,7 @@
 // clair_bamidx_*: the .bai of a coordinate-sorted BAM built on the device (include/clair_amd.h; docs/index_bam.md).  A translation unit of its
 // own, outside the forward pass's sources (build.csrc_digest).  The rules are csrc/bam_index_core.h, shared with the host twin
-// (hostsrc/host_bam_index.cpp); this file holds the kernels and the handle.
+// (hostsrc/host_bam_index.cpp); this file holds the kernels and the handle.  The front of a batch -- the stream and the record starts, steps 1 and
+// 2 below -- is declared in bam_front.h and defined here; sort_bam (bam_sort.hip) runs on it too.
 //
 // A batch: the BGZF blocks are inflated (inflate_bgzf_kernel of inflate.hip, a wave per block) behind the bytes the batch before carried
 // over, into one device buffer that never goes back to the host.  Records are then framed where they lie:
@@ -25,6 +26,7 @@
 
 #define CLAIR_BIX_FN __host__ __device__ inline
 #include "bam_index_core.h"
+#include "bam_front.h"
 #include "device_buffer.h"
 #include "device_scan.h"
 #include "hip_status.h"
@@ -174,80 +176,166 @@ inline unsigned blocks_of(int64_t n, int per) { return (unsigned)((n + per - 1) 
 }  // namespace clair_bix
 
 struct clair_bamidx {
-    int device = 0, max_blocks = 0;
-    uint32_t seg = clair_bix::SEG_DEFAULT;
+    int device = 0;
     hipStream_t stream = nullptr;
     std::string error;
     // the file
     int n_ref = -1;
     std::vector<int64_t> first_window;
     DeviceBuffer d_first_window, d_linear, d_acc;
-    // the stream of a batch: two buffers, so that the bytes carried over are copied from one to the front of the other
-    DeviceBuffer d_stream[2];
-    int cur = 0;
-    int64_t carry_at = 0, carry = 0;             // in d_stream[cur]
-    uint64_t carry_voff = 0;
+    // the stream of a batch and its record starts (bam_front.h)
+    clair_bix::Front front;
     // a batch
-    DeviceBuffer d_cdata, d_meta, d_exit, d_seg_entry, d_count, d_first, d_scan, d_starts, d_result, d_tid, d_bin, d_beg, d_opens, d_run_scan, d_runs, d_detail;
-    std::vector<uint8_t> meta;
+    DeviceBuffer d_tid, d_bin, d_beg, d_opens, d_run_scan, d_runs, d_detail;
     std::vector<clair_bamidx_run_t> runs;
 };
 
-namespace {
+// ---- the batch front (bam_front.h): shared with bam_sort.hip
+namespace clair_bix {
 
-constexpr int64_t PAD = 16;                      // behind the stream and the offsets array: room the kernels must leave alone
-
-std::string g_bix_error;
-inline HipFail bix_fail(clair_bamidx *h) { return {h ? h->error : g_bix_error}; }
-
-// at least n bytes, grown by half when it has to grow: a record longer than a batch makes the stream longer batch by batch
 hipError_t at_least(DeviceBuffer &b, size_t n) {
     if (b.p && b.bytes >= n) return hipSuccess;
     return b.ensure(n + n / 2 + 256);
 }
 
-struct Framed { int64_t n_rec = 0, tail = 0; bool bad = false; };
+void Front::reset() {
+    for (DeviceBuffer *b : {&d_stream[0], &d_stream[1], &d_cdata, &d_meta, &d_exit, &d_seg_entry, &d_count, &d_first, &d_scan, &d_starts, &d_result}) b->reset();
+}
 
-// the framing of d_stream[0 .. len) from `entry`, enqueued and waited for: -> d_starts [n_rec], and what the chain ended on
-int frame(clair_bamidx *h, const uint8_t *d_stream, int64_t len, int64_t entry, Framed *out) {
-    using namespace clair_bix;
+int Front::frame(const HipFail &fail, const uint8_t *stream_bytes, int64_t stream_len, int64_t entry, Framed *out) {
     using clair_scan::totals_kernel; using clair_scan::walk_kernel; using clair_scan::write_kernel;
     *out = Framed();
     out->tail = entry;
-    if (len == 0) return 0;
-    const uint32_t seg = h->seg;
-    const int64_t n_seg = (len + seg - 1) / seg, nb = (n_seg + SCAN_BLOCK - 1) / SCAN_BLOCK, cap = len / MIN_RECORD + 1;
-    CLAIR_HIP_TRY(bix_fail(h), at_least(h->d_exit, (size_t)(n_seg * seg) * 4));
-    CLAIR_HIP_TRY(bix_fail(h), at_least(h->d_seg_entry, (size_t)n_seg * 8));
-    CLAIR_HIP_TRY(bix_fail(h), at_least(h->d_count, (size_t)n_seg * 4));
-    CLAIR_HIP_TRY(bix_fail(h), at_least(h->d_first, (size_t)n_seg * 4));
-    CLAIR_HIP_TRY(bix_fail(h), at_least(h->d_scan, (size_t)(nb + 1) * 4));
-    CLAIR_HIP_TRY(bix_fail(h), at_least(h->d_starts, (size_t)(cap + PAD) * 8));
-    CLAIR_HIP_TRY(bix_fail(h), h->d_result.ensure(2 * 8));
-    const Bytes m{d_stream};
-    uint32_t *d_exit = h->d_exit.as<uint32_t>(), *d_count = h->d_count.as<uint32_t>(), *d_first = h->d_first.as<uint32_t>(), *d_scan = h->d_scan.as<uint32_t>();
-    int64_t *d_seg_entry = h->d_seg_entry.as<int64_t>(), *d_starts = h->d_starts.as<int64_t>(), *d_result = h->d_result.as<int64_t>();
-    hipLaunchKernelGGL(exits_kernel, dim3((unsigned)n_seg), dim3(256), seg * 4, h->stream, m, len, seg, jump_rounds(seg), d_exit);
-    hipLaunchKernelGGL(chain_kernel, dim3(1), dim3(64), 0, h->stream, m, len, entry, seg, n_seg, (const uint32_t *)d_exit, d_seg_entry, d_result);
-    hipLaunchKernelGGL(count_kernel, dim3(blocks_of(n_seg, 64)), dim3(64), 0, h->stream, m, len, seg, n_seg, (const int64_t *)d_seg_entry, d_count);
-    const Counts counts{d_count};
-    hipLaunchKernelGGL((totals_kernel<Counts, ITEMS>), dim3((unsigned)nb), dim3(256), 0, h->stream, counts, n_seg, d_scan);
-    hipLaunchKernelGGL((walk_kernel<Counts, false>), dim3(1), dim3(256), 0, h->stream, Counts{d_scan}, nb, d_scan, d_scan + nb);
-    hipLaunchKernelGGL((write_kernel<Counts, ITEMS, WriteFirst>), dim3((unsigned)nb), dim3(256), 0, h->stream, counts, n_seg, (const uint32_t *)d_scan, WriteFirst{d_first});
-    hipLaunchKernelGGL(emit_kernel, dim3(blocks_of(n_seg, 64)), dim3(64), 0, h->stream, m, len, seg, n_seg, (const int64_t *)d_seg_entry, (const uint32_t *)d_first,
-                       d_starts, cap);
-    CLAIR_HIP_TRY(bix_fail(h), hipGetLastError());
+    if (stream_len == 0) return 0;
+    const int64_t n_seg = (stream_len + seg - 1) / seg, nb = (n_seg + SCAN_BLOCK - 1) / SCAN_BLOCK, cap = stream_len / MIN_RECORD + 1;
+    CLAIR_HIP_TRY(fail, at_least(d_exit, (size_t)(n_seg * seg) * 4));
+    CLAIR_HIP_TRY(fail, at_least(d_seg_entry, (size_t)n_seg * 8));
+    CLAIR_HIP_TRY(fail, at_least(d_count, (size_t)n_seg * 4));
+    CLAIR_HIP_TRY(fail, at_least(d_first, (size_t)n_seg * 4));
+    CLAIR_HIP_TRY(fail, at_least(d_scan, (size_t)(nb + 1) * 4));
+    CLAIR_HIP_TRY(fail, at_least(d_starts, (size_t)(cap + PAD) * 8));
+    CLAIR_HIP_TRY(fail, d_result.ensure(2 * 8));
+    const Bytes m{stream_bytes};
+    uint32_t *exit_d = d_exit.as<uint32_t>(), *count_d = d_count.as<uint32_t>(), *first_d = d_first.as<uint32_t>(), *scan_d = d_scan.as<uint32_t>();
+    int64_t *seg_entry_d = d_seg_entry.as<int64_t>(), *starts_d = d_starts.as<int64_t>(), *result_d = d_result.as<int64_t>();
+    hipLaunchKernelGGL(exits_kernel, dim3((unsigned)n_seg), dim3(256), seg * 4, stream, m, stream_len, seg, jump_rounds(seg), exit_d);
+    hipLaunchKernelGGL(chain_kernel, dim3(1), dim3(64), 0, stream, m, stream_len, entry, seg, n_seg, (const uint32_t *)exit_d, seg_entry_d, result_d);
+    hipLaunchKernelGGL(count_kernel, dim3(blocks_of(n_seg, 64)), dim3(64), 0, stream, m, stream_len, seg, n_seg, (const int64_t *)seg_entry_d, count_d);
+    const Counts counts{count_d};
+    hipLaunchKernelGGL((totals_kernel<Counts, ITEMS>), dim3((unsigned)nb), dim3(256), 0, stream, counts, n_seg, scan_d);
+    hipLaunchKernelGGL((walk_kernel<Counts, false>), dim3(1), dim3(256), 0, stream, Counts{scan_d}, nb, scan_d, scan_d + nb);
+    hipLaunchKernelGGL((write_kernel<Counts, ITEMS, WriteFirst>), dim3((unsigned)nb), dim3(256), 0, stream, counts, n_seg, (const uint32_t *)scan_d, WriteFirst{first_d});
+    hipLaunchKernelGGL(emit_kernel, dim3(blocks_of(n_seg, 64)), dim3(64), 0, stream, m, stream_len, seg, n_seg, (const int64_t *)seg_entry_d, (const uint32_t *)first_d,
+                       starts_d, cap);
+    CLAIR_HIP_TRY(fail, hipGetLastError());
     uint32_t n_rec = 0;
     int64_t result[2] = {0, 0};
-    CLAIR_HIP_TRY(bix_fail(h), hipMemcpyAsync(&n_rec, d_scan + nb, 4, hipMemcpyDeviceToHost, h->stream));
-    CLAIR_HIP_TRY(bix_fail(h), hipMemcpyAsync(result, d_result, sizeof result, hipMemcpyDeviceToHost, h->stream));
-    CLAIR_HIP_TRY(bix_fail(h), hipStreamSynchronize(h->stream));
-    if ((int64_t)n_rec > cap || result[0] < entry || result[0] > len) return bix_fail(h)("framing: %u records, tail %lld in %lld bytes: the frame pass is broken", n_rec, (long long)result[0], (long long)len);
+    CLAIR_HIP_TRY(fail, hipMemcpyAsync(&n_rec, scan_d + nb, 4, hipMemcpyDeviceToHost, stream));
+    CLAIR_HIP_TRY(fail, hipMemcpyAsync(result, result_d, sizeof result, hipMemcpyDeviceToHost, stream));
+    CLAIR_HIP_TRY(fail, hipStreamSynchronize(stream));
+    if ((int64_t)n_rec > cap || result[0] < entry || result[0] > stream_len) return fail("framing: %u records, tail %lld in %lld bytes: the frame pass is broken", n_rec, (long long)result[0], (long long)stream_len);
     out->n_rec = n_rec;
     out->tail = result[0];
     out->bad = result[1] != 0;
     return 0;
 }
+
+int Front::open_batch(const HipFail &fail, const uint8_t *cdata, int64_t cbytes, int n, const int64_t *in_at, const int32_t *csize, const int32_t *out_len,
+                      const int64_t *coffset, int64_t end_coffset, int64_t entry) {
+    if (clair_inf::check_blocks(fail, n, max_blocks, cbytes, in_at, csize, out_len)) return 1;
+    len = carry;
+    for (int i = 0; i < n; ++i) {
+        if (coffset[i] < 0) return fail("block %d: negative offset", i);
+        len += out_len[i];
+    }
+    if (entry > len) return fail("batch: entry %lld beyond the %lld bytes of the batch", (long long)entry, (long long)len);
+    // 1. the stream: the carried bytes to the front of the other buffer, the blocks inflated behind them
+    to = 1 - cur;
+    CLAIR_HIP_TRY(fail, at_least(d_stream[to], (size_t)(len + PAD)));
+    bytes = d_stream[to].as<uint8_t>();
+    if (carry) CLAIR_HIP_TRY(fail, hipMemcpyAsync(bytes, d_stream[cur].as<uint8_t>() + carry_at, (size_t)carry, hipMemcpyDeviceToDevice, stream));
+    // meta, one copy: the table (at, voff: n_tab entries each), then the blocks' arrays (inflate_launch.h)
+    n_tab = n + 1 + (carry ? 1 : 0);
+    const size_t N = (size_t)n, T = (size_t)n_tab;
+    meta.assign(T * 16 + N * clair_inf::META_PER_BLOCK, 0);
+    int64_t *at = (int64_t *)meta.data();
+    uint64_t *voff = (uint64_t *)(at + T);
+    m_at = at;
+    m_voff = voff;
+    const clair_inf::BlockMeta mb = clair_inf::carve_meta(voff + T, N);
+    {
+        int k = 0;
+        int64_t pos = carry;
+        if (carry) { at[k] = 0; voff[k++] = carry_voff; }
+        for (int i = 0; i < n; ++i) {
+            at[k] = pos;
+            voff[k++] = (uint64_t)coffset[i] << 16;
+            mb.in_at[i] = in_at[i];
+            mb.out_at[i] = pos;
+            mb.csize[i] = csize[i];
+            mb.out_len[i] = out_len[i];
+            pos += out_len[i];
+        }
+        at[k] = len;
+        voff[k] = (uint64_t)end_coffset << 16;
+    }
+    CLAIR_HIP_TRY(fail, at_least(d_meta, meta.size()));
+    CLAIR_HIP_TRY(fail, hipMemcpyAsync(d_meta.p, meta.data(), meta.size(), hipMemcpyHostToDevice, stream));
+    d_at = d_meta.as<int64_t>();
+    d_voff = (const uint64_t *)(d_at + T);
+    const clair_inf::BlockMeta db = clair_inf::carve_meta(d_meta.as<int64_t>() + 2 * T, N);
+    std::vector<int32_t> status(N, 0);
+    if (n > 0) {
+        // (the inflate kernel reads whole 16-byte pieces around each deflate stream)
+        if (!d_cdata.p || d_cdata.bytes < (size_t)cbytes + 32) {
+            CLAIR_HIP_TRY(fail, d_cdata.ensure((size_t)std::max<int64_t>(cbytes, (int64_t)max_blocks * 32768) + 32));
+            CLAIR_HIP_TRY(fail, hipMemsetAsync(d_cdata.p, 0, d_cdata.bytes, stream));
+        }
+        CLAIR_HIP_TRY(fail, hipMemcpyAsync(d_cdata.p, cdata, (size_t)cbytes, hipMemcpyHostToDevice, stream));
+        CLAIR_HIP_TRY(fail, clair_inf::launch_bgzf(stream, d_cdata.as<uint8_t>(), n, db, bytes));
+        CLAIR_HIP_TRY(fail, hipMemcpyAsync(status.data(), db.status, N * 4, hipMemcpyDeviceToHost, stream));
+    }
+    // 2. the record starts (waits for the stream: the statuses are here with them)
+    if (frame(fail, bytes, len, entry, &fr)) return 1;
+    if (len == 0) CLAIR_HIP_TRY(fail, hipStreamSynchronize(stream));
+    for (int i = 0; i < n; ++i)
+        if (status[(size_t)i] != 0) return fail("BGZF block at compressed offset %lld: %s", (long long)coffset[i], clair_inf::bgzf_status_text(status[(size_t)i]));
+    return 0;
+}
+
+int Front::close_batch(const HipFail &fail, int last) {
+    // the verdicts of the frame step: the 4 bytes of the size word the chain stopped on are all that is read back
+    if (fr.bad) {
+        uint8_t word[4] = {0, 0, 0, 0};
+        CLAIR_HIP_TRY(fail, hipMemcpyAsync(word, bytes + fr.tail, 4, hipMemcpyDeviceToHost, stream));
+        CLAIR_HIP_TRY(fail, hipStreamSynchronize(stream));
+        char buf[200];
+        describe_bad_step(buf, sizeof buf, voffset(fr.tail), Bytes{word}.le32(0));
+        return fail("%s", buf);
+    }
+    if (last && fr.tail < len) {
+        CLAIR_HIP_TRY(fail, hipStreamSynchronize(stream));
+        char buf[200];
+        describe_cut(buf, sizeof buf, voffset(fr.tail));
+        return fail("%s", buf);
+    }
+    CLAIR_HIP_TRY(fail, hipStreamSynchronize(stream));
+    cur = to;
+    carry_at = fr.tail;
+    carry = len - fr.tail;
+    carry_voff = carry ? voffset(fr.tail) : 0;
+    return 0;
+}
+
+}  // namespace clair_bix
+
+namespace {
+
+using clair_bix::at_least;
+using clair_bix::PAD;
+
+std::string g_bix_error;
+inline HipFail bix_fail(clair_bamidx *h) { return {h ? h->error : g_bix_error}; }
 
 }  // namespace
 
@@ -266,14 +354,15 @@ int clair_bamidx_create(int device, int max_blocks, int segment_bytes, clair_bam
     if (hip_device_check(bix_fail(nullptr), device, "the device index build runs on an MI355X only (the host one is index_bam --backend host)")) return 1;
     clair_bamidx *h = new clair_bamidx;
     h->device = device;
-    h->max_blocks = max_blocks;
-    h->seg = (uint32_t)segment_bytes;
+    h->front.max_blocks = max_blocks;
+    h->front.seg = (uint32_t)segment_bytes;
     const auto open = [&]() -> int {
         CLAIR_HIP_TRY(bix_fail(nullptr), hipSetDevice(device));
         CLAIR_HIP_TRY(bix_fail(nullptr), hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
         return 0;
     };
     if (open()) { clair_bamidx_destroy(h); return 1; }
+    h->front.stream = h->stream;
     *out = h;
     return 0;
 }
@@ -282,10 +371,9 @@ void clair_bamidx_destroy(clair_bamidx_t *h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (DeviceBuffer *b : {&h->d_first_window, &h->d_linear, &h->d_acc, &h->d_stream[0], &h->d_stream[1], &h->d_cdata, &h->d_meta, &h->d_exit, &h->d_seg_entry,
-                            &h->d_count, &h->d_first, &h->d_scan, &h->d_starts, &h->d_result, &h->d_tid, &h->d_bin, &h->d_beg, &h->d_opens, &h->d_run_scan,
-                            &h->d_runs, &h->d_detail})
+    for (DeviceBuffer *b : {&h->d_first_window, &h->d_linear, &h->d_acc, &h->d_tid, &h->d_bin, &h->d_beg, &h->d_opens, &h->d_run_scan, &h->d_runs, &h->d_detail})
         b->reset();                              // before the stream goes, not in the destructor
+    h->front.reset();
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -308,8 +396,7 @@ int clair_bamidx_begin(clair_bamidx_t *h, int n_ref, const int64_t *ref_len) {
     const unsigned long long acc[A_WORDS] = {NO_ERROR, 0, 0, 0};
     CLAIR_HIP_TRY(bix_fail(h), hipMemcpyAsync(h->d_acc.p, acc, sizeof acc, hipMemcpyHostToDevice, h->stream));
     CLAIR_HIP_TRY(bix_fail(h), hipStreamSynchronize(h->stream));
-    h->carry = h->carry_at = 0;
-    h->carry_voff = 0;
+    h->front.rewind();
     h->n_ref = n_ref;
     return 0;
 }
@@ -326,68 +413,17 @@ int clair_bamidx_batch(clair_bamidx_t *h, const uint8_t *cdata, int64_t cbytes, 
     if (cbytes < 0 || end_coffset < 0 || entry < 0) return bix_fail(h)("batch: negative argument");
     const int n_ref = h->n_ref;
     h->n_ref = -1;                               // a batch that fails leaves a handle that wants begin
-    if (clair_inf::check_blocks(bix_fail(h), n, h->max_blocks, cbytes, in_at, csize, out_len)) return 1;
-    int64_t len = h->carry;
-    for (int i = 0; i < n; ++i) {
-        if (coffset[i] < 0) return bix_fail(h)("block %d: negative offset", i);
-        len += out_len[i];
-    }
-    if (entry > len) return bix_fail(h)("batch: entry %lld beyond the %lld bytes of the batch", (long long)entry, (long long)len);
     CLAIR_HIP_TRY(bix_fail(h), hipSetDevice(h->device));
-    // 1. the stream: the carried bytes to the front of the other buffer, the blocks inflated behind them
-    const int to = 1 - h->cur;
-    CLAIR_HIP_TRY(bix_fail(h), at_least(h->d_stream[to], (size_t)(len + PAD)));
-    uint8_t *d_stream = h->d_stream[to].as<uint8_t>();
-    if (h->carry) CLAIR_HIP_TRY(bix_fail(h), hipMemcpyAsync(d_stream, h->d_stream[h->cur].as<uint8_t>() + h->carry_at, (size_t)h->carry, hipMemcpyDeviceToDevice, h->stream));
-    // meta, one copy: the table (at, voff: n_tab entries each), then the blocks' arrays (inflate_launch.h)
-    const int n_tab = n + 1 + (h->carry ? 1 : 0);
-    const size_t N = (size_t)n, T = (size_t)n_tab;
-    h->meta.assign(T * 16 + N * clair_inf::META_PER_BLOCK, 0);
-    int64_t *m_at = (int64_t *)h->meta.data();
-    uint64_t *m_voff = (uint64_t *)(m_at + T);
-    const clair_inf::BlockMeta mb = clair_inf::carve_meta(m_voff + T, N);
-    {
-        int k = 0;
-        int64_t pos = h->carry;
-        if (h->carry) { m_at[k] = 0; m_voff[k++] = h->carry_voff; }
-        for (int i = 0; i < n; ++i) {
-            m_at[k] = pos;
-            m_voff[k++] = (uint64_t)coffset[i] << 16;
-            mb.in_at[i] = in_at[i];
-            mb.out_at[i] = pos;
-            mb.csize[i] = csize[i];
-            mb.out_len[i] = out_len[i];
-            pos += out_len[i];
-        }
-        m_at[k] = len;
-        m_voff[k] = (uint64_t)end_coffset << 16;
-    }
-    CLAIR_HIP_TRY(bix_fail(h), at_least(h->d_meta, h->meta.size()));
-    CLAIR_HIP_TRY(bix_fail(h), hipMemcpyAsync(h->d_meta.p, h->meta.data(), h->meta.size(), hipMemcpyHostToDevice, h->stream));
-    const int64_t *d_at = h->d_meta.as<int64_t>();
-    const uint64_t *d_voff = (const uint64_t *)(d_at + T);
-    const clair_inf::BlockMeta db = clair_inf::carve_meta(h->d_meta.as<int64_t>() + 2 * T, N);
-    std::vector<int32_t> status(N, 0);
-    if (n > 0) {
-        // (the inflate kernel reads whole 16-byte pieces around each deflate stream)
-        if (!h->d_cdata.p || h->d_cdata.bytes < (size_t)cbytes + 32) {
-            CLAIR_HIP_TRY(bix_fail(h), h->d_cdata.ensure((size_t)std::max<int64_t>(cbytes, (int64_t)h->max_blocks * 32768) + 32));
-            CLAIR_HIP_TRY(bix_fail(h), hipMemsetAsync(h->d_cdata.p, 0, h->d_cdata.bytes, h->stream));
-        }
-        CLAIR_HIP_TRY(bix_fail(h), hipMemcpyAsync(h->d_cdata.p, cdata, (size_t)cbytes, hipMemcpyHostToDevice, h->stream));
-        CLAIR_HIP_TRY(bix_fail(h), clair_inf::launch_bgzf(h->stream, h->d_cdata.as<uint8_t>(), n, db, d_stream));
-        CLAIR_HIP_TRY(bix_fail(h), hipMemcpyAsync(status.data(), db.status, N * 4, hipMemcpyDeviceToHost, h->stream));
-    }
-    // 2. the record starts (waits for the stream: the statuses are here with them)
-    Framed fr;
-    if (frame(h, d_stream, len, entry, &fr)) return 1;
-    if (len == 0) CLAIR_HIP_TRY(bix_fail(h), hipStreamSynchronize(h->stream));
-    for (int i = 0; i < n; ++i)
-        if (status[(size_t)i] != 0) return bix_fail(h)("BGZF block at compressed offset %lld: %s", (long long)coffset[i], clair_inf::bgzf_status_text(status[(size_t)i]));
+    // 1, 2. the stream and the record starts (bam_front.h)
+    Front &front = h->front;
+    if (front.open_batch(bix_fail(h), cdata, cbytes, n, in_at, csize, out_len, coffset, end_coffset, entry)) return 1;
+    const Framed &fr = front.fr;
+    const int64_t len = front.len;
+    uint8_t *d_stream = front.bytes;
+    const int n_tab = front.n_tab;
     const int64_t n_rec = fr.n_rec;
     const Bytes m{d_stream};
-    const Table table{d_at, d_voff, n_tab, n_ref, h->d_first_window.as<int64_t>()};
-    const auto voffset = [&](int64_t p) { return voffset_at(m_at, m_voff, n_tab, p); };
+    const Table table{front.d_at, front.d_voff, n_tab, n_ref, h->d_first_window.as<int64_t>()};
     h->runs.clear();
     uint32_t n_runs = 0;
     if (n_rec > 0) {
@@ -399,7 +435,7 @@ int clair_bamidx_batch(clair_bamidx_t *h, const uint8_t *cdata, int64_t cbytes, 
         CLAIR_HIP_TRY(bix_fail(h), at_least(h->d_opens, (size_t)n_rec));
         CLAIR_HIP_TRY(bix_fail(h), at_least(h->d_run_scan, (size_t)(nb + 1) * 4));
         CLAIR_HIP_TRY(bix_fail(h), at_least(h->d_runs, (size_t)n_rec * sizeof(clair_bamidx_run_t)));
-        const int64_t *d_starts = h->d_starts.as<int64_t>();
+        const int64_t *d_starts = front.starts();
         int32_t *d_tid = h->d_tid.as<int32_t>();
         uint32_t *d_bin = h->d_bin.as<uint32_t>(), *d_scan = h->d_run_scan.as<uint32_t>();
         uint64_t *d_beg = h->d_beg.as<uint64_t>();
@@ -439,40 +475,22 @@ int clair_bamidx_batch(clair_bamidx_t *h, const uint8_t *cdata, int64_t cbytes, 
         h->runs.resize(n_runs);
         CLAIR_HIP_TRY(bix_fail(h), hipMemcpyAsync(h->runs.data(), h->d_runs.p, (size_t)n_runs * sizeof(clair_bamidx_run_t), hipMemcpyDeviceToHost, h->stream));
     }
-    // the verdicts of the frame step: the 4 bytes of the size word the chain stopped on are all that is read back
-    if (fr.bad) {
-        uint8_t word[4] = {0, 0, 0, 0};
-        CLAIR_HIP_TRY(bix_fail(h), hipMemcpyAsync(word, d_stream + fr.tail, 4, hipMemcpyDeviceToHost, h->stream));
-        CLAIR_HIP_TRY(bix_fail(h), hipStreamSynchronize(h->stream));
-        char buf[200];
-        describe_bad_step(buf, sizeof buf, voffset(fr.tail), Bytes{word}.le32(0));
-        return bix_fail(h)("%s", buf);
-    }
-    if (last && fr.tail < len) {
-        CLAIR_HIP_TRY(bix_fail(h), hipStreamSynchronize(h->stream));
-        char buf[200];
-        describe_cut(buf, sizeof buf, voffset(fr.tail));
-        return bix_fail(h)("%s", buf);
-    }
+    if (front.close_batch(bix_fail(h), last)) return 1;
     // the last record's (tid, pos): 8 bytes
     int32_t last_key[2] = {(int32_t)state[ST_PREV_TID], (int32_t)state[ST_PREV_POS]};
     if (n_rec > 0) {
         int64_t last_start = 0;
-        CLAIR_HIP_TRY(bix_fail(h), hipMemcpyAsync(&last_start, h->d_starts.as<int64_t>() + (n_rec - 1), 8, hipMemcpyDeviceToHost, h->stream));
+        CLAIR_HIP_TRY(bix_fail(h), hipMemcpyAsync(&last_start, front.starts() + (n_rec - 1), 8, hipMemcpyDeviceToHost, h->stream));
         CLAIR_HIP_TRY(bix_fail(h), hipStreamSynchronize(h->stream));
         if (last_start < 0 || last_start + 12 > len) return bix_fail(h)("batch: last record at %lld of %lld bytes: the frame pass is broken", (long long)last_start, (long long)len);
         CLAIR_HIP_TRY(bix_fail(h), hipMemcpyAsync(last_key, d_stream + last_start + 4, 8, hipMemcpyDeviceToHost, h->stream));
     }
     CLAIR_HIP_TRY(bix_fail(h), hipStreamSynchronize(h->stream));
-    h->cur = to;
-    h->carry_at = fr.tail;
-    h->carry = len - fr.tail;
-    h->carry_voff = h->carry ? voffset(fr.tail) : 0;
     state[ST_N_RECORDS] = n_rec;
     state[ST_N_RUNS] = (int64_t)n_runs;
     state[ST_LAST_TID] = last_key[0];
     state[ST_LAST_POS] = last_key[1];
-    state[ST_CARRY] = h->carry;
+    state[ST_CARRY] = front.carry;
     *runs = h->runs.data();
     h->n_ref = n_ref;
     return 0;
@@ -511,23 +529,24 @@ int clair_bamidx_debug_frame(clair_bamidx_t *h, const uint8_t *stream, int64_t n
     if (!h) return bix_fail(nullptr)("bamidx handle is NULL");
     if (n < 0 || n > (int64_t)INT32_MAX || (n > 0 && !stream) || entry < 0 || entry > n || cap < 0 || (cap > 0 && !starts) || !result) return bix_fail(h)("debug_frame: bad arguments");
     CLAIR_HIP_TRY(bix_fail(h), hipSetDevice(h->device));
-    h->carry = h->carry_at = 0;                  // the stream buffers are borrowed: a file in progress is over
+    Front &front = h->front;
+    front.rewind();                              // the stream buffers are borrowed: a file in progress is over
     h->n_ref = -1;
     const int64_t max_rec = n / MIN_RECORD + 1;
-    CLAIR_HIP_TRY(bix_fail(h), at_least(h->d_stream[0], (size_t)(n + PAD)));
-    CLAIR_HIP_TRY(bix_fail(h), at_least(h->d_starts, (size_t)(max_rec + PAD) * 8));
-    uint8_t *d_stream = h->d_stream[0].as<uint8_t>();
+    CLAIR_HIP_TRY(bix_fail(h), at_least(front.d_stream[0], (size_t)(n + PAD)));
+    CLAIR_HIP_TRY(bix_fail(h), at_least(front.d_starts, (size_t)(max_rec + PAD) * 8));
+    uint8_t *d_stream = front.d_stream[0].as<uint8_t>();
     // sentinels: PAD bytes behind the stream, PAD words behind the most offsets there can be
     CLAIR_HIP_TRY(bix_fail(h), hipMemsetAsync(d_stream + n, 0xa5, (size_t)PAD, h->stream));
-    CLAIR_HIP_TRY(bix_fail(h), hipMemsetAsync(h->d_starts.as<int64_t>() + max_rec, 0xa5, (size_t)PAD * 8, h->stream));
+    CLAIR_HIP_TRY(bix_fail(h), hipMemsetAsync(front.d_starts.as<int64_t>() + max_rec, 0xa5, (size_t)PAD * 8, h->stream));
     if (n) CLAIR_HIP_TRY(bix_fail(h), hipMemcpyAsync(d_stream, stream, (size_t)n, hipMemcpyHostToDevice, h->stream));
     Framed fr;
-    if (frame(h, d_stream, n, entry, &fr)) return 1;
+    if (front.frame(bix_fail(h), d_stream, n, entry, &fr)) return 1;
     if (fr.n_rec > cap) return bix_fail(h)("debug_frame: %lld records, room for %lld", (long long)fr.n_rec, (long long)cap);
     uint8_t behind[PAD + PAD * 8];
-    if (fr.n_rec) CLAIR_HIP_TRY(bix_fail(h), hipMemcpyAsync(starts, h->d_starts.p, (size_t)fr.n_rec * 8, hipMemcpyDeviceToHost, h->stream));
+    if (fr.n_rec) CLAIR_HIP_TRY(bix_fail(h), hipMemcpyAsync(starts, front.d_starts.p, (size_t)fr.n_rec * 8, hipMemcpyDeviceToHost, h->stream));
     CLAIR_HIP_TRY(bix_fail(h), hipMemcpyAsync(behind, d_stream + n, (size_t)PAD, hipMemcpyDeviceToHost, h->stream));
-    CLAIR_HIP_TRY(bix_fail(h), hipMemcpyAsync(behind + PAD, h->d_starts.as<int64_t>() + max_rec, (size_t)PAD * 8, hipMemcpyDeviceToHost, h->stream));
+    CLAIR_HIP_TRY(bix_fail(h), hipMemcpyAsync(behind + PAD, front.d_starts.as<int64_t>() + max_rec, (size_t)PAD * 8, hipMemcpyDeviceToHost, h->stream));
     CLAIR_HIP_TRY(bix_fail(h), hipStreamSynchronize(h->stream));
     bool intact = true;
     for (uint8_t b : behind) intact = intact && b == 0xa5;

@@ -19,6 +19,7 @@
 #define CLAIR_DEF_WAVE 1
 #include "device_buffer.h"
 #include "deflate_core.h"
+#include "deflate_launch.h"
 
 namespace clair_def {
 
@@ -64,6 +65,12 @@ __global__ __launch_bounds__(64) void deflate_bgzf_kernel(const uint8_t *__restr
     c.sync();
     const uint32_t cs = deflate_bgzf(c, len);
     if (lane == 0) csize[b] = (int32_t)cs;
+}
+
+hipError_t launch_deflate_bgzf(hipStream_t stream, const uint8_t *data, int n, const int32_t *in_at, const int32_t *in_len, uint8_t *out, int32_t *csize) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(deflate_bgzf_kernel, dim3((unsigned)n), dim3(64), 0, stream, data, n, in_at, in_len, out, csize);
+    return hipGetLastError();
 }
 
 }  // namespace clair_def
@@ -136,9 +143,7 @@ int clair_deflate_blocks(clair_deflate_t *h, const uint8_t *data, int64_t bytes,
     int32_t *d_at = h->d_meta.as<int32_t>(), *d_len = d_at + N, *d_csize = d_len + N;
     if (total) CLAIR_HIP_TRY(def_fail(h), hipMemcpyAsync(h->d_in.p, h_in, (size_t)total, hipMemcpyHostToDevice, h->stream));
     CLAIR_HIP_TRY(def_fail(h), hipMemcpyAsync(h->d_meta.p, h->h_meta.p, N * 2 * 4, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(clair_def::deflate_bgzf_kernel, dim3((unsigned)n), dim3(64), 0, h->stream, h->d_in.as<const uint8_t>(), n, (const int32_t *)d_at,
-                       (const int32_t *)d_len, h->d_out.as<uint8_t>(), d_csize);
-    CLAIR_HIP_TRY(def_fail(h), hipGetLastError());
+    CLAIR_HIP_TRY(def_fail(h), clair_def::launch_deflate_bgzf(h->stream, h->d_in.as<const uint8_t>(), n, d_at, d_len, h->d_out.as<uint8_t>(), d_csize));
     CLAIR_HIP_TRY(def_fail(h), hipMemcpyAsync(h_out, h->d_out.p, (size_t)n * DEF_SLOT, hipMemcpyDeviceToHost, h->stream));
     CLAIR_HIP_TRY(def_fail(h), hipMemcpyAsync(m_csize, d_csize, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
     CLAIR_HIP_TRY(def_fail(h), hipStreamSynchronize(h->stream));

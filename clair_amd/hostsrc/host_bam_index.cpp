@@ -1,14 +1,14 @@
 // index_bam on the CPU (include/clair_host.h: clair_host_bamidx_*; docs/index_bam.md).  Three things:
 //   - the host twin of csrc/bam_index.hip: the same batch interface and the rules of csrc/bam_index_core.h as sequential loops.  Blocks are
-//     inflated by zlib on a few threads (hostsrc/bgzf_file.h); records are framed by the plain walk, or -- so that the parallel rule can be held against the walk
-//     on a machine without a GPU -- by a restatement of the segmented framing the device runs (jump table per segment, pointer jumping, the
-//     chain over the segments, counts, offsets);
+//     inflated by zlib on a few threads (hostsrc/bgzf_file.h); records are framed by the plain walk, or by the restatement of the segmented
+//     framing the device runs (hostsrc/bam_frame.h, shared with host_bam_sort.cpp);
 //   - the file driver both backends run under: the BAM header (hostsrc/bam_header.h), block after block of the file (hostsrc/bgzf_file.h) in
 //     batches of max_blocks, the runs joined across batches;
 //   - the result the Python side writes the .bai from (clair_amd/index_bam.py).
 // Plain C++17 + zlib, no HIP.
 #include "../../include/clair_host.h"
 #include "../csrc/bam_index_core.h"
+#include "bam_frame.h"
 #include "bam_header.h"
 #include "bgzf_file.h"
 
@@ -23,45 +23,7 @@ namespace {
 
 using namespace clair_bix;
 using namespace clair_bgzf;
-
-// ---- framing.  Both give the record starts from `entry`, the tail (where the chain stops) and whether it stopped on a bad step.
-void frame_walk(const Bytes &m, int64_t len, int64_t entry, std::vector<int64_t> &starts, int64_t *tail, bool *bad) {
-    int64_t o = entry, next = 0;
-    int rc;
-    while ((rc = step(m, o, len, &next)) == STEP_NEXT) { starts.push_back(o); o = next; }
-    *tail = o;
-    *bad = rc == STEP_BAD;
-}
-
-// the device's rule, restated: what each kernel of csrc/bam_index.hip does, a loop per kernel
-void frame_segmented(const Bytes &m, int64_t len, int64_t entry, uint32_t seg, std::vector<int64_t> &starts, int64_t *tail, bool *bad) {
-    const int64_t n_seg = (len + seg - 1) / seg;
-    std::vector<uint32_t> exit((size_t)(n_seg * seg)), now(seg);
-    const int rounds = jump_rounds(seg);
-    for (int64_t s = 0; s < n_seg; ++s) {                    // exits_kernel: a workgroup per segment
-        uint32_t *e = exit.data() + s * seg;
-        for (uint32_t o = 0; o < seg; ++o) e[o] = seg_next(m, s * (int64_t)seg, o, len);
-        for (int r = 0; r < rounds; ++r) {
-            for (uint32_t o = 0; o < seg; ++o) now[o] = e[o] < seg ? e[e[o]] : e[o];     // every lane reads, a barrier, every lane writes
-            std::copy(now.begin(), now.end(), e);
-        }
-    }
-    std::vector<int64_t> seg_entry((size_t)n_seg), first((size_t)n_seg + 1, 0);
-    int64_t result[2];
-    chain_walk(m, len, entry, seg, n_seg, exit.data(), seg_entry.data(), result);        // chain_kernel: one thread
-    for (int64_t s = 0; s < n_seg; ++s)                      // count_kernel and the scan
-        first[(size_t)s + 1] = first[(size_t)s] + (seg_entry[(size_t)s] < 0 ? 0 : seg_records(m, len, seg, s, seg_entry[(size_t)s], nullptr, 0, 0));
-    const size_t before = starts.size();
-    starts.resize(before + (size_t)first[(size_t)n_seg]);
-    for (int64_t s = 0; s < n_seg; ++s)                      // emit_kernel
-        if (seg_entry[(size_t)s] >= 0) seg_records(m, len, seg, s, seg_entry[(size_t)s], starts.data() + before, first[(size_t)s], first[(size_t)n_seg]);
-    *tail = result[0];
-    *bad = result[1] != 0;
-}
-
-bool good_segment(int segment_bytes) {
-    return segment_bytes >= (int)SEG_MIN && segment_bytes <= (int)SEG_MAX && (segment_bytes & (segment_bytes - 1)) == 0;
-}
+using namespace clair_frame;
 
 }  // namespace
 

@@ -1,0 +1,548 @@
+// sort_bam on the CPU (include/clair_host.h: clair_host_bamsort_*; docs/sort_bam.md).  Two things:
+//   - the host twin of csrc/bam_sort.hip: the same calls and the rules of csrc/bam_sort_core.h as sequential loops.  Blocks are inflated by
+//     zlib on a few threads (hostsrc/bgzf_file.h), records framed as host_bam_index.cpp frames them (hostsrc/bam_frame.h), kept records
+//     compacted into the group buffer, the group ordered by std::stable_sort over (key, index), gathered, cut every 65280 bytes and
+//     compressed by the host twin of the device compressor (host_deflate.cpp);
+//   - the file driver both backends run under: the BAM header (hostsrc/bam_header.h), the first read with the byte histogram, the groups of
+//     buckets when the file does not fit, one more read per group, the blocks appended to the output, the EOF marker.
+// Plain C++17 + zlib, no HIP.
+#include "../../include/clair_host.h"
+#include "../csrc/bam_sort_core.h"
+#include "bam_frame.h"
+#include "bam_header.h"
+#include "bgzf_file.h"
+
+#include <algorithm>
+#include <climits>
+#include <cstdio>
+#include <cstring>
+#include <numeric>
+#include <string>
+#include <thread>
+#include <vector>
+
+namespace {
+
+using namespace clair_bsort;
+using namespace clair_bgzf;
+using namespace clair_frame;
+
+// payload i of n: in_len[i] bytes at data + i * PAYLOAD -> one BGZF block in its slot, its size in sizes[i]; thread t takes t, t + nt, ...
+int deflate_payloads(int threads, const uint8_t *data, int n, const int32_t *in_len, uint8_t *out, int32_t *sizes) {
+    std::vector<int> rc((size_t)n, 0);
+    const auto one = [&](int i) {
+        int64_t n_out = 0;
+        rc[(size_t)i] = clair_host_deflate_bgzf(data + (int64_t)i * PAYLOAD, in_len[i], out + (int64_t)i * SLOT, &n_out);
+        sizes[i] = (int32_t)n_out;
+    };
+    const int nt = std::max(1, std::min(threads, n));
+    if (nt == 1) {
+        for (int i = 0; i < n; ++i) one(i);
+    } else {
+        std::vector<std::thread> pool;
+        for (int t = 0; t < nt; ++t) pool.emplace_back([&, t] { for (int i = t; i < n; i += nt) one(i); });
+        for (auto &th : pool) th.join();
+    }
+    for (int i = 0; i < n; ++i) if (rc[(size_t)i]) return clair_host_fail("deflate of payload %d failed", i);
+    return 0;
+}
+
+// one BGZF block by zlib at level 6; stored when that is what fits the 64 KiB (clair_amd/bgzf.py: zlib_block)
+int zlib_payload(const uint8_t *data, int32_t len, uint8_t *out, int32_t *size) {
+    static const uint8_t head[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
+    for (int level : {6, 0}) {
+        z_stream z{};
+        if (deflateInit2(&z, level, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) return clair_host_fail("deflateInit2 failed");
+        z.next_in = const_cast<uint8_t *>(data);
+        z.avail_in = (uInt)len;
+        z.next_out = out + BGZF_HEADER;
+        z.avail_out = (uInt)(SLOT - BGZF_HEADER - BGZF_FOOTER);
+        const int rc = deflate(&z, Z_FINISH);
+        const size_t got = z.total_out;
+        deflateEnd(&z);
+        if (rc != Z_STREAM_END) continue;
+        memcpy(out, head, 16);
+        const uint32_t total = (uint32_t)got + BGZF_HEADER + BGZF_FOOTER, crc = (uint32_t)crc32(0L, data, (uInt)len);
+        out[16] = (uint8_t)((total - 1) & 0xff);
+        out[17] = (uint8_t)((total - 1) >> 8);
+        uint8_t *foot = out + BGZF_HEADER + got;
+        for (int k = 0; k < 4; ++k) { foot[k] = (uint8_t)(crc >> (8 * k)); foot[4 + k] = (uint8_t)((uint32_t)len >> (8 * k)); }
+        *size = (int32_t)total;
+        return 0;
+    }
+    return clair_host_fail("a payload of %d bytes does not fit a BGZF block", len);
+}
+
+}  // namespace
+
+struct clair_host_bamsort {
+    int threads = 4, max_blocks = 0;
+    uint32_t seg = 0;                            // 0: the sequential walk
+    // the file
+    int n_ref = -1;
+    int64_t memory = 0;
+    std::vector<int64_t> ref_len, first_bucket;  // n_ref; n_ref + 1
+    std::vector<int64_t> hist;
+    // the read in progress
+    int64_t lo = 0, hi = 0;
+    bool first = false, overflow = false;
+    std::vector<uint8_t> stream, carry;
+    uint64_t carry_voff = 0;
+    std::vector<int64_t> at, starts;
+    std::vector<uint64_t> voff;
+    // the group
+    std::vector<uint8_t> group;
+    std::vector<uint64_t> keys;
+    std::vector<int64_t> off;                    // of each kept record in the group buffer, one more for its end
+    // the output
+    std::vector<uint8_t> sorted, out_carry;
+    int64_t total = 0;
+};
+
+struct clair_host_bamsort_job {
+    std::string path;
+    FILE *file = nullptr;
+    int64_t file_size = 0;
+    std::vector<uint8_t> text;                   // the inflated header, and what follows it in its last block
+    BamHeader header;
+    int64_t coffset = 0, entry = 0;              // where the first record's block starts, the record's offset in it
+    ~clair_host_bamsort_job() { if (file) fclose(file); }
+};
+
+extern "C" {
+
+int clair_host_bamsort_create(int threads, int max_blocks, int segment_bytes, clair_host_bamsort_t **out) {
+    if (!out) return clair_host_fail("out is NULL");
+    *out = nullptr;
+    if (threads < 1 || threads > 16) return clair_host_fail("BAM threads: %d (1 .. 16)", threads);
+    if (max_blocks < 1 || max_blocks > 16384) return clair_host_fail("max_blocks %d: 1 .. 16384", max_blocks);
+    if (segment_bytes != 0 && !good_segment(segment_bytes)) return clair_host_fail("segment_bytes %d: a power of two in %u .. %u, or 0", segment_bytes, SEG_MIN, SEG_MAX);
+    clair_host_bamsort *h = new clair_host_bamsort;
+    h->threads = threads;
+    h->max_blocks = max_blocks;
+    h->seg = (uint32_t)segment_bytes;
+    *out = h;
+    return 0;
+}
+
+void clair_host_bamsort_destroy(clair_host_bamsort_t *h) { delete h; }
+
+int clair_host_bamsort_begin(clair_host_bamsort_t *h, int n_ref, const int64_t *ref_len, int64_t memory) {
+    if (!h || n_ref < 0 || (n_ref > 0 && !ref_len)) return clair_host_fail("bamsort begin: bad arguments");
+    if (memory < 1) return clair_host_fail("bamsort begin: memory %lld", (long long)memory);
+    h->ref_len.assign(ref_len, ref_len + n_ref);
+    h->first_bucket.assign((size_t)n_ref + 1, 0);
+    for (int r = 0; r < n_ref; ++r) h->first_bucket[(size_t)r + 1] = h->first_bucket[(size_t)r] + buckets_of(ref_len[r]);
+    h->hist.assign((size_t)h->first_bucket[(size_t)n_ref] + 1, 0);
+    h->memory = memory;
+    h->n_ref = n_ref;
+    h->out_carry.clear();
+    h->total = 0;
+    h->lo = h->hi = 0;
+    return 0;
+}
+
+int clair_host_bamsort_pass(clair_host_bamsort_t *h, int64_t bucket_lo, int64_t bucket_hi, int first) {
+    if (!h || h->n_ref < 0) return clair_host_fail("bamsort pass: begin first");
+    if (bucket_lo < 0 || bucket_hi < bucket_lo || bucket_hi > (int64_t)h->hist.size()) return clair_host_fail("bamsort pass: buckets [%lld, %lld) of %zu", (long long)bucket_lo, (long long)bucket_hi, h->hist.size());
+    h->lo = bucket_lo;
+    h->hi = bucket_hi;
+    h->first = first != 0;
+    h->overflow = false;
+    h->carry.clear();
+    h->carry_voff = 0;
+    h->group.clear();
+    h->keys.clear();
+    h->off.assign(1, 0);
+    if (h->first) std::fill(h->hist.begin(), h->hist.end(), 0);
+    return 0;
+}
+
+int clair_host_bamsort_batch(clair_host_bamsort_t *h, const uint8_t *cdata, int64_t cbytes, int n, const int64_t *in_at, const int32_t *csize,
+                             const int32_t *out_len, const int64_t *coffset, int64_t end_coffset, int64_t entry, int last, int64_t *state) {
+    if (!h || !state) return clair_host_fail("bamsort batch: NULL argument");
+    if (h->n_ref < 0 || h->off.empty()) return clair_host_fail("bamsort batch: begin and pass first");
+    if (n > 0 && (!cdata || !in_at || !csize || !out_len || !coffset)) return clair_host_fail("bamsort batch: NULL argument");
+    if (cbytes < 0 || end_coffset < 0 || entry < 0) return clair_host_fail("bamsort batch: negative argument");
+    if (clair_inf::check_blocks(clair_host_fail, n, h->max_blocks, cbytes, in_at, csize, out_len)) return 1;
+    int64_t len = (int64_t)h->carry.size();
+    for (int i = 0; i < n; ++i) {
+        if (coffset[i] < 0) return clair_host_fail("block %d: negative offset", i);
+        len += out_len[i];
+    }
+    if (entry > len) return clair_host_fail("bamsort batch: entry %lld beyond the %lld bytes of the batch", (long long)entry, (long long)len);
+    // 1. the stream and the table of its pieces
+    h->stream.resize((size_t)len);
+    h->at.clear();
+    h->voff.clear();
+    if (!h->carry.empty()) {
+        memcpy(h->stream.data(), h->carry.data(), h->carry.size());
+        h->at.push_back(0);
+        h->voff.push_back(h->carry_voff);
+    }
+    std::vector<int32_t> status((size_t)n, 0);
+    int64_t pos = (int64_t)h->carry.size();
+    const size_t first_block = h->at.size();
+    for (int i = 0; i < n; ++i) {
+        h->at.push_back(pos);
+        h->voff.push_back((uint64_t)coffset[i] << 16);
+        pos += out_len[i];
+    }
+    h->at.push_back(len);
+    h->voff.push_back((uint64_t)end_coffset << 16);
+    inflate_blocks(h->threads, cdata, n, in_at, csize, h->at.data() + first_block, out_len, h->stream.data(), status.data());
+    for (int i = 0; i < n; ++i)
+        if (status[(size_t)i]) return clair_host_fail("BGZF block at compressed offset %lld: %s", (long long)coffset[i], inflate_text(status[(size_t)i]));
+    // 2. the record starts
+    const Bytes m{h->stream.data()};
+    const int n_tab = (int)h->at.size();
+    h->starts.clear();
+    int64_t tail = 0;
+    bool bad = false;
+    if (h->seg) frame_segmented(m, len, entry, h->seg, h->starts, &tail, &bad);
+    else frame_walk(m, len, entry, h->starts, &tail, &bad);
+    const int64_t n_rec = (int64_t)h->starts.size();
+    const auto voffset = [&](int64_t p) { return voffset_at(h->at.data(), h->voff.data(), n_tab, p); };
+    // 3. keys, the histogram, the order, the records of this group
+    uint64_t prev = (uint64_t)state[SS_PREV_KEY];
+    int64_t kept = 0, kept_bytes = 0, mapped = 0, unplaced = 0, unsorted = 0;
+    for (int64_t k = 0; k < n_rec; ++k) {
+        const int64_t o = h->starts[(size_t)k];
+        const Fields f = fields(m, o, h->n_ref);
+        if (sort_verdict(f.verdict) != V_OK) {
+            const Detail d{state[SS_RECORDS_BEFORE] + k, f.tid, f.pos, 0, 0, f.end, voffset(o), m.le32(o), f.verdict};
+            char buf[400];
+            describe(buf, sizeof buf, d);
+            return clair_host_fail("%s", buf);
+        }
+        const uint64_t key = sort_key(f.tid, f.pos, f.flag);
+        const int64_t size = 4 + (int64_t)m.le32(o), bucket = bucket_of(f.tid, f.pos, h->n_ref, h->first_bucket.data(), h->ref_len.data());
+        if (key < prev) unsorted = 1;
+        prev = key;
+        if (f.tid < 0) ++unplaced;
+        else if (!(f.flag & 4)) ++mapped;
+        if (h->first) h->hist[(size_t)bucket] += size;
+        if (bucket < h->lo || bucket >= h->hi || h->overflow) continue;
+        if ((int64_t)h->group.size() + size > h->memory) {
+            if (!h->first) return clair_host_fail("bamsort batch: the group outgrows the %lld bytes the histogram gave it", (long long)h->memory);
+            h->overflow = true;                  // the file does not fit: what was compacted is dropped, the read goes on for the histogram
+            h->group.clear();
+            h->keys.clear();
+            h->off.assign(1, 0);
+            continue;
+        }
+        if ((int64_t)h->keys.size() >= MAX_GROUP_RECORDS) return clair_host_fail("more than 2^31 - 1 records in one group: a smaller --memory makes smaller groups");
+        h->group.insert(h->group.end(), h->stream.begin() + (ptrdiff_t)o, h->stream.begin() + (ptrdiff_t)(o + size));
+        h->keys.push_back(key);
+        h->off.push_back((int64_t)h->group.size());
+        ++kept;
+        kept_bytes += size;
+    }
+    if (bad) {
+        char buf[200];
+        describe_bad_step(buf, sizeof buf, voffset(tail), m.le32(tail));
+        return clair_host_fail("%s", buf);
+    }
+    if (last && tail < len) {
+        char buf[200];
+        describe_cut(buf, sizeof buf, voffset(tail));
+        return clair_host_fail("%s", buf);
+    }
+    h->carry_voff = tail < len ? voffset(tail) : 0;
+    std::vector<uint8_t> keep(h->stream.begin() + (ptrdiff_t)tail, h->stream.end());
+    h->carry.swap(keep);
+    state[SS_N_RECORDS] = n_rec;
+    state[SS_LAST_KEY] = (int64_t)prev;
+    state[SS_KEPT] = h->overflow ? 0 : kept;
+    state[SS_KEPT_BYTES] = h->overflow ? 0 : kept_bytes;
+    state[SS_UNSORTED] = unsorted;
+    state[SS_OVERFLOW] = h->overflow ? 1 : 0;
+    state[SS_MAPPED] = mapped;
+    state[SS_UNPLACED] = unplaced;
+    state[SS_CARRY] = (int64_t)h->carry.size();
+    return 0;
+}
+
+int clair_host_bamsort_histogram(clair_host_bamsort_t *h, int64_t *bytes, int64_t n_buckets) {
+    if (!h || !bytes || h->n_ref < 0) return clair_host_fail("bamsort histogram: bad arguments");
+    if (n_buckets != (int64_t)h->hist.size()) return clair_host_fail("bamsort histogram: %lld buckets, the handle has %zu", (long long)n_buckets, h->hist.size());
+    memcpy(bytes, h->hist.data(), h->hist.size() * 8);
+    return 0;
+}
+
+int clair_host_bamsort_sort(clair_host_bamsort_t *h, int last, int64_t *info) {
+    if (!h || !info || h->n_ref < 0 || h->off.empty()) return clair_host_fail("bamsort sort: bad arguments");
+    const size_t n = h->keys.size();
+    std::vector<uint32_t> perm(n);
+    std::iota(perm.begin(), perm.end(), 0u);
+    std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return h->keys[a] < h->keys[b]; });
+    h->sorted.assign(h->out_carry.begin(), h->out_carry.end());
+    h->sorted.reserve(h->out_carry.size() + h->group.size());
+    for (size_t i = 0; i < n; ++i) h->sorted.insert(h->sorted.end(), h->group.begin() + (ptrdiff_t)h->off[perm[i]], h->group.begin() + (ptrdiff_t)h->off[(size_t)perm[i] + 1]);
+    h->total = (int64_t)h->sorted.size();
+    const int64_t payloads = payloads_of(h->total, last != 0);
+    h->out_carry.assign(h->sorted.begin() + (ptrdiff_t)std::min(h->total, payloads * PAYLOAD), h->sorted.end());
+    h->group.clear();
+    h->keys.clear();
+    h->off.clear();                              // a new pass before the next batch
+    info[SI_BYTES] = h->total;
+    info[SI_PAYLOADS] = payloads;
+    info[SI_RECORDS] = (int64_t)n;
+    info[SI_PASSES] = 0;
+    return 0;
+}
+
+int clair_host_bamsort_emit(clair_host_bamsort_t *h, int64_t first, int n, int compressed, uint8_t *out, int32_t *sizes) {
+    if (!h || !out || !sizes || first < 0 || n < 0) return clair_host_fail("bamsort emit: bad arguments");
+    if ((first + n - 1) * PAYLOAD >= h->total && n > 0) return clair_host_fail("bamsort emit: payloads [%lld, +%d) of %lld bytes", (long long)first, n, (long long)h->total);
+    for (int i = 0; i < n; ++i) sizes[i] = (int32_t)std::min(PAYLOAD, h->total - (first + i) * PAYLOAD);
+    const uint8_t *data = h->sorted.data() + first * PAYLOAD;
+    if (!compressed) {
+        if (n) memcpy(out, data, (size_t)((int64_t)(n - 1) * PAYLOAD + sizes[n - 1]));
+        return 0;
+    }
+    const std::vector<int32_t> in_len(sizes, sizes + n);
+    return deflate_payloads(h->threads, data, n, in_len.data(), out, sizes);
+}
+
+static int twin_begin(void *ctx, int n_ref, const int64_t *ref_len, int64_t memory) { return clair_host_bamsort_begin((clair_host_bamsort_t *)ctx, n_ref, ref_len, memory); }
+static int twin_pass(void *ctx, int64_t lo, int64_t hi, int first) { return clair_host_bamsort_pass((clair_host_bamsort_t *)ctx, lo, hi, first); }
+static int twin_batch(void *ctx, const uint8_t *cdata, int64_t cbytes, int n, const int64_t *in_at, const int32_t *csize, const int32_t *out_len,
+                      const int64_t *coffset, int64_t end_coffset, int64_t entry, int last, int64_t *state) {
+    return clair_host_bamsort_batch((clair_host_bamsort_t *)ctx, cdata, cbytes, n, in_at, csize, out_len, coffset, end_coffset, entry, last, state);
+}
+static int twin_histogram(void *ctx, int64_t *bytes, int64_t n_buckets) { return clair_host_bamsort_histogram((clair_host_bamsort_t *)ctx, bytes, n_buckets); }
+static int twin_sort(void *ctx, int last, int64_t *info) { return clair_host_bamsort_sort((clair_host_bamsort_t *)ctx, last, info); }
+static int twin_emit(void *ctx, int64_t first, int n, int compressed, uint8_t *out, int32_t *sizes) { return clair_host_bamsort_emit((clair_host_bamsort_t *)ctx, first, n, compressed, out, sizes); }
+static const char *twin_last_error(const void *) { return clair_host_last_error(); }
+
+int clair_host_bamsort_backend(clair_host_bamsort_t *h, clair_bamsort_backend_t *out) {
+    if (!h || !out) return clair_host_fail("bamsort backend: NULL argument");
+    *out = clair_bamsort_backend_t{h, twin_begin, twin_pass, twin_batch, twin_histogram, twin_sort, twin_emit, twin_last_error};
+    return 0;
+}
+
+int clair_host_bamsort_debug_sort(const uint64_t *keys, int64_t n, uint32_t *perm) {
+    if (n < 0 || n > MAX_GROUP_RECORDS || (n > 0 && (!keys || !perm))) return clair_host_fail("debug_sort: bad arguments");
+    std::iota(perm, perm + n, 0u);
+    std::stable_sort(perm, perm + n, [&](uint32_t a, uint32_t b) { return keys[a] < keys[b]; });
+    return 0;
+}
+
+int clair_host_bamsort_debug_gather(const uint8_t *stream, int64_t stream_bytes, const int64_t *starts, const uint32_t *perm, int64_t n, uint8_t *out, int64_t out_bytes) {
+    if (n < 0 || stream_bytes < 0 || out_bytes < 0 || (n > 0 && (!stream || !starts || !perm || !out))) return clair_host_fail("debug_gather: bad arguments");
+    int64_t at = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        if ((int64_t)perm[i] >= n) return clair_host_fail("debug_gather: perm[%lld] = %u of %lld", (long long)i, perm[i], (long long)n);
+        const int64_t o = starts[perm[i]];
+        int64_t next = 0;
+        if (o < 0 || step(Bytes{stream}, o, stream_bytes, &next) != STEP_NEXT) return clair_host_fail("debug_gather: no record at %lld", (long long)o);
+        if (at + (next - o) > out_bytes) return clair_host_fail("debug_gather: the records need more than %lld bytes", (long long)out_bytes);
+        memcpy(out + at, stream + o, (size_t)(next - o));
+        at += next - o;
+    }
+    if (at != out_bytes) return clair_host_fail("debug_gather: %lld bytes gathered, %lld expected", (long long)at, (long long)out_bytes);
+    return 0;
+}
+
+// ---- the file driver
+int clair_host_bamsort_open(const char *path, clair_host_bamsort_job_t **out) {
+    if (!out) return clair_host_fail("out is NULL");
+    *out = nullptr;
+    if (!path) return clair_host_fail("bamsort open: NULL argument");
+    clair_host_bamsort_job *job = new clair_host_bamsort_job;
+    struct Guard { clair_host_bamsort_job *j; ~Guard() { delete j; } } guard{job};
+    job->path = path;
+    job->file = fopen(path, "rb");
+    if (!job->file) return clair_host_fail("%s: cannot open", path);
+    if (fseeko(job->file, 0, SEEK_END) != 0) return clair_host_fail("%s: cannot seek", path);
+    job->file_size = (int64_t)ftello(job->file);
+    uint8_t magic[4] = {0, 0, 0, 0};
+    if (job->file_size < BGZF_HEADER || fseeko(job->file, 0, SEEK_SET) != 0 || fread(magic, 1, 4, job->file) != 4 || !gzip_with_extra(magic))
+        return clair_host_fail("%s is not a BGZF-compressed BAM (SAM text and CRAM are out of scope)", path);
+    std::vector<uint8_t> cbuf;
+    std::vector<std::pair<int64_t, int64_t>> pieces;          // (position in text, coffset)
+    int64_t coffset = 0;
+    const auto need = [&](size_t bytes) -> int {
+        while (job->text.size() < bytes) {
+            if (coffset >= job->file_size) return clair_host_fail("%s: the BAM header is truncated", path);
+            cbuf.clear();
+            uint32_t csize = 0, isize = 0;
+            if (read_block(job->file, path, (uint64_t)job->file_size, (uint64_t)coffset, cbuf, &csize, &isize)) return 1;
+            const size_t at = job->text.size();
+            job->text.resize(at + isize);
+            const int status = inflate_block(cbuf.data(), csize, job->text.data() + at, isize);
+            if (status) return clair_host_fail("%s: BGZF block at compressed offset %lld: %s", path, (long long)coffset, inflate_text(status));
+            pieces.emplace_back((int64_t)at, coffset);
+            coffset += csize;
+        }
+        return 0;
+    };
+    if (parse_bam_header(path, "", need, [&] { return (const uint8_t *)job->text.data(); }, &job->header)) return 1;
+    const size_t at = job->header.end;
+    job->coffset = coffset;
+    job->entry = 0;
+    if (at < job->text.size()) {                             // the first record: in the last header block, or at the start of the block after it
+        size_t k = pieces.size() - 1;
+        while (pieces[k].first > (int64_t)at) --k;
+        job->coffset = pieces[k].second;
+        job->entry = (int64_t)at - pieces[k].first;
+    }
+    guard.j = nullptr;
+    *out = job;
+    return 0;
+}
+
+void clair_host_bamsort_close(clair_host_bamsort_job_t *job) { delete job; }
+
+int clair_host_bamsort_header(const clair_host_bamsort_job_t *job, uint8_t *out, int64_t cap, int64_t *bytes) {
+    if (!job || !bytes) return clair_host_fail("bamsort header: NULL argument");
+    *bytes = (int64_t)job->header.end;
+    if (out && cap >= *bytes) memcpy(out, job->text.data(), job->header.end);
+    return 0;
+}
+
+// deflate: 0 the backend's own compressor, 1 zlib, 2 the host twin of the device compressor on `threads` threads.
+// stats [CLAIR_BAMSORT_STATS] = records, mapped, unplaced, groups, input reads, already sorted, bytes appended to out_path
+int clair_host_bamsort_run(clair_host_bamsort_job_t *job, const clair_bamsort_backend_t *be, const char *out_path, int deflate, int64_t memory, int max_blocks,
+                           int threads, int64_t *stats) {
+    if (!job || !be || !out_path || !stats || !be->begin || !be->pass || !be->batch || !be->histogram || !be->sort || !be->emit || !be->last_error)
+        return clair_host_fail("bamsort run: NULL argument");
+    if (max_blocks < 1 || max_blocks > 16384) return clair_host_fail("max_blocks %d: 1 .. 16384", max_blocks);
+    if (deflate < 0 || deflate > 2 || threads < 1 || threads > 16 || memory < 1) return clair_host_fail("bamsort run: bad arguments");
+    const char *path = job->path.c_str();
+    const auto failed = [&] { return clair_host_fail("%s: %s", path, be->last_error(be->ctx)); };
+    const int n_ref = (int)job->header.lengths.size();
+    const std::vector<int64_t> &ref_len = job->header.lengths;
+    std::vector<int64_t> first_bucket((size_t)n_ref + 1, 0);
+    for (int r = 0; r < n_ref; ++r) first_bucket[(size_t)r + 1] = first_bucket[(size_t)r] + buckets_of(ref_len[(size_t)r]);
+    const int64_t n_buckets = first_bucket[(size_t)n_ref] + 1;
+    if (be->begin(be->ctx, n_ref, ref_len.data(), memory)) return failed();
+
+    std::vector<uint8_t> cbuf;
+    std::vector<int64_t> in_at, offs;
+    std::vector<int32_t> csizes, out_lens;
+    int64_t records = 0, mapped = 0, unplaced = 0;
+    bool sorted = true, overflow = false;
+    // one read of the input, every batch through the backend
+    const auto read_all = [&](bool first) -> int {
+        int64_t coffset = job->coffset, entry = job->entry;
+        int64_t state[SS_WORDS] = {0};
+        bool last = false;
+        while (!last) {
+            cbuf.clear(); in_at.clear(); offs.clear(); csizes.clear(); out_lens.clear();
+            while ((int)offs.size() < max_blocks && coffset < job->file_size) {
+                const size_t here = cbuf.size();
+                uint32_t csize = 0, isize = 0;
+                if (read_block(job->file, path, (uint64_t)job->file_size, (uint64_t)coffset, cbuf, &csize, &isize)) return 1;
+                in_at.push_back((int64_t)here);
+                offs.push_back(coffset);
+                csizes.push_back((int32_t)csize);
+                out_lens.push_back((int32_t)isize);
+                coffset += csize;
+            }
+            last = coffset >= job->file_size;
+            if (be->batch(be->ctx, cbuf.data(), (int64_t)cbuf.size(), (int)offs.size(), in_at.data(), csizes.data(), out_lens.data(), offs.data(), coffset, entry,
+                          last ? 1 : 0, state))
+                return failed();
+            if (first) {
+                records += state[SS_N_RECORDS];
+                mapped += state[SS_MAPPED];
+                unplaced += state[SS_UNPLACED];
+                sorted = sorted && !state[SS_UNSORTED];
+                overflow = overflow || state[SS_OVERFLOW];
+            } else if (state[SS_OVERFLOW]) {
+                return clair_host_fail("%s: a group outgrew --memory on its second read: the file changed", path);
+            }
+            state[SS_RECORDS_BEFORE] += state[SS_N_RECORDS];
+            state[SS_PREV_KEY] = state[SS_LAST_KEY];
+            entry = 0;
+        }
+        return 0;
+    };
+
+    FILE *out = fopen(out_path, "ab");
+    if (!out) return clair_host_fail("%s: cannot write", out_path);
+    struct Closer { FILE *f; ~Closer() { if (f) fclose(f); } } closer{out};
+    int64_t written = 0;
+    constexpr int EMIT = 64;                                  // payloads per emit
+    std::vector<uint8_t> slots((size_t)EMIT * SLOT), raw((size_t)EMIT * PAYLOAD);
+    std::vector<int32_t> sizes((size_t)EMIT);
+    // the sorted group goes out: whole payloads, and with `final` the partial one behind them
+    const auto write_group = [&](bool final) -> int {
+        int64_t info[SI_WORDS] = {0};
+        if (be->sort(be->ctx, final ? 1 : 0, info)) return failed();
+        for (int64_t at = 0; at < info[SI_PAYLOADS]; at += EMIT) {
+            const int n = (int)std::min<int64_t>(EMIT, info[SI_PAYLOADS] - at);
+            if (deflate == 0) {
+                if (be->emit(be->ctx, at, n, 1, slots.data(), sizes.data())) return failed();
+            } else {
+                if (be->emit(be->ctx, at, n, 0, raw.data(), sizes.data())) return failed();
+                if (deflate == 2) {
+                    const std::vector<int32_t> in_len(sizes.begin(), sizes.begin() + n);
+                    if (deflate_payloads(threads, raw.data(), n, in_len.data(), slots.data(), sizes.data())) return 1;
+                } else {
+                    for (int i = 0; i < n; ++i)
+                        if (zlib_payload(raw.data() + (int64_t)i * PAYLOAD, sizes[(size_t)i], slots.data() + (int64_t)i * SLOT, &sizes[(size_t)i])) return 1;
+                }
+            }
+            for (int i = 0; i < n; ++i) {
+                const int32_t cs = sizes[(size_t)i];
+                if (cs < BGZF_HEADER + BGZF_FOOTER || cs > SLOT) return clair_host_fail("%s: a compressed block of %d bytes", path, cs);
+                if (fwrite(slots.data() + (int64_t)i * SLOT, 1, (size_t)cs, out) != (size_t)cs) return clair_host_fail("%s: write failed", out_path);
+                written += cs;
+            }
+        }
+        return 0;
+    };
+
+    int64_t groups = 1, reads = 1;
+    if (be->pass(be->ctx, 0, n_buckets, 1)) return failed();
+    if (read_all(true)) return 1;
+    if (!overflow) {
+        if (write_group(true)) return 1;
+    } else {
+        std::vector<int64_t> hist((size_t)n_buckets, 0);
+        if (be->histogram(be->ctx, hist.data(), n_buckets)) return failed();
+        std::vector<std::pair<int64_t, int64_t>> ranges;      // consecutive buckets, greedily, up to `memory` bytes
+        for (int64_t b = 0; b < n_buckets;) {
+            if (hist[(size_t)b] > memory) {
+                int r = 0;
+                while (r < n_ref && first_bucket[(size_t)r + 1] <= b) ++r;
+                if (r >= n_ref)
+                    return clair_host_fail("%s: the reads without a reference hold %lld bytes, more than --memory %lld: a sort cannot split them", path,
+                                           (long long)hist[(size_t)b], (long long)memory);
+                const int64_t from = (b - first_bucket[(size_t)r]) << BUCKET_SHIFT;
+                const bool last_of_ref = b + 1 == first_bucket[(size_t)r + 1];
+                const int64_t to = last_of_ref ? std::max(ref_len[(size_t)r], from + 1) : from + ((int64_t)1 << BUCKET_SHIFT);
+                return clair_host_fail("%s: the reads of %s:%lld-%lld hold %lld bytes, more than --memory %lld: a sort cannot split them", path,
+                                       job->header.names[(size_t)r].c_str(), (long long)from + 1, (long long)to, (long long)hist[(size_t)b], (long long)memory);
+            }
+            int64_t e = b, sum = 0;
+            while (e < n_buckets && sum + hist[(size_t)e] <= memory) sum += hist[(size_t)e++];
+            ranges.emplace_back(b, e);
+            b = e;
+        }
+        groups = (int64_t)ranges.size();
+        for (size_t g = 0; g < ranges.size(); ++g) {
+            if (be->pass(be->ctx, ranges[g].first, ranges[g].second, 0)) return failed();
+            if (read_all(false)) return 1;
+            ++reads;
+            if (write_group(g + 1 == ranges.size())) return 1;
+        }
+    }
+    if (fwrite(BGZF_EOF, 1, sizeof BGZF_EOF, out) != sizeof BGZF_EOF) return clair_host_fail("%s: write failed", out_path);
+    written += (int64_t)sizeof BGZF_EOF;
+    closer.f = nullptr;
+    if (fclose(out) != 0) return clair_host_fail("%s: write failed", out_path);
+    stats[0] = records;
+    stats[1] = mapped;
+    stats[2] = unplaced;
+    stats[3] = groups;
+    stats[4] = reads;
+    stats[5] = sorted ? 1 : 0;
+    stats[6] = written;
+    return 0;
+}
+
+}  // extern "C"

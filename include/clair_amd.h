@@ -704,6 +704,64 @@ int clair_bamidx_finish(clair_bamidx_t *h, uint64_t *linear, int64_t n_windows, 
 int clair_bamidx_backend(clair_bamidx_t *h, clair_bamidx_backend_t *out);
 int clair_bamidx_debug_frame(clair_bamidx_t *h, const uint8_t *stream, int64_t n, int64_t entry, int64_t *starts, int64_t cap, int64_t *result);
 
+/* ---- sort_bam: a BAM sorted by coordinate on the device (csrc/bam_sort.hip; docs/sort_bam.md) ----
+ * One handle: one stream, the device buffers of a batch (those of index_bam's batch front), the group buffer, the sorted buffer and the
+ * byte histogram.  The key of a record is (uint32)tid << 32 | (uint32)(pos + 1) << 1 | reverse strand; equal keys keep their input order.
+ * _begin: a new file with n_ref references of ref_len bases; memory: the most record bytes a group may hold.  The histogram has one bucket
+ *   per 2^20 positions of every reference (at least one each) and a last one for the records without a reference.
+ * _pass: a new read of the input: records whose bucket lies in [bucket_lo, bucket_hi) are kept.  first != 0: the histogram is counted and a
+ *   group that outgrows `memory` is dropped and reported (state[7]) instead of refused.
+ * _batch: n <= max_blocks whole BGZF blocks, as clair_bamidx_batch takes them.  Inflated, framed, every record's key, length and bucket
+ *   computed on the device, the kept ones compacted behind the group's records.  Back comes only state (CLAIR_BAMSORT_STATE).
+ * _histogram: bytes of records per bucket, as the first read counted them.
+ * _sort: the group sorted (stable LSD radix sort, 8 bits a pass, passes whose digit is the same in every key skipped) and gathered behind
+ *   the bytes the group before left over; info (CLAIR_BAMSORT_INFO).  last == 0: the bytes behind the last whole payload of 65280 are kept
+ *   for the next group; last != 0: they are a payload of their own.
+ * _emit: payloads [first, first + n) of the sorted buffer, n <= 64.  compressed != 0: deflate_bgzf_kernel over the device-resident bytes,
+ *   block i in out[i * 65536 .. + sizes[i]); compressed == 0: the bytes themselves, packed, sizes[i] bytes each.
+ * _backend: the calls above with the handle, as clair_host_bamsort_run takes them.
+ * _debug_sort: the radix sort alone: perm [n] = the stable order of keys [n].  _debug_gather: the gather alone: the records at starts [n] of
+ *   `stream` in the order perm into out[0 .. out_bytes), which must be their total length; a guard region in front of and behind the device's
+ *   output is checked after the kernel.
+ * Non-zero on failure, message from clair_bamsort_last_error (NULL handle: the failure of create).  clair_host_bamsort_* (include/clair_host.h)
+ * gives the same bytes on the CPU. */
+typedef struct clair_bamsort clair_bamsort_t;
+#ifndef CLAIR_BAMSORT_TYPES
+#define CLAIR_BAMSORT_TYPES
+/* the interface of a sort, as the file driver (clair_host_bamsort_run) calls it: the entry points of one backend with its handle */
+typedef struct clair_bamsort_backend {
+    void *ctx;
+    int (*begin)(void *ctx, int n_ref, const int64_t *ref_len, int64_t memory);
+    int (*pass)(void *ctx, int64_t bucket_lo, int64_t bucket_hi, int first);
+    int (*batch)(void *ctx, const uint8_t *cdata, int64_t cbytes, int n, const int64_t *in_at, const int32_t *csize, const int32_t *out_len,
+                 const int64_t *coffset, int64_t end_coffset, int64_t entry, int last, int64_t *state);
+    int (*histogram)(void *ctx, int64_t *bytes, int64_t n_buckets);
+    int (*sort)(void *ctx, int last, int64_t *info);
+    int (*emit)(void *ctx, int64_t first, int n, int compressed, uint8_t *out, int32_t *sizes);
+    const char *(*last_error)(const void *ctx);
+} clair_bamsort_backend_t;
+#define CLAIR_BAMSORT_STATE 11 /* int64 words of `state`: in 0 records before the batch, 1 the key of the record before it (0: none); out 2 records,
+                                * 3 the last record's key (1 when there is none), 4 5 records and bytes kept for the group, 6 a record came before
+                                * its predecessor, 7 the group outgrew `memory` and was dropped (first read only), 8 9 mapped and unplaced records,
+                                * 10 bytes carried over */
+#define CLAIR_BAMSORT_INFO 4   /* int64 words of _sort's `info`: bytes in the sorted buffer, payloads ready for _emit, records sorted, radix passes run */
+#define CLAIR_BAMSORT_STATS 7  /* of clair_host_bamsort_run: records, mapped, unplaced, groups, reads of the input, already sorted, bytes appended */
+#endif
+int clair_bamsort_create(int device, int max_blocks, int segment_bytes, clair_bamsort_t **out);
+void clair_bamsort_destroy(clair_bamsort_t *h);
+const char *clair_bamsort_last_error(const clair_bamsort_t *h);
+int clair_bamsort_begin(clair_bamsort_t *h, int n_ref, const int64_t *ref_len, int64_t memory);
+int clair_bamsort_pass(clair_bamsort_t *h, int64_t bucket_lo, int64_t bucket_hi, int first);
+int clair_bamsort_batch(clair_bamsort_t *h, const uint8_t *cdata, int64_t cbytes, int n, const int64_t *in_at, const int32_t *csize, const int32_t *out_len,
+                        const int64_t *coffset, int64_t end_coffset, int64_t entry, int last, int64_t *state);
+int clair_bamsort_histogram(clair_bamsort_t *h, int64_t *bytes, int64_t n_buckets);
+int clair_bamsort_sort(clair_bamsort_t *h, int last, int64_t *info);
+int clair_bamsort_emit(clair_bamsort_t *h, int64_t first, int n, int compressed, uint8_t *out, int32_t *sizes);
+int clair_bamsort_backend(clair_bamsort_t *h, clair_bamsort_backend_t *out);
+int clair_bamsort_debug_sort(clair_bamsort_t *h, const uint64_t *keys, int64_t n, uint32_t *perm);
+int clair_bamsort_debug_gather(clair_bamsort_t *h, const uint8_t *stream, int64_t stream_bytes, const int64_t *starts, const uint32_t *perm, int64_t n,
+                               uint8_t *out, int64_t out_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -387,6 +387,58 @@ int clair_host_bamidx_result_info(const clair_host_bamidx_result_t *r, int64_t *
 int clair_host_bamidx_result_copy(const clair_host_bamidx_result_t *r, clair_bamidx_run_t *runs, uint64_t *linear, int64_t *first_window);
 void clair_host_bamidx_result_free(clair_host_bamidx_result_t *r);
 
+/* -- sort_bam on the CPU (hostsrc/host_bam_sort.cpp; docs/sort_bam.md): the host twin of clair_bamsort_* (include/clair_amd.h) with the rules
+ *    of csrc/bam_sort_core.h, and the file driver both backends run under.
+ *    _create .. _backend, _debug_sort, _debug_gather: the twin, the same calls with the same arguments and results; blocks are inflated by
+ *      zlib on `threads` threads, the group is ordered by std::stable_sort, `compressed` payloads are compressed by clair_host_deflate_bgzf.
+ *    _open: the BAM header of `path` read and checked -> a job; _header: its bytes as they are in the file (magic, text, reference list;
+ *      *bytes is their length, copied when cap has room); _close.
+ *    _run: the records of the job's file sorted through a backend and appended to out_path (which holds the header's blocks already), the
+ *      EOF marker behind them.  deflate: 0 the backend's own compressor, 1 zlib level 6, 2 clair_host_deflate_bgzf here.  memory: the most
+ *      record bytes held at once.  stats [CLAIR_BAMSORT_STATS].
+ *    Messages go to clair_host_last_error. */
+typedef struct clair_host_bamsort clair_host_bamsort_t;
+typedef struct clair_host_bamsort_job clair_host_bamsort_job_t;
+#ifndef CLAIR_BAMSORT_TYPES
+#define CLAIR_BAMSORT_TYPES
+/* the interface of a sort, as the file driver (clair_host_bamsort_run) calls it: the entry points of one backend with its handle */
+typedef struct clair_bamsort_backend {
+    void *ctx;
+    int (*begin)(void *ctx, int n_ref, const int64_t *ref_len, int64_t memory);
+    int (*pass)(void *ctx, int64_t bucket_lo, int64_t bucket_hi, int first);
+    int (*batch)(void *ctx, const uint8_t *cdata, int64_t cbytes, int n, const int64_t *in_at, const int32_t *csize, const int32_t *out_len,
+                 const int64_t *coffset, int64_t end_coffset, int64_t entry, int last, int64_t *state);
+    int (*histogram)(void *ctx, int64_t *bytes, int64_t n_buckets);
+    int (*sort)(void *ctx, int last, int64_t *info);
+    int (*emit)(void *ctx, int64_t first, int n, int compressed, uint8_t *out, int32_t *sizes);
+    const char *(*last_error)(const void *ctx);
+} clair_bamsort_backend_t;
+#define CLAIR_BAMSORT_STATE 11 /* int64 words of `state`: in 0 records before the batch, 1 the key of the record before it (0: none); out 2 records,
+                                * 3 the last record's key (1 when there is none), 4 5 records and bytes kept for the group, 6 a record came before
+                                * its predecessor, 7 the group outgrew `memory` and was dropped (first read only), 8 9 mapped and unplaced records,
+                                * 10 bytes carried over */
+#define CLAIR_BAMSORT_INFO 4   /* int64 words of _sort's `info`: bytes in the sorted buffer, payloads ready for _emit, records sorted, radix passes run */
+#define CLAIR_BAMSORT_STATS 7  /* of clair_host_bamsort_run: records, mapped, unplaced, groups, reads of the input, already sorted, bytes appended */
+#endif
+int clair_host_bamsort_create(int threads, int max_blocks, int segment_bytes, clair_host_bamsort_t **out);
+void clair_host_bamsort_destroy(clair_host_bamsort_t *h);
+int clair_host_bamsort_begin(clair_host_bamsort_t *h, int n_ref, const int64_t *ref_len, int64_t memory);
+int clair_host_bamsort_pass(clair_host_bamsort_t *h, int64_t bucket_lo, int64_t bucket_hi, int first);
+int clair_host_bamsort_batch(clair_host_bamsort_t *h, const uint8_t *cdata, int64_t cbytes, int n, const int64_t *in_at, const int32_t *csize,
+                             const int32_t *out_len, const int64_t *coffset, int64_t end_coffset, int64_t entry, int last, int64_t *state);
+int clair_host_bamsort_histogram(clair_host_bamsort_t *h, int64_t *bytes, int64_t n_buckets);
+int clair_host_bamsort_sort(clair_host_bamsort_t *h, int last, int64_t *info);
+int clair_host_bamsort_emit(clair_host_bamsort_t *h, int64_t first, int n, int compressed, uint8_t *out, int32_t *sizes);
+int clair_host_bamsort_backend(clair_host_bamsort_t *h, clair_bamsort_backend_t *out);
+int clair_host_bamsort_debug_sort(const uint64_t *keys, int64_t n, uint32_t *perm);
+int clair_host_bamsort_debug_gather(const uint8_t *stream, int64_t stream_bytes, const int64_t *starts, const uint32_t *perm, int64_t n, uint8_t *out,
+                                    int64_t out_bytes);
+int clair_host_bamsort_open(const char *path, clair_host_bamsort_job_t **out);
+void clair_host_bamsort_close(clair_host_bamsort_job_t *job);
+int clair_host_bamsort_header(const clair_host_bamsort_job_t *job, uint8_t *out, int64_t cap, int64_t *bytes);
+int clair_host_bamsort_run(clair_host_bamsort_job_t *job, const clair_bamsort_backend_t *backend, const char *out_path, int deflate, int64_t memory,
+                           int max_blocks, int threads, int64_t *stats);
+
 /* -- gVCF on the CPU (hostsrc/host_gvcf.cpp; docs/gvcf.md): the host twin of clair_frontend_position_tallies / _gvcf_blocks
  *    (include/clair_amd.h) with the rule of csrc/gvcf_core.h, and the block rows' text.
  *    _tally: adds one slab of the host packer (clair_host_sampack_slab) to tallies [n][7] = A C G T I D N of the 0-based positions

@@ -1,0 +1,372 @@
+"""sort_bam on the CPU (docs/sort_bam.md): the host backend (hostsrc/host_bam_sort.cpp over csrc/bam_sort_core.h) against the order
+np.lexsort gives the fixture's records, the file's bytes under every batch size, segment, block layout and --memory, the header rule, the
+error verdicts, the command line, the radix rule restated in NumPy, and the host side once more as a stand-alone program under the address
+and undefined-behaviour sanitizers."""
+import os
+import re
+import shutil
+import struct
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+sys.path.insert(0, HERE)
+import index_bam_cases as ic  # noqa: E402
+import sort_bam_cases as sc  # noqa: E402
+
+from clair_amd import _capi, _hostapi, index_bam, sort_bam  # noqa: E402
+from clair_amd._hostapi import BamError, BamReader  # noqa: E402
+
+ENV = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+
+
+@pytest.fixture(scope="module")
+def case(tmp_path_factory):
+    """the shuffled BAM written three ways, the sorted file of the plain call, and what it must inflate to"""
+    tmp = tmp_path_factory.mktemp("sort_bam")
+    b = sc.bam()
+    paths = {}
+    for way, kw in sc.WAYS.items():
+        paths[way] = str(tmp / (way + ".bam"))
+        b.write(paths[way], index=False, **kw)
+    out = str(tmp / "sorted.bam")
+    result = sort_bam.sort_bam(paths["straddle"], out, backend="host")
+    return dict(bam=b, paths=paths, sorted=out, result=result, want=sc.expected_stream(b), tmp=tmp)
+
+
+def _records_of(path, ctg):
+    """the records of one contig the native reader hands out when it scans the file (no index)"""
+    r = BamReader(path, threads=2)
+    tid = [n for n, _ in r.references()].index(ctg)
+    assert not r.query(ctg, use_index=False)
+    buf, offsets, out = np.empty(1 << 20, dtype=np.uint8), np.empty(64, dtype=np.int64), []
+    while True:
+        n_bytes, n_rec = r.readinto(buf, offsets)
+        if n_rec == 0:
+            break
+        recs = [bytes(buf[offsets[k]:offsets[k + 1] if k + 1 < n_rec else n_bytes]) for k in range(n_rec)]
+        out += [rec for rec in recs if struct.unpack_from("<i", rec, 4)[0] == tid]
+    r.close()
+    return out
+
+
+# -- order and content ------------------------------------------------------------------------------------------------------------------------
+def test_the_fixture_has_what_the_issue_lists(case):
+    records = case["bam"].records
+    assert 250 <= len(records) <= 350 and len({r.tid for r in records}) == 4
+    assert any(r.pos == 0 for r in records) and max(len(r.encode()) for r in records) > 70000
+    assert sum(r.tid < 0 for r in records) >= 20 and sum(r.tid >= 0 and r.flag & 4 for r in records) >= 10
+    keys = sc.keys_of(records)
+    assert max(np.unique(keys, return_counts=True)[1]) >= 20                          # the runs that show stability
+    assert np.any(np.diff(keys.astype(np.int64)) < 0)                                 # and the input is not in order
+    assert len(case["want"]) - len(case["bam"].header()) > 2 * sc.PAYLOAD
+
+
+def test_the_output_is_the_records_in_the_yardsticks_order(case):
+    got, eof = sc.read_bgzf(case["sorted"])
+    assert eof and b"".join(got) == case["want"]
+    records = case["bam"].records
+    r = case["result"]
+    assert (r["records"], r["unplaced"], r["groups"], r["input_reads"], r["already_sorted"], r["backend"]) == \
+        (len(records), sum(x.tid < 0 for x in records), 1, 1, False, "host")
+    assert r["mapped"] == sum(x.tid >= 0 and not x.flag & 4 for x in records)
+    assert r["bytes_in"] == os.path.getsize(case["paths"]["straddle"]) and r["bytes_out"] == os.path.getsize(case["sorted"])
+    # the header in blocks of its own, the records cut every 65280 bytes behind it
+    header = len(case["bam"].header())
+    sizes = [len(p) for p in got]
+    assert sizes[0] == header and all(s == sc.PAYLOAD for s in sizes[1:-2]) and 0 < sizes[-2] <= sc.PAYLOAD and sizes[-1] == 0
+    assert not [f for f in os.listdir(str(case["tmp"])) if ".tmp." in f]
+
+
+def test_the_keys_of_the_module_are_the_yardsticks(case):
+    records = case["bam"].records
+    keys = sort_bam.sort_keys([r.tid for r in records], [r.pos for r in records], [r.flag for r in records])
+    assert np.array_equal(keys, sc.keys_of(records))
+    assert np.array_equal(np.argsort(keys, kind="stable"), sc.order(records))
+
+
+def test_index_bam_takes_the_output_and_refused_the_input(case, tmp_path):
+    with pytest.raises(BamError, match="not sorted by coordinate"):
+        index_bam.build_index(case["paths"]["whole"], str(tmp_path / "in.bai"), backend="host")
+    r = index_bam.build_index(case["sorted"], str(tmp_path / "out.bai"), backend="host")
+    assert r["records"] == len(case["bam"].records)
+
+
+def test_the_reader_reads_the_inputs_records_from_the_output(case):
+    """The native reader ends a scan at the first record past the queried contig, as it may on the sorted files it is made for, so it cannot
+    list an unsorted input; the input's side of the comparison is what the fixture wrote into it."""
+    seen = 0
+    for tid, (ctg, _) in enumerate(sc.REFS):
+        after = _records_of(case["sorted"], ctg)
+        assert after == [r.encode() for r in sc.sorted_records(case["bam"]) if r.tid == tid], ctg
+        assert sorted(after) == sorted(r.encode() for r in case["bam"].records if r.tid == tid), ctg
+        seen += len(after)
+    assert seen == sum(r.tid >= 0 for r in case["bam"].records)
+    assert len(_records_of(case["paths"]["per_record"], "chr1")) < sum(r.tid == 0 for r in case["bam"].records)
+
+
+# -- invariance -----------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("max_blocks", [1, 2, 64])
+@pytest.mark.parametrize("segment", [64, 4096, 8192])
+def test_batches_and_segments_do_not_change_the_file(case, max_blocks, segment, tmp_path):
+    out = str(tmp_path / "out.bam")
+    sort_bam.sort_bam(case["paths"]["straddle"], out, backend="host", max_blocks=max_blocks, segment_bytes=segment)
+    assert open(out, "rb").read() == open(case["sorted"], "rb").read()
+
+
+@pytest.mark.parametrize("way", list(sc.WAYS))
+def test_the_inputs_blocks_do_not_change_the_file(case, way, tmp_path):
+    out = str(tmp_path / "out.bam")
+    sort_bam.sort_bam(case["paths"][way], out, backend="host", max_blocks=3)
+    assert open(out, "rb").read() == open(case["sorted"], "rb").read()
+
+
+def test_memory_does_not_change_the_file(case, tmp_path):
+    hist = sc.bucket_bytes(case["bam"])
+    total, largest = sum(hist), max(hist)
+    seen = set()
+    for memory in (total, total - 1, largest + 20000, largest + 1000, largest):
+        groups, reads = sc.expected_groups(case["bam"], memory)
+        out = str(tmp_path / ("out%d.bam" % memory))
+        r = sort_bam.sort_bam(case["paths"]["straddle"], out, backend="host", memory=memory, max_blocks=2)
+        assert (r["groups"], r["input_reads"]) == (groups, reads), memory
+        assert open(out, "rb").read() == open(case["sorted"], "rb").read(), memory
+        seen.add(groups)
+    assert 1 in seen and max(seen) >= 3 and len(seen) >= 3
+    assert sc.expected_groups(case["bam"], total) == (1, 1) and sc.expected_groups(case["bam"], total - 1)[0] >= 2
+
+
+def test_one_group_per_bucket(tmp_path):
+    b = sc.bucket_bam()
+    hist = sc.bucket_bytes(b)
+    assert len(hist) == 10 and min(hist) > max(hist) // 2                             # no two buckets fit a group of the largest bucket's bytes
+    b.write(str(tmp_path / "in.bam"), index=False, block=700)
+    one = sort_bam.sort_bam(str(tmp_path / "in.bam"), str(tmp_path / "one.bam"), backend="host")
+    each = sort_bam.sort_bam(str(tmp_path / "in.bam"), str(tmp_path / "each.bam"), backend="host", memory=max(hist))
+    assert (one["groups"], one["input_reads"], each["groups"], each["input_reads"]) == (1, 1, 10, 11) == (1, 1) + sc.expected_groups(b, max(hist))
+    assert open(str(tmp_path / "each.bam"), "rb").read() == open(str(tmp_path / "one.bam"), "rb").read()
+    assert sc.inflated(str(tmp_path / "each.bam")) == sc.expected_stream(b)
+
+
+def test_memory_takes_suffixes():
+    assert [sort_bam.parse_memory(v) for v in (None, 5, "7", "3K", "2m", "1G")] == [8 << 30, 5, 7, 3072, 2 << 20, 1 << 30]
+    for bad in ("", "G", "-1", "0", "12Q"):
+        with pytest.raises(BamError, match="--memory"):
+            sort_bam.parse_memory(bad)
+
+
+# -- sorted and empty input ----------------------------------------------------------------------------------------------------------------
+def test_sorted_input_and_an_empty_file(case, tmp_path):
+    again = str(tmp_path / "again.bam")
+    r = sort_bam.sort_bam(case["sorted"], again, backend="host")
+    assert r["already_sorted"] and sc.inflated(again) == case["want"]
+    assert open(again, "rb").read() == open(case["sorted"], "rb").read()
+    from bam_fixture import Bam
+    empty = Bam("", sc.REFS)
+    empty.write(str(tmp_path / "empty.bam"), index=False)
+    r = sort_bam.sort_bam(str(tmp_path / "empty.bam"), str(tmp_path / "empty_sorted.bam"), backend="host")
+    got, eof = sc.read_bgzf(str(tmp_path / "empty_sorted.bam"))
+    assert eof and got == [empty.header(), b""] and r["records"] == 0 and r["already_sorted"] and r["groups"] == 1
+
+
+# -- the header -------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(sc.HEADER_CASES))
+def test_header_rewriting(name, tmp_path):
+    text, want = sc.HEADER_CASES[name]
+    b = sc.HeaderBam(text, sc.sam_text(seed=9)[:4000].rsplit("\n", 1)[0] + "\n", sc.REFS)
+    b.write(str(tmp_path / "in.bam"), index=False, block=500)
+    sort_bam.sort_bam(str(tmp_path / "in.bam"), str(tmp_path / "out.bam"), backend="host")
+    got = sc.inflated(str(tmp_path / "out.bam"))
+    header = b.header()
+    want_header = header[:4] + struct.pack("<I", len(want)) + want + header[8 + len(text):]
+    assert got[:len(want_header)] == want_header
+    assert got == sc.expected_stream(b, want_header)
+    assert sort_bam.coordinate_header(want_header) == want_header                      # and a second sort leaves it alone
+
+
+# -- errors -------------------------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def bad_files(tmp_path_factory):
+    return ic.malformed(tmp_path_factory.mktemp("sort_bam_bad"))
+
+
+NOT_A_SORTS = ("swapped_records", "swapped_contigs", "mapped_after_unplaced", "beyond_2_29")     # the order and the .bai's extent: index_bam's
+
+
+@pytest.mark.parametrize("segment", [None, 64])
+def test_error_verdicts(bad_files, segment, tmp_path):
+    for name, (path, pattern) in bad_files.items():
+        out = str(tmp_path / "out.bam")
+        if name in NOT_A_SORTS:                            # these sort fine; the position beyond 2^29 is still only the index's to refuse
+            r = sort_bam.sort_bam(path, out, backend="host", segment_bytes=segment, max_blocks=2)
+            assert r["already_sorted"] == (name == "beyond_2_29"), name
+            if name == "beyond_2_29":
+                with pytest.raises(BamError, match=r"beyond 2\^29"):
+                    index_bam.build_index(out, backend="host")
+            else:
+                index_bam.build_index(out, backend="host")
+            for f in os.listdir(str(tmp_path)):
+                os.remove(str(tmp_path / f))
+            continue
+        with pytest.raises(BamError) as e:
+            sort_bam.sort_bam(path, out, backend="host", segment_bytes=segment, max_blocks=2)
+            pytest.fail("%s was sorted" % name)
+        assert re.search(pattern, str(e.value)), (name, str(e.value))
+        assert os.path.basename(path) in str(e.value), name
+        assert not os.listdir(str(tmp_path)), name            # no partial output, no temporary file
+
+
+def test_a_bucket_over_memory(case, tmp_path):
+    hist = sc.bucket_bytes(case["bam"])
+    largest = max(hist)
+    assert hist.index(largest) == 5 + 1 + 1                  # chr3's second bucket: the long record's
+    with pytest.raises(BamError) as e:
+        sort_bam.sort_bam(case["paths"]["whole"], str(tmp_path / "out.bam"), backend="host", memory=largest - 1)
+    message = str(e.value)
+    assert "chr3:1048577-2097152" in message and "%d bytes" % largest in message and "--memory %d" % (largest - 1) in message
+    assert not os.listdir(str(tmp_path))
+
+
+def test_existing_output_and_output_equal_to_input(case, tmp_path):
+    src = str(tmp_path / "reads.bam")
+    shutil.copy(case["paths"]["whole"], src)
+    out = str(tmp_path / "out.bam")
+    with open(out, "wb") as f:
+        f.write(b"old")
+    with pytest.raises(BamError, match="exists: --force"):
+        sort_bam.sort_bam(src, out, backend="host")
+    assert open(out, "rb").read() == b"old"
+    sort_bam.sort_bam(src, out, backend="host", force=True)
+    assert open(out, "rb").read() == open(case["sorted"], "rb").read()
+    for same in (src, str(tmp_path / "." / "reads.bam")):
+        with pytest.raises(BamError, match="the output is the input"):
+            sort_bam.sort_bam(src, same, backend="host", force=True)
+    os.symlink(src, str(tmp_path / "link.bam"))
+    with pytest.raises(BamError, match="the output is the input"):
+        sort_bam.sort_bam(src, str(tmp_path / "link.bam"), backend="host", force=True)
+    assert open(src, "rb").read() == open(case["paths"]["whole"], "rb").read()
+    with pytest.raises(BamError, match="auto, device or host"):
+        sort_bam.sort_bam(src, out, backend="gpu", force=True)
+    with pytest.raises(BamError, match="needs --backend device"):
+        sort_bam.sort_bam(src, out, backend="host", deflate="device", force=True)
+    with pytest.raises(BamError, match="cannot open"):
+        sort_bam.sort_bam(str(tmp_path / "nowhere.bam"), out, force=True)
+    assert sorted(os.listdir(str(tmp_path))) == ["link.bam", "out.bam", "reads.bam"]
+
+
+def test_zlib_writes_other_bytes_with_the_same_content(case, tmp_path):
+    out = str(tmp_path / "zlib.bam")
+    sort_bam.sort_bam(case["paths"]["whole"], out, backend="host", deflate="zlib")
+    assert open(out, "rb").read() != open(case["sorted"], "rb").read()
+    got, eof = sc.read_bgzf(out)
+    assert eof and got == sc.read_bgzf(case["sorted"])[0]
+
+
+# -- the command line -----------------------------------------------------------------------------------------------------------------------------
+def test_command_line_dispatcher_and_index(case, bad_files, tmp_path):
+    n = len(case["bam"].records)
+    for k, module in enumerate((["clair_amd", "sort_bam"], ["clair_amd.sort_bam"])):
+        out = str(tmp_path / ("out%d.bam" % k))
+        cmd = [sys.executable, "-m"] + module + ["--bam_fn", case["paths"]["straddle"], "--sorted_fn", out, "--backend", "host", "--bam_threads", "2",
+                                                "--memory", "100K", "--index"]
+        done = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, env=ENV, cwd=str(tmp_path))
+        assert done.returncode == 0 and "%d records" % n in done.stderr and "Traceback" not in done.stderr, done.stderr
+        assert open(out, "rb").read() == open(case["sorted"], "rb").read()
+        index_bam.build_index(out, str(tmp_path / "separate.bai"), backend="host", force=True)
+        assert open(out + ".bai", "rb").read() == open(str(tmp_path / "separate.bai"), "rb").read()
+        again = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, env=ENV, cwd=str(tmp_path))
+        assert again.returncode == 1 and "exists: --force" in again.stderr and "Traceback" not in again.stderr
+        assert subprocess.run(cmd + ["--force"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=ENV, cwd=str(tmp_path)).returncode == 0
+    bad = subprocess.run([sys.executable, "-m", "clair_amd.sort_bam", "--bam_fn", bad_files["negative_l_seq"][0], "--sorted_fn", str(tmp_path / "bad.bam"),
+                          "--backend", "host"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, env=ENV, cwd=str(tmp_path))
+    assert bad.returncode == 1 and "negative l_seq" in bad.stderr and "Traceback" not in bad.stderr and not os.path.exists(str(tmp_path / "bad.bam"))
+    from clair_amd.__main__ import SUBMODULES
+    assert SUBMODULES["sort_bam"] == "clair_amd.sort_bam"
+
+
+def test_symbols_are_declared_and_in_the_tables():
+    amd_h, host_h = open(os.path.join(ROOT, "include", "clair_amd.h")).read(), open(os.path.join(ROOT, "include", "clair_host.h")).read()
+    host = _hostapi.load()
+    for name in ("create", "destroy", "begin", "pass", "batch", "histogram", "sort", "emit", "backend", "debug_sort", "debug_gather"):
+        assert "clair_bamsort_" + name + "(" in amd_h and "clair_bamsort_" + name in _capi.SIGNATURES
+        assert "clair_host_bamsort_" + name + "(" in host_h and "clair_host_bamsort_" + name in _hostapi.SIGNATURES and hasattr(host, "clair_host_bamsort_" + name)
+    assert "clair_bamsort_last_error" in _capi.SIGNATURES
+    for name in ("open", "close", "header", "run"):
+        assert "clair_host_bamsort_" + name in _hostapi.SIGNATURES and hasattr(host, "clair_host_bamsort_" + name)
+    core = open(os.path.join(ROOT, "clair_amd", "csrc", "bam_sort_core.h")).read()
+    assert "RADIX_ITEMS = %d;" % sort_bam.RADIX_ITEMS in core and sort_bam.RADIX_TILE == 256 * sort_bam.RADIX_ITEMS
+
+
+# -- the radix rule -----------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(sc.key_sets(0)))
+def test_the_twins_sort_and_the_radix_rule_restated(name):
+    for n in sc.sizes_for(sort_bam.RADIX_TILE):
+        keys = sc.key_sets(n)[name]
+        want = np.argsort(keys, kind="stable")
+        assert np.array_equal(sort_bam.host_debug_sort(keys), want), n
+        got, passes = sc.radix_restated(keys, sort_bam.RADIX_TILE)
+        assert np.array_equal(got, want), n
+        if n >= 255:
+            assert passes == {"random": 8, "three_values": passes, "top_byte": 1, "bit_0": 1, "all_equal": 0, "bit_63": 4, "real": passes}[name], n
+    assert sc.radix_restated(sc.key_sets(300)["real"], 2048)[1] < 8                   # few references, small positions: upper passes skipped
+
+
+def test_the_twins_gather():
+    stream, starts, perm = sc.gather_case()
+    want = b"".join(stream[starts[p]:starts[p] + 4 + struct.unpack_from("<I", stream, starts[p])[0]] for p in perm)
+    assert sort_bam.host_debug_gather(stream, starts, perm) == want
+    with pytest.raises(BamError, match="no record at"):
+        sort_bam.host_debug_gather(stream, [starts[0] + 1] + starts[1:], perm)
+
+
+# -- the host side under the sanitizers, as a program of its own -------------------------------------------------------------------------------------
+SANITIZE = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g", "-O1", "-std=c++17"]
+
+
+def _checksum(data):
+    h = 0xcbf29ce484222325
+    for b in data:
+        h = ((h ^ b) * 0x100000001b3) & 0xffffffffffffffff
+    return h
+
+
+def test_host_side_under_address_and_undefined_sanitizers(case, bad_files, tmp_path):
+    cxx = shutil.which(os.environ.get("CXX", "g++"))
+    if cxx is None:
+        pytest.skip("no C++ compiler")
+    probe = str(tmp_path / "probe.cpp")
+    with open(probe, "w") as f:
+        f.write("int main() { return 0; }\n")
+    if subprocess.run([cxx] + SANITIZE + [probe, "-o", str(tmp_path / "probe")], stdout=subprocess.PIPE, stderr=subprocess.PIPE).returncode != 0 \
+            or subprocess.run([str(tmp_path / "probe")], stdout=subprocess.PIPE, stderr=subprocess.PIPE).returncode != 0:
+        pytest.skip("the sanitizer runtimes are not installed")
+    program = str(tmp_path / "sort_bam_sanitize")
+    hostsrc = os.path.join(ROOT, "clair_amd", "hostsrc")
+    subprocess.check_call([cxx] + SANITIZE + ["-Wall", "-pthread", os.path.join(HERE, "sort_bam_sanitize.cpp"), os.path.join(hostsrc, "host_bam_sort.cpp"),
+                                               os.path.join(hostsrc, "host_deflate.cpp"), "-o", program, "-lz"])
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
+    n = len(case["bam"].records)
+    head = len(sort_bam.header_blocks(sort_bam.coordinate_header(case["bam"].header()), "host"))
+    want = "%016x" % _checksum(open(case["sorted"], "rb").read()[head:])                # what the driver appended in this process
+    hist = sc.bucket_bytes(case["bam"])
+    for way, segment, max_blocks, memory in (("straddle", 0, 64, 8 << 30), ("straddle", 64, 1, 8 << 30), ("whole", 4096, 2, max(hist) + 20000),
+                                             ("per_record", 8192, 3, max(hist)), ("whole", 0, 64, sum(hist) - 1)):
+        out = str(tmp_path / "out.part")
+        done = subprocess.run([program, case["paths"][way], out, str(segment), str(max_blocks), str(memory)], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                              universal_newlines=True, env=env)
+        assert done.returncode == 0 and done.stderr == "", done.stderr[-2000:]
+        groups, reads = sc.expected_groups(case["bam"], memory)
+        assert done.stdout.split() == [str(v) for v in (n, groups, reads, 0)] + [want], (way, segment, memory, done.stdout)
+        os.remove(out)
+    bad = dict(bad_files, over_memory=(case["paths"]["whole"], r"more than --memory"))
+    for name, (path, pattern) in bad.items():
+        if name in NOT_A_SORTS:
+            continue
+        for segment in (0, 64):
+            done = subprocess.run([program, path, str(tmp_path / "bad.part"), str(segment), "2", str(max(hist) - 1 if name == "over_memory" else 1 << 20)],
+                                  stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, env=env)
+            assert done.returncode == 2 and done.stderr == "" and re.search(pattern, done.stdout), (name, done.stdout, done.stderr[-2000:])
