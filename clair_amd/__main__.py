@@ -19,6 +19,7 @@ SUBMODULES = {
     "compare_vcf": "clair_amd.compare_vcf",
     "index_bam": "clair_amd.index_bam",
     "sort_bam": "clair_amd.sort_bam",
+    "markdup_bam": "clair_amd.markdup_bam",
     "gvcf": "clair_amd.gvcf",
 }
 NOT_COVERED = ("plot_tensor", "train", "Tensor2Bin", "CombineBins", "Bin2To3", "overlap_variant")

@@ -176,6 +176,19 @@ SIGNATURES = {
     "clair_bamsort_backend": _sig(c_vp, c_vp),
     "clair_bamsort_debug_sort": _sig(c_vp, c_vp, c_i64, c_vp),
     "clair_bamsort_debug_gather": _sig(c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64),
+    "clair_markdup_create": _sig(c_int, c_int, c_int, p_vp),
+    "clair_markdup_destroy": _sig(c_vp, restype=None),
+    "clair_markdup_last_error": _sig(c_vp, restype=c_cp),
+    "clair_markdup_begin": _sig(c_vp, c_int, c_i64, c_int),
+    "clair_markdup_batch": _sig(c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_vp),
+    "clair_markdup_resolve": _sig(c_vp),
+    "clair_markdup_mark": _sig(c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_vp),
+    "clair_markdup_emit": _sig(c_vp, c_i64, c_int, c_int, c_vp, c_vp),
+    "clair_markdup_stats": _sig(c_vp, c_vp),
+    "clair_markdup_backend": _sig(c_vp, c_vp),
+    "clair_markdup_debug_summary": _sig(c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_vp),
+    "clair_markdup_debug_resolve": _sig(c_vp, c_vp, c_i64, c_vp),
+    "clair_markdup_debug_mark": _sig(c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_int, c_vp, c_vp, c_vp),
 }
 SYMBOLS = tuple(SIGNATURES)
 ENSEMBLE_MAX_MODELS = 8                                      # CLAIR_ENSEMBLE_MAX_MODELS

@@ -133,6 +133,21 @@ SIGNATURES = {
     "clair_host_bamsort_close": _sig(vp, restype=None),
     "clair_host_bamsort_header": _sig(vp, vp, i64, p_i64),
     "clair_host_bamsort_run": _sig(vp, vp, cp, i32, i64, i32, i32, vp),
+    "clair_host_markdup_create": _sig(i32, i32, i32, p_vp),
+    "clair_host_markdup_destroy": _sig(vp, restype=None),
+    "clair_host_markdup_begin": _sig(vp, i32, i64, i32),
+    "clair_host_markdup_batch": _sig(vp, vp, i64, i32, vp, vp, vp, vp, i64, i64, i32, vp),
+    "clair_host_markdup_resolve": _sig(vp),
+    "clair_host_markdup_mark": _sig(vp, vp, i64, i32, vp, vp, vp, vp, i64, i64, i32, vp),
+    "clair_host_markdup_emit": _sig(vp, i64, i32, i32, vp, vp),
+    "clair_host_markdup_stats": _sig(vp, vp),
+    "clair_host_markdup_backend": _sig(vp, vp),
+    "clair_host_markdup_debug_summary": _sig(vp, i64, vp, i64, i32, vp),
+    "clair_host_markdup_debug_resolve": _sig(vp, i64, vp),
+    "clair_host_markdup_open": _sig(cp, p_vp),
+    "clair_host_markdup_close": _sig(vp, restype=None),
+    "clair_host_markdup_header": _sig(vp, vp, i64, p_i64),
+    "clair_host_markdup_run": _sig(vp, vp, cp, i32, i64, i32, i32, i32, vp),
     "clair_host_gvcf_tally": _sig(vp, i64, vp, i64, vp, i64, i64, i64, vp, vp),
     "clair_host_gvcf_blocks": _sig(vp, i64, i64, vp, i64, i64, i32, i32, i32, vp, vp, vp, i64, vp, i64, p_i64),
     "clair_host_gvcf_format": _sig(vp, i64, i64, cp, vp, i64, i64, vp, i64, p_i64, vp),

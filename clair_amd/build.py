@@ -9,7 +9,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # (csrc/indel_lookup.hip, train_set.hip and gvcf.hip are part of frontend.hip's translation unit: they work on that handle's slabs and tables)
-SRCS = [os.path.join(HERE, "csrc", f) for f in ("engine.hip", "comm.hip", "frontend.hip", "inflate.hip", "deflate.hip", "overlap.hip", "train.hip", "compare.hip", "bam_index.hip", "bam_sort.hip")]
+SRCS = [os.path.join(HERE, "csrc", f) for f in ("engine.hip", "comm.hip", "frontend.hip", "inflate.hip", "deflate.hip", "overlap.hip", "train.hip", "compare.hip", "bam_index.hip", "bam_sort.hip", "markdup.hip")]
 OUT = os.path.join(HERE, "libclair_amd.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
@@ -37,7 +37,7 @@ def needs_build():
 
 
 HOST_SRCS = [os.path.join(HERE, "hostsrc", f) for f in ("host_io.cpp", "host_decode.cpp", "host_pileup.cpp", "host_sampack.cpp",
-                                                              "host_bam.cpp", "host_inflate.cpp", "host_deflate.cpp", "host_indel.cpp", "host_ensemble.cpp", "host_overlap.cpp", "host_sites.cpp", "host_train_set.cpp", "host_compare.cpp", "host_bam_index.cpp", "host_gvcf.cpp", "host_bam_sort.cpp")]
+                                                              "host_bam.cpp", "host_inflate.cpp", "host_deflate.cpp", "host_indel.cpp", "host_ensemble.cpp", "host_overlap.cpp", "host_sites.cpp", "host_train_set.cpp", "host_compare.cpp", "host_bam_index.cpp", "host_gvcf.cpp", "host_bam_sort.cpp", "host_markdup.cpp")]
 HOST_OUT = os.path.join(HERE, "libclair_host.so")
 CXX = os.environ.get("CXX", "g++")
 
@@ -58,8 +58,10 @@ def build_host(force=False):
     hdrs.append(os.path.join(HERE, "csrc", "train_set_core.h"))     # the sampling, pairing and label rules host_train_set.cpp shares with the device (csrc/train_set.hip)
     hdrs.append(os.path.join(HERE, "csrc", "compare_core.h"))       # the row, trim and join rules host_compare.cpp shares with the device (csrc/compare.hip)
     hdrs.append(os.path.join(HERE, "csrc", "bam_index_core.h"))     # the framing, field and order rules host_bam_index.cpp shares with the device (csrc/bam_index.hip)
-    hdrs.append(os.path.join(HERE, "hostsrc", "bam_frame.h"))       # records framed on the host: host_bam_index.cpp, host_bam_sort.cpp
+    hdrs.append(os.path.join(HERE, "hostsrc", "bam_frame.h"))       # the front of a batch on the host (inflate, framing, carry): host_bam_index.cpp, host_bam_sort.cpp, host_markdup.cpp
     hdrs.append(os.path.join(HERE, "csrc", "bam_sort_core.h"))      # the key, the bucket and the verdicts host_bam_sort.cpp shares with the device (csrc/bam_sort.hip)
+    hdrs.append(os.path.join(HERE, "hostsrc", "bam_job.h"))         # the input as a job, its batches and the output's blocks: host_bam_sort.cpp, host_markdup.cpp
+    hdrs.append(os.path.join(HERE, "csrc", "markdup_core.h"))       # the duplicate rule host_markdup.cpp shares with the device (csrc/markdup.hip)
     hdrs.append(os.path.join(HERE, "csrc", "gvcf_core.h"))          # the reference-confidence rule and the block record host_gvcf.cpp shares with the device (csrc/gvcf.hip)
     hdrs.append(os.path.join(HERE, "csrc", "subsample_core.h"))     # the read-name rule host_bam.cpp shares with the device (csrc/frontend.hip)
     if (force or not os.path.isfile(HOST_OUT)

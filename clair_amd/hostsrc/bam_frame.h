@@ -1,11 +1,14 @@
-// Framing a stream of BAM records on the host, for the twins that take batches of inflated blocks (host_bam_index.cpp, host_bam_sort.cpp):
+// The front of a batch on the host, for the twins that take batches of BGZF blocks (host_bam_index.cpp, host_bam_sort.cpp,
+// host_markdup.cpp): HostFront, which inflates the blocks behind the carried bytes and frames the records, over the two framings:
 // the sequential walk, and -- so that the parallel rule can be held against the walk on a machine without a GPU -- a restatement of the
 // segmented framing the device runs (csrc/bam_index.hip: jump table per segment, pointer jumping, the chain over the segments, counts,
 // offsets).  The rules themselves are csrc/bam_index_core.h.  Host only.
 #pragma once
 #include "../csrc/bam_index_core.h"
+#include "bgzf_file.h"
 
 #include <algorithm>
+#include <cstring>
 #include <vector>
 
 namespace clair_frame {
@@ -50,5 +53,82 @@ inline void frame_segmented(const Bytes &m, int64_t len, int64_t entry, uint32_t
 inline bool good_segment(int segment_bytes) {
     return segment_bytes >= (int)SEG_MIN && segment_bytes <= (int)SEG_MAX && (segment_bytes & (segment_bytes - 1)) == 0;
 }
+
+// ---- the front of a batch on the host, what clair_bix::Front (csrc/bam_front.h) is on the device: the blocks of a batch inflated behind the
+// bytes the batch before carried over, the records framed there, the table that turns a stream position into a virtual offset, the verdicts
+// of the frame step and the carry to the next batch.  `who` names the stage in the messages ("bamsort batch").
+struct HostFront {
+    int threads = 4, max_blocks = 0;
+    uint32_t seg = 0;                            // 0: the sequential walk
+    std::vector<uint8_t> stream, carry;
+    uint64_t carry_voff = 0;
+    std::vector<int64_t> at, starts;
+    std::vector<uint64_t> voff;
+    // the batch between open_batch and close_batch
+    int64_t len = 0, tail = 0;
+    bool bad = false;
+
+    void rewind() { carry.clear(); carry_voff = 0; }         // a new file, or a new read of one
+    uint64_t voffset(int64_t p) const { return voffset_at(at.data(), voff.data(), (int)at.size(), p); }
+
+    int open_batch(const char *who, const uint8_t *cdata, int64_t cbytes, int n, const int64_t *in_at, const int32_t *csize, const int32_t *out_len,
+                   const int64_t *coffset, int64_t end_coffset, int64_t entry) {
+        if (n > 0 && (!cdata || !in_at || !csize || !out_len || !coffset)) return clair_host_fail("%s: NULL argument", who);
+        if (cbytes < 0 || end_coffset < 0 || entry < 0) return clair_host_fail("%s: negative argument", who);
+        if (clair_inf::check_blocks(clair_host_fail, n, max_blocks, cbytes, in_at, csize, out_len)) return 1;
+        len = (int64_t)carry.size();
+        for (int i = 0; i < n; ++i) {
+            if (coffset[i] < 0) return clair_host_fail("block %d: negative offset", i);
+            len += out_len[i];
+        }
+        if (entry > len) return clair_host_fail("%s: entry %lld beyond the %lld bytes of the batch", who, (long long)entry, (long long)len);
+        // 1. the stream and the table of its pieces
+        stream.resize((size_t)len);
+        at.clear();
+        voff.clear();
+        if (!carry.empty()) {
+            memcpy(stream.data(), carry.data(), carry.size());
+            at.push_back(0);
+            voff.push_back(carry_voff);
+        }
+        std::vector<int32_t> status((size_t)n, 0);
+        int64_t pos = (int64_t)carry.size();
+        const size_t first_block = at.size();
+        for (int i = 0; i < n; ++i) {
+            at.push_back(pos);
+            voff.push_back((uint64_t)coffset[i] << 16);
+            pos += out_len[i];
+        }
+        at.push_back(len);
+        voff.push_back((uint64_t)end_coffset << 16);
+        clair_bgzf::inflate_blocks(threads, cdata, n, in_at, csize, at.data() + first_block, out_len, stream.data(), status.data());
+        for (int i = 0; i < n; ++i)
+            if (status[(size_t)i]) return clair_host_fail("BGZF block at compressed offset %lld: %s", (long long)coffset[i], clair_bgzf::inflate_text(status[(size_t)i]));
+        // 2. the record starts
+        const Bytes m{stream.data()};
+        starts.clear();
+        tail = 0;
+        bad = false;
+        if (seg) frame_segmented(m, len, entry, seg, starts, &tail, &bad);
+        else frame_walk(m, len, entry, starts, &tail, &bad);
+        return 0;
+    }
+    // the verdicts of the frame step (a size word that cannot be; with `last`, bytes behind the last whole record), then the carry
+    int close_batch(int last) {
+        char buf[200];
+        if (bad) {
+            describe_bad_step(buf, sizeof buf, voffset(tail), Bytes{stream.data()}.le32(tail));
+            return clair_host_fail("%s", buf);
+        }
+        if (last && tail < len) {
+            describe_cut(buf, sizeof buf, voffset(tail));
+            return clair_host_fail("%s", buf);
+        }
+        carry_voff = tail < len ? voffset(tail) : 0;
+        std::vector<uint8_t> keep(stream.begin() + (ptrdiff_t)tail, stream.end());
+        carry.swap(keep);
+        return 0;
+    }
+};
 
 }  // namespace clair_frame

@@ -10,7 +10,6 @@
 #include "../csrc/bam_index_core.h"
 #include "bam_frame.h"
 #include "bam_header.h"
-#include "bgzf_file.h"
 
 #include <algorithm>
 #include <climits>
@@ -28,16 +27,11 @@ using namespace clair_frame;
 }  // namespace
 
 struct clair_host_bamidx {
-    int threads = 4, max_blocks = 0;
-    uint32_t seg = 0;                            // 0: the sequential walk
+    clair_frame::HostFront front;                // the batch: the stream, the record starts, the carry
     int n_ref = -1;
     std::vector<int64_t> first_window;           // n_ref + 1
     std::vector<uint64_t> linear;
     int64_t counts[3] = {0, 0, 0};
-    std::vector<uint8_t> stream, carry;
-    uint64_t carry_voff = 0;
-    std::vector<int64_t> at, starts;
-    std::vector<uint64_t> voff;
     std::vector<clair_bamidx_run_t> runs;
 };
 
@@ -57,9 +51,9 @@ int clair_host_bamidx_create(int threads, int max_blocks, int segment_bytes, cla
     if (max_blocks < 1 || max_blocks > 16384) return clair_host_fail("max_blocks %d: 1 .. 16384", max_blocks);
     if (segment_bytes != 0 && !good_segment(segment_bytes)) return clair_host_fail("segment_bytes %d: a power of two in %u .. %u, or 0", segment_bytes, SEG_MIN, SEG_MAX);
     clair_host_bamidx *h = new clair_host_bamidx;
-    h->threads = threads;
-    h->max_blocks = max_blocks;
-    h->seg = (uint32_t)segment_bytes;
+    h->front.threads = threads;
+    h->front.max_blocks = max_blocks;
+    h->front.seg = (uint32_t)segment_bytes;
     *out = h;
     return 0;
 }
@@ -73,8 +67,7 @@ int clair_host_bamidx_begin(clair_host_bamidx_t *h, int n_ref, const int64_t *re
     h->linear.assign((size_t)h->first_window[(size_t)n_ref], NO_OFFSET);
     h->n_ref = n_ref;
     h->counts[0] = h->counts[1] = h->counts[2] = 0;
-    h->carry.clear();
-    h->carry_voff = 0;
+    h->front.rewind();
     return 0;
 }
 
@@ -83,52 +76,17 @@ int clair_host_bamidx_batch(clair_host_bamidx_t *h, const uint8_t *cdata, int64_
                             const clair_bamidx_run_t **runs) {
     if (!h || !state || !runs) return clair_host_fail("bamidx batch: NULL argument");
     if (h->n_ref < 0) return clair_host_fail("bamidx batch: begin first");
-    if (n > 0 && (!cdata || !in_at || !csize || !out_len || !coffset)) return clair_host_fail("bamidx batch: NULL argument");
-    if (cbytes < 0 || end_coffset < 0 || entry < 0) return clair_host_fail("bamidx batch: negative argument");
-    if (clair_inf::check_blocks(clair_host_fail, n, h->max_blocks, cbytes, in_at, csize, out_len)) return 1;
-    int64_t len = (int64_t)h->carry.size();
-    for (int i = 0; i < n; ++i) {
-        if (coffset[i] < 0) return clair_host_fail("block %d: negative offset", i);
-        len += out_len[i];
-    }
-    if (entry > len) return clair_host_fail("bamidx batch: entry %lld beyond the %lld bytes of the batch", (long long)entry, (long long)len);
-    // 1. the stream and the table of its pieces
-    h->stream.resize((size_t)len);
-    h->at.clear();
-    h->voff.clear();
-    if (!h->carry.empty()) {
-        memcpy(h->stream.data(), h->carry.data(), h->carry.size());
-        h->at.push_back(0);
-        h->voff.push_back(h->carry_voff);
-    }
-    std::vector<int32_t> status((size_t)n, 0);
-    int64_t pos = (int64_t)h->carry.size();
-    const size_t first_block = h->at.size();
-    for (int i = 0; i < n; ++i) {
-        h->at.push_back(pos);
-        h->voff.push_back((uint64_t)coffset[i] << 16);
-        pos += out_len[i];
-    }
-    h->at.push_back(len);
-    h->voff.push_back((uint64_t)end_coffset << 16);
-    inflate_blocks(h->threads, cdata, n, in_at, csize, h->at.data() + first_block, out_len, h->stream.data(), status.data());
-    for (int i = 0; i < n; ++i)
-        if (status[(size_t)i]) return clair_host_fail("BGZF block at compressed offset %lld: %s", (long long)coffset[i], inflate_text(status[(size_t)i]));
-    // 2. the record starts
-    const Bytes m{h->stream.data()};
-    const int n_tab = (int)h->at.size();
-    h->starts.clear();
-    int64_t tail = 0;
-    bool bad = false;
-    if (h->seg) frame_segmented(m, len, entry, h->seg, h->starts, &tail, &bad);
-    else frame_walk(m, len, entry, h->starts, &tail, &bad);
-    const int64_t n_rec = (int64_t)h->starts.size();
-    const auto voffset = [&](int64_t p) { return voffset_at(h->at.data(), h->voff.data(), n_tab, p); };
+    // 1, 2. the stream and the record starts (bam_frame.h)
+    HostFront &front = h->front;
+    if (front.open_batch("bamidx batch", cdata, cbytes, n, in_at, csize, out_len, coffset, end_coffset, entry)) return 1;
+    const Bytes m{front.stream.data()};
+    const int64_t n_rec = (int64_t)front.starts.size(), tail = front.tail;
+    const auto voffset = [&](int64_t p) { return front.voffset(p); };
     // 3 - 5. fields, runs, the linear index
     h->runs.clear();
     int32_t prev_tid = (int32_t)state[ST_PREV_TID], prev_pos = (int32_t)state[ST_PREV_POS];
     for (int64_t k = 0; k < n_rec; ++k) {
-        const int64_t o = h->starts[(size_t)k];
+        const int64_t o = front.starts[(size_t)k];
         Fields f = fields(m, o, h->n_ref);
         if (f.verdict == V_OK && order_key(f.tid, f.pos) < order_key(prev_tid, prev_pos)) f.verdict = V_UNSORTED;
         if (f.verdict != V_OK) {
@@ -137,7 +95,7 @@ int clair_host_bamidx_batch(clair_host_bamidx_t *h, const uint8_t *cdata, int64_
             describe(buf, sizeof buf, d);
             return clair_host_fail("%s", buf);
         }
-        const uint64_t beg = voffset(o), end = voffset(k + 1 < n_rec ? h->starts[(size_t)k + 1] : tail);
+        const uint64_t beg = voffset(o), end = voffset(k + 1 < n_rec ? front.starts[(size_t)k + 1] : tail);
         h->counts[0] += 1;
         if (f.tid < 0) h->counts[2] += 1;
         else if (!(f.flag & 4)) h->counts[1] += 1;
@@ -153,24 +111,12 @@ int clair_host_bamidx_batch(clair_host_bamidx_t *h, const uint8_t *cdata, int64_
         prev_tid = f.tid;
         prev_pos = f.pos;
     }
-    if (bad) {
-        char buf[200];
-        describe_bad_step(buf, sizeof buf, voffset(tail), m.le32(tail));
-        return clair_host_fail("%s", buf);
-    }
-    if (last && tail < len) {
-        char buf[200];
-        describe_cut(buf, sizeof buf, voffset(tail));
-        return clair_host_fail("%s", buf);
-    }
-    h->carry_voff = tail < len ? voffset(tail) : 0;
-    std::vector<uint8_t> keep(h->stream.begin() + (ptrdiff_t)tail, h->stream.end());
-    h->carry.swap(keep);
+    if (front.close_batch(last)) return 1;
     state[ST_N_RECORDS] = n_rec;
     state[ST_N_RUNS] = (int64_t)h->runs.size();
     state[ST_LAST_TID] = prev_tid;
     state[ST_LAST_POS] = prev_pos;
-    state[ST_CARRY] = (int64_t)h->carry.size();
+    state[ST_CARRY] = (int64_t)front.carry.size();
     *runs = h->runs.data();
     return 0;
 }

@@ -9,8 +9,7 @@
 #include "../../include/clair_host.h"
 #include "../csrc/bam_sort_core.h"
 #include "bam_frame.h"
-#include "bam_header.h"
-#include "bgzf_file.h"
+#include "bam_job.h"
 
 #include <algorithm>
 #include <climits>
@@ -26,58 +25,13 @@ namespace {
 using namespace clair_bsort;
 using namespace clair_bgzf;
 using namespace clair_frame;
-
-// payload i of n: in_len[i] bytes at data + i * PAYLOAD -> one BGZF block in its slot, its size in sizes[i]; thread t takes t, t + nt, ...
-int deflate_payloads(int threads, const uint8_t *data, int n, const int32_t *in_len, uint8_t *out, int32_t *sizes) {
-    std::vector<int> rc((size_t)n, 0);
-    const auto one = [&](int i) {
-        int64_t n_out = 0;
-        rc[(size_t)i] = clair_host_deflate_bgzf(data + (int64_t)i * PAYLOAD, in_len[i], out + (int64_t)i * SLOT, &n_out);
-        sizes[i] = (int32_t)n_out;
-    };
-    const int nt = std::max(1, std::min(threads, n));
-    if (nt == 1) {
-        for (int i = 0; i < n; ++i) one(i);
-    } else {
-        std::vector<std::thread> pool;
-        for (int t = 0; t < nt; ++t) pool.emplace_back([&, t] { for (int i = t; i < n; i += nt) one(i); });
-        for (auto &th : pool) th.join();
-    }
-    for (int i = 0; i < n; ++i) if (rc[(size_t)i]) return clair_host_fail("deflate of payload %d failed", i);
-    return 0;
-}
-
-// one BGZF block by zlib at level 6; stored when that is what fits the 64 KiB (clair_amd/bgzf.py: zlib_block)
-int zlib_payload(const uint8_t *data, int32_t len, uint8_t *out, int32_t *size) {
-    static const uint8_t head[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
-    for (int level : {6, 0}) {
-        z_stream z{};
-        if (deflateInit2(&z, level, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) return clair_host_fail("deflateInit2 failed");
-        z.next_in = const_cast<uint8_t *>(data);
-        z.avail_in = (uInt)len;
-        z.next_out = out + BGZF_HEADER;
-        z.avail_out = (uInt)(SLOT - BGZF_HEADER - BGZF_FOOTER);
-        const int rc = deflate(&z, Z_FINISH);
-        const size_t got = z.total_out;
-        deflateEnd(&z);
-        if (rc != Z_STREAM_END) continue;
-        memcpy(out, head, 16);
-        const uint32_t total = (uint32_t)got + BGZF_HEADER + BGZF_FOOTER, crc = (uint32_t)crc32(0L, data, (uInt)len);
-        out[16] = (uint8_t)((total - 1) & 0xff);
-        out[17] = (uint8_t)((total - 1) >> 8);
-        uint8_t *foot = out + BGZF_HEADER + got;
-        for (int k = 0; k < 4; ++k) { foot[k] = (uint8_t)(crc >> (8 * k)); foot[4 + k] = (uint8_t)((uint32_t)len >> (8 * k)); }
-        *size = (int32_t)total;
-        return 0;
-    }
-    return clair_host_fail("a payload of %d bytes does not fit a BGZF block", len);
-}
+using clair_job::deflate_payloads;
+using clair_job::zlib_payload;
 
 }  // namespace
 
 struct clair_host_bamsort {
-    int threads = 4, max_blocks = 0;
-    uint32_t seg = 0;                            // 0: the sequential walk
+    clair_frame::HostFront front;                // the batch: the stream, the record starts, the carry
     // the file
     int n_ref = -1;
     int64_t memory = 0;
@@ -86,10 +40,6 @@ struct clair_host_bamsort {
     // the read in progress
     int64_t lo = 0, hi = 0;
     bool first = false, overflow = false;
-    std::vector<uint8_t> stream, carry;
-    uint64_t carry_voff = 0;
-    std::vector<int64_t> at, starts;
-    std::vector<uint64_t> voff;
     // the group
     std::vector<uint8_t> group;
     std::vector<uint64_t> keys;
@@ -99,15 +49,7 @@ struct clair_host_bamsort {
     int64_t total = 0;
 };
 
-struct clair_host_bamsort_job {
-    std::string path;
-    FILE *file = nullptr;
-    int64_t file_size = 0;
-    std::vector<uint8_t> text;                   // the inflated header, and what follows it in its last block
-    BamHeader header;
-    int64_t coffset = 0, entry = 0;              // where the first record's block starts, the record's offset in it
-    ~clair_host_bamsort_job() { if (file) fclose(file); }
-};
+struct clair_host_bamsort_job : clair_job::Job {};
 
 extern "C" {
 
@@ -118,9 +60,9 @@ int clair_host_bamsort_create(int threads, int max_blocks, int segment_bytes, cl
     if (max_blocks < 1 || max_blocks > 16384) return clair_host_fail("max_blocks %d: 1 .. 16384", max_blocks);
     if (segment_bytes != 0 && !good_segment(segment_bytes)) return clair_host_fail("segment_bytes %d: a power of two in %u .. %u, or 0", segment_bytes, SEG_MIN, SEG_MAX);
     clair_host_bamsort *h = new clair_host_bamsort;
-    h->threads = threads;
-    h->max_blocks = max_blocks;
-    h->seg = (uint32_t)segment_bytes;
+    h->front.threads = threads;
+    h->front.max_blocks = max_blocks;
+    h->front.seg = (uint32_t)segment_bytes;
     *out = h;
     return 0;
 }
@@ -149,8 +91,7 @@ int clair_host_bamsort_pass(clair_host_bamsort_t *h, int64_t bucket_lo, int64_t 
     h->hi = bucket_hi;
     h->first = first != 0;
     h->overflow = false;
-    h->carry.clear();
-    h->carry_voff = 0;
+    h->front.rewind();
     h->group.clear();
     h->keys.clear();
     h->off.assign(1, 0);
@@ -162,52 +103,17 @@ int clair_host_bamsort_batch(clair_host_bamsort_t *h, const uint8_t *cdata, int6
                              const int32_t *out_len, const int64_t *coffset, int64_t end_coffset, int64_t entry, int last, int64_t *state) {
     if (!h || !state) return clair_host_fail("bamsort batch: NULL argument");
     if (h->n_ref < 0 || h->off.empty()) return clair_host_fail("bamsort batch: begin and pass first");
-    if (n > 0 && (!cdata || !in_at || !csize || !out_len || !coffset)) return clair_host_fail("bamsort batch: NULL argument");
-    if (cbytes < 0 || end_coffset < 0 || entry < 0) return clair_host_fail("bamsort batch: negative argument");
-    if (clair_inf::check_blocks(clair_host_fail, n, h->max_blocks, cbytes, in_at, csize, out_len)) return 1;
-    int64_t len = (int64_t)h->carry.size();
-    for (int i = 0; i < n; ++i) {
-        if (coffset[i] < 0) return clair_host_fail("block %d: negative offset", i);
-        len += out_len[i];
-    }
-    if (entry > len) return clair_host_fail("bamsort batch: entry %lld beyond the %lld bytes of the batch", (long long)entry, (long long)len);
-    // 1. the stream and the table of its pieces
-    h->stream.resize((size_t)len);
-    h->at.clear();
-    h->voff.clear();
-    if (!h->carry.empty()) {
-        memcpy(h->stream.data(), h->carry.data(), h->carry.size());
-        h->at.push_back(0);
-        h->voff.push_back(h->carry_voff);
-    }
-    std::vector<int32_t> status((size_t)n, 0);
-    int64_t pos = (int64_t)h->carry.size();
-    const size_t first_block = h->at.size();
-    for (int i = 0; i < n; ++i) {
-        h->at.push_back(pos);
-        h->voff.push_back((uint64_t)coffset[i] << 16);
-        pos += out_len[i];
-    }
-    h->at.push_back(len);
-    h->voff.push_back((uint64_t)end_coffset << 16);
-    inflate_blocks(h->threads, cdata, n, in_at, csize, h->at.data() + first_block, out_len, h->stream.data(), status.data());
-    for (int i = 0; i < n; ++i)
-        if (status[(size_t)i]) return clair_host_fail("BGZF block at compressed offset %lld: %s", (long long)coffset[i], inflate_text(status[(size_t)i]));
-    // 2. the record starts
-    const Bytes m{h->stream.data()};
-    const int n_tab = (int)h->at.size();
-    h->starts.clear();
-    int64_t tail = 0;
-    bool bad = false;
-    if (h->seg) frame_segmented(m, len, entry, h->seg, h->starts, &tail, &bad);
-    else frame_walk(m, len, entry, h->starts, &tail, &bad);
-    const int64_t n_rec = (int64_t)h->starts.size();
-    const auto voffset = [&](int64_t p) { return voffset_at(h->at.data(), h->voff.data(), n_tab, p); };
+    // 1, 2. the stream and the record starts (bam_frame.h)
+    HostFront &front = h->front;
+    if (front.open_batch("bamsort batch", cdata, cbytes, n, in_at, csize, out_len, coffset, end_coffset, entry)) return 1;
+    const Bytes m{front.stream.data()};
+    const int64_t n_rec = (int64_t)front.starts.size();
+    const auto voffset = [&](int64_t p) { return front.voffset(p); };
     // 3. keys, the histogram, the order, the records of this group
     uint64_t prev = (uint64_t)state[SS_PREV_KEY];
     int64_t kept = 0, kept_bytes = 0, mapped = 0, unplaced = 0, unsorted = 0;
     for (int64_t k = 0; k < n_rec; ++k) {
-        const int64_t o = h->starts[(size_t)k];
+        const int64_t o = front.starts[(size_t)k];
         const Fields f = fields(m, o, h->n_ref);
         if (sort_verdict(f.verdict) != V_OK) {
             const Detail d{state[SS_RECORDS_BEFORE] + k, f.tid, f.pos, 0, 0, f.end, voffset(o), m.le32(o), f.verdict};
@@ -232,25 +138,13 @@ int clair_host_bamsort_batch(clair_host_bamsort_t *h, const uint8_t *cdata, int6
             continue;
         }
         if ((int64_t)h->keys.size() >= MAX_GROUP_RECORDS) return clair_host_fail("more than 2^31 - 1 records in one group: a smaller --memory makes smaller groups");
-        h->group.insert(h->group.end(), h->stream.begin() + (ptrdiff_t)o, h->stream.begin() + (ptrdiff_t)(o + size));
+        h->group.insert(h->group.end(), front.stream.begin() + (ptrdiff_t)o, front.stream.begin() + (ptrdiff_t)(o + size));
         h->keys.push_back(key);
         h->off.push_back((int64_t)h->group.size());
         ++kept;
         kept_bytes += size;
     }
-    if (bad) {
-        char buf[200];
-        describe_bad_step(buf, sizeof buf, voffset(tail), m.le32(tail));
-        return clair_host_fail("%s", buf);
-    }
-    if (last && tail < len) {
-        char buf[200];
-        describe_cut(buf, sizeof buf, voffset(tail));
-        return clair_host_fail("%s", buf);
-    }
-    h->carry_voff = tail < len ? voffset(tail) : 0;
-    std::vector<uint8_t> keep(h->stream.begin() + (ptrdiff_t)tail, h->stream.end());
-    h->carry.swap(keep);
+    if (front.close_batch(last)) return 1;
     state[SS_N_RECORDS] = n_rec;
     state[SS_LAST_KEY] = (int64_t)prev;
     state[SS_KEPT] = h->overflow ? 0 : kept;
@@ -259,7 +153,7 @@ int clair_host_bamsort_batch(clair_host_bamsort_t *h, const uint8_t *cdata, int6
     state[SS_OVERFLOW] = h->overflow ? 1 : 0;
     state[SS_MAPPED] = mapped;
     state[SS_UNPLACED] = unplaced;
-    state[SS_CARRY] = (int64_t)h->carry.size();
+    state[SS_CARRY] = (int64_t)front.carry.size();
     return 0;
 }
 
@@ -302,7 +196,7 @@ int clair_host_bamsort_emit(clair_host_bamsort_t *h, int64_t first, int n, int c
         return 0;
     }
     const std::vector<int32_t> in_len(sizes, sizes + n);
-    return deflate_payloads(h->threads, data, n, in_len.data(), out, sizes);
+    return deflate_payloads(h->front.threads, data, n, in_len.data(), out, sizes);
 }
 
 static int twin_begin(void *ctx, int n_ref, const int64_t *ref_len, int64_t memory) { return clair_host_bamsort_begin((clair_host_bamsort_t *)ctx, n_ref, ref_len, memory); }
@@ -352,42 +246,7 @@ int clair_host_bamsort_open(const char *path, clair_host_bamsort_job_t **out) {
     if (!path) return clair_host_fail("bamsort open: NULL argument");
     clair_host_bamsort_job *job = new clair_host_bamsort_job;
     struct Guard { clair_host_bamsort_job *j; ~Guard() { delete j; } } guard{job};
-    job->path = path;
-    job->file = fopen(path, "rb");
-    if (!job->file) return clair_host_fail("%s: cannot open", path);
-    if (fseeko(job->file, 0, SEEK_END) != 0) return clair_host_fail("%s: cannot seek", path);
-    job->file_size = (int64_t)ftello(job->file);
-    uint8_t magic[4] = {0, 0, 0, 0};
-    if (job->file_size < BGZF_HEADER || fseeko(job->file, 0, SEEK_SET) != 0 || fread(magic, 1, 4, job->file) != 4 || !gzip_with_extra(magic))
-        return clair_host_fail("%s is not a BGZF-compressed BAM (SAM text and CRAM are out of scope)", path);
-    std::vector<uint8_t> cbuf;
-    std::vector<std::pair<int64_t, int64_t>> pieces;          // (position in text, coffset)
-    int64_t coffset = 0;
-    const auto need = [&](size_t bytes) -> int {
-        while (job->text.size() < bytes) {
-            if (coffset >= job->file_size) return clair_host_fail("%s: the BAM header is truncated", path);
-            cbuf.clear();
-            uint32_t csize = 0, isize = 0;
-            if (read_block(job->file, path, (uint64_t)job->file_size, (uint64_t)coffset, cbuf, &csize, &isize)) return 1;
-            const size_t at = job->text.size();
-            job->text.resize(at + isize);
-            const int status = inflate_block(cbuf.data(), csize, job->text.data() + at, isize);
-            if (status) return clair_host_fail("%s: BGZF block at compressed offset %lld: %s", path, (long long)coffset, inflate_text(status));
-            pieces.emplace_back((int64_t)at, coffset);
-            coffset += csize;
-        }
-        return 0;
-    };
-    if (parse_bam_header(path, "", need, [&] { return (const uint8_t *)job->text.data(); }, &job->header)) return 1;
-    const size_t at = job->header.end;
-    job->coffset = coffset;
-    job->entry = 0;
-    if (at < job->text.size()) {                             // the first record: in the last header block, or at the start of the block after it
-        size_t k = pieces.size() - 1;
-        while (pieces[k].first > (int64_t)at) --k;
-        job->coffset = pieces[k].second;
-        job->entry = (int64_t)at - pieces[k].first;
-    }
+    if (clair_job::open_job(path, job)) return 1;
     guard.j = nullptr;
     *out = job;
     return 0;

@@ -762,6 +762,76 @@ int clair_bamsort_debug_sort(clair_bamsort_t *h, const uint64_t *keys, int64_t n
 int clair_bamsort_debug_gather(clair_bamsort_t *h, const uint8_t *stream, int64_t stream_bytes, const int64_t *starts, const uint32_t *perm, int64_t n,
                                uint8_t *out, int64_t out_bytes);
 
+/* ---- markdup_bam: duplicate reads flagged (0x400) or removed on the device (csrc/markdup.hip; docs/markdup_bam.md) ----
+ * One handle: one stream, the device buffers of a batch (those of index_bam's batch front), one 32-byte summary per record of the file
+ * (clair_markdup_summary_t), the buffers of the resolution (the radix sort of sort_bam) and the output of the second read.
+ * _begin: a new file with n_ref references; memory: the most bytes the summaries may hold; remove != 0: the second read drops the records
+ *   the rule flagged instead of writing them.
+ * _batch: the first read.  n <= max_blocks whole BGZF blocks, as clair_bamidx_batch takes them: inflated, framed, every record summarised on
+ *   the device (end, name hash, score, bits, index).  Back comes only state (CLAIR_MARKDUP_STATE).
+ * _resolve: the rule over the summaries -> one byte per record on the device, 1: duplicate.  No atomic decides an order: stable radix sorts
+ *   and neighbour comparisons only, so two runs give the same bytes.
+ * _mark: the second read, the same batches in the same order.  Bit 0x400 of every examined record set or cleared where it lies, then the
+ *   batch's records (remove: those kept, compacted) put behind the bytes the batch before left over; info (CLAIR_MARKDUP_INFO).  last == 0:
+ *   the bytes behind the last whole payload of 65280 are kept for the next batch; last != 0: they are a payload of their own.
+ * _emit: payloads [first, first + n) of that buffer, n <= 64, as clair_bamsort_emit hands them out.
+ * _stats: counts [CLAIR_MARKDUP_COUNTS] of the resolution.
+ * _backend: the calls above with the handle, as clair_host_markdup_run takes them.
+ * _debug_summary: the summaries of the n records at `starts` of a raw record stream (every start checked on the host first).
+ * _debug_resolve: the resolution alone over n given summaries -> duplicate [n].
+ * _debug_mark: the second read's kernels alone over n back-to-back records of a raw stream with given summaries and duplicate bytes ->
+ *   patched_stream [stream_bytes] and the records written (remove != 0: compacted) in out, which has room for all n; *out_bytes their
+ *   length.  Guard regions in front of and behind the device's stream and output are checked after the kernels.
+ * Non-zero on failure, message from clair_markdup_last_error (NULL handle: the failure of create).  clair_host_markdup_* (include/clair_host.h)
+ * gives the same bytes on the CPU. */
+typedef struct clair_markdup clair_markdup_t;
+#ifndef CLAIR_MARKDUP_TYPES
+#define CLAIR_MARKDUP_TYPES
+typedef struct clair_markdup_summary {
+    uint64_t end;   /* tid << 33 | (unclipped 5' position + 2^31) << 1 | reverse strand; all ones: the record is not examined */
+    uint64_t hash;  /* FNV-1a (64 bit) of the read name without its NUL */
+    uint32_t score; /* sum of the base qualities >= 15, clamped */
+    uint32_t index; /* of the record in the file */
+    uint32_t bits;  /* 1 examined, 2 can have a mate, 4 read 2 (else read 1), 8 reverse strand */
+    uint32_t pad;
+} clair_markdup_summary_t;
+/* the interface of the stage, as the file driver (clair_host_markdup_run) calls it: the entry points of one backend with its handle */
+typedef struct clair_markdup_backend {
+    void *ctx;
+    int (*begin)(void *ctx, int n_ref, int64_t memory, int remove);
+    int (*batch)(void *ctx, const uint8_t *cdata, int64_t cbytes, int n, const int64_t *in_at, const int32_t *csize, const int32_t *out_len,
+                 const int64_t *coffset, int64_t end_coffset, int64_t entry, int last, int64_t *state);
+    int (*resolve)(void *ctx);
+    int (*mark)(void *ctx, const uint8_t *cdata, int64_t cbytes, int n, const int64_t *in_at, const int32_t *csize, const int32_t *out_len,
+                const int64_t *coffset, int64_t end_coffset, int64_t entry, int last, int64_t *info);
+    int (*emit)(void *ctx, int64_t first, int n, int compressed, uint8_t *out, int32_t *sizes);
+    int (*stats)(void *ctx, int64_t *counts);
+    const char *(*last_error)(const void *ctx);
+} clair_markdup_backend_t;
+#define CLAIR_MARKDUP_STATE 3  /* int64 words of _batch's `state`: records summarised so far, records of this batch, bytes carried over */
+#define CLAIR_MARKDUP_INFO 4   /* of _mark's `info`: bytes in the output buffer, payloads ready for _emit, records of this batch, records written */
+#define CLAIR_MARKDUP_COUNTS 6 /* of _stats: records, examined, pairs, fragments, duplicate pairs, duplicate fragments */
+#define CLAIR_MARKDUP_STATS 9  /* of clair_host_markdup_run: the six counts, duplicate records, records written, bytes appended */
+#endif
+int clair_markdup_create(int device, int max_blocks, int segment_bytes, clair_markdup_t **out);
+void clair_markdup_destroy(clair_markdup_t *h);
+const char *clair_markdup_last_error(const clair_markdup_t *h);
+int clair_markdup_begin(clair_markdup_t *h, int n_ref, int64_t memory, int remove);
+int clair_markdup_batch(clair_markdup_t *h, const uint8_t *cdata, int64_t cbytes, int n, const int64_t *in_at, const int32_t *csize, const int32_t *out_len,
+                        const int64_t *coffset, int64_t end_coffset, int64_t entry, int last, int64_t *state);
+int clair_markdup_resolve(clair_markdup_t *h);
+int clair_markdup_mark(clair_markdup_t *h, const uint8_t *cdata, int64_t cbytes, int n, const int64_t *in_at, const int32_t *csize, const int32_t *out_len,
+                       const int64_t *coffset, int64_t end_coffset, int64_t entry, int last, int64_t *info);
+int clair_markdup_emit(clair_markdup_t *h, int64_t first, int n, int compressed, uint8_t *out, int32_t *sizes);
+int clair_markdup_stats(clair_markdup_t *h, int64_t *counts);
+int clair_markdup_backend(clair_markdup_t *h, clair_markdup_backend_t *out);
+int clair_markdup_debug_summary(clair_markdup_t *h, const uint8_t *stream, int64_t stream_bytes, const int64_t *starts, int64_t n, int n_ref,
+                                clair_markdup_summary_t *out);
+int clair_markdup_debug_resolve(clair_markdup_t *h, const clair_markdup_summary_t *summaries, int64_t n, uint8_t *duplicate);
+int clair_markdup_debug_mark(clair_markdup_t *h, const uint8_t *stream, int64_t stream_bytes, const int64_t *starts, int64_t n,
+                             const clair_markdup_summary_t *summaries, const uint8_t *duplicate, int remove, uint8_t *patched_stream, uint8_t *out,
+                             int64_t *out_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -439,6 +439,66 @@ int clair_host_bamsort_header(const clair_host_bamsort_job_t *job, uint8_t *out,
 int clair_host_bamsort_run(clair_host_bamsort_job_t *job, const clair_bamsort_backend_t *backend, const char *out_path, int deflate, int64_t memory,
                            int max_blocks, int threads, int64_t *stats);
 
+/* -- markdup_bam on the CPU (hostsrc/host_markdup.cpp; docs/markdup_bam.md): the host twin of clair_markdup_* (include/clair_amd.h) with the
+ *    rule of csrc/markdup_core.h, and the file driver both backends run under.
+ *    _create .. _backend, _debug_summary, _debug_resolve: the twin, the same calls with the same arguments and results; blocks are inflated
+ *      by zlib on `threads` threads, the resolution orders by std::stable_sort, `compressed` payloads are compressed by clair_host_deflate_bgzf.
+ *    _open: the BAM header of `path` read and checked -> a job; _header: its bytes as they are in the file; _close.
+ *    _run: two reads of the job's file through a backend: every record summarised, the rule resolved, the records -- flagged, or with
+ *      remove != 0 without the flagged ones -- appended to out_path (which holds the header's blocks already), the EOF marker behind them.
+ *      deflate: 0 the backend's own compressor, 1 zlib level 6, 2 clair_host_deflate_bgzf here.  memory: the most bytes the summaries may
+ *      hold.  stats [CLAIR_MARKDUP_STATS].
+ *    Messages go to clair_host_last_error. */
+typedef struct clair_host_markdup clair_host_markdup_t;
+typedef struct clair_host_markdup_job clair_host_markdup_job_t;
+#ifndef CLAIR_MARKDUP_TYPES
+#define CLAIR_MARKDUP_TYPES
+typedef struct clair_markdup_summary {
+    uint64_t end;   /* tid << 33 | (unclipped 5' position + 2^31) << 1 | reverse strand; all ones: the record is not examined */
+    uint64_t hash;  /* FNV-1a (64 bit) of the read name without its NUL */
+    uint32_t score; /* sum of the base qualities >= 15, clamped */
+    uint32_t index; /* of the record in the file */
+    uint32_t bits;  /* 1 examined, 2 can have a mate, 4 read 2 (else read 1), 8 reverse strand */
+    uint32_t pad;
+} clair_markdup_summary_t;
+/* the interface of the stage, as the file driver (clair_host_markdup_run) calls it: the entry points of one backend with its handle */
+typedef struct clair_markdup_backend {
+    void *ctx;
+    int (*begin)(void *ctx, int n_ref, int64_t memory, int remove);
+    int (*batch)(void *ctx, const uint8_t *cdata, int64_t cbytes, int n, const int64_t *in_at, const int32_t *csize, const int32_t *out_len,
+                 const int64_t *coffset, int64_t end_coffset, int64_t entry, int last, int64_t *state);
+    int (*resolve)(void *ctx);
+    int (*mark)(void *ctx, const uint8_t *cdata, int64_t cbytes, int n, const int64_t *in_at, const int32_t *csize, const int32_t *out_len,
+                const int64_t *coffset, int64_t end_coffset, int64_t entry, int last, int64_t *info);
+    int (*emit)(void *ctx, int64_t first, int n, int compressed, uint8_t *out, int32_t *sizes);
+    int (*stats)(void *ctx, int64_t *counts);
+    const char *(*last_error)(const void *ctx);
+} clair_markdup_backend_t;
+#define CLAIR_MARKDUP_STATE 3  /* int64 words of _batch's `state`: records summarised so far, records of this batch, bytes carried over */
+#define CLAIR_MARKDUP_INFO 4   /* of _mark's `info`: bytes in the output buffer, payloads ready for _emit, records of this batch, records written */
+#define CLAIR_MARKDUP_COUNTS 6 /* of _stats: records, examined, pairs, fragments, duplicate pairs, duplicate fragments */
+#define CLAIR_MARKDUP_STATS 9  /* of clair_host_markdup_run: the six counts, duplicate records, records written, bytes appended */
+#endif
+int clair_host_markdup_create(int threads, int max_blocks, int segment_bytes, clair_host_markdup_t **out);
+void clair_host_markdup_destroy(clair_host_markdup_t *h);
+int clair_host_markdup_begin(clair_host_markdup_t *h, int n_ref, int64_t memory, int remove);
+int clair_host_markdup_batch(clair_host_markdup_t *h, const uint8_t *cdata, int64_t cbytes, int n, const int64_t *in_at, const int32_t *csize,
+                             const int32_t *out_len, const int64_t *coffset, int64_t end_coffset, int64_t entry, int last, int64_t *state);
+int clair_host_markdup_resolve(clair_host_markdup_t *h);
+int clair_host_markdup_mark(clair_host_markdup_t *h, const uint8_t *cdata, int64_t cbytes, int n, const int64_t *in_at, const int32_t *csize,
+                            const int32_t *out_len, const int64_t *coffset, int64_t end_coffset, int64_t entry, int last, int64_t *info);
+int clair_host_markdup_emit(clair_host_markdup_t *h, int64_t first, int n, int compressed, uint8_t *out, int32_t *sizes);
+int clair_host_markdup_stats(clair_host_markdup_t *h, int64_t *counts);
+int clair_host_markdup_backend(clair_host_markdup_t *h, clair_markdup_backend_t *out);
+int clair_host_markdup_debug_summary(const uint8_t *stream, int64_t stream_bytes, const int64_t *starts, int64_t n, int n_ref,
+                                     clair_markdup_summary_t *out);
+int clair_host_markdup_debug_resolve(const clair_markdup_summary_t *summaries, int64_t n, uint8_t *duplicate);
+int clair_host_markdup_open(const char *path, clair_host_markdup_job_t **out);
+void clair_host_markdup_close(clair_host_markdup_job_t *job);
+int clair_host_markdup_header(const clair_host_markdup_job_t *job, uint8_t *out, int64_t cap, int64_t *bytes);
+int clair_host_markdup_run(clair_host_markdup_job_t *job, const clair_markdup_backend_t *backend, const char *out_path, int deflate, int64_t memory,
+                           int max_blocks, int threads, int remove, int64_t *stats);
+
 /* -- gVCF on the CPU (hostsrc/host_gvcf.cpp; docs/gvcf.md): the host twin of clair_frontend_position_tallies / _gvcf_blocks
  *    (include/clair_amd.h) with the rule of csrc/gvcf_core.h, and the block rows' text.
  *    _tally: adds one slab of the host packer (clair_host_sampack_slab) to tallies [n][7] = A C G T I D N of the 0-based positions
