@@ -118,6 +118,9 @@ SIGNATURES = {
     "clair_host_bamidx_result_info": _sig(vp, vp),
     "clair_host_bamidx_result_copy": _sig(vp, vp, vp, vp),
     "clair_host_bamidx_result_free": _sig(vp, restype=None),
+    "clair_host_bam_job_open": _sig(cp, p_vp),
+    "clair_host_bam_job_close": _sig(vp, restype=None),
+    "clair_host_bam_job_header": _sig(vp, vp, i64, p_i64),
     "clair_host_bamsort_create": _sig(i32, i32, i32, p_vp),
     "clair_host_bamsort_destroy": _sig(vp, restype=None),
     "clair_host_bamsort_begin": _sig(vp, i32, vp, i64),
@@ -129,9 +132,6 @@ SIGNATURES = {
     "clair_host_bamsort_backend": _sig(vp, vp),
     "clair_host_bamsort_debug_sort": _sig(vp, i64, vp),
     "clair_host_bamsort_debug_gather": _sig(vp, i64, vp, vp, i64, vp, i64),
-    "clair_host_bamsort_open": _sig(cp, p_vp),
-    "clair_host_bamsort_close": _sig(vp, restype=None),
-    "clair_host_bamsort_header": _sig(vp, vp, i64, p_i64),
     "clair_host_bamsort_run": _sig(vp, vp, cp, i32, i64, i32, i32, vp),
     "clair_host_markdup_create": _sig(i32, i32, i32, p_vp),
     "clair_host_markdup_destroy": _sig(vp, restype=None),
@@ -144,9 +144,6 @@ SIGNATURES = {
     "clair_host_markdup_backend": _sig(vp, vp),
     "clair_host_markdup_debug_summary": _sig(vp, i64, vp, i64, i32, vp),
     "clair_host_markdup_debug_resolve": _sig(vp, i64, vp),
-    "clair_host_markdup_open": _sig(cp, p_vp),
-    "clair_host_markdup_close": _sig(vp, restype=None),
-    "clair_host_markdup_header": _sig(vp, vp, i64, p_i64),
     "clair_host_markdup_run": _sig(vp, vp, cp, i32, i64, i32, i32, i32, vp),
     "clair_host_gvcf_tally": _sig(vp, i64, vp, i64, vp, i64, i64, i64, vp, vp),
     "clair_host_gvcf_blocks": _sig(vp, i64, i64, vp, i64, i64, i32, i32, i32, vp, vp, vp, i64, vp, i64, p_i64),

@@ -37,7 +37,7 @@ def needs_build():
 
 
 HOST_SRCS = [os.path.join(HERE, "hostsrc", f) for f in ("host_io.cpp", "host_decode.cpp", "host_pileup.cpp", "host_sampack.cpp",
-                                                              "host_bam.cpp", "host_inflate.cpp", "host_deflate.cpp", "host_indel.cpp", "host_ensemble.cpp", "host_overlap.cpp", "host_sites.cpp", "host_train_set.cpp", "host_compare.cpp", "host_bam_index.cpp", "host_gvcf.cpp", "host_bam_sort.cpp", "host_markdup.cpp")]
+                                                              "host_bam.cpp", "host_inflate.cpp", "host_deflate.cpp", "host_indel.cpp", "host_ensemble.cpp", "host_overlap.cpp", "host_sites.cpp", "host_train_set.cpp", "host_compare.cpp", "host_bam_index.cpp", "host_gvcf.cpp", "host_bam_job.cpp", "host_bam_sort.cpp", "host_markdup.cpp")]
 HOST_OUT = os.path.join(HERE, "libclair_host.so")
 CXX = os.environ.get("CXX", "g++")
 
@@ -47,8 +47,8 @@ def build_host(force=False):
     # every header a host source includes: clair_call.h is the 32-byte record host_decode.cpp shares bit for bit with the device decode
     hdrs = [os.path.join(HERE, "..", "include", h) for h in ("clair_host.h", "clair_reads.h", "clair_call.h", "clair_amd.h")]
     hdrs.append(os.path.join(HERE, "hostsrc", "sam_line.h"))
-    hdrs.append(os.path.join(HERE, "hostsrc", "bgzf_file.h"))       # BGZF blocks of a file, read and inflated: host_bam.cpp, host_bam_index.cpp
-    hdrs.append(os.path.join(HERE, "hostsrc", "bam_header.h"))      # the BAM header: the same two
+    hdrs.append(os.path.join(HERE, "hostsrc", "bgzf_file.h"))       # BGZF blocks of a file, read and inflated: host_bam.cpp, and bam_frame.h and bam_job.h for the BAM tools
+    hdrs.append(os.path.join(HERE, "hostsrc", "bam_header.h"))      # the BAM header: host_bam.cpp, bam_job.h
     hdrs.append(os.path.join(HERE, "csrc", "bam_record_core.h"))    # the rules of a BAM record they share with the device (csrc/frontend.hip, csrc/bam_index.hip)
     hdrs.append(os.path.join(HERE, "csrc", "inflate_core.h"))       # the decoder host_inflate.cpp shares with the device (csrc/inflate.hip)
     hdrs.append(os.path.join(HERE, "csrc", "deflate_core.h"))       # the compressor host_deflate.cpp shares with the device (csrc/deflate.hip)
@@ -60,7 +60,7 @@ def build_host(force=False):
     hdrs.append(os.path.join(HERE, "csrc", "bam_index_core.h"))     # the framing, field and order rules host_bam_index.cpp shares with the device (csrc/bam_index.hip)
     hdrs.append(os.path.join(HERE, "hostsrc", "bam_frame.h"))       # the front of a batch on the host (inflate, framing, carry): host_bam_index.cpp, host_bam_sort.cpp, host_markdup.cpp
     hdrs.append(os.path.join(HERE, "csrc", "bam_sort_core.h"))      # the key, the bucket and the verdicts host_bam_sort.cpp shares with the device (csrc/bam_sort.hip)
-    hdrs.append(os.path.join(HERE, "hostsrc", "bam_job.h"))         # the input as a job, its batches and the output's blocks: host_bam_sort.cpp, host_markdup.cpp
+    hdrs.append(os.path.join(HERE, "hostsrc", "bam_job.h"))         # the input as a job and its batches: host_bam_index.cpp, host_bam_job.cpp, host_bam_sort.cpp, host_markdup.cpp; the output's blocks: the last two
     hdrs.append(os.path.join(HERE, "csrc", "markdup_core.h"))       # the duplicate rule host_markdup.cpp shares with the device (csrc/markdup.hip)
     hdrs.append(os.path.join(HERE, "csrc", "gvcf_core.h"))          # the reference-confidence rule and the block record host_gvcf.cpp shares with the device (csrc/gvcf.hip)
     hdrs.append(os.path.join(HERE, "csrc", "subsample_core.h"))     # the read-name rule host_bam.cpp shares with the device (csrc/frontend.hip)

@@ -1,4 +1,5 @@
-// The front of a batch for the stages that work on BAM records where they lie on the device (bam_index.hip, bam_sort.hip): the raw BGZF
+// The front of a batch for the stages that work on BAM records where they lie on the device (bam_index.hip, bam_sort.hip, markdup.hip), and
+// what their handles start from (StageHandle: the device, the stream, the message, the front).  The front: the raw BGZF
 // blocks of a batch inflated (inflate_bgzf_kernel) behind the bytes the batch before carried over, into a stream that stays on the device;
 // the records framed there (exits_kernel, chain_kernel, count_kernel, the scan, emit_kernel: bam_index.hip, which defines what is declared
 // here); the table that turns a stream position into a virtual offset; the verdicts of the frame step and the carry to the next batch.
@@ -7,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <string>
 #include <vector>
 
 #include "bam_index_core.h"
@@ -55,6 +57,50 @@ struct Front {
                    const int64_t *coffset, int64_t end_coffset, int64_t entry);
     // the verdicts of the frame step (a size word that cannot be; with `last`, bytes behind the last whole record), then the carry
     int close_batch(const HipFail &fail, int last);
+};
+
+// the arguments every entry point that takes a batch is given, before anything is done with them.  who: "batch", "mark"
+inline int check_batch_args(const HipFail &fail, const char *who, const uint8_t *cdata, int64_t cbytes, int n, const int64_t *in_at, const int32_t *csize,
+                            const int32_t *out_len, const int64_t *coffset, int64_t end_coffset, int64_t entry) {
+    if (n > 0 && (!cdata || !in_at || !csize || !out_len || !coffset)) return fail("%s: NULL argument", who);
+    if (cbytes < 0 || end_coffset < 0 || entry < 0) return fail("%s: negative argument", who);
+    return 0;
+}
+
+// what the handle of a stage starts from (clair_bamidx, clair_bamsort, clair_markdup derive from it)
+struct StageHandle {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    std::string error;
+    Front front;
+
+    // a new handle: the arguments of _create checked, the device set, the stream made.  fail: the stage's, for a handle that is not there
+    // yet; device_only: its sentence for a machine without an MI355X.  A handle that fails here goes through the stage's _destroy
+    int open(const HipFail &fail, int on_device, int max_blocks, int segment_bytes, const char *device_only) {
+        if (max_blocks < 1 || max_blocks > 16384) return fail("max_blocks %d: 1 .. 16384", max_blocks);
+        if (segment_bytes == 0) segment_bytes = (int)SEG_DEFAULT;
+        if (segment_bytes < (int)SEG_MIN || segment_bytes > (int)SEG_MAX || (segment_bytes & (segment_bytes - 1)))
+            return fail("segment_bytes %d: a power of two in %u .. %u, or 0", segment_bytes, SEG_MIN, SEG_MAX);
+        if (hip_device_check(fail, on_device, device_only)) return 1;
+        device = on_device;
+        front.max_blocks = max_blocks;
+        front.seg = (uint32_t)segment_bytes;
+        CLAIR_HIP_TRY(fail, hipSetDevice(device));
+        CLAIR_HIP_TRY(fail, hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        front.stream = stream;
+        return 0;
+    }
+    // the two halves of _destroy, the stage's own buffers freed between them: before the stream goes, not in a destructor
+    void settle() {
+        if (!stream) return;                     // open failed: nothing was enqueued, no buffer is held
+        (void)hipSetDevice(device);
+        (void)hipStreamSynchronize(stream);
+    }
+    void close() {
+        front.reset();
+        if (stream) (void)hipStreamDestroy(stream);
+        stream = nullptr;
+    }
 };
 
 }  // namespace clair_bix

@@ -175,16 +175,11 @@ inline unsigned blocks_of(int64_t n, int per) { return (unsigned)((n + per - 1) 
 
 }  // namespace clair_bix
 
-struct clair_bamidx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string error;
+struct clair_bamidx : clair_bix::StageHandle {
     // the file
     int n_ref = -1;
     std::vector<int64_t> first_window;
     DeviceBuffer d_first_window, d_linear, d_acc;
-    // the stream of a batch and its record starts (bam_front.h)
-    clair_bix::Front front;
     // a batch
     DeviceBuffer d_tid, d_bin, d_beg, d_opens, d_run_scan, d_runs, d_detail;
     std::vector<clair_bamidx_run_t> runs;
@@ -344,37 +339,23 @@ extern "C" {
 const char *clair_bamidx_last_error(const clair_bamidx_t *h) { return h ? h->error.c_str() : g_bix_error.c_str(); }
 
 int clair_bamidx_create(int device, int max_blocks, int segment_bytes, clair_bamidx_t **out) {
-    using namespace clair_bix;
     if (!out) return bix_fail(nullptr)("out is NULL");
     *out = nullptr;
-    if (max_blocks < 1 || max_blocks > 16384) return bix_fail(nullptr)("max_blocks %d: 1 .. 16384", max_blocks);
-    if (segment_bytes == 0) segment_bytes = (int)SEG_DEFAULT;
-    if (segment_bytes < (int)SEG_MIN || segment_bytes > (int)SEG_MAX || (segment_bytes & (segment_bytes - 1)))
-        return bix_fail(nullptr)("segment_bytes %d: a power of two in %u .. %u, or 0", segment_bytes, SEG_MIN, SEG_MAX);
-    if (hip_device_check(bix_fail(nullptr), device, "the device index build runs on an MI355X only (the host one is index_bam --backend host)")) return 1;
     clair_bamidx *h = new clair_bamidx;
-    h->device = device;
-    h->front.max_blocks = max_blocks;
-    h->front.seg = (uint32_t)segment_bytes;
-    const auto open = [&]() -> int {
-        CLAIR_HIP_TRY(bix_fail(nullptr), hipSetDevice(device));
-        CLAIR_HIP_TRY(bix_fail(nullptr), hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        return 0;
-    };
-    if (open()) { clair_bamidx_destroy(h); return 1; }
-    h->front.stream = h->stream;
+    if (h->open(bix_fail(nullptr), device, max_blocks, segment_bytes, "the device index build runs on an MI355X only (the host one is index_bam --backend host)")) {
+        clair_bamidx_destroy(h);
+        return 1;
+    }
     *out = h;
     return 0;
 }
 
 void clair_bamidx_destroy(clair_bamidx_t *h) {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    h->settle();
     for (DeviceBuffer *b : {&h->d_first_window, &h->d_linear, &h->d_acc, &h->d_tid, &h->d_bin, &h->d_beg, &h->d_opens, &h->d_run_scan, &h->d_runs, &h->d_detail})
         b->reset();                              // before the stream goes, not in the destructor
-    h->front.reset();
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    h->close();
     delete h;
 }
 
@@ -409,8 +390,7 @@ int clair_bamidx_batch(clair_bamidx_t *h, const uint8_t *cdata, int64_t cbytes, 
     if (!h) return bix_fail(nullptr)("bamidx handle is NULL");
     if (!state || !runs) return bix_fail(h)("batch: NULL argument");
     if (h->n_ref < 0) return bix_fail(h)("batch: begin first");
-    if (n > 0 && (!cdata || !in_at || !csize || !out_len || !coffset)) return bix_fail(h)("batch: NULL argument");
-    if (cbytes < 0 || end_coffset < 0 || entry < 0) return bix_fail(h)("batch: negative argument");
+    if (check_batch_args(bix_fail(h), "batch", cdata, cbytes, n, in_at, csize, out_len, coffset, end_coffset, entry)) return 1;
     const int n_ref = h->n_ref;
     h->n_ref = -1;                               // a batch that fails leaves a handle that wants begin
     CLAIR_HIP_TRY(bix_fail(h), hipSetDevice(h->device));

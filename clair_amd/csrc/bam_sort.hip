@@ -122,10 +122,7 @@ struct PermLen {
 };
 }  // namespace clair_bsort
 
-struct clair_bamsort {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string error;
+struct clair_bamsort : clair_bix::StageHandle {
     // the file
     int n_ref = -1;
     int64_t memory = 0, n_buckets = 0;
@@ -133,7 +130,6 @@ struct clair_bamsort {
     // the read in progress
     bool in_pass = false, first = false, overflow = false;
     int64_t lo = 0, hi = 0;
-    clair_bix::Front front;
     DeviceBuffer b_key, b_len, b_keep, b_dst, b_scan;
     // the group
     DeviceBuffer d_group, g_key, g_off, g_len;
@@ -141,9 +137,7 @@ struct clair_bamsort {
     // the sort and the gather
     clair_bsort::RadixSort radix;
     DeviceBuffer d_out_off, d_len_scan;
-    // the output
-    DeviceBuffer d_sorted, d_carry, e_meta, e_out;
-    int64_t total = 0, out_carry = 0;
+    clair_bsort::PayloadOut out;                 // the sorted records
     // the debug entries
     DeviceBuffer t_stream, t_starts, t_perm, t_len, t_out, t_keys;
 };
@@ -194,40 +188,26 @@ extern "C" {
 const char *clair_bamsort_last_error(const clair_bamsort_t *h) { return h ? h->error.c_str() : g_bsort_error.c_str(); }
 
 int clair_bamsort_create(int device, int max_blocks, int segment_bytes, clair_bamsort_t **out) {
-    using namespace clair_bix;
     if (!out) return bsort_fail(nullptr)("out is NULL");
     *out = nullptr;
-    if (max_blocks < 1 || max_blocks > 16384) return bsort_fail(nullptr)("max_blocks %d: 1 .. 16384", max_blocks);
-    if (segment_bytes == 0) segment_bytes = (int)SEG_DEFAULT;
-    if (segment_bytes < (int)SEG_MIN || segment_bytes > (int)SEG_MAX || (segment_bytes & (segment_bytes - 1)))
-        return bsort_fail(nullptr)("segment_bytes %d: a power of two in %u .. %u, or 0", segment_bytes, SEG_MIN, SEG_MAX);
-    if (hip_device_check(bsort_fail(nullptr), device, "the device sort runs on an MI355X only (the host one is sort_bam --backend host)")) return 1;
     clair_bamsort *h = new clair_bamsort;
-    h->device = device;
-    h->front.max_blocks = max_blocks;
-    h->front.seg = (uint32_t)segment_bytes;
-    const auto open = [&]() -> int {
-        CLAIR_HIP_TRY(bsort_fail(nullptr), hipSetDevice(device));
-        CLAIR_HIP_TRY(bsort_fail(nullptr), hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        return 0;
-    };
-    if (open()) { clair_bamsort_destroy(h); return 1; }
-    h->front.stream = h->stream;
+    if (h->open(bsort_fail(nullptr), device, max_blocks, segment_bytes, "the device sort runs on an MI355X only (the host one is sort_bam --backend host)")) {
+        clair_bamsort_destroy(h);
+        return 1;
+    }
     *out = h;
     return 0;
 }
 
 void clair_bamsort_destroy(clair_bamsort_t *h) {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    h->settle();
     for (DeviceBuffer *b : {&h->d_refs, &h->d_hist, &h->d_acc, &h->b_key, &h->b_len, &h->b_keep, &h->b_dst, &h->b_scan, &h->d_group, &h->g_key, &h->g_off, &h->g_len,
-                            &h->d_out_off, &h->d_len_scan,
-                            &h->d_sorted, &h->d_carry, &h->e_meta, &h->e_out, &h->t_stream, &h->t_starts, &h->t_perm, &h->t_len, &h->t_out, &h->t_keys})
+                            &h->d_out_off, &h->d_len_scan, &h->t_stream, &h->t_starts, &h->t_perm, &h->t_len, &h->t_out, &h->t_keys})
         b->reset();                              // before the stream goes, not in the destructor
+    h->out.reset();
     h->radix.reset();
-    h->front.reset();
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    h->close();
     delete h;
 }
 
@@ -252,7 +232,7 @@ int clair_bamsort_begin(clair_bamsort_t *h, int n_ref, const int64_t *ref_len, i
     CLAIR_HIP_TRY(bsort_fail(h), hipMemsetAsync(h->d_hist.p, 0, (size_t)h->n_buckets * 8, h->stream));
     CLAIR_HIP_TRY(bsort_fail(h), hipStreamSynchronize(h->stream));
     h->memory = memory;
-    h->total = h->out_carry = 0;
+    h->out.rewind();
     h->g_n = h->g_bytes = 0;
     h->n_ref = n_ref;
     return 0;
@@ -280,8 +260,7 @@ int clair_bamsort_batch(clair_bamsort_t *h, const uint8_t *cdata, int64_t cbytes
     if (!h) return bsort_fail(nullptr)("bamsort handle is NULL");
     if (!state) return bsort_fail(h)("batch: NULL argument");
     if (h->n_ref < 0 || !h->in_pass) return bsort_fail(h)("batch: begin and pass first");
-    if (n > 0 && (!cdata || !in_at || !csize || !out_len || !coffset)) return bsort_fail(h)("batch: NULL argument");
-    if (cbytes < 0 || end_coffset < 0 || entry < 0) return bsort_fail(h)("batch: negative argument");
+    if (check_batch_args(bsort_fail(h), "batch", cdata, cbytes, n, in_at, csize, out_len, coffset, end_coffset, entry)) return 1;
     h->in_pass = false;                          // a batch that fails leaves a handle that wants a new pass
     CLAIR_HIP_TRY(bsort_fail(h), hipSetDevice(h->device));
     // 1, 2. the stream and the record starts (bam_front.h)
@@ -386,25 +365,19 @@ int clair_bamsort_sort(clair_bamsort_t *h, int last, int64_t *info) {
     if (!info || h->n_ref < 0 || !h->in_pass) return bsort_fail(h)("sort: no read of the input is open, or info is NULL");
     h->in_pass = false;
     CLAIR_HIP_TRY(bsort_fail(h), hipSetDevice(h->device));
-    const int64_t n = h->g_n, carry = h->out_carry, total = carry + h->g_bytes;
-    CLAIR_HIP_TRY(bsort_fail(h), at_least(h->d_sorted, (size_t)(total + PAD)));
-    CLAIR_HIP_TRY(bsort_fail(h), at_least(h->d_carry, (size_t)(PAYLOAD + PAD)));
-    uint8_t *d_sorted = h->d_sorted.as<uint8_t>();
-    if (carry) CLAIR_HIP_TRY(bsort_fail(h), hipMemcpyAsync(d_sorted, h->d_carry.p, (size_t)carry, hipMemcpyDeviceToDevice, h->stream));
+    const int64_t n = h->g_n;
+    uint8_t *d_sorted = nullptr;                 // behind what the group before carried over
+    if (h->out.begin(bsort_fail(h), h->stream, h->g_bytes, &d_sorted)) return 1;
     int passes = 0;
     if (n > 0) {
         const uint32_t *perm = nullptr;
         if (radix_sort(h, h->g_key.as<uint64_t>(), n, &perm, &passes)) return 1;
-        if (gather(h, h->d_group.as<uint8_t>(), h->g_off.as<int64_t>(), perm, h->g_len.as<uint32_t>(), n, d_sorted + carry)) return 1;
+        if (gather(h, h->d_group.as<uint8_t>(), h->g_off.as<int64_t>(), perm, h->g_len.as<uint32_t>(), n, d_sorted)) return 1;
     }
-    CLAIR_HIP_TRY(bsort_fail(h), hipMemsetAsync(d_sorted + total, 0, (size_t)PAD, h->stream));
-    const int64_t payloads = payloads_of(total, last != 0), rest = total - std::min(total, payloads * PAYLOAD);
-    if (rest) CLAIR_HIP_TRY(bsort_fail(h), hipMemcpyAsync(h->d_carry.p, d_sorted + payloads * PAYLOAD, (size_t)rest, hipMemcpyDeviceToDevice, h->stream));
-    CLAIR_HIP_TRY(bsort_fail(h), hipStreamSynchronize(h->stream));
-    h->total = total;
-    h->out_carry = rest;
+    int64_t payloads = 0;
+    if (h->out.cut(bsort_fail(h), h->stream, h->g_bytes, last != 0, &payloads)) return 1;
     h->g_n = h->g_bytes = 0;
-    info[SI_BYTES] = total;
+    info[SI_BYTES] = h->out.total;
     info[SI_PAYLOADS] = payloads;
     info[SI_RECORDS] = n;
     info[SI_PASSES] = passes;
@@ -414,7 +387,7 @@ int clair_bamsort_sort(clair_bamsort_t *h, int last, int64_t *info) {
 int clair_bamsort_emit(clair_bamsort_t *h, int64_t first, int n, int compressed, uint8_t *out, int32_t *sizes) {
     if (!h) return bsort_fail(nullptr)("bamsort handle is NULL");
     CLAIR_HIP_TRY(bsort_fail(h), hipSetDevice(h->device));
-    return emit_payloads(bsort_fail(h), h->stream, h->d_sorted.as<uint8_t>(), h->total, first, n, compressed, out, sizes, h->e_meta, h->e_out);
+    return h->out.emit(bsort_fail(h), h->stream, first, n, compressed, out, sizes);
 }
 
 static int bsort_begin(void *ctx, int n_ref, const int64_t *ref_len, int64_t memory) { return clair_bamsort_begin((clair_bamsort_t *)ctx, n_ref, ref_len, memory); }

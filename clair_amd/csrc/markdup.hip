@@ -207,10 +207,7 @@ struct WritePlace {                              // dst[i]: where a kept record'
 
 }  // namespace clair_md
 
-struct clair_markdup {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string error;
+struct clair_markdup : clair_bix::StageHandle {
     // the file
     int n_ref = -1;
     int64_t memory = 0, n_records = 0, marked = 0;
@@ -218,14 +215,11 @@ struct clair_markdup {
     int64_t counts[clair_md::MC_WORDS] = {0};
     DeviceBuffer d_summaries, d_dup, d_acc;
     // the batch
-    clair_bix::Front front;
     DeviceBuffer b_qual, b_lseq, b_len, b_keep, b_dst, b_scan;
     // the resolution
     clair_bsort::RadixSort radix;
     DeviceBuffer r_keys, r_order[2], r_mate;
-    // the output
-    DeviceBuffer d_out, d_carry, e_meta, e_out;
-    int64_t total = 0, out_carry = 0;
+    clair_bsort::PayloadOut out;                 // the records of the second read
     // the debug entries
     DeviceBuffer t_stream, t_starts, t_out;
 };
@@ -372,39 +366,26 @@ extern "C" {
 const char *clair_markdup_last_error(const clair_markdup_t *h) { return h ? h->error.c_str() : g_md_error.c_str(); }
 
 int clair_markdup_create(int device, int max_blocks, int segment_bytes, clair_markdup_t **out) {
-    using namespace clair_bix;
     if (!out) return md_fail(nullptr)("out is NULL");
     *out = nullptr;
-    if (max_blocks < 1 || max_blocks > 16384) return md_fail(nullptr)("max_blocks %d: 1 .. 16384", max_blocks);
-    if (segment_bytes == 0) segment_bytes = (int)SEG_DEFAULT;
-    if (segment_bytes < (int)SEG_MIN || segment_bytes > (int)SEG_MAX || (segment_bytes & (segment_bytes - 1)))
-        return md_fail(nullptr)("segment_bytes %d: a power of two in %u .. %u, or 0", segment_bytes, SEG_MIN, SEG_MAX);
-    if (hip_device_check(md_fail(nullptr), device, "the device duplicate marking runs on an MI355X only (the host one is markdup_bam --backend host)")) return 1;
     clair_markdup *h = new clair_markdup;
-    h->device = device;
-    h->front.max_blocks = max_blocks;
-    h->front.seg = (uint32_t)segment_bytes;
-    const auto open = [&]() -> int {
-        CLAIR_HIP_TRY(md_fail(nullptr), hipSetDevice(device));
-        CLAIR_HIP_TRY(md_fail(nullptr), hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        return 0;
-    };
-    if (open()) { clair_markdup_destroy(h); return 1; }
-    h->front.stream = h->stream;
+    if (h->open(md_fail(nullptr), device, max_blocks, segment_bytes, "the device duplicate marking runs on an MI355X only (the host one is markdup_bam --backend host)")) {
+        clair_markdup_destroy(h);
+        return 1;
+    }
     *out = h;
     return 0;
 }
 
 void clair_markdup_destroy(clair_markdup_t *h) {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    h->settle();
     for (DeviceBuffer *b : {&h->d_summaries, &h->d_dup, &h->d_acc, &h->b_qual, &h->b_lseq, &h->b_len, &h->b_keep, &h->b_dst, &h->b_scan, &h->r_keys, &h->r_order[0],
-                            &h->r_order[1], &h->r_mate, &h->d_out, &h->d_carry, &h->e_meta, &h->e_out, &h->t_stream, &h->t_starts, &h->t_out})
+                            &h->r_order[1], &h->r_mate, &h->t_stream, &h->t_starts, &h->t_out})
         b->reset();                              // before the stream goes, not in the destructor
+    h->out.reset();
     h->radix.reset();
-    h->front.reset();
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    h->close();
     delete h;
 }
 
@@ -418,7 +399,8 @@ int clair_markdup_begin(clair_markdup_t *h, int n_ref, int64_t memory, int remov
     h->memory = memory;
     h->remove = remove != 0;
     h->resolved = false;
-    h->n_records = h->marked = h->total = h->out_carry = 0;
+    h->n_records = h->marked = 0;
+    h->out.rewind();
     h->front.rewind();
     return 0;
 }
@@ -429,8 +411,7 @@ int clair_markdup_batch(clair_markdup_t *h, const uint8_t *cdata, int64_t cbytes
     if (!h) return md_fail(nullptr)("markdup handle is NULL");
     if (!state) return md_fail(h)("batch: NULL argument");
     if (h->n_ref < 0 || h->resolved) return md_fail(h)("batch: begin first");
-    if (n > 0 && (!cdata || !in_at || !csize || !out_len || !coffset)) return md_fail(h)("batch: NULL argument");
-    if (cbytes < 0 || end_coffset < 0 || entry < 0) return md_fail(h)("batch: negative argument");
+    if (check_batch_args(md_fail(h), "batch", cdata, cbytes, n, in_at, csize, out_len, coffset, end_coffset, entry)) return 1;
     CLAIR_HIP_TRY(md_fail(h), hipSetDevice(h->device));
     Front &front = h->front;
     if (front.open_batch(md_fail(h), cdata, cbytes, n, in_at, csize, out_len, coffset, end_coffset, entry)) { h->n_ref = -1; return 1; }
@@ -466,7 +447,8 @@ int clair_markdup_resolve(clair_markdup_t *h) {
         if (resolve(h, h->d_summaries.as<Summary>(), h->n_records, h->d_dup.as<uint8_t>(), h->counts)) return 1;
     }
     h->resolved = true;
-    h->marked = h->total = h->out_carry = 0;
+    h->marked = 0;
+    h->out.rewind();
     h->front.rewind();
     return 0;
 }
@@ -477,37 +459,29 @@ int clair_markdup_mark(clair_markdup_t *h, const uint8_t *cdata, int64_t cbytes,
     if (!h) return md_fail(nullptr)("markdup handle is NULL");
     if (!info) return md_fail(h)("mark: NULL argument");
     if (h->n_ref < 0 || !h->resolved) return md_fail(h)("mark: resolve first");
-    if (n > 0 && (!cdata || !in_at || !csize || !out_len || !coffset)) return md_fail(h)("mark: NULL argument");
-    if (cbytes < 0 || end_coffset < 0 || entry < 0) return md_fail(h)("mark: negative argument");
+    if (check_batch_args(md_fail(h), "mark", cdata, cbytes, n, in_at, csize, out_len, coffset, end_coffset, entry)) return 1;
     CLAIR_HIP_TRY(md_fail(h), hipSetDevice(h->device));
     Front &front = h->front;
     const auto refuse = [&](int rc) { h->n_ref = -1; return rc; };
     if (front.open_batch(md_fail(h), cdata, cbytes, n, in_at, csize, out_len, coffset, end_coffset, entry)) return refuse(1);
-    const int64_t n_rec = front.fr.n_rec, carry = h->out_carry;
+    const int64_t n_rec = front.fr.n_rec;
     if (h->marked + n_rec > h->n_records)
         return refuse(md_fail(h)("the second read finds more than the %lld records of the first: the file changed", (long long)h->n_records));
     const int64_t range = n_rec > 0 ? front.fr.tail - entry : 0;
     if (range < 0 || entry + range > front.len) return refuse(md_fail(h)("mark: records [%lld, %lld) of %lld bytes: the frame pass is broken", (long long)entry, (long long)front.fr.tail, (long long)front.len));
-    CLAIR_HIP_TRY(md_fail(h), at_least(h->d_out, (size_t)(carry + range + PAD)));
-    CLAIR_HIP_TRY(md_fail(h), at_least(h->d_carry, (size_t)(PAYLOAD + PAD)));
-    uint8_t *d_out = h->d_out.as<uint8_t>();
-    if (carry) CLAIR_HIP_TRY(md_fail(h), hipMemcpyAsync(d_out, h->d_carry.p, (size_t)carry, hipMemcpyDeviceToDevice, h->stream));
+    uint8_t *d_out = nullptr;                    // behind what the batch before carried over
+    if (h->out.begin(md_fail(h), h->stream, range, &d_out)) return 1;
     int64_t bytes = 0, written = 0;
     if (n_rec > 0 && patch_and_place(h, front.bytes, front.starts(), n_rec, h->d_summaries.as<Summary>() + h->marked, h->d_dup.as<uint8_t>() + h->marked, h->remove, entry,
-                                     range, d_out + carry, &bytes, &written))
+                                     range, d_out, &bytes, &written))
         return refuse(1);
     if (front.close_batch(md_fail(h), last)) return refuse(1);
     h->marked += n_rec;
     if (last && h->marked != h->n_records)
         return refuse(md_fail(h)("the second read finds %lld records, the first found %lld: the file changed", (long long)h->marked, (long long)h->n_records));
-    const int64_t total = carry + bytes;
-    CLAIR_HIP_TRY(md_fail(h), hipMemsetAsync(d_out + total, 0, (size_t)PAD, h->stream));
-    const int64_t payloads = payloads_of(total, last != 0), rest = total - std::min(total, payloads * PAYLOAD);
-    if (rest) CLAIR_HIP_TRY(md_fail(h), hipMemcpyAsync(h->d_carry.p, d_out + payloads * PAYLOAD, (size_t)rest, hipMemcpyDeviceToDevice, h->stream));
-    CLAIR_HIP_TRY(md_fail(h), hipStreamSynchronize(h->stream));
-    h->total = total;
-    h->out_carry = rest;
-    info[MI_BYTES] = total;
+    int64_t payloads = 0;
+    if (h->out.cut(md_fail(h), h->stream, bytes, last != 0, &payloads)) return 1;
+    info[MI_BYTES] = h->out.total;
     info[MI_PAYLOADS] = payloads;
     info[MI_RECORDS] = n_rec;
     info[MI_WRITTEN] = written;
@@ -517,7 +491,7 @@ int clair_markdup_mark(clair_markdup_t *h, const uint8_t *cdata, int64_t cbytes,
 int clair_markdup_emit(clair_markdup_t *h, int64_t first, int n, int compressed, uint8_t *out, int32_t *sizes) {
     if (!h) return md_fail(nullptr)("markdup handle is NULL");
     CLAIR_HIP_TRY(md_fail(h), hipSetDevice(h->device));
-    return clair_bsort::emit_payloads(md_fail(h), h->stream, h->d_out.as<uint8_t>(), h->total, first, n, compressed, out, sizes, h->e_meta, h->e_out);
+    return h->out.emit(md_fail(h), h->stream, first, n, compressed, out, sizes);
 }
 
 int clair_markdup_stats(clair_markdup_t *h, int64_t *counts) {

@@ -1,5 +1,6 @@
 // What the stages that order BAM records on the device share (bam_sort.hip, markdup.hip): the stable radix sort over 64-bit keys, the scan
-// policy that counts kept records and their bytes, and the unaligned wave-per-record copy.  Device translation units only; the kernels have
+// policy that counts kept records and their bytes, the unaligned wave-per-record copy, and (host side) the output cut into payloads
+// (PayloadOut, emit_payloads).  Device translation units only; the kernels have
 // internal linkage, so that every translation unit that includes this header carries its own.
 //
 //   the radix sort   stable, least significant digit first, 8 bits a pass over (key, uint32 index) pairs in ping-pong buffers.
@@ -225,6 +226,44 @@ inline int emit_payloads(const HipFail &fail, hipStream_t stream, const uint8_t 
         if (sizes[i] < 26 || sizes[i] > SLOT) return fail("payload %lld: the kernel reports %d bytes", (long long)(first + i), sizes[i]);
     return 0;
 }
+
+// the output of a stage that writes records: the bytes it has for the file on the device, cut into payloads; what no whole payload takes
+// is carried to the front of the next bytes.  Owned by a stage's handle, freed (reset) before the handle's stream goes.  Everything is
+// enqueued on `stream`; cut waits for it.
+struct PayloadOut {
+    DeviceBuffer d_bytes, d_carry, e_meta, e_out;
+    int64_t total = 0, carry = 0;
+
+    void rewind() { total = carry = 0; }         // a new file
+    void reset() {
+        for (DeviceBuffer *b : {&d_bytes, &d_carry, &e_meta, &e_out}) b->reset();
+    }
+    uint8_t *data() const { return d_bytes.as<uint8_t>(); }
+    // room for the carried bytes, `bytes` more and PAD; the carried bytes put in front -> *at: where the new ones go
+    int begin(const HipFail &fail, hipStream_t stream, int64_t bytes, uint8_t **at) {
+        CLAIR_HIP_TRY(fail, clair_bix::at_least(d_bytes, (size_t)(carry + bytes + clair_bix::PAD)));
+        CLAIR_HIP_TRY(fail, clair_bix::at_least(d_carry, (size_t)(PAYLOAD + clair_bix::PAD)));
+        if (carry) CLAIR_HIP_TRY(fail, hipMemcpyAsync(d_bytes.p, d_carry.p, (size_t)carry, hipMemcpyDeviceToDevice, stream));
+        *at = data() + carry;
+        return 0;
+    }
+    // `added` bytes were put behind the carried ones: PAD zeroed behind them, -> *payloads ready for emit (with `last` the partial one
+    // too), the rest carried
+    int cut(const HipFail &fail, hipStream_t stream, int64_t added, bool last, int64_t *payloads) {
+        const int64_t all = carry + added;
+        CLAIR_HIP_TRY(fail, hipMemsetAsync(data() + all, 0, (size_t)clair_bix::PAD, stream));
+        *payloads = payloads_of(all, last);
+        const int64_t rest = all - std::min(all, *payloads * PAYLOAD);
+        if (rest) CLAIR_HIP_TRY(fail, hipMemcpyAsync(d_carry.p, data() + *payloads * PAYLOAD, (size_t)rest, hipMemcpyDeviceToDevice, stream));
+        CLAIR_HIP_TRY(fail, hipStreamSynchronize(stream));
+        total = all;
+        carry = rest;
+        return 0;
+    }
+    int emit(const HipFail &fail, hipStream_t stream, int64_t first, int n, int compressed, uint8_t *out, int32_t *sizes) {
+        return emit_payloads(fail, stream, data(), total, first, n, compressed, out, sizes, e_meta, e_out);
+    }
+};
 
 // the sort's buffers and its driver: owned by a stage's handle, freed (reset) before the handle's stream goes
 struct RadixSort {

@@ -54,6 +54,11 @@ inline bool good_segment(int segment_bytes) {
     return segment_bytes >= (int)SEG_MIN && segment_bytes <= (int)SEG_MAX && (segment_bytes & (segment_bytes - 1)) == 0;
 }
 
+// the BGZF blocks of a batch: of a handle, and of the file driver that feeds it
+inline int check_max_blocks(int max_blocks) {
+    return max_blocks < 1 || max_blocks > 16384 ? clair_host_fail("max_blocks %d: 1 .. 16384", max_blocks) : 0;
+}
+
 // ---- the front of a batch on the host, what clair_bix::Front (csrc/bam_front.h) is on the device: the blocks of a batch inflated behind the
 // bytes the batch before carried over, the records framed there, the table that turns a stream position into a virtual offset, the verdicts
 // of the frame step and the carry to the next batch.  `who` names the stage in the messages ("bamsort batch").
@@ -68,6 +73,16 @@ struct HostFront {
     int64_t len = 0, tail = 0;
     bool bad = false;
 
+    // what every _create takes, checked; segment_bytes 0: the sequential walk
+    int configure(int n_threads, int blocks, int segment_bytes) {
+        if (n_threads < 1 || n_threads > 16) return clair_host_fail("BAM threads: %d (1 .. 16)", n_threads);
+        if (check_max_blocks(blocks)) return 1;
+        if (segment_bytes != 0 && !good_segment(segment_bytes)) return clair_host_fail("segment_bytes %d: a power of two in %u .. %u, or 0", segment_bytes, SEG_MIN, SEG_MAX);
+        threads = n_threads;
+        max_blocks = blocks;
+        seg = (uint32_t)segment_bytes;
+        return 0;
+    }
     void rewind() { carry.clear(); carry_voff = 0; }         // a new file, or a new read of one
     uint64_t voffset(int64_t p) const { return voffset_at(at.data(), voff.data(), (int)at.size(), p); }
 

@@ -1,6 +1,8 @@
-// What the file drivers that rewrite a BAM share (host_bam_sort.cpp, host_markdup.cpp): the input as a job -- the file opened, its header
-// read and checked, where the first record lies --, the batches of whole BGZF blocks a read of the input is made of, and the payloads of
-// 65280 bytes compressed into the blocks of the output.  Host only: plain C++17 + zlib.
+// What the file drivers of the BAM tools share.  All three (host_bam_index.cpp, host_bam_sort.cpp, host_markdup.cpp): the input as a job --
+// the file opened, its header read and checked, where the first record lies -- and the batches of whole BGZF blocks a read of the input is
+// made of.  The two that rewrite a BAM (host_bam_sort.cpp, host_markdup.cpp; the job's entry points are host_bam_job.cpp): the twin's output
+// stream cut into payloads of 65280 bytes, the payloads handed out, compressed into the blocks of the output and written, the EOF marker
+// behind them.  Host only: plain C++17 + zlib.
 #pragma once
 #include "../../include/clair_host.h"
 #include "../csrc/bam_sort_core.h"
@@ -15,24 +17,26 @@
 #include <utility>
 #include <vector>
 
-namespace clair_job {
-
-using namespace clair_bgzf;
-using clair_bsort::PAYLOAD;
-using clair_bsort::SLOT;
-
-struct Job {
+// the job: clair_host_bam_job_t of include/clair_host.h
+struct clair_host_bam_job {
     std::string path;
     FILE *file = nullptr;
     int64_t file_size = 0;
     std::vector<uint8_t> text;                   // the inflated header, and what follows it in its last block
     BamHeader header;
     int64_t coffset = 0, entry = 0;              // where the first record's block starts, the record's offset in it
-    ~Job() { if (file) fclose(file); }
+    ~clair_host_bam_job() { if (file) fclose(file); }
 };
 
-// the BAM header of `path` read and checked into *job (empty); -> 0, or the message set
-inline int open_job(const char *path, Job *job) {
+namespace clair_job {
+
+using namespace clair_bgzf;
+using clair_bsort::PAYLOAD;
+using clair_bsort::SLOT;
+using Job = ::clair_host_bam_job;
+
+// the BAM header of `path` read and checked into *job (empty); -> 0, or the message set.  kinds: the sentence about files that are no BAM
+inline int open_job(const char *path, const char *kinds, Job *job) {
     job->path = path;
     job->file = fopen(path, "rb");
     if (!job->file) return clair_host_fail("%s: cannot open", path);
@@ -40,7 +44,7 @@ inline int open_job(const char *path, Job *job) {
     job->file_size = (int64_t)ftello(job->file);
     uint8_t magic[4] = {0, 0, 0, 0};
     if (job->file_size < BGZF_HEADER || fseeko(job->file, 0, SEEK_SET) != 0 || fread(magic, 1, 4, job->file) != 4 || !gzip_with_extra(magic))
-        return clair_host_fail("%s is not a BGZF-compressed BAM (SAM text and CRAM are out of scope)", path);
+        return clair_host_fail("%s is not a BGZF-compressed BAM %s", path, kinds);
     std::vector<uint8_t> cbuf;
     std::vector<std::pair<int64_t, int64_t>> pieces;          // (position in text, coffset)
     int64_t coffset = 0;
@@ -82,7 +86,7 @@ struct Batches {
     std::vector<int32_t> csizes, out_lens;
     bool last = false;
     Batches(const Job *j, int blocks) : job(j), max_blocks(blocks), coffset(j->coffset), entry(j->entry) {}
-    // the next batch (its record chain starts at `entry`; set it to 0 once the batch is through); `last` with the file's last block
+    // the next batch (its record chain starts at `entry`: 0 once a batch went `through`); `last` with the file's last block
     int next() {
         cbuf.clear(); in_at.clear(); offs.clear(); csizes.clear(); out_lens.clear();
         while ((int)offs.size() < max_blocks && coffset < job->file_size) {
@@ -97,6 +101,13 @@ struct Batches {
         }
         last = coffset >= job->file_size;
         return 0;
+    }
+    // the batch through a backend's entry point (batch, mark), `more` behind the arguments every one of them takes; then on to the next batch
+    template <class Fn, class... More> int through(Fn fn, void *ctx, More... more) {
+        const int rc = fn(ctx, cbuf.data(), (int64_t)cbuf.size(), (int)offs.size(), in_at.data(), csizes.data(), out_lens.data(), offs.data(), coffset, entry,
+                          last ? 1 : 0, more...);
+        entry = 0;
+        return rc;
     }
 };
 
@@ -165,5 +176,73 @@ inline int write_payloads(FILE *out, const char *path, const char *out_path, int
     }
     return 0;
 }
+
+// ---- the output of a twin: the bytes it has for the file, cut into payloads; what no whole payload takes waits for the next bytes
+struct OutStream {
+    std::vector<uint8_t> bytes, carry;
+    int64_t total = 0;
+    void rewind() { carry.clear(); total = 0; }              // a new file
+    void begin() { bytes.assign(carry.begin(), carry.end()); }                        // new bytes go behind what was carried over
+    // -> the payloads ready (with `last` the partial one too); the rest is carried
+    int64_t cut(bool last) {
+        total = (int64_t)bytes.size();
+        const int64_t payloads = clair_bsort::payloads_of(total, last);
+        carry.assign(bytes.begin() + (ptrdiff_t)std::min(total, payloads * PAYLOAD), bytes.end());
+        return payloads;
+    }
+};
+
+// payloads [first, first + n) of the `total` bytes at data -> out: packed as they are, or (compressed) a BGZF block each in its slot; sizes [n]
+inline int emit_payloads(const uint8_t *data, int64_t total, int threads, int64_t first, int n, int compressed, uint8_t *out, int32_t *sizes, const char *who) {
+    if (!out || !sizes || first < 0 || n < 0) return clair_host_fail("%s emit: bad arguments", who);
+    if ((first + n - 1) * PAYLOAD >= total && n > 0) return clair_host_fail("%s emit: payloads [%lld, +%d) of %lld bytes", who, (long long)first, n, (long long)total);
+    for (int i = 0; i < n; ++i) sizes[i] = (int32_t)std::min(PAYLOAD, total - (first + i) * PAYLOAD);
+    data += first * PAYLOAD;
+    if (!compressed) {
+        if (n) memcpy(out, data, (size_t)((int64_t)(n - 1) * PAYLOAD + sizes[n - 1]));
+        return 0;
+    }
+    const std::vector<int32_t> in_len(sizes, sizes + n);
+    return deflate_payloads(threads, data, n, in_len.data(), out, sizes);
+}
+
+// ---- the output file of a driver: it holds the header's blocks already; the payloads a backend has ready are appended EMIT at a time
+// through the compressor the caller chose (write_payloads), the EOF marker behind the last
+struct Writer {
+    static constexpr int EMIT = 64;                          // payloads per emit
+    const char *path = nullptr, *out_path = nullptr;         // the input (it names the messages about blocks), the output
+    int deflate = 0, threads = 1;
+    FILE *file = nullptr;
+    int64_t written = 0;
+    std::vector<uint8_t> slots, raw;
+    std::vector<int32_t> sizes;
+    ~Writer() { if (file) fclose(file); }
+    int open(const char *in_path, const char *to, int deflate_mode, int n_threads) {
+        path = in_path; out_path = to; deflate = deflate_mode; threads = n_threads;
+        file = fopen(out_path, "ab");
+        if (!file) return clair_host_fail("%s: cannot write", out_path);
+        slots.resize((size_t)EMIT * SLOT);
+        raw.resize(deflate ? (size_t)EMIT * PAYLOAD : 1);
+        sizes.resize((size_t)EMIT);
+        return 0;
+    }
+    // emit: the backend's, with its handle; failed(): the driver's message from the backend's, -> nonzero
+    template <class Emit, class Failed> int payloads(int64_t n_payloads, Emit emit, void *ctx, Failed failed) {
+        for (int64_t at = 0; at < n_payloads; at += EMIT) {
+            const int n = (int)std::min<int64_t>(EMIT, n_payloads - at);
+            if (emit(ctx, at, n, deflate == 0 ? 1 : 0, deflate == 0 ? slots.data() : raw.data(), sizes.data())) return failed();
+            if (write_payloads(file, path, out_path, deflate, threads, n, raw.data(), slots.data(), sizes.data(), &written)) return 1;
+        }
+        return 0;
+    }
+    int finish() {
+        if (fwrite(BGZF_EOF, 1, sizeof BGZF_EOF, file) != sizeof BGZF_EOF) return clair_host_fail("%s: write failed", out_path);
+        written += (int64_t)sizeof BGZF_EOF;
+        FILE *f = file;
+        file = nullptr;
+        if (fclose(f) != 0) return clair_host_fail("%s: write failed", out_path);
+        return 0;
+    }
+};
 
 }  // namespace clair_job

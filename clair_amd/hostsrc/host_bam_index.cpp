@@ -2,14 +2,14 @@
 //   - the host twin of csrc/bam_index.hip: the same batch interface and the rules of csrc/bam_index_core.h as sequential loops.  Blocks are
 //     inflated by zlib on a few threads (hostsrc/bgzf_file.h); records are framed by the plain walk, or by the restatement of the segmented
 //     framing the device runs (hostsrc/bam_frame.h, shared with host_bam_sort.cpp);
-//   - the file driver both backends run under: the BAM header (hostsrc/bam_header.h), block after block of the file (hostsrc/bgzf_file.h) in
-//     batches of max_blocks, the runs joined across batches;
+//   - the file driver both backends run under: the input as a job and its batches of max_blocks blocks (hostsrc/bam_job.h), the runs joined
+//     across batches;
 //   - the result the Python side writes the .bai from (clair_amd/index_bam.py).
 // Plain C++17 + zlib, no HIP.
 #include "../../include/clair_host.h"
 #include "../csrc/bam_index_core.h"
 #include "bam_frame.h"
-#include "bam_header.h"
+#include "bam_job.h"
 
 #include <algorithm>
 #include <climits>
@@ -47,13 +47,8 @@ extern "C" {
 int clair_host_bamidx_create(int threads, int max_blocks, int segment_bytes, clair_host_bamidx_t **out) {
     if (!out) return clair_host_fail("out is NULL");
     *out = nullptr;
-    if (threads < 1 || threads > 16) return clair_host_fail("BAM threads: %d (1 .. 16)", threads);
-    if (max_blocks < 1 || max_blocks > 16384) return clair_host_fail("max_blocks %d: 1 .. 16384", max_blocks);
-    if (segment_bytes != 0 && !good_segment(segment_bytes)) return clair_host_fail("segment_bytes %d: a power of two in %u .. %u, or 0", segment_bytes, SEG_MIN, SEG_MAX);
     clair_host_bamidx *h = new clair_host_bamidx;
-    h->front.threads = threads;
-    h->front.max_blocks = max_blocks;
-    h->front.seg = (uint32_t)segment_bytes;
+    if (h->front.configure(threads, max_blocks, segment_bytes)) { delete h; return 1; }
     *out = h;
     return 0;
 }
@@ -165,74 +160,20 @@ int clair_host_bamidx_build(const char *path, const clair_bamidx_backend_t *be, 
     if (!out) return clair_host_fail("out is NULL");
     *out = nullptr;
     if (!path || !be || !be->begin || !be->batch || !be->finish || !be->last_error) return clair_host_fail("bamidx build: NULL argument");
-    if (max_blocks < 1 || max_blocks > 16384) return clair_host_fail("max_blocks %d: 1 .. 16384", max_blocks);
-    FILE *file = fopen(path, "rb");
-    if (!file) return clair_host_fail("%s: cannot open", path);
-    struct Closer { FILE *f; ~Closer() { fclose(f); } } closer{file};
-    if (fseeko(file, 0, SEEK_END) != 0) return clair_host_fail("%s: cannot seek", path);
-    const int64_t file_size = (int64_t)ftello(file);
-    std::vector<uint8_t> cbuf;
-    {
-        uint8_t magic[4] = {0, 0, 0, 0};
-        if (file_size < BGZF_HEADER || fseeko(file, 0, SEEK_SET) != 0 || fread(magic, 1, 4, file) != 4 || !gzip_with_extra(magic))
-            return clair_host_fail("%s is not a BGZF-compressed BAM (SAM text, CRAM and plain gzip have no .bai)", path);
-    }
-    // the header, block by block (zlib), with where each block's bytes start in it
-    std::vector<uint8_t> text;
-    std::vector<std::pair<int64_t, int64_t>> pieces;          // (position in text, coffset)
-    int64_t coffset = 0;
-    const auto need = [&](size_t bytes) -> int {
-        while (text.size() < bytes) {
-            if (coffset >= file_size) return clair_host_fail("%s: the BAM header is truncated", path);
-            cbuf.clear();
-            uint32_t csize = 0, isize = 0;
-            if (read_block(file, path, (uint64_t)file_size, (uint64_t)coffset, cbuf, &csize, &isize)) return 1;
-            const size_t at = text.size();
-            text.resize(at + isize);
-            const int status = inflate_block(cbuf.data(), csize, text.data() + at, isize);
-            if (status) return clair_host_fail("%s: BGZF block at compressed offset %lld: %s", path, (long long)coffset, inflate_text(status));
-            pieces.emplace_back((int64_t)at, coffset);
-            coffset += csize;
-        }
-        return 0;
-    };
-    BamHeader header;
-    if (parse_bam_header(path, "", need, [&] { return (const uint8_t *)text.data(); }, &header)) return 1;
-    const int32_t n_ref = (int32_t)header.lengths.size();
-    const std::vector<int64_t> &ref_len = header.lengths;
-    const size_t at = header.end;
-    // the first record: in the last header block, or at the start of the block after it
-    int64_t entry = 0;
-    if (at < text.size()) {
-        size_t k = pieces.size() - 1;
-        while (pieces[k].first > (int64_t)at) --k;
-        coffset = pieces[k].second;
-        entry = (int64_t)at - pieces[k].first;
-    }
+    if (check_max_blocks(max_blocks)) return 1;
+    clair_job::Job job;
+    if (clair_job::open_job(path, "(SAM text, CRAM and plain gzip have no .bai)", &job)) return 1;
+    const int32_t n_ref = (int32_t)job.header.lengths.size();
+    const std::vector<int64_t> &ref_len = job.header.lengths;
     if (be->begin(be->ctx, n_ref, ref_len.data())) return clair_host_fail("%s: %s", path, be->last_error(be->ctx));
     clair_host_bamidx_result *res = new clair_host_bamidx_result;
     struct Guard { clair_host_bamidx_result *r; ~Guard() { delete r; } } guard{res};
-    std::vector<int64_t> in_at, offs;
-    std::vector<int32_t> csizes, out_lens;
     int64_t state[STATE_WORDS] = {0, 0, INT32_MIN, 0, 0, 0, INT32_MIN, 0};
-    bool last = false;
-    while (!last) {
-        cbuf.clear(); in_at.clear(); offs.clear(); csizes.clear(); out_lens.clear();
-        while ((int)offs.size() < max_blocks && coffset < file_size) {
-            const size_t here = cbuf.size();
-            uint32_t csize = 0, isize = 0;
-            if (read_block(file, path, (uint64_t)file_size, (uint64_t)coffset, cbuf, &csize, &isize)) return 1;
-            in_at.push_back((int64_t)here);
-            offs.push_back(coffset);
-            csizes.push_back((int32_t)csize);
-            out_lens.push_back((int32_t)isize);
-            coffset += csize;
-        }
-        last = coffset >= file_size;
+    clair_job::Batches in(&job, max_blocks);
+    while (!in.last) {
+        if (in.next()) return 1;
         const clair_bamidx_run_t *runs = nullptr;
-        if (be->batch(be->ctx, cbuf.data(), (int64_t)cbuf.size(), (int)offs.size(), in_at.data(), csizes.data(), out_lens.data(), offs.data(), coffset, entry,
-                      last ? 1 : 0, state, &runs))
-            return clair_host_fail("%s: %s", path, be->last_error(be->ctx));
+        if (in.through(be->batch, be->ctx, state, &runs)) return clair_host_fail("%s: %s", path, be->last_error(be->ctx));
         for (int64_t k = 0; k < state[ST_N_RUNS]; ++k) {
             const clair_bamidx_run_t &r = runs[k];
             if (r.tid < 0) continue;
@@ -242,7 +183,6 @@ int clair_host_bamidx_build(const char *path, const clair_bamidx_backend_t *be, 
         state[ST_RECORDS_BEFORE] += state[ST_N_RECORDS];
         state[ST_PREV_TID] = state[ST_LAST_TID];
         state[ST_PREV_POS] = state[ST_LAST_POS];
-        entry = 0;
     }
     res->first_window.assign((size_t)n_ref + 1, 0);
     for (int r = 0; r < n_ref; ++r) res->first_window[(size_t)r + 1] = res->first_window[(size_t)r] + windows_of(ref_len[(size_t)r]);

@@ -3,8 +3,9 @@
 //     zlib on a few threads (hostsrc/bgzf_file.h), records framed as host_bam_index.cpp frames them (hostsrc/bam_frame.h), kept records
 //     compacted into the group buffer, the group ordered by std::stable_sort over (key, index), gathered, cut every 65280 bytes and
 //     compressed by the host twin of the device compressor (host_deflate.cpp);
-//   - the file driver both backends run under: the BAM header (hostsrc/bam_header.h), the first read with the byte histogram, the groups of
-//     buckets when the file does not fit, one more read per group, the blocks appended to the output, the EOF marker.
+//   - the file driver both backends run under (the job, its batches and the output's writer are hostsrc/bam_job.h): the first read with the
+//     byte histogram, the groups of buckets when the file does not fit, one more read per group, the blocks appended to the output, the EOF
+//     marker.
 // Plain C++17 + zlib, no HIP.
 #include "../../include/clair_host.h"
 #include "../csrc/bam_sort_core.h"
@@ -25,9 +26,6 @@ namespace {
 using namespace clair_bsort;
 using namespace clair_bgzf;
 using namespace clair_frame;
-using clair_job::deflate_payloads;
-using clair_job::zlib_payload;
-
 }  // namespace
 
 struct clair_host_bamsort {
@@ -44,25 +42,16 @@ struct clair_host_bamsort {
     std::vector<uint8_t> group;
     std::vector<uint64_t> keys;
     std::vector<int64_t> off;                    // of each kept record in the group buffer, one more for its end
-    // the output
-    std::vector<uint8_t> sorted, out_carry;
-    int64_t total = 0;
+    clair_job::OutStream out;                    // the sorted records
 };
-
-struct clair_host_bamsort_job : clair_job::Job {};
 
 extern "C" {
 
 int clair_host_bamsort_create(int threads, int max_blocks, int segment_bytes, clair_host_bamsort_t **out) {
     if (!out) return clair_host_fail("out is NULL");
     *out = nullptr;
-    if (threads < 1 || threads > 16) return clair_host_fail("BAM threads: %d (1 .. 16)", threads);
-    if (max_blocks < 1 || max_blocks > 16384) return clair_host_fail("max_blocks %d: 1 .. 16384", max_blocks);
-    if (segment_bytes != 0 && !good_segment(segment_bytes)) return clair_host_fail("segment_bytes %d: a power of two in %u .. %u, or 0", segment_bytes, SEG_MIN, SEG_MAX);
     clair_host_bamsort *h = new clair_host_bamsort;
-    h->front.threads = threads;
-    h->front.max_blocks = max_blocks;
-    h->front.seg = (uint32_t)segment_bytes;
+    if (h->front.configure(threads, max_blocks, segment_bytes)) { delete h; return 1; }
     *out = h;
     return 0;
 }
@@ -78,8 +67,7 @@ int clair_host_bamsort_begin(clair_host_bamsort_t *h, int n_ref, const int64_t *
     h->hist.assign((size_t)h->first_bucket[(size_t)n_ref] + 1, 0);
     h->memory = memory;
     h->n_ref = n_ref;
-    h->out_carry.clear();
-    h->total = 0;
+    h->out.rewind();
     h->lo = h->hi = 0;
     return 0;
 }
@@ -170,16 +158,15 @@ int clair_host_bamsort_sort(clair_host_bamsort_t *h, int last, int64_t *info) {
     std::vector<uint32_t> perm(n);
     std::iota(perm.begin(), perm.end(), 0u);
     std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return h->keys[a] < h->keys[b]; });
-    h->sorted.assign(h->out_carry.begin(), h->out_carry.end());
-    h->sorted.reserve(h->out_carry.size() + h->group.size());
-    for (size_t i = 0; i < n; ++i) h->sorted.insert(h->sorted.end(), h->group.begin() + (ptrdiff_t)h->off[perm[i]], h->group.begin() + (ptrdiff_t)h->off[(size_t)perm[i] + 1]);
-    h->total = (int64_t)h->sorted.size();
-    const int64_t payloads = payloads_of(h->total, last != 0);
-    h->out_carry.assign(h->sorted.begin() + (ptrdiff_t)std::min(h->total, payloads * PAYLOAD), h->sorted.end());
+    std::vector<uint8_t> &sorted = h->out.bytes;
+    h->out.begin();
+    sorted.reserve(sorted.size() + h->group.size());
+    for (size_t i = 0; i < n; ++i) sorted.insert(sorted.end(), h->group.begin() + (ptrdiff_t)h->off[perm[i]], h->group.begin() + (ptrdiff_t)h->off[(size_t)perm[i] + 1]);
+    const int64_t payloads = h->out.cut(last != 0);
     h->group.clear();
     h->keys.clear();
     h->off.clear();                              // a new pass before the next batch
-    info[SI_BYTES] = h->total;
+    info[SI_BYTES] = h->out.total;
     info[SI_PAYLOADS] = payloads;
     info[SI_RECORDS] = (int64_t)n;
     info[SI_PASSES] = 0;
@@ -187,16 +174,8 @@ int clair_host_bamsort_sort(clair_host_bamsort_t *h, int last, int64_t *info) {
 }
 
 int clair_host_bamsort_emit(clair_host_bamsort_t *h, int64_t first, int n, int compressed, uint8_t *out, int32_t *sizes) {
-    if (!h || !out || !sizes || first < 0 || n < 0) return clair_host_fail("bamsort emit: bad arguments");
-    if ((first + n - 1) * PAYLOAD >= h->total && n > 0) return clair_host_fail("bamsort emit: payloads [%lld, +%d) of %lld bytes", (long long)first, n, (long long)h->total);
-    for (int i = 0; i < n; ++i) sizes[i] = (int32_t)std::min(PAYLOAD, h->total - (first + i) * PAYLOAD);
-    const uint8_t *data = h->sorted.data() + first * PAYLOAD;
-    if (!compressed) {
-        if (n) memcpy(out, data, (size_t)((int64_t)(n - 1) * PAYLOAD + sizes[n - 1]));
-        return 0;
-    }
-    const std::vector<int32_t> in_len(sizes, sizes + n);
-    return deflate_payloads(h->front.threads, data, n, in_len.data(), out, sizes);
+    if (!h) return clair_host_fail("bamsort emit: bad arguments");
+    return clair_job::emit_payloads(h->out.bytes.data(), h->out.total, h->front.threads, first, n, compressed, out, sizes, "bamsort");
 }
 
 static int twin_begin(void *ctx, int n_ref, const int64_t *ref_len, int64_t memory) { return clair_host_bamsort_begin((clair_host_bamsort_t *)ctx, n_ref, ref_len, memory); }
@@ -240,34 +219,13 @@ int clair_host_bamsort_debug_gather(const uint8_t *stream, int64_t stream_bytes,
 }
 
 // ---- the file driver
-int clair_host_bamsort_open(const char *path, clair_host_bamsort_job_t **out) {
-    if (!out) return clair_host_fail("out is NULL");
-    *out = nullptr;
-    if (!path) return clair_host_fail("bamsort open: NULL argument");
-    clair_host_bamsort_job *job = new clair_host_bamsort_job;
-    struct Guard { clair_host_bamsort_job *j; ~Guard() { delete j; } } guard{job};
-    if (clair_job::open_job(path, job)) return 1;
-    guard.j = nullptr;
-    *out = job;
-    return 0;
-}
-
-void clair_host_bamsort_close(clair_host_bamsort_job_t *job) { delete job; }
-
-int clair_host_bamsort_header(const clair_host_bamsort_job_t *job, uint8_t *out, int64_t cap, int64_t *bytes) {
-    if (!job || !bytes) return clair_host_fail("bamsort header: NULL argument");
-    *bytes = (int64_t)job->header.end;
-    if (out && cap >= *bytes) memcpy(out, job->text.data(), job->header.end);
-    return 0;
-}
-
 // deflate: 0 the backend's own compressor, 1 zlib, 2 the host twin of the device compressor on `threads` threads.
 // stats [CLAIR_BAMSORT_STATS] = records, mapped, unplaced, groups, input reads, already sorted, bytes appended to out_path
-int clair_host_bamsort_run(clair_host_bamsort_job_t *job, const clair_bamsort_backend_t *be, const char *out_path, int deflate, int64_t memory, int max_blocks,
+int clair_host_bamsort_run(clair_host_bam_job_t *job, const clair_bamsort_backend_t *be, const char *out_path, int deflate, int64_t memory, int max_blocks,
                            int threads, int64_t *stats) {
     if (!job || !be || !out_path || !stats || !be->begin || !be->pass || !be->batch || !be->histogram || !be->sort || !be->emit || !be->last_error)
         return clair_host_fail("bamsort run: NULL argument");
-    if (max_blocks < 1 || max_blocks > 16384) return clair_host_fail("max_blocks %d: 1 .. 16384", max_blocks);
+    if (check_max_blocks(max_blocks)) return 1;
     if (deflate < 0 || deflate > 2 || threads < 1 || threads > 16 || memory < 1) return clair_host_fail("bamsort run: bad arguments");
     const char *path = job->path.c_str();
     const auto failed = [&] { return clair_host_fail("%s: %s", path, be->last_error(be->ctx)); };
@@ -278,32 +236,15 @@ int clair_host_bamsort_run(clair_host_bamsort_job_t *job, const clair_bamsort_ba
     const int64_t n_buckets = first_bucket[(size_t)n_ref] + 1;
     if (be->begin(be->ctx, n_ref, ref_len.data(), memory)) return failed();
 
-    std::vector<uint8_t> cbuf;
-    std::vector<int64_t> in_at, offs;
-    std::vector<int32_t> csizes, out_lens;
     int64_t records = 0, mapped = 0, unplaced = 0;
     bool sorted = true, overflow = false;
     // one read of the input, every batch through the backend
     const auto read_all = [&](bool first) -> int {
-        int64_t coffset = job->coffset, entry = job->entry;
+        clair_job::Batches in(job, max_blocks);
         int64_t state[SS_WORDS] = {0};
-        bool last = false;
-        while (!last) {
-            cbuf.clear(); in_at.clear(); offs.clear(); csizes.clear(); out_lens.clear();
-            while ((int)offs.size() < max_blocks && coffset < job->file_size) {
-                const size_t here = cbuf.size();
-                uint32_t csize = 0, isize = 0;
-                if (read_block(job->file, path, (uint64_t)job->file_size, (uint64_t)coffset, cbuf, &csize, &isize)) return 1;
-                in_at.push_back((int64_t)here);
-                offs.push_back(coffset);
-                csizes.push_back((int32_t)csize);
-                out_lens.push_back((int32_t)isize);
-                coffset += csize;
-            }
-            last = coffset >= job->file_size;
-            if (be->batch(be->ctx, cbuf.data(), (int64_t)cbuf.size(), (int)offs.size(), in_at.data(), csizes.data(), out_lens.data(), offs.data(), coffset, entry,
-                          last ? 1 : 0, state))
-                return failed();
+        while (!in.last) {
+            if (in.next()) return 1;
+            if (in.through(be->batch, be->ctx, state)) return failed();
             if (first) {
                 records += state[SS_N_RECORDS];
                 mapped += state[SS_MAPPED];
@@ -315,44 +256,17 @@ int clair_host_bamsort_run(clair_host_bamsort_job_t *job, const clair_bamsort_ba
             }
             state[SS_RECORDS_BEFORE] += state[SS_N_RECORDS];
             state[SS_PREV_KEY] = state[SS_LAST_KEY];
-            entry = 0;
         }
         return 0;
     };
 
-    FILE *out = fopen(out_path, "ab");
-    if (!out) return clair_host_fail("%s: cannot write", out_path);
-    struct Closer { FILE *f; ~Closer() { if (f) fclose(f); } } closer{out};
-    int64_t written = 0;
-    constexpr int EMIT = 64;                                  // payloads per emit
-    std::vector<uint8_t> slots((size_t)EMIT * SLOT), raw((size_t)EMIT * PAYLOAD);
-    std::vector<int32_t> sizes((size_t)EMIT);
+    clair_job::Writer out;
+    if (out.open(path, out_path, deflate, threads)) return 1;
     // the sorted group goes out: whole payloads, and with `final` the partial one behind them
     const auto write_group = [&](bool final) -> int {
         int64_t info[SI_WORDS] = {0};
         if (be->sort(be->ctx, final ? 1 : 0, info)) return failed();
-        for (int64_t at = 0; at < info[SI_PAYLOADS]; at += EMIT) {
-            const int n = (int)std::min<int64_t>(EMIT, info[SI_PAYLOADS] - at);
-            if (deflate == 0) {
-                if (be->emit(be->ctx, at, n, 1, slots.data(), sizes.data())) return failed();
-            } else {
-                if (be->emit(be->ctx, at, n, 0, raw.data(), sizes.data())) return failed();
-                if (deflate == 2) {
-                    const std::vector<int32_t> in_len(sizes.begin(), sizes.begin() + n);
-                    if (deflate_payloads(threads, raw.data(), n, in_len.data(), slots.data(), sizes.data())) return 1;
-                } else {
-                    for (int i = 0; i < n; ++i)
-                        if (zlib_payload(raw.data() + (int64_t)i * PAYLOAD, sizes[(size_t)i], slots.data() + (int64_t)i * SLOT, &sizes[(size_t)i])) return 1;
-                }
-            }
-            for (int i = 0; i < n; ++i) {
-                const int32_t cs = sizes[(size_t)i];
-                if (cs < BGZF_HEADER + BGZF_FOOTER || cs > SLOT) return clair_host_fail("%s: a compressed block of %d bytes", path, cs);
-                if (fwrite(slots.data() + (int64_t)i * SLOT, 1, (size_t)cs, out) != (size_t)cs) return clair_host_fail("%s: write failed", out_path);
-                written += cs;
-            }
-        }
-        return 0;
+        return out.payloads(info[SI_PAYLOADS], be->emit, be->ctx, failed);
     };
 
     int64_t groups = 1, reads = 1;
@@ -390,17 +304,14 @@ int clair_host_bamsort_run(clair_host_bamsort_job_t *job, const clair_bamsort_ba
             if (write_group(g + 1 == ranges.size())) return 1;
         }
     }
-    if (fwrite(BGZF_EOF, 1, sizeof BGZF_EOF, out) != sizeof BGZF_EOF) return clair_host_fail("%s: write failed", out_path);
-    written += (int64_t)sizeof BGZF_EOF;
-    closer.f = nullptr;
-    if (fclose(out) != 0) return clair_host_fail("%s: write failed", out_path);
+    if (out.finish()) return 1;
     stats[0] = records;
     stats[1] = mapped;
     stats[2] = unplaced;
     stats[3] = groups;
     stats[4] = reads;
     stats[5] = sorted ? 1 : 0;
-    stats[6] = written;
+    stats[6] = out.written;
     return 0;
 }
 

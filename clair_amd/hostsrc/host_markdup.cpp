@@ -92,25 +92,16 @@ struct clair_host_markdup {
     std::vector<uint8_t> dup;
     int64_t counts[MC_WORDS] = {0};
     int64_t marked = 0;
-    // the output
-    std::vector<uint8_t> out, out_carry;
-    int64_t total = 0;
+    clair_job::OutStream out;                    // the records of the second read
 };
-
-struct clair_host_markdup_job : clair_job::Job {};
 
 extern "C" {
 
 int clair_host_markdup_create(int threads, int max_blocks, int segment_bytes, clair_host_markdup_t **out) {
     if (!out) return clair_host_fail("out is NULL");
     *out = nullptr;
-    if (threads < 1 || threads > 16) return clair_host_fail("BAM threads: %d (1 .. 16)", threads);
-    if (max_blocks < 1 || max_blocks > 16384) return clair_host_fail("max_blocks %d: 1 .. 16384", max_blocks);
-    if (segment_bytes != 0 && !good_segment(segment_bytes)) return clair_host_fail("segment_bytes %d: a power of two in %u .. %u, or 0", segment_bytes, SEG_MIN, SEG_MAX);
     clair_host_markdup *h = new clair_host_markdup;
-    h->front.threads = threads;
-    h->front.max_blocks = max_blocks;
-    h->front.seg = (uint32_t)segment_bytes;
+    if (h->front.configure(threads, max_blocks, segment_bytes)) { delete h; return 1; }
     *out = h;
     return 0;
 }
@@ -127,8 +118,8 @@ int clair_host_markdup_begin(clair_host_markdup_t *h, int n_ref, int64_t memory,
     h->summaries.clear();
     h->dup.clear();
     h->front.rewind();
-    h->out_carry.clear();
-    h->total = h->marked = 0;
+    h->out.rewind();
+    h->marked = 0;
     return 0;
 }
 
@@ -173,8 +164,8 @@ int clair_host_markdup_resolve(clair_host_markdup_t *h) {
     resolve(h->summaries.data(), (int64_t)h->summaries.size(), h->dup.data(), h->counts);
     h->resolved = true;
     h->front.rewind();
-    h->out_carry.clear();
-    h->total = h->marked = 0;
+    h->out.rewind();
+    h->marked = 0;
     return 0;
 }
 
@@ -188,7 +179,8 @@ int clair_host_markdup_mark(clair_host_markdup_t *h, const uint8_t *cdata, int64
     const int64_t n_rec = (int64_t)front.starts.size();
     if (h->marked + n_rec > (int64_t)h->summaries.size())
         return clair_host_fail("the second read finds more than the %zu records of the first: the file changed", h->summaries.size());
-    h->out.assign(h->out_carry.begin(), h->out_carry.end());
+    std::vector<uint8_t> &out = h->out.bytes;
+    h->out.begin();
     int64_t written = 0;
     for (int64_t k = 0; k < n_rec; ++k) {
         const int64_t o = front.starts[(size_t)k], size = 4 + (int64_t)m.le32(o);
@@ -196,35 +188,24 @@ int clair_host_markdup_mark(clair_host_markdup_t *h, const uint8_t *cdata, int64
         const bool seen = (h->summaries[g].bits & S_EXAMINED) != 0, duplicate = seen && h->dup[g];
         if (seen) front.stream[(size_t)o + 19] = patched(front.stream[(size_t)o + 19], duplicate);
         if (h->remove && duplicate) continue;
-        if (h->remove) h->out.insert(h->out.end(), front.stream.begin() + (ptrdiff_t)o, front.stream.begin() + (ptrdiff_t)(o + size));
+        if (h->remove) out.insert(out.end(), front.stream.begin() + (ptrdiff_t)o, front.stream.begin() + (ptrdiff_t)(o + size));
         ++written;
     }
-    if (!h->remove && n_rec > 0) h->out.insert(h->out.end(), front.stream.begin() + (ptrdiff_t)front.starts[0], front.stream.begin() + (ptrdiff_t)front.tail);
+    if (!h->remove && n_rec > 0) out.insert(out.end(), front.stream.begin() + (ptrdiff_t)front.starts[0], front.stream.begin() + (ptrdiff_t)front.tail);
     if (front.close_batch(last)) return 1;
     h->marked += n_rec;
     if (last && h->marked != (int64_t)h->summaries.size())
         return clair_host_fail("the second read finds %lld records, the first found %zu: the file changed", (long long)h->marked, h->summaries.size());
-    h->total = (int64_t)h->out.size();
-    const int64_t payloads = payloads_of(h->total, last != 0);
-    h->out_carry.assign(h->out.begin() + (ptrdiff_t)std::min(h->total, payloads * PAYLOAD), h->out.end());
-    info[MI_BYTES] = h->total;
-    info[MI_PAYLOADS] = payloads;
+    info[MI_PAYLOADS] = h->out.cut(last != 0);
+    info[MI_BYTES] = h->out.total;
     info[MI_RECORDS] = n_rec;
     info[MI_WRITTEN] = written;
     return 0;
 }
 
 int clair_host_markdup_emit(clair_host_markdup_t *h, int64_t first, int n, int compressed, uint8_t *out, int32_t *sizes) {
-    if (!h || !out || !sizes || first < 0 || n < 0) return clair_host_fail("markdup emit: bad arguments");
-    if ((first + n - 1) * PAYLOAD >= h->total && n > 0) return clair_host_fail("markdup emit: payloads [%lld, +%d) of %lld bytes", (long long)first, n, (long long)h->total);
-    for (int i = 0; i < n; ++i) sizes[i] = (int32_t)std::min(PAYLOAD, h->total - (first + i) * PAYLOAD);
-    const uint8_t *data = h->out.data() + first * PAYLOAD;
-    if (!compressed) {
-        if (n) memcpy(out, data, (size_t)((int64_t)(n - 1) * PAYLOAD + sizes[n - 1]));
-        return 0;
-    }
-    const std::vector<int32_t> in_len(sizes, sizes + n);
-    return clair_job::deflate_payloads(h->front.threads, data, n, in_len.data(), out, sizes);
+    if (!h) return clair_host_fail("markdup emit: bad arguments");
+    return clair_job::emit_payloads(h->out.bytes.data(), h->out.total, h->front.threads, first, n, compressed, out, sizes, "markdup");
 }
 
 int clair_host_markdup_stats(clair_host_markdup_t *h, int64_t *counts) {
@@ -277,30 +258,11 @@ int clair_host_markdup_debug_resolve(const clair_markdup_summary_t *summaries, i
 }
 
 // ---- the file driver
-int clair_host_markdup_open(const char *path, clair_host_markdup_job_t **out) {
-    if (!out) return clair_host_fail("out is NULL");
-    *out = nullptr;
-    if (!path) return clair_host_fail("markdup open: NULL argument");
-    clair_host_markdup_job *job = new clair_host_markdup_job;
-    if (clair_job::open_job(path, job)) { delete job; return 1; }
-    *out = job;
-    return 0;
-}
-
-void clair_host_markdup_close(clair_host_markdup_job_t *job) { delete job; }
-
-int clair_host_markdup_header(const clair_host_markdup_job_t *job, uint8_t *out, int64_t cap, int64_t *bytes) {
-    if (!job || !bytes) return clair_host_fail("markdup header: NULL argument");
-    *bytes = (int64_t)job->header.end;
-    if (out && cap >= *bytes) memcpy(out, job->text.data(), job->header.end);
-    return 0;
-}
-
-int clair_host_markdup_run(clair_host_markdup_job_t *job, const clair_markdup_backend_t *be, const char *out_path, int deflate, int64_t memory, int max_blocks,
+int clair_host_markdup_run(clair_host_bam_job_t *job, const clair_markdup_backend_t *be, const char *out_path, int deflate, int64_t memory, int max_blocks,
                            int threads, int remove, int64_t *stats) {
     if (!job || !be || !out_path || !stats || !be->begin || !be->batch || !be->resolve || !be->mark || !be->emit || !be->stats || !be->last_error)
         return clair_host_fail("markdup run: NULL argument");
-    if (max_blocks < 1 || max_blocks > 16384) return clair_host_fail("max_blocks %d: 1 .. 16384", max_blocks);
+    if (check_max_blocks(max_blocks)) return 1;
     if (deflate < 0 || deflate > 2 || threads < 1 || threads > 16 || memory < 1) return clair_host_fail("markdup run: bad arguments");
     const char *path = job->path.c_str();
     const auto failed = [&] { return clair_host_fail("%s: %s", path, be->last_error(be->ctx)); };
@@ -310,48 +272,31 @@ int clair_host_markdup_run(clair_host_markdup_job_t *job, const clair_markdup_ba
         int64_t state[MS_WORDS] = {0};
         while (!in.last) {
             if (in.next()) return 1;
-            if (be->batch(be->ctx, in.cbuf.data(), (int64_t)in.cbuf.size(), (int)in.offs.size(), in.in_at.data(), in.csizes.data(), in.out_lens.data(), in.offs.data(),
-                          in.coffset, in.entry, in.last ? 1 : 0, state))
-                return failed();
-            in.entry = 0;
+            if (in.through(be->batch, be->ctx, state)) return failed();
         }
     }
     if (be->resolve(be->ctx)) return failed();
     int64_t counts[MC_WORDS] = {0};
     if (be->stats(be->ctx, counts)) return failed();
 
-    FILE *out = fopen(out_path, "ab");
-    if (!out) return clair_host_fail("%s: cannot write", out_path);
-    struct Closer { FILE *f; ~Closer() { if (f) fclose(f); } } closer{out};
-    int64_t written = 0, records_out = 0;
-    constexpr int EMIT = 64;                                  // payloads per emit
-    std::vector<uint8_t> slots((size_t)EMIT * SLOT), raw(deflate ? (size_t)EMIT * PAYLOAD : 1);
-    std::vector<int32_t> sizes((size_t)EMIT);
+    clair_job::Writer out;
+    if (out.open(path, out_path, deflate, threads)) return 1;
+    int64_t records_out = 0;
     {   // the second read: the flags patched, the records out
         clair_job::Batches in(job, max_blocks);
         while (!in.last) {
             if (in.next()) return 1;
             int64_t info[MI_WORDS] = {0};
-            if (be->mark(be->ctx, in.cbuf.data(), (int64_t)in.cbuf.size(), (int)in.offs.size(), in.in_at.data(), in.csizes.data(), in.out_lens.data(), in.offs.data(),
-                         in.coffset, in.entry, in.last ? 1 : 0, info))
-                return failed();
-            in.entry = 0;
+            if (in.through(be->mark, be->ctx, info)) return failed();
             records_out += info[MI_WRITTEN];
-            for (int64_t at = 0; at < info[MI_PAYLOADS]; at += EMIT) {
-                const int n = (int)std::min<int64_t>(EMIT, info[MI_PAYLOADS] - at);
-                if (be->emit(be->ctx, at, n, deflate == 0 ? 1 : 0, deflate == 0 ? slots.data() : raw.data(), sizes.data())) return failed();
-                if (clair_job::write_payloads(out, path, out_path, deflate, threads, n, raw.data(), slots.data(), sizes.data(), &written)) return 1;
-            }
+            if (out.payloads(info[MI_PAYLOADS], be->emit, be->ctx, failed)) return 1;
         }
     }
-    if (fwrite(BGZF_EOF, 1, sizeof BGZF_EOF, out) != sizeof BGZF_EOF) return clair_host_fail("%s: write failed", out_path);
-    written += (int64_t)sizeof BGZF_EOF;
-    closer.f = nullptr;
-    if (fclose(out) != 0) return clair_host_fail("%s: write failed", out_path);
+    if (out.finish()) return 1;
     for (int i = 0; i < MC_WORDS; ++i) stats[i] = counts[i];
     stats[MC_WORDS] = 2 * counts[MC_DUPLICATE_PAIRS] + counts[MC_DUPLICATE_FRAGMENTS];
     stats[MC_WORDS + 1] = records_out;
-    stats[MC_WORDS + 2] = written;
+    stats[MC_WORDS + 2] = out.written;
     return 0;
 }
 

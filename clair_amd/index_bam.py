@@ -21,72 +21,32 @@ from argparse import ArgumentParser
 
 import numpy as np
 
-from clair_amd import _hostapi
+from clair_amd import _hostapi, bam_stage
 from clair_amd._hostapi import BamError
+from clair_amd.bam_stage import BATCH_BLOCKS
 
 RUN_DTYPE = np.dtype([("tid", "<i4"), ("bin", "<u4"), ("beg", "<u8"), ("end", "<u8")])     # clair_bamidx_run_t
 BACKEND_WORDS = 5                                # clair_bamidx_backend_t: ctx and four function pointers
-BATCH_BLOCKS = 64                                # BGZF blocks per batch: 4 MiB of records at a time
 FRAME_WORDS = 4                                  # clair_*bamidx_debug_frame's result
 SEGMENT_MIN, SEGMENT_DEFAULT = 64, 8192          # clair_bix::SEG_MIN, SEG_DEFAULT (csrc/bam_index_core.h)
 NO_OFFSET = np.uint64(0xffffffffffffffff)
 
 
-class HostIndexer(_hostapi.Handle):
-    """clair_host_bamidx_*: the host twin.  segment_bytes 0: records framed by the sequential walk; a power of two: by the segmented rule."""
-    _error = BamError
-
-    def __init__(self, threads=4, max_blocks=BATCH_BLOCKS, segment_bytes=0):
-        self._lib = _hostapi.load()
-        out = self._own(self._lib.clair_host_bamidx_destroy, self._lib.clair_host_last_error)
-        self._check(self._lib.clair_host_bamidx_create(int(threads), int(max_blocks), int(segment_bytes), out))
-        self.max_blocks = int(max_blocks)
-
-    def backend(self):
-        table = (ctypes.c_void_p * BACKEND_WORDS)()
-        self._check(self._lib.clair_host_bamidx_backend(self._h, table))
-        return table
+class HostIndexer(bam_stage.HostBackend):
+    """clair_host_bamidx_*: the host twin (hostsrc/host_bam_index.cpp)."""
+    prefix, words = "bamidx", BACKEND_WORDS
 
 
-class DeviceIndexer(object):
+class DeviceIndexer(bam_stage.DeviceBackend):
     """clair_bamidx_*: the device backend (csrc/bam_index.hip)."""
-
-    def __init__(self, device=0, max_blocks=BATCH_BLOCKS, segment_bytes=0):
-        from clair_amd import _capi
-        try:
-            self._lib = _capi.load()
-        except _capi.EngineError as e:
-            raise BamError(str(e))
-        self._h = ctypes.c_void_p()
-        if self._lib.clair_bamidx_create(int(device), int(max_blocks), int(segment_bytes), ctypes.byref(self._h)) != 0:
-            raise BamError("clair_bamidx_create failed: %s" % self._lib.clair_bamidx_last_error(None).decode())
-        self.max_blocks = int(max_blocks)
-
-    def backend(self):
-        table = (ctypes.c_void_p * BACKEND_WORDS)()
-        if self._lib.clair_bamidx_backend(self._h, table) != 0:
-            raise BamError(self._lib.clair_bamidx_last_error(self._h).decode())
-        return table
+    prefix, words = "bamidx", BACKEND_WORDS
 
     def frame(self, stream, entry=0):
         """clair_bamidx_debug_frame -> (starts, tail, bad, sentinels intact)"""
         stream = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8))
         starts, result = np.zeros(len(stream) // 36 + 2, dtype=np.int64), np.zeros(FRAME_WORDS, dtype=np.int64)
-        if self._lib.clair_bamidx_debug_frame(self._h, stream.ctypes.data, len(stream), int(entry), starts.ctypes.data, len(starts), result.ctypes.data) != 0:
-            raise BamError(self._lib.clair_bamidx_last_error(self._h).decode())
+        self._check(self._lib.clair_bamidx_debug_frame(self._h, stream.ctypes.data, len(stream), int(entry), starts.ctypes.data, len(starts), result.ctypes.data))
         return starts[:result[0]].tolist(), int(result[1]), bool(result[2]), bool(result[3])
-
-    def close(self):
-        if self._h:
-            self._lib.clair_bamidx_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def host_frame(stream, entry=0, segment_bytes=0):
     """clair_host_bamidx_debug_frame -> (starts, tail, bad): segment_bytes 0 is the sequential walk, else the segmented rule restated."""
@@ -149,23 +109,13 @@ def build_index(bam_fn, out_fn=None, backend="auto", device=0, threads=4, force=
     """-> dict(references, records, mapped, unplaced, chunks, bytes, backend, path).  backend "auto": the device when one is present (a choice
     of convenience, not of measured speed: docs/index_bam.md), else the host.  segment_bytes None: the device's default segment, the host's
     sequential walk."""
-    if backend not in ("auto", "device", "host"):
-        raise BamError("--backend %s: auto, device or host" % backend)
-    if not isinstance(threads, int) or not 1 <= threads <= 16:
-        raise BamError("--bam_threads %s: 1 .. 16" % threads)
+    backend = bam_stage.resolve_backend(backend)
+    bam_stage.check_threads(threads)
     if not os.path.isfile(bam_fn):
         raise BamError("%s: cannot open" % bam_fn)
     out_fn = out_fn or bam_fn + ".bai"
     if os.path.exists(out_fn) and not force:
         raise BamError("%s exists: --force overwrites it" % out_fn)
-    if backend == "auto":
-        backend = "host"
-        try:
-            from clair_amd import _capi
-            if _capi.load().clair_device_count() > 0:
-                backend = "device"
-        except Exception:
-            pass
     if backend == "device":
         indexer = DeviceIndexer(device=device, max_blocks=max_blocks, segment_bytes=segment_bytes or 0)
     else:
@@ -192,11 +142,7 @@ def build_parser():
     add = parser.add_argument
     add('--bam_fn', type=str, required=True, help="coordinate-sorted BAM")
     add('--bai_fn', type=str, default=None, help="the index to write, default: <bam_fn>.bai")
-    add('--backend', type=str, default="auto", choices=("auto", "device", "host"),
-        help="where records are framed and indexed: the GPU, the host, or the GPU when one is present (convenience, not measured speed), default: %(default)s")
-    add('--device', type=int, default=0, help="GPU of --backend device, default: %(default)s")
-    add('--bam_threads', type=int, default=4, help="BGZF inflate threads of --backend host (1 .. 16), default: %(default)s")
-    add('--force', action='store_true', help="overwrite an existing index")
+    bam_stage.add_backend_arguments(parser, "framed and indexed", "BGZF inflate threads of --backend host", force_help="overwrite an existing index")
     return parser
 
 

@@ -18,9 +18,9 @@ from argparse import ArgumentParser
 
 import numpy as np
 
-from clair_amd import _hostapi, bgzf
+from clair_amd import _hostapi, bam_stage
 from clair_amd._hostapi import BamError
-from clair_amd.sort_bam import BATCH_BLOCKS, DEFLATE_MODES, header_blocks, parse_memory
+from clair_amd.bam_stage import BATCH_BLOCKS
 
 BACKEND_WORDS = 8                                # clair_markdup_backend_t: ctx and seven function pointers
 STATS_WORDS = 9                                  # CLAIR_MARKDUP_STATS
@@ -35,20 +35,9 @@ def _stream_arguments(stream, starts):
     return stream, np.ascontiguousarray(starts, dtype=np.int64)
 
 
-class HostMarker(_hostapi.Handle):
-    """clair_host_markdup_*: the host twin.  segment_bytes 0: records framed by the sequential walk; a power of two: by the segmented rule."""
-    _error = BamError
-    name = "host"
-
-    def __init__(self, threads=4, max_blocks=BATCH_BLOCKS, segment_bytes=0):
-        self._lib = _hostapi.load()
-        out = self._own(self._lib.clair_host_markdup_destroy, self._lib.clair_host_last_error)
-        self._check(self._lib.clair_host_markdup_create(int(threads), int(max_blocks), int(segment_bytes), out))
-
-    def backend(self):
-        table = (ctypes.c_void_p * BACKEND_WORDS)()
-        self._check(self._lib.clair_host_markdup_backend(self._h, table))
-        return table
+class HostMarker(bam_stage.HostBackend):
+    """clair_host_markdup_*: the host twin (hostsrc/host_markdup.cpp)."""
+    prefix, words = "markdup", BACKEND_WORDS
 
 
 def host_debug_summary(stream, starts, n_ref):
@@ -71,28 +60,9 @@ def host_debug_resolve(summaries):
     return out
 
 
-class DeviceMarker(object):
+class DeviceMarker(bam_stage.DeviceBackend):
     """clair_markdup_*: the device backend (csrc/markdup.hip)."""
-    name = "device"
-
-    def __init__(self, device=0, max_blocks=BATCH_BLOCKS, segment_bytes=0):
-        from clair_amd import _capi
-        try:
-            self._lib = _capi.load()
-        except _capi.EngineError as e:
-            raise BamError(str(e))
-        self._h = ctypes.c_void_p()
-        if self._lib.clair_markdup_create(int(device), int(max_blocks), int(segment_bytes), ctypes.byref(self._h)) != 0:
-            raise BamError("clair_markdup_create failed: %s" % self._lib.clair_markdup_last_error(None).decode())
-
-    def _check(self, rc):
-        if rc != 0:
-            raise BamError(self._lib.clair_markdup_last_error(self._h).decode())
-
-    def backend(self):
-        table = (ctypes.c_void_p * BACKEND_WORDS)()
-        self._check(self._lib.clair_markdup_backend(self._h, table))
-        return table
+    prefix, words = "markdup", BACKEND_WORDS
 
     def summary(self, stream, starts, n_ref):
         """clair_markdup_debug_summary -> SUMMARY [n]"""
@@ -120,82 +90,17 @@ class DeviceMarker(object):
                                                        duplicate.ctypes.data, int(bool(remove)), patched.ctypes.data, out.ctypes.data, ctypes.byref(n)))
         return patched.tobytes(), out[:n.value].tobytes()
 
-    def close(self):
-        if self._h:
-            self._lib.clair_markdup_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
 def markdup_bam(bam_fn, marked_fn, remove=False, backend="auto", device=0, threads=4, memory=None, deflate=None, index=False, force=False,
                 max_blocks=BATCH_BLOCKS, segment_bytes=None):
     """-> dict(records, examined, pairs, fragments, duplicate_pairs, duplicate_fragments, duplicates, written, bytes_in, bytes_out, backend,
     path).  backend "auto": the device when one is present (a choice of convenience, not of speed: docs/markdup_bam.md), else the
     host.  deflate None: the backend's own compressor.  segment_bytes None: the device's default segment, the host's sequential walk."""
-    if backend not in ("auto", "device", "host"):
-        raise BamError("--backend %s: auto, device or host" % backend)
-    if deflate is not None and deflate not in bgzf.BACKENDS:
-        raise BamError("--bgzf_deflate %s: %s" % (deflate, ", ".join(bgzf.BACKENDS)))
-    if not isinstance(threads, int) or not 1 <= threads <= 16:
-        raise BamError("--bam_threads %s: 1 .. 16" % threads)
-    memory = parse_memory(memory)
-    if not os.path.isfile(bam_fn):
-        raise BamError("%s: cannot open" % bam_fn)
-    if os.path.realpath(bam_fn) == os.path.realpath(marked_fn) or (os.path.exists(marked_fn) and os.path.samefile(bam_fn, marked_fn)):
-        raise BamError("%s: the output is the input" % marked_fn)
-    for fn in [marked_fn] + ([marked_fn + ".bai"] if index else []):
-        if os.path.exists(fn) and not force:
-            raise BamError("%s exists: --force overwrites it" % fn)
-    if backend == "auto":
-        backend = "host"
-        try:
-            from clair_amd import _capi
-            if _capi.load().clair_device_count() > 0:
-                backend = "device"
-        except Exception:
-            pass
-    deflate = deflate or backend
-    if deflate == "device" and backend != "device":
-        raise BamError("--bgzf_deflate device compresses the device-resident records: it needs --backend device")
-    lib = _hostapi.load()
-    job = ctypes.c_void_p()
-    if lib.clair_host_markdup_open(bam_fn.encode(), ctypes.byref(job)) != 0:
-        raise BamError(lib.clair_host_last_error().decode())
-    tmp = "%s.tmp.%d" % (marked_fn, os.getpid())
-    marker = None
-    try:
-        n = ctypes.c_int64()
-        lib.clair_host_markdup_header(job, None, 0, ctypes.byref(n))
-        raw = np.zeros(n.value, dtype=np.uint8)
-        lib.clair_host_markdup_header(job, raw.ctypes.data, len(raw), ctypes.byref(n))
-        if backend == "device":
-            marker = DeviceMarker(device=device, max_blocks=max_blocks, segment_bytes=segment_bytes or 0)
-        else:
-            marker = HostMarker(threads=threads, max_blocks=max_blocks, segment_bytes=segment_bytes or 0)
-        head = header_blocks(raw.tobytes(), deflate)
-        with open(tmp, "wb") as f:
-            f.write(head)
-        stats = np.zeros(STATS_WORDS, dtype=np.int64)
-        mode = DEFLATE_MODES["own" if deflate == backend else deflate]
-        if lib.clair_host_markdup_run(job, marker.backend(), tmp.encode(), mode, memory, int(max_blocks), threads, int(bool(remove)), stats.ctypes.data) != 0:
-            raise BamError(lib.clair_host_last_error().decode())
-        os.replace(tmp, marked_fn)
-    finally:
-        lib.clair_host_markdup_close(job)
-        if marker is not None:
-            marker.close()
-        if os.path.exists(tmp):
-            os.remove(tmp)
+    stats, head_bytes, backend = bam_stage.rewrite(
+        bam_fn, marked_fn, host=HostMarker, device_backend=DeviceMarker, header_of=bytes, run_args=(int(bool(remove)),), stats_words=STATS_WORDS,
+        device_needs="records", backend=backend, device=device, threads=threads, memory=memory, deflate=deflate, index=index, force=force,
+        max_blocks=max_blocks, segment_bytes=segment_bytes)
     result = dict(zip(STAT_NAMES, (int(v) for v in stats[:8])))
-    result.update(bytes_in=os.path.getsize(bam_fn), bytes_out=len(head) + int(stats[8]), backend=backend, path=marked_fn)
-    if index:
-        from clair_amd import index_bam
-        index_bam.build_index(marked_fn, backend=backend, device=device, threads=threads, force=force)
+    result.update(bytes_in=os.path.getsize(bam_fn), bytes_out=head_bytes + int(stats[8]), backend=backend, path=marked_fn)
     return result
 
 
@@ -205,14 +110,10 @@ def build_parser():
     add('--bam_fn', type=str, required=True, help="the BAM to read, in any order")
     add('--marked_fn', type=str, required=True, help="the BAM to write: the input's records in the input's order")
     add('--remove_duplicates', action='store_true', help="drop the records the rule flags instead of writing them with 0x400")
-    add('--backend', type=str, default="auto", choices=("auto", "device", "host"),
-        help="where records are framed, summarised, resolved and patched: the GPU, the host, or the GPU when one is present (convenience, not speed: docs/markdup_bam.md), default: %(default)s")
-    add('--device', type=int, default=0, help="GPU of --backend device, default: %(default)s")
-    add('--bam_threads', type=int, default=4, help="BGZF inflate and deflate threads on the host (1 .. 16), default: %(default)s")
-    add('--memory', type=str, default=None, help="most bytes of record summaries (32 a record), BYTES[K|M|G]; a larger file is refused, default: 8G")
-    add('--bgzf_deflate', type=str, default=None, choices=bgzf.BACKENDS, help="who compresses the output's blocks, default: the backend itself")
-    add('--index', action='store_true', help="write <marked_fn>.bai as index_bam does, with the same backend (the input must be sorted by coordinate)")
-    add('--force', action='store_true', help="overwrite an existing output")
+    bam_stage.add_backend_arguments(parser, "framed, summarised, resolved and patched", "BGZF inflate and deflate threads on the host",
+                                    speed="convenience, not speed: docs/markdup_bam.md",
+                                    memory_help="most bytes of record summaries (32 a record), BYTES[K|M|G]; a larger file is refused, default: 8G",
+                                    index_help="write <marked_fn>.bai as index_bam does, with the same backend (the input must be sorted by coordinate)")
     add('--json_fn', type=str, default=None, help="write the counts as JSON")
     return parser
 

@@ -387,18 +387,25 @@ int clair_host_bamidx_result_info(const clair_host_bamidx_result_t *r, int64_t *
 int clair_host_bamidx_result_copy(const clair_host_bamidx_result_t *r, clair_bamidx_run_t *runs, uint64_t *linear, int64_t *first_window);
 void clair_host_bamidx_result_free(clair_host_bamidx_result_t *r);
 
+/* -- the input of the tools that rewrite a BAM, as a job (hostsrc/host_bam_job.cpp, hostsrc/bam_job.h): what clair_host_bamsort_run and
+ *    clair_host_markdup_run read.
+ *    _open: the BAM header of `path` read and checked -> a job; _header: its bytes as they are in the file (magic, text, reference list;
+ *      *bytes is their length, copied when cap has room); _close.
+ *    Messages go to clair_host_last_error. */
+typedef struct clair_host_bam_job clair_host_bam_job_t;
+int clair_host_bam_job_open(const char *path, clair_host_bam_job_t **out);
+void clair_host_bam_job_close(clair_host_bam_job_t *job);
+int clair_host_bam_job_header(const clair_host_bam_job_t *job, uint8_t *out, int64_t cap, int64_t *bytes);
+
 /* -- sort_bam on the CPU (hostsrc/host_bam_sort.cpp; docs/sort_bam.md): the host twin of clair_bamsort_* (include/clair_amd.h) with the rules
  *    of csrc/bam_sort_core.h, and the file driver both backends run under.
  *    _create .. _backend, _debug_sort, _debug_gather: the twin, the same calls with the same arguments and results; blocks are inflated by
  *      zlib on `threads` threads, the group is ordered by std::stable_sort, `compressed` payloads are compressed by clair_host_deflate_bgzf.
- *    _open: the BAM header of `path` read and checked -> a job; _header: its bytes as they are in the file (magic, text, reference list;
- *      *bytes is their length, copied when cap has room); _close.
- *    _run: the records of the job's file sorted through a backend and appended to out_path (which holds the header's blocks already), the
- *      EOF marker behind them.  deflate: 0 the backend's own compressor, 1 zlib level 6, 2 clair_host_deflate_bgzf here.  memory: the most
+ *    _run: the records of a job's file (clair_host_bam_job_open) sorted through a backend and appended to out_path (which holds the
+ *      header's blocks already), the EOF marker behind them.  deflate: 0 the backend's own compressor, 1 zlib level 6, 2 clair_host_deflate_bgzf here.  memory: the most
  *      record bytes held at once.  stats [CLAIR_BAMSORT_STATS].
  *    Messages go to clair_host_last_error. */
 typedef struct clair_host_bamsort clair_host_bamsort_t;
-typedef struct clair_host_bamsort_job clair_host_bamsort_job_t;
 #ifndef CLAIR_BAMSORT_TYPES
 #define CLAIR_BAMSORT_TYPES
 /* the interface of a sort, as the file driver (clair_host_bamsort_run) calls it: the entry points of one backend with its handle */
@@ -433,24 +440,19 @@ int clair_host_bamsort_backend(clair_host_bamsort_t *h, clair_bamsort_backend_t 
 int clair_host_bamsort_debug_sort(const uint64_t *keys, int64_t n, uint32_t *perm);
 int clair_host_bamsort_debug_gather(const uint8_t *stream, int64_t stream_bytes, const int64_t *starts, const uint32_t *perm, int64_t n, uint8_t *out,
                                     int64_t out_bytes);
-int clair_host_bamsort_open(const char *path, clair_host_bamsort_job_t **out);
-void clair_host_bamsort_close(clair_host_bamsort_job_t *job);
-int clair_host_bamsort_header(const clair_host_bamsort_job_t *job, uint8_t *out, int64_t cap, int64_t *bytes);
-int clair_host_bamsort_run(clair_host_bamsort_job_t *job, const clair_bamsort_backend_t *backend, const char *out_path, int deflate, int64_t memory,
+int clair_host_bamsort_run(clair_host_bam_job_t *job, const clair_bamsort_backend_t *backend, const char *out_path, int deflate, int64_t memory,
                            int max_blocks, int threads, int64_t *stats);
 
 /* -- markdup_bam on the CPU (hostsrc/host_markdup.cpp; docs/markdup_bam.md): the host twin of clair_markdup_* (include/clair_amd.h) with the
  *    rule of csrc/markdup_core.h, and the file driver both backends run under.
  *    _create .. _backend, _debug_summary, _debug_resolve: the twin, the same calls with the same arguments and results; blocks are inflated
  *      by zlib on `threads` threads, the resolution orders by std::stable_sort, `compressed` payloads are compressed by clair_host_deflate_bgzf.
- *    _open: the BAM header of `path` read and checked -> a job; _header: its bytes as they are in the file; _close.
- *    _run: two reads of the job's file through a backend: every record summarised, the rule resolved, the records -- flagged, or with
- *      remove != 0 without the flagged ones -- appended to out_path (which holds the header's blocks already), the EOF marker behind them.
+ *    _run: two reads of a job's file (clair_host_bam_job_open) through a backend: every record summarised, the rule resolved, the
+ *      records -- flagged, or with remove != 0 without the flagged ones -- appended to out_path (which holds the header's blocks already), the EOF marker behind them.
  *      deflate: 0 the backend's own compressor, 1 zlib level 6, 2 clair_host_deflate_bgzf here.  memory: the most bytes the summaries may
  *      hold.  stats [CLAIR_MARKDUP_STATS].
  *    Messages go to clair_host_last_error. */
 typedef struct clair_host_markdup clair_host_markdup_t;
-typedef struct clair_host_markdup_job clair_host_markdup_job_t;
 #ifndef CLAIR_MARKDUP_TYPES
 #define CLAIR_MARKDUP_TYPES
 typedef struct clair_markdup_summary {
@@ -493,10 +495,7 @@ int clair_host_markdup_backend(clair_host_markdup_t *h, clair_markdup_backend_t 
 int clair_host_markdup_debug_summary(const uint8_t *stream, int64_t stream_bytes, const int64_t *starts, int64_t n, int n_ref,
                                      clair_markdup_summary_t *out);
 int clair_host_markdup_debug_resolve(const clair_markdup_summary_t *summaries, int64_t n, uint8_t *duplicate);
-int clair_host_markdup_open(const char *path, clair_host_markdup_job_t **out);
-void clair_host_markdup_close(clair_host_markdup_job_t *job);
-int clair_host_markdup_header(const clair_host_markdup_job_t *job, uint8_t *out, int64_t cap, int64_t *bytes);
-int clair_host_markdup_run(clair_host_markdup_job_t *job, const clair_markdup_backend_t *backend, const char *out_path, int deflate, int64_t memory,
+int clair_host_markdup_run(clair_host_bam_job_t *job, const clair_markdup_backend_t *backend, const char *out_path, int deflate, int64_t memory,
                            int max_blocks, int threads, int remove, int64_t *stats);
 
 /* -- gVCF on the CPU (hostsrc/host_gvcf.cpp; docs/gvcf.md): the host twin of clair_frontend_position_tallies / _gvcf_blocks

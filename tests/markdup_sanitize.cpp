@@ -33,21 +33,21 @@ int main(int argc, char **argv) {
     const int segment = atoi(argv[3]), max_blocks = atoi(argv[4]), remove_them = atoi(argv[6]);
     const int64_t memory = atoll(argv[5]);
     clair_host_markdup_t *twin = nullptr;
-    clair_host_markdup_job_t *job = nullptr;
+    clair_host_bam_job_t *job = nullptr;
     clair_markdup_backend_t backend;
     int64_t stats[CLAIR_MARKDUP_STATS] = {0};
     int status = 0;
     remove(argv[2]);
     if (clair_host_markdup_create(2, max_blocks, segment, &twin) != 0 || clair_host_markdup_backend(twin, &backend) != 0 ||
-        clair_host_markdup_open(argv[1], &job) != 0 || clair_host_markdup_run(job, &backend, argv[2], 0, memory, max_blocks, 2, remove_them, stats) != 0) {
+        clair_host_bam_job_open(argv[1], &job) != 0 || clair_host_markdup_run(job, &backend, argv[2], 0, memory, max_blocks, 2, remove_them, stats) != 0) {
         printf("%s\n", g_message.c_str());
         remove(argv[2]);
         status = 2;
     } else {
         int64_t header_bytes = 0;
-        clair_host_markdup_header(job, nullptr, 0, &header_bytes);
+        clair_host_bam_job_header(job, nullptr, 0, &header_bytes);
         std::vector<uint8_t> header((size_t)header_bytes);                       // exactly as long as its contents: a write past the end is seen
-        clair_host_markdup_header(job, header.data(), header_bytes, &header_bytes);
+        clair_host_bam_job_header(job, header.data(), header_bytes, &header_bytes);
         uint64_t h = 0xcbf29ce484222325ull;
         int64_t bytes = 0;
         FILE *f = fopen(argv[2], "rb");
@@ -57,7 +57,7 @@ int main(int argc, char **argv) {
         else printf("%lld %lld %lld %lld %lld %lld %lld %016llx\n", (long long)stats[0], (long long)stats[1], (long long)stats[2], (long long)stats[3], (long long)stats[4],
                     (long long)stats[5], (long long)stats[7], (unsigned long long)h);
     }
-    clair_host_markdup_close(job);
+    clair_host_bam_job_close(job);
     clair_host_markdup_destroy(twin);
     return status;
 }

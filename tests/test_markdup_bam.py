@@ -314,8 +314,8 @@ def test_symbols_are_declared_and_in_the_tables():
         assert "clair_markdup_" + name + "(" in amd_h and "clair_markdup_" + name in _capi.SIGNATURES
         assert "clair_host_markdup_" + name + "(" in host_h and "clair_host_markdup_" + name in _hostapi.SIGNATURES and hasattr(host, "clair_host_markdup_" + name)
     assert "clair_markdup_last_error" in _capi.SIGNATURES and "clair_markdup_debug_mark" in _capi.SIGNATURES
-    for name in ("open", "close", "header", "run"):
-        assert "clair_host_markdup_" + name in _hostapi.SIGNATURES and hasattr(host, "clair_host_markdup_" + name)
+    for name in ("clair_host_bam_job_open", "clair_host_bam_job_close", "clair_host_bam_job_header", "clair_host_markdup_run"):
+        assert name + "(" in host_h and name in _hostapi.SIGNATURES and hasattr(host, name)
     assert hasattr(_capi.load(), "clair_markdup_debug_resolve")
     core = open(os.path.join(ROOT, "clair_amd", "csrc", "markdup_core.h")).read()
     assert mb.SUMMARY.itemsize == 32 and "MIN_QUALITY = %d;" % mc.MIN_QUALITY in core
@@ -346,7 +346,7 @@ def test_host_side_under_address_and_undefined_sanitizers(case, bad_files, tmp_p
     program = str(tmp_path / "markdup_sanitize")
     hostsrc = os.path.join(ROOT, "clair_amd", "hostsrc")
     subprocess.check_call([cxx] + SANITIZE + ["-Wall", "-pthread", os.path.join(HERE, "markdup_sanitize.cpp"), os.path.join(hostsrc, "host_markdup.cpp"),
-                                               os.path.join(hostsrc, "host_deflate.cpp"), "-o", program, "-lz"])
+                                               os.path.join(hostsrc, "host_bam_job.cpp"), os.path.join(hostsrc, "host_deflate.cpp"), "-o", program, "-lz"])
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
     b, c = case["bam"], case["counts"]
     n = len(b.records)

@@ -295,8 +295,8 @@ def test_symbols_are_declared_and_in_the_tables():
         assert "clair_bamsort_" + name + "(" in amd_h and "clair_bamsort_" + name in _capi.SIGNATURES
         assert "clair_host_bamsort_" + name + "(" in host_h and "clair_host_bamsort_" + name in _hostapi.SIGNATURES and hasattr(host, "clair_host_bamsort_" + name)
     assert "clair_bamsort_last_error" in _capi.SIGNATURES
-    for name in ("open", "close", "header", "run"):
-        assert "clair_host_bamsort_" + name in _hostapi.SIGNATURES and hasattr(host, "clair_host_bamsort_" + name)
+    for name in ("clair_host_bam_job_open", "clair_host_bam_job_close", "clair_host_bam_job_header", "clair_host_bamsort_run"):
+        assert name + "(" in host_h and name in _hostapi.SIGNATURES and hasattr(host, name)
     core = open(os.path.join(ROOT, "clair_amd", "csrc", "bam_sort_core.h")).read()
     assert "RADIX_ITEMS = %d;" % sort_bam.RADIX_ITEMS in core and sort_bam.RADIX_TILE == 256 * sort_bam.RADIX_ITEMS
 
@@ -347,7 +347,7 @@ def test_host_side_under_address_and_undefined_sanitizers(case, bad_files, tmp_p
     program = str(tmp_path / "sort_bam_sanitize")
     hostsrc = os.path.join(ROOT, "clair_amd", "hostsrc")
     subprocess.check_call([cxx] + SANITIZE + ["-Wall", "-pthread", os.path.join(HERE, "sort_bam_sanitize.cpp"), os.path.join(hostsrc, "host_bam_sort.cpp"),
-                                               os.path.join(hostsrc, "host_deflate.cpp"), "-o", program, "-lz"])
+                                               os.path.join(hostsrc, "host_bam_job.cpp"), os.path.join(hostsrc, "host_deflate.cpp"), "-o", program, "-lz"])
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
     n = len(case["bam"].records)
     head = len(sort_bam.header_blocks(sort_bam.coordinate_header(case["bam"].header()), "host"))
